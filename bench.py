@@ -13,7 +13,11 @@ and results are complete inside the timed region.  With N > 1 every rank (one pr
 started by this script itself when it is run bare, or by torch.distributed.run) processes its own 32 clips per
 step (weak scaling) and the timed region ends with ONE RCCL all-gather of all per-clip class scores.
 
-Prints one JSON line (rank 0).
+Prints one JSON line (rank 0).  A plain run sets up, warms up, times the K steps and prints the headline (`value` clips/s,
+`ms_per_step`); everything below is measured only with `--full` (null otherwise):
+
+    python bench.py --gpus 1 --steps K --warmup W --full
+
   roofline      the dominant kernels (TV-L1 inner iterations), against the bound they obey: fp32 VECTOR arithmetic.
                 `achieved` = pixel-iterations x 55 FLOP (one S6 pixel-iteration counted from the specification, DESIGN.md
                 section 3: every fmaf = 2) / wall time the kernels run (HIP events around every run of their launches, union
@@ -30,6 +34,10 @@ Prints one JSON line (rank 0).
   roofline_cnn / roofline_cnn_bf16   the conv/FC stack alone (fp32 parity configuration / BASELINE config 5's bf16 per GPU):
                 TFLOP/s of a CNN-only leg timed after the main region, against the dense MFMA peak of the dtype.
   cpu_baseline  the CPU oracle (C TV-L1 with OpenMP across pairs + torch-CPU VGG) on a bounded sample.
+
+`--dump-outputs DIR` writes what the last timed step returned to its caller (rank 0: class scores and descriptors of both
+streams; with N > 1 also the gathered class scores of every rank's last step) as float32 DIR/<name>.npy.  The inputs
+and weights are seeded: the same arguments give the same inputs on every run and build.
 """
 import argparse
 import hashlib
@@ -290,10 +298,17 @@ def main():
                          "CNN has no idle CUs to hide in, and low-priority fragments disturb the two TV-L1 streams")
     ap.add_argument("--no-flow", action="store_true", help="CNN only on precomputed flow volumes (not the headline metric)")
     ap.add_argument("--main-only", action="store_true",
-                    help="skip the legs after the timed region (tvl1_hd, roofline_cnn*, cpu_baseline): the profiler passes of "
-                         "tools/profile_bench.sh use it so that their per-kernel sums hold the benchmark's own launches only")
+                    help="with --full: skip the legs after the timed region (tvl1_hd, roofline_cnn*, cpu_baseline): the profiler "
+                         "passes of tools/profile_bench.sh use it so that their per-kernel sums hold the benchmark's own launches only")
     ap.add_argument("--tvl1-params", default="", help="name=value,... overrides of va_tvl1_params (experiments)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: the live roofline of the timed steps (kernel events "
+                         "recorded inside them) and the legs after the timed region (tvl1_hd, roofline_cnn*, cpu_baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step as float32 DIR/<name>.npy (rank 0)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
     if args.cpu_clips is not None and args.cpu_clips == 0:
         args.cpu_pairs_per_core = 0
 
@@ -338,7 +353,7 @@ def main():
 
     def run_steps(n, keep):
         """n passes of the hot path; every pass is complete -- and its scores are in `scores` -- when this returns
-        control to the timed region's closing synchronisation."""
+        control to the timed region's closing synchronisation.  -> the last pass's outputs (None when n == 0)."""
         outs = []
         for _ in range(n):
             outs.append(pipe.submit(rgb, gray, flow_stack=stack))
@@ -349,29 +364,41 @@ def main():
             for i, out in enumerate(outs):
                 scores[i * BATCH:(i + 1) * BATCH, 0] = out["logits_s"]
                 scores[i * BATCH:(i + 1) * BATCH, 1] = out["logits_t"]
+        return outs[-1] if outs else None
 
     run_steps(Wm, False)
     torch.cuda.synchronize()
-    vflow.profile_enable(True, local_rank)
-    vflow.profile_read(reset=True, device=local_rank)
-    vflow.profile_levels(16, reset=True, device=local_rank)
+    if args.full:
+        vflow.profile_enable(True, local_rank)
+        vflow.profile_read(reset=True, device=local_rank)
+        vflow.profile_levels(16, reset=True, device=local_rank)
     vdist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    run_steps(K, True)
+    last = run_steps(K, True)
     allscores = vdist.gather_scores(scores, world * K * BATCH, world) if world > 1 else scores
     torch.cuda.synchronize()
     vdist.barrier()
     t1 = time.perf_counter()
     elapsed = vdist.max_over_ranks(t1 - t0, dev)
-    prof = vflow.profile_read(reset=False, device=local_rank)
-    levels = vflow.profile_levels(16, reset=True, device=local_rank)
-    vflow.profile_read(reset=True, device=local_rank)
-    vflow.profile_enable(False, local_rank)
+    if args.full:
+        prof = vflow.profile_read(reset=False, device=local_rank)
+        levels = vflow.profile_levels(16, reset=True, device=local_rank)
+        vflow.profile_read(reset=True, device=local_rank)
+        vflow.profile_enable(False, local_rank)
     assert allscores.shape[0] == world * K * BATCH
     ranks_seen = vdist.ranks_seen()
     finite = bool(torch.isfinite(allscores).all().item())
+    if args.dump_outputs and rank == 0:
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        dump = {k: last[k] for k in ("logits_s", "logits_t", "desc_s", "desc_t")}
+        if world > 1:  # every rank's last step, in rank order (rank r's clips are rows [r*K*BATCH, (r+1)*K*BATCH))
+            dump["logits_all_ranks"] = allscores.view(world, K, BATCH, 2, -1)[:, K - 1]
+        for name, t in dump.items():
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), t.detach().float().cpu().numpy())
 
+    legs = args.full and world == 1 and not args.main_only  # the measurements after the timed region
     if rank == 0:
         clips = world * K * BATCH
         value = clips / elapsed
@@ -382,7 +409,7 @@ def main():
                   "tvl1_params": args.tvl1_params, "tvl1_hip_blob": git_blob_hash(TVL1_SRC),
                   "parallelism": "clips sharded x%d" % world, "finite": finite}
         roof = None
-        if prof["launches"] > 0 and prof["ms"] > 0:
+        if args.full and prof["launches"] > 0 and prof["ms"] > 0:
             # wall time during which the inner-iteration kernels run: the union of the HIP-event intervals (with
             # --flow-streams > 1 launches of different streams overlap); everything below is per step of THIS run
             busy_ms = prof["union_ms"] if prof["union_ms"] > 0 else prof["ms"]
@@ -415,11 +442,11 @@ def main():
             for l in per_level:
                 roof["ns_per_kpx_iter_l%d" % l["level"]] = l["ns_per_kpx_iter"]
         hd = cnn = cnn_bf16 = None
-        if world == 1 and not args.main_only and roof is not None and stack is None:
+        if legs and roof is not None and stack is None:
             # the per-level figures above are taken INSIDE the two-stream step, where the spatial CNN runs beside the coarsest
             # level; the same batch's TV-L1 alone (no CNN on the GPU) separates the kernels' own cost from that sharing
             roof.update(tvl1_only_leg(pipe, gray, params, args.flow_streams, local_rank))
-        if world == 1 and not args.main_only:
+        if legs:
             hd = tvl1_hd_leg(args, dev)
             # CNN-only legs (outside the timed region): both VGG-16 streams on precomputed flow volumes
             # (a synthetic flow volume: the CNN's time does not depend on the values, and no TV-L1 work is added to the run)
@@ -437,7 +464,7 @@ def main():
             cnn_bf16["logit_range_f32"] = float((lg1 if args.cnn_dtype == "f32" else lg2).abs().max().item())
             cnn_bf16["argmax_agreement"] = float((lg1.argmax(-1) == lg2.argmax(-1)).float().mean().item())
         cpu = None
-        if world == 1 and args.cpu_pairs_per_core > 0 and not args.main_only:
+        if legs and args.cpu_pairs_per_core > 0:
             cpu = cpu_baseline(args.cpu_pairs_per_core, tv_kw)
         line = {
             "metric": "clips/sec (224x224, RGB+10-flow two-stream)",
@@ -447,7 +474,7 @@ def main():
             "config": config, "roofline": roof, "tvl1_hd": hd, "roofline_cnn": cnn, "roofline_cnn_bf16": cnn_bf16, "cpu_baseline": cpu,
         }
         print(json.dumps(line))
-    if not (rank == 0 and world == 1 and not args.main_only):
+    if not (rank == 0 and legs):
         pipe.close()
     if world > 1:
         import torch.distributed as td

@@ -7,6 +7,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -25,20 +26,56 @@ def _json_line(stdout):
     return json.loads(lines[0])
 
 
-def test_bench_started_bare_runs_two_ranks():
+def test_bench_started_bare_runs_two_ranks(tmp_path):
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0",
-                        "--cpu-clips", "0", "--main-only"], capture_output=True, text=True, timeout=900,
-                       env=_env(VA_DIST_BACKEND="gloo", VA_FORCE_DEVICE="0"))
+                        "--cpu-clips", "0", "--full", "--main-only", "--dump-outputs", str(tmp_path)],
+                       capture_output=True, text=True, timeout=900, env=_env(VA_DIST_BACKEND="gloo", VA_FORCE_DEVICE="0"))
     assert r.returncode == 0, r.stderr[-2000:]
     d = _json_line(r.stdout)
     assert d["n_gpus"] == 2 and d["ranks_seen"] == 2 and d["scaling"] == "weak"
     assert d["config"]["global_batch"] == 64 and d["config"]["finite"] is True
     assert d["value"] > 0 and d["cpu_baseline"] is None  # the CPU leg runs at N = 1 only
     assert d["roofline"]["launches"] > 0
+    # the gathered scores of the last step, rank 0's block first: rank 0's own outputs
+    g = np.load(str(tmp_path / "logits_all_ranks.npy"))
+    assert g.shape == (2, 32, 2, 101) and g.dtype == np.float32 and np.isfinite(g).all()
+    assert np.array_equal(g[0, :, 0], np.load(str(tmp_path / "logits_s.npy")))
+    assert np.array_equal(g[0, :, 1], np.load(str(tmp_path / "logits_t.npy")))
+    assert not np.array_equal(g[0], g[1])  # distinct clips per rank
+
+
+def test_bench_plain_run_reports_the_headline_and_dumps_the_last_step(tmp_path):
+    """A plain run (no --full): the headline fields only, --steps timed steps, and --dump-outputs holds what the last timed
+    step handed to its caller -- equal bit for bit to a direct run of the same seeded batch through the pipeline."""
+    import torch
+    from video_analytics_amd import _ffi, pipeline, synth
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "0",
+                        "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=900, env=_env())
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = _json_line(r.stdout)
+    assert d["metric"] == "clips/sec (224x224, RGB+10-flow two-stream)" and d["unit"] == "clips/s"
+    assert d["higher_is_better"] is True and d["dtype"] == "f32" and d["steps"] == 2 and d["warmup"] == 0
+    assert d["ms_per_step"] > 0 and abs(d["value"] - 32 * 1e3 / d["ms_per_step"]) < 1e-6 * d["value"]
+    assert d["config"]["finite"] is True
+    for k in ("roofline", "tvl1_hd", "roofline_cnn", "roofline_cnn_bf16", "cpu_baseline"):
+        assert d[k] is None, k  # measured with --full only
+    dumped = {k: np.load(str(tmp_path / (k + ".npy"))) for k in ("logits_s", "logits_t", "desc_s", "desc_t")}
+    assert sorted(os.listdir(str(tmp_path))) == sorted(k + ".npy" for k in dumped)
+    dev = torch.device("cuda", 0)
+    params = _ffi.default_tvl1_params(block_iters=0, fast_math=0, epsilon=0.0, iters=300, warps=5, nscales=5)
+    pipe = pipeline.TwoStreamPipeline(device=0, tvl1_params=params, flow_streams=2)
+    rgb, gray, _ = synth.synth_clips(32, seed=0, first_clip=0)
+    out = pipe.run_batch(rgb.to(dev), gray.to(dev))
+    torch.cuda.synchronize()
+    for k, a in dumped.items():
+        assert a.dtype == np.float32 and a.shape == tuple(out[k].shape), k
+        assert np.array_equal(a, out[k].cpu().numpy()), k
+    pipe.close()
 
 
 def test_bench_single_gpu_line_has_the_contract_fields():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "1", "--cpu-clips", "0"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "1", "--cpu-clips", "0",
+                        "--full"],
                        capture_output=True, text=True, timeout=900, env=_env())
     assert r.returncode == 0, r.stderr[-2000:]
     d = _json_line(r.stdout)

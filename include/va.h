@@ -220,6 +220,25 @@ int va_flow_to_stack(va_ctx* ctx, const void* flow, int n_pairs, int w, int h,
  */
 int va_selftest_exact_math(va_ctx* ctx, float lo, float hi, unsigned long long* mismatches, void* stream);
 
+/* ------------------------------------------------------------ testing entry points --- */
+
+/*
+ * One 3x3 convolution layer (stride 1, zero padding 1) through exactly the dispatch the model uses (fp32: the forward pass's
+ * and the training step's; bf16: the forward pass's), for layer-by-layer tests:
+ *   out = maxpool2x2?(mask?(relu?(conv(in, w) + bias)))
+ * in: NHWC [batch][hw][hw][cin_pad] of dtype; w_packed: [cout][9][cin_pad] of dtype (tap 3 ky + kx, channel innermost);
+ * bias: f32 [cout]; out: NHWC [batch][hw'][hw'][cout] of dtype, or f32 when out_f32 (hw' = hw / 2 when pool, else hw);
+ * mask: f32, same layout as out, or NULL (zero the output where mask <= 0: training dgrad); zeros: >= 256 zero bytes.
+ * kernel_opt: fp32: VA_OPT_F32_CONV_KERNEL (0, 1); bf16: VA_OPT_BF16_VARIANT (0, 1, 2, 5, 7).
+ * linear = 1: no ReLU (fp32 only).  out_f32: bf16 with pool only.  cin_pad: a multiple of 16 (fp32) / 64 (bf16);
+ * cout: a multiple of 64; pool: even hw; mask: fp32 without pool.  Other shapes: VA_ERR_INVALID.
+ * kernel_name: HOST buffer of name_len bytes or NULL; receives the kernel instantiation that was launched, with its
+ * template arguments (e.g. "k_conv3x3_dma_f32<1,true,3>").  Pointers 16-byte aligned.
+ */
+int va_conv3x3_layer(va_ctx* ctx, int dtype, int kernel_opt, int hw, int cin_pad, int cout, int pool, int linear,
+                     int out_f32, int batch, const void* in, const void* w_packed, const float* bias, const float* mask,
+                     const void* zeros, void* out, char* kernel_name, int name_len, void* stream);
+
 /*
  * Measurement hooks (bench.py): when enabled, va_tvl1_flow brackets every run of
  * inner-iteration launches with HIP events on `stream`.  va_tvl1_profile_read synchronises

@@ -79,13 +79,15 @@ def test_two_sgd_steps_match_autograd(c_in, B):
     m.close()
 
 
-@pytest.mark.parametrize("c_in,B", [(3, 2), (20, 3)])
-def test_conv_updates_under_the_products_own_decisions(c_in, B):
+@pytest.mark.parametrize("c_in,B,f32_conv", [pytest.param(3, 2, 1, id="3-2"), pytest.param(20, 3, 1, id="20-3"),
+                                             pytest.param(3, 2, 0, id="3-2-f32conv0")])
+def test_conv_updates_under_the_products_own_decisions(c_in, B, f32_conv):
     """One SGD step where the autograd oracle uses the ReLU masks and pooling arg-maxima of the HIP forward pass
     (read from the training workspace: all 13 conv outputs stay there; va_vgg16_train_plan gives the offsets).  With
     the decisions shared, nothing but fp32 summation order separates the two backward passes: every parameter update,
     conv layers 0..9 included, must agree to TOL_UPDATE_DECIDED (max AND rms), and the decisions themselves must
-    differ from the oracle's own in at most a few elements per million."""
+    differ from the oracle's own in at most a few elements per million.  f32_conv = 0: VA_OPT_F32_CONV_KERNEL = 0 (the
+    register-staged kernel in the forward pass and in every dgrad convolution)."""
     import ctypes
     from oracle import train_oracle, vgg_oracle
     from video_analytics_amd import _ffi, synth, vgg
@@ -98,6 +100,7 @@ def test_conv_updates_under_the_products_own_decisions(c_in, B):
     x = torch.from_numpy(u * 4.0 - 2.0)
     labels = torch.tensor([(7 * i + 1) % 101 for i in range(B)], dtype=torch.int64)
     m = vgg.Vgg16Stream(w["conv_w"], w["conv_b"], w["fc_w"], w["fc_b"], 101, 256)
+    m.set_option(_ffi.VA_OPT_F32_CONV_KERNEL, f32_conv)
     stats, _ = m.train_step(x.cuda(), labels.cuda(), lr, mu, 1000)
     torch.cuda.synchronize()
     off = (ctypes.c_ulonglong * 30)()

@@ -339,21 +339,24 @@ def test_bad_shapes_raise_value_error(weights3):
     m.close()
 
 
-@pytest.mark.parametrize("c_in,seed", [(3, 1), (20, 2)])
-def test_fp32_stream_against_an_independent_gpu_implementation(c_in, seed):
+@pytest.mark.parametrize("c_in,seed,f32_conv", [pytest.param(3, 1, 1, id="3-1"), pytest.param(20, 2, 1, id="20-2"),
+                                                pytest.param(3, 1, 0, id="3-1-f32conv0"),
+                                                pytest.param(20, 2, 0, id="20-2-f32conv0")])
+def test_fp32_stream_against_an_independent_gpu_implementation(c_in, seed, f32_conv):
     """A second, independent fp32 evaluation of the same network ON THE GPU -- torch's own ``conv2d`` / ``max_pool2d`` /
     ``linear`` (MIOpen / rocBLAS kernels: nothing of this library) -- as a witness beside the torch-CPU oracle: the HIP
     stream, the CPU oracle and the vendor kernels agree within the 1e-3 of the north star on every class score of a
     9-clip batch (checker only: SURVEY.md section 7 allows MIOpen as an optional cross-check in tests, never on the
-    measured path)."""
+    measured path).  f32_conv = 0: VA_OPT_F32_CONV_KERNEL = 0, the register-staged kernel on every layer."""
     import torch.nn.functional as F
     from oracle import vgg_oracle
-    from video_analytics_amd import synth, vgg
+    from video_analytics_amd import _ffi, synth, vgg
     w = synth.synth_vgg16_weights(c_in=c_in, seed=seed)
     if c_in != 3:
         w["conv_w"][0] = vgg_oracle.copy_first_layer(w["conv_w"][0], c_in)
     x = _inputs(9, c_in, seed=40 + c_in)
     m = vgg.Vgg16Stream(w["conv_w"], w["conv_b"], w["fc_w"], w["fc_b"], 101, 256)
+    m.set_option(_ffi.VA_OPT_F32_CONV_KERNEL, f32_conv)
     feat, desc, logits = m.forward(x.cuda(), want_feat=True)
     with torch.no_grad():
         op, i = x.cuda(), 0
@@ -373,4 +376,43 @@ def test_fp32_stream_against_an_independent_gpu_implementation(c_in, seed):
     assert float((feat - feat_g).abs().max()) < TOL * max(1.0, float(feat_g.abs().max()))
     assert float((logits_g.cpu() - log_r).abs().max()) < TOL  # (and the two witnesses agree with each other)
     assert float(log_r.abs().max()) > 1.0
+    m.close()
+
+
+@pytest.mark.parametrize("n_classes,desc_dim", [(1, 16), (129, 16), (4096, 16), (1, 4096), (129, 4096), (4096, 4096)])
+def test_classifier_at_other_shapes_against_float64(n_classes, desc_dim):
+    """``va_vgg16_classify`` on random features at batches 1, 31, 33, 65 (the 32-row M tiles of k_fc_splitk and their ragged
+    ends) and at class / descriptor counts that leave a ragged 128-column N tile (1, 129) or fill it (16 -> one tile,
+    4096), against the float64 linear chain.  Error bound: the fp32 rule of tests/test_conv_layers_gpu.py,
+    |got - ref| < C_F32 2^-24 S: for the descriptor with the magnitude sums of the chain S_k = |W_k| S_(k-1) + |b_k|,
+    S_0 = |feat| (an error of an earlier layer reaches the later ones through |W_k|; ReLU does not enlarge it); for the
+    class scores layer by layer, against the last Linear applied in float64 to the descriptor the kernels returned
+    (measured: r <= 2e-4 on the descriptor, <= 1e-5 on the scores)."""
+    from test_conv_layers_gpu import C_F32, U
+    from video_analytics_amd import synth, vgg
+    w = synth.synth_vgg16_weights(c_in=3, n_classes=n_classes, desc_dim=desc_dim, seed=9, device="cuda")
+    m = vgg.Vgg16Stream(w["conv_w"], w["conv_b"], w["fc_w"], w["fc_b"], n_classes, desc_dim)
+    g = torch.Generator(device="cuda").manual_seed(n_classes + desc_dim)
+    W = [t.double() for t in w["fc_w"]]
+    Bs = [t.double() for t in w["fc_b"]]
+    for B in (1, 31, 33, 65):
+        feat = torch.randn(B, 512, 7, 7, device="cuda", generator=g)
+        desc, logits = m.classify(feat)
+        h, s = feat.double().reshape(B, -1), feat.double().abs().reshape(B, -1)  # CHW-major flatten order
+        for k in range(4):
+            h = torch.nn.functional.linear(h, W[k], Bs[k])
+            s = torch.nn.functional.linear(s, W[k].abs(), Bs[k].abs())
+            if k < 3:
+                h = h.clamp_min(0.0)
+            if k == 2:
+                desc_r, s_desc = h, s
+        d = desc.double()
+        log_r = torch.nn.functional.linear(d, W[3], Bs[3])
+        s_log = torch.nn.functional.linear(d.abs(), W[3].abs(), Bs[3].abs())
+        for got, ref, sk, what in ((desc, desc_r, s_desc, "desc"), (logits, h, s, "logits (chain)"),
+                                   (logits, log_r, s_log, "logits")):
+            r = float(((got.double() - ref).abs() / (U * sk)).max())
+            print("classifier %d classes, desc %d, batch %d: %s normalised error %.3g" % (n_classes, desc_dim, B, what, r))
+            assert r < C_F32, (what, B, r)
+        assert float(h.abs().max()) > 0.0
     m.close()

@@ -23,6 +23,7 @@ EXPORTS = [
     "va_meter_update", "va_meter_average", "va_linear_svm_predict",
     "va_vgg16_train_init", "va_vgg16_train_workspace_bytes", "va_vgg16_train_step",
     "va_vgg16_export_state", "va_vgg16_import_state", "va_vgg16_train_plan",
+    "va_conv3x3_layer",
 ]
 
 
@@ -148,6 +149,8 @@ def lib():
     L.va_vgg16_export_state.restype = ci
     L.va_vgg16_import_state.argtypes = [vp, ci, pp, pp, pp, pp, vp]
     L.va_vgg16_import_state.restype = ci
+    L.va_conv3x3_layer.argtypes = [vp, ci, ci, ci, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, ctypes.c_char_p, ci, vp]
+    L.va_conv3x3_layer.restype = ci
     _lib = L
     return L
 

@@ -1666,10 +1666,13 @@ __device__ __forceinline__ void conv3x3_img14_body(const Img14Args& a)
         // weight fragment first: register 4 g4 + j of lane (r31, hh) is channel 8 g4 + 4 hh + j of the column block, row r31
         // of the row block: four consecutive channels of one pixel = one 8-/16-byte LDS write into a wave-private 32-row x 64-channel
         // tile, read back as whole pixel lines, 16 bytes per lane (direct 8-byte stores cost 4.6 us per layer).
-        // The tile lives in brick buffer 0, whose last reader (step T - 4) every wave has left behind at barrier T - 1;
+        // The tile lives in the brick buffer the last chunk did NOT use (buffer nchunks & 1: the last chunk, nchunks - 1, sat in
+        // buffer (nchunks - 1) & 1).  Its last reader is step T - 4 (chunk nchunks - 2), which every wave has left behind at
+        // barrier T - 1, or nobody (one chunk); the last chunk's buffer may still be read by a slower wave's final fragments,
+        // and no barrier separates the loop from this epilogue.  (Even chunk counts -- every VGG-16 layer -- use buffer 0.)
         // 16-byte chunk c of row r sits at slot c ^ (r & (chunks per row - 1)).
         constexpr int NCHK = 64 / EPC;  // 16-byte chunks per 64-channel row: 8 (bf16) / 16 (fp32)
-        T* const stage = sBrick + wave * 32 * 64;  // 4 / 8 KB per wave
+        T* const stage = sBrick + (nchunks & 1) * BRICK + wave * 32 * 64;  // 4 / 8 KB per wave
         T* const out = (T*)a.out + (size_t)b * 196 * a.Cout + n0;
 #pragma unroll
         for (int i = 0; i < MT; ++i) {
@@ -2099,8 +2102,16 @@ void pick_brick(int W, int H, int B, int& lgTW, int& lgTH, int& TB, int lgpx = 7
         }
 }
 
+// `launched` (tests: va_conv3x3_layer): receives the name of the kernel instantiation that was launched; NULL on the model's paths
+#define VA_LAUNCHED(name_)                 \
+    do {                                   \
+        if (launched) *launched = (name_); \
+    } while (0)
+static_assert(VA_RING == 3, "the launched-kernel names below spell the ring depth");
+
 int launch_conv_ex(int hw, int cin_pad, int cout, const float* wp, const float* bias, const float* in, float* out,
-                   const float* mask, int linear, bool pool, int B, const float* zeros, int f32_conv, hipStream_t st)
+                   const float* mask, int linear, bool pool, int B, const float* zeros, int f32_conv, hipStream_t st,
+                   const char** launched = nullptr)
 {
     ConvArgs a{};
     a.in = in;
@@ -2125,6 +2136,7 @@ int launch_conv_ex(int hw, int cin_pad, int cout, const float* wp, const float* 
         const unsigned gridi = (unsigned)(B * (cout / 64));
         if (pool) k_conv3x3_img14<float, true><<<gridi, 512, 0, st>>>(ia);
         else k_conv3x3_img14<float, false><<<gridi, 512, 0, st>>>(ia);
+        VA_LAUNCHED(pool ? "k_conv3x3_img14<float,true>" : "k_conv3x3_img14<float,false>");
         VA_LAUNCH_CHECK();
         return VA_OK;
     }
@@ -2135,12 +2147,13 @@ int launch_conv_ex(int hw, int cin_pad, int cout, const float* wp, const float* 
         const bool wide = !ring && cout % 128 == 0;
         a.tiles_n = cout / (wide ? 128 : 64);
         const unsigned grid = (unsigned)(a.tiles_n * a.tiles_x * a.tiles_y * tiles_b);
-#define VA_LAUNCH_F32(NT_, NB_)                                                      \
-    {                                                                                \
-        if (pool) k_conv3x3_dma_f32<NT_, true, NB_><<<grid, 256, 0, st>>>(a);        \
-        else k_conv3x3_dma_f32<NT_, false, NB_><<<grid, 256, 0, st>>>(a);            \
+#define VA_LAUNCH_F32(NT_, NB_)                                                                                      \
+    {                                                                                                                \
+        if (pool) k_conv3x3_dma_f32<NT_, true, NB_><<<grid, 256, 0, st>>>(a);                                        \
+        else k_conv3x3_dma_f32<NT_, false, NB_><<<grid, 256, 0, st>>>(a);                                            \
+        VA_LAUNCHED(pool ? "k_conv3x3_dma_f32<" #NT_ ",true," #NB_ ">" : "k_conv3x3_dma_f32<" #NT_ ",false," #NB_ ">"); \
     }
-        if (ring) VA_LAUNCH_F32(1, VA_RING)
+        if (ring) VA_LAUNCH_F32(1, 3)  // (VA_RING)
         else if (wide) VA_LAUNCH_F32(2, 1)
         else VA_LAUNCH_F32(1, 1)
 #undef VA_LAUNCH_F32
@@ -2156,11 +2169,13 @@ int launch_conv_ex(int hw, int cin_pad, int cout, const float* wp, const float* 
         const unsigned grid = (unsigned)(a.tiles_n * a.tiles_x * a.tiles_y * tiles_b);
         if (pool) k_conv3x3_mfma<2, 2, 2, 2, true, 16><<<grid, 256, 0, st>>>(a);
         else k_conv3x3_mfma<2, 2, 2, 2, false, 16><<<grid, 256, 0, st>>>(a);
+        VA_LAUNCHED(pool ? "k_conv3x3_mfma<2,2,2,2,true,16>" : "k_conv3x3_mfma<2,2,2,2,false,16>");
     } else {
         a.tiles_n = cout / 64;
         const unsigned grid = (unsigned)(a.tiles_n * a.tiles_x * a.tiles_y * tiles_b);
         if (pool) k_conv3x3_mfma<2, 2, 2, 1, true, 16><<<grid, 256, 0, st>>>(a);
         else k_conv3x3_mfma<2, 2, 2, 1, false, 16><<<grid, 256, 0, st>>>(a);
+        VA_LAUNCHED(pool ? "k_conv3x3_mfma<2,2,2,1,true,16>" : "k_conv3x3_mfma<2,2,2,1,false,16>");
     }
     VA_LAUNCH_CHECK();
     return VA_OK;
@@ -2172,7 +2187,7 @@ int launch_conv(const ConvLayer& L, const float* zeros, const float* in, float* 
 }
 
 int launch_conv_bf16(const ConvLayer& L, const __bf16* zeros, int variant, const __bf16* in, void* out, bool out_f32, int B, int n_cu,
-                     hipStream_t st)
+                     hipStream_t st, const char** launched = nullptr)
 {
     ConvArgsBf a{};
     a.in = in;
@@ -2220,9 +2235,11 @@ int launch_conv_bf16(const ConvLayer& L, const __bf16* zeros, int variant, const
         if (nt4) {
             if (L.pool) k_conv3x3_pp_bf16<4, true><<<gridp, 512, 0, st>>>(a);
             else k_conv3x3_pp_bf16<4, false><<<gridp, 512, 0, st>>>(a);
+            VA_LAUNCHED(L.pool ? "k_conv3x3_pp_bf16<4,true>" : "k_conv3x3_pp_bf16<4,false>");
         } else {
             if (L.pool) k_conv3x3_pp_bf16<2, true><<<gridp, 512, 0, st>>>(a);
             else k_conv3x3_pp_bf16<2, false><<<gridp, 512, 0, st>>>(a);
+            VA_LAUNCHED(L.pool ? "k_conv3x3_pp_bf16<2,true>" : "k_conv3x3_pp_bf16<2,false>");
         }
         VA_LAUNCH_CHECK();
         return VA_OK;
@@ -2235,6 +2252,7 @@ int launch_conv_bf16(const ConvLayer& L, const __bf16* zeros, int variant, const
         const Img14Args ia{a.in, a.wp, a.bias, a.out, B, a.Cin, a.Cout};
         if (out_f32) k_conv3x3_img14<__bf16, true><<<gridi, 512, 0, st>>>(ia);
         else k_conv3x3_img14<__bf16, false><<<gridi, 512, 0, st>>>(ia);
+        VA_LAUNCHED(out_f32 ? "k_conv3x3_img14<__bf16,true>" : "k_conv3x3_img14<__bf16,false>");
         VA_LAUNCH_CHECK();
         return VA_OK;
     }
@@ -2253,6 +2271,7 @@ int launch_conv_bf16(const ConvLayer& L, const __bf16* zeros, int variant, const
         const unsigned gridw = (unsigned)((n_cu / nh) * nh);  // one workgroup per CU (158 KB of LDS), whole channel-half groups
         if (L.pool) k_conv3x3_ws_bf16<true><<<gridw, 256, 0, st>>>(w);
         else k_conv3x3_ws_bf16<false><<<gridw, 256, 0, st>>>(w);
+        VA_LAUNCHED(L.pool ? "k_conv3x3_ws_bf16<true>" : "k_conv3x3_ws_bf16<false>");
         VA_LAUNCH_CHECK();
         return VA_OK;
     }
@@ -2272,6 +2291,8 @@ int launch_conv_bf16(const ConvLayer& L, const __bf16* zeros, int variant, const
     {                                                                                        \
         if (L.pool) k_conv3x3_bpp_bf16<LG_, LG_, NT_, true><<<gridb, 512, 0, st>>>(a);       \
         else k_conv3x3_bpp_bf16<LG_, LG_, NT_, false><<<gridb, 512, 0, st>>>(a);             \
+        VA_LAUNCHED(L.pool ? "k_conv3x3_bpp_bf16<" #LG_ "," #LG_ "," #NT_ ",true>"            \
+                           : "k_conv3x3_bpp_bf16<" #LG_ "," #LG_ "," #NT_ ",false>");         \
     }
         if (lg == 4 && nt4) VA_LAUNCH_BPP(4, 4)
         else if (lg == 4) VA_LAUNCH_BPP(4, 2)
@@ -2291,19 +2312,23 @@ int launch_conv_bf16(const ConvLayer& L, const __bf16* zeros, int variant, const
     const bool wide = autosel && !ring && L.cout % 128 == 0;
     a.tiles_n = L.cout / (wide ? 128 : 64);
     const unsigned grid = (unsigned)(a.tiles_n * a.tiles_x * a.tiles_y * tiles_b);
-#define VA_LAUNCH_BF(NT_, NB_)                                                                   \
-    {                                                                                            \
-        if (out_f32) k_conv3x3_mfma_bf16<NT_, true, true, NB_><<<grid, 256, 0, st>>>(a);         \
-        else if (L.pool) k_conv3x3_mfma_bf16<NT_, true, false, NB_><<<grid, 256, 0, st>>>(a);    \
-        else k_conv3x3_mfma_bf16<NT_, false, false, NB_><<<grid, 256, 0, st>>>(a);               \
+#define VA_LAUNCH_BF(NT_, NB_)                                                                                  \
+    {                                                                                                           \
+        if (out_f32) k_conv3x3_mfma_bf16<NT_, true, true, NB_><<<grid, 256, 0, st>>>(a);                        \
+        else if (L.pool) k_conv3x3_mfma_bf16<NT_, true, false, NB_><<<grid, 256, 0, st>>>(a);                   \
+        else k_conv3x3_mfma_bf16<NT_, false, false, NB_><<<grid, 256, 0, st>>>(a);                              \
+        VA_LAUNCHED(out_f32  ? "k_conv3x3_mfma_bf16<" #NT_ ",true,true," #NB_ ">"                                \
+                    : L.pool ? "k_conv3x3_mfma_bf16<" #NT_ ",true,false," #NB_ ">"                               \
+                             : "k_conv3x3_mfma_bf16<" #NT_ ",false,false," #NB_ ">");                            \
     }
-    if (ring) VA_LAUNCH_BF(1, VA_RING)
+    if (ring) VA_LAUNCH_BF(1, 3)  // (VA_RING)
     else if (wide) VA_LAUNCH_BF(2, 1)
     else VA_LAUNCH_BF(1, 1)
 #undef VA_LAUNCH_BF
     VA_LAUNCH_CHECK();
     return VA_OK;
 }
+#undef VA_LAUNCHED
 
 struct FcPlan {
     int S, kchunk, Npad, Mtiles;
@@ -2387,6 +2412,62 @@ int va_fc_f32(const float* A, const float* Wt, const float* bias, float* out, fl
 }
 
 size_t va_fc_slab_floats(int M, int N, int K) { return plan_fc(M, N, K).slab_floats; }
+
+extern "C" int va_conv3x3_layer(va_ctx* ctx, int dtype, int kernel_opt, int hw, int cin_pad, int cout, int pool, int linear,
+                                int out_f32, int batch, const void* in, const void* w_packed, const float* bias, const float* mask,
+                                const void* zeros, void* out, char* kernel_name, int name_len, void* stream)
+{
+    VA_CHECK_ARG(ctx != nullptr, "va_conv3x3_layer: ctx is NULL");
+    VA_USE_DEVICE(ctx);
+    if (kernel_name && name_len > 0) kernel_name[0] = 0;
+    VA_CHECK_ARG(in && w_packed && bias && zeros && out, "va_conv3x3_layer: NULL in/w_packed/bias/zeros/out");
+    VA_CHECK_ARG((((uintptr_t)in | (uintptr_t)w_packed | (uintptr_t)bias | (uintptr_t)zeros | (uintptr_t)out | (uintptr_t)mask) & 15) == 0,
+                 "va_conv3x3_layer: every pointer must be 16-byte aligned (16-byte vector accesses)");
+    VA_CHECK_ARG(dtype == VA_DTYPE_F32 || dtype == VA_DTYPE_BF16, "va_conv3x3_layer: dtype must be VA_DTYPE_F32 or VA_DTYPE_BF16");
+    const bool bf = dtype == VA_DTYPE_BF16;
+    if (bf)
+        VA_CHECK_ARG((kernel_opt >= 0 && kernel_opt <= 2) || kernel_opt == 5 || kernel_opt == 7 || (kernel_opt == 6 && kVaExperiments),
+                     "va_conv3x3_layer: bf16 kernel_opt (VA_OPT_BF16_VARIANT) must be 0, 1, 2, 5 or 7 (6: -DVA_EXPERIMENTS builds)");
+    else
+        VA_CHECK_ARG(kernel_opt == 0 || kernel_opt == 1, "va_conv3x3_layer: fp32 kernel_opt (VA_OPT_F32_CONV_KERNEL) must be 0 or 1");
+    VA_CHECK_ARG(batch >= 1, "va_conv3x3_layer: batch %d < 1", batch);
+    VA_CHECK_ARG(hw >= 1, "va_conv3x3_layer: hw %d < 1", hw);
+    // K steps: 16 fp32 channels (k_conv3x3_mfma), 64 bf16 channels (k_conv3x3_mfma_bf16); N tiles of 64 channels everywhere
+    VA_CHECK_ARG(bf ? cin_pad >= 64 && cin_pad % 64 == 0 : cin_pad >= 16 && cin_pad % 16 == 0,
+                 "va_conv3x3_layer: cin_pad %d must be a positive multiple of %d", cin_pad, bf ? 64 : 16);
+    VA_CHECK_ARG(cout >= 64 && cout % 64 == 0, "va_conv3x3_layer: cout %d must be a positive multiple of 64", cout);
+    VA_CHECK_ARG(pool == 0 || pool == 1, "va_conv3x3_layer: pool must be 0 or 1");
+    // the pooling epilogues write the window whose origin (even x, y) lies in the image: with an odd hw the last one would
+    // pool a pixel outside the image into a column / row the (hw / 2)-wide output does not have
+    VA_CHECK_ARG(!pool || hw % 2 == 0, "va_conv3x3_layer: pooling needs an even hw (got %d)", hw);
+    // the bf16 kernels always apply ReLU and have no mask; their only fp32-output forms pool
+    VA_CHECK_ARG(!out_f32 || (bf && pool), "va_conv3x3_layer: out_f32 needs dtype bf16 and pool");
+    VA_CHECK_ARG(!linear || !bf, "va_conv3x3_layer: linear (no ReLU) is an fp32-only form (training dgrad)");
+    VA_CHECK_ARG(mask == nullptr || (!bf && !pool), "va_conv3x3_layer: mask needs dtype fp32 and no pool");
+    // launch grids and the buffer resources' sizes are 32-bit quantities
+    VA_CHECK_ARG((long)batch * hw * hw * cin_pad < 2147483647L && (long)batch * hw * hw * cout < 2147483647L,
+                 "va_conv3x3_layer: %d x %d x %d x %d/%d activations exceed 2^31 elements", batch, hw, hw, cin_pad, cout);
+    VA_CHECK_ARG((long)cout * 9 * cin_pad * (bf ? 2 : 4) < 2147483647L, "va_conv3x3_layer: packed weights exceed 2 GiB");
+    hipStream_t st = (hipStream_t)stream;
+    const char* name = nullptr;
+    int rc;
+    if (bf) {
+        ConvLayer L{};
+        L.cin = L.cin_pad = cin_pad;
+        L.cout = cout;
+        L.hw = hw;
+        L.pool = pool != 0;
+        L.xcol = false;
+        L.wp_bf = (__bf16*)w_packed;
+        L.bias = (float*)bias;
+        rc = launch_conv_bf16(L, (const __bf16*)zeros, kernel_opt, (const __bf16*)in, out, out_f32 != 0, batch, ctx->n_cu, st, &name);
+    } else {
+        rc = launch_conv_ex(hw, cin_pad, cout, (const float*)w_packed, bias, (const float*)in, (float*)out, mask, linear, pool != 0,
+                            batch, (const float*)zeros, kernel_opt, st, &name);
+    }
+    if (rc == VA_OK && kernel_name && name_len > 0) snprintf(kernel_name, (size_t)name_len, "%s", name ? name : "");
+    return rc;
+}
 
 int va_input_to_nhwc_f32(const va_vgg16* m, const void* x, int x_is_u8, int B, float* out, hipStream_t st)
 {

@@ -359,6 +359,38 @@ class _ClassifierStage(object):
         return head[1]
 
 
+def conv3x3_layer(x, w_packed, bias, out, kernel_opt=1, pool=False, linear=False, mask=None, zeros=None):
+    """One conv layer through the model's own kernel dispatch (``va_conv3x3_layer``, a testing entry point); returns the
+    name of the kernel instantiation that ran.  Layouts are the kernels' own: x NHWC [B][hw][hw][cin_pad] (float32 or
+    bfloat16), w_packed [cout][9][cin_pad] of x's dtype, bias float32 [cout], out NHWC [B][hw'][hw'][cout] of x's dtype or
+    float32 (bf16 with pool: the fp32-output form), hw' = hw // 2 when pooling; mask float32 shaped like out or None;
+    zeros: >= 256 zero bytes on the device (None: allocated here).  kernel_opt is VA_OPT_F32_CONV_KERNEL (fp32) or
+    VA_OPT_BF16_VARIANT (bf16).  Enqueued on the current stream; nothing is synchronised."""
+    if x.dtype not in (torch.float32, torch.bfloat16) or x.dim() != 4 or x.shape[1] != x.shape[2]:
+        raise ValueError("conv3x3_layer: x must be float32 / bfloat16 NHWC [B][hw][hw][cin_pad]")
+    B, hw, _, cin_pad = x.shape
+    cout = w_packed.shape[0]
+    bf = x.dtype == torch.bfloat16
+    out_f32 = bf and out.dtype == torch.float32
+    hwo = hw // 2 if pool else hw
+    tensors = [x, w_packed, bias, out] + ([mask] if mask is not None else [])
+    if (w_packed.dtype != x.dtype or tuple(w_packed.shape) != (cout, 9, cin_pad) or bias.dtype != torch.float32
+            or tuple(bias.shape) != (cout,) or out.dtype not in (x.dtype, torch.float32)
+            or tuple(out.shape) != (B, hwo, hwo, cout) or (mask is not None and (mask.dtype != torch.float32
+                                                                                 or mask.shape != out.shape))):
+        raise ValueError("conv3x3_layer: w_packed / bias / out / mask do not match x")
+    if any(not t.is_cuda or t.device != x.device or not t.is_contiguous() for t in tensors):
+        raise ValueError("conv3x3_layer: every tensor must be a contiguous tensor on x's device")
+    if zeros is None:
+        zeros = torch.zeros(256, dtype=torch.uint8, device=x.device)
+    name = ctypes.create_string_buffer(128)
+    _ffi.check(_ffi.lib().va_conv3x3_layer(
+        _ffi.ctx(x.device.index), 1 if bf else 0, int(kernel_opt), hw, cin_pad, cout, int(bool(pool)), int(bool(linear)),
+        int(out_f32), B, _ffi.ptr(x), _ffi.ptr(w_packed), _ffi.ptr(bias), _ffi.ptr(mask), _ffi.ptr(zeros), _ffi.ptr(out),
+        name, len(name), _ffi.stream_ptr(x.device)))
+    return name.value.decode()
+
+
 def _ffi_conv_cout(i):
     return (64, 64, 128, 128, 256, 256, 256, 512, 512, 512, 512, 512, 512)[i]
 

@@ -18,6 +18,11 @@
  *   va_flow_to_stack  the 8-bit flow image + getTransforms' ToTensor/Normalize + the x/y
  *                     interleave of TemporalDataset.__getitem__: Sheet03/temporalModel.py:83-90,
  *                     Sheet03/utils.py:148-150.
+ *   va_flow_to_stack_crop   va_flow_to_stack for full-size flow (UCF-101's 320x240) with getTransforms'
+ *                     RandomCrop(224) / RandomHorizontalFlip() applied to each of the 2L flow images:
+ *                     Sheet03/temporalModel.py:76-90, Sheet03/utils.py:143,145.
+ *   va_crop_images_u8 the same crop and flip of the RGB frame SpatialDataset loads:
+ *                     Sheet03/spatialModel.py:64-81, Sheet03/utils.py:143,145.
  *   va_validate_batch the loss / argmax / correct-count lines of validate():
  *                     Sheet03/spatialModel.py:219-221.
  *   va_meter_*        the per-video AverageMeter collation of validate():
@@ -62,7 +67,7 @@ extern "C" {
 typedef struct va_ctx va_ctx;
 typedef struct va_vgg16 va_vgg16;
 
-/* version number (currently 3) + VA_VERSION_EXPERIMENTS when the library was built with -DVA_EXPERIMENTS, i.e. when it
+/* version number (currently 4) + VA_VERSION_EXPERIMENTS when the library was built with -DVA_EXPERIMENTS, i.e. when it
  * also holds the measured-slower kernel families behind va_tvl1_params.tuning / VA_OPT_BF16_VARIANT 6 */
 #define VA_VERSION_EXPERIMENTS 0x10000
 int va_version(void);
@@ -212,6 +217,28 @@ int va_tvl1_flow(va_ctx* ctx, const void* frames, int frames_are_u8, int n_seq, 
  */
 int va_flow_to_stack(va_ctx* ctx, const void* flow, int n_pairs, int w, int h,
                      float bound, float mean, float stdv, void* stack, void* stream);
+
+/*
+ * va_flow_to_stack with a crop and flip per output channel (DESIGN.md S10 then S9; Sheet03/temporalModel.py:76-90, the
+ * transform applied to each flow image independently at :86; Sheet03/utils.py:143,145,148-150).
+ * flow f32 [n_pairs][2][h][w] -> stack f32 [2*n_pairs][out_h][out_w].
+ * crops: DEVICE int32 [2*n_pairs][3] = {top, left, flip}, one per output channel (channel 2k = x flow of pair k).
+ * Output pixel (y, x) of channel ch reads source (top + y, left + (flip ? out_w-1-x : x)) of its plane, then quantises and
+ * normalises it exactly as va_flow_to_stack does.  A flip mirrors the quantised image and does not negate the x flow.
+ * top and left are clamped to [0, h-out_h] x [0, w-out_w] on the device; callers validate them on the host.
+ */
+int va_flow_to_stack_crop(va_ctx* ctx, const void* flow, int n_pairs, int w, int h, float bound, float mean, float stdv,
+                          const void* crops, int out_w, int out_h, void* stack, void* stream);
+
+/*
+ * The crop and flip of getTransforms() on u8 frames (Sheet03/spatialModel.py:64-81, Sheet03/utils.py:143,145):
+ * src u8 [n][c][h][w] (src_nhwc = 0) or [n][h][w][c] (src_nhwc = 1, the decode order of PIL and JPEG);
+ * crops: DEVICE int32 [n][3] = {top, left, flip}, one per image, shared by its channels (clamped like
+ * va_flow_to_stack_crop's); dst u8 [n][c][out_h][out_w] NCHW: the u8 input of va_vgg16_forward, which applies
+ * ToTensor + Normalize (Sheet03/utils.py:148-150).
+ */
+int va_crop_images_u8(va_ctx* ctx, const void* src, int n, int c, int w, int h, int src_nhwc,
+                      const void* crops, int out_w, int out_h, void* dst, void* stream);
 
 /*
  * Self-test of the arithmetic contract: compares the kernel's packed correctly-rounded sqrt and

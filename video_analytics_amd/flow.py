@@ -148,6 +148,30 @@ def flow_to_stack(flow, bound=FLOW_BOUND, mean=NORM_MEANS_TF[0], std=NORM_STDS_T
     return out
 
 
+def crop_flow_to_stack(flow, crops, size=224, bound=FLOW_BOUND, mean=NORM_MEANS_TF[0], std=NORM_STDS_TF[0], out=None):
+    """``flow_to_stack`` of full-size flow with one crop and flip per output channel (then S9): flow
+    ``[N,2,H,W]`` float32 (H, W >= ``size``), crops CPU int32 ``[2N,3]`` rows ``{top, left, flip}`` (row 2k: the x flow of
+    pair k; ``augment.draw_flow_crops``) -> ``[2N,size,size]`` float32.  Only the crop windows are read."""
+    from . import augment
+    if not isinstance(flow, torch.Tensor) or not flow.is_cuda or flow.dtype != torch.float32:
+        raise ValueError("crop_flow_to_stack: flow must be a CUDA float32 tensor")
+    if flow.dim() != 4 or flow.shape[1] != 2:
+        raise ValueError("crop_flow_to_stack: flow must be [N,2,H,W]")
+    N, _, H, W = flow.shape
+    augment.check_crops(crops, 2 * N, H, W, size, "crop_flow_to_stack")
+    flow = flow.contiguous()
+    if out is None:
+        out = torch.empty((2 * N, size, size), dtype=torch.float32, device=flow.device)
+    elif out.numel() != 2 * N * size * size or out.dtype != torch.float32 or not out.is_contiguous() or out.device != flow.device:
+        raise ValueError("crop_flow_to_stack: out must be a contiguous float32 tensor of %d elements on the flow's device"
+                         % (2 * N * size * size))
+    dcrops = augment.crops_to_device(crops, flow.device)
+    _ffi.check(_ffi.lib().va_flow_to_stack_crop(_ffi.ctx(flow.device.index), _ffi.ptr(flow), N, W, H, float(bound),
+                                                float(mean), float(std), _ffi.ptr(dcrops), size, size, _ffi.ptr(out),
+                                                _ffi.stream_ptr(flow.device)))
+    return out
+
+
 def pyramid_sizes(w, h, params=None):
     p = params if params is not None else _ffi.default_tvl1_params()
     ws = (ctypes.c_int * 16)()

@@ -2,14 +2,16 @@
 
 One clip = 1 RGB frame ``u8[3,224,224]`` + 11 gray frames ``u8[11,224,224]`` -> 10 TV-L1 pairs ->
 ``f32[20,224,224]`` flow volume -> spatial and temporal forward -> class scores ``f32[2,101]`` and
-descriptors ``f32[2,256]``.  In the reference the first half happens offline
+descriptors ``f32[2,256]``.  Larger frames (UCF-101's 320x240) come with crops
+(``augment.draw_clip_crops``): TV-L1 then runs on the full frames and the crop and flip of getTransforms() are applied on
+the device.  In the reference the first half happens offline
 (precomputed flow JPEGs, Sheet03/temporalModel.py:76-90) and the second half is ``validate()``'s
 forward (Sheet03/spatialModel.py:212-218, Sheet03/temporalModel.py:241-247).
 """
 import torch
 
 from . import flow as vflow
-from . import synth, vgg
+from . import augment, synth, vgg
 from .parameters import (NACTION_CLASSES, NORM_MEANS_TF, NORM_STDS_TF, VIDEO_DESCRIPTOR_DIM,
                          VIDEO_INPUT_FLOW_COUNT)
 
@@ -94,11 +96,41 @@ class TwoStreamPipeline(object):
             bank[k] = t = torch.empty(shape, dtype=torch.float32, device=self.device)
         return t
 
-    def submit(self, rgb, gray=None, flow_stack=None):
+    def _check_inputs(self, rgb, gray, flow_stack, crops):
+        """Host-side checks before anything is enqueued -> (rgb_crops, flow_crops), either None where that input is used as
+        it is (it must then be 224x224)."""
+        rgb_crops = flow_crops = None
+        if crops is not None:
+            if not isinstance(crops, (tuple, list)) or len(crops) != 2:
+                raise ValueError("submit: crops= must be (rgb_crops, flow_crops) as augment.draw_clip_crops returns")
+            rgb_crops, flow_crops = crops
+        if rgb_crops is not None:
+            if not isinstance(rgb, torch.Tensor) or rgb.dtype != torch.uint8 or rgb.dim() != 4:
+                raise ValueError("submit: cropped rgb must be a uint8 [B,3,H,W] tensor")
+            augment.check_crops(rgb_crops, rgb.shape[0], rgb.shape[2], rgb.shape[3], augment.CROP_SIZE, "submit(crops=)")
+        elif tuple(rgb.shape[-2:]) != (224, 224):
+            raise ValueError("submit: rgb frames of %dx%d need crops= (augment.draw_clip_crops)" % (rgb.shape[-1], rgb.shape[-2]))
+        if flow_stack is not None:
+            if flow_crops is not None:
+                raise ValueError("submit: flow_stack= is already cropped; pass crops=(rgb_crops, None)")
+        elif flow_crops is not None:
+            B, F, H, W = gray.shape
+            augment.check_crops(flow_crops, B * 2 * self.L, H, W, augment.CROP_SIZE, "submit(crops=)")
+        elif tuple(gray.shape[-2:]) != (224, 224):
+            raise ValueError("submit: gray frames of %dx%d need crops= (augment.draw_clip_crops)" % (gray.shape[-1], gray.shape[-2]))
+        return rgb_crops, flow_crops
+
+    def submit(self, rgb, gray=None, flow_stack=None, crops=None):
         """Enqueue one batch; -> dict(logits_s, logits_t, desc_s, desc_t, done) of tensors that the CNN stream is still
         writing (``done``: the event recorded behind them): call ``wait()`` (or ``run_batch``) before reading them
         on another stream.  ``flow_stack``
-        (precomputed volumes, the reference's actual input) skips TV-L1."""
+        (precomputed volumes, the reference's actual input) skips TV-L1.
+
+        ``crops``: ``(rgb_crops [B,3], flow_crops [B*2L,3])`` from ``augment.draw_clip_crops`` for frames larger than
+        224x224 (u8 rgb ``[B,3,Hr,Wr]``, gray ``[B,L+1,Hg,Wg]``, each side >= 224): TV-L1 runs on the full gray frames
+        and both inputs are cropped and flipped on the CNN stream.  Either entry may be None for an input that is
+        224x224 already."""
+        rgb_crops, flow_crops = self._check_inputs(rgb, gray, flow_stack, crops)
         dev = self.device
         cur = torch.cuda.current_stream(dev)
         ready = torch.cuda.Event()
@@ -116,12 +148,16 @@ class TwoStreamPipeline(object):
         with torch.cuda.stream(self._cnn):
             self._cnn.wait_event(ready)
             rgb.record_stream(self._cnn)
-            _, desc_s, logits_s = self.spatial.forward(rgb)
+            _, desc_s, logits_s = self.spatial.forward(rgb if rgb_crops is None else augment.crop_images(rgb, rgb_crops))
             if flow_stack is None:
                 for ev in evs:
                     self._cnn.wait_event(ev)
                 B, F, H, W = gray.shape
-                stack = vflow.flow_to_stack(flow, out=self._buffer(self._stack, k, (B, 2 * self.L, H, W)))
+                if flow_crops is None:
+                    stack = vflow.flow_to_stack(flow, out=self._buffer(self._stack, k, (B, 2 * self.L, H, W)))
+                else:  # the flow buffer is full-frame, the volume 224x224
+                    stack = vflow.crop_flow_to_stack(flow, flow_crops,
+                                                     out=self._buffer(self._stack, k, (B, 2 * self.L, 224, 224)))
                 done = torch.cuda.Event()
                 done.record(self._cnn)
                 self._flow_read[k] = done
@@ -158,9 +194,9 @@ class TwoStreamPipeline(object):
             t.record_stream(s)
         self._handed_out = []
 
-    def run_batch(self, rgb, gray=None, flow_stack=None):
+    def run_batch(self, rgb, gray=None, flow_stack=None, crops=None):
         """-> dict(logits_s, logits_t, desc_s, desc_t), ready on the current stream (``submit`` + ``wait``)."""
-        out = self.submit(rgb, gray, flow_stack)
+        out = self.submit(rgb, gray, flow_stack, crops)
         self.wait()
         return out
 

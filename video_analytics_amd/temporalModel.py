@@ -57,14 +57,19 @@ class TemporalDataset(Dataset):
         return flowVolume, actionLabel, videoName
 
 
-def flowVolumesFromFrames(gray, flowSampleSize=VIDEO_INPUT_FLOW_COUNT, tvl1_params=None, bound=vflow.FLOW_BOUND):
+def flowVolumesFromFrames(gray, flowSampleSize=VIDEO_INPUT_FLOW_COUNT, tvl1_params=None, bound=vflow.FLOW_BOUND, crops=None):
     """gray CUDA u8/f32 ``[B, L+1, H, W]`` -> flow volumes f32 ``[B, 2L, H, W]`` on the GPU: TV-L1 on the
     L consecutive pairs, 8-bit quantisation, ToTensor+Normalize, x/y interleave -- the tensor
-    ``TemporalDataset.__getitem__`` would have assembled from the upstream tool's JPEGs."""
+    ``TemporalDataset.__getitem__`` would have assembled from the upstream tool's JPEGs.
+
+    ``crops``: CPU int32 ``[B*2L,3]`` (``augment.draw_flow_crops``): frames of any size >= 224 then give
+    ``[B, 2L, 224, 224]``, each flow image cropped and flipped by its own row (Sheet03/temporalModel.py:86)."""
     if gray.dim() != 4 or gray.shape[1] != flowSampleSize + 1:
         raise ValueError("flowVolumesFromFrames: gray must be [B,%d,H,W]" % (flowSampleSize + 1))
     B, _, H, W = gray.shape
     fl = vflow.tvl1_flow(gray, tvl1_params)
+    if crops is not None:
+        return vflow.crop_flow_to_stack(fl, crops, bound=bound).view(B, 2 * flowSampleSize, 224, 224)
     return vflow.flow_to_stack(fl, bound=bound).view(B, 2 * flowSampleSize, H, W)
 
 

@@ -23,6 +23,9 @@
  *                     Sheet03/temporalModel.py:76-90, Sheet03/utils.py:143,145.
  *   va_crop_images_u8 the same crop and flip of the RGB frame SpatialDataset loads:
  *                     Sheet03/spatialModel.py:64-81, Sheet03/utils.py:143,145.
+ *   va_flow_to_stack_views, va_crop_images_u8_views, va_view_mean   ten-crop evaluation (the test protocol of the
+ *                     two-stream paper; no reference counterpart): V crop-and-flip views of every clip and the mean of
+ *                     the per-view outputs.
  *   va_validate_batch the loss / argmax / correct-count lines of validate():
  *                     Sheet03/spatialModel.py:219-221.
  *   va_meter_*        the per-video AverageMeter collation of validate():
@@ -67,7 +70,7 @@ extern "C" {
 typedef struct va_ctx va_ctx;
 typedef struct va_vgg16 va_vgg16;
 
-/* version number (currently 4) + VA_VERSION_EXPERIMENTS when the library was built with -DVA_EXPERIMENTS, i.e. when it
+/* version number (currently 5) + VA_VERSION_EXPERIMENTS when the library was built with -DVA_EXPERIMENTS, i.e. when it
  * also holds the measured-slower kernel families behind va_tvl1_params.tuning / VA_OPT_BF16_VARIANT 6 */
 #define VA_VERSION_EXPERIMENTS 0x10000
 int va_version(void);
@@ -239,6 +242,35 @@ int va_flow_to_stack_crop(va_ctx* ctx, const void* flow, int n_pairs, int w, int
  */
 int va_crop_images_u8(va_ctx* ctx, const void* src, int n, int c, int w, int h, int src_nhwc,
                       const void* crops, int out_w, int out_h, void* dst, void* stream);
+
+/*
+ * V views of every clip (ten-crop evaluation): flow f32 [n_clips*flow_count][2][h][w] -> stack f32
+ * [n_clips][n_views][2*flow_count][out_h][out_w].  Output plane o = (b*n_views + v)*2L + c (L = flow_count; c = 2k is the
+ * x flow of pair k, 2k+1 its y flow) reads source plane b*2L + c through crops row o, then quantises and normalises it as
+ * va_flow_to_stack_crop does.  crops: DEVICE int32 [n_clips*n_views*2L][3] = {top, left, flip}, one row per output plane
+ * (clamped on the device like va_flow_to_stack_crop's).  invert_x_on_flip = 1: a flipped x-flow plane (c even) is also
+ * inverted, q -> 255 - q, before the normalisation (the TSN convention: mirroring reverses horizontal motion); 0: the
+ * reference's mirror without inversion.  n_views = 1 with per-plane crops gives the reference's random crops with TSN
+ * flips.  At most 65535 output planes per call.
+ */
+int va_flow_to_stack_views(va_ctx* ctx, const void* flow, int n_clips, int flow_count, int n_views, int w, int h,
+                           float bound, float mean, float stdv, const void* crops, int invert_x_on_flip, int out_w,
+                           int out_h, void* stack, void* stream);
+
+/*
+ * V views of every image: src u8 [n][c][h][w] (src_nhwc = 0) or [n][h][w][c] (src_nhwc = 1) -> dst u8
+ * [n][n_views][c][out_h][out_w]; output image i reads source image i / n_views through crops row i.
+ * crops: DEVICE int32 [n*n_views][3] = {top, left, flip}.  At most 65535 output planes (n*n_views*c) per call.
+ */
+int va_crop_images_u8_views(va_ctx* ctx, const void* src, int n, int c, int w, int h, int src_nhwc, int n_views,
+                            const void* crops, int out_w, int out_h, void* dst, void* stream);
+
+/*
+ * The mean over views: x f32 [n][n_views][d] -> out f32 [n][d],
+ * out[b][j] = (((x[b][0][j] + x[b][1][j]) + ...) + x[b][n_views-1][j]) / (float)n_views, summed in view order with one
+ * division at the end (no atomics: the result does not depend on scheduling).
+ */
+int va_view_mean(va_ctx* ctx, const void* x, int n, int n_views, int d, void* out, void* stream);
 
 /*
  * Self-test of the arithmetic contract: compares the kernel's packed correctly-rounded sqrt and

@@ -5,6 +5,9 @@ The random numbers are drawn on the host with Python's ``random`` (the global ge
 transforms use it), in exactly the order the reference draws them, so that a seeded run replays the reference's data path
 crop for crop.  A crop is one row ``{top, left, flip}`` of a CPU int32 ``[n,3]`` tensor; the kernels
 (``va_crop_images_u8``, ``va_flow_to_stack_crop``: DESIGN.md S10) receive the rows as a device copy.
+
+Ten-crop evaluation (``ten_crop_views``) uses the same rows: a CPU int32 ``[V,3]`` view table that every clip, and every
+flow image of a clip, is seen through (``crop_image_views``, ``flow.crop_flow_to_stack_views``).
 """
 import random
 
@@ -124,3 +127,55 @@ def crop_images(x_u8, crops, size=CROP_SIZE, layout="NCHW"):
                                             _ffi.ptr(dcrops), size, size, _ffi.ptr(out), _ffi.stream_ptr(dev)))
     return out
 
+
+def ten_crop_views(h, w, size=CROP_SIZE):
+    """torchvision's ``TenCrop(size)`` of an ``h x w`` image as a CPU int32 ``[10,3]`` view table ``{top, left, flip}``:
+    ``five_crop`` of the image (top-left, top-right, bottom-left, bottom-right, centre), then ``five_crop`` of its
+    mirror, with every row in the original frame's coordinates.  View 4 is ``draw_image_crops(mode="center")``; view 9,
+    the mirror's centre, has ``left = (w-size) - cl``, which differs from view 4's ``cl`` when ``w - size`` is odd.
+    Draws no random numbers."""
+    _check_frame(h, w, size, "ten_crop_views")
+    ct, cl, _ = _center(h, w, size)
+    b, r = h - size, w - size
+    five = [(0, 0), (0, r), (b, 0), (b, r), (ct, cl)]
+    mirrored = [(0, r), (0, 0), (b, r), (b, 0), (ct, r - cl)]  # five_crop of the mirror: its left is r - left
+    rows = [(t, l, 0) for t, l in five] + [(t, l, 1) for t, l in mirrored]
+    return torch.tensor(rows, dtype=torch.int32)
+
+
+def check_views(views, h, w, size, who):
+    """Host-side validation (ValueError) of a view table for ``h x w`` frames: CPU int32 ``[V,3]`` with V >= 1 and the
+    rules of ``check_crops`` for every row."""
+    if not isinstance(views, torch.Tensor) or views.dim() != 2 or views.shape[0] < 1 or views.shape[1] != 3:
+        raise ValueError("%s: views must be a CPU int32 [V,3] tensor with V >= 1 (augment.ten_crop_views)" % who)
+    check_crops(views, views.shape[0], h, w, size, who)
+
+
+def expand_views(views, n, per=1):
+    """A ``[V,3]`` view table -> the crop table of ``n`` items with ``per`` planes each seen through every view: row
+    ``(i*V + v)*per + c`` is view v (``per = 2L``: one row per output plane of a flow volume; ``per = 1``: one per
+    output image)."""
+    return views.repeat_interleave(int(per), dim=0).repeat(int(n), 1).contiguous()
+
+
+def crop_image_views(x_u8, views, size=CROP_SIZE, layout="NCHW"):
+    """x_u8: CUDA uint8 ``[n,c,h,w]`` (``layout="NCHW"``) or ``[n,h,w,c]`` (``"NHWC"``); views: CPU int32 ``[V,3]``
+    (``ten_crop_views``) -> CUDA uint8 ``[n,V,c,size,size]``: every image through every view, the u8 input of
+    ``Vgg16Stream.forward_views``."""
+    if not isinstance(x_u8, torch.Tensor) or not x_u8.is_cuda or x_u8.dtype != torch.uint8 or x_u8.dim() != 4:
+        raise ValueError("crop_image_views: x must be a 4-d CUDA uint8 tensor")
+    if layout == "NCHW":
+        n, c, h, w = x_u8.shape
+    elif layout == "NHWC":
+        n, h, w, c = x_u8.shape
+    else:
+        raise ValueError("crop_image_views: layout must be 'NCHW' or 'NHWC', got %r" % (layout,))
+    check_views(views, h, w, size, "crop_image_views")
+    V = views.shape[0]
+    x_u8 = x_u8.contiguous()
+    dev = x_u8.device
+    out = torch.empty((n, V, c, size, size), dtype=torch.uint8, device=dev)
+    dcrops = crops_to_device(expand_views(views, n), dev)
+    _ffi.check(_ffi.lib().va_crop_images_u8_views(_ffi.ctx(dev.index), _ffi.ptr(x_u8), n, c, w, h, int(layout == "NHWC"), V,
+                                                  _ffi.ptr(dcrops), size, size, _ffi.ptr(out), _ffi.stream_ptr(dev)))
+    return out

@@ -3,10 +3,10 @@
 // clips reach the 224x224 networks without a trip through the host.  The crops are drawn on the host
 // (video_analytics_amd/augment.py) and handed over as DEVICE int32 {top, left, flip} triples.
 //
-// Both kernels are pure gathers: thread i of a channel plane writes output element i (the writes of a wave are one
-// contiguous run) and reads source row top + y, column left + x -- or left + out_w - 1 - x when flipped, the same
-// contiguous source segment in reverse lane order.  A wave whose 64 elements straddle two output rows reads two such
-// segments.  No LDS.
+// Both gathers are pure gathers: a thread writes runs of 4 consecutive output elements of a channel plane (the writes of a
+// wave are one contiguous run) and reads source row top + y, column left + x -- or left + out_w - 1 - x when flipped, the
+// same contiguous source segment in reverse order.  A wave whose elements straddle two output rows reads two such
+// segments.  No LDS.  Ten-crop evaluation uses the same kernels with V views per source plane.
 #include "va_internal.h"
 
 // A crop triple as the kernels use it: offsets clamped to the frame, so that no crop value can address memory outside
@@ -24,59 +24,203 @@ __device__ __forceinline__ CropWin load_crop(const int* __restrict__ crops, int 
     return c;
 }
 
-// S10 then S9: flow f32 [n_pairs][2][h][w] -> stack f32 [2 n_pairs][out_h][out_w]; channel ch = 2k + plane reads plane
-// `plane` of pair k through crop ch.  The quantisation and normalisation are k_flow_to_stack's expressions in its order;
-// the flip mirrors the quantised image and leaves the sign of the x flow alone (the reference flips 8-bit images).
+// S10 then S9, for V views of every clip: flow f32 [n_clips][2L][h][w] (= [n_clips*L][2][h][w]) -> stack f32
+// [n_clips][V][2L][out_h][out_w].  Output plane o = (b*V + v)*2L + c reads source plane b*2L + c through crop row o.
+// Block row blockIdx.y = (b*2L + c)*V + v: the V views of one source plane are adjacent in dispatch order, so the
+// re-reads of a plane come from L2 / the Infinity Cache.  The quantisation and normalisation are k_flow_to_stack's
+// expressions in its order; the flip mirrors the quantised image.  With invert_x set, a flipped x-flow plane (c even)
+// also becomes q -> 255 - q (the TSN convention); with it clear, as in the reference, the sign of the x flow is kept.
+// V = 1, one clip of n_pairs pairs and invert_x = 0 is va_flow_to_stack_crop: o = blockIdx.y = the source plane.
+//
+// The kernel is write-bound: each thread writes kGatherSteps runs of 4 consecutive outputs (one 16-byte store when the
+// plane holds a multiple of 4 floats; one 16-byte load when the crop's left offset is a multiple of 4 as well), so that a
+// workgroup writes 16 KB instead of 1 KB (measured on the ten-view volume: one float per thread spent more time launching
+// workgroups than moving bytes).
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+constexpr int kGatherSteps = 4;
+constexpr int kGatherPerBlock = 256 * 4 * kGatherSteps;
+
 __global__ void __launch_bounds__(256) k_flow_crop_stack(const float* __restrict__ flow, const int* __restrict__ crops,
                                                          float* __restrict__ stack, int w, int h, int out_w, int out_h,
-                                                         float bound, float mean, float stdv)
+                                                         int chans, int n_views, int invert_x, int vec4, float bound,
+                                                         float mean, float stdv)
 {
-    const int ch = blockIdx.y;
-    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= out_w * out_h) return;
-    const CropWin c = load_crop(crops, ch, h, w, out_h, out_w);
-    const int y = idx / out_w, x = idx - y * out_w;
-    const int sx = c.left + (c.flip ? out_w - 1 - x : x);
-    const float v = flow[(size_t)ch * h * w + (size_t)(c.top + y) * w + sx];  // plane ch of [n_pairs][2] is pair ch/2, plane ch%2
-    const float t = (255.0f * (v + bound)) / (2.0f * bound);
-    const float q = rintf(fminf(fmaxf(t, 0.0f), 255.0f));
-    stack[(size_t)ch * out_h * out_w + idx] = (q / 255.0f - mean) / stdv;
+    const int src = blockIdx.y / n_views, v = blockIdx.y - src * n_views;
+    const int b = src / chans, c = src - b * chans;
+    const int o = (b * n_views + v) * chans + c;
+    const int n = out_w * out_h;
+    const CropWin cw = load_crop(crops, o, h, w, out_h, out_w);
+    const bool inv = invert_x && cw.flip && (c & 1) == 0;
+    const float* __restrict__ plane = flow + (size_t)src * h * w + (size_t)cw.top * w;
+    float* __restrict__ dst = stack + (size_t)o * n;
+    // vec4 bit 1: 16-byte aligned flow, w and out_w multiples of 4; with a left offset of 4k too, every run of 4 outputs
+    // (never split between rows) reads one aligned float4
+    const bool ld4 = (vec4 & 2) && (cw.left & 3) == 0;
+#pragma unroll
+    for (int s = 0; s < kGatherSteps; ++s) {
+        const int i0 = ((blockIdx.x * kGatherSteps + s) * blockDim.x + threadIdx.x) * 4;
+        if (i0 >= n) continue;
+        int y = i0 / out_w, x = i0 - y * out_w;
+        float val[4], r[4];
+        if (ld4) {  // the 4 sources are one aligned 16-byte run of row y (reversed when flipped)
+            const int sx = cw.flip ? cw.left + out_w - 4 - x : cw.left + x;
+            const f32x4 f = *reinterpret_cast<const f32x4*>(plane + (size_t)y * w + sx);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) val[k] = cw.flip ? f[3 - k] : f[k];
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const int sx = cw.left + (cw.flip ? out_w - 1 - x : x);
+                val[k] = i0 + k < n ? plane[(size_t)y * w + sx] : 0.0f;  // plane c of clip b: pair c/2, plane c%2
+                if (++x == out_w) x = 0, ++y;
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const float t = (255.0f * (val[k] + bound)) / (2.0f * bound);
+            float q = rintf(fminf(fmaxf(t, 0.0f), 255.0f));
+            if (inv) q = 255.0f - q;
+            r[k] = (q / 255.0f - mean) / stdv;
+        }
+        if (vec4 & 1) {  // 16-byte aligned stack and planes of a multiple of 4 floats: the run lies in the plane, aligned
+            // streamed past the caches: the volume is written once and read by the next kernel, the flow planes are not
+            __builtin_nontemporal_store(f32x4{r[0], r[1], r[2], r[3]}, reinterpret_cast<f32x4*>(dst + i0));
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                if (i0 + k < n) dst[i0 + k] = r[k];
+        }
+    }
 }
 
-// S10 on u8 images: src [n][c][h][w] (NHWC = false) or [n][h][w][c] (NHWC = true) -> dst [n][c][out_h][out_w]; one crop
-// per image, shared by its channels.  Block row blockIdx.y = image * c + channel.
+// S10 on u8 images, V views of each: src [n][c][h][w] (NHWC = false) or [n][h][w][c] (NHWC = true) -> dst
+// [n*V][c][out_h][out_w]; output image i reads source image i / V through crop row i, shared by its channels.  Block row
+// blockIdx.y = i * c + channel (the views of one source image are adjacent).  Each thread writes kGatherSteps runs of 4
+// consecutive bytes (one 4-byte store when vec4 says the runs are aligned), as k_flow_crop_stack does.
 template <bool NHWC>
 __global__ void __launch_bounds__(256) k_crop_images_u8(const unsigned char* __restrict__ src, const int* __restrict__ crops,
                                                         unsigned char* __restrict__ dst, int c, int w, int h, int out_w,
-                                                        int out_h)
+                                                        int out_h, int n_views, int vec4)
 {
     const int img = blockIdx.y / c, chn = blockIdx.y - img * c;
-    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= out_w * out_h) return;
+    const int simg = img / n_views;
+    const int n = out_w * out_h;
     const CropWin cw = load_crop(crops, img, h, w, out_h, out_w);
-    const int y = idx / out_w, x = idx - y * out_w;
-    const int sy = cw.top + y, sx = cw.left + (cw.flip ? out_w - 1 - x : x);
-    const size_t s = NHWC ? (((size_t)img * h + sy) * w + sx) * c + chn : (((size_t)img * c + chn) * h + sy) * w + sx;
-    dst[(size_t)blockIdx.y * out_h * out_w + idx] = src[s];
+    unsigned char* __restrict__ out = dst + (size_t)blockIdx.y * n;
+#pragma unroll
+    for (int s = 0; s < kGatherSteps; ++s) {
+        const int i0 = ((blockIdx.x * kGatherSteps + s) * blockDim.x + threadIdx.x) * 4;
+        if (i0 >= n) continue;
+        int y = i0 / out_w, x = i0 - y * out_w;
+        unsigned r[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int sy = cw.top + y, sx = cw.left + (cw.flip ? out_w - 1 - x : x);
+            const size_t si = NHWC ? (((size_t)simg * h + sy) * w + sx) * c + chn : (((size_t)simg * c + chn) * h + sy) * w + sx;
+            r[k] = i0 + k < n ? src[si] : 0u;
+            if (++x == out_w) x = 0, ++y;
+        }
+        if (vec4) {
+            *reinterpret_cast<unsigned*>(out + i0) = r[0] | (r[1] << 8) | (r[2] << 16) | (r[3] << 24);
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                if (i0 + k < n) out[i0 + k] = (unsigned char)r[k];
+        }
+    }
+}
+
+// The mean over V views: x f32 [n][V][d] -> out f32 [n][d], out = (((x_0 + x_1) + ...) + x_{V-1}) / V in view order.  One
+// thread per (b, j); the loads of a wave are contiguous in j.
+__global__ void __launch_bounds__(256) k_view_mean(const float* __restrict__ x, float* __restrict__ out, int n, int n_views,
+                                                   int d)
+{
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (long long)n * d) return;
+    const int b = (int)(i / d), j = (int)(i - (long long)b * d);
+    const float* p = x + (size_t)b * n_views * d + j;
+    float s = p[0];
+    for (int v = 1; v < n_views; ++v) s += p[(size_t)v * d];
+    out[i] = s / (float)n_views;
 }
 
 static constexpr int kMaxGridY = 65535;
+
+// The checks every flow gather shares; -> VA_OK or the error va_last_error() then reports.
+static int check_flow_gather(const char* who, const void* flow, const void* crops, const void* stack, long long planes,
+                             int w, int h, int out_w, int out_h, float bound, float stdv)
+{
+    VA_CHECK_ARG(flow != nullptr && crops != nullptr && stack != nullptr, "%s: NULL buffer", who);
+    VA_CHECK_ARG(w >= 1 && h >= 1, "%s: bad shape", who);
+    VA_CHECK_ARG(planes <= kMaxGridY, "%s: %lld output planes exceed %d per call", who, planes, kMaxGridY);
+    VA_CHECK_ARG(out_w >= 1 && out_h >= 1 && out_w <= w && out_h <= h, "%s: crop %dx%d does not fit the %dx%d frame", who,
+                 out_w, out_h, w, h);
+    VA_CHECK_ARG(bound > 0.0f && stdv > 0.0f, "%s: bound and std must be > 0", who);
+    return VA_OK;
+}
+
+static void launch_flow_gather(const float* flow, const int* crops, float* stack, int w, int h, int out_w, int out_h,
+                               int chans, int planes, int n_views, int invert_x, float bound, float mean, float stdv,
+                               hipStream_t stream)
+{
+    const dim3 g((unsigned)va_cdiv(out_w * out_h, kGatherPerBlock), (unsigned)planes);
+    const int vec4 = ((out_w * out_h) % 4 == 0 && reinterpret_cast<uintptr_t>(stack) % 16 == 0 ? 1 : 0) |
+                     (w % 4 == 0 && out_w % 4 == 0 && reinterpret_cast<uintptr_t>(flow) % 16 == 0 ? 2 : 0);
+    k_flow_crop_stack<<<g, 256, 0, stream>>>(flow, crops, stack, w, h, out_w, out_h, chans, n_views, invert_x, vec4, bound,
+                                             mean, stdv);
+}
 
 extern "C" int va_flow_to_stack_crop(va_ctx* ctx, const void* flow, int n_pairs, int w, int h, float bound, float mean,
                                      float stdv, const void* crops, int out_w, int out_h, void* stack, void* stream)
 {
     VA_CHECK_ARG(ctx != nullptr, "va_flow_to_stack_crop: ctx is NULL");
     VA_USE_DEVICE(ctx);
-    VA_CHECK_ARG(flow != nullptr && crops != nullptr && stack != nullptr, "va_flow_to_stack_crop: NULL buffer");
-    VA_CHECK_ARG(n_pairs >= 1 && w >= 1 && h >= 1, "va_flow_to_stack_crop: bad shape");
-    VA_CHECK_ARG(2 * (long long)n_pairs <= kMaxGridY, "va_flow_to_stack_crop: %d pairs exceed %d channels per call", n_pairs,
+    VA_CHECK_ARG(n_pairs >= 1, "va_flow_to_stack_crop: bad shape");
+    const int rc = check_flow_gather("va_flow_to_stack_crop", flow, crops, stack, 2LL * n_pairs, w, h, out_w, out_h, bound,
+                                     stdv);
+    if (rc != VA_OK) return rc;
+    launch_flow_gather((const float*)flow, (const int*)crops, (float*)stack, w, h, out_w, out_h, 2 * n_pairs, 2 * n_pairs, 1,
+                       0, bound, mean, stdv, (hipStream_t)stream);
+    VA_LAUNCH_CHECK();
+    return VA_OK;
+}
+
+extern "C" int va_flow_to_stack_views(va_ctx* ctx, const void* flow, int n_clips, int flow_count, int n_views, int w, int h,
+                                      float bound, float mean, float stdv, const void* crops, int invert_x_on_flip,
+                                      int out_w, int out_h, void* stack, void* stream)
+{
+    VA_CHECK_ARG(ctx != nullptr, "va_flow_to_stack_views: ctx is NULL");
+    VA_USE_DEVICE(ctx);
+    VA_CHECK_ARG(n_clips >= 1 && flow_count >= 1 && n_views >= 1, "va_flow_to_stack_views: bad shape");
+    VA_CHECK_ARG(invert_x_on_flip == 0 || invert_x_on_flip == 1, "va_flow_to_stack_views: invert_x_on_flip must be 0 or 1");
+    const long long planes = (long long)n_clips * n_views * 2 * flow_count;
+    const int rc = check_flow_gather("va_flow_to_stack_views", flow, crops, stack, planes, w, h, out_w, out_h, bound, stdv);
+    if (rc != VA_OK) return rc;
+    launch_flow_gather((const float*)flow, (const int*)crops, (float*)stack, w, h, out_w, out_h, 2 * flow_count,
+                       (int)planes, n_views, invert_x_on_flip, bound, mean, stdv, (hipStream_t)stream);
+    VA_LAUNCH_CHECK();
+    return VA_OK;
+}
+
+// The checks and the launch every image gather shares (n_views = 1: va_crop_images_u8).
+static int crop_images(const char* who, const void* src, int n, int c, int w, int h, int src_nhwc, int n_views,
+                       const void* crops, int out_w, int out_h, void* dst, hipStream_t stream)
+{
+    VA_CHECK_ARG(src != nullptr && crops != nullptr && dst != nullptr, "%s: NULL buffer", who);
+    VA_CHECK_ARG(n >= 1 && c >= 1 && w >= 1 && h >= 1 && n_views >= 1, "%s: bad shape", who);
+    VA_CHECK_ARG(src_nhwc == 0 || src_nhwc == 1, "%s: src_nhwc must be 0 or 1", who);
+    VA_CHECK_ARG((long long)n * n_views * c <= kMaxGridY, "%s: %d x %d x %d planes exceed %d per call", who, n, n_views, c,
                  kMaxGridY);
-    VA_CHECK_ARG(out_w >= 1 && out_h >= 1 && out_w <= w && out_h <= h,
-                 "va_flow_to_stack_crop: crop %dx%d does not fit the %dx%d frame", out_w, out_h, w, h);
-    VA_CHECK_ARG(bound > 0.0f && stdv > 0.0f, "va_flow_to_stack_crop: bound and std must be > 0");
-    const dim3 g((unsigned)va_cdiv(out_w * out_h, 256), (unsigned)(2 * n_pairs));
-    k_flow_crop_stack<<<g, 256, 0, (hipStream_t)stream>>>((const float*)flow, (const int*)crops, (float*)stack, w, h, out_w,
-                                                         out_h, bound, mean, stdv);
+    VA_CHECK_ARG(out_w >= 1 && out_h >= 1 && out_w <= w && out_h <= h, "%s: crop %dx%d does not fit the %dx%d image", who,
+                 out_w, out_h, w, h);
+    const dim3 g((unsigned)va_cdiv(out_w * out_h, kGatherPerBlock), (unsigned)(n * n_views * c));
+    const int vec4 = (out_w * out_h) % 4 == 0 && reinterpret_cast<uintptr_t>(dst) % 4 == 0;
+    if (src_nhwc)
+        k_crop_images_u8<true><<<g, 256, 0, stream>>>((const unsigned char*)src, (const int*)crops, (unsigned char*)dst, c, w,
+                                                      h, out_w, out_h, n_views, vec4);
+    else
+        k_crop_images_u8<false><<<g, 256, 0, stream>>>((const unsigned char*)src, (const int*)crops, (unsigned char*)dst, c,
+                                                       w, h, out_w, out_h, n_views, vec4);
     VA_LAUNCH_CHECK();
     return VA_OK;
 }
@@ -86,19 +230,28 @@ extern "C" int va_crop_images_u8(va_ctx* ctx, const void* src, int n, int c, int
 {
     VA_CHECK_ARG(ctx != nullptr, "va_crop_images_u8: ctx is NULL");
     VA_USE_DEVICE(ctx);
-    VA_CHECK_ARG(src != nullptr && crops != nullptr && dst != nullptr, "va_crop_images_u8: NULL buffer");
-    VA_CHECK_ARG(n >= 1 && c >= 1 && w >= 1 && h >= 1, "va_crop_images_u8: bad shape");
-    VA_CHECK_ARG(src_nhwc == 0 || src_nhwc == 1, "va_crop_images_u8: src_nhwc must be 0 or 1");
-    VA_CHECK_ARG((long long)n * c <= kMaxGridY, "va_crop_images_u8: %d x %d planes exceed %d per call", n, c, kMaxGridY);
-    VA_CHECK_ARG(out_w >= 1 && out_h >= 1 && out_w <= w && out_h <= h,
-                 "va_crop_images_u8: crop %dx%d does not fit the %dx%d image", out_w, out_h, w, h);
-    const dim3 g((unsigned)va_cdiv(out_w * out_h, 256), (unsigned)(n * c));
-    if (src_nhwc)
-        k_crop_images_u8<true><<<g, 256, 0, (hipStream_t)stream>>>((const unsigned char*)src, (const int*)crops,
-                                                                   (unsigned char*)dst, c, w, h, out_w, out_h);
-    else
-        k_crop_images_u8<false><<<g, 256, 0, (hipStream_t)stream>>>((const unsigned char*)src, (const int*)crops,
-                                                                    (unsigned char*)dst, c, w, h, out_w, out_h);
+    return crop_images("va_crop_images_u8", src, n, c, w, h, src_nhwc, 1, crops, out_w, out_h, dst, (hipStream_t)stream);
+}
+
+extern "C" int va_crop_images_u8_views(va_ctx* ctx, const void* src, int n, int c, int w, int h, int src_nhwc, int n_views,
+                                       const void* crops, int out_w, int out_h, void* dst, void* stream)
+{
+    VA_CHECK_ARG(ctx != nullptr, "va_crop_images_u8_views: ctx is NULL");
+    VA_USE_DEVICE(ctx);
+    return crop_images("va_crop_images_u8_views", src, n, c, w, h, src_nhwc, n_views, crops, out_w, out_h, dst,
+                       (hipStream_t)stream);
+}
+
+extern "C" int va_view_mean(va_ctx* ctx, const void* x, int n, int n_views, int d, void* out, void* stream)
+{
+    VA_CHECK_ARG(ctx != nullptr, "va_view_mean: ctx is NULL");
+    VA_USE_DEVICE(ctx);
+    VA_CHECK_ARG(x != nullptr && out != nullptr, "va_view_mean: NULL buffer");
+    VA_CHECK_ARG(n >= 1 && n_views >= 1 && d >= 1, "va_view_mean: bad shape");
+    const long long threads = (long long)n * d;
+    VA_CHECK_ARG(threads <= 0x7fffffffLL, "va_view_mean: %d x %d outputs exceed one launch", n, d);
+    k_view_mean<<<(unsigned)((threads + 255) / 256), 256, 0, (hipStream_t)stream>>>((const float*)x, (float*)out, n, n_views,
+                                                                                  d);
     VA_LAUNCH_CHECK();
     return VA_OK;
 }

@@ -148,28 +148,74 @@ def flow_to_stack(flow, bound=FLOW_BOUND, mean=NORM_MEANS_TF[0], std=NORM_STDS_T
     return out
 
 
-def crop_flow_to_stack(flow, crops, size=224, bound=FLOW_BOUND, mean=NORM_MEANS_TF[0], std=NORM_STDS_TF[0], out=None):
+def _check_flow(flow, who):
+    if not isinstance(flow, torch.Tensor) or not flow.is_cuda or flow.dtype != torch.float32:
+        raise ValueError("%s: flow must be a CUDA float32 tensor" % who)
+    if flow.dim() != 4 or flow.shape[1] != 2:
+        raise ValueError("%s: flow must be [N,2,H,W]" % who)
+
+
+def _check_out(out, shape, flow, who):
+    n = 1
+    for k in shape:
+        n *= k
+    if out is None:
+        return torch.empty(shape, dtype=torch.float32, device=flow.device)
+    if out.numel() != n or out.dtype != torch.float32 or not out.is_contiguous() or out.device != flow.device:
+        raise ValueError("%s: out must be a contiguous float32 tensor of %d elements on the flow's device" % (who, n))
+    return out
+
+
+def _views_call(flow, dcrops, n_clips, flow_count, n_views, invert, size, bound, mean, std, out):
+    N, _, H, W = flow.shape
+    _ffi.check(_ffi.lib().va_flow_to_stack_views(_ffi.ctx(flow.device.index), _ffi.ptr(flow), n_clips, flow_count, n_views, W,
+                                                 H, float(bound), float(mean), float(std), _ffi.ptr(dcrops), int(bool(invert)),
+                                                 size, size, _ffi.ptr(out), _ffi.stream_ptr(flow.device)))
+
+
+def crop_flow_to_stack(flow, crops, size=224, bound=FLOW_BOUND, mean=NORM_MEANS_TF[0], std=NORM_STDS_TF[0], out=None,
+                       invert_x_on_flip=False):
     """``flow_to_stack`` of full-size flow with one crop and flip per output channel (then S9): flow
     ``[N,2,H,W]`` float32 (H, W >= ``size``), crops CPU int32 ``[2N,3]`` rows ``{top, left, flip}`` (row 2k: the x flow of
-    pair k; ``augment.draw_flow_crops``) -> ``[2N,size,size]`` float32.  Only the crop windows are read."""
+    pair k; ``augment.draw_flow_crops``) -> ``[2N,size,size]`` float32.  Only the crop windows are read.
+
+    ``invert_x_on_flip``: a flipped x-flow image also becomes ``q -> 255 - q`` (TSN flips: mirroring reverses horizontal
+    motion); the default mirrors without inverting, as the reference does."""
     from . import augment
-    if not isinstance(flow, torch.Tensor) or not flow.is_cuda or flow.dtype != torch.float32:
-        raise ValueError("crop_flow_to_stack: flow must be a CUDA float32 tensor")
-    if flow.dim() != 4 or flow.shape[1] != 2:
-        raise ValueError("crop_flow_to_stack: flow must be [N,2,H,W]")
+    _check_flow(flow, "crop_flow_to_stack")
     N, _, H, W = flow.shape
     augment.check_crops(crops, 2 * N, H, W, size, "crop_flow_to_stack")
     flow = flow.contiguous()
-    if out is None:
-        out = torch.empty((2 * N, size, size), dtype=torch.float32, device=flow.device)
-    elif out.numel() != 2 * N * size * size or out.dtype != torch.float32 or not out.is_contiguous() or out.device != flow.device:
-        raise ValueError("crop_flow_to_stack: out must be a contiguous float32 tensor of %d elements on the flow's device"
-                         % (2 * N * size * size))
+    out = _check_out(out, (2 * N, size, size), flow, "crop_flow_to_stack")
     dcrops = augment.crops_to_device(crops, flow.device)
+    if invert_x_on_flip:  # one "clip" of N pairs seen through one view: the crop table has one row per output plane
+        _views_call(flow, dcrops, 1, N, 1, True, size, bound, mean, std, out)
+        return out
     _ffi.check(_ffi.lib().va_flow_to_stack_crop(_ffi.ctx(flow.device.index), _ffi.ptr(flow), N, W, H, float(bound),
                                                 float(mean), float(std), _ffi.ptr(dcrops), size, size, _ffi.ptr(out),
                                                 _ffi.stream_ptr(flow.device)))
     return out
+
+
+def crop_flow_to_stack_views(flow, views, flow_count, invert_x_on_flip=False, size=224, bound=FLOW_BOUND,
+                             mean=NORM_MEANS_TF[0], std=NORM_STDS_TF[0], out=None):
+    """Ten-crop flow volumes: flow ``[B*L,2,H,W]`` float32 of B clips of ``flow_count`` = L pairs, views
+    CPU int32 ``[V,3]`` (``augment.ten_crop_views``) -> ``[B,V,2L,size,size]`` float32: every flow image of every clip
+    seen through every view, quantised and normalised as ``crop_flow_to_stack``.  ``invert_x_on_flip``: TSN flips (a
+    mirrored x-flow image becomes ``q -> 255 - q``); the default mirrors without inverting."""
+    from . import augment
+    _check_flow(flow, "crop_flow_to_stack_views")
+    N, _, H, W = flow.shape
+    L = int(flow_count)
+    if L < 1 or N % L:
+        raise ValueError("crop_flow_to_stack_views: %d flow pairs are not a whole number of clips of %d" % (N, L))
+    augment.check_views(views, H, W, size, "crop_flow_to_stack_views")
+    B, V = N // L, views.shape[0]
+    flow = flow.contiguous()
+    out = _check_out(out, (B, V, 2 * L, size, size), flow, "crop_flow_to_stack_views")
+    dcrops = augment.crops_to_device(augment.expand_views(views, B, 2 * L), flow.device)
+    _views_call(flow, dcrops, B, L, V, invert_x_on_flip, size, bound, mean, std, out)
+    return out.view(B, V, 2 * L, size, size)
 
 
 def pyramid_sizes(w, h, params=None):

@@ -4,7 +4,8 @@ One clip = 1 RGB frame ``u8[3,224,224]`` + 11 gray frames ``u8[11,224,224]`` -> 
 ``f32[20,224,224]`` flow volume -> spatial and temporal forward -> class scores ``f32[2,101]`` and
 descriptors ``f32[2,256]``.  Larger frames (UCF-101's 320x240) come with crops
 (``augment.draw_clip_crops``): TV-L1 then runs on the full frames and the crop and flip of getTransforms() are applied on
-the device.  In the reference the first half happens offline
+the device, or go through V views each (``views=``: ten-crop evaluation) whose outputs are averaged.
+In the reference the first half happens offline
 (precomputed flow JPEGs, Sheet03/temporalModel.py:76-90) and the second half is ``validate()``'s
 forward (Sheet03/spatialModel.py:212-218, Sheet03/temporalModel.py:241-247).
 """
@@ -96,6 +97,21 @@ class TwoStreamPipeline(object):
             bank[k] = t = torch.empty(shape, dtype=torch.float32, device=self.device)
         return t
 
+    def _check_views(self, rgb, gray, flow_stack, views):
+        """Host-side checks of ``views=`` before anything is enqueued -> (rgb_views, flow_views)."""
+        if flow_stack is not None:
+            raise ValueError("submit: views= needs gray frames; flow_stack= is already cropped")
+        if not isinstance(views, (tuple, list)) or len(views) != 2:
+            raise ValueError("submit: views= must be (rgb_views, flow_views), e.g. two augment.ten_crop_views tables")
+        rgb_views, flow_views = views
+        if not isinstance(rgb, torch.Tensor) or rgb.dtype != torch.uint8 or rgb.dim() != 4:
+            raise ValueError("submit: rgb must be a uint8 [B,3,H,W] tensor with views=")
+        augment.check_views(rgb_views, rgb.shape[2], rgb.shape[3], augment.CROP_SIZE, "submit(views=)")
+        if gray is None or gray.dim() != 4:
+            raise ValueError("submit: gray must be [B,L+1,H,W] with views=")
+        augment.check_views(flow_views, gray.shape[2], gray.shape[3], augment.CROP_SIZE, "submit(views=)")
+        return rgb_views, flow_views
+
     def _check_inputs(self, rgb, gray, flow_stack, crops):
         """Host-side checks before anything is enqueued -> (rgb_crops, flow_crops), either None where that input is used as
         it is (it must then be 224x224)."""
@@ -120,7 +136,7 @@ class TwoStreamPipeline(object):
             raise ValueError("submit: gray frames of %dx%d need crops= (augment.draw_clip_crops)" % (gray.shape[-1], gray.shape[-2]))
         return rgb_crops, flow_crops
 
-    def submit(self, rgb, gray=None, flow_stack=None, crops=None):
+    def submit(self, rgb, gray=None, flow_stack=None, crops=None, views=None, invert_flow_x=False):
         """Enqueue one batch; -> dict(logits_s, logits_t, desc_s, desc_t, done) of tensors that the CNN stream is still
         writing (``done``: the event recorded behind them): call ``wait()`` (or ``run_batch``) before reading them
         on another stream.  ``flow_stack``
@@ -129,7 +145,20 @@ class TwoStreamPipeline(object):
         ``crops``: ``(rgb_crops [B,3], flow_crops [B*2L,3])`` from ``augment.draw_clip_crops`` for frames larger than
         224x224 (u8 rgb ``[B,3,Hr,Wr]``, gray ``[B,L+1,Hg,Wg]``, each side >= 224): TV-L1 runs on the full gray frames
         and both inputs are cropped and flipped on the CNN stream.  Either entry may be None for an input that is
-        224x224 already."""
+        224x224 already.
+
+        ``views``: ``(rgb_views [Vs,3], flow_views [Vt,3])`` view tables (``augment.ten_crop_views``): every clip is seen
+        through every view of its stream (ten-crop evaluation).  ``logits_*`` / ``desc_*`` are then the
+        view means ``[B,...]`` and ``logits_*_views`` / ``desc_*_views`` hold the per-view outputs ``[B,V,...]``.  Not
+        with ``crops=`` or ``flow_stack=``.  ``invert_flow_x``: TSN flips, a mirrored x-flow image becomes
+        ``q -> 255 - q`` (with ``views=`` or ``crops=``; the default mirrors without inverting, as the reference)."""
+        if views is not None:
+            if crops is not None:
+                raise ValueError("submit: views= and crops= exclude each other")
+            rgb_views, flow_views = self._check_views(rgb, gray, flow_stack, views)
+            return self._submit_views(rgb, gray, rgb_views, flow_views, bool(invert_flow_x))
+        if invert_flow_x and flow_stack is not None:
+            raise ValueError("submit: invert_flow_x needs gray frames; flow_stack= is already quantised")
         rgb_crops, flow_crops = self._check_inputs(rgb, gray, flow_stack, crops)
         dev = self.device
         cur = torch.cuda.current_stream(dev)
@@ -157,7 +186,8 @@ class TwoStreamPipeline(object):
                     stack = vflow.flow_to_stack(flow, out=self._buffer(self._stack, k, (B, 2 * self.L, H, W)))
                 else:  # the flow buffer is full-frame, the volume 224x224
                     stack = vflow.crop_flow_to_stack(flow, flow_crops,
-                                                     out=self._buffer(self._stack, k, (B, 2 * self.L, 224, 224)))
+                                                     out=self._buffer(self._stack, k, (B, 2 * self.L, 224, 224)),
+                                                     invert_x_on_flip=bool(invert_flow_x))
                 done = torch.cuda.Event()
                 done.record(self._cnn)
                 self._flow_read[k] = done
@@ -186,6 +216,45 @@ class TwoStreamPipeline(object):
         out["done"] = finished  # host-side throttle: out["done"].synchronize() blocks the HOST until this batch is complete
         return out
 
+    def _submit_views(self, rgb, gray, rgb_views, flow_views, invert):
+        """``submit(views=)``: the stream layout of the crops= path, with B*V images per stream and the view means."""
+        dev = self.device
+        cur = torch.cuda.current_stream(dev)
+        ready = torch.cuda.Event()
+        ready.record(cur)
+        k = self._n % self.depth
+        self._n += 1
+        B, F, H, W = gray.shape
+        if F != self.L + 1:
+            raise ValueError("submit: need %d gray frames per clip, got %d" % (self.L + 1, F))
+        fbuf = self._buffer(self._flow, k, (B * self.L, 2, H, W))
+        flow, evs = vflow.tvl1_flow_concurrent(gray, self.tvl1_params, self.flow_streams, out=fbuf,
+                                               after=[ready, self._flow_read[k]], join=False)
+        with torch.cuda.stream(self._cnn):
+            self._cnn.wait_event(ready)
+            rgb.record_stream(self._cnn)
+            desc_s, logits_s, desc_sv, logits_sv = self.spatial.forward_views(augment.crop_image_views(rgb, rgb_views))
+            for ev in evs:
+                self._cnn.wait_event(ev)
+            Vt = flow_views.shape[0]
+            stack = vflow.crop_flow_to_stack_views(flow, flow_views, self.L, invert_x_on_flip=invert,
+                                                   out=self._buffer(self._stack, k, (B, Vt, 2 * self.L, 224, 224)))
+            done = torch.cuda.Event()
+            done.record(self._cnn)
+            self._flow_read[k] = done
+            if self._t_done is not None:
+                self._cnn.wait_event(self._t_done)
+            desc_t, logits_t, desc_tv, logits_tv = self.temporal.forward_views(stack)
+            self._t_done = torch.cuda.Event()
+            self._t_done.record(self._cnn)
+            finished = torch.cuda.Event()
+            finished.record(self._cnn)
+        out = dict(logits_s=logits_s, logits_t=logits_t, desc_s=desc_s, desc_t=desc_t, logits_s_views=logits_sv,
+                   logits_t_views=logits_tv, desc_s_views=desc_sv, desc_t_views=desc_tv)
+        self._handed_out.extend(out.values())
+        out["done"] = finished
+        return out
+
     def wait(self, stream=None):
         """Make ``stream`` (default: the current one) wait for every batch submitted so far."""
         s = torch.cuda.current_stream(self.device) if stream is None else stream
@@ -194,9 +263,10 @@ class TwoStreamPipeline(object):
             t.record_stream(s)
         self._handed_out = []
 
-    def run_batch(self, rgb, gray=None, flow_stack=None, crops=None):
-        """-> dict(logits_s, logits_t, desc_s, desc_t), ready on the current stream (``submit`` + ``wait``)."""
-        out = self.submit(rgb, gray, flow_stack, crops)
+    def run_batch(self, rgb, gray=None, flow_stack=None, crops=None, views=None, invert_flow_x=False):
+        """-> dict(logits_s, logits_t, desc_s, desc_t), ready on the current stream (``submit`` + ``wait``); with
+        ``views=`` also the per-view ``*_views`` entries."""
+        out = self.submit(rgb, gray, flow_stack, crops, views, invert_flow_x)
         self.wait()
         return out
 

@@ -118,14 +118,20 @@ class SpatialNetwork(object):
                                device=self.device.index)
 
     def validate(self):
-        """Sheet03/spatialModel.py:197-231: returns (correct / totalTest, summed per-batch mean CE)."""
+        """Sheet03/spatialModel.py:197-231: returns (correct / totalTest, summed per-batch mean CE).
+
+        Batches of ``[B,V,C,224,224]`` (a multi-view transform such as ``utils.getTenCropTransforms``) run through
+        ``forward_views``: the loss, the hits and the per-video descriptors then use the means over the V views."""
         correct = 0
         loss = 0
         pending = []
         for iBatch, (data, labels, videoNames) in enumerate(self.testLoader):
             ip = data.to(self.device, non_blocking=True)
-            op = self.features(ip)
-            featureVectors, op = self.classify(op)
+            if ip.dim() == 5:
+                featureVectors, op, _, _ = self.model.forward_views(ip)
+            else:
+                op = self.features(ip)
+                featureVectors, op = self.classify(op)
             pending.append(vgg.validate_batch(op, labels))  # [mean CE, n correct] on the device, no sync
             # per-video running means (Sheet03/spatialModel.py:223-228) accumulate in HBM: no copy per batch
             self.testMeters.update(featureVectors, videoNames, labels)

@@ -52,24 +52,40 @@ class TemporalDataset(Dataset):
         # the transform is applied to each of the 2L images independently: 2L independent random
         # crops / flips (Sheet03/temporalModel.py:86, quirk 2)
         tf = self.imageTransforms if self.imageTransforms is not None else ToTensor()
+        if getattr(tf, "nViews", None):
+            # a multi-view transform (utils.getTenCropTransforms): each image gives [V,1,224,224] and is told whether it
+            # is x flow; the volume is [V,2L,224,224], views first, so that the default collate gives [B,V,2L,224,224]
+            views = [tf(Image.open(frame), flowX=(ax == "x")) for frame, (ax, _) in zip(flowFrames, order)]
+            return torch.cat(views, dim=1), actionLabel, videoName
         loadedFrames = [tf(Image.open(frame)) for frame in flowFrames]
         flowVolume = torch.squeeze(torch.stack(loadedFrames, dim=0))  # [2L,1,H,W] -> [2L,H,W]
         return flowVolume, actionLabel, videoName
 
 
-def flowVolumesFromFrames(gray, flowSampleSize=VIDEO_INPUT_FLOW_COUNT, tvl1_params=None, bound=vflow.FLOW_BOUND, crops=None):
+def flowVolumesFromFrames(gray, flowSampleSize=VIDEO_INPUT_FLOW_COUNT, tvl1_params=None, bound=vflow.FLOW_BOUND, crops=None,
+                          views=None, invert_flow_x=False):
     """gray CUDA u8/f32 ``[B, L+1, H, W]`` -> flow volumes f32 ``[B, 2L, H, W]`` on the GPU: TV-L1 on the
     L consecutive pairs, 8-bit quantisation, ToTensor+Normalize, x/y interleave -- the tensor
     ``TemporalDataset.__getitem__`` would have assembled from the upstream tool's JPEGs.
 
     ``crops``: CPU int32 ``[B*2L,3]`` (``augment.draw_flow_crops``): frames of any size >= 224 then give
-    ``[B, 2L, 224, 224]``, each flow image cropped and flipped by its own row (Sheet03/temporalModel.py:86)."""
+    ``[B, 2L, 224, 224]``, each flow image cropped and flipped by its own row (Sheet03/temporalModel.py:86).
+    ``views``: CPU int32 ``[V,3]`` (``augment.ten_crop_views``): ``[B, V, 2L, 224, 224]``, every clip through every view.
+    ``invert_flow_x``: with ``crops`` or ``views``, a mirrored x-flow image becomes ``q -> 255 - q`` (TSN flips)."""
     if gray.dim() != 4 or gray.shape[1] != flowSampleSize + 1:
         raise ValueError("flowVolumesFromFrames: gray must be [B,%d,H,W]" % (flowSampleSize + 1))
+    if crops is not None and views is not None:
+        raise ValueError("flowVolumesFromFrames: crops= and views= exclude each other")
     B, _, H, W = gray.shape
+    if views is not None:
+        from . import augment
+        augment.check_views(views, H, W, 224, "flowVolumesFromFrames")
     fl = vflow.tvl1_flow(gray, tvl1_params)
+    if views is not None:
+        return vflow.crop_flow_to_stack_views(fl, views, flowSampleSize, invert_x_on_flip=invert_flow_x, bound=bound)
     if crops is not None:
-        return vflow.crop_flow_to_stack(fl, crops, bound=bound).view(B, 2 * flowSampleSize, 224, 224)
+        return vflow.crop_flow_to_stack(fl, crops, bound=bound, invert_x_on_flip=invert_flow_x).view(B, 2 * flowSampleSize,
+                                                                                                      224, 224)
     return vflow.flow_to_stack(fl, bound=bound).view(B, 2 * flowSampleSize, H, W)
 
 

@@ -309,6 +309,43 @@ def getTransforms(cropSize=CROP_SIZE_TF, hortizontalFlip=HORIZONTAL_FLIP_TF, nor
     return Compose(imgTrans)
 
 
+class TenCrop(object):
+    """Ten-crop evaluation (the test protocol of the two-stream paper; torchvision's ``TenCrop``): an image -> float32
+    ``[10,C,224,224]``, the four corners and the centre, then the same five of the mirrored image
+    (``augment.ten_crop_views``), each through ``ToTensor`` and ``Normalize``.  ``nViews`` tells the datasets that one
+    image gives ten.  ``flowX=True`` marks an x-flow image: with ``invertFlowX`` its mirrored views are inverted,
+    ``q -> 255 - q`` (TSN flips: mirroring reverses horizontal motion).  Draws no random numbers."""
+
+    nViews = 10
+
+    def __init__(self, size=224, normMeans=NORM_MEANS_TF, normStds=NORM_STDS_TF, invertFlowX=False):
+        self.size = int(size)
+        self.invertFlowX = bool(invertFlowX)
+        self.toTensor = ToTensor()
+        self.normalize = Normalize(mean=normMeans, std=normStds) if normMeans and normStds else None
+
+    def __call__(self, img, flowX=False):
+        from .augment import ten_crop_views
+        a = np.asarray(img)
+        s = self.size
+        out = []
+        for top, left, flip in ten_crop_views(a.shape[0], a.shape[1], s).tolist():
+            v = a[top:top + s, left:left + s]
+            if flip:
+                v = v[:, ::-1]
+                if flowX and self.invertFlowX:
+                    v = (255 - v.astype(np.int32)).astype(a.dtype)
+            t = self.toTensor(v)
+            out.append(self.normalize(t) if self.normalize is not None else t)
+        return torch.stack(out)
+
+
+def getTenCropTransforms(normMeans=NORM_MEANS_TF, normStds=NORM_STDS_TF, invertFlowX=False):
+    """The deterministic test-time counterpart of ``getTransforms()``: ten 224x224 views of every image (``TenCrop``),
+    for ``SpatialDataset`` / ``TemporalDataset`` and the five-dimensional batches ``validate()`` then averages over."""
+    return TenCrop(224, normMeans, normStds, invertFlowX)
+
+
 def getDataLoader(dataset, batchSize=TEMPORAL_BATCH_SIZE, nWorkers=NWORKERS_LOADER, shuffle=SHUFFLE_LOADER):
     """Sheet03/utils.py:125-133: default collate, last batch partial, shuffle on (also for test)."""
     return DataLoader(dataset=dataset, batch_size=batchSize, shuffle=shuffle, num_workers=nWorkers)

@@ -137,6 +137,41 @@ class Vgg16Stream(object):
                                       _ffi.ptr(desc), _ffi.ptr(logits), _ffi.ptr(ws), ws.numel(), _ffi.stream_ptr(self.device)))
         return feat, desc, logits
 
+    VIEW_CHUNK = 320  # images per forward call of forward_views (ten views x the configured batch of 32)
+
+    def forward_views(self, x):
+        """x: CUDA float32 (normalised) or uint8 ``[B,V,C,224,224]``, V views of every clip (ten-crop evaluation,
+        DESIGN.md S10).  Returns (desc [B,D], logits [B,nClasses], desc_views [B,V,D], logits_views [B,V,nClasses]):
+        the per-view outputs of ``forward`` and their ``view_mean``.
+
+        The B*V images run in chunks of whole clips of at most ``VIEW_CHUNK`` images: the bf16 conv stack refuses more
+        than about 334 images at 224x224 (32-bit buffer offsets), fp32 224x224x64 activations pass 2^31 elements at 669
+        images, and 320 is ten views of the configured batch of 32.  A chunk's outputs are the rows ``forward`` gives for
+        that chunk alone."""
+        if not isinstance(x, torch.Tensor) or not x.is_cuda:
+            raise ValueError("Vgg16Stream.forward_views: x must be a CUDA tensor")
+        if x.dim() != 5 or tuple(x.shape[2:]) != (self.c_in, 224, 224):
+            raise ValueError("Vgg16Stream.forward_views: x must be [B,V,%d,224,224], got %s" % (self.c_in, tuple(x.shape)))
+        if x.dtype not in (torch.float32, torch.uint8):
+            raise ValueError("Vgg16Stream.forward_views: x must be float32 or uint8")
+        self._on_my_device(x, "forward_views")
+        B, V = int(x.shape[0]), int(x.shape[1])
+        if B < 1 or V < 1 or V > self.VIEW_CHUNK:
+            raise ValueError("Vgg16Stream.forward_views: need 1..%d views and at least one clip, got B=%d V=%d"
+                             % (self.VIEW_CHUNK, B, V))
+        x = x.contiguous().view(B * V, self.c_in, 224, 224)
+        per = (self.VIEW_CHUNK // V) * V
+        L = _ffi.lib()
+        ws = _workspace(L.va_vgg16_workspace_bytes(self._h, min(per, B * V)), x.device, self.ws_slot)
+        desc_v = torch.empty((B, V, self.desc_dim), dtype=torch.float32, device=x.device)
+        logits_v = torch.empty((B, V, self.n_classes), dtype=torch.float32, device=x.device)
+        dflat, lflat = desc_v.view(B * V, -1), logits_v.view(B * V, -1)
+        for i0 in range(0, B * V, per):
+            n = min(per, B * V - i0)
+            _ffi.check(L.va_vgg16_forward(self._h, _ffi.ptr(x[i0:i0 + n]), int(x.dtype == torch.uint8), n, None,
+                                          _ffi.ptr(dflat[i0:i0 + n]), _ffi.ptr(lflat[i0:i0 + n]), _ffi.ptr(ws), ws.numel(),
+                                          _ffi.stream_ptr(self.device)))
+        return view_mean(desc_v), view_mean(logits_v), desc_v, logits_v
 
     def features(self, x):
         """``self.features(ip)`` of the reference (Sheet03/spatialModel.py:212): [B,C,224,224] -> [B,512,7,7]."""
@@ -405,6 +440,20 @@ def _check_labels(labels, n_classes, who):
         lo, hi = int(labels.min()), int(labels.max())
         if lo < 0 or hi >= n_classes:
             raise ValueError("%s: Target %d is out of bounds for %d classes" % (who, hi if hi >= n_classes else lo, n_classes))
+
+
+def view_mean(x):
+    """x: CUDA float32 ``[B,V,...]`` -> ``[B,...]``, the mean over the V views (``va_view_mean``): summed in view order,
+    ``((x[:,0] + x[:,1]) + ...) + x[:,V-1]``, then divided by V once."""
+    if not isinstance(x, torch.Tensor) or not x.is_cuda or x.dtype != torch.float32 or x.dim() < 2:
+        raise ValueError("view_mean: x must be a CUDA float32 tensor [B,V,...]")
+    x = x.contiguous()
+    B, V = int(x.shape[0]), int(x.shape[1])
+    d = x.numel() // max(1, B * V)
+    out = torch.empty((B,) + tuple(x.shape[2:]), dtype=torch.float32, device=x.device)
+    _ffi.check(_ffi.lib().va_view_mean(_ffi.ctx(x.device.index), _ffi.ptr(x), B, V, d, _ffi.ptr(out),
+                                       _ffi.stream_ptr(x.device)))
+    return out
 
 
 def validate_batch(logits, labels):

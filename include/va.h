@@ -26,6 +26,8 @@
  *   va_flow_to_stack_views, va_crop_images_u8_views, va_view_mean   ten-crop evaluation (the test protocol of the
  *                     two-stream paper; no reference counterpart): V crop-and-flip views of every clip and the mean of
  *                     the per-view outputs.
+ *   va_flow_field_means, va_flow_motion   mean flow subtraction and trajectory stacking, two of the temporal-ConvNet
+ *                     inputs of the two-stream paper (no reference counterpart).
  *   va_validate_batch the loss / argmax / correct-count lines of validate():
  *                     Sheet03/spatialModel.py:219-221.
  *   va_meter_*        the per-video AverageMeter collation of validate():
@@ -70,7 +72,7 @@ extern "C" {
 typedef struct va_ctx va_ctx;
 typedef struct va_vgg16 va_vgg16;
 
-/* version number (currently 5) + VA_VERSION_EXPERIMENTS when the library was built with -DVA_EXPERIMENTS, i.e. when it
+/* version number (currently 6) + VA_VERSION_EXPERIMENTS when the library was built with -DVA_EXPERIMENTS, i.e. when it
  * also holds the measured-slower kernel families behind va_tvl1_params.tuning / VA_OPT_BF16_VARIANT 6 */
 #define VA_VERSION_EXPERIMENTS 0x10000
 int va_version(void);
@@ -271,6 +273,25 @@ int va_crop_images_u8_views(va_ctx* ctx, const void* src, int n, int c, int w, i
  * division at the end (no atomics: the result does not depend on scheduling).
  */
 int va_view_mean(va_ctx* ctx, const void* x, int n, int n_views, int d, void* out, void* stream);
+
+/*
+ * Mean flow subtraction, step one: flow f32 [n_pairs][2][h][w] -> means f32 [n_pairs][2], the mean of
+ * every displacement field's component over the full frame.  Each value is clamped to [-32768, 32768] (a NaN becomes
+ * -32768) and summed as the exact integer rint(a * 65536) in int64, so the result does not depend on the reduction
+ * order: means[n][c] = (float)((double)S / ((double)(w*h) * 65536.0)).
+ */
+int va_flow_field_means(va_ctx* ctx, const void* flow, int n_pairs, int w, int h, void* means, void* stream);
+
+/*
+ * The motion field: flow f32 [n_chains*chain_len][2][h][w] -> out f32 of the same shape and pair order,
+ * so that va_flow_to_stack / _crop / _views apply to it unchanged.  trajectory = 1: trajectory stacking, every pixel
+ * (x, y) of chain b starts at p_0 = (x, y); pair n = b*chain_len + k is sampled bilinearly at p_k (clamped into the
+ * frame) and p_{k+1} = p_k + that raw sample.  trajectory = 0: the flow itself.  means (DEVICE f32 [n_pairs][2], from
+ * va_flow_field_means; NULL = none) is subtracted from every output value of its pair and component.  trajectory = 0
+ * with means = NULL is rejected (nothing to do).  out must not overlap flow.  At most 65535 chains per call.
+ */
+int va_flow_motion(va_ctx* ctx, const void* flow, int n_chains, int chain_len, int trajectory, int w, int h,
+                   const void* means, void* out, void* stream);
 
 /*
  * Self-test of the arithmetic contract: compares the kernel's packed correctly-rounded sqrt and

@@ -20,7 +20,8 @@ EXPORTS = [
     "va_copy_first_layer", "va_validate_batch",
     "va_tvl1_default_params", "va_tvl1_pyramid_sizes", "va_tvl1_tile_plan", "va_tvl1_workspace_bytes", "va_tvl1_flow",
     "va_flow_to_stack", "va_flow_to_stack_crop", "va_crop_images_u8",
-    "va_flow_to_stack_views", "va_crop_images_u8_views", "va_view_mean", "va_selftest_exact_math", "va_tvl1_profile_enable", "va_tvl1_profile_read", "va_tvl1_profile_levels",
+    "va_flow_to_stack_views", "va_crop_images_u8_views", "va_view_mean", "va_flow_field_means", "va_flow_motion",
+    "va_selftest_exact_math", "va_tvl1_profile_enable", "va_tvl1_profile_read", "va_tvl1_profile_levels",
     "va_meter_update", "va_meter_average", "va_linear_svm_predict",
     "va_vgg16_train_init", "va_vgg16_train_workspace_bytes", "va_vgg16_train_step",
     "va_vgg16_export_state", "va_vgg16_import_state", "va_vgg16_train_plan",
@@ -134,6 +135,10 @@ def lib():
     L.va_crop_images_u8_views.restype = ci
     L.va_view_mean.argtypes = [vp, vp, ci, ci, ci, vp, vp]
     L.va_view_mean.restype = ci
+    L.va_flow_field_means.argtypes = [vp, vp, ci, ci, ci, vp, vp]
+    L.va_flow_field_means.restype = ci
+    L.va_flow_motion.argtypes = [vp, vp, ci, ci, ci, ci, ci, vp, vp, vp]
+    L.va_flow_motion.restype = ci
     L.va_selftest_exact_math.argtypes = [vp, cf, cf, vp, vp]
     L.va_selftest_exact_math.restype = ci
     L.va_tvl1_profile_enable.argtypes = [vp, ci]

@@ -218,6 +218,96 @@ def crop_flow_to_stack_views(flow, views, flow_count, invert_x_on_flip=False, si
     return out.view(B, V, 2 * L, size, size)
 
 
+
+# The temporal-ConvNet inputs of the two-stream paper: "stack" is optical-flow stacking (the default and
+# the reference's input), "trajectory" samples the flow along the trajectory that starts at each pixel of the first frame,
+# "bidirectional" stacks L/2 forward fields from the clip's centre frame on and L/2 backward ones from it back.
+MOTIONS = ("stack", "trajectory", "bidirectional")
+
+
+def check_motion(motion, mean_flow, flow_count, who):
+    """Host-side checks of the motion options, before anything is enqueued: an unknown motion, trajectory stacking of
+    bi-directional flow (the paper does not combine them) and bi-directional flow of an odd L raise ValueError."""
+    parts = motion.split("+") if isinstance(motion, str) else list(motion) if isinstance(motion, (tuple, list)) else []
+    if "trajectory" in parts and "bidirectional" in parts:
+        raise ValueError("%s: trajectory stacking of bi-directional flow is not offered (the two-stream paper does not "
+                         "combine them)" % who)
+    if not isinstance(motion, str) or motion not in MOTIONS:
+        raise ValueError("%s: motion must be one of %s, got %r" % (who, ", ".join(MOTIONS), motion))
+    if motion == "bidirectional" and (flow_count < 2 or flow_count % 2):
+        raise ValueError("%s: bi-directional flow needs an even number of flow pairs, got %d" % (who, flow_count))
+    if not isinstance(mean_flow, bool):
+        raise ValueError("%s: mean_flow must be True or False" % who)
+
+
+def bidirectional_sequences(gray):
+    """Bi-directional flow's TV-L1 input: gray ``[B,L+1,H,W]`` (L even; frame L/2 is tau) ->
+    ``[2B,L/2+1,H,W]``, per clip the forward sequence ``(f_{L/2}, ..., f_L)`` and then the backward one
+    ``(f_{L/2}, f_{L/2-1}, ..., f_0)``.  TV-L1 of it gives per clip L/2 forward fields tau+k -> tau+k+1 and then L/2
+    backward fields tau-j -> tau-j-1: L pairs in the usual ``[B*L,2,H,W]`` layout.  Plain indexing (CPU tensors too)."""
+    if not isinstance(gray, torch.Tensor) or gray.dim() != 4:
+        raise ValueError("bidirectional_sequences: gray must be a [B,L+1,H,W] tensor")
+    B, F, H, W = gray.shape
+    L = F - 1
+    if L < 2 or L % 2:
+        raise ValueError("bidirectional_sequences: bi-directional flow needs an even number of flow pairs, got %d" % L)
+    h = L // 2
+    idx = torch.stack([torch.arange(h, L + 1), torch.arange(h, -1, -1)]).to(gray.device)  # [2, L/2+1]
+    return gray[:, idx].reshape(2 * B, h + 1, H, W)
+
+
+def flow_field_means(flow, out=None):
+    """S11: flow ``[N,2,H,W]`` float32 -> ``[N,2]`` float32, the mean vector of every displacement field over the full
+    frame, summed as exact 2^-16 fixed point (the same bits in any reduction order)."""
+    _check_flow(flow, "flow_field_means")
+    flow = flow.contiguous()
+    N, _, H, W = flow.shape
+    out = _check_out(out, (N, 2), flow, "flow_field_means")
+    _ffi.check(_ffi.lib().va_flow_field_means(_ffi.ctx(flow.device.index), _ffi.ptr(flow), N, W, H, _ffi.ptr(out),
+                                              _ffi.stream_ptr(flow.device)))
+    return out.view(N, 2)
+
+
+def _overlaps(a, b):
+    a0, b0 = a.data_ptr(), b.data_ptr()
+    return a0 < b0 + b.numel() * b.element_size() and b0 < a0 + a.numel() * a.element_size()
+
+
+def motion_field(flow, flow_count, trajectory=False, means=None, out=None):
+    """S12: flow ``[N,2,H,W]`` float32 of clips of ``flow_count`` = L pairs -> a float32 array of the same shape and pair
+    order, which every S9 / S10 consumer (``flow_to_stack``, ``crop_flow_to_stack``, ``crop_flow_to_stack_views``) takes
+    as it takes flow.  ``trajectory``: pair k of a clip is sampled along the trajectory that starts at each pixel of the
+    clip's first frame and follows the raw flow.  ``means``: CUDA float32 ``[N,2]`` (``flow_field_means``) subtracted
+    from every value of its field.  ``out`` must not overlap ``flow``."""
+    _check_flow(flow, "motion_field")
+    N, _, H, W = flow.shape
+    L = int(flow_count)
+    if L < 1 or N % L:
+        raise ValueError("motion_field: %d flow pairs are not a whole number of clips of %d" % (N, L))
+    if not trajectory and means is None:
+        raise ValueError("motion_field: nothing to do (no trajectory and no means)")
+    if means is not None:
+        if (not isinstance(means, torch.Tensor) or means.dtype != torch.float32 or means.device != flow.device
+                or means.numel() != 2 * N):
+            raise ValueError("motion_field: means must be a float32 [%d,2] tensor on the flow's device" % N)
+        means = means.contiguous()
+    flow = flow.contiguous()
+    out = _check_out(out, (N, 2, H, W), flow, "motion_field")
+    if _overlaps(out, flow):
+        raise ValueError("motion_field: out must not overlap flow")
+    _ffi.check(_ffi.lib().va_flow_motion(_ffi.ctx(flow.device.index), _ffi.ptr(flow), N // L, L, int(bool(trajectory)), W, H,
+                                         _ffi.ptr(means), _ffi.ptr(out), _ffi.stream_ptr(flow.device)))
+    return out.view(N, 2, H, W)
+
+
+def apply_motion(flow, flow_count, motion="stack", mean_flow=False, out=None):
+    """The float array S9 / S10 read for the given motion options (checked by ``check_motion``): ``flow`` itself for
+    plain or bi-directional stacking without means (no kernel, no buffer), else ``motion_field`` of it (into ``out``)."""
+    if motion != "trajectory" and not mean_flow:
+        return flow
+    means = flow_field_means(flow) if mean_flow else None
+    return motion_field(flow, flow_count, trajectory=motion == "trajectory", means=means, out=out)
+
 def pyramid_sizes(w, h, params=None):
     p = params if params is not None else _ffi.default_tvl1_params()
     ws = (ctypes.c_int * 16)()

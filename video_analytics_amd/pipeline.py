@@ -38,13 +38,19 @@ class TwoStreamPipeline(object):
     batch i, so batch i's flow quantisation and temporal CNN (which can only start when its last flow is done) run
     beside batch i + 1's TV-L1 instead of holding the TV-L1 streams idle (12 ms of a 140 ms step in round 1).
     ``run_batch()`` = ``submit()`` + ``wait()``: the unpipelined form, same results bit for bit.
-    Buffers that cross streams (flow, flow volume) are owned by the pipeline, ``depth`` of each, guarded by events."""
+    Buffers that cross streams (flow, flow volume) are owned by the pipeline, ``depth`` of each, guarded by events.
+
+    ``motion`` / ``mean_flow``: the temporal model's input representation (``flow.MOTIONS``), applied
+    to every batch that comes with gray frames.  Bi-directional flow reorders the gray frames on the caller's stream; the
+    means and the trajectory resampling run on the CNN stream into a pipeline-owned full-frame buffer."""
 
     def __init__(self, device=None, spatial_seed=1, temporal_seed=2, flow_count=VIDEO_INPUT_FLOW_COUNT,
-                 tvl1_params=None, weights=None, flow_streams=2, cnn_dtype="f32", depth=2):
+                 tvl1_params=None, weights=None, flow_streams=2, cnn_dtype="f32", depth=2, motion="stack", mean_flow=False):
+        vflow.check_motion(motion, mean_flow, flow_count, "TwoStreamPipeline")
         dev = torch.device("cuda", torch.cuda.current_device() if device is None else device)
         self.device = dev
         self.L = flow_count
+        self.motion, self.mean_flow = motion, mean_flow
         with torch.cuda.device(dev):
             ws = weights[0] if weights else build_stream_weights(3, spatial_seed, dev)
             wt = weights[1] if weights else build_stream_weights(2 * flow_count, temporal_seed, dev)
@@ -61,6 +67,7 @@ class TwoStreamPipeline(object):
         self._n = 0
         self._flow = [None] * self.depth      # per slot: flow [pairs,2,H,W] written by the TV-L1 streams
         self._stack = [None] * self.depth     # per slot: flow volume read by the temporal CNN
+        self._motion = [None] * self.depth    # per slot: the motion field S9 / S10 read instead of the flow (S12)
         self._flow_read = [None] * self.depth  # per slot: event "the flow buffer has been quantised" (it may be overwritten)
         self._handed_out = []                 # output tensors allocated on the CNN stream since the last wait()
         self._retired = []                    # dropped cross-stream buffers + the events after which they may be freed
@@ -71,11 +78,26 @@ class TwoStreamPipeline(object):
         B, F, H, W = gray.shape
         if F != self.L + 1:
             raise ValueError("flow_volume: need %d gray frames per clip, got %d" % (self.L + 1, F))
+        tv = self._tvl1_frames(gray)
         if self.flow_streams > 1:
-            fl = vflow.tvl1_flow_concurrent(gray, self.tvl1_params, self.flow_streams)
+            fl = vflow.tvl1_flow_concurrent(tv, self.tvl1_params, self.flow_streams)
         else:
-            fl = vflow.tvl1_flow(gray, self.tvl1_params)
+            fl = vflow.tvl1_flow(tv, self.tvl1_params)
+        fl = vflow.apply_motion(fl, self.L, self.motion, self.mean_flow)
         return vflow.flow_to_stack(fl).view(B, 2 * self.L, H, W)
+
+    def _tvl1_frames(self, gray):
+        """The TV-L1 input of gray ``[B,L+1,H,W]``: the frames themselves, or with bi-directional flow the forward and
+        backward sequences ``[2B,L/2+1,H,W]`` (S13), reordered on the current stream."""
+        return vflow.bidirectional_sequences(gray) if self.motion == "bidirectional" else gray
+
+    def _motion_field(self, flow, k):
+        """On the CNN stream, after the TV-L1 events: the array S9 / S10 read -- the flow itself, or the
+        motion field in slot k's buffer."""
+        if self.motion != "trajectory" and not self.mean_flow:
+            return flow
+        return vflow.apply_motion(flow, self.L, self.motion, self.mean_flow,
+                                  out=self._buffer(self._motion, k, tuple(flow.shape)))
 
     def _buffer(self, bank, k, shape):
         """Slot k's buffer, re-allocated when the batch shape changes (a ragged last batch).  The buffers are allocated on
@@ -151,7 +173,11 @@ class TwoStreamPipeline(object):
         through every view of its stream (ten-crop evaluation).  ``logits_*`` / ``desc_*`` are then the
         view means ``[B,...]`` and ``logits_*_views`` / ``desc_*_views`` hold the per-view outputs ``[B,V,...]``.  Not
         with ``crops=`` or ``flow_stack=``.  ``invert_flow_x``: TSN flips, a mirrored x-flow image becomes
-        ``q -> 255 - q`` (with ``views=`` or ``crops=``; the default mirrors without inverting, as the reference)."""
+        ``q -> 255 - q`` (with ``views=`` or ``crops=``; the default mirrors without inverting, as the reference).
+        The pipeline's ``motion`` / ``mean_flow`` apply with and without ``crops=`` / ``views=``; they need gray frames."""
+        if flow_stack is not None and (self.motion != "stack" or self.mean_flow):
+            raise ValueError("submit: motion=%r / mean_flow=%r need gray frames; flow_stack= is already quantised"
+                             % (self.motion, self.mean_flow))
         if views is not None:
             if crops is not None:
                 raise ValueError("submit: views= and crops= exclude each other")
@@ -160,8 +186,11 @@ class TwoStreamPipeline(object):
         if invert_flow_x and flow_stack is not None:
             raise ValueError("submit: invert_flow_x needs gray frames; flow_stack= is already quantised")
         rgb_crops, flow_crops = self._check_inputs(rgb, gray, flow_stack, crops)
+        if flow_stack is None and gray.shape[1] != self.L + 1:
+            raise ValueError("submit: need %d gray frames per clip, got %d" % (self.L + 1, gray.shape[1]))
         dev = self.device
         cur = torch.cuda.current_stream(dev)
+        tv = self._tvl1_frames(gray) if flow_stack is None else None
         ready = torch.cuda.Event()
         ready.record(cur)  # the inputs are complete here; nothing below makes `cur` wait for anything
         k = self._n % self.depth
@@ -169,10 +198,8 @@ class TwoStreamPipeline(object):
         flow = evs = None
         if flow_stack is None:
             B, F, H, W = gray.shape
-            if F != self.L + 1:
-                raise ValueError("submit: need %d gray frames per clip, got %d" % (self.L + 1, F))
             fbuf = self._buffer(self._flow, k, (B * self.L, 2, H, W))
-            flow, evs = vflow.tvl1_flow_concurrent(gray, self.tvl1_params, self.flow_streams, out=fbuf,
+            flow, evs = vflow.tvl1_flow_concurrent(tv, self.tvl1_params, self.flow_streams, out=fbuf,
                                                    after=[ready, self._flow_read[k]], join=False)
         with torch.cuda.stream(self._cnn):
             self._cnn.wait_event(ready)
@@ -182,15 +209,16 @@ class TwoStreamPipeline(object):
                 for ev in evs:
                     self._cnn.wait_event(ev)
                 B, F, H, W = gray.shape
+                src = self._motion_field(flow, k)
                 if flow_crops is None:
-                    stack = vflow.flow_to_stack(flow, out=self._buffer(self._stack, k, (B, 2 * self.L, H, W)))
+                    stack = vflow.flow_to_stack(src, out=self._buffer(self._stack, k, (B, 2 * self.L, H, W)))
                 else:  # the flow buffer is full-frame, the volume 224x224
-                    stack = vflow.crop_flow_to_stack(flow, flow_crops,
+                    stack = vflow.crop_flow_to_stack(src, flow_crops,
                                                      out=self._buffer(self._stack, k, (B, 2 * self.L, 224, 224)),
                                                      invert_x_on_flip=bool(invert_flow_x))
                 done = torch.cuda.Event()
                 done.record(self._cnn)
-                self._flow_read[k] = done
+                self._flow_read[k] = done  # after the motion kernel and the gather: both have read the flow
                 if self._t_done is not None:
                     self._cnn.wait_event(self._t_done)
                 _, desc_t, logits_t = self.temporal.forward(stack)
@@ -219,16 +247,17 @@ class TwoStreamPipeline(object):
     def _submit_views(self, rgb, gray, rgb_views, flow_views, invert):
         """``submit(views=)``: the stream layout of the crops= path, with B*V images per stream and the view means."""
         dev = self.device
+        B, F, H, W = gray.shape
+        if F != self.L + 1:
+            raise ValueError("submit: need %d gray frames per clip, got %d" % (self.L + 1, F))
         cur = torch.cuda.current_stream(dev)
+        tv = self._tvl1_frames(gray)
         ready = torch.cuda.Event()
         ready.record(cur)
         k = self._n % self.depth
         self._n += 1
-        B, F, H, W = gray.shape
-        if F != self.L + 1:
-            raise ValueError("submit: need %d gray frames per clip, got %d" % (self.L + 1, F))
         fbuf = self._buffer(self._flow, k, (B * self.L, 2, H, W))
-        flow, evs = vflow.tvl1_flow_concurrent(gray, self.tvl1_params, self.flow_streams, out=fbuf,
+        flow, evs = vflow.tvl1_flow_concurrent(tv, self.tvl1_params, self.flow_streams, out=fbuf,
                                                after=[ready, self._flow_read[k]], join=False)
         with torch.cuda.stream(self._cnn):
             self._cnn.wait_event(ready)
@@ -237,11 +266,12 @@ class TwoStreamPipeline(object):
             for ev in evs:
                 self._cnn.wait_event(ev)
             Vt = flow_views.shape[0]
-            stack = vflow.crop_flow_to_stack_views(flow, flow_views, self.L, invert_x_on_flip=invert,
+            src = self._motion_field(flow, k)
+            stack = vflow.crop_flow_to_stack_views(src, flow_views, self.L, invert_x_on_flip=invert,
                                                    out=self._buffer(self._stack, k, (B, Vt, 2 * self.L, 224, 224)))
             done = torch.cuda.Event()
             done.record(self._cnn)
-            self._flow_read[k] = done
+            self._flow_read[k] = done  # after the motion kernel and the gather
             if self._t_done is not None:
                 self._cnn.wait_event(self._t_done)
             desc_t, logits_t, desc_tv, logits_tv = self.temporal.forward_views(stack)

@@ -26,6 +26,10 @@
  *   va_flow_to_stack_views, va_crop_images_u8_views, va_view_mean   ten-crop evaluation (the test protocol of the
  *                     two-stream paper; no reference counterpart): V crop-and-flip views of every clip and the mean of
  *                     the per-view outputs.
+ *   va_flow_to_stack_snippets, va_score_consensus, va_fuse_scores   whole-video evaluation (the test protocols the
+ *                     reference's notes state, Sheet03/notes.txt:113-116 and 225-230: 25 snippets of a video, ten crops
+ *                     of each, class scores averaged; fusion by averaging, notes.txt:121-124; no reference code):
+ *                     DESIGN.md S14-S16.
  *   va_flow_field_means, va_flow_motion   mean flow subtraction and trajectory stacking, two of the temporal-ConvNet
  *                     inputs of the two-stream paper (no reference counterpart).
  *   va_validate_batch the loss / argmax / correct-count lines of validate():
@@ -275,6 +279,20 @@ int va_crop_images_u8_views(va_ctx* ctx, const void* src, int n, int c, int w, i
 int va_view_mean(va_ctx* ctx, const void* x, int n, int n_views, int d, void* out, void* stream);
 
 /*
+ * The flow volumes of the snippets of ONE video (the 25 equally spaced flow stacks of
+ * Sheet03/notes.txt:113-116,225-230): flow f32 [n_pairs][2][h][w], the video's flow fields, each computed once ->
+ * stack f32 [n_snippets][n_views][2*flow_count][out_h][out_w].  Snippet s is the window of L = flow_count fields that
+ * starts at field starts[s]; windows may overlap and repeat.  Output plane o = (s*n_views + v)*2L + c reads source plane
+ * 2*(starts[s] + c/2) + c%2 through crops row o, with the quantisation, normalisation, flip and inversion of
+ * va_flow_to_stack_views: with starts[s] = s*L the two entry points give the same bits.  starts: DEVICE int32
+ * [n_snippets], clamped to [0, n_pairs - L] on the device (callers validate it on the host); crops: DEVICE int32
+ * [n_snippets*n_views*2L][3].  n_pairs >= flow_count; the other limits are va_flow_to_stack_views'.
+ */
+int va_flow_to_stack_snippets(va_ctx* ctx, const void* flow, int n_pairs, const void* starts, int n_snippets,
+                              int flow_count, int n_views, int w, int h, float bound, float mean, float stdv,
+                              const void* crops, int invert_x_on_flip, int out_w, int out_h, void* stack, void* stream);
+
+/*
  * Mean flow subtraction, step one: flow f32 [n_pairs][2][h][w] -> means f32 [n_pairs][2], the mean of
  * every displacement field's component over the full frame.  Each value is clamped to [-32768, 32768] (a NaN becomes
  * -32768) and summed as the exact integer rint(a * 65536) in int64, so the result does not depend on the reduction
@@ -364,6 +382,29 @@ int va_meter_average(va_ctx* ctx, const void* sums, const void* counts, int n_sl
 int va_linear_svm_predict(va_ctx* ctx, const void* x, int n, int dim, const void* coef,
                           const void* intercept, int n_class_rows, void* scores, void* pred,
                           void* stream);
+
+/*
+ * The consensus over the k items (snippets x views, snippet-major) of each of n videos:
+ * logits f32 [n][k][c] -> scores f32 [n][c], one launch for all videos.
+ *   mode 0 ("softmax"; Simonyan and Zisserman's testing, Sheet03/notes.txt:113-116): per item
+ *          p_j = exp(x_j - max_j x) / sum_j exp(x_j - max_j x) in f32, then ((p_0 + p_1) + ...) + p_{k-1} in item order
+ *          and one division by (float)k, as va_view_mean.
+ *   mode 1 ("logits"; TSN's H(G(...)), notes.txt:176-185): the mean of the logits in item order, then one softmax.
+ * No atomics: the result does not depend on scheduling.  A NaN logit makes the scores of its video NaN.
+ * k <= 4096, c <= 4096.
+ */
+int va_score_consensus(va_ctx* ctx, const void* logits, int n, int k, int c, int mode, void* scores, void* stream);
+
+/*
+ * Fusion of the two streams' scores by weighted averaging (Sheet03/notes.txt:121-124; TSN's weighting,
+ * notes.txt:225-230): a, b f32 [n][c] -> fused f32 [n][c] = (wa*a + wb*b) / (wa + wb), every operation rounded to f32,
+ * and pred i32 [n], the arg-max of fused with the first maximum winning (as va_validate_batch and
+ * va_linear_svm_predict).  wa = wb = 1 is plain averaging, (1, 1.5) TSN's spatial : temporal weighting.
+ * wa, wb >= 0 and wa + wb > 0, else VA_ERR_INVALID.  (Fusion by a linear SVM on the stacked scores [n][2c] or on the
+ * joined descriptors [n][512] is va_linear_svm_predict.)
+ */
+int va_fuse_scores(va_ctx* ctx, const void* a, const void* b, int n, int c, float wa, float wb, void* fused, void* pred,
+                   void* stream);
 
 /* ------------------------------------------------------------------ training step --- */
 

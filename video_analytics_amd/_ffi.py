@@ -22,6 +22,7 @@ EXPORTS = [
     "va_flow_to_stack", "va_flow_to_stack_crop", "va_crop_images_u8",
     "va_flow_to_stack_views", "va_crop_images_u8_views", "va_view_mean", "va_flow_field_means", "va_flow_motion",
     "va_selftest_exact_math", "va_tvl1_profile_enable", "va_tvl1_profile_read", "va_tvl1_profile_levels",
+    "va_flow_to_stack_snippets", "va_score_consensus", "va_fuse_scores",
     "va_meter_update", "va_meter_average", "va_linear_svm_predict",
     "va_vgg16_train_init", "va_vgg16_train_workspace_bytes", "va_vgg16_train_step",
     "va_vgg16_export_state", "va_vgg16_import_state", "va_vgg16_train_plan",
@@ -133,6 +134,12 @@ def lib():
     L.va_flow_to_stack_views.restype = ci
     L.va_crop_images_u8_views.argtypes = [vp, vp, ci, ci, ci, ci, ci, ci, vp, ci, ci, vp, vp]
     L.va_crop_images_u8_views.restype = ci
+    L.va_flow_to_stack_snippets.argtypes = [vp, vp, ci, vp, ci, ci, ci, ci, ci, cf, cf, cf, vp, ci, ci, ci, vp, vp]
+    L.va_flow_to_stack_snippets.restype = ci
+    L.va_score_consensus.argtypes = [vp, vp, ci, ci, ci, ci, vp, vp]
+    L.va_score_consensus.restype = ci
+    L.va_fuse_scores.argtypes = [vp, vp, vp, ci, ci, cf, cf, vp, vp, vp]
+    L.va_fuse_scores.restype = ci
     L.va_view_mean.argtypes = [vp, vp, ci, ci, ci, vp, vp]
     L.va_view_mean.restype = ci
     L.va_flow_field_means.argtypes = [vp, vp, ci, ci, ci, vp, vp]

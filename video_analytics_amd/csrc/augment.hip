@@ -40,7 +40,16 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 constexpr int kGatherSteps = 4;
 constexpr int kGatherPerBlock = 256 * 4 * kGatherSteps;
 
+//
+// SNIPPETS (S15, va_flow_to_stack_snippets): clip b is snippet b of ONE video of n_pairs flow fields and its window starts
+// at pair starts[b] (clamped to [0, n_pairs - L]), so that output plane o reads source plane 2*(starts[b] + c/2) + c%2 =
+// 2*starts[b] + c: windows that overlap in the source instead of n copies of the flow.  The block order is the same,
+// snippet-major with the V views of a plane adjacent; a plane that the next snippet reads again was last read one
+// snippet earlier, i.e. 2L full-frame planes (6 MB at 320x240) and V*2L streamed output planes (40 MB) ago: those re-reads
+// come from the Infinity Cache, the V re-reads within a snippet from L2.  Everything after the plane's address is shared.
+template <bool SNIPPETS>
 __global__ void __launch_bounds__(256) k_flow_crop_stack(const float* __restrict__ flow, const int* __restrict__ crops,
+                                                         const int* __restrict__ starts, int n_pairs,
                                                          float* __restrict__ stack, int w, int h, int out_w, int out_h,
                                                          int chans, int n_views, int invert_x, int vec4, float bound,
                                                          float mean, float stdv)
@@ -51,7 +60,8 @@ __global__ void __launch_bounds__(256) k_flow_crop_stack(const float* __restrict
     const int n = out_w * out_h;
     const CropWin cw = load_crop(crops, o, h, w, out_h, out_w);
     const bool inv = invert_x && cw.flip && (c & 1) == 0;
-    const float* __restrict__ plane = flow + (size_t)src * h * w + (size_t)cw.top * w;
+    const int splane = SNIPPETS ? 2 * min(max(starts[b], 0), n_pairs - chans / 2) + c : src;
+    const float* __restrict__ plane = flow + (size_t)splane * h * w + (size_t)cw.top * w;
     float* __restrict__ dst = stack + (size_t)o * n;
     // vec4 bit 1: 16-byte aligned flow, w and out_w multiples of 4; with a left offset of 4k too, every run of 4 outputs
     // (never split between rows) reads one aligned float4
@@ -161,13 +171,17 @@ static int check_flow_gather(const char* who, const void* flow, const void* crop
 
 static void launch_flow_gather(const float* flow, const int* crops, float* stack, int w, int h, int out_w, int out_h,
                                int chans, int planes, int n_views, int invert_x, float bound, float mean, float stdv,
-                               hipStream_t stream)
+                               hipStream_t stream, const int* starts = nullptr, int n_pairs = 0)
 {
     const dim3 g((unsigned)va_cdiv(out_w * out_h, kGatherPerBlock), (unsigned)planes);
     const int vec4 = ((out_w * out_h) % 4 == 0 && reinterpret_cast<uintptr_t>(stack) % 16 == 0 ? 1 : 0) |
                      (w % 4 == 0 && out_w % 4 == 0 && reinterpret_cast<uintptr_t>(flow) % 16 == 0 ? 2 : 0);
-    k_flow_crop_stack<<<g, 256, 0, stream>>>(flow, crops, stack, w, h, out_w, out_h, chans, n_views, invert_x, vec4, bound,
-                                             mean, stdv);
+    if (starts)
+        k_flow_crop_stack<true><<<g, 256, 0, stream>>>(flow, crops, starts, n_pairs, stack, w, h, out_w, out_h, chans, n_views,
+                                                       invert_x, vec4, bound, mean, stdv);
+    else
+        k_flow_crop_stack<false><<<g, 256, 0, stream>>>(flow, crops, nullptr, 0, stack, w, h, out_w, out_h, chans, n_views,
+                                                        invert_x, vec4, bound, mean, stdv);
 }
 
 extern "C" int va_flow_to_stack_crop(va_ctx* ctx, const void* flow, int n_pairs, int w, int h, float bound, float mean,
@@ -198,6 +212,27 @@ extern "C" int va_flow_to_stack_views(va_ctx* ctx, const void* flow, int n_clips
     if (rc != VA_OK) return rc;
     launch_flow_gather((const float*)flow, (const int*)crops, (float*)stack, w, h, out_w, out_h, 2 * flow_count,
                        (int)planes, n_views, invert_x_on_flip, bound, mean, stdv, (hipStream_t)stream);
+    VA_LAUNCH_CHECK();
+    return VA_OK;
+}
+
+extern "C" int va_flow_to_stack_snippets(va_ctx* ctx, const void* flow, int n_pairs, const void* starts, int n_snippets,
+                                         int flow_count, int n_views, int w, int h, float bound, float mean, float stdv,
+                                         const void* crops, int invert_x_on_flip, int out_w, int out_h, void* stack,
+                                         void* stream)
+{
+    VA_CHECK_ARG(ctx != nullptr, "va_flow_to_stack_snippets: ctx is NULL");
+    VA_USE_DEVICE(ctx);
+    VA_CHECK_ARG(n_snippets >= 1 && flow_count >= 1 && n_views >= 1, "va_flow_to_stack_snippets: bad shape");
+    VA_CHECK_ARG(n_pairs >= flow_count && n_pairs <= 0x3fffffff, "va_flow_to_stack_snippets: %d flow pairs do not hold a window of %d",
+                 n_pairs, flow_count);
+    VA_CHECK_ARG(starts != nullptr, "va_flow_to_stack_snippets: NULL buffer");
+    VA_CHECK_ARG(invert_x_on_flip == 0 || invert_x_on_flip == 1, "va_flow_to_stack_snippets: invert_x_on_flip must be 0 or 1");
+    const long long planes = (long long)n_snippets * n_views * 2 * flow_count;
+    const int rc = check_flow_gather("va_flow_to_stack_snippets", flow, crops, stack, planes, w, h, out_w, out_h, bound, stdv);
+    if (rc != VA_OK) return rc;
+    launch_flow_gather((const float*)flow, (const int*)crops, (float*)stack, w, h, out_w, out_h, 2 * flow_count, (int)planes,
+                       n_views, invert_x_on_flip, bound, mean, stdv, (hipStream_t)stream, (const int*)starts, n_pairs);
     VA_LAUNCH_CHECK();
     return VA_OK;
 }

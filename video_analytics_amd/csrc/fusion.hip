@@ -1,6 +1,8 @@
 // Video-level aggregation and two-stream fusion on the device:
 // the AverageMeter bank of validate() (Sheet03/utils.py:154-171, Sheet03/spatialModel.py:223-228)
-// and LinearSVC.predict of the fusion step (Sheet03/combinedModel.py:38).  Both are small,
+// and LinearSVC.predict of the fusion step (Sheet03/combinedModel.py:38); the consensus over a video's snippets and
+// views and the weighted average of the two streams' scores (the test protocols of
+// Sheet03/notes.txt:113-116,121-124,225-230).  All are small,
 // HBM/latency-bound byte-and-index work: plain coalesced kernels, no MFMA.
 #include "va_internal.h"
 
@@ -65,7 +67,129 @@ __global__ void k_svm_argmax(const double* __restrict__ scores, int N, int C, in
     pred[n] = am;
 }
 
+// Wave-wide max and sum over 64 lanes as xor butterflies (offsets 32, 16, ..., 1): every lane ends with the same bits, and
+// the order of the additions is fixed by the lane numbers, not by scheduling.  fmaxf skips NaNs; the sums carry them.
+__device__ __forceinline__ float wave_max(float v)
+{
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
+    return v;
+}
+
+__device__ __forceinline__ float wave_sum(float v)
+{
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) v = v + __shfl_xor(v, off, 64);
+    return v;
+}
+
+// The softmax terms of one row x[0..c) for a whole wave: m = max_j x_j and s = sum_j exp(x_j - m), lane l adding its
+// classes l, l + 64, ... in ascending order before the butterfly.  A NaN in the row makes s NaN (exp(NaN - m)); a row of
+// -inf or one holding +inf makes it NaN too (inf - inf).
+__device__ __forceinline__ void wave_softmax_terms(const float* __restrict__ x, int c, int lane, float& m, float& s)
+{
+    float mx = -INFINITY;
+    for (int j = lane; j < c; j += 64) mx = fmaxf(mx, x[j]);
+    m = wave_max(mx);
+    float acc = 0.0f;
+    for (int j = lane; j < c; j += 64) acc = acc + expf(x[j] - m);
+    s = wave_sum(acc);
+}
+
+// S16, the consensus of one video per workgroup: logits [n][k][c] -> scores [n][c].
+//   mode 0: phase one, wave per item (items wave, wave + 4, ...): the item's max and exp-sum into LDS; phase two, thread per
+//           class (classes t, t + 256, ...): acc = p_0 + p_1 + ... in item order with p_i = exp(x_ij - m_i) / s_i, then
+//           acc / (float)k.
+//   mode 1: thread per class: the mean of the logits in item order into LDS, then every wave computes the one softmax's
+//           max and sum for itself (the same bits in all four) and the threads write exp(mean_j - m) / s.
+// LDS: 2k floats (m, s) followed by c floats (the mean logits).  No atomics.
+__global__ void __launch_bounds__(256) k_score_consensus(const float* __restrict__ logits, int k, int c, int mode,
+                                                         float* __restrict__ scores)
+{
+    extern __shared__ float lds[];
+    const float* __restrict__ x = logits + (size_t)blockIdx.x * k * c;
+    float* __restrict__ out = scores + (size_t)blockIdx.x * c;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (mode == 0) {
+        float* im = lds;
+        float* is = lds + k;
+        for (int i = wave; i < k; i += 4) {
+            float m, s;
+            wave_softmax_terms(x + (size_t)i * c, c, lane, m, s);
+            if (lane == 0) im[i] = m, is[i] = s;
+        }
+        __syncthreads();
+        for (int j = threadIdx.x; j < c; j += 256) {
+            float acc = expf(x[j] - im[0]) / is[0];
+            for (int i = 1; i < k; ++i) acc = acc + expf(x[(size_t)i * c + j] - im[i]) / is[i];
+            out[j] = acc / (float)k;
+        }
+    } else {
+        float* mean = lds + 2 * k;
+        for (int j = threadIdx.x; j < c; j += 256) {
+            float acc = x[j];
+            for (int i = 1; i < k; ++i) acc = acc + x[(size_t)i * c + j];
+            mean[j] = acc / (float)k;
+        }
+        __syncthreads();
+        float m, s;
+        wave_softmax_terms(mean, c, lane, m, s);
+        for (int j = threadIdx.x; j < c; j += 256) out[j] = expf(mean[j] - m) / s;
+    }
+}
+
+// S16, the fusion of one video per workgroup: fused = (wa*a + wb*b) / (wa + wb), each operation rounded to f32; thread 0
+// then walks the classes as k_svm_argmax does (strict >, so the first maximum wins), recomputing the same expression.
+__global__ void __launch_bounds__(256) k_fuse_scores(const float* __restrict__ a, const float* __restrict__ b, int c, float wa,
+                                                     float wb, float* __restrict__ fused, int* __restrict__ pred)
+{
+    const float* __restrict__ pa = a + (size_t)blockIdx.x * c;
+    const float* __restrict__ pb = b + (size_t)blockIdx.x * c;
+    const float wsum = wa + wb;
+    for (int j = threadIdx.x; j < c; j += 256) fused[(size_t)blockIdx.x * c + j] = (wa * pa[j] + wb * pb[j]) / wsum;
+    if (threadIdx.x == 0) {
+        float mx = (wa * pa[0] + wb * pb[0]) / wsum;
+        int am = 0;
+        for (int j = 1; j < c; ++j) {
+            const float f = (wa * pa[j] + wb * pb[j]) / wsum;
+            if (f > mx) { mx = f; am = j; }
+        }
+        pred[blockIdx.x] = am;
+    }
+}
+
 }  // namespace
+
+static constexpr int kConsensusMaxItems = 4096, kConsensusMaxClasses = 4096;  // (2k + c) floats of LDS: at most 48 KB
+
+extern "C" int va_score_consensus(va_ctx* ctx, const void* logits, int n, int k, int c, int mode, void* scores, void* stream)
+{
+    VA_CHECK_ARG(ctx != nullptr, "va_score_consensus: ctx is NULL");
+    VA_USE_DEVICE(ctx);
+    VA_CHECK_ARG(logits && scores, "va_score_consensus: NULL pointer");
+    VA_CHECK_ARG(n >= 1 && k >= 1 && c >= 1 && k <= kConsensusMaxItems && c <= kConsensusMaxClasses,
+                 "va_score_consensus: need n >= 1, 1 <= k <= %d items, 1 <= c <= %d classes (got %d, %d, %d)", kConsensusMaxItems,
+                 kConsensusMaxClasses, n, k, c);
+    VA_CHECK_ARG(mode == 0 || mode == 1, "va_score_consensus: mode must be 0 (softmax) or 1 (logits), got %d", mode);
+    k_score_consensus<<<n, 256, (size_t)(2 * k + c) * sizeof(float), (hipStream_t)stream>>>((const float*)logits, k, c, mode,
+                                                                                            (float*)scores);
+    VA_LAUNCH_CHECK();
+    return VA_OK;
+}
+
+extern "C" int va_fuse_scores(va_ctx* ctx, const void* a, const void* b, int n, int c, float wa, float wb, void* fused, void* pred,
+                              void* stream)
+{
+    VA_CHECK_ARG(ctx != nullptr, "va_fuse_scores: ctx is NULL");
+    VA_USE_DEVICE(ctx);
+    VA_CHECK_ARG(a && b && fused && pred, "va_fuse_scores: NULL pointer");
+    VA_CHECK_ARG(n >= 1 && c >= 1, "va_fuse_scores: need n >= 1 and c >= 1 (got %d, %d)", n, c);
+    VA_CHECK_ARG(wa >= 0.0f && wb >= 0.0f && wa + wb > 0.0f && wa + wb <= 3.0e38f,
+                 "va_fuse_scores: need finite weights >= 0 with a positive sum (got %g, %g)", (double)wa, (double)wb);
+    k_fuse_scores<<<n, 256, 0, (hipStream_t)stream>>>((const float*)a, (const float*)b, c, wa, wb, (float*)fused, (int*)pred);
+    VA_LAUNCH_CHECK();
+    return VA_OK;
+}
 
 extern "C" int va_meter_update(va_ctx* ctx, const void* desc, const void* slot, int batch, int dim, void* sums, void* counts, int n_slots,
                                void* stream)

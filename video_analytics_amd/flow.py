@@ -218,6 +218,47 @@ def crop_flow_to_stack_views(flow, views, flow_count, invert_x_on_flip=False, si
     return out.view(B, V, 2 * L, size, size)
 
 
+def check_starts(starts, n_pairs, flow_count, who):
+    """Host-side validation (ValueError) of snippet starts for ``n_pairs`` flow fields: a CPU int32 ``[n]`` tensor (or a
+    list of ints) with n >= 1 and every start in [0, n_pairs - flow_count] -> the CPU int32 tensor."""
+    if not isinstance(starts, torch.Tensor):
+        try:
+            starts = torch.tensor([int(s) for s in starts], dtype=torch.int32)
+        except (TypeError, ValueError):
+            raise ValueError("%s: starts must be a CPU int32 [n] tensor or a list of ints" % who)
+    if starts.is_cuda or starts.dtype != torch.int32 or starts.dim() != 1 or starts.shape[0] < 1:
+        raise ValueError("%s: starts must be a CPU int32 [n] tensor with n >= 1" % who)
+    if n_pairs < flow_count or bool((starts < 0).any()) or bool((starts > n_pairs - flow_count).any()):
+        raise ValueError("%s: a window of %d pairs starting at %d..%d does not lie in the %d flow fields"
+                         % (who, flow_count, int(starts.min()), int(starts.max()), n_pairs))
+    return starts
+
+
+def crop_flow_to_stack_snippets(flow, starts, views, flow_count, invert_x_on_flip=False, size=224, bound=FLOW_BOUND,
+                                mean=NORM_MEANS_TF[0], std=NORM_STDS_TF[0], out=None):
+    """The flow volumes of the snippets of one video: flow ``[N,2,H,W]`` float32, the video's flow fields
+    each computed once; starts CPU int32 ``[n]`` (or a list), snippet s being the ``flow_count`` = L fields from
+    ``starts[s]`` on (windows may overlap and repeat); views CPU int32 ``[V,3]`` -> ``[n,V,2L,size,size]`` float32,
+    quantised and normalised as ``crop_flow_to_stack_views``: with ``starts = [0, L, 2L, ...]`` the same bits."""
+    from . import augment
+    _check_flow(flow, "crop_flow_to_stack_snippets")
+    N, _, H, W = flow.shape
+    L = int(flow_count)
+    if L < 1:
+        raise ValueError("crop_flow_to_stack_snippets: flow_count must be >= 1, got %d" % L)
+    starts = check_starts(starts, N, L, "crop_flow_to_stack_snippets")
+    augment.check_views(views, H, W, size, "crop_flow_to_stack_snippets")
+    n, V = starts.shape[0], views.shape[0]
+    flow = flow.contiguous()
+    out = _check_out(out, (n, V, 2 * L, size, size), flow, "crop_flow_to_stack_snippets")
+    dcrops = augment.crops_to_device(augment.expand_views(views, n, 2 * L), flow.device)
+    dstarts = augment.crops_to_device(starts, flow.device)
+    _ffi.check(_ffi.lib().va_flow_to_stack_snippets(_ffi.ctx(flow.device.index), _ffi.ptr(flow), N, _ffi.ptr(dstarts), n, L, V,
+                                                    W, H, float(bound), float(mean), float(std), _ffi.ptr(dcrops),
+                                                    int(bool(invert_x_on_flip)), size, size, _ffi.ptr(out),
+                                                    _ffi.stream_ptr(flow.device)))
+    return out.view(n, V, 2 * L, size, size)
+
 
 # The temporal-ConvNet inputs of the two-stream paper (DESIGN.md S11-S13): "stack" is optical-flow stacking (the default and
 # the reference's input), "trajectory" samples the flow along the trajectory that starts at each pixel of the first frame,

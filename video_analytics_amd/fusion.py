@@ -3,7 +3,9 @@
 ``DescriptorMeters`` is the bank of per-video ``AverageMeter`` objects that ``validate()`` fills
 (Sheet03/utils.py:154-171, Sheet03/spatialModel.py:223-228), kept in HBM so that the batch loop
 needs no device-to-host copy; ``linear_svm_predict`` is ``LinearSVC.predict`` of the fusion step
-(Sheet03/combinedModel.py:38) on the joined descriptors.
+(Sheet03/combinedModel.py:38) on the joined descriptors.  ``score_consensus`` and ``fuse_scores`` are the video-level
+half of the papers' test protocol (Sheet03/notes.txt:113-116, 121-124, 225-230): the class scores of a
+video's snippets and views averaged, then the two streams' scores fused by a weighted average.
 """
 import numpy as np
 import torch
@@ -85,9 +87,72 @@ class DescriptorMeters(object):
         return out
 
 
+CONSENSUS_MODES = ("softmax", "logits")
+
+
+def check_consensus(mode, who):
+    if not isinstance(mode, str) or mode not in CONSENSUS_MODES:
+        raise ValueError("%s: consensus must be one of %s, got %r" % (who, ", ".join(CONSENSUS_MODES), mode))
+    return CONSENSUS_MODES.index(mode)
+
+
+def check_fusion_weights(weights, who):
+    """-> (wa, wb) as floats; ValueError unless both are finite, >= 0 and their sum is > 0."""
+    try:
+        wa, wb = (float(w) for w in weights)
+    except (TypeError, ValueError):
+        raise ValueError("%s: fusion weights must be two numbers (spatial, temporal), got %r" % (who, weights))
+    if not (np.isfinite(wa) and np.isfinite(wb)) or wa < 0 or wb < 0 or wa + wb <= 0:
+        raise ValueError("%s: fusion weights must be >= 0 with a positive sum, got (%g, %g)" % (who, wa, wb))
+    return wa, wb
+
+
+def score_consensus(logits, mode="softmax"):
+    """The video score from the class logits of its items (``va_score_consensus``): logits CUDA float32
+    ``[N,k,C]`` -- or ``[N,n,V,C]``, snippets x views, read snippet-major -- -> ``[N,C]`` float32.
+
+    ``"softmax"`` (Simonyan and Zisserman's testing): the softmax of every item, then their mean in item order;
+    ``"logits"`` (TSN's consensus, then the prediction function): the mean of the logits in item order, then one softmax."""
+    m = check_consensus(mode, "score_consensus")
+    if not isinstance(logits, torch.Tensor) or not logits.is_cuda or logits.dtype != torch.float32 or logits.dim() not in (3, 4):
+        raise ValueError("score_consensus: logits must be a CUDA float32 [N,k,C] or [N,n,V,C] tensor")
+    N, C = int(logits.shape[0]), int(logits.shape[-1])
+    k = logits.numel() // max(1, N * C)
+    if N < 1 or k < 1 or C < 1:
+        raise ValueError("score_consensus: empty logits %s" % (tuple(logits.shape),))
+    logits = logits.contiguous()
+    scores = torch.empty((N, C), dtype=torch.float32, device=logits.device)
+    _ffi.check(_ffi.lib().va_score_consensus(_ffi.ctx(logits.device.index), _ffi.ptr(logits), N, k, C, m, _ffi.ptr(scores),
+                                             _ffi.stream_ptr(logits.device)))
+    return scores
+
+
+def fuse_scores(a, b, weights=(1.0, 1.0)):
+    """Two-stream fusion by weighted averaging (``va_fuse_scores``): a, b CUDA float32 ``[N,C]`` ->
+    ``(fused [N,C] float32, pred [N] int32)``, ``fused = (wa*a + wb*b) / (wa + wb)`` and ``pred`` its arg-max with the
+    first maximum winning.  ``(1, 1)`` is the two-stream paper's averaging, ``(1, 1.5)`` TSN's spatial : temporal weights."""
+    wa, wb = check_fusion_weights(weights, "fuse_scores")
+    for t in (a, b):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32 or t.dim() != 2:
+            raise ValueError("fuse_scores: a and b must be CUDA float32 [N,C] tensors")
+    if a.shape != b.shape or a.device != b.device or a.shape[0] < 1 or a.shape[1] < 1:
+        raise ValueError("fuse_scores: a %s and b %s must have one non-empty shape on one device" % (tuple(a.shape), tuple(b.shape)))
+    a, b = a.contiguous(), b.contiguous()
+    N, C = int(a.shape[0]), int(a.shape[1])
+    fused = torch.empty((N, C), dtype=torch.float32, device=a.device)
+    pred = torch.empty((N,), dtype=torch.int32, device=a.device)
+    _ffi.check(_ffi.lib().va_fuse_scores(_ffi.ctx(a.device.index), _ffi.ptr(a), _ffi.ptr(b), N, C, wa, wb, _ffi.ptr(fused),
+                                         _ffi.ptr(pred), _ffi.stream_ptr(a.device)))
+    return fused, pred
+
+
 def linear_svm_predict(descriptors, coef, intercept, classes, device=None, return_scores=False):
     """``LinearSVC.predict`` (Sheet03/combinedModel.py:38): classes[argmax(X coef^T + intercept)]; a single
-    coefficient row is sklearn's binary problem (classes[score > 0]).  Inputs: array-likes (float64)."""
+    coefficient row is sklearn's binary problem (classes[score > 0]).  Inputs: array-likes (float64).
+
+    Any ``dim``: the reference's use is the joined descriptors ``[N,512]`` of ``combineDescriptors``
+    (``video.evaluateVideos`` returns them for whole videos); fusion by an SVM on the streams' scores
+    (Sheet03/notes.txt:124) is the same call on the stacked scores ``[N,2C]``, ``concatenate([scores_s, scores_t], 1)``."""
     if not torch.cuda.is_available():
         raise RuntimeError("linear_svm_predict: no GPU visible; the hot path has no CPU fallback")
     dev = torch.device("cuda", torch.cuda.current_device() if device is None else device)

@@ -12,7 +12,7 @@ forward (Sheet03/spatialModel.py:212-218, Sheet03/temporalModel.py:241-247).
 import torch
 
 from . import flow as vflow
-from . import augment, synth, vgg
+from . import augment, fusion, synth, vgg, video
 from .parameters import (NACTION_CLASSES, NORM_MEANS_TF, NORM_STDS_TF, VIDEO_DESCRIPTOR_DIM,
                          VIDEO_INPUT_FLOW_COUNT)
 
@@ -24,6 +24,42 @@ def build_stream_weights(c_in, seed, device):
     if c_in != 3:
         w["conv_w"][0] = vgg.copy_first_layer(w["conv_w"][0].to(device), c_in)
     return w
+
+
+def check_video(rgb, gray, flow_count, motion, n_snippets, views, consensus, fusion_weights, crops=None):
+    """The host-side checks of ``TwoStreamPipeline.submit_video`` (ValueError; nothing touches the device) ->
+    (plan, rgb_views, flow_views, consensus mode, wa, wb)."""
+    if crops is not None:
+        raise ValueError("submit_video: a video takes views=, not crops= (one table for all its snippets)")
+    if motion != "stack":
+        raise ValueError("submit_video: motion=%r is not offered for whole videos (its chains depend on the window); "
+                         "use motion='stack'" % (motion,))
+    if not isinstance(rgb, torch.Tensor) or rgb.dtype != torch.uint8 or rgb.dim() != 4 or rgb.shape[1] != 3:
+        raise ValueError("submit_video: rgb must be a uint8 [T,3,H,W] tensor")
+    if not isinstance(gray, torch.Tensor) or gray.dim() != 3 or gray.dtype not in (torch.uint8, torch.float32):
+        raise ValueError("submit_video: gray must be a uint8 or float32 [T,H,W] tensor")
+    if gray.shape[0] != rgb.shape[0]:
+        raise ValueError("submit_video: %d rgb frames but %d gray frames" % (rgb.shape[0], gray.shape[0]))
+    mode = fusion.check_consensus(consensus, "submit_video")
+    wa, wb = fusion.check_fusion_weights(fusion_weights, "submit_video")
+    try:
+        plan = video.snippetPlan(int(gray.shape[0]), flow_count, int(n_snippets))
+    except ValueError as e:
+        raise ValueError("submit_video: %s" % e)
+    if views is None:  # one view: the frame itself
+        if tuple(rgb.shape[-2:]) != (224, 224) or tuple(gray.shape[-2:]) != (224, 224):
+            raise ValueError("submit_video: frames of %dx%d need views= (augment.ten_crop_views)" % (rgb.shape[-1], rgb.shape[-2]))
+        rgb_views = flow_views = torch.zeros((1, 3), dtype=torch.int32)
+    else:
+        if not isinstance(views, (tuple, list)) or len(views) != 2:
+            raise ValueError("submit_video: views= must be (rgb_views, flow_views), e.g. two augment.ten_crop_views tables")
+        rgb_views, flow_views = views
+        augment.check_views(rgb_views, rgb.shape[2], rgb.shape[3], augment.CROP_SIZE, "submit_video(views=)")
+        augment.check_views(flow_views, gray.shape[1], gray.shape[2], augment.CROP_SIZE, "submit_video(views=)")
+    for v in (rgb_views, flow_views):
+        if v.shape[0] > vgg.Vgg16Stream.VIEW_CHUNK:
+            raise ValueError("submit_video: at most %d views, got %d" % (vgg.Vgg16Stream.VIEW_CHUNK, v.shape[0]))
+    return plan, rgb_views, flow_views, mode, wa, wb
 
 
 class TwoStreamPipeline(object):
@@ -39,6 +75,9 @@ class TwoStreamPipeline(object):
     beside batch i + 1's TV-L1 instead of holding the TV-L1 streams idle (12 ms of a 140 ms step in round 1).
     ``run_batch()`` = ``submit()`` + ``wait()``: the unpipelined form, same results bit for bit.
     Buffers that cross streams (flow, flow volume) are owned by the pipeline, ``depth`` of each, guarded by events.
+
+    ``submit_video()`` / ``run_video()`` classify a whole video on the same streams: its snippets share
+    one TV-L1 pass over the frame pairs they need, and the scores of snippets and views are averaged and fused on the device.
 
     ``motion`` / ``mean_flow``: the temporal model's input representation (``flow.MOTIONS``), applied
     to every batch that comes with gray frames.  Bi-directional flow reorders the gray frames on the caller's stream; the
@@ -283,6 +322,87 @@ class TwoStreamPipeline(object):
                    logits_t_views=logits_tv, desc_s_views=desc_sv, desc_t_views=desc_tv)
         self._handed_out.extend(out.values())
         out["done"] = finished
+        return out
+
+    def _check_video(self, rgb, gray, n_snippets, views, consensus, fusion_weights, crops):
+        """Host-side checks of ``submit_video`` before anything is enqueued -> (plan, rgb_views, flow_views, mode, wa, wb)."""
+        checked = check_video(rgb, gray, self.L, self.motion, n_snippets, views, consensus, fusion_weights, crops)
+        if not rgb.is_cuda or not gray.is_cuda or rgb.device != self.device or gray.device != self.device:
+            raise ValueError("submit_video: rgb and gray must be on %s" % (self.device,))
+        return checked
+
+    def submit_video(self, rgb, gray, n_snippets=video.N_SNIPPETS, views=None, invert_flow_x=False, consensus="softmax",
+                     fusion_weights=(1.0, 1.0), crops=None):
+        """Enqueue one whole video (the test protocol of Sheet03/notes.txt:113-116 and 225-230):
+        rgb u8 ``[T,3,H,W]``, gray u8 or f32 ``[T,H,W]``, the frames of one video on the device.  ``n_snippets`` snippets
+        are placed by ``video.snippetStarts``; the frame pairs they share go through TV-L1 once each
+        (``video.snippetPlan``), every snippet is seen through every view, and the class scores are averaged over snippets
+        and views (``consensus``: ``"softmax"`` or ``"logits"``, ``fusion.score_consensus``) and fused with
+        ``fusion_weights`` = (spatial, temporal) (``fusion.fuse_scores``).
+
+        ``views=(rgb_views, flow_views)`` as in ``submit(views=)``; None is one view of 224x224 frames.  Returns a dict of
+        tensors the CNN stream is still writing (``wait()`` first): ``scores_s``, ``scores_t``, ``scores`` f32 ``[C]``,
+        ``pred`` int32 ``[]``, ``desc_s``, ``desc_t`` f32 ``[256]`` (the mean over snippets and views in item order),
+        ``logits_s_items``, ``logits_t_items`` ``[n,V,C]``, and ``starts`` (the snippets' first pairs, a list), ``plan``,
+        ``done``.  The stream layout is ``submit(views=)``'s: the TV-L1 of the next video queues behind this one's.
+        ``mean_flow=True`` subtracts every planned field's own mean; trajectory and bi-directional pipelines raise
+        ValueError, as do bad shapes, a video shorter than one snippet and ``crops=``, before anything is enqueued."""
+        plan, rgb_views, flow_views, mode, wa, wb = self._check_video(rgb, gray, n_snippets, views, consensus, fusion_weights,
+                                                                      crops)
+        dev = self.device
+        n, U = plan.n, len(plan.pairs)
+        T, H, W = gray.shape
+        cur = torch.cuda.current_stream(dev)
+        seq = augment.crops_to_device(torch.tensor(plan.sequences, dtype=torch.int64), dev)
+        tv = gray[seq]                                                     # [U,2,H,W]: one two-frame sequence per planned pair
+        frames = rgb[augment.crops_to_device(torch.tensor(plan.starts, dtype=torch.int64), dev)]  # [n,3,H,W]
+        ready = torch.cuda.Event()
+        ready.record(cur)
+        k = self._n % self.depth
+        self._n += 1
+        fbuf = self._buffer(self._flow, k, (U, 2, H, W))
+        flow, evs = vflow.tvl1_flow_concurrent(tv, self.tvl1_params, self.flow_streams, out=fbuf,
+                                               after=[ready, self._flow_read[k]], join=False)
+        with torch.cuda.stream(self._cnn):
+            self._cnn.wait_event(ready)
+            frames.record_stream(self._cnn)
+            _, _, desc_sv, logits_sv = self.spatial.forward_views(augment.crop_image_views(frames, rgb_views))
+            for ev in evs:
+                self._cnn.wait_event(ev)
+            Vt = flow_views.shape[0]
+            src = flow
+            if self.mean_flow:  # S11 / S12 per planned field: no chains, so the clip length does not matter
+                src = vflow.apply_motion(flow, 1, "stack", True, out=self._buffer(self._motion, k, tuple(flow.shape)))
+            stack = vflow.crop_flow_to_stack_snippets(src, plan.index, flow_views, self.L, invert_x_on_flip=bool(invert_flow_x),
+                                                      out=self._buffer(self._stack, k, (n, Vt, 2 * self.L, 224, 224)))
+            done = torch.cuda.Event()
+            done.record(self._cnn)
+            self._flow_read[k] = done
+            if self._t_done is not None:
+                self._cnn.wait_event(self._t_done)
+            _, _, desc_tv, logits_tv = self.temporal.forward_views(stack)
+            self._t_done = torch.cuda.Event()
+            self._t_done.record(self._cnn)
+            scores_s = fusion.score_consensus(logits_sv.unsqueeze(0), consensus)
+            scores_t = fusion.score_consensus(logits_tv.unsqueeze(0), consensus)
+            scores, pred = fusion.fuse_scores(scores_s, scores_t, (wa, wb))
+            desc_s = vgg.view_mean(desc_sv.view(1, -1, desc_sv.shape[-1]))
+            desc_t = vgg.view_mean(desc_tv.view(1, -1, desc_tv.shape[-1]))
+            finished = torch.cuda.Event()
+            finished.record(self._cnn)
+        out = dict(scores_s=scores_s[0], scores_t=scores_t[0], scores=scores[0], pred=pred[0], desc_s=desc_s[0], desc_t=desc_t[0],
+                   logits_s_items=logits_sv, logits_t_items=logits_tv)
+        self._handed_out.extend(out.values())
+        out["starts"] = list(plan.starts)
+        out["plan"] = plan
+        out["done"] = finished
+        return out
+
+    def run_video(self, rgb, gray, n_snippets=video.N_SNIPPETS, views=None, invert_flow_x=False, consensus="softmax",
+                  fusion_weights=(1.0, 1.0), crops=None):
+        """``submit_video`` + ``wait()``: the results are ready on the current stream."""
+        out = self.submit_video(rgb, gray, n_snippets, views, invert_flow_x, consensus, fusion_weights, crops)
+        self.wait()
         return out
 
     def wait(self, stream=None):

@@ -293,6 +293,25 @@ int va_flow_to_stack_snippets(va_ctx* ctx, const void* flow, int n_pairs, const 
                               const void* crops, int invert_x_on_flip, int out_w, int out_h, void* stack, void* stream);
 
 /*
+ * Crop-resize gathers: scale jittering, the one input transform that resamples.  table: DEVICE i32
+ * [n_out][6] rows {src, top, left, ch, cw, flip}, 1 <= ch <= h, 1 <= cw <= w, the rectangle inside the frame; the output is
+ * always 224 x 224.  Output pixel (y, x), x' = flip ? 223 - x : x, plain f32 without fmaf: s = (float)cw / 224.0f,
+ * u = ((float)x' + 0.5f) * s - 0.5f clamped to [0, cw - 1], x0 = floor(u), ax = u - x0, x1 = min(x0 + 1, cw - 1); rows
+ * likewise from y, ch, top (no vertical flip); val = t + ay*(b - t), t = A + ax*(B - A), b = C + ax*(D - C): bilinear
+ * with half-pixel centres, no antialiasing, confined to the crop.  ch = cw = 224: the plain crop, bit for bit.
+ *   va_flow_to_stack_resize  flow f32 [n_pairs][2][h][w]; src indexes its 2*n_pairs planes (even: x flow); stack f32
+ *                            [n_out][224][224] = va_flow_to_stack's quantisation and normalisation of val (the FLOAT field
+ *                            is resampled, then quantised once); invert_x_on_flip as va_flow_to_stack_views
+ *   va_resize_images_u8      src u8 [n][c][h][w] or (src_nhwc) [n][h][w][c]; src indexes images; dst u8 NCHW
+ *                            [n_out][c][224][224] = (u8) rintf(clamp(val, 0, 255)) of the u8 values as floats
+ * Rows are validated by the host wrappers and clamped into range on the device.  n_out (x c) <= 65535 per call.
+ */
+int va_flow_to_stack_resize(va_ctx* ctx, const void* flow, int n_pairs, int w, int h, float bound, float mean, float stdv,
+                            const void* table, int n_out, int invert_x_on_flip, void* stack, void* stream);
+int va_resize_images_u8(va_ctx* ctx, const void* src, int n, int c, int w, int h, int src_nhwc, const void* table, int n_out,
+                        void* dst, void* stream);
+
+/*
  * Mean flow subtraction, step one: flow f32 [n_pairs][2][h][w] -> means f32 [n_pairs][2], the mean of
  * every displacement field's component over the full frame.  Each value is clamped to [-32768, 32768] (a NaN becomes
  * -32768) and summed as the exact integer rint(a * 65536) in int64, so the result does not depend on the reduction
@@ -428,6 +447,16 @@ size_t va_vgg16_train_workspace_bytes(const va_vgg16* model, int batch);
 int va_vgg16_train_step(va_vgg16* model, const void* x, int x_is_u8, const void* labels, int batch,
                         float lr, float momentum, unsigned long long dropout_seed, void* desc,
                         void* loss_out, void* workspace, size_t workspace_bytes, void* stream);
+/*
+ * The same step with the loss on the consensus of each video's snippets (TSN, Sheet03/notes.txt:165-185):
+ * x holds n*k images, video-major (n*k <= 64), labels i64 [n].  With logits z[n][k][c]: m[v][c] = (z[v][0][c] + ... +
+ * z[v][k-1][c]) / (float)k, summed in snippet order; loss (mean over the n videos), hits (arg-max of m) and the gradient
+ * g at m are va_vgg16_train_step's on m; every snippet receives g / (float)k.  Forward, backward and update are the same
+ * code; k = 1 gives va_vgg16_train_step's bits.  desc: [n*k][desc_dim]; workspace: va_vgg16_train_workspace_bytes(n*k).
+ */
+int va_vgg16_train_step_consensus(va_vgg16* model, const void* x, int x_is_u8, const void* labels, int n, int k,
+                                  float lr, float momentum, unsigned long long dropout_seed, void* desc,
+                                  void* loss_out, void* workspace, size_t workspace_bytes, void* stream);
 /*
  * Checkpoints (Sheet03/spatialModel.py:234-260, Sheet03/utils.py:29-35): copy the parameters (which = 0) or the
  * momentum buffers (which = 1) out to / in from device tensors in the reference's layouts -- conv OIHW

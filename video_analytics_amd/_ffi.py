@@ -27,6 +27,7 @@ EXPORTS = [
     "va_vgg16_train_init", "va_vgg16_train_workspace_bytes", "va_vgg16_train_step",
     "va_vgg16_export_state", "va_vgg16_import_state", "va_vgg16_train_plan",
     "va_conv3x3_layer",
+    "va_flow_to_stack_resize", "va_resize_images_u8", "va_vgg16_train_step_consensus",
 ]
 
 
@@ -136,6 +137,10 @@ def lib():
     L.va_crop_images_u8_views.restype = ci
     L.va_flow_to_stack_snippets.argtypes = [vp, vp, ci, vp, ci, ci, ci, ci, ci, cf, cf, cf, vp, ci, ci, ci, vp, vp]
     L.va_flow_to_stack_snippets.restype = ci
+    L.va_flow_to_stack_resize.argtypes = [vp, vp, ci, ci, ci, cf, cf, cf, vp, ci, ci, vp, vp]
+    L.va_flow_to_stack_resize.restype = ci
+    L.va_resize_images_u8.argtypes = [vp, vp, ci, ci, ci, ci, ci, vp, ci, vp, vp]
+    L.va_resize_images_u8.restype = ci
     L.va_score_consensus.argtypes = [vp, vp, ci, ci, ci, ci, vp, vp]
     L.va_score_consensus.restype = ci
     L.va_fuse_scores.argtypes = [vp, vp, vp, ci, ci, cf, cf, vp, vp, vp]
@@ -166,6 +171,8 @@ def lib():
     L.va_vgg16_train_workspace_bytes.restype = sz
     L.va_vgg16_train_step.argtypes = [vp, vp, ci, vp, ci, cf, cf, ctypes.c_ulonglong, vp, vp, vp, sz, vp]
     L.va_vgg16_train_step.restype = ci
+    L.va_vgg16_train_step_consensus.argtypes = [vp, vp, ci, vp, ci, ci, cf, cf, ctypes.c_ulonglong, vp, vp, vp, sz, vp]
+    L.va_vgg16_train_step_consensus.restype = ci
     L.va_vgg16_train_plan.argtypes = [vp, ci, ctypes.POINTER(ctypes.c_ulonglong)]
     L.va_vgg16_train_plan.restype = ci
     L.va_vgg16_export_state.argtypes = [vp, ci, pp, pp, pp, pp, vp]

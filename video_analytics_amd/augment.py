@@ -8,6 +8,11 @@ crop for crop.  A crop is one row ``{top, left, flip}`` of a CPU int32 ``[n,3]``
 
 Ten-crop evaluation (``ten_crop_views``) uses the same rows: a CPU int32 ``[V,3]`` view table that every clip, and every
 flow image of a clip, is seen through (``crop_image_views``, ``flow.crop_flow_to_stack_views``).
+
+TSN's training augmentations (Sheet03/notes.txt:212-223), corner cropping and scale jittering, draw a
+crop size as well: ``draw_scale_jitter_crops`` gives rows ``{top, left, ch, cw, flip}``, one per snippet, and
+``snippet_tables`` expands them into the ``{src, top, left, ch, cw, flip}`` tables of the crop-resize gathers
+(``resize_images``, ``flow.resize_flow_to_stack``), which resample every crop to 224x224.
 """
 import random
 
@@ -179,3 +184,132 @@ def crop_image_views(x_u8, views, size=CROP_SIZE, layout="NCHW"):
     _ffi.check(_ffi.lib().va_crop_images_u8_views(_ffi.ctx(dev.index), _ffi.ptr(x_u8), n, c, w, h, int(layout == "NHWC"), V,
                                                   _ffi.ptr(dcrops), size, size, _ffi.ptr(out), _ffi.stream_ptr(dev)))
     return out
+
+
+# ---- TSN's multi-scale crop ----
+
+SCALE_JITTER_SCALES = (1, .875, .75, .66)  # TSN's scale_ratios
+
+
+def scale_jitter_sizes(h, w, scales=SCALE_JITTER_SCALES):
+    """-> (sizes, pairs): ``sizes[i] = int(min(h, w) * scales[i])``, a size within 3 of 224 becoming 224; ``pairs`` the
+    candidate ``(cw, ch)`` = ``(sizes[j], sizes[i])`` with ``|i - j| <= 1`` in i-major order (ten for four scales)."""
+    base = min(int(h), int(w))
+    sizes = [int(base * s) for s in scales]
+    sizes = [CROP_SIZE if abs(x - CROP_SIZE) < 3 else x for x in sizes]
+    pairs = [(sizes[j], sizes[i]) for i in range(len(sizes)) for j in range(len(sizes)) if abs(i - j) <= 1]
+    return sizes, pairs
+
+
+def fixed_offsets(h, w, ch, cw, more=True):
+    """The ``(left, top)`` corner-crop offsets of a ``ch x cw`` crop in an ``h x w`` frame: the four corners and the
+    centre, with ``more`` also the four edge centres and the four quarter points (thirteen in all)."""
+    ws, hs = (int(w) - int(cw)) // 4, (int(h) - int(ch)) // 4
+    ret = [(0, 0), (4 * ws, 0), (0, 4 * hs), (4 * ws, 4 * hs), (2 * ws, 2 * hs)]
+    if more:
+        ret += [(0, 2 * hs), (4 * ws, 2 * hs), (2 * ws, 4 * hs), (2 * ws, 0), (ws, hs), (3 * ws, hs), (ws, 3 * hs),
+                (3 * ws, 3 * hs)]
+    return ret
+
+
+def draw_scale_jitter_crops(n, h, w, rng=None, fix=True, more=True, scales=SCALE_JITTER_SCALES):
+    """``n`` multi-scale crops of ``h x w`` frames -> CPU int32 ``[n,5]`` rows ``{top, left, ch, cw, flip}``.  Per crop, in
+    this order: ``rng.choice`` of the size pairs, ``rng.choice`` of the fixed offsets (``fix=False``:
+    ``rng.randint(0, w - cw)`` then ``rng.randint(0, h - ch)``), ``rng.random() < 0.5``.  One crop serves a whole snippet,
+    its RGB frame and all 2L flow planes (TSN's group transform)."""
+    rng = random if rng is None else rng
+    h, w = int(h), int(w)
+    _, pairs = scale_jitter_sizes(h, w, scales)
+    pairs = [(cw, ch) for cw, ch in pairs if 1 <= cw <= w and 1 <= ch <= h]
+    if not pairs:
+        raise ValueError("draw_scale_jitter_crops: no crop size fits a %dx%d frame" % (w, h))
+    rows = []
+    for _ in range(int(n)):
+        cw, ch = rng.choice(pairs)
+        if fix:
+            left, top = rng.choice(fixed_offsets(h, w, ch, cw, more))
+        else:
+            left = rng.randint(0, w - cw)
+            top = rng.randint(0, h - ch)
+        rows.append((top, left, ch, cw, int(rng.random() < 0.5)))
+    return torch.tensor(rows, dtype=torch.int32).view(int(n), 5)
+
+
+def check_jitter_crops(crops, n, h, w, who):
+    """Host-side validation (ValueError) of ``n`` rows ``{top, left, ch, cw, flip}`` for ``h x w`` frames: CPU int32
+    ``[n,5]``, ``1 <= ch <= h``, ``1 <= cw <= w``, the rectangle inside the frame, ``flip`` 0 or 1."""
+    if not isinstance(crops, torch.Tensor) or crops.is_cuda or crops.dtype != torch.int32:
+        raise ValueError("%s: crops must be a CPU int32 tensor (augment.draw_scale_jitter_crops)" % who)
+    if crops.dim() != 2 or tuple(crops.shape) != (n, 5):
+        raise ValueError("%s: crops must be [%d,5], got %s" % (who, n, tuple(crops.shape)))
+    _check_rects(crops, h, w, who)
+
+
+def _check_rects(rows, h, w, who):
+    top, left, ch, cw, flip = (rows[:, i].to(torch.int64) for i in range(5))
+    if bool((ch < 1).any()) or bool((ch > h).any()) or bool((cw < 1).any()) or bool((cw > w).any()):
+        raise ValueError("%s: a crop size lies outside 1..%d x 1..%d" % (who, w, h))
+    if bool((top < 0).any()) or bool((top + ch > h).any()) or bool((left < 0).any()) or bool((left + cw > w).any()):
+        raise ValueError("%s: a crop rectangle leaves the %dx%d frame" % (who, w, h))
+    if bool(((flip != 0) & (flip != 1)).any()):
+        raise ValueError("%s: flip must be 0 or 1" % who)
+
+
+def check_resize_table(table, n_src, h, w, who):
+    """Host-side validation (ValueError) of a crop-resize table over ``n_src`` planes or images of
+    ``h x w`` pixels: CPU int32 ``[n_out,6]`` rows ``{src, top, left, ch, cw, flip}`` with n_out >= 1, ``src`` in
+    [0, n_src) and the rules of ``check_jitter_crops`` for the rest."""
+    if not isinstance(table, torch.Tensor) or table.is_cuda or table.dtype != torch.int32:
+        raise ValueError("%s: the table must be a CPU int32 tensor (augment.snippet_tables)" % who)
+    if table.dim() != 2 or table.shape[0] < 1 or table.shape[1] != 6:
+        raise ValueError("%s: the table must be [n_out,6] with n_out >= 1, got %s" % (who, tuple(table.shape)))
+    if bool((table[:, 0] < 0).any()) or bool((table[:, 0] >= n_src).any()):
+        raise ValueError("%s: src must lie in [0, %d)" % (who, n_src))
+    _check_rects(table[:, 1:], h, w, who)
+
+
+def snippet_tables(crops, frames, flow_starts, flow_count):
+    """One crop per snippet -> the two S17 tables.  crops: CPU int32 ``[n,5]`` (``draw_scale_jitter_crops``); ``frames[i]``:
+    the index of snippet i's RGB frame among the images handed to ``resize_images``; ``flow_starts[i]``: the index of its
+    first flow field among the fields handed to ``flow.resize_flow_to_stack``, its window being the ``flow_count`` = L
+    fields from there.  Returns ``(rgb_table [n,6], flow_table [n*2L,6])``: flow row ``i*2L + c`` reads source plane
+    ``2*flow_starts[i] + c`` through snippet i's crop (channel 2k = x flow of the window's pair k)."""
+    if not isinstance(crops, torch.Tensor) or crops.dim() != 2 or crops.shape[1] != 5 or crops.dtype != torch.int32:
+        raise ValueError("snippet_tables: crops must be a CPU int32 [n,5] tensor")
+    n, C = crops.shape[0], 2 * int(flow_count)
+    if len(frames) != n or len(flow_starts) != n or C < 2:
+        raise ValueError("snippet_tables: need one frame and one flow start per crop and flow_count >= 1")
+    fr = torch.tensor([int(f) for f in frames], dtype=torch.int32).view(n, 1)
+    fs = torch.tensor([int(f) for f in flow_starts], dtype=torch.int32).view(n, 1)
+    rgb = torch.cat([fr, crops], dim=1)
+    src = (2 * fs + torch.arange(C, dtype=torch.int32).view(1, C)).reshape(n * C, 1)
+    flow = torch.cat([src, crops.repeat_interleave(C, dim=0)], dim=1)
+    return rgb.contiguous(), flow.contiguous()
+
+
+def resize_images(x_u8, table, layout="NCHW", out=None):
+    """x_u8: CUDA uint8 ``[n,c,h,w]`` (``layout="NCHW"``) or ``[n,h,w,c]`` (``"NHWC"``); table: CPU int32 ``[n_out,6]`` rows
+    ``{src, top, left, ch, cw, flip}`` -> CUDA uint8 ``[n_out,c,224,224]`` NCHW: crop ``src``'s rectangle, resample it
+    bilinearly to 224x224 and mirror it (``va_resize_images_u8``), into ``out`` when given."""
+    if not isinstance(x_u8, torch.Tensor) or not x_u8.is_cuda or x_u8.dtype != torch.uint8 or x_u8.dim() != 4:
+        raise ValueError("resize_images: x must be a 4-d CUDA uint8 tensor")
+    if layout == "NCHW":
+        n, c, h, w = x_u8.shape
+    elif layout == "NHWC":
+        n, h, w, c = x_u8.shape
+    else:
+        raise ValueError("resize_images: layout must be 'NCHW' or 'NHWC', got %r" % (layout,))
+    check_resize_table(table, n, h, w, "resize_images")
+    n_out = table.shape[0]
+    x_u8 = x_u8.contiguous()
+    dev = x_u8.device
+    if out is None:
+        out = torch.empty((n_out, c, CROP_SIZE, CROP_SIZE), dtype=torch.uint8, device=dev)
+    elif (out.numel() != n_out * c * CROP_SIZE * CROP_SIZE or out.dtype != torch.uint8 or not out.is_contiguous()
+          or out.device != dev):
+        raise ValueError("resize_images: out must be a contiguous uint8 tensor of %d elements on x's device"
+                         % (n_out * c * CROP_SIZE * CROP_SIZE))
+    dtable = crops_to_device(table, dev)
+    _ffi.check(_ffi.lib().va_resize_images_u8(_ffi.ctx(dev.index), _ffi.ptr(x_u8), n, c, w, h, int(layout == "NHWC"),
+                                              _ffi.ptr(dtable), n_out, _ffi.ptr(out), _ffi.stream_ptr(dev)))
+    return out.view(n_out, c, CROP_SIZE, CROP_SIZE)

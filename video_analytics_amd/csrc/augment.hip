@@ -140,6 +140,153 @@ __global__ void __launch_bounds__(256) k_crop_images_u8(const unsigned char* __r
     }
 }
 
+// ---------------------------------------------------------------- S17: crop-resize gather ------
+//
+// Scale jittering is the one input transform that resamples: a crop of ch x cw source pixels becomes a
+// 224 x 224 input by bilinear interpolation with half-pixel centres and no antialiasing (align_corners = False), confined to
+// the crop.  One table row {src, top, left, ch, cw, flip} per output plane (flow) or output image (u8); src is explicit, so
+// snippet windows, overlaps and shared crops are all the host's table.  At ch = cw = 224 every weight is exactly 0 and the
+// result is S10's gather bit for bit.
+//
+// A thread produces 4 x 4 outputs: its four columns' taps (x0, x1, ax) once, then row by row the two source rows' taps.  A
+// workgroup of 448 threads = 8 row groups x 56 column groups writes 32 output rows; 7 workgroups a plane, no thread out of
+// range.  The stores of a row group's 56 threads are one contiguous output row (896 bytes of f32, 224 of u8).  Block row
+// blockIdx.y = the table row: the host emits rows snippet-major, so the planes a neighbouring snippet reads again, and the
+// channels of one image, are adjacent in dispatch order (L2 / Infinity Cache), as in the gathers above.
+constexpr int kResizeSize = 224;
+constexpr int kResizeColGroups = kResizeSize / 4;                    // 56
+constexpr int kResizeRowGroups = 8;                                  // per workgroup
+constexpr int kResizeThreads = kResizeColGroups * kResizeRowGroups;  // 448 = 7 waves
+constexpr int kResizeBlocks = kResizeSize / (4 * kResizeRowGroups);  // 7
+
+struct ResizeWin {
+    int src, top, left, ch, cw, flip;
+};
+
+// a table row clamped so that no value can address memory outside source plane / image [0, n_src) (the host wrappers
+// reject such rows before they get here)
+__device__ __forceinline__ ResizeWin load_resize(const int* __restrict__ table, int i, int n_src, int h, int w)
+{
+    const int* t = table + 6 * (size_t)i;
+    ResizeWin r;
+    r.src = min(max(t[0], 0), n_src - 1);
+    r.ch = min(max(t[3], 1), h);
+    r.cw = min(max(t[4], 1), w);
+    r.top = min(max(t[1], 0), h - r.ch);
+    r.left = min(max(t[2], 0), w - r.cw);
+    r.flip = t[5] != 0;
+    return r;
+}
+
+// S17's position of output index o along an axis of `size` source pixels, in its written order (plain float32, no fmaf)
+__device__ __forceinline__ void resize_tap(int o, int size, int& i0, int& i1, float& a)
+{
+    const float s = (float)size / 224.0f;
+    float u = ((float)o + 0.5f) * s - 0.5f;
+    u = fminf(fmaxf(u, 0.0f), (float)(size - 1));
+    i0 = (int)floorf(u);
+    a = u - (float)i0;
+    i1 = min(i0 + 1, size - 1);
+}
+
+// S12's bilinear form
+__device__ __forceinline__ float resize_lerp(float A, float B, float C, float D, float ax, float ay)
+{
+    const float t = A + ax * (B - A);
+    const float b = C + ax * (D - C);
+    return t + ay * (b - t);
+}
+
+// flow f32 [n_src/2][2][h][w] -> stack f32 [n_out][224][224]: S17, then S9 in S9's order; TSN inversion as S10's
+__global__ void __launch_bounds__(kResizeThreads) k_flow_resize_stack(const float* __restrict__ flow, const int* __restrict__ table,
+                                                                      float* __restrict__ stack, int n_src, int w, int h,
+                                                                      int invert_x, int vec4, float bound, float mean, float stdv)
+{
+    const int o = blockIdx.y;
+    const ResizeWin r = load_resize(table, o, n_src, h, w);
+    const int cg = threadIdx.x % kResizeColGroups, rg = blockIdx.x * kResizeRowGroups + threadIdx.x / kResizeColGroups;
+    const bool inv = invert_x && r.flip && (r.src & 1) == 0;
+    const float* __restrict__ plane = flow + (size_t)r.src * h * w + (size_t)r.top * w + r.left;
+    float* __restrict__ dst = stack + (size_t)o * (kResizeSize * kResizeSize) + 4 * cg;
+    int x0[4], x1[4];
+    float ax[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int x = 4 * cg + k;
+        resize_tap(r.flip ? kResizeSize - 1 - x : x, r.cw, x0[k], x1[k], ax[k]);
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int y = 4 * rg + j;
+        int y0, y1;
+        float ay;
+        resize_tap(y, r.ch, y0, y1, ay);
+        const float* __restrict__ ra = plane + (size_t)y0 * w;
+        const float* __restrict__ rb = plane + (size_t)y1 * w;
+        float q4[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const float val = resize_lerp(ra[x0[k]], ra[x1[k]], rb[x0[k]], rb[x1[k]], ax[k], ay);
+            const float t = (255.0f * (val + bound)) / (2.0f * bound);
+            float q = rintf(fminf(fmaxf(t, 0.0f), 255.0f));
+            if (inv) q = 255.0f - q;
+            q4[k] = (q / 255.0f - mean) / stdv;
+        }
+        if (vec4) {  // 16-byte aligned stack: streamed past the caches, as k_flow_crop_stack's
+            __builtin_nontemporal_store(f32x4{q4[0], q4[1], q4[2], q4[3]}, reinterpret_cast<f32x4*>(dst + (size_t)y * kResizeSize));
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) dst[(size_t)y * kResizeSize + k] = q4[k];
+        }
+    }
+}
+
+// u8 images [n_src][c][h][w] (NHWC = false) or [n_src][h][w][c] (true) -> dst u8 [n_out][c][224][224]; block row
+// blockIdx.y = output image * c + channel; the value is (u8) rintf(clamp(val, 0, 255)) on the u8 values as floats
+template <bool NHWC>
+__global__ void __launch_bounds__(kResizeThreads) k_resize_images_u8(const unsigned char* __restrict__ src,
+                                                                     const int* __restrict__ table, unsigned char* __restrict__ dst,
+                                                                     int n_src, int c, int w, int h, int vec4)
+{
+    const int img = blockIdx.y / c, chn = blockIdx.y - img * c;
+    const ResizeWin r = load_resize(table, img, n_src, h, w);
+    const int cg = threadIdx.x % kResizeColGroups, rg = blockIdx.x * kResizeRowGroups + threadIdx.x / kResizeColGroups;
+    // element (sy, sx) of the channel plane: base[sy * sy_stride + sx * sx_stride]
+    const size_t sx_stride = NHWC ? (size_t)c : 1, sy_stride = (size_t)w * sx_stride;
+    const unsigned char* __restrict__ base =
+        src + (NHWC ? (size_t)r.src * h * w * c + chn : ((size_t)r.src * c + chn) * h * w) + r.top * sy_stride + r.left * sx_stride;
+    unsigned char* __restrict__ out = dst + (size_t)blockIdx.y * (kResizeSize * kResizeSize) + 4 * cg;
+    int x0[4], x1[4];
+    float ax[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int x = 4 * cg + k;
+        resize_tap(r.flip ? kResizeSize - 1 - x : x, r.cw, x0[k], x1[k], ax[k]);
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int y = 4 * rg + j;
+        int y0, y1;
+        float ay;
+        resize_tap(y, r.ch, y0, y1, ay);
+        const unsigned char* __restrict__ ra = base + y0 * sy_stride;
+        const unsigned char* __restrict__ rb = base + y1 * sy_stride;
+        unsigned q4[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const float val = resize_lerp((float)ra[x0[k] * sx_stride], (float)ra[x1[k] * sx_stride], (float)rb[x0[k] * sx_stride],
+                                          (float)rb[x1[k] * sx_stride], ax[k], ay);
+            q4[k] = (unsigned)rintf(fminf(fmaxf(val, 0.0f), 255.0f));
+        }
+        if (vec4) {
+            *reinterpret_cast<unsigned*>(out + (size_t)y * kResizeSize) = q4[0] | (q4[1] << 8) | (q4[2] << 16) | (q4[3] << 24);
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) out[(size_t)y * kResizeSize + k] = (unsigned char)q4[k];
+        }
+    }
+}
+
 // The mean over V views: x f32 [n][V][d] -> out f32 [n][d], out = (((x_0 + x_1) + ...) + x_{V-1}) / V in view order.  One
 // thread per (b, j); the loads of a wave are contiguous in j.
 __global__ void __launch_bounds__(256) k_view_mean(const float* __restrict__ x, float* __restrict__ out, int n, int n_views,
@@ -275,6 +422,44 @@ extern "C" int va_crop_images_u8_views(va_ctx* ctx, const void* src, int n, int 
     VA_USE_DEVICE(ctx);
     return crop_images("va_crop_images_u8_views", src, n, c, w, h, src_nhwc, n_views, crops, out_w, out_h, dst,
                        (hipStream_t)stream);
+}
+
+extern "C" int va_flow_to_stack_resize(va_ctx* ctx, const void* flow, int n_pairs, int w, int h, float bound, float mean,
+                                       float stdv, const void* table, int n_out, int invert_x_on_flip, void* stack, void* stream)
+{
+    VA_CHECK_ARG(ctx != nullptr, "va_flow_to_stack_resize: ctx is NULL");
+    VA_USE_DEVICE(ctx);
+    VA_CHECK_ARG(flow != nullptr && table != nullptr && stack != nullptr, "va_flow_to_stack_resize: NULL buffer");
+    VA_CHECK_ARG(n_pairs >= 1 && n_pairs <= 0x3fffffff && w >= 1 && h >= 1 && n_out >= 1, "va_flow_to_stack_resize: bad shape");
+    VA_CHECK_ARG(n_out <= kMaxGridY, "va_flow_to_stack_resize: %d output planes exceed %d per call", n_out, kMaxGridY);
+    VA_CHECK_ARG(invert_x_on_flip == 0 || invert_x_on_flip == 1, "va_flow_to_stack_resize: invert_x_on_flip must be 0 or 1");
+    VA_CHECK_ARG(bound > 0.0f && stdv > 0.0f, "va_flow_to_stack_resize: bound and std must be > 0");
+    const int vec4 = reinterpret_cast<uintptr_t>(stack) % 16 == 0;
+    k_flow_resize_stack<<<dim3(kResizeBlocks, (unsigned)n_out), kResizeThreads, 0, (hipStream_t)stream>>>(
+        (const float*)flow, (const int*)table, (float*)stack, 2 * n_pairs, w, h, invert_x_on_flip, vec4, bound, mean, stdv);
+    VA_LAUNCH_CHECK();
+    return VA_OK;
+}
+
+extern "C" int va_resize_images_u8(va_ctx* ctx, const void* src, int n, int c, int w, int h, int src_nhwc, const void* table,
+                                   int n_out, void* dst, void* stream)
+{
+    VA_CHECK_ARG(ctx != nullptr, "va_resize_images_u8: ctx is NULL");
+    VA_USE_DEVICE(ctx);
+    VA_CHECK_ARG(src != nullptr && table != nullptr && dst != nullptr, "va_resize_images_u8: NULL buffer");
+    VA_CHECK_ARG(n >= 1 && c >= 1 && w >= 1 && h >= 1 && n_out >= 1, "va_resize_images_u8: bad shape");
+    VA_CHECK_ARG(src_nhwc == 0 || src_nhwc == 1, "va_resize_images_u8: src_nhwc must be 0 or 1");
+    VA_CHECK_ARG((long long)n_out * c <= kMaxGridY, "va_resize_images_u8: %d x %d planes exceed %d per call", n_out, c, kMaxGridY);
+    const dim3 g(kResizeBlocks, (unsigned)(n_out * c));
+    const int vec4 = reinterpret_cast<uintptr_t>(dst) % 4 == 0;
+    if (src_nhwc)
+        k_resize_images_u8<true><<<g, kResizeThreads, 0, (hipStream_t)stream>>>((const unsigned char*)src, (const int*)table,
+                                                                                (unsigned char*)dst, n, c, w, h, vec4);
+    else
+        k_resize_images_u8<false><<<g, kResizeThreads, 0, (hipStream_t)stream>>>((const unsigned char*)src, (const int*)table,
+                                                                                 (unsigned char*)dst, n, c, w, h, vec4);
+    VA_LAUNCH_CHECK();
+    return VA_OK;
 }
 
 extern "C" int va_view_mean(va_ctx* ctx, const void* x, int n, int n_views, int d, void* out, void* stream)

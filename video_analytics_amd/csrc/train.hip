@@ -131,6 +131,57 @@ __global__ void k_ce_fwd_bwd(const float* __restrict__ logits, const long long* 
     }
 }
 
+// Consensus loss (TSN's segmental consensus, Sheet03/notes.txt:165-185): logits z[B][K][C] of B videos of K
+// snippets each, labels i64 [B].  m[v][c] = (((z[v][0][c] + z[v][1][c]) + ...) + z[v][K-1][c]) / (float)K (consensus mode 1's
+// mean, va_score_consensus); loss, hits and g[v][c] are k_ce_fwd_bwd's expressions on m with B videos, and every snippet
+// receives dz[v][j][c] = g[v][c] / (float)K.  Row 0 of a video's K gradient rows holds m until the gradient replaces it
+// element by element, so no workspace is added.  K = 1: every added operation is a division by 1 -- k_ce_fwd_bwd's bits.
+__global__ void k_ce_consensus_fwd_bwd(const float* __restrict__ logits, const long long* __restrict__ labels, int B, int K, int C,
+                                       float* __restrict__ dlogits, float* __restrict__ out)
+{
+    __shared__ float sloss[256];
+    __shared__ int scorr[256];
+    float loss = 0.0f;
+    int corr = 0;
+    const float invB = 1.0f / (float)B;
+    const float fk = (float)K;
+    for (int b = threadIdx.x; b < B; b += blockDim.x) {
+        const float* z = logits + (size_t)b * K * C;
+        float* l = dlogits + (size_t)b * K * C;
+        for (int c = 0; c < C; ++c) {
+            float s = z[c];
+            for (int j = 1; j < K; ++j) s += z[(size_t)j * C + c];
+            l[c] = s / fk;
+        }
+        float mx = l[0];
+        int am = 0;
+        for (int c = 1; c < C; ++c)
+            if (l[c] > mx) { mx = l[c]; am = c; }
+        float se = 0.0f;
+        for (int c = 0; c < C; ++c) se += expf(l[c] - mx);
+        const long long y = labels[b];  // outside [0, C): NaN loss and NaN gradient rows, as k_ce_fwd_bwd
+        const bool yok = y >= 0 && y < (long long)C;
+        loss += yok ? (logf(se) + mx) - l[yok ? y : 0] : __builtin_nanf("");
+        corr += (yok && am == (int)y);
+        const float inv = yok ? 1.0f / se : __builtin_nanf("");
+        for (int c = 0; c < C; ++c) {
+            const float g = (expf(l[c] - mx) * inv - (c == (int)y ? 1.0f : 0.0f)) * invB;
+            const float gk = g / fk;
+            for (int j = 0; j < K; ++j) l[(size_t)j * C + c] = gk;
+        }
+    }
+    sloss[threadIdx.x] = loss;
+    scorr[threadIdx.x] = corr;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float L = 0.0f;
+        int Cc = 0;
+        for (int i = 0; i < (int)blockDim.x; ++i) { L += sloss[i]; Cc += scorr[i]; }
+        out[0] = L * invB;
+        out[1] = (float)Cc;
+    }
+}
+
 // ---------------------------------------------------------------- classifier backward ----------
 
 // dX[b][i] = sum_o dZ[b][o] * W[o][i], then * scale where mask[b][i] > 0, else 0 (mask may be NULL).
@@ -632,19 +683,22 @@ extern "C" size_t va_vgg16_train_workspace_bytes(const va_vgg16* m, int batch)
     return plan_train(m, batch).total;
 }
 
-extern "C" int va_vgg16_train_step(va_vgg16* m, const void* x, int x_is_u8, const void* labels, int batch, float lr, float momentum,
-                                   unsigned long long dropout_seed, void* desc, void* loss_out, void* workspace, size_t workspace_bytes,
-                                   void* stream)
+// The step both entry points share.  segments = 0: va_vgg16_train_step, the loss of every image (k_ce_fwd_bwd);
+// segments = K >= 1: va_vgg16_train_step_consensus, `batch` = videos * K images, video-major, and the loss of the videos'
+// consensus (k_ce_consensus_fwd_bwd).  Everything but that one launch is the same code.
+static int train_step(const char* who, va_vgg16* m, const void* x, int x_is_u8, const void* labels, int batch, int segments, float lr,
+                      float momentum, unsigned long long dropout_seed, void* desc, void* loss_out, void* workspace,
+                      size_t workspace_bytes, void* stream)
 {
-    VA_CHECK_ARG(m != nullptr && x != nullptr && labels != nullptr && loss_out != nullptr, "va_vgg16_train_step: NULL argument");
+    VA_CHECK_ARG(m != nullptr && x != nullptr && labels != nullptr && loss_out != nullptr, "%s: NULL argument", who);
     VA_USE_DEVICE(m->ctx);
-    VA_CHECK_ARG(m->dtype == VA_DTYPE_F32, "va_vgg16_train_step: training is fp32 only");
-    VA_CHECK_ARG(batch >= 1 && batch <= 64, "va_vgg16_train_step: batch %d out of range [1,64]", batch);
-    VA_CHECK_ARG(m->conv[0].mom_w != nullptr && m->zeros_f32 != nullptr, "va_vgg16_train_step: call va_vgg16_train_init first");
-    VA_CHECK_ARG(!x_is_u8 || (m->in_mean && m->in_std), "va_vgg16_train_step: u8 input needs the model's mean/std");
+    VA_CHECK_ARG(m->dtype == VA_DTYPE_F32, "%s: training is fp32 only", who);
+    VA_CHECK_ARG(batch >= 1 && batch <= 64, "%s: batch %d out of range [1,64]", who, batch);
+    VA_CHECK_ARG(m->conv[0].mom_w != nullptr && m->zeros_f32 != nullptr, "%s: call va_vgg16_train_init first", who);
+    VA_CHECK_ARG(!x_is_u8 || (m->in_mean && m->in_std), "%s: u8 input needs the model's mean/std", who);
     const TrainPlan T = plan_train(m, batch);
     if (workspace == nullptr || workspace_bytes < T.total) {
-        va_set_error("va_vgg16_train_step: workspace of %zu bytes needed, %zu given", T.total, workspace_bytes);
+        va_set_error("%s: workspace of %zu bytes needed, %zu given", who, T.total, workspace_bytes);
         return VA_ERR_WORKSPACE;
     }
     hipStream_t st = (hipStream_t)stream;
@@ -680,7 +734,11 @@ extern "C" int va_vgg16_train_step(va_vgg16* m, const void* x, int x_is_u8, cons
         }
     }
     if (desc) VA_HIP(hipMemcpyAsync(desc, F(T.a_d[2]), (size_t)B * m->desc_dim * sizeof(float), hipMemcpyDeviceToDevice, st));
-    k_ce_fwd_bwd<<<1, 256, 0, st>>>(F(T.logits), (const long long*)labels, B, m->n_classes, F(T.dlogits), (float*)loss_out);
+    if (segments == 0)
+        k_ce_fwd_bwd<<<1, 256, 0, st>>>(F(T.logits), (const long long*)labels, B, m->n_classes, F(T.dlogits), (float*)loss_out);
+    else
+        k_ce_consensus_fwd_bwd<<<1, 256, 0, st>>>(F(T.logits), (const long long*)labels, B / segments, segments, m->n_classes,
+                                                  F(T.dlogits), (float*)loss_out);
     VA_LAUNCH_CHECK();
 
     // ---------------- classifier backward + update ----------------
@@ -755,11 +813,29 @@ extern "C" int va_vgg16_train_step(va_vgg16* m, const void* x, int x_is_u8, cons
         if (i > 0) cur = 1 - cur;
         VA_LAUNCH_CHECK();
         if (stop_at == i) {  // debugging aid of the tests: leave the gradient buffers as layer i left them; NOT a completed step
-            va_set_error("va_vgg16_train_step: stopped after the backward pass of conv layer %d (VA_OPT_TRAIN_STOP_AT); layers below were not updated", i);
+            va_set_error("%s: stopped after the backward pass of conv layer %d (VA_OPT_TRAIN_STOP_AT); layers below were not updated", who, i);
             return VA_ERR_STOPPED;
         }
     }
     return VA_OK;
+}
+
+extern "C" int va_vgg16_train_step(va_vgg16* m, const void* x, int x_is_u8, const void* labels, int batch, float lr, float momentum,
+                                   unsigned long long dropout_seed, void* desc, void* loss_out, void* workspace, size_t workspace_bytes,
+                                   void* stream)
+{
+    return train_step("va_vgg16_train_step", m, x, x_is_u8, labels, batch, 0, lr, momentum, dropout_seed, desc, loss_out, workspace,
+                      workspace_bytes, stream);
+}
+
+extern "C" int va_vgg16_train_step_consensus(va_vgg16* m, const void* x, int x_is_u8, const void* labels, int n, int k, float lr,
+                                             float momentum, unsigned long long dropout_seed, void* desc, void* loss_out,
+                                             void* workspace, size_t workspace_bytes, void* stream)
+{
+    VA_CHECK_ARG(n >= 1 && k >= 1 && (long long)n * k <= 64, "va_vgg16_train_step_consensus: %d videos x %d snippets out of range (n*k in [1,64])",
+                 n, k);
+    return train_step("va_vgg16_train_step_consensus", m, x, x_is_u8, labels, n * k, k, lr, momentum, dropout_seed, desc, loss_out,
+                      workspace, workspace_bytes, stream);
 }
 
 // which = 0: parameters, 1: momentum buffers.  Destination tensors in the reference's layouts (conv OIHW

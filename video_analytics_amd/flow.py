@@ -260,6 +260,27 @@ def crop_flow_to_stack_snippets(flow, starts, views, flow_count, invert_x_on_fli
     return out.view(n, V, 2 * L, size, size)
 
 
+def resize_flow_to_stack(flow, table, invert_x_on_flip=False, bound=FLOW_BOUND, mean=NORM_MEANS_TF[0], std=NORM_STDS_TF[0],
+                         out=None):
+    """The crop-resize gather of flow (then S9; ``va_flow_to_stack_resize``): flow ``[N,2,H,W]`` float32 (or
+    an S11-S13 motion field of that shape), table CPU int32 ``[n_out,6]`` rows ``{src, top, left, ch, cw, flip}`` with
+    ``src`` one of the 2N planes (``augment.snippet_tables``) -> ``[n_out,224,224]`` float32: the float field is resampled
+    bilinearly inside the crop, then quantised and normalised once as ``flow_to_stack``.  ``invert_x_on_flip``: a flipped
+    plane with an even ``src`` (x flow) also becomes ``q -> 255 - q`` (TSN flips)."""
+    from . import augment
+    _check_flow(flow, "resize_flow_to_stack")
+    N, _, H, W = flow.shape
+    augment.check_resize_table(table, 2 * N, H, W, "resize_flow_to_stack")
+    n_out = table.shape[0]
+    flow = flow.contiguous()
+    out = _check_out(out, (n_out, 224, 224), flow, "resize_flow_to_stack")
+    dtable = augment.crops_to_device(table, flow.device)
+    _ffi.check(_ffi.lib().va_flow_to_stack_resize(_ffi.ctx(flow.device.index), _ffi.ptr(flow), N, W, H, float(bound),
+                                                  float(mean), float(std), _ffi.ptr(dtable), n_out,
+                                                  int(bool(invert_x_on_flip)), _ffi.ptr(out), _ffi.stream_ptr(flow.device)))
+    return out.view(n_out, 224, 224)
+
+
 # The temporal-ConvNet inputs of the two-stream paper (DESIGN.md S11-S13): "stack" is optical-flow stacking (the default and
 # the reference's input), "trajectory" samples the flow along the trajectory that starts at each pixel of the first frame,
 # "bidirectional" stacks L/2 forward fields from the clip's centre frame on and L/2 backward ones from it back.

@@ -405,6 +405,121 @@ class TwoStreamPipeline(object):
         self.wait()
         return out
 
+    def _check_train_videos(self, videos, labels, k, starts, crops, rng):
+        """Host-side checks and draws of ``train_videos`` before anything is enqueued -> (videos, labels, plans, crops)."""
+        who = "train_videos"
+        if self.spatial.dtype != "f32" or self.temporal.dtype != "f32":
+            raise ValueError("%s: training is fp32 only; this pipeline was built with cnn_dtype=%r" % (who, self.spatial.dtype))
+        videos = list(videos)
+        n, k = len(videos), int(k)
+        if n < 1 or k < 1 or n * k > 64:
+            raise ValueError("%s: %d videos x %d snippets out of range (n*k in 1..64)" % (who, n, k))
+        for v in videos:
+            if not isinstance(v, (tuple, list)) or len(v) != 2:
+                raise ValueError("%s: videos must be a list of (rgb u8 [T,3,H,W], gray [T,H,W]) pairs" % who)
+            rgb, gray = v
+            if not isinstance(rgb, torch.Tensor) or rgb.dtype != torch.uint8 or rgb.dim() != 4 or rgb.shape[1] != 3:
+                raise ValueError("%s: rgb must be a uint8 [T,3,H,W] tensor" % who)
+            if not isinstance(gray, torch.Tensor) or gray.dim() != 3 or gray.dtype not in (torch.uint8, torch.float32):
+                raise ValueError("%s: gray must be a uint8 or float32 [T,H,W] tensor" % who)
+            if gray.shape[0] != rgb.shape[0]:
+                raise ValueError("%s: %d rgb frames but %d gray frames" % (who, rgb.shape[0], gray.shape[0]))
+            if not rgb.is_cuda or not gray.is_cuda or rgb.device != self.device or gray.device != self.device:
+                raise ValueError("%s: rgb and gray must be on %s" % (who, self.device))
+            if (tuple(rgb.shape[2:]) != tuple(videos[0][0].shape[2:]) or tuple(gray.shape[1:]) != tuple(videos[0][1].shape[1:])
+                    or gray.dtype != videos[0][1].dtype):
+                raise ValueError("%s: the videos of one step must share their frame size and gray dtype" % who)
+        if tuple(videos[0][0].shape[2:]) != tuple(videos[0][1].shape[1:]):
+            raise ValueError("%s: one crop serves a snippet's RGB frame and flow planes: rgb and gray frames must have one "
+                             "size" % who)
+        H, W = (int(d) for d in videos[0][1].shape[1:])
+        if not isinstance(labels, torch.Tensor):
+            try:
+                labels = torch.tensor([int(l) for l in labels], dtype=torch.int64)
+            except (TypeError, ValueError):
+                raise ValueError("%s: labels must be a tensor or a list of %d class indices" % (who, n))
+        if labels.dim() != 1 or labels.shape[0] != n:
+            raise ValueError("%s: %d videos but labels of shape %s" % (who, n, tuple(labels.shape)))
+        vgg._check_labels(labels, self.spatial.n_classes, who)
+        if starts is not None and (not isinstance(starts, (tuple, list)) or len(starts) != n):
+            raise ValueError("%s: starts must hold one list of %d window starts per video" % (who, k))
+        plans = []
+        try:
+            for i, (_, gray) in enumerate(videos):
+                T = int(gray.shape[0])
+                if starts is None:
+                    st = video.segmentStarts(T, k, self.L, rng)
+                else:
+                    st = [int(x) for x in starts[i]]
+                    if len(st) != k:
+                        raise ValueError("video %d has %d starts, not k=%d" % (i, len(st), k))
+                plans.append(video.segmentPlan(T, st, self.L))
+        except (TypeError, ValueError) as e:
+            raise ValueError("%s: %s" % (who, e))
+        if crops is None:
+            crops = augment.draw_scale_jitter_crops(n * k, H, W, rng)
+        augment.check_jitter_crops(crops, n * k, H, W, who)
+        return videos, labels, plans, crops
+
+    def train_videos(self, videos, labels, k=video.N_SEGMENTS, starts=None, crops=None, lr=1e-3, momentum=0.9, dropout_seed=0,
+                     invert_flow_x=False, rng=None):
+        """One TSN training step of both streams on whole videos (Sheet03/notes.txt:165-185, 212-223).
+        ``videos``: a list of n ``(rgb u8 [T,3,H,W], gray [T,H,W])`` pairs on the device, one frame size, any lengths;
+        ``labels``: their n class indices; ``n*k <= 64``.
+
+        Each video gives ``k`` snippets, one per temporal segment (``starts``: a list of k window starts per video;
+        None draws them with ``video.segmentStarts``), and each snippet one scale-jitter crop for its RGB frame and its
+        2L flow planes (``crops``: CPU int32 ``[n*k,5]`` rows ``{top, left, ch, cw, flip}``, video-major; None draws them
+        with ``augment.draw_scale_jitter_crops``); ``rng``: the ``random.Random`` of both draws (starts of all videos
+        first, then the crops).  TV-L1 runs once on each frame pair the snippets need (``video.segmentPlan``), the
+        pipeline's ``motion`` / ``mean_flow`` apply per snippet window, the two crop-resize gathers build the 224x224
+        inputs, and each stream takes one step on the consensus loss (``Vgg16Stream.train_step_consensus``) with ``lr``,
+        ``momentum`` and ``dropout_seed``.  ``invert_flow_x``: TSN flips.
+
+        Returns a dict: ``stats_s``, ``stats_t`` f32 ``[2]`` = (loss, hits) and ``desc_s``, ``desc_t`` f32 ``[n*k,256]``
+        per stream, ready on the current stream, and ``starts``, ``crops``, ``plans``, ``flow`` (the planned TV-L1
+        fields, video-major).  Everything runs in order on the current stream, TV-L1 on the flow streams in between; batches
+        submitted before are waited for, later ones see the updated weights.  A bf16 pipeline, ``n*k > 64``, a video
+        shorter than one snippet and a bad table raise ValueError before anything is enqueued."""
+        videos, labels, plans, crops = self._check_train_videos(videos, labels, k, starts, crops, rng)
+        dev, L, n, k = self.device, self.L, len(videos), int(k)
+        cur = torch.cuda.current_stream(dev)
+        frames = torch.cat([rgb[augment.crops_to_device(torch.tensor(p.starts, dtype=torch.int64), dev)]
+                            for (rgb, _), p in zip(videos, plans)])  # [n*k,3,H,W]
+        if self.motion == "bidirectional":  # S13 per snippet window: its own forward and backward sequences, no sharing
+            win = torch.cat([gray[augment.crops_to_device(torch.tensor([[s + f for f in range(L + 1)] for s in p.starts],
+                                                                        dtype=torch.int64), dev)]
+                             for (_, gray), p in zip(videos, plans)])  # [n*k,L+1,H,W]
+            tv = vflow.bidirectional_sequences(win)
+            first = [i * L for i in range(n * k)]
+        else:
+            tv = torch.cat([gray[augment.crops_to_device(torch.tensor(p.sequences, dtype=torch.int64), dev)]
+                            for (_, gray), p in zip(videos, plans)])  # [U,2,H,W]: one two-frame sequence per planned pair
+            first, base = [], 0
+            for p in plans:
+                first += [base + j for j in p.index]
+                base += len(p.pairs)
+        flow = vflow.tvl1_flow_concurrent(tv, self.tvl1_params, self.flow_streams)
+        if self.motion == "trajectory":  # S12 chains follow a window: the windows are laid out one after the other
+            idx = torch.tensor([f + j for f in first for j in range(L)], dtype=torch.int64)
+            src = vflow.apply_motion(flow[augment.crops_to_device(idx, dev)], L, "trajectory", self.mean_flow)
+            first = [i * L for i in range(n * k)]
+        elif self.motion == "bidirectional":
+            src = vflow.apply_motion(flow, L, "bidirectional", self.mean_flow)
+        else:  # S11 / S12 per planned field
+            src = vflow.apply_motion(flow, 1, "stack", self.mean_flow)
+        rgb_table, flow_table = augment.snippet_tables(crops, list(range(n * k)), first, L)
+        xs = augment.resize_images(frames, rgb_table)
+        xt = vflow.resize_flow_to_stack(src, flow_table, invert_x_on_flip=bool(invert_flow_x)).view(n * k, 2 * L, 224, 224)
+        cur.wait_stream(self._cnn)   # forwards submitted earlier read the weights this step updates
+        cur.wait_stream(self._cnn2)
+        stats_s, desc_s = self.spatial.train_step_consensus(xs, labels, k, lr, momentum, dropout_seed)
+        stats_t, desc_t = self.temporal.train_step_consensus(xt, labels, k, lr, momentum, dropout_seed)
+        self._cnn.wait_stream(cur)
+        self._cnn2.wait_stream(cur)
+        return dict(stats_s=stats_s, desc_s=desc_s, stats_t=stats_t, desc_t=desc_t, starts=[list(p.starts) for p in plans],
+                    crops=crops, plans=plans, flow=flow)
+
     def wait(self, stream=None):
         """Make ``stream`` (default: the current one) wait for every batch submitted so far."""
         s = torch.cuda.current_stream(self.device) if stream is None else stream

@@ -259,6 +259,44 @@ class Vgg16Stream(object):
                                          _ffi.ptr(ws), ws.numel(), _ffi.stream_ptr(self.device)))
         return stats, desc
 
+    def train_step_consensus(self, x, labels, k, lr, momentum, dropout_seed):
+        """``train_step`` with the loss on the consensus of each video's ``k`` snippets (TSN's segmental
+        consensus): x ``[n*k,C,224,224]``, video-major, labels ``[n]``, ``n*k <= 64``.  The k snippets' class scores are
+        averaged (in snippet order), the mean cross-entropy of the n averages is the loss, and every snippet receives
+        1/k of its video's gradient.  Returns (stats, descriptors): ``stats`` = (loss, arg-max hits of the averaged
+        scores), ``descriptors`` ``[n*k,D]``.  ``k = 1`` is ``train_step`` bit for bit."""
+        if not getattr(self, "_train_ready", False):
+            self.train_init()
+        who = "Vgg16Stream.train_step_consensus"
+        if not isinstance(x, torch.Tensor) or not x.is_cuda or x.dtype not in (torch.float32, torch.uint8):
+            raise ValueError("%s: x must be a CUDA float32/uint8 tensor" % who)
+        if x.dim() != 4 or tuple(x.shape[1:]) != (self.c_in, 224, 224):
+            raise ValueError("%s: x must be [n*k,%d,224,224], got %s" % (who, self.c_in, tuple(x.shape)))
+        self._on_my_device(x, "train_step_consensus")
+        B, k = int(x.shape[0]), int(k)
+        if k < 1 or B < 1 or B % k:
+            raise ValueError("%s: %d images are not a whole number of videos of k=%d snippets" % (who, B, k))
+        n = B // k
+        _check_labels(labels, self.n_classes, who)
+        if not isinstance(labels, torch.Tensor):
+            raise ValueError("%s: labels must be a tensor [n]" % who)
+        labels = labels.to(device=x.device, dtype=torch.int64).contiguous()
+        if labels.dim() != 1 or labels.shape[0] != n:
+            raise ValueError("%s: labels must be [%d], one per video" % (who, n))
+        x = x.contiguous()
+        L = _ffi.lib()
+        nbytes = L.va_vgg16_train_workspace_bytes(self._h, B)
+        if nbytes == 0:
+            raise ValueError("%s: %d videos x %d snippets unsupported (n*k in 1..64, fp32 model)" % (who, n, k))
+        ws = _workspace(nbytes, x.device, ("train", self.ws_slot))
+        stats = torch.empty(2, dtype=torch.float32, device=x.device)
+        desc = torch.empty((B, self.desc_dim), dtype=torch.float32, device=x.device)
+        _ffi.check(L.va_vgg16_train_step_consensus(self._h, _ffi.ptr(x), int(x.dtype == torch.uint8), _ffi.ptr(labels), n, k,
+                                                   float(lr), float(momentum), int(dropout_seed) & 0xFFFFFFFFFFFFFFFF,
+                                                   _ffi.ptr(desc), _ffi.ptr(stats), _ffi.ptr(ws), ws.numel(),
+                                                   _ffi.stream_ptr(self.device)))
+        return stats, desc
+
     def _state_tensors(self, device):
         cin = self.c_in
         cw, cb = [], []

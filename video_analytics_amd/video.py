@@ -6,6 +6,9 @@ or flow stacks with equal temporal spacing, ten crops of each, the class scores 
 (notes.txt:121-124).  ``snippetStarts`` places the snippets, ``snippetPlan`` lists the frame pairs they share so that
 each goes through TV-L1 once, and ``evaluateVideos`` is the loop over videos on ``TwoStreamPipeline.submit_video``.
 Everything here but ``evaluateVideos`` is integer arithmetic on the host.
+
+Training samples differently (TSN, notes.txt:165-175): ``segmentStarts`` draws one snippet from each of k
+equal segments and ``segmentPlan`` lists the pairs those snippets need (``TwoStreamPipeline.train_videos``).
 """
 import numpy as np
 
@@ -60,6 +63,59 @@ def snippetPlan(T, L=VIDEO_INPUT_FLOW_COUNT, n=N_SNIPPETS):
     pairs is contiguous in the sorted set U, because every pair of it is in U; ``len(U) <= min(T - 1, n * L)``.  At L = 10,
     n = 25: 149 pairs for a 150-frame video (250 for 25 independent clips), 250 of 299 at T = 300."""
     return SnippetPlan(T, L, n)
+
+
+N_SEGMENTS = 3  # TSN's number of segments
+
+
+def segmentStarts(T, k=N_SEGMENTS, L=VIDEO_INPUT_FLOW_COUNT, rng=None):
+    """Training-time temporal segment sampling: the first frame pair of each of ``k`` snippets of a ``T``-frame video
+    (P = T - 1 pairs, window starts 0 .. P - L).  ``avg = (P - L + 1) // k``; with ``avg > 0`` snippet i starts at
+    ``i * avg + rng.randrange(avg)``, one per segment; a video with fewer than k starts gets the sorted list of k draws
+    of ``rng.randrange(P - L + 1)``; ValueError when it holds no window.  ``rng``: a ``random.Random`` (default: the
+    global generator).  Snippet i covers pairs ``s_i .. s_i + L - 1`` and its RGB frame is frame ``s_i``."""
+    import random
+    rng = random if rng is None else rng
+    T, k, L = int(T), int(k), int(L)
+    P = T - 1
+    if L < 1:
+        raise ValueError("segmentStarts: need at least one flow pair per snippet, got L=%d" % L)
+    if k < 1:
+        raise ValueError("segmentStarts: need at least one segment, got k=%d" % k)
+    if P < L:
+        raise ValueError("segmentStarts: a video of %d frames has %d frame pairs, fewer than one snippet's %d" % (T, P, L))
+    avg = (P - L + 1) // k
+    if avg > 0:
+        return [i * avg + rng.randrange(avg) for i in range(k)]
+    return sorted(rng.randrange(P - L + 1) for _ in range(k))
+
+
+class SegmentPlan(SnippetPlan):
+    """``SnippetPlan`` for given starts: ``pairs`` the sorted, duplicate-free pairs the windows need, ``index`` each start
+    re-indexed into them, ``sequences`` one two-frame TV-L1 sequence per pair."""
+
+    def __init__(self, T, starts, L):
+        self.T, self.L = int(T), int(L)
+        self.starts = [int(s) for s in starts]
+        self.n = len(self.starts)
+        P = self.T - 1
+        if self.L < 1 or self.n < 1:
+            raise ValueError("segmentPlan: need at least one snippet of at least one pair")
+        if any(s < 0 or s + self.L > P for s in self.starts):
+            raise ValueError("segmentPlan: a window of %d pairs starting at %d..%d does not lie in the %d pairs of a "
+                             "%d-frame video" % (self.L, min(self.starts), max(self.starts), P, self.T))
+        need = sorted(set(p for s in self.starts for p in range(s, s + self.L)))
+        where = dict((p, j) for j, p in enumerate(need))
+        self.pairs = need
+        self.index = [where[s] for s in self.starts]
+        self.sequences = [(p, p + 1) for p in need]
+        self.pair_computations = len(self.sequences)
+
+
+def segmentPlan(T, starts, L=VIDEO_INPUT_FLOW_COUNT):
+    """The pairs of a ``T``-frame video the snippets at ``starts`` need, each once (``SegmentPlan``): at most ``k * L``,
+    30 TV-L1 pairs per video at k = 3, L = 10.  ValueError when a window leaves the video."""
+    return SegmentPlan(T, starts, L)
 
 
 def evaluateVideos(pipe, videos, labels, **kw):

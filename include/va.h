@@ -32,6 +32,8 @@
  *                     DESIGN.md S14-S16.
  *   va_flow_field_means, va_flow_motion   mean flow subtraction and trajectory stacking, two of the temporal-ConvNet
  *                     inputs of the two-stream paper (no reference counterpart).
+ *   va_flow_homography, va_flow_compensate   warped optical flow, TSN's camera-compensated temporal input
+ *                     (Sheet03/notes.txt:187-194; no reference code): DESIGN.md S21, S22.
  *   va_validate_batch the loss / argmax / correct-count lines of validate():
  *                     Sheet03/spatialModel.py:219-221.
  *   va_meter_*        the per-video AverageMeter collation of validate():
@@ -329,6 +331,29 @@ int va_flow_field_means(va_ctx* ctx, const void* flow, int n_pairs, int w, int h
  */
 int va_flow_motion(va_ctx* ctx, const void* flow, int n_chains, int chain_len, int trajectory, int w, int h,
                    const void* means, void* out, void* stream);
+
+/*
+ * Warped optical flow, step one: the homography that explains most of each dense flow field, the camera's
+ * motion.  flow f32 [n_fields][2][h][w] -> H f64 [n_fields][3][3] (pixel coordinates, H[2][2] = 1) and stats f64
+ * [n_fields][2] = {share of the frame the last solve trusted (sum of its weights / (w*h)), status}.  Reweighted least
+ * squares in float64 over every pixel's correspondence (x, y) -> (x + dx, y + dy) in normalised coordinates: iters
+ * solves (1..1024), the first with unit weights, the others with Tukey's biweight of the last solution's transfer error
+ * at the squared scale max(cmin_sq, c0_sq * 2^-k) px^2 (0 < cmin_sq <= c0_sq).  A pixel whose flow is not finite has
+ * weight 0.  A field whose 8x8 system has no Cholesky factor (a pivot not above 2^-40 x its largest diagonal entry: too
+ * few pixels, all on a line, none valid) gets H = I and status 1.  The summation order is fixed: a call repeats its bits.
+ */
+int va_flow_homography(va_ctx* ctx, const void* flow, int n_fields, int w, int h, int iters, double c0_sq, double cmin_sq,
+                       void* H, void* stats, void* stream);
+
+/*
+ * Warped optical flow, step two: out = flow minus the camera's displacement field,
+ *   out[n][0](y, x) = flow[n][0](y, x) - (float)(X/D - x), out[n][1](y, x) = flow[n][1](y, x) - (float)(Y/D - y),
+ *   (X, Y, D) = H[n] (x, y, 1)^T in float64, left to right, no fused multiply-add.
+ * H: DEVICE f64 [n_fields][3][3].  out has the flow's shape and pair order (every va_flow_to_stack* and va_flow_motion
+ * applies to it unchanged); it may be the flow buffer itself (in place) or must not overlap it.  H = I returns the flow's
+ * bits.  At most 65535 fields per call.
+ */
+int va_flow_compensate(va_ctx* ctx, const void* flow, int n_fields, int w, int h, const void* H, void* out, void* stream);
 
 /*
  * Self-test of the arithmetic contract: compares the kernel's packed correctly-rounded sqrt and

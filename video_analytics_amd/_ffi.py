@@ -28,6 +28,7 @@ EXPORTS = [
     "va_vgg16_export_state", "va_vgg16_import_state", "va_vgg16_train_plan",
     "va_conv3x3_layer",
     "va_flow_to_stack_resize", "va_resize_images_u8", "va_vgg16_train_step_consensus",
+    "va_flow_homography", "va_flow_compensate",
 ]
 
 
@@ -151,6 +152,10 @@ def lib():
     L.va_flow_field_means.restype = ci
     L.va_flow_motion.argtypes = [vp, vp, ci, ci, ci, ci, ci, vp, vp, vp]
     L.va_flow_motion.restype = ci
+    L.va_flow_homography.argtypes = [vp, vp, ci, ci, ci, ci, ctypes.c_double, ctypes.c_double, vp, vp, vp]
+    L.va_flow_homography.restype = ci
+    L.va_flow_compensate.argtypes = [vp, vp, ci, ci, ci, vp, vp, vp]
+    L.va_flow_compensate.restype = ci
     L.va_selftest_exact_math.argtypes = [vp, cf, cf, vp, vp]
     L.va_selftest_exact_math.restype = ci
     L.va_tvl1_profile_enable.argtypes = [vp, ci]

@@ -287,9 +287,22 @@ def resize_flow_to_stack(flow, table, invert_x_on_flip=False, bound=FLOW_BOUND, 
 MOTIONS = ("stack", "trajectory", "bidirectional")
 
 
-def check_motion(motion, mean_flow, flow_count, who):
+# Camera compensation of the flow: "homography" is TSN's warped optical flow, every field minus the
+# displacement field of the homography fitted to it; it comes before the motion options above, which then see the
+# compensated field in place of the TV-L1 output.
+CAMERAS = ("none", "homography")
+
+
+def check_camera(camera, who):
+    if not isinstance(camera, str) or camera not in CAMERAS:
+        raise ValueError("%s: camera must be one of %s, got %r" % (who, ", ".join(CAMERAS), camera))
+
+
+def check_motion(motion, mean_flow, flow_count, who, camera="none"):
     """Host-side checks of the motion options, before anything is enqueued: an unknown motion, trajectory stacking of
-    bi-directional flow (the paper does not combine them) and bi-directional flow of an odd L raise ValueError."""
+    bi-directional flow (the paper does not combine them), bi-directional flow of an odd L and an unknown camera raise
+    ValueError."""
+    check_camera(camera, who)
     parts = motion.split("+") if isinstance(motion, str) else list(motion) if isinstance(motion, (tuple, list)) else []
     if "trajectory" in parts and "bidirectional" in parts:
         raise ValueError("%s: trajectory stacking of bi-directional flow is not offered (the two-stream paper does not "
@@ -362,9 +375,68 @@ def motion_field(flow, flow_count, trajectory=False, means=None, out=None):
     return out.view(N, 2, H, W)
 
 
-def apply_motion(flow, flow_count, motion="stack", mean_flow=False, out=None):
+def fit_homography(flow, iters=16, c0=16.0, c_min=1.0):
+    """S21: flow ``[N,2,H,W]`` float32 -> ``(H [N,3,3] float64, stats [N,2] float64)`` on the flow's device: per field the
+    homography (pixel coordinates, ``H[2,2] = 1``) that a Tukey-reweighted least-squares fit over every pixel's
+    correspondence finds -- the camera's motion where the background covers most of the frame -- and
+    ``stats[:,0]`` the share of the frame the last solve trusted, ``stats[:,1]`` 1.0 for a degenerate field (``H = I``).
+    ``iters`` solves; the scale of the biweight anneals from ``c0`` px, halving its square every iteration, to ``c_min`` px."""
+    _check_flow(flow, "fit_homography")
+    try:
+        iters, c0, c_min = int(iters), float(c0), float(c_min)
+    except (TypeError, ValueError):
+        raise ValueError("fit_homography: iters, c0 and c_min must be numbers")
+    if not 1 <= iters <= 1024:
+        raise ValueError("fit_homography: iters must be in 1..1024, got %d" % iters)
+    if not (0.0 < c_min <= c0 < 1e150):
+        raise ValueError("fit_homography: need 0 < c_min <= c0, got c0=%r c_min=%r" % (c0, c_min))
+    flow = flow.contiguous()
+    N, _, H, W = flow.shape
+    Hm = torch.empty((N, 3, 3), dtype=torch.float64, device=flow.device)
+    stats = torch.empty((N, 2), dtype=torch.float64, device=flow.device)
+    _ffi.check(_ffi.lib().va_flow_homography(_ffi.ctx(flow.device.index), _ffi.ptr(flow), N, W, H, iters, c0 * c0,
+                                             c_min * c_min, _ffi.ptr(Hm), _ffi.ptr(stats), _ffi.stream_ptr(flow.device)))
+    return Hm, stats
+
+
+def compensate_camera(flow, H, out=None):
+    """S22: flow ``[N,2,H,W]`` float32 minus the displacement field of ``H`` (CUDA float64 ``[N,3,3]``, ``fit_homography``)
+    -> a float32 array of the same shape and pair order, which every S9 - S17 consumer takes as it takes flow.  ``out``
+    may be ``flow`` itself (in place) or must not overlap it."""
+    _check_flow(flow, "compensate_camera")
+    N, _, h, w = flow.shape
+    if (not isinstance(H, torch.Tensor) or H.dtype != torch.float64 or H.device != flow.device
+            or tuple(H.shape) != (N, 3, 3)):
+        raise ValueError("compensate_camera: H must be a float64 [%d,3,3] tensor on the flow's device" % N)
+    if out is not None and not flow.is_contiguous():
+        raise ValueError("compensate_camera: with out=, flow must be contiguous")
+    flow = flow.contiguous()
+    H = H.contiguous()
+    out = _check_out(out, (N, 2, h, w), flow, "compensate_camera")
+    if out.data_ptr() != flow.data_ptr() and _overlaps(out, flow):
+        raise ValueError("compensate_camera: out must be flow itself or must not overlap it")
+    _ffi.check(_ffi.lib().va_flow_compensate(_ffi.ctx(flow.device.index), _ffi.ptr(flow), N, w, h, _ffi.ptr(H), _ffi.ptr(out),
+                                             _ffi.stream_ptr(flow.device)))
+    return out.view(N, 2, h, w)
+
+
+def apply_camera(flow, camera="none", in_place=False):
+    """S21 + S22 for ``camera`` (``CAMERAS``) -> ``(field, H, share)``: with ``"none"`` the flow itself and two Nones (no
+    kernel, no buffer); with ``"homography"`` the compensated field (written over ``flow`` when ``in_place``), the fitted
+    ``H [N,3,3]`` and the trusted share ``[N]`` of every field."""
+    if camera == "none":
+        return flow, None, None
+    H, stats = fit_homography(flow)
+    return compensate_camera(flow, H, out=flow if in_place else None), H, stats[:, 0]
+
+
+def apply_motion(flow, flow_count, motion="stack", mean_flow=False, out=None, camera="none"):
     """The float array S9 / S10 read for the given motion options (checked by ``check_motion``): ``flow`` itself for
-    plain or bi-directional stacking without means (no kernel, no buffer), else ``motion_field`` of it (into ``out``)."""
+    plain or bi-directional stacking without means (no kernel, no buffer), else ``motion_field`` of it (into ``out``).
+    ``camera="homography"`` compensates the camera first (S21, S22, into a new array: ``flow`` is left as it is) and the
+    motion options then act on the compensated field."""
+    if camera != "none":
+        flow = apply_camera(flow, camera)[0]
     if motion != "trajectory" and not mean_flow:
         return flow
     means = flow_field_means(flow) if mean_flow else None

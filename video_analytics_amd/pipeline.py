@@ -81,15 +81,21 @@ class TwoStreamPipeline(object):
 
     ``motion`` / ``mean_flow``: the temporal model's input representation (``flow.MOTIONS``), applied
     to every batch that comes with gray frames.  Bi-directional flow reorders the gray frames on the caller's stream; the
-    means and the trajectory resampling run on the CNN stream into a pipeline-owned full-frame buffer."""
+    means and the trajectory resampling run on the CNN stream into a pipeline-owned full-frame buffer.
+
+    ``camera``: ``"homography"`` turns the flow into TSN's warped optical flow (``flow.CAMERAS``): on the
+    CNN stream, behind the TV-L1 events, a homography is fitted to every field and its displacement field subtracted in
+    place in the slot's flow buffer; the motion options and every gather then read the compensated field.  The results
+    gain ``homography`` f64 ``[pairs,3,3]`` and ``camera_share`` f64 ``[pairs]``."""
 
     def __init__(self, device=None, spatial_seed=1, temporal_seed=2, flow_count=VIDEO_INPUT_FLOW_COUNT,
-                 tvl1_params=None, weights=None, flow_streams=2, cnn_dtype="f32", depth=2, motion="stack", mean_flow=False):
-        vflow.check_motion(motion, mean_flow, flow_count, "TwoStreamPipeline")
+                 tvl1_params=None, weights=None, flow_streams=2, cnn_dtype="f32", depth=2, motion="stack", mean_flow=False,
+                 camera="none"):
+        vflow.check_motion(motion, mean_flow, flow_count, "TwoStreamPipeline", camera=camera)
         dev = torch.device("cuda", torch.cuda.current_device() if device is None else device)
         self.device = dev
         self.L = flow_count
-        self.motion, self.mean_flow = motion, mean_flow
+        self.motion, self.mean_flow, self.camera = motion, mean_flow, camera
         with torch.cuda.device(dev):
             ws = weights[0] if weights else build_stream_weights(3, spatial_seed, dev)
             wt = weights[1] if weights else build_stream_weights(2 * flow_count, temporal_seed, dev)
@@ -122,13 +128,20 @@ class TwoStreamPipeline(object):
             fl = vflow.tvl1_flow_concurrent(tv, self.tvl1_params, self.flow_streams)
         else:
             fl = vflow.tvl1_flow(tv, self.tvl1_params)
-        fl = vflow.apply_motion(fl, self.L, self.motion, self.mean_flow)
+        fl = vflow.apply_motion(fl, self.L, self.motion, self.mean_flow, camera=self.camera)
         return vflow.flow_to_stack(fl).view(B, 2 * self.L, H, W)
 
     def _tvl1_frames(self, gray):
         """The TV-L1 input of gray ``[B,L+1,H,W]``: the frames themselves, or with bi-directional flow the forward and
         backward sequences ``[2B,L/2+1,H,W]`` (S13), reordered on the current stream."""
         return vflow.bidirectional_sequences(gray) if self.motion == "bidirectional" else gray
+
+    def _camera(self, flow, out):
+        """On the CNN stream, after the TV-L1 events and before ``_motion_field``: S21 and S22 in place in the flow buffer
+        (no buffer of its own); the fitted homographies and trusted shares go into the result dict ``out``."""
+        if self.camera != "none":
+            _, out["homography"], out["camera_share"] = vflow.apply_camera(flow, self.camera, in_place=True)
+        return flow
 
     def _motion_field(self, flow, k):
         """On the CNN stream, after the TV-L1 events: the array S9 / S10 read -- the flow itself, or the
@@ -217,6 +230,8 @@ class TwoStreamPipeline(object):
         if flow_stack is not None and (self.motion != "stack" or self.mean_flow):
             raise ValueError("submit: motion=%r / mean_flow=%r need gray frames; flow_stack= is already quantised"
                              % (self.motion, self.mean_flow))
+        if flow_stack is not None and self.camera != "none":
+            raise ValueError("submit: camera=%r needs gray frames; flow_stack= is already quantised" % (self.camera,))
         if views is not None:
             if crops is not None:
                 raise ValueError("submit: views= and crops= exclude each other")
@@ -235,6 +250,7 @@ class TwoStreamPipeline(object):
         k = self._n % self.depth
         self._n += 1
         flow = evs = None
+        extra = {}
         if flow_stack is None:
             B, F, H, W = gray.shape
             fbuf = self._buffer(self._flow, k, (B * self.L, 2, H, W))
@@ -248,7 +264,7 @@ class TwoStreamPipeline(object):
                 for ev in evs:
                     self._cnn.wait_event(ev)
                 B, F, H, W = gray.shape
-                src = self._motion_field(flow, k)
+                src = self._motion_field(self._camera(flow, extra), k)
                 if flow_crops is None:
                     stack = vflow.flow_to_stack(src, out=self._buffer(self._stack, k, (B, 2 * self.L, H, W)))
                 else:  # the flow buffer is full-frame, the volume 224x224
@@ -278,7 +294,7 @@ class TwoStreamPipeline(object):
                 self._cnn.wait_stream(self._cnn2)
             finished = torch.cuda.Event()
             finished.record(self._cnn)
-        out = dict(logits_s=logits_s, logits_t=logits_t, desc_s=desc_s, desc_t=desc_t)
+        out = dict(logits_s=logits_s, logits_t=logits_t, desc_s=desc_s, desc_t=desc_t, **extra)
         self._handed_out.extend(out.values())
         out["done"] = finished  # host-side throttle: out["done"].synchronize() blocks the HOST until this batch is complete
         return out
@@ -305,7 +321,8 @@ class TwoStreamPipeline(object):
             for ev in evs:
                 self._cnn.wait_event(ev)
             Vt = flow_views.shape[0]
-            src = self._motion_field(flow, k)
+            extra = {}
+            src = self._motion_field(self._camera(flow, extra), k)
             stack = vflow.crop_flow_to_stack_views(src, flow_views, self.L, invert_x_on_flip=invert,
                                                    out=self._buffer(self._stack, k, (B, Vt, 2 * self.L, 224, 224)))
             done = torch.cuda.Event()
@@ -319,7 +336,7 @@ class TwoStreamPipeline(object):
             finished = torch.cuda.Event()
             finished.record(self._cnn)
         out = dict(logits_s=logits_s, logits_t=logits_t, desc_s=desc_s, desc_t=desc_t, logits_s_views=logits_sv,
-                   logits_t_views=logits_tv, desc_s_views=desc_sv, desc_t_views=desc_tv)
+                   logits_t_views=logits_tv, desc_s_views=desc_sv, desc_t_views=desc_tv, **extra)
         self._handed_out.extend(out.values())
         out["done"] = finished
         return out
@@ -345,8 +362,9 @@ class TwoStreamPipeline(object):
         ``pred`` int32 ``[]``, ``desc_s``, ``desc_t`` f32 ``[256]`` (the mean over snippets and views in item order),
         ``logits_s_items``, ``logits_t_items`` ``[n,V,C]``, and ``starts`` (the snippets' first pairs, a list), ``plan``,
         ``done``.  The stream layout is ``submit(views=)``'s: the TV-L1 of the next video queues behind this one's.
-        ``mean_flow=True`` subtracts every planned field's own mean; trajectory and bi-directional pipelines raise
-        ValueError, as do bad shapes, a video shorter than one snippet and ``crops=``, before anything is enqueued."""
+        ``mean_flow=True`` subtracts every planned field's own mean and ``camera="homography"`` compensates every planned
+        field (the result gains ``homography`` and ``camera_share``, one entry per planned pair); trajectory and
+        bi-directional pipelines raise ValueError, as do bad shapes, a video shorter than one snippet and ``crops=``, before anything is enqueued."""
         plan, rgb_views, flow_views, mode, wa, wb = self._check_video(rgb, gray, n_snippets, views, consensus, fusion_weights,
                                                                       crops)
         dev = self.device
@@ -370,9 +388,10 @@ class TwoStreamPipeline(object):
             for ev in evs:
                 self._cnn.wait_event(ev)
             Vt = flow_views.shape[0]
-            src = flow
+            extra = {}
+            src = self._camera(flow, extra)  # per planned field, like the means
             if self.mean_flow:  # S11 / S12 per planned field: no chains, so the clip length does not matter
-                src = vflow.apply_motion(flow, 1, "stack", True, out=self._buffer(self._motion, k, tuple(flow.shape)))
+                src = vflow.apply_motion(src, 1, "stack", True, out=self._buffer(self._motion, k, tuple(flow.shape)))
             stack = vflow.crop_flow_to_stack_snippets(src, plan.index, flow_views, self.L, invert_x_on_flip=bool(invert_flow_x),
                                                       out=self._buffer(self._stack, k, (n, Vt, 2 * self.L, 224, 224)))
             done = torch.cuda.Event()
@@ -391,7 +410,7 @@ class TwoStreamPipeline(object):
             finished = torch.cuda.Event()
             finished.record(self._cnn)
         out = dict(scores_s=scores_s[0], scores_t=scores_t[0], scores=scores[0], pred=pred[0], desc_s=desc_s[0], desc_t=desc_t[0],
-                   logits_s_items=logits_sv, logits_t_items=logits_tv)
+                   logits_s_items=logits_sv, logits_t_items=logits_tv, **extra)
         self._handed_out.extend(out.values())
         out["starts"] = list(plan.starts)
         out["plan"] = plan
@@ -478,7 +497,8 @@ class TwoStreamPipeline(object):
 
         Returns a dict: ``stats_s``, ``stats_t`` f32 ``[2]`` = (loss, hits) and ``desc_s``, ``desc_t`` f32 ``[n*k,256]``
         per stream, ready on the current stream, and ``starts``, ``crops``, ``plans``, ``flow`` (the planned TV-L1
-        fields, video-major).  Everything runs in order on the current stream, TV-L1 on the flow streams in between; batches
+        fields, video-major; with ``camera="homography"`` the compensated fields, beside ``homography`` and
+        ``camera_share``).  Everything runs in order on the current stream, TV-L1 on the flow streams in between; batches
         submitted before are waited for, later ones see the updated weights.  A bf16 pipeline, ``n*k > 64``, a video
         shorter than one snippet and a bad table raise ValueError before anything is enqueued."""
         videos, labels, plans, crops = self._check_train_videos(videos, labels, k, starts, crops, rng)
@@ -500,6 +520,8 @@ class TwoStreamPipeline(object):
                 first += [base + j for j in p.index]
                 base += len(p.pairs)
         flow = vflow.tvl1_flow_concurrent(tv, self.tvl1_params, self.flow_streams)
+        extra = {}
+        flow = self._camera(flow, extra)  # per planned field, in place: everything below reads the compensated field
         if self.motion == "trajectory":  # S12 chains follow a window: the windows are laid out one after the other
             idx = torch.tensor([f + j for f in first for j in range(L)], dtype=torch.int64)
             src = vflow.apply_motion(flow[augment.crops_to_device(idx, dev)], L, "trajectory", self.mean_flow)
@@ -518,7 +540,7 @@ class TwoStreamPipeline(object):
         self._cnn.wait_stream(cur)
         self._cnn2.wait_stream(cur)
         return dict(stats_s=stats_s, desc_s=desc_s, stats_t=stats_t, desc_t=desc_t, starts=[list(p.starts) for p in plans],
-                    crops=crops, plans=plans, flow=flow)
+                    crops=crops, plans=plans, flow=flow, **extra)
 
     def wait(self, stream=None):
         """Make ``stream`` (default: the current one) wait for every batch submitted so far."""

@@ -314,6 +314,24 @@ int va_resize_images_u8(va_ctx* ctx, const void* src, int n, int c, int w, int h
                         void* dst, void* stream);
 
 /*
+ * The RGB-difference volume, TSN's third input modality (Sheet03/notes.txt:187-191): frames u8
+ * [n_frames][3][h][w] or (src_nhwc) [n_frames][h][w][3] -> stack f32 [n_out][3*n_diff][224][224].  n_diff = D, 1 <= D,
+ * 3*D <= 64.  table: DEVICE i32 [n_out][6] rows {src, top, left, ch, cw, flip} in the crop-resize gathers' format; src is
+ * the FIRST frame of the item's window of D + 1 frames, src + D <= n_frames - 1 (validated by the host wrapper; the device
+ * clamps src to [0, n_frames - 1 - D] and the rectangle as the crop-resize gathers do).  den: HOST float[3],
+ * den[c] = 255.0f * std[c] rounded to f32 once on the host, finite and > 0.
+ * For frame src + j (j = 0..D) and channel c let r_j,c(y, x) be the u8 value va_resize_images_u8 gives for that frame,
+ * channel and table row (S17's val, clamped, rintf; same taps, same order, no fmaf; at ch = cw = 224 the plain crop).
+ * Plane 3j + c of item o holds (float)((int)r_{j+1},c - (int)r_j,c) / den[c], one IEEE f32 division: every frame is
+ * transformed identically and normalised, then neighbours are subtracted (TSN's order), so the mean cancels exactly and the
+ * integer difference is exact in f32; a horizontal flip mirrors the images and changes no sign; resampling before
+ * differencing makes the result equal to differences of va_resize_images_u8 outputs bit for bit.
+ * n_out <= 65535 per call; n_frames > D.  Bad arguments: VA_ERR_INVALID.
+ */
+int va_rgbdiff_to_stack(va_ctx* ctx, const void* frames, int n_frames, int w, int h, int src_nhwc, int n_diff,
+                        const float* den, const void* table, int n_out, void* stack, void* stream);
+
+/*
  * Mean flow subtraction, step one: flow f32 [n_pairs][2][h][w] -> means f32 [n_pairs][2], the mean of
  * every displacement field's component over the full frame.  Each value is clamped to [-32768, 32768] (a NaN becomes
  * -32768) and summed as the exact integer rint(a * 65536) in int64, so the result does not depend on the reduction
@@ -449,6 +467,15 @@ int va_score_consensus(va_ctx* ctx, const void* logits, int n, int k, int c, int
  */
 int va_fuse_scores(va_ctx* ctx, const void* a, const void* b, int n, int c, float wa, float wb, void* fused, void* pred,
                    void* stream);
+
+/*
+ * Fusion of m streams' scores by weighted averaging: scores: HOST array of m DEVICE pointers to f32 [n][c];
+ * weights: HOST float[m]; 2 <= m <= 8.  fused f32 [n][c] = (((w0*a0 + w1*a1) + w2*a2) + ...) / (((w0 + w1) + w2) + ...),
+ * every operation rounded to f32, in stream order; pred i32 [n], the arg-max of fused with the first maximum winning.  Every
+ * weight finite and >= 0 with a positive (finite) sum, else VA_ERR_INVALID.  m = 2 gives va_fuse_scores' bits.
+ */
+int va_fuse_scores_n(va_ctx* ctx, const void* const* scores, const float* weights, int m, int n, int c, void* fused,
+                     void* pred, void* stream);
 
 /* ------------------------------------------------------------------ training step --- */
 

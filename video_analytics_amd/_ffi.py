@@ -29,6 +29,7 @@ EXPORTS = [
     "va_conv3x3_layer",
     "va_flow_to_stack_resize", "va_resize_images_u8", "va_vgg16_train_step_consensus",
     "va_flow_homography", "va_flow_compensate",
+    "va_rgbdiff_to_stack", "va_fuse_scores_n",
 ]
 
 
@@ -142,10 +143,14 @@ def lib():
     L.va_flow_to_stack_resize.restype = ci
     L.va_resize_images_u8.argtypes = [vp, vp, ci, ci, ci, ci, ci, vp, ci, vp, vp]
     L.va_resize_images_u8.restype = ci
+    L.va_rgbdiff_to_stack.argtypes = [vp, vp, ci, ci, ci, ci, ci, fpp, vp, ci, vp, vp]
+    L.va_rgbdiff_to_stack.restype = ci
     L.va_score_consensus.argtypes = [vp, vp, ci, ci, ci, ci, vp, vp]
     L.va_score_consensus.restype = ci
     L.va_fuse_scores.argtypes = [vp, vp, vp, ci, ci, cf, cf, vp, vp, vp]
     L.va_fuse_scores.restype = ci
+    L.va_fuse_scores_n.argtypes = [vp, pp, fpp, ci, ci, ci, vp, vp, vp]
+    L.va_fuse_scores_n.restype = ci
     L.va_view_mean.argtypes = [vp, vp, ci, ci, ci, vp, vp]
     L.va_view_mean.restype = ci
     L.va_flow_field_means.argtypes = [vp, vp, ci, ci, ci, vp, vp]

@@ -287,6 +287,96 @@ __global__ void __launch_bounds__(kResizeThreads) k_resize_images_u8(const unsig
     }
 }
 
+// S23, the RGB-difference gather: frames u8 [n_frames][3][h][w] (NHWC = false) or [n_frames][h][w][3] (true) -> stack f32
+// [n_out][3*D][224][224].  Block row blockIdx.y = the output ITEM (not a plane): table row {src, top, left, ch, cw, flip} with
+// src the first of the item's D + 1 frames.  The thread layout is k_resize_images_u8's (4 x 4 outputs a thread, 448 threads,
+// 7 workgroups an item); a thread computes its column taps once per item and its four rows' taps once, then walks channel
+// by channel through frames src .. src + D, keeping the previous frame's 16 resampled u8 values in registers, so that every
+// source frame is read once.  Plane 3j + c = (float)((int)r_{j+1,c} - (int)r_{j,c}) / den_c with r the value
+// k_resize_images_u8 writes: each difference row of a thread is one 16-byte non-temporal store (scalar stores when the stack
+// is not 16-byte aligned).  No LDS, no atomics.
+template <bool NHWC>
+__global__ void __launch_bounds__(kResizeThreads) k_rgbdiff_stack(const unsigned char* __restrict__ src,
+                                                                  const int* __restrict__ table, float* __restrict__ stack,
+                                                                  int n_frames, int n_diff, int w, int h, int vec4, float den0,
+                                                                  float den1, float den2)
+{
+    constexpr int kPlane = kResizeSize * kResizeSize;
+    const int o = blockIdx.y;
+    const ResizeWin r = load_resize(table, o, n_frames - n_diff, h, w);  // src + n_diff <= n_frames - 1
+    const int cg = threadIdx.x % kResizeColGroups, rg = blockIdx.x * kResizeRowGroups + threadIdx.x / kResizeColGroups;
+    // element (sy, sx) of channel chn of frame f: src[f * frame + chn * chn_stride + sy * sy_stride + sx * sx_stride]; the
+    // frame, channel and crop corner are the same for the whole workgroup (a scalar base), a thread's own taps 32-bit offsets
+    // from it (the entry point refuses frames of 2^31 bytes or more)
+    const int sx_stride = NHWC ? 3 : 1, sy_stride = w * sx_stride;
+    const size_t frame = (size_t)3 * h * w, chn_stride = NHWC ? 1 : (size_t)h * w;
+    // (the table row is one per workgroup: saying so keeps the base in scalar registers and the loads in base + offset form)
+    const size_t corner = (size_t)__builtin_amdgcn_readfirstlane(r.src) * frame +
+                          (size_t)__builtin_amdgcn_readfirstlane(r.top * sy_stride + r.left * sx_stride);
+    const unsigned char* __restrict__ first = src + corner;
+    float* __restrict__ out = stack + (size_t)o * 3 * n_diff * kPlane + (size_t)(4 * rg) * kResizeSize + 4 * cg;
+    unsigned x0[4], x1[4], ra[4], rb[4];
+    float ax[4], ay[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int x = 4 * cg + k;
+        int i0, i1;
+        resize_tap(r.flip ? kResizeSize - 1 - x : x, r.cw, i0, i1, ax[k]);
+        x0[k] = (unsigned)(i0 * sx_stride);
+        x1[k] = (unsigned)(i1 * sx_stride);
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        int y0, y1;
+        resize_tap(4 * rg + j, r.ch, y0, y1, ay[j]);
+        ra[j] = (unsigned)(y0 * sy_stride);
+        rb[j] = (unsigned)(y1 * sy_stride);
+    }
+    for (int chn = 0; chn < 3; ++chn) {
+        const float den = chn == 0 ? den0 : (chn == 1 ? den1 : den2);
+        const unsigned char* __restrict__ plane = first + chn * chn_stride;
+        int prev[16];
+#pragma unroll 1
+        for (int f = 0; f <= n_diff; ++f) {
+            int cur[16];
+            // The frame's offset and the taps are made opaque to the optimiser here (no instruction is emitted): the loads
+            // then take the form scalar base + 32-bit offset, 16 tap registers in all.  Without it the 64 addresses are
+            // hoisted out of the loop as 64 per-thread 64-bit pointers advanced frame by frame: 128 registers, and spills.
+            size_t foff = f * frame;
+            asm volatile("" : "+s"(foff));
+            const unsigned char* __restrict__ base = plane + foff;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) asm volatile("" : "+v"(x0[k]), "+v"(x1[k]), "+v"(ra[k]), "+v"(rb[k]));
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const float val = resize_lerp((float)base[ra[j] + x0[k]], (float)base[ra[j] + x1[k]], (float)base[rb[j] + x0[k]],
+                                                  (float)base[rb[j] + x1[k]], ax[k], ay[j]);
+                    cur[4 * j + k] = (int)rintf(fminf(fmaxf(val, 0.0f), 255.0f));
+                }
+            }
+            if (f > 0) {
+                float* __restrict__ dst = out + (size_t)(3 * (f - 1) + chn) * kPlane;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    float d4[4];
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) d4[k] = (float)(cur[4 * j + k] - prev[4 * j + k]) / den;
+                    if (vec4) {  // 16-byte aligned stack: streamed past the caches, as k_flow_resize_stack's
+                        __builtin_nontemporal_store(f32x4{d4[0], d4[1], d4[2], d4[3]}, reinterpret_cast<f32x4*>(dst + j * kResizeSize));
+                    } else {
+#pragma unroll
+                        for (int k = 0; k < 4; ++k) dst[j * kResizeSize + k] = d4[k];
+                    }
+                }
+            }
+#pragma unroll
+            for (int i = 0; i < 16; ++i) prev[i] = cur[i];
+        }
+    }
+}
+
 // The mean over V views: x f32 [n][V][d] -> out f32 [n][d], out = (((x_0 + x_1) + ...) + x_{V-1}) / V in view order.  One
 // thread per (b, j); the loads of a wave are contiguous in j.
 __global__ void __launch_bounds__(256) k_view_mean(const float* __restrict__ x, float* __restrict__ out, int n, int n_views,
@@ -458,6 +548,35 @@ extern "C" int va_resize_images_u8(va_ctx* ctx, const void* src, int n, int c, i
     else
         k_resize_images_u8<false><<<g, kResizeThreads, 0, (hipStream_t)stream>>>((const unsigned char*)src, (const int*)table,
                                                                                  (unsigned char*)dst, n, c, w, h, vec4);
+    VA_LAUNCH_CHECK();
+    return VA_OK;
+}
+
+extern "C" int va_rgbdiff_to_stack(va_ctx* ctx, const void* frames, int n_frames, int w, int h, int src_nhwc, int n_diff,
+                                   const float* den, const void* table, int n_out, void* stack, void* stream)
+{
+    VA_CHECK_ARG(ctx != nullptr, "va_rgbdiff_to_stack: ctx is NULL");
+    VA_USE_DEVICE(ctx);
+    VA_CHECK_ARG(frames != nullptr && den != nullptr && table != nullptr && stack != nullptr, "va_rgbdiff_to_stack: NULL buffer");
+    VA_CHECK_ARG(w >= 1 && h >= 1 && n_out >= 1 && 3LL * w * h <= 0x7fffffffLL, "va_rgbdiff_to_stack: bad shape");
+    VA_CHECK_ARG(src_nhwc == 0 || src_nhwc == 1, "va_rgbdiff_to_stack: src_nhwc must be 0 or 1");
+    VA_CHECK_ARG(n_diff >= 1 && 3 * (long long)n_diff <= 64, "va_rgbdiff_to_stack: n_diff must lie in 1..21 (3*n_diff <= 64 channels), got %d",
+                 n_diff);
+    VA_CHECK_ARG(n_frames > n_diff && n_frames <= 0x3fffffff, "va_rgbdiff_to_stack: %d frames do not hold a window of %d differences",
+                 n_frames, n_diff);
+    VA_CHECK_ARG(n_out <= kMaxGridY, "va_rgbdiff_to_stack: %d output items exceed %d per call", n_out, kMaxGridY);
+    for (int c = 0; c < 3; ++c)
+        VA_CHECK_ARG(den[c] > 0.0f && den[c] <= 3.0e38f, "va_rgbdiff_to_stack: den[%d] must be finite and > 0", c);
+    const dim3 g(kResizeBlocks, (unsigned)n_out);
+    const int vec4 = reinterpret_cast<uintptr_t>(stack) % 16 == 0;
+    if (src_nhwc)
+        k_rgbdiff_stack<true><<<g, kResizeThreads, 0, (hipStream_t)stream>>>((const unsigned char*)frames, (const int*)table,
+                                                                             (float*)stack, n_frames, n_diff, w, h, vec4, den[0],
+                                                                             den[1], den[2]);
+    else
+        k_rgbdiff_stack<false><<<g, kResizeThreads, 0, (hipStream_t)stream>>>((const unsigned char*)frames, (const int*)table,
+                                                                              (float*)stack, n_frames, n_diff, w, h, vec4, den[0],
+                                                                              den[1], den[2]);
     VA_LAUNCH_CHECK();
     return VA_OK;
 }

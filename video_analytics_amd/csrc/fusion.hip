@@ -158,6 +158,42 @@ __global__ void __launch_bounds__(256) k_fuse_scores(const float* __restrict__ a
     }
 }
 
+// S24, the fusion of m streams: fused = (((w0*a0 + w1*a1) + w2*a2) + ...) / (((w0 + w1) + w2) + ...), every operation
+// rounded to f32 in stream order; the arg-max as k_fuse_scores'.  m = 2 is k_fuse_scores' expression.
+constexpr int kFuseMaxStreams = 8;
+struct FuseStreams {
+    const float* p[kFuseMaxStreams];
+    float w[kFuseMaxStreams];
+};
+
+__device__ __forceinline__ float fuse_n(const FuseStreams& s, int m, size_t i, float wsum)
+{
+    float acc = s.w[0] * s.p[0][i];
+#pragma unroll  // constant indices into the kernel arguments: no private copy of the struct
+    for (int k = 1; k < kFuseMaxStreams; ++k)
+        if (k < m) acc = acc + s.w[k] * s.p[k][i];
+    return acc / wsum;
+}
+
+__global__ void __launch_bounds__(256) k_fuse_scores_n(FuseStreams s, int m, int c, float* __restrict__ fused, int* __restrict__ pred)
+{
+    const size_t row = (size_t)blockIdx.x * c;
+    float wsum = s.w[0];
+#pragma unroll
+    for (int k = 1; k < kFuseMaxStreams; ++k)
+        if (k < m) wsum = wsum + s.w[k];
+    for (int j = threadIdx.x; j < c; j += 256) fused[row + j] = fuse_n(s, m, row + j, wsum);
+    if (threadIdx.x == 0) {
+        float mx = fuse_n(s, m, row, wsum);
+        int am = 0;
+        for (int j = 1; j < c; ++j) {
+            const float f = fuse_n(s, m, row + j, wsum);
+            if (f > mx) { mx = f; am = j; }
+        }
+        pred[blockIdx.x] = am;
+    }
+}
+
 }  // namespace
 
 static constexpr int kConsensusMaxItems = 4096, kConsensusMaxClasses = 4096;  // (2k + c) floats of LDS: at most 48 KB
@@ -187,6 +223,30 @@ extern "C" int va_fuse_scores(va_ctx* ctx, const void* a, const void* b, int n, 
     VA_CHECK_ARG(wa >= 0.0f && wb >= 0.0f && wa + wb > 0.0f && wa + wb <= 3.0e38f,
                  "va_fuse_scores: need finite weights >= 0 with a positive sum (got %g, %g)", (double)wa, (double)wb);
     k_fuse_scores<<<n, 256, 0, (hipStream_t)stream>>>((const float*)a, (const float*)b, c, wa, wb, (float*)fused, (int*)pred);
+    VA_LAUNCH_CHECK();
+    return VA_OK;
+}
+
+extern "C" int va_fuse_scores_n(va_ctx* ctx, const void* const* scores, const float* weights, int m, int n, int c, void* fused,
+                                void* pred, void* stream)
+{
+    VA_CHECK_ARG(ctx != nullptr, "va_fuse_scores_n: ctx is NULL");
+    VA_USE_DEVICE(ctx);
+    VA_CHECK_ARG(m >= 2 && m <= kFuseMaxStreams, "va_fuse_scores_n: need 2 <= m <= %d streams (got %d)", kFuseMaxStreams, m);
+    VA_CHECK_ARG(scores && weights && fused && pred, "va_fuse_scores_n: NULL pointer");
+    VA_CHECK_ARG(n >= 1 && c >= 1, "va_fuse_scores_n: need n >= 1 and c >= 1 (got %d, %d)", n, c);
+    FuseStreams s = {};
+    float wsum = 0.0f;
+    for (int k = 0; k < m; ++k) {
+        VA_CHECK_ARG(scores[k] != nullptr, "va_fuse_scores_n: scores[%d] is NULL", k);
+        VA_CHECK_ARG(weights[k] >= 0.0f && weights[k] <= 3.0e38f, "va_fuse_scores_n: need finite weights >= 0 (weights[%d] = %g)", k,
+                     (double)weights[k]);
+        s.p[k] = (const float*)scores[k];
+        s.w[k] = weights[k];
+        wsum = k == 0 ? weights[0] : wsum + weights[k];
+    }
+    VA_CHECK_ARG(wsum > 0.0f && wsum <= 3.0e38f, "va_fuse_scores_n: the weights need a positive finite sum (got %g)", (double)wsum);
+    k_fuse_scores_n<<<n, 256, 0, (hipStream_t)stream>>>(s, m, c, (float*)fused, (int*)pred);
     VA_LAUNCH_CHECK();
     return VA_OK;
 }

@@ -5,8 +5,11 @@
 needs no device-to-host copy; ``linear_svm_predict`` is ``LinearSVC.predict`` of the fusion step
 (Sheet03/combinedModel.py:38) on the joined descriptors.  ``score_consensus`` and ``fuse_scores`` are the video-level
 half of the papers' test protocol (Sheet03/notes.txt:113-116, 121-124, 225-230): the class scores of a
-video's snippets and views averaged, then the two streams' scores fused by a weighted average.
+video's snippets and views averaged, then the two streams' scores fused by a weighted average (``fuse_scores_n``: any
+number of streams up to eight).
 """
+import ctypes
+
 import numpy as np
 import torch
 
@@ -143,6 +146,54 @@ def fuse_scores(a, b, weights=(1.0, 1.0)):
     pred = torch.empty((N,), dtype=torch.int32, device=a.device)
     _ffi.check(_ffi.lib().va_fuse_scores(_ffi.ctx(a.device.index), _ffi.ptr(a), _ffi.ptr(b), N, C, wa, wb, _ffi.ptr(fused),
                                          _ffi.ptr(pred), _ffi.stream_ptr(a.device)))
+    return fused, pred
+
+
+def check_fusion_weights_n(weights, m, who):
+    """-> the m weights as a tuple of floats; ValueError unless there are exactly ``m`` (2..8) of them, each finite (as a
+    float32 too) and >= 0, with a positive sum."""
+    m = int(m)
+    if m < 2 or m > 8:
+        raise ValueError("%s: fusion takes 2..8 streams, got %d" % (who, m))
+    try:
+        ws = tuple(float(w) for w in weights)
+    except (TypeError, ValueError):
+        raise ValueError("%s: fusion weights must be %d numbers, got %r" % (who, m, weights))
+    if len(ws) != m:
+        raise ValueError("%s: %d fusion weights for %d streams" % (who, len(ws), m))
+    with np.errstate(over="ignore"):
+        w32 = np.asarray(ws, dtype=np.float32)
+        total = np.float32(0.0)
+        for w in w32:
+            total = np.float32(total + w)
+    if not np.isfinite(w32).all() or (w32 < 0).any() or not np.isfinite(total) or not sum(ws) > 0 or not total > 0:
+        raise ValueError("%s: fusion weights must be finite and >= 0 with a positive sum, got %r" % (who, ws))
+    return ws
+
+
+def fuse_scores_n(scores, weights=None):
+    """Fusion of m streams by weighted averaging (``va_fuse_scores_n``): scores a list of m (2..8) CUDA
+    float32 ``[N,C]`` tensors, ``weights`` m numbers (None: all ones) -> ``(fused [N,C] float32, pred [N] int32)``,
+    ``fused = (((w0*a0 + w1*a1) + w2*a2) + ...) / (((w0 + w1) + w2) + ...)`` with every operation rounded to float32 in
+    stream order, and ``pred`` its arg-max with the first maximum winning.  m = 2 gives ``fuse_scores``' bits."""
+    if not isinstance(scores, (tuple, list)):
+        raise ValueError("fuse_scores_n: scores must be a list of CUDA float32 [N,C] tensors")
+    m = len(scores)
+    ws = check_fusion_weights_n((1.0,) * m if weights is None else weights, m, "fuse_scores_n")
+    for t in scores:
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32 or t.dim() != 2:
+            raise ValueError("fuse_scores_n: scores must be CUDA float32 [N,C] tensors")
+    a = scores[0]
+    if any(t.shape != a.shape or t.device != a.device for t in scores) or a.shape[0] < 1 or a.shape[1] < 1:
+        raise ValueError("fuse_scores_n: the scores must have one non-empty shape on one device")
+    scores = [t.contiguous() for t in scores]
+    N, C = int(a.shape[0]), int(a.shape[1])
+    fused = torch.empty((N, C), dtype=torch.float32, device=a.device)
+    pred = torch.empty((N,), dtype=torch.int32, device=a.device)
+    ptrs = (ctypes.c_void_p * m)(*[t.data_ptr() for t in scores])
+    cw = (ctypes.c_float * m)(*ws)
+    _ffi.check(_ffi.lib().va_fuse_scores_n(_ffi.ctx(a.device.index), ptrs, cw, m, N, C, _ffi.ptr(fused), _ffi.ptr(pred),
+                                           _ffi.stream_ptr(a.device)))
     return fused, pred
 
 

@@ -12,7 +12,7 @@ forward (Sheet03/spatialModel.py:212-218, Sheet03/temporalModel.py:241-247).
 import torch
 
 from . import flow as vflow
-from . import augment, fusion, synth, vgg, video
+from . import augment, fusion, rgbdiff, synth, vgg, video
 from .parameters import (NACTION_CLASSES, NORM_MEANS_TF, NORM_STDS_TF, VIDEO_DESCRIPTOR_DIM,
                          VIDEO_INPUT_FLOW_COUNT)
 
@@ -86,12 +86,22 @@ class TwoStreamPipeline(object):
     ``camera``: ``"homography"`` turns the flow into TSN's warped optical flow (``flow.CAMERAS``): on the
     CNN stream, behind the TV-L1 events, a homography is fitted to every field and its displacement field subtracted in
     place in the slot's flow buffer; the motion options and every gather then read the compensated field.  The results
-    gain ``homography`` f64 ``[pairs,3,3]`` and ``camera_share`` f64 ``[pairs]``."""
+    gain ``homography`` f64 ``[pairs,3,3]`` and ``camera_share`` f64 ``[pairs]``.
+
+    ``rgb_diff``: True adds TSN's RGB-difference stream: ``self.diff``, a third VGG-16 of
+    ``3 * rgb_diff_count`` input channels (seed ``diff_seed`` or ``weights[2]``; its first layer is the cross-modality copy of
+    an RGB one) that ``submit_video`` / ``run_video`` and ``train_videos`` feed with the differences of each snippet's first
+    ``rgb_diff_count + 1`` RGB frames.  ``submit`` / ``run_batch`` receive one RGB frame per clip: they ignore the third
+    stream.  With the default nothing is allocated and every result keeps its bits."""
 
     def __init__(self, device=None, spatial_seed=1, temporal_seed=2, flow_count=VIDEO_INPUT_FLOW_COUNT,
                  tvl1_params=None, weights=None, flow_streams=2, cnn_dtype="f32", depth=2, motion="stack", mean_flow=False,
-                 camera="none"):
+                 rgb_diff=False, rgb_diff_count=rgbdiff.RGB_DIFF_COUNT, diff_seed=3, camera="none"):
         vflow.check_motion(motion, mean_flow, flow_count, "TwoStreamPipeline", camera=camera)
+        self.D = rgbdiff.check_diff_count(rgb_diff_count, flow_count, "TwoStreamPipeline") if rgb_diff else 0
+        if weights and len(weights) != (3 if rgb_diff and len(weights) > 2 else 2):
+            raise ValueError("TwoStreamPipeline: weights= holds the spatial and temporal weights, and a third entry only with "
+                             "rgb_diff=True; got %d entries" % len(weights))
         dev = torch.device("cuda", torch.cuda.current_device() if device is None else device)
         self.device = dev
         self.L = flow_count
@@ -104,6 +114,11 @@ class TwoStreamPipeline(object):
                                            dtype=cnn_dtype)
             self.temporal = vgg.Vgg16Stream(wt["conv_w"], wt["conv_b"], wt["fc_w"], wt["fc_b"], NACTION_CLASSES,
                                             VIDEO_DESCRIPTOR_DIM, device=dev.index, dtype=cnn_dtype)
+            self.diff = None
+            if rgb_diff:  # float input (the differences are normalised by the gather), a workspace of its own
+                wd = weights[2] if weights and len(weights) > 2 else build_stream_weights(3 * self.D, diff_seed, dev)
+                self.diff = vgg.Vgg16Stream(wd["conv_w"], wd["conv_b"], wd["fc_w"], wd["fc_b"], NACTION_CLASSES,
+                                            VIDEO_DESCRIPTOR_DIM, device=dev.index, ws_slot=2, dtype=cnn_dtype)
         self.tvl1_params = tvl1_params
         self.flow_streams = max(1, int(flow_streams))
         self.depth = max(1, int(depth))
@@ -113,6 +128,7 @@ class TwoStreamPipeline(object):
         self._flow = [None] * self.depth      # per slot: flow [pairs,2,H,W] written by the TV-L1 streams
         self._stack = [None] * self.depth     # per slot: flow volume read by the temporal CNN
         self._motion = [None] * self.depth    # per slot: the motion field S9 / S10 read instead of the flow (S12)
+        self._dstack = [None] * self.depth    # per slot: the RGB-difference volume (S23), written and read on the CNN stream
         self._flow_read = [None] * self.depth  # per slot: event "the flow buffer has been quantised" (it may be overwritten)
         self._handed_out = []                 # output tensors allocated on the CNN stream since the last wait()
         self._retired = []                    # dropped cross-stream buffers + the events after which they may be freed
@@ -226,7 +242,9 @@ class TwoStreamPipeline(object):
         view means ``[B,...]`` and ``logits_*_views`` / ``desc_*_views`` hold the per-view outputs ``[B,V,...]``.  Not
         with ``crops=`` or ``flow_stack=``.  ``invert_flow_x``: TSN flips, a mirrored x-flow image becomes
         ``q -> 255 - q`` (with ``views=`` or ``crops=``; the default mirrors without inverting, as the reference).
-        The pipeline's ``motion`` / ``mean_flow`` apply with and without ``crops=`` / ``views=``; they need gray frames."""
+        The pipeline's ``motion`` / ``mean_flow`` apply with and without ``crops=`` / ``views=``; they need gray frames.
+        A batch holds one RGB frame per clip, so an ``rgb_diff=True`` pipeline ignores its third stream here: the results
+        are those of a plain pipeline."""
         if flow_stack is not None and (self.motion != "stack" or self.mean_flow):
             raise ValueError("submit: motion=%r / mean_flow=%r need gray frames; flow_stack= is already quantised"
                              % (self.motion, self.mean_flow))
@@ -342,20 +360,43 @@ class TwoStreamPipeline(object):
         return out
 
     def _check_video(self, rgb, gray, n_snippets, views, consensus, fusion_weights, crops):
-        """Host-side checks of ``submit_video`` before anything is enqueued -> (plan, rgb_views, flow_views, mode, wa, wb)."""
-        checked = check_video(rgb, gray, self.L, self.motion, n_snippets, views, consensus, fusion_weights, crops)
+        """Host-side checks of ``submit_video`` before anything is enqueued -> (plan, rgb_views, flow_views, mode, weights):
+        one fusion weight per stream, None meaning all ones."""
+        m = 2 if self.diff is None else 3
+        if fusion_weights is None:
+            fusion_weights = (1.0,) * m
+        try:
+            given = len(fusion_weights)
+        except TypeError:
+            raise ValueError("submit_video: fusion weights must be %d numbers, got %r" % (m, fusion_weights))
+        if given != m:
+            raise ValueError("submit_video: this pipeline fuses %d streams (spatial, temporal%s), got %d fusion weights"
+                             % (m, ", difference" if m == 3 else "", given))
+        if m == 2:
+            plan, rgb_views, flow_views, mode, wa, wb = check_video(rgb, gray, self.L, self.motion, n_snippets, views, consensus,
+                                                                    fusion_weights, crops)
+            ws = (wa, wb)
+        else:
+            ws = fusion.check_fusion_weights_n(fusion_weights, m, "submit_video")
+            plan, rgb_views, flow_views, mode, _, _ = check_video(rgb, gray, self.L, self.motion, n_snippets, views, consensus,
+                                                                  (1.0, 1.0), crops)
         if not rgb.is_cuda or not gray.is_cuda or rgb.device != self.device or gray.device != self.device:
             raise ValueError("submit_video: rgb and gray must be on %s" % (self.device,))
-        return checked
+        return plan, rgb_views, flow_views, mode, ws
 
     def submit_video(self, rgb, gray, n_snippets=video.N_SNIPPETS, views=None, invert_flow_x=False, consensus="softmax",
-                     fusion_weights=(1.0, 1.0), crops=None):
+                     fusion_weights=None, crops=None):
         """Enqueue one whole video (the test protocol of Sheet03/notes.txt:113-116 and 225-230):
         rgb u8 ``[T,3,H,W]``, gray u8 or f32 ``[T,H,W]``, the frames of one video on the device.  ``n_snippets`` snippets
         are placed by ``video.snippetStarts``; the frame pairs they share go through TV-L1 once each
         (``video.snippetPlan``), every snippet is seen through every view, and the class scores are averaged over snippets
         and views (``consensus``: ``"softmax"`` or ``"logits"``, ``fusion.score_consensus``) and fused with
-        ``fusion_weights`` = (spatial, temporal) (``fusion.fuse_scores``).
+        ``fusion_weights`` = (spatial, temporal) (``fusion.fuse_scores``; None: all ones).
+
+        On an ``rgb_diff=True`` pipeline snippet s also gives the differences of frames ``starts[s] ..
+        starts[s] + rgb_diff_count`` of ``rgb``, read in place through every RGB view (``rgbdiff.rgb_diff_stack``), to the
+        third stream, beside the TV-L1 that is still running; ``fusion_weights`` then takes three entries (spatial, temporal,
+        difference; ``fusion.fuse_scores_n``) and the result gains ``scores_d``, ``desc_d`` and ``logits_d_items``.
 
         ``views=(rgb_views, flow_views)`` as in ``submit(views=)``; None is one view of 224x224 frames.  Returns a dict of
         tensors the CNN stream is still writing (``wait()`` first): ``scores_s``, ``scores_t``, ``scores`` f32 ``[C]``,
@@ -365,8 +406,7 @@ class TwoStreamPipeline(object):
         ``mean_flow=True`` subtracts every planned field's own mean and ``camera="homography"`` compensates every planned
         field (the result gains ``homography`` and ``camera_share``, one entry per planned pair); trajectory and
         bi-directional pipelines raise ValueError, as do bad shapes, a video shorter than one snippet and ``crops=``, before anything is enqueued."""
-        plan, rgb_views, flow_views, mode, wa, wb = self._check_video(rgb, gray, n_snippets, views, consensus, fusion_weights,
-                                                                      crops)
+        plan, rgb_views, flow_views, mode, fw = self._check_video(rgb, gray, n_snippets, views, consensus, fusion_weights, crops)
         dev = self.device
         n, U = plan.n, len(plan.pairs)
         T, H, W = gray.shape
@@ -385,10 +425,16 @@ class TwoStreamPipeline(object):
             self._cnn.wait_event(ready)
             frames.record_stream(self._cnn)
             _, _, desc_sv, logits_sv = self.spatial.forward_views(augment.crop_image_views(frames, rgb_views))
+            extra = {}
+            if self.diff is not None:  # S23 / S25: before the wait, so that it fills the time TV-L1 is still running
+                Vs, C = rgb_views.shape[0], 3 * self.D
+                rgb.record_stream(self._cnn)
+                dstack = rgbdiff.rgb_diff_stack(rgb, rgbdiff.view_table(plan.starts, rgb_views), self.D,
+                                                out=self._buffer(self._dstack, k, (n, Vs, C, 224, 224)))
+                _, _, desc_dv, logits_dv = self.diff.forward_views(dstack.view(n, Vs, C, 224, 224))
             for ev in evs:
                 self._cnn.wait_event(ev)
             Vt = flow_views.shape[0]
-            extra = {}
             src = self._camera(flow, extra)  # per planned field, like the means
             if self.mean_flow:  # S11 / S12 per planned field: no chains, so the clip length does not matter
                 src = vflow.apply_motion(src, 1, "stack", True, out=self._buffer(self._motion, k, tuple(flow.shape)))
@@ -404,9 +450,15 @@ class TwoStreamPipeline(object):
             self._t_done.record(self._cnn)
             scores_s = fusion.score_consensus(logits_sv.unsqueeze(0), consensus)
             scores_t = fusion.score_consensus(logits_tv.unsqueeze(0), consensus)
-            scores, pred = fusion.fuse_scores(scores_s, scores_t, (wa, wb))
             desc_s = vgg.view_mean(desc_sv.view(1, -1, desc_sv.shape[-1]))
             desc_t = vgg.view_mean(desc_tv.view(1, -1, desc_tv.shape[-1]))
+            if self.diff is None:
+                scores, pred = fusion.fuse_scores(scores_s, scores_t, fw)
+            else:
+                scores_d = fusion.score_consensus(logits_dv.unsqueeze(0), consensus)
+                scores, pred = fusion.fuse_scores_n([scores_s, scores_t, scores_d], fw)
+                desc_d = vgg.view_mean(desc_dv.view(1, -1, desc_dv.shape[-1]))
+                extra.update(scores_d=scores_d[0], desc_d=desc_d[0], logits_d_items=logits_dv)
             finished = torch.cuda.Event()
             finished.record(self._cnn)
         out = dict(scores_s=scores_s[0], scores_t=scores_t[0], scores=scores[0], pred=pred[0], desc_s=desc_s[0], desc_t=desc_t[0],
@@ -418,7 +470,7 @@ class TwoStreamPipeline(object):
         return out
 
     def run_video(self, rgb, gray, n_snippets=video.N_SNIPPETS, views=None, invert_flow_x=False, consensus="softmax",
-                  fusion_weights=(1.0, 1.0), crops=None):
+                  fusion_weights=None, crops=None):
         """``submit_video`` + ``wait()``: the results are ready on the current stream."""
         out = self.submit_video(rgb, gray, n_snippets, views, invert_flow_x, consensus, fusion_weights, crops)
         self.wait()
@@ -500,7 +552,11 @@ class TwoStreamPipeline(object):
         fields, video-major; with ``camera="homography"`` the compensated fields, beside ``homography`` and
         ``camera_share``).  Everything runs in order on the current stream, TV-L1 on the flow streams in between; batches
         submitted before are waited for, later ones see the updated weights.  A bf16 pipeline, ``n*k > 64``, a video
-        shorter than one snippet and a bad table raise ValueError before anything is enqueued."""
+        shorter than one snippet and a bad table raise ValueError before anything is enqueued.
+
+        On an ``rgb_diff=True`` pipeline the third stream takes the same step on the differences of each
+        snippet's first ``rgb_diff_count + 1`` RGB frames, seen through the snippet's crop (``rgbdiff.rgb_diff_stack``);
+        the result gains ``stats_d`` and ``desc_d``."""
         videos, labels, plans, crops = self._check_train_videos(videos, labels, k, starts, crops, rng)
         dev, L, n, k = self.device, self.L, len(videos), int(k)
         cur = torch.cuda.current_stream(dev)
@@ -537,6 +593,13 @@ class TwoStreamPipeline(object):
         cur.wait_stream(self._cnn2)
         stats_s, desc_s = self.spatial.train_step_consensus(xs, labels, k, lr, momentum, dropout_seed)
         stats_t, desc_t = self.temporal.train_step_consensus(xt, labels, k, lr, momentum, dropout_seed)
+        if self.diff is not None:  # S25: the windows' frames one after the other, one S23 call on the snippets' crops
+            D = self.D
+            win = torch.cat([rgb[augment.crops_to_device(torch.tensor([s + f for s in p.starts for f in range(D + 1)],
+                                                                       dtype=torch.int64), dev)]
+                             for (rgb, _), p in zip(videos, plans)])  # [n*k*(D+1),3,H,W]
+            xd = rgbdiff.rgb_diff_stack(win, rgbdiff.window_table([i * (D + 1) for i in range(n * k)], crops), D)
+            extra["stats_d"], extra["desc_d"] = self.diff.train_step_consensus(xd, labels, k, lr, momentum, dropout_seed)
         self._cnn.wait_stream(cur)
         self._cnn2.wait_stream(cur)
         return dict(stats_s=stats_s, desc_s=desc_s, stats_t=stats_t, desc_t=desc_t, starts=[list(p.starts) for p in plans],
@@ -562,3 +625,5 @@ class TwoStreamPipeline(object):
         self._cnn.synchronize()
         self.spatial.close()
         self.temporal.close()
+        if self.diff is not None:
+            self.diff.close()

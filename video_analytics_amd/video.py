@@ -124,13 +124,19 @@ def evaluateVideos(pipe, videos, labels, **kw):
     ``(acc_spatial, acc_temporal, acc_fused, descriptors)``: the fractions of videos whose spatial, temporal and fused
     scores have their first maximum at the label, and the float32 ``[N,512]`` joined descriptors (spatial then temporal,
     the layout of ``combineDescriptors``) for SVM fusion.  ``submit_video`` runs one video ahead of the read-back: video
-    i + 1 is enqueued before the host waits for video i."""
+    i + 1 is enqueued before the host waits for video i.
+
+    On a pipeline with the RGB-difference stream (``rgb_diff=True``) the result is
+    ``(acc_spatial, acc_temporal, acc_fused, descriptors, acc_difference)`` with descriptors ``[N,768]`` (spatial, temporal,
+    difference) and ``fusion_weights`` of three entries."""
     labels = [int(l) for l in labels]
     rows, pending, n = [], None, 0
+    third = getattr(pipe, "diff", None) is not None
+    keys = ("scores_s", "scores_t", "pred", "desc_s", "desc_t") + (("desc_d", "scores_d") if third else ())
 
     def collect(out):
         out["done"].synchronize()
-        rows.append(tuple(out[key].cpu().numpy() for key in ("scores_s", "scores_t", "pred", "desc_s", "desc_t")))
+        rows.append(tuple(out[key].cpu().numpy() for key in keys))
 
     for rgb, gray in videos:
         out = pipe.submit_video(rgb, gray, **kw)
@@ -149,5 +155,8 @@ def evaluateVideos(pipe, videos, labels, **kw):
     acc_s = float(np.mean(np.array([int(np.argmax(r[0])) for r in rows]) == y))
     acc_t = float(np.mean(np.array([int(np.argmax(r[1])) for r in rows]) == y))
     acc_f = float(np.mean(np.array([int(r[2]) for r in rows]) == y))
-    desc = np.stack([np.concatenate([r[3], r[4]]) for r in rows]).astype(np.float32)
+    desc = np.stack([np.concatenate(r[3:6]) for r in rows]).astype(np.float32)
+    if third:
+        acc_d = float(np.mean(np.array([int(np.argmax(r[6])) for r in rows]) == y))
+        return acc_s, acc_t, acc_f, desc, acc_d
     return acc_s, acc_t, acc_f, desc

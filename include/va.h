@@ -400,6 +400,58 @@ int va_conv3x3_layer(va_ctx* ctx, int dtype, int kernel_opt, int hw, int cin_pad
                      const void* zeros, void* out, char* kernel_name, int name_len, void* stream);
 
 /*
+ * The kernels of the training step (va_vgg16_train_step), one layer at a time, through the very functions the step
+ * calls, for kernel-by-kernel tests.  fp32 throughout; every pointer 16-byte aligned; shapes the kernels do not take are
+ * VA_ERR_INVALID before anything is launched.  `info`: HOST buffer of info_len bytes or NULL; receives what ran.
+ *
+ * va_train_conv_backward_layer: backward of one 3x3 conv layer.  dy: NHWC [batch][hw][hw][cout], the gradient at the
+ * layer's post-ReLU, pre-pool output (ReLU mask applied); x: the layer's input, NHWC [batch][hw][hw][cin_pad] (channels
+ * >= cin zero); w_packed / mom_w: [cout][9][cin_pad]; bias / mom_b: [cout]; cin: the real input channels.
+ *   dx != NULL: dx = mask?(conv(dy, flip-transpose(w_packed))), NHWC [batch][hw][hw][cin], from the weights BEFORE the
+ *     update (k_pack_dgrad_w into wt, then the forward dispatch, kernel_opt = VA_OPT_F32_CONV_KERNEL); mask: f32 shaped
+ *     like dx or NULL (dx is zeroed where mask <= 0).  Needs cin == cin_pad, cin % 64 == 0.
+ *   then, in place: g_w = sum over pixels of dy x (k_conv_wgrad into slab, k_wgrad_reduce_sgd), g_b = sum of dy
+ *     (k_conv_bgrad_partial into bpart, k_conv_bgrad_sgd); V = momentum V + g; W -= lr V.
+ * cin_pad and cout: multiples of 4 (16-byte loads); with dx: cout a multiple of 16, cin of 64; batch 1..64; 1 <= cin <= cin_pad.
+ * Scratch: slab, wt (may be NULL when dx is), bpart; scratch_floats: HOST array of 3 = {slab, wt, bpart} in floats: on
+ * entry the sizes given, on return the sizes needed (wt = cin 9 cout; bpart = blocks cout; slab = S Mpad Npad of the
+ * reported plan).  slab == NULL: size query, nothing is launched.  Too small: VA_ERR_WORKSPACE.
+ * info: "k_conv_wgrad<1,3> S=2 chunk=304 Mpad=64 Npad=192 bgrad_blocks=588 dgrad=k_conv3x3_dma_f32<1,false,3>"
+ * (dgrad=none without dx).  zeros: >= max(512, cin) zero floats.
+ */
+int va_train_conv_backward_layer(va_ctx* ctx, int kernel_opt, int batch, int hw, int cin, int cin_pad, int cout,
+                                 const float* dy, const float* x, float* w_packed, float* bias, float* mom_w, float* mom_b,
+                                 float lr, float momentum, float* dx, const float* mask, const float* zeros, float* slab,
+                                 float* wt, float* bpart, size_t* scratch_floats, char* info, int info_len, void* stream);
+/*
+ * Backward of one Linear layer (fc_backward_dispatch): dz f32 [batch][out_f], x f32 [batch][in_f] (the layer's input),
+ * w / mom_w [out_f][in_f], bias / mom_b [out_f].  dx [batch][in_f] = dz W (weights before the update), times `scale`
+ * where mask > 0 and 0 elsewhere (mask f32 [batch][in_f] or NULL: no mask, no scale); then in place
+ * V = momentum V + dz^T x, W -= lr V, and the same for the bias.  batch 1..64, out_f, in_f >= 1.
+ * info: "k_fc_dx<32>" (batch <= 32) or "k_fc_dx<64>": the instantiation of all three classifier kernels.
+ */
+int va_train_fc_backward_layer(va_ctx* ctx, int batch, int out_f, int in_f, const float* dz, const float* x, float* w,
+                               float* bias, float* mom_w, float* mom_b, float lr, float momentum, float* dx,
+                               const float* mask, float scale, char* info, int info_len, void* stream);
+/*
+ * 2x2/2 max-pool of y NHWC [batch][hw][hw][c] into p [batch][hw/2][hw/2][c] (k_maxpool) and, when dp != NULL, its
+ * backward fused with the ReLU mask of the pooled value (k_unpool): dy gets dp at the FIRST maximum of each window in
+ * row-major order where p > 0, and 0 everywhere else.  hw even, c a multiple of 4.
+ */
+int va_train_pool_layer(va_ctx* ctx, int batch, int hw, int c, const float* y, float* p, const float* dp, float* dy,
+                        void* stream);
+/*
+ * Loss of the step: k = 0: mean cross-entropy of logits [n][c] (k_ce_fwd_bwd); k >= 1: of the mean over the k snippets
+ * of logits [n][k][c] (k_ce_consensus_fwd_bwd).  labels i64 [n]; dlogits like logits; out f32 [2] = loss, hits.
+ * n >= 1, n * max(k, 1) <= 64, c >= 1.
+ */
+int va_train_loss(va_ctx* ctx, const float* logits, const void* labels, int n, int k, int c, float* dlogits, float* out,
+                  void* stream);
+/* Dropout(p = 0.5) of the step's classifier layer `layer` (0..2) in place on x f32 [n] (k_dropout, keys from
+ * (dropout_seed, layer) as va_vgg16_train_step derives them). */
+int va_train_dropout(va_ctx* ctx, float* x, size_t n, unsigned long long dropout_seed, int layer, void* stream);
+
+/*
  * Measurement hooks (bench.py): when enabled, va_tvl1_flow brackets every run of
  * inner-iteration launches with HIP events on `stream`.  va_tvl1_profile_read synchronises
  * those events and returns, summed over all va_tvl1_flow calls since the last reset:

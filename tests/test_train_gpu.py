@@ -276,7 +276,8 @@ def test_execute_trains_validates_checkpoints_and_resumes(tmp_path, monkeypatch)
 def test_large_batch_step_is_deterministic():
     """Batch 40 takes the 64-row instantiations of the classifier kernels and crosses a batch brick of the
     convolution tiles.  No CPU oracle at this size (minutes on 8 cores): two runs from the same state must give
-    bit-identical statistics, descriptors and parameters (there are no atomics anywhere in the step)."""
+    bit-identical statistics, descriptors and parameters (there are no atomics anywhere in the step), and the step
+    agrees with torch autograd on the GPU (vendor kernels) at the tolerances of the small-batch oracle tests."""
     from video_analytics_amd import synth, vgg
     w = synth.synth_vgg16_weights(c_in=3, seed=12)
     x = torch.from_numpy(synth.hash_uniform(91, 2, 40 * 3 * 224 * 224).reshape(40, 3, 224, 224) * 4.0 - 2.0).cuda()
@@ -292,6 +293,45 @@ def test_large_batch_step_is_deterministic():
     assert torch.equal(outs[0][0], outs[1][0]) and torch.equal(outs[0][1], outs[1][1])
     assert all(torch.equal(a, b) for a, b in zip(outs[0][2], outs[1][2]))
     assert any(not torch.equal(a, b) for a, b in zip(outs[0][2][:26:2], w["conv_w"]))  # conv weights moved
+    # A second witness, which determinism cannot give (two runs overlap their workspace regions the same way): the same step
+    # by torch autograd ON THE GPU -- vendor conv / linear kernels in fp32 and torch.optim.SGD, nothing of this library; the
+    # precedent is test_fp32_stream_against_an_independent_gpu_implementation -- with the dropout masks of the oracle.
+    import time
+    t0 = time.time()
+    loss_g, state_g = _vendor_autograd_step(w, x, y, 1e-4, 0.9, 77)
+    print("batch 40: the vendor-kernel step took %.1f s" % (time.time() - t0))
+    loss = float(outs[0][0][0])
+    assert abs(loss - loss_g) < 2e-4 * max(1.0, abs(loss_g)), (loss, loss_g)
+    keys = [(k, i) for k in ("conv_w", "conv_b", "fc_w", "fc_b") for i in range(len(w[k]))]
+    worst = {"conv": (0.0, None), "fc": (0.0, None)}
+    for (k, i), got, ref in zip(keys, outs[0][2], state_g):
+        w0 = w[k][i].cuda()
+        e = _relerr(got.cuda() - w0, ref - w0)
+        print("batch 40 %-6s %2d: update err against the vendor-kernel step %.2e" % (k, i, e))
+        worst[k[:-2]] = max(worst[k[:-2]], (e, (k, i)))
+    assert worst["conv"][0] < TOL_UPDATE, worst["conv"]
+    assert worst["fc"][0] < 5e-4, worst["fc"]
+
+
+def _vendor_autograd_step(w, x, y, lr, mu, seed):
+    """One training step by torch autograd on the GPU (fp32 vendor kernels) + torch.optim.SGD from the weights ``w``, with the
+    dropout masks of oracle.train_oracle: -> (loss, updated parameters on the GPU in the order conv_w, conv_b, fc_w, fc_b)."""
+    import torch.nn.functional as F
+    from oracle import train_oracle, vgg_oracle
+    p = {k: [t.clone().cuda().requires_grad_(True) for t in v] for k, v in w.items()}
+    flat = [t for k in ("conv_w", "conv_b", "fc_w", "fc_b") for t in p[k]]
+    opt = torch.optim.SGD(flat, lr, momentum=mu)
+    feat = vgg_oracle.features(x.cuda().to(torch.float32), p["conv_w"], p["conv_b"])
+    op = feat.reshape(feat.size(0), -1)
+    for l in range(3):
+        op = F.relu(F.linear(op, p["fc_w"][l], p["fc_b"][l]))
+        op = op * train_oracle.dropout_mask(seed, l, tuple(op.shape)).cuda()
+    loss = F.cross_entropy(F.linear(op, p["fc_w"][3], p["fc_b"][3]), y.cuda())
+    opt.zero_grad()
+    loss.backward()
+    opt.step()
+    torch.cuda.synchronize()
+    return float(loss.detach()), [t.detach() for t in flat]
 
 
 @pytest.mark.parametrize("layer", [12, 9, 4])

@@ -30,6 +30,7 @@ EXPORTS = [
     "va_flow_to_stack_resize", "va_resize_images_u8", "va_vgg16_train_step_consensus",
     "va_flow_homography", "va_flow_compensate",
     "va_rgbdiff_to_stack", "va_fuse_scores_n",
+    "va_train_conv_backward_layer", "va_train_fc_backward_layer", "va_train_pool_layer", "va_train_loss", "va_train_dropout",
 ]
 
 
@@ -191,6 +192,17 @@ def lib():
     L.va_vgg16_import_state.restype = ci
     L.va_conv3x3_layer.argtypes = [vp, ci, ci, ci, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, ctypes.c_char_p, ci, vp]
     L.va_conv3x3_layer.restype = ci
+    L.va_train_conv_backward_layer.argtypes = [vp, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, cf, cf, vp, vp, vp, vp, vp, vp,
+                                               ctypes.POINTER(sz), ctypes.c_char_p, ci, vp]
+    L.va_train_conv_backward_layer.restype = ci
+    L.va_train_fc_backward_layer.argtypes = [vp, ci, ci, ci, vp, vp, vp, vp, vp, vp, cf, cf, vp, vp, cf, ctypes.c_char_p, ci, vp]
+    L.va_train_fc_backward_layer.restype = ci
+    L.va_train_pool_layer.argtypes = [vp, ci, ci, ci, vp, vp, vp, vp, vp]
+    L.va_train_pool_layer.restype = ci
+    L.va_train_loss.argtypes = [vp, vp, vp, ci, ci, ci, vp, vp, vp]
+    L.va_train_loss.restype = ci
+    L.va_train_dropout.argtypes = [vp, vp, sz, ctypes.c_ulonglong, ci, vp]
+    L.va_train_dropout.restype = ci
     _lib = L
     return L
 

@@ -10,6 +10,7 @@
 // split over workgroups and reduced in a fixed order together with the SGD update).
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <type_traits>
 #include "vgg_internal.h"
 
@@ -84,13 +85,14 @@ __device__ __forceinline__ unsigned mix32(unsigned x)
 }
 
 // Dropout(p = 0.5) in place: element i is kept (and doubled) iff the top bit of mix(mix(i ^ key) + key2) is set,
-// i.e. iff synth.hash_uniform(seed, stream)[i] >= 0.5 (the host derives key/key2 from (seed, stream)).
+// i.e. iff synth.hash_uniform(seed, stream)[i] >= 0.5 (the host derives key/key2 from (seed, stream)).  A product with the
+// 0 / 2 mask, as nn.Dropout's: a dropped negative element becomes -0, a dropped NaN stays NaN (the step's inputs are >= 0).
 __global__ void k_dropout(float* __restrict__ x, size_t n, unsigned key, unsigned key2)
 {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const unsigned h = mix32(mix32((unsigned)i ^ key) + key2);
-    x[i] = (h & 0x80000000u) ? 2.0f * x[i] : 0.0f;
+    x[i] = x[i] * ((h & 0x80000000u) ? 2.0f : 0.0f);
 }
 
 // logits [B][C], labels i64 -> dlogits = (softmax - onehot) / B; out[0] = mean CE, out[1] = #(argmax == label)
@@ -649,6 +651,93 @@ int fc_backward_dispatch(int B, F&& f)
     return f(std::integral_constant<int, 64>());
 }
 
+// ---- the per-layer bodies of the step: train_step and the testing entry points (va_train_*) call these ----
+
+void pool_forward(const float* y, float* p, int B, int hw, int C, hipStream_t st)
+{
+    const size_t n = (size_t)B * (hw / 2) * (hw / 2) * (C / 4);
+    k_maxpool<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(y, p, B, hw, C);
+}
+
+void pool_backward(const float* dp, const float* y, const float* p, float* dy, int B, int hw, int C, hipStream_t st)
+{
+    const size_t n = (size_t)B * (hw / 2) * (hw / 2) * (C / 4);
+    k_unpool<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(dp, y, p, dy, B, hw, C);
+}
+
+void dropout_layer(float* x, size_t n, unsigned long long seed, int layer, hipStream_t st)
+{
+    unsigned key, key2;
+    keys_for(seed, 100u + (unsigned)layer, key, key2);
+    k_dropout<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(x, n, key, key2);
+}
+
+// segments = 0: the loss of every row of logits [B][C]; segments = K >= 1: of the consensus of B / K videos
+void loss_layer(const float* logits, const long long* labels, int B, int segments, int C, float* dlogits, float* out, hipStream_t st)
+{
+    if (segments == 0) k_ce_fwd_bwd<<<1, 256, 0, st>>>(logits, labels, B, C, dlogits, out);
+    else k_ce_consensus_fwd_bwd<<<1, 256, 0, st>>>(logits, labels, B / segments, segments, C, dlogits, out);
+}
+
+// dx (with mask and scale), then the weight and bias updates in place; *inst (may be NULL): the batch instantiation, 32 or 64
+int fc_backward_layer(int B, int O, int I, const float* dz, const float* x, float* w, float* bias, float* vw, float* vb, float* dx,
+                      const float* mask, float scale, float lr, float mu, hipStream_t st, int* inst)
+{
+    int rc = fc_backward_dispatch(B, [&](auto BM) {
+        constexpr int bm = decltype(BM)::value;
+        if (inst) *inst = bm;
+        k_fc_dx<bm><<<va_cdiv(I, 64), 256, 0, st>>>(dz, w, dx, B, O, I, mask, scale);
+        const int orows = 16;
+        k_fc_wgrad_sgd<bm><<<dim3(va_cdiv(I, 256), va_cdiv(O, orows)), 256, (size_t)orows * bm * sizeof(float), st>>>(
+            dz, x, w, vw, B, O, I, orows, lr, mu);
+        return VA_OK;
+    });
+    if (rc) return rc;
+    k_fc_bgrad_sgd<<<va_cdiv(O, 256), 256, 0, st>>>(dz, bias, vb, B, O, lr, mu);
+    return VA_OK;
+}
+
+// bias gradient, pass 1: pixels per block and the number of blocks (at most kBgradBlocks)
+long bgrad_chunk(long P) { return (P + kBgradBlocks - 1) / kBgradBlocks; }
+int bgrad_blocks(long P) { return (int)((P + bgrad_chunk(P) - 1) / bgrad_chunk(P)); }
+
+// Backward of one conv layer.  dx != NULL: the data gradient first (it needs this step's weights): k_pack_dgrad_w into wt,
+// then a linear 3x3 convolution of dy through the forward dispatch, zeroed where mask <= 0 (mask may be NULL).  Then the
+// weight and bias gradients with the momentum-SGD update in place (dy stays intact).
+int conv_backward_layer(int B, int hw, int cin, int cin_pad, int cout, const float* dy, const float* x, float* w, float* bias, float* vw,
+                        float* vb, float* dx, const float* mask, const float* zeros, int f32_conv, float* wt, float* slab, float* bpart,
+                        float lr, float mu, hipStream_t st, const char** dgrad_launched = nullptr)
+{
+    if (dx) {
+        const size_t nwt = (size_t)cin * 9 * cout;
+        k_pack_dgrad_w<<<(unsigned)((nwt + 255) / 256), 256, 0, st>>>(w, wt, cout, cin_pad, cin);
+        if (int rc = va_conv3x3_f32(hw, cout, cin, wt, zeros, dy, dx, mask, 1, 0, B, zeros, f32_conv, st, dgrad_launched)) return rc;
+    }
+    const WgradPlan wp = plan_wgrad(B, hw, cout, cin_pad);
+    WgradArgs a{};
+    a.dy = dy;
+    a.x = x;
+    a.slab = slab;
+    a.B = B;
+    a.H = hw;
+    a.Cout = cout;
+    a.cin_pad = cin_pad;
+    a.N = 9 * cin_pad;
+    a.Npad = wp.Npad;
+    a.Mpad = wp.Mpad;
+    a.P = (long)B * hw * hw;
+    a.chunk = wp.chunk;
+    if (wp.BM == 64) k_conv_wgrad<1, 3><<<dim3(wp.Npad / 192, wp.Mpad / 64, wp.S), 192, 0, st>>>(a);
+    else k_conv_wgrad<2, 2><<<dim3(wp.Npad / 128, wp.Mpad / 128, wp.S), 256, 0, st>>>(a);
+    const size_t nw = (size_t)cout * a.N;
+    k_wgrad_reduce_sgd<<<(unsigned)((nw + 31) / 32), 256, 0, st>>>(slab, w, vw, cout, a.N, wp.Mpad, wp.Npad, wp.S, lr, mu);
+    const int nblk = bgrad_blocks(a.P);
+    k_conv_bgrad_partial<<<nblk, 256, 0, st>>>(dy, bpart, a.P, cout, bgrad_chunk(a.P));
+    k_conv_bgrad_sgd<<<va_cdiv(cout, 64), 256, 0, st>>>(bpart, nblk, bias, vb, cout, lr, mu);
+    VA_LAUNCH_CHECK();
+    return VA_OK;
+}
+
 }  // namespace
 
 extern "C" int va_vgg16_train_init(va_vgg16* m, void* stream)
@@ -715,8 +804,7 @@ static int train_step(const char* who, va_vgg16* m, const void* x, int x_is_u8, 
         if (int rc = va_conv3x3_f32(L.hw, L.cin_pad, L.cout, L.wp, L.bias, in, F(T.y[i]), nullptr, 0, 0, B, m->zeros_f32, m->f32_conv, st)) return rc;
         in = F(T.y[i]);
         if (L.pool) {
-            const size_t n = (size_t)B * (L.hw / 2) * (L.hw / 2) * (L.cout / 4);
-            k_maxpool<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(F(T.y[i]), F(T.p[i]), B, L.hw, L.cout);
+            pool_forward(F(T.y[i]), F(T.p[i]), B, L.hw, L.cout, st);
             in = F(T.p[i]);
         }
     }
@@ -726,19 +814,10 @@ static int train_step(const char* who, va_vgg16* m, const void* x, int x_is_u8, 
     float* fout[4] = {F(T.a_d[0]), F(T.a_d[1]), F(T.a_d[2]), F(T.logits)};
     for (int l = 0; l < 4; ++l) {
         if (int rc = va_fc_f32(fin[l], m->fcw[l], m->fcb[l], fout[l], slab, B, m->fc_out[l], m->fc_in[l], l < 3, st)) return rc;
-        if (l < 3) {
-            unsigned key, key2;
-            keys_for(dropout_seed, 100u + (unsigned)l, key, key2);
-            const size_t n = (size_t)B * m->fc_out[l];
-            k_dropout<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(fout[l], n, key, key2);
-        }
+        if (l < 3) dropout_layer(fout[l], (size_t)B * m->fc_out[l], dropout_seed, l, st);
     }
     if (desc) VA_HIP(hipMemcpyAsync(desc, F(T.a_d[2]), (size_t)B * m->desc_dim * sizeof(float), hipMemcpyDeviceToDevice, st));
-    if (segments == 0)
-        k_ce_fwd_bwd<<<1, 256, 0, st>>>(F(T.logits), (const long long*)labels, B, m->n_classes, F(T.dlogits), (float*)loss_out);
-    else
-        k_ce_consensus_fwd_bwd<<<1, 256, 0, st>>>(F(T.logits), (const long long*)labels, B / segments, segments, m->n_classes,
-                                                  F(T.dlogits), (float*)loss_out);
+    loss_layer(F(T.logits), (const long long*)labels, B, segments, m->n_classes, F(T.dlogits), (float*)loss_out, st);
     VA_LAUNCH_CHECK();
 
     // ---------------- classifier backward + update ----------------
@@ -749,16 +828,9 @@ static int train_step(const char* who, va_vgg16* m, const void* x, int x_is_u8, 
     for (int l = 3; l >= 0; --l) {
         const int O = m->fc_out[l], I = m->fc_in[l];
         const float* mask = l > 0 ? fin[l] : nullptr;  // fin[l] = post-dropout activation of layer l-1
-        int rc = fc_backward_dispatch(B, [&](auto BM) {
-            constexpr int bm = decltype(BM)::value;
-            k_fc_dx<bm><<<va_cdiv(I, 64), 256, 0, st>>>(dz[l], m->fcw[l], dxo[l], B, O, I, mask, 2.0f);
-            const int orows = 16;
-            k_fc_wgrad_sgd<bm><<<dim3(va_cdiv(I, 256), va_cdiv(O, orows)), 256, (size_t)orows * bm * sizeof(float), st>>>(
-                dz[l], fin[l], m->fcw[l], m->fc_mom_w[l], B, O, I, orows, lr, momentum);
-            return VA_OK;
-        });
-        if (rc) return rc;
-        k_fc_bgrad_sgd<<<va_cdiv(O, 256), 256, 0, st>>>(dz[l], m->fcb[l], m->fc_mom_b[l], B, O, lr, momentum);
+        if (int rc = fc_backward_layer(B, O, I, dz[l], fin[l], m->fcw[l], m->fcb[l], m->fc_mom_w[l], m->fc_mom_b[l], dxo[l], mask, 2.0f, lr,
+                                       momentum, st, nullptr))
+            return rc;
     }
     VA_LAUNCH_CHECK();
 
@@ -772,46 +844,18 @@ static int train_step(const char* who, va_vgg16* m, const void* x, int x_is_u8, 
         const float* dyr = dout;
         if (L.pool) {
             const int dst = cur == 0 ? 1 : 0;
-            const size_t n = (size_t)B * (L.hw / 2) * (L.hw / 2) * (L.cout / 4);
-            k_unpool<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(dout, F(T.y[i]), F(T.p[i]), F(T.g[dst]), B, L.hw, L.cout);
+            pool_backward(dout, F(T.y[i]), F(T.p[i]), F(T.g[dst]), B, L.hw, L.cout, st);
             dyr = F(T.g[dst]);
             cur = dst;
         }
-        // data gradient first (it needs this step's weights), into the other gradient buffer
-        if (i > 0) {
-            const int cin = L.cin;  // = previous layer's cout
-            const size_t nwt = (size_t)cin * 9 * L.cout;
-            k_pack_dgrad_w<<<(unsigned)((nwt + 255) / 256), 256, 0, st>>>(L.wp, F(T.wt), L.cout, L.cin_pad, cin);
-            float* g = F(T.g[1 - cur]);
-            const float* mask = m->conv[i - 1].pool ? nullptr : F(T.y[i - 1]);
-            if (int rc = va_conv3x3_f32(L.hw, L.cout, cin, F(T.wt), m->zeros_f32, dyr, g, mask, 1, 0, B, m->zeros_f32, m->f32_conv, st)) return rc;
-            dout = g;
-        }
-        // weight and bias gradients + update (dyr stays intact: the data gradient went to the other buffer)
-        const WgradPlan wp = plan_wgrad(B, L.hw, L.cout, L.cin_pad);
-        WgradArgs a{};
-        a.dy = dyr;
-        a.x = lin;
-        a.slab = slab;
-        a.B = B;
-        a.H = L.hw;
-        a.Cout = L.cout;
-        a.cin_pad = L.cin_pad;
-        a.N = 9 * L.cin_pad;
-        a.Npad = wp.Npad;
-        a.Mpad = wp.Mpad;
-        a.P = (long)B * L.hw * L.hw;
-        a.chunk = wp.chunk;
-        if (wp.BM == 64) k_conv_wgrad<1, 3><<<dim3(wp.Npad / 192, wp.Mpad / 64, wp.S), 192, 0, st>>>(a);
-        else k_conv_wgrad<2, 2><<<dim3(wp.Npad / 128, wp.Mpad / 128, wp.S), 256, 0, st>>>(a);
-        const size_t nw = (size_t)L.cout * a.N;
-        k_wgrad_reduce_sgd<<<(unsigned)((nw + 31) / 32), 256, 0, st>>>(slab, L.wp, L.mom_w, L.cout, a.N, wp.Mpad, wp.Npad, wp.S, lr, momentum);
-        const long bchunk = (a.P + kBgradBlocks - 1) / kBgradBlocks;
-        const int nblk = (int)((a.P + bchunk - 1) / bchunk);
-        k_conv_bgrad_partial<<<nblk, 256, 0, st>>>(dyr, F(T.bpart), a.P, L.cout, bchunk);
-        k_conv_bgrad_sgd<<<va_cdiv(L.cout, 64), 256, 0, st>>>(F(T.bpart), nblk, L.bias, L.mom_b, L.cout, lr, momentum);
+        // data gradient (not for the first layer) into the other gradient buffer, then the weight and bias updates
+        float* g = i > 0 ? F(T.g[1 - cur]) : nullptr;
+        const float* mask = i > 0 && !m->conv[i - 1].pool ? F(T.y[i - 1]) : nullptr;
+        if (int rc = conv_backward_layer(B, L.hw, L.cin, L.cin_pad, L.cout, dyr, lin, L.wp, L.bias, L.mom_w, L.mom_b, g, mask, m->zeros_f32,
+                                         m->f32_conv, F(T.wt), slab, F(T.bpart), lr, momentum, st))
+            return rc;
+        if (i > 0) dout = g;
         if (i > 0) cur = 1 - cur;
-        VA_LAUNCH_CHECK();
         if (stop_at == i) {  // debugging aid of the tests: leave the gradient buffers as layer i left them; NOT a completed step
             va_set_error("%s: stopped after the backward pass of conv layer %d (VA_OPT_TRAIN_STOP_AT); layers below were not updated", who, i);
             return VA_ERR_STOPPED;
@@ -906,5 +950,126 @@ extern "C" int va_vgg16_train_plan(const va_vgg16* m, int batch, unsigned long l
     out[27] = T.g[1];
     out[28] = T.da0;
     out[29] = T.x0;
+    return VA_OK;
+}
+
+// ---------------------------------------------------------------- testing entry points ---------
+// One layer of the step at a time through the functions train_step calls (include/va.h, "testing entry points").
+
+#define VA_ALIGNED16(...) ((va_or_ptrs({__VA_ARGS__}) & 15) == 0)
+static uintptr_t va_or_ptrs(std::initializer_list<const void*> ps)
+{
+    uintptr_t v = 0;
+    for (const void* p : ps) v |= (uintptr_t)p;
+    return v;
+}
+
+extern "C" int va_train_conv_backward_layer(va_ctx* ctx, int kernel_opt, int batch, int hw, int cin, int cin_pad, int cout, const float* dy,
+                                            const float* x, float* w_packed, float* bias, float* mom_w, float* mom_b, float lr,
+                                            float momentum, float* dx, const float* mask, const float* zeros, float* slab, float* wt,
+                                            float* bpart, size_t* scratch_floats, char* info, int info_len, void* stream)
+{
+    const char* who = "va_train_conv_backward_layer";
+    VA_CHECK_ARG(ctx != nullptr, "%s: ctx is NULL", who);
+    VA_USE_DEVICE(ctx);
+    if (info && info_len > 0) info[0] = 0;
+    VA_CHECK_ARG(scratch_floats != nullptr, "%s: scratch_floats is NULL", who);
+    VA_CHECK_ARG(kernel_opt == 0 || kernel_opt == 1, "%s: kernel_opt (VA_OPT_F32_CONV_KERNEL) must be 0 or 1", who);
+    VA_CHECK_ARG(batch >= 1 && batch <= 64, "%s: batch %d out of range [1,64]", who, batch);
+    VA_CHECK_ARG(hw >= 1 && hw <= 224, "%s: hw %d out of range [1,224]", who, hw);
+    VA_CHECK_ARG(cin_pad >= 4 && cin_pad % 4 == 0 && cin_pad <= 4096, "%s: cin_pad %d must be a multiple of 4 in [4,4096] (16-byte loads)", who, cin_pad);
+    VA_CHECK_ARG(cout >= 4 && cout % 4 == 0 && cout <= 4096, "%s: cout %d must be a multiple of 4 in [4,4096] (16-byte loads)", who, cout);
+    VA_CHECK_ARG(cin >= 1 && cin <= cin_pad, "%s: cin %d outside [1, cin_pad = %d]", who, cin, cin_pad);
+    VA_CHECK_ARG(mask == nullptr || dx != nullptr, "%s: mask without dx", who);
+    // the data gradient runs the forward dispatch: 16-channel K steps, 64-channel N tiles
+    VA_CHECK_ARG(!dx || (cin == cin_pad && cin % 64 == 0 && cout % 16 == 0),
+                 "%s: dx needs cin == cin_pad, cin %% 64 == 0 and cout %% 16 == 0 (got cin %d, cin_pad %d, cout %d)", who, cin, cin_pad, cout);
+    const WgradPlan wp = plan_wgrad(batch, hw, cout, cin_pad);
+    const int nblk = bgrad_blocks((long)batch * hw * hw);
+    const size_t need[3] = {wp.slab_floats, (size_t)cin * 9 * cout, (size_t)nblk * cout};
+    const size_t have[3] = {scratch_floats[0], scratch_floats[1], scratch_floats[2]};
+    for (int i = 0; i < 3; ++i) scratch_floats[i] = need[i];
+    char plan[160];
+    snprintf(plan, sizeof plan, "k_conv_wgrad<%s> S=%d chunk=%d Mpad=%d Npad=%d bgrad_blocks=%d", wp.BM == 64 ? "1,3" : "2,2", wp.S, wp.chunk,
+             wp.Mpad, wp.Npad, nblk);
+    if (slab == nullptr) {  // size query
+        if (info && info_len > 0) snprintf(info, (size_t)info_len, "%s dgrad=%s", plan, "none");
+        return VA_OK;
+    }
+    VA_CHECK_ARG(dy && x && w_packed && bias && mom_w && mom_b && zeros && bpart && (wt || !dx), "%s: NULL argument", who);
+    VA_CHECK_ARG(VA_ALIGNED16(dy, x, w_packed, bias, mom_w, mom_b, dx, mask, zeros, slab, wt, bpart),
+                 "%s: every pointer must be 16-byte aligned (16-byte vector accesses)", who);
+    if (have[0] < need[0] || have[2] < need[2] || (dx && have[1] < need[1])) {
+        va_set_error("%s: scratch of {%zu, %zu, %zu} floats needed (slab, wt, bpart), {%zu, %zu, %zu} given", who, need[0], dx ? need[1] : 0,
+                     need[2], have[0], have[1], have[2]);
+        return VA_ERR_WORKSPACE;
+    }
+    const char* dname = nullptr;
+    if (int rc = conv_backward_layer(batch, hw, cin, cin_pad, cout, dy, x, w_packed, bias, mom_w, mom_b, dx, mask, zeros, kernel_opt, wt, slab,
+                                     bpart, lr, momentum, (hipStream_t)stream, &dname))
+        return rc;
+    if (info && info_len > 0) snprintf(info, (size_t)info_len, "%s dgrad=%s", plan, dname ? dname : "none");
+    return VA_OK;
+}
+
+extern "C" int va_train_fc_backward_layer(va_ctx* ctx, int batch, int out_f, int in_f, const float* dz, const float* x, float* w, float* bias,
+                                          float* mom_w, float* mom_b, float lr, float momentum, float* dx, const float* mask, float scale,
+                                          char* info, int info_len, void* stream)
+{
+    const char* who = "va_train_fc_backward_layer";
+    VA_CHECK_ARG(ctx != nullptr, "%s: ctx is NULL", who);
+    VA_USE_DEVICE(ctx);
+    if (info && info_len > 0) info[0] = 0;
+    VA_CHECK_ARG(batch >= 1 && batch <= 64, "%s: batch %d out of range [1,64]", who, batch);
+    VA_CHECK_ARG(out_f >= 1 && in_f >= 1 && out_f <= 16 * 65535 && (long)out_f * in_f < 2147483647L, "%s: out_f %d / in_f %d out of range", who,
+                 out_f, in_f);
+    VA_CHECK_ARG(dz && x && w && bias && mom_w && mom_b && dx, "%s: NULL argument", who);
+    VA_CHECK_ARG(VA_ALIGNED16(dz, x, w, bias, mom_w, mom_b, dx, mask), "%s: every pointer must be 16-byte aligned", who);
+    int inst = 0;
+    if (int rc = fc_backward_layer(batch, out_f, in_f, dz, x, w, bias, mom_w, mom_b, dx, mask, scale, lr, momentum, (hipStream_t)stream, &inst))
+        return rc;
+    VA_LAUNCH_CHECK();
+    if (info && info_len > 0) snprintf(info, (size_t)info_len, "k_fc_dx<%d>", inst);
+    return VA_OK;
+}
+
+extern "C" int va_train_pool_layer(va_ctx* ctx, int batch, int hw, int c, const float* y, float* p, const float* dp, float* dy, void* stream)
+{
+    const char* who = "va_train_pool_layer";
+    VA_CHECK_ARG(ctx != nullptr, "%s: ctx is NULL", who);
+    VA_USE_DEVICE(ctx);
+    VA_CHECK_ARG(batch >= 1 && batch <= 64, "%s: batch %d out of range [1,64]", who, batch);
+    VA_CHECK_ARG(hw >= 2 && hw % 2 == 0 && hw <= 224, "%s: hw %d must be even and in [2,224]", who, hw);
+    VA_CHECK_ARG(c >= 4 && c % 4 == 0 && c <= 4096, "%s: c %d must be a multiple of 4 in [4,4096] (four channels per thread)", who, c);
+    VA_CHECK_ARG(y && p && ((dp == nullptr) == (dy == nullptr)), "%s: NULL y / p, or only one of dp / dy", who);
+    VA_CHECK_ARG(VA_ALIGNED16(y, p, dp, dy), "%s: every pointer must be 16-byte aligned", who);
+    pool_forward(y, p, batch, hw, c, (hipStream_t)stream);
+    if (dp) pool_backward(dp, y, p, dy, batch, hw, c, (hipStream_t)stream);
+    VA_LAUNCH_CHECK();
+    return VA_OK;
+}
+
+extern "C" int va_train_loss(va_ctx* ctx, const float* logits, const void* labels, int n, int k, int c, float* dlogits, float* out, void* stream)
+{
+    const char* who = "va_train_loss";
+    VA_CHECK_ARG(ctx != nullptr, "%s: ctx is NULL", who);
+    VA_USE_DEVICE(ctx);
+    VA_CHECK_ARG(n >= 1 && k >= 0 && (long long)n * (k > 0 ? k : 1) <= 64, "%s: %d rows x %d snippets out of range (n * max(k, 1) in [1,64])", who, n, k);
+    VA_CHECK_ARG(c >= 1 && c <= (1 << 20), "%s: c %d out of range", who, c);
+    VA_CHECK_ARG(logits && labels && dlogits && out, "%s: NULL argument", who);
+    loss_layer(logits, (const long long*)labels, n * (k > 0 ? k : 1), k, c, dlogits, out, (hipStream_t)stream);
+    VA_LAUNCH_CHECK();
+    return VA_OK;
+}
+
+extern "C" int va_train_dropout(va_ctx* ctx, float* x, size_t n, unsigned long long dropout_seed, int layer, void* stream)
+{
+    const char* who = "va_train_dropout";
+    VA_CHECK_ARG(ctx != nullptr, "%s: ctx is NULL", who);
+    VA_USE_DEVICE(ctx);
+    VA_CHECK_ARG(x != nullptr && n >= 1 && n <= (size_t)1 << 31, "%s: NULL x or n out of range [1, 2^31]", who);
+    VA_CHECK_ARG(layer >= 0 && layer <= 2, "%s: layer %d out of range [0,2]", who, layer);
+    dropout_layer(x, n, dropout_seed, layer, (hipStream_t)stream);
+    VA_LAUNCH_CHECK();
     return VA_OK;
 }

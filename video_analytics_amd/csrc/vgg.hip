@@ -2401,9 +2401,9 @@ WsPlan plan_ws(const va_vgg16* m, int B)
 }  // namespace
 
 int va_conv3x3_f32(int hw, int cin_pad, int cout, const float* wp, const float* bias, const float* in, float* out,
-                   const float* mask, int linear, int pool, int B, const float* zeros, int f32_conv, hipStream_t st)
+                   const float* mask, int linear, int pool, int B, const float* zeros, int f32_conv, hipStream_t st, const char** launched)
 {
-    return launch_conv_ex(hw, cin_pad, cout, wp, bias, in, out, mask, linear, pool != 0, B, zeros, f32_conv, st);
+    return launch_conv_ex(hw, cin_pad, cout, wp, bias, in, out, mask, linear, pool != 0, B, zeros, f32_conv, st, launched);
 }
 
 int va_fc_f32(const float* A, const float* Wt, const float* bias, float* out, float* slab, int M, int N, int K, int relu, hipStream_t st)

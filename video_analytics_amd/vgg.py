@@ -464,6 +464,120 @@ def conv3x3_layer(x, w_packed, bias, out, kernel_opt=1, pool=False, linear=False
     return name.value.decode()
 
 
+def _f32_cuda(who, ref, **tensors):
+    for name, t in tensors.items():
+        if t is None:
+            continue
+        if t.dtype != torch.float32 or not t.is_cuda or t.device != ref.device or not t.is_contiguous():
+            raise ValueError("%s: %s must be a contiguous float32 tensor on %s" % (who, name, ref.device))
+
+
+def train_conv_backward_scratch(B, hw, cin, cin_pad, cout, device=None):
+    """(slab, wt, bpart) sizes in floats and the weight-gradient plan of ``train_conv_backward_layer`` (the size query of
+    ``va_train_conv_backward_layer``: nothing is launched)."""
+    dev = torch.device("cuda", torch.cuda.current_device() if device is None else device)
+    need = (ctypes.c_size_t * 3)(0, 0, 0)
+    info = ctypes.create_string_buffer(192)
+    _ffi.check(_ffi.lib().va_train_conv_backward_layer(
+        _ffi.ctx(dev.index), 1, B, hw, cin, cin_pad, cout, None, None, None, None, None, None, 0.0, 0.0, None, None, None, None, None,
+        None, need, info, len(info), _ffi.stream_ptr(dev)))
+    return tuple(int(v) for v in need), _parse_plan(info.value.decode())
+
+
+def _parse_plan(text):
+    parts = text.split()
+    plan = {"wgrad": parts[0]}
+    for kv in parts[1:]:
+        k, v = kv.split("=", 1)
+        plan[k] = v if k == "dgrad" else int(v)
+    return plan
+
+
+def train_conv_backward_layer(dy, x, w_packed, bias, mom_w, mom_b, lr, momentum, cin, dx=None, mask=None, kernel_opt=1, zeros=None,
+                              scratch=None):
+    """Backward of one conv layer exactly as the training step does it (``va_train_conv_backward_layer``, a testing entry
+    point): dy NHWC [B][hw][hw][cout], x NHWC [B][hw][hw][cin_pad], w_packed / mom_w [cout][9][cin_pad], bias / mom_b [cout],
+    all float32 on one device; parameters and momentum buffers are updated in place.  dx: NHWC [B][hw][hw][cin] or None
+    (no data gradient); mask shaped like dx or None.  scratch: (slab, wt, bpart) float32 tensors or None (allocated here).
+    Returns the plan that ran as a dict (wgrad, S, chunk, Mpad, Npad, bgrad_blocks, dgrad)."""
+    who = "train_conv_backward_layer"
+    if dy.dim() != 4 or x.dim() != 4 or dy.shape[:3] != x.shape[:3] or dy.shape[1] != dy.shape[2]:
+        raise ValueError("%s: dy / x must be NHWC [B][hw][hw][cout] / [B][hw][hw][cin_pad]" % who)
+    B, hw, _, cout = dy.shape
+    cin_pad = x.shape[3]
+    _f32_cuda(who, dy, dy=dy, x=x, w_packed=w_packed, bias=bias, mom_w=mom_w, mom_b=mom_b, dx=dx, mask=mask, zeros=zeros)
+    if (tuple(w_packed.shape) != (cout, 9, cin_pad) or mom_w.shape != w_packed.shape or tuple(bias.shape) != (cout,)
+            or mom_b.shape != bias.shape or (dx is not None and tuple(dx.shape) != (B, hw, hw, cin))
+            or (mask is not None and (dx is None or mask.shape != dx.shape))):
+        raise ValueError("%s: w_packed / bias / momentum buffers / dx / mask do not match dy and x" % who)
+    if zeros is None:
+        zeros = torch.zeros(max(512, cin), dtype=torch.float32, device=dy.device)
+    if scratch is None:
+        sizes, _ = train_conv_backward_scratch(B, hw, cin, cin_pad, cout, dy.device.index)
+        scratch = tuple(torch.empty(n, dtype=torch.float32, device=dy.device) for n in sizes)
+    slab, wt, bpart = scratch
+    _f32_cuda(who, dy, slab=slab, wt=wt, bpart=bpart)
+    have = (ctypes.c_size_t * 3)(slab.numel(), wt.numel() if wt is not None else 0, bpart.numel())
+    info = ctypes.create_string_buffer(192)
+    _ffi.check(_ffi.lib().va_train_conv_backward_layer(
+        _ffi.ctx(dy.device.index), int(kernel_opt), B, hw, int(cin), cin_pad, cout, _ffi.ptr(dy), _ffi.ptr(x), _ffi.ptr(w_packed),
+        _ffi.ptr(bias), _ffi.ptr(mom_w), _ffi.ptr(mom_b), float(lr), float(momentum), _ffi.ptr(dx), _ffi.ptr(mask), _ffi.ptr(zeros),
+        _ffi.ptr(slab), _ffi.ptr(wt), _ffi.ptr(bpart), have, info, len(info), _ffi.stream_ptr(dy.device)))
+    return _parse_plan(info.value.decode())
+
+
+def train_fc_backward_layer(dz, x, w, bias, mom_w, mom_b, lr, momentum, dx, mask=None, scale=1.0):
+    """Backward of one Linear layer as the training step does it (``va_train_fc_backward_layer``): dz [B][O], x [B][I],
+    w / mom_w [O][I], bias / mom_b [O], dx [B][I], mask [B][I] or None; updates in place; returns the instantiation
+    ("k_fc_dx<32>" or "k_fc_dx<64>")."""
+    who = "train_fc_backward_layer"
+    if dz.dim() != 2 or x.dim() != 2 or dz.shape[0] != x.shape[0]:
+        raise ValueError("%s: dz / x must be [B][O] / [B][I]" % who)
+    (B, O), I = dz.shape, x.shape[1]
+    _f32_cuda(who, dz, dz=dz, x=x, w=w, bias=bias, mom_w=mom_w, mom_b=mom_b, dx=dx, mask=mask)
+    if (tuple(w.shape) != (O, I) or mom_w.shape != w.shape or tuple(bias.shape) != (O,) or mom_b.shape != bias.shape
+            or dx.shape != x.shape or (mask is not None and mask.shape != x.shape)):
+        raise ValueError("%s: w / bias / momentum buffers / dx / mask do not match dz and x" % who)
+    info = ctypes.create_string_buffer(64)
+    _ffi.check(_ffi.lib().va_train_fc_backward_layer(
+        _ffi.ctx(dz.device.index), B, O, I, _ffi.ptr(dz), _ffi.ptr(x), _ffi.ptr(w), _ffi.ptr(bias), _ffi.ptr(mom_w), _ffi.ptr(mom_b),
+        float(lr), float(momentum), _ffi.ptr(dx), _ffi.ptr(mask), float(scale), info, len(info), _ffi.stream_ptr(dz.device)))
+    return info.value.decode()
+
+
+def train_pool_layer(y, p, dp=None, dy=None):
+    """``va_train_pool_layer``: p = 2x2/2 max-pool of y (NHWC float32) and, with dp and dy, the step's max-pool backward
+    (first maximum in row-major order, nothing where the pooled value is <= 0)."""
+    who = "train_pool_layer"
+    if y.dim() != 4 or y.shape[1] != y.shape[2]:
+        raise ValueError("%s: y must be NHWC [B][hw][hw][c]" % who)
+    B, hw, _, c = y.shape
+    _f32_cuda(who, y, y=y, p=p, dp=dp, dy=dy)
+    if tuple(p.shape) != (B, hw // 2, hw // 2, c) or (dp is not None and dp.shape != p.shape) or (dy is not None and dy.shape != y.shape):
+        raise ValueError("%s: p / dp / dy do not match y" % who)
+    _ffi.check(_ffi.lib().va_train_pool_layer(_ffi.ctx(y.device.index), B, hw, c, _ffi.ptr(y), _ffi.ptr(p), _ffi.ptr(dp), _ffi.ptr(dy),
+                                              _ffi.stream_ptr(y.device)))
+
+
+def train_loss(logits, labels, dlogits, out, k=0):
+    """``va_train_loss``: logits [n][c] (k = 0) or [n][k][c]; labels int64 [n] on the device; dlogits like logits;
+    out float32 [2] = mean cross-entropy (of the snippet consensus when k >= 1), hits."""
+    who = "train_loss"
+    _f32_cuda(who, logits, logits=logits, dlogits=dlogits, out=out)
+    n, c = logits.shape[0], logits.shape[-1]
+    if (tuple(logits.shape) != ((n, c) if k == 0 else (n, k, c)) or dlogits.shape != logits.shape or out.numel() < 2
+            or labels.dtype != torch.int64 or tuple(labels.shape) != (n,) or labels.device != logits.device or not labels.is_contiguous()):
+        raise ValueError("%s: logits / labels / dlogits / out do not match" % who)
+    _ffi.check(_ffi.lib().va_train_loss(_ffi.ctx(logits.device.index), _ffi.ptr(logits), _ffi.ptr(labels), n, int(k), c, _ffi.ptr(dlogits),
+                                        _ffi.ptr(out), _ffi.stream_ptr(logits.device)))
+
+
+def train_dropout(x, seed, layer):
+    """``va_train_dropout``: the step's Dropout(0.5) of classifier layer ``layer`` (0..2) in place on float32 x."""
+    _f32_cuda("train_dropout", x, x=x)
+    _ffi.check(_ffi.lib().va_train_dropout(_ffi.ctx(x.device.index), _ffi.ptr(x), x.numel(), int(seed), int(layer), _ffi.stream_ptr(x.device)))
+
+
 def _ffi_conv_cout(i):
     return (64, 64, 128, 128, 256, 256, 256, 512, 512, 512, 512, 512, 512)[i]
 

@@ -167,11 +167,13 @@ typedef struct va_tvl1_params {
     float tau;        /* 0.25 */
     float lambda;     /* 0.15 */
     float theta;      /* 0.3  */
-    int nscales;      /* 5    */
+    int nscales;      /* 5; pyramid levels wanted: fewer are used where the next level would be under 16 pixels wide or
+                         high, and never more than 16 (a larger value is read as 16, not rejected) */
     int warps;        /* 5    */
     float epsilon;    /* 0.01; <= 0: run exactly `iters` inner iterations per warp */
     int iters;        /* 300  */
-    float scale_step; /* 0.8  */
+    float scale_step; /* 0.8; in (0,1).  The zoom-out Gaussian (sigma = 0.6 sqrt(1/step^2 - 1)) has radius
+                         min((int)(3 sigma) + 1, 8): the clamp to 8 applies for scale_step <= 0.2195 */
     int block_iters;  /* inner iterations fused per launch (register-resident temporal
                          blocking); 0 = library default.  Results do not depend on it.
                          Forced to 1 when epsilon > 0. */

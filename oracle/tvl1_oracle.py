@@ -61,6 +61,8 @@ def lib():
         L.ora_tvl1_pyramid_sizes.restype = ctypes.c_int
         L.ora_tvl1_zoom_out.argtypes = [fp, ctypes.c_int, ctypes.c_int, fp, ctypes.c_int, ctypes.c_int, ctypes.c_float]
         L.ora_tvl1_zoom_out.restype = None
+        L.ora_tvl1_zoom_taps.argtypes = [ctypes.c_float, fp]
+        L.ora_tvl1_zoom_taps.restype = ctypes.c_int
         L.ora_tvl1_level.argtypes = [fp, fp, fp, fp, ctypes.c_int, ctypes.c_int, ctypes.POINTER(OraTvl1Params), fp, fp]
         L.ora_tvl1_level.restype = ctypes.c_long
         L.ora_tvl1_centered_gradient.argtypes = [fp, ctypes.c_int, ctypes.c_int, fp, fp]
@@ -105,6 +107,13 @@ def zoom_out(img, step=0.8):
     out = np.empty((oh, ow), dtype=np.float32)
     lib().ora_tvl1_zoom_out(_fp(img), w, h, _fp(out), ow, oh, step)
     return out
+
+
+def zoom_taps(step):
+    """(radius R, float32 taps [2R+1]) of the zoom-out Gaussian for one scale step."""
+    taps = (ctypes.c_float * 17)()
+    R = lib().ora_tvl1_zoom_taps(step, taps)
+    return R, np.array(taps[:2 * R + 1], dtype=np.float32)
 
 
 def flow_to_stack(flow, bound=20.0, mean=0.485, std=0.229):

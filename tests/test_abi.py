@@ -45,6 +45,50 @@ def test_host_only_entry_points(lib):
     assert b"out of range" in lib.va_last_error()
 
 
+def test_pyramid_sizes_equal_the_oracle_over_steps_and_depths(lib):
+    """va_tvl1_pyramid_sizes against the oracle's (host arithmetic on both sides): sizes at and just above the 16-pixel
+    minimum, odd sizes, every scale step the GPU tests use, nscales up to and above the 16 levels both sides clamp to."""
+    from oracle import tvl1_oracle
+    from video_analytics_amd import _ffi, flow
+    sizes = (16, 17, 20, 40, 224, 333, 1280)
+    deepest = 0
+    for step in (0.1, 0.2, 0.5, 0.65, 0.8, 0.9, 0.95):
+        for nscales in (1, 5, 16, 40):
+            p = _ffi.default_tvl1_params(scale_step=step, nscales=nscales)
+            for w in sizes:
+                for h in sizes:
+                    got = flow.pyramid_sizes(w, h, p)
+                    assert got == tvl1_oracle.pyramid_sizes(w, h, nscales, step), (w, h, step, nscales)
+                    assert 1 <= len(got) <= min(nscales, 16) and got[0] == (w, h) and min(min(s) for s in got) >= 16
+                    deepest = max(deepest, len(got))
+    assert deepest == 16  # the clamp of nscales = 40 is reached (1280 x 1280 at step 0.9 and 0.95)
+    assert len(flow.pyramid_sizes(56, 40, _ffi.default_tvl1_params(scale_step=0.95, nscales=40))) == 16
+
+
+BAD_TVL1_PARAMS = [
+    (dict(scale_step=0.0), "scale_step"), (dict(scale_step=1.0), "scale_step"), (dict(scale_step=float("nan")), "scale_step"),
+    (dict(tau=0.0), "must be > 0"), (dict(tau=-0.25), "must be > 0"), (dict(tau=float("nan")), "must be > 0"),
+    (dict(lambda_=0.0), "must be > 0"), (dict(lambda_=-0.15), "must be > 0"), (dict(lambda_=float("nan")), "must be > 0"),
+    (dict(theta=0.0), "must be > 0"), (dict(theta=-0.3), "must be > 0"), (dict(theta=float("nan")), "must be > 0"),
+    (dict(tau=1.0, theta=0.0005), "<= 1000"),      # tau / theta = 2000
+    (dict(lambda_=100.0, theta=20.0), "<= 1000"),  # lambda * theta = 2000 (tau / theta = 0.0125)
+    (dict(nscales=0), "must be >= 1"),
+]
+
+
+@pytest.mark.parametrize("over,msg", BAD_TVL1_PARAMS, ids=[",".join("%s=%s" % kv for kv in o.items()) for o, _ in BAD_TVL1_PARAMS])
+def test_workspace_bytes_rejects_bad_tvl1_parameters(lib, over, msg):
+    """va_tvl1_workspace_bytes answers 0 and leaves a message naming the parameter (flow.tvl1_flow turns exactly that into
+    its ValueError: tests/test_tvl1_params_gpu.py, the call needs a device); the neighbouring legal values are accepted."""
+    from video_analytics_amd import _ffi
+    p = _ffi.default_tvl1_params(**over)
+    assert lib.va_tvl1_workspace_bytes(64, 64, 1, 2, ctypes.byref(p)) == 0, over
+    assert msg in lib.va_last_error().decode(), (over, lib.va_last_error())
+    for ok in (dict(scale_step=0.1), dict(scale_step=0.95), dict(tau=1.0, theta=0.001), dict(lambda_=100.0, theta=10.0), dict(nscales=1),
+               dict(nscales=40)):
+        assert lib.va_tvl1_workspace_bytes(64, 64, 1, 2, ctypes.byref(_ffi.default_tvl1_params(**ok))) > 0, ok
+
+
 def test_ctx_create_fails_loudly_without_a_gpu(lib):
     import torch
     if torch.cuda.is_available():

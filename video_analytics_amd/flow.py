@@ -35,7 +35,9 @@ def tvl1_flow(frames, params=None, ws_slot=0, out=None, **over):
 
     Returns float32 ``[S*(F-1), 2, H, W]`` (written into ``out`` when given): plane 0 = x flow, plane 1 = y
     flow of every consecutive frame pair.  ``params``: ``_ffi.Tvl1Params`` or keyword overrides (tau, lambda_, theta, nscales,
-    warps, epsilon, iters, scale_step, block_iters).
+    warps, epsilon, iters, scale_step, block_iters).  ``lambda`` is a Python keyword: pass it as ``lambda_=0.1`` (or as
+    ``**{"lambda": 0.1}``, which is taken as the same field).  Parameters out of range (``va_tvl1_params`` in include/va.h)
+    raise ValueError.
     """
     if not isinstance(frames, torch.Tensor) or not frames.is_cuda:
         raise ValueError("tvl1_flow: frames must be a CUDA tensor")

@@ -449,6 +449,15 @@ int va_train_pool_layer(va_ctx* ctx, int batch, int hw, int c, const float* y, f
  */
 int va_train_loss(va_ctx* ctx, const float* logits, const void* labels, int n, int k, int c, float* dlogits, float* out,
                   void* stream);
+/*
+ * The multi-task form of the step's loss (k_ce_multitask_fwd_bwd), through the function
+ * va_vgg16_train_step_multitask calls: logits [n][c] (k = 0) or [n][k][c] with c = the sum of head_sizes; labels i64 [n],
+ * LOCAL to the video's head; tasks i32 [n]; head_sizes: HOST int[n_heads]; dlogits like logits; out f32 [2 + 2 n_heads] =
+ * loss, hits, loss per head, hits per head.  n >= 1, n * max(k, 1) <= 64, 1 <= n_heads <= 8, every head >= 1 class, c <= 2^20;
+ * anything else is VA_ERR_INVALID before a launch.
+ */
+int va_train_loss_multitask(va_ctx* ctx, const float* logits, const void* labels, const void* tasks, int n, int k,
+                            int n_heads, const int* head_sizes, float* dlogits, float* out, void* stream);
 /* Dropout(p = 0.5) of the step's classifier layer `layer` (0..2) in place on x f32 [n] (k_dropout, keys from
  * (dropout_seed, layer) as va_vgg16_train_step derives them). */
 int va_train_dropout(va_ctx* ctx, float* x, size_t n, unsigned long long dropout_seed, int layer, void* stream);
@@ -563,6 +572,21 @@ int va_vgg16_train_step(va_vgg16* model, const void* x, int x_is_u8, const void*
 int va_vgg16_train_step_consensus(va_vgg16* model, const void* x, int x_is_u8, const void* labels, int n, int k,
                                   float lr, float momentum, unsigned long long dropout_seed, void* desc,
                                   void* loss_out, void* workspace, size_t workspace_bytes, void* stream);
+/*
+ * The same step with one loss per dataset (multi-task learning, Sheet03/notes.txt:88-96): the model's last
+ * layer holds n_heads heads, head t the outputs [o_t, o_t + head_sizes[t]) with o_t = head_sizes[0] + ... + head_sizes[t-1];
+ * the sum of head_sizes (HOST int[n_heads], 1 <= n_heads <= 8, each >= 1) must be the model's n_classes.  tasks i32 [n]
+ * (device) names each video's head, labels i64 [n] are local to it.  Each head's loss is va_vgg16_train_step_consensus's
+ * on the head's videos and outputs (its mean over that head's videos); the step descends the sum of the heads' losses; the
+ * outputs of the other heads receive a zero gradient, so a head without a video in the batch moves by its momentum alone, as
+ * the rows of one torch parameter do under torch.optim.SGD.  loss_out: device f32 [2 + 2 n_heads] = { loss, hits, loss of
+ * every head, hits of every head }.  k >= 1, n*k <= 64; n_heads = 1 gives va_vgg16_train_step_consensus's bits.
+ * workspace: va_vgg16_train_workspace_bytes(n*k).  A task outside [0, n_heads) or a label outside its head: NaN loss.
+ */
+int va_vgg16_train_step_multitask(va_vgg16* model, const void* x, int x_is_u8, const void* labels, const void* tasks,
+                                  int n, int k, int n_heads, const int* head_sizes, float lr, float momentum,
+                                  unsigned long long dropout_seed, void* desc, void* loss_out, void* workspace,
+                                  size_t workspace_bytes, void* stream);
 /*
  * Checkpoints (Sheet03/spatialModel.py:234-260, Sheet03/utils.py:29-35): copy the parameters (which = 0) or the
  * momentum buffers (which = 1) out to / in from device tensors in the reference's layouts -- conv OIHW

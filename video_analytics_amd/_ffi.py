@@ -31,6 +31,7 @@ EXPORTS = [
     "va_flow_homography", "va_flow_compensate",
     "va_rgbdiff_to_stack", "va_fuse_scores_n",
     "va_train_conv_backward_layer", "va_train_fc_backward_layer", "va_train_pool_layer", "va_train_loss", "va_train_dropout",
+    "va_vgg16_train_step_multitask", "va_train_loss_multitask",
 ]
 
 
@@ -203,6 +204,11 @@ def lib():
     L.va_train_loss.restype = ci
     L.va_train_dropout.argtypes = [vp, vp, sz, ctypes.c_ulonglong, ci, vp]
     L.va_train_dropout.restype = ci
+    pi = ctypes.POINTER(ci)
+    L.va_vgg16_train_step_multitask.argtypes = [vp, vp, ci, vp, vp, ci, ci, ci, pi, cf, cf, ctypes.c_ulonglong, vp, vp, vp, sz, vp]
+    L.va_vgg16_train_step_multitask.restype = ci
+    L.va_train_loss_multitask.argtypes = [vp, vp, vp, vp, ci, ci, ci, pi, vp, vp, vp]
+    L.va_train_loss_multitask.restype = ci
     _lib = L
     return L
 

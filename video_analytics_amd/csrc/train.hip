@@ -672,11 +672,21 @@ void dropout_layer(float* x, size_t n, unsigned long long seed, int layer, hipSt
     k_dropout<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(x, n, key, key2);
 }
 
-// segments = 0: the loss of every row of logits [B][C]; segments = K >= 1: of the consensus of B / K videos
-void loss_layer(const float* logits, const long long* labels, int B, int segments, int C, float* dlogits, float* out, hipStream_t st)
+// The heads of the multi-task form of the loss: tasks i32 [videos] on the device
+struct MultiTask {
+    const int* tasks;
+    va_heads heads;
+};
+
+// segments = 0: the loss of every row of logits [B][C]; segments = K >= 1: of the consensus of B / K videos; mt != NULL: the
+// multi-task consensus loss of B / max(K, 1) videos (k_ce_multitask_fwd_bwd in multitask.hip), every head on its own columns
+int loss_layer(const float* logits, const long long* labels, int B, int segments, int C, float* dlogits, float* out, hipStream_t st,
+               const MultiTask* mt = nullptr)
 {
+    if (mt) return va_ce_multitask(logits, labels, mt->tasks, B / (segments > 0 ? segments : 1), segments > 0 ? segments : 1, mt->heads, dlogits, out, st);
     if (segments == 0) k_ce_fwd_bwd<<<1, 256, 0, st>>>(logits, labels, B, C, dlogits, out);
     else k_ce_consensus_fwd_bwd<<<1, 256, 0, st>>>(logits, labels, B / segments, segments, C, dlogits, out);
+    return VA_OK;
 }
 
 // dx (with mask and scale), then the weight and bias updates in place; *inst (may be NULL): the batch instantiation, 32 or 64
@@ -774,10 +784,11 @@ extern "C" size_t va_vgg16_train_workspace_bytes(const va_vgg16* m, int batch)
 
 // The step both entry points share.  segments = 0: va_vgg16_train_step, the loss of every image (k_ce_fwd_bwd);
 // segments = K >= 1: va_vgg16_train_step_consensus, `batch` = videos * K images, video-major, and the loss of the videos'
-// consensus (k_ce_consensus_fwd_bwd).  Everything but that one launch is the same code.
+// consensus (k_ce_consensus_fwd_bwd); mt != NULL: va_vgg16_train_step_multitask, the consensus loss of every head on its own
+// videos and columns (k_ce_multitask_fwd_bwd, loss_out f32 [2 + 2H]).  Everything but that one launch is the same code.
 static int train_step(const char* who, va_vgg16* m, const void* x, int x_is_u8, const void* labels, int batch, int segments, float lr,
                       float momentum, unsigned long long dropout_seed, void* desc, void* loss_out, void* workspace,
-                      size_t workspace_bytes, void* stream)
+                      size_t workspace_bytes, void* stream, const MultiTask* mt = nullptr)
 {
     VA_CHECK_ARG(m != nullptr && x != nullptr && labels != nullptr && loss_out != nullptr, "%s: NULL argument", who);
     VA_USE_DEVICE(m->ctx);
@@ -817,7 +828,7 @@ static int train_step(const char* who, va_vgg16* m, const void* x, int x_is_u8, 
         if (l < 3) dropout_layer(fout[l], (size_t)B * m->fc_out[l], dropout_seed, l, st);
     }
     if (desc) VA_HIP(hipMemcpyAsync(desc, F(T.a_d[2]), (size_t)B * m->desc_dim * sizeof(float), hipMemcpyDeviceToDevice, st));
-    loss_layer(F(T.logits), (const long long*)labels, B, segments, m->n_classes, F(T.dlogits), (float*)loss_out, st);
+    if (int rc = loss_layer(F(T.logits), (const long long*)labels, B, segments, m->n_classes, F(T.dlogits), (float*)loss_out, st, mt)) return rc;
     VA_LAUNCH_CHECK();
 
     // ---------------- classifier backward + update ----------------
@@ -880,6 +891,18 @@ extern "C" int va_vgg16_train_step_consensus(va_vgg16* m, const void* x, int x_i
                  n, k);
     return train_step("va_vgg16_train_step_consensus", m, x, x_is_u8, labels, n * k, k, lr, momentum, dropout_seed, desc, loss_out,
                       workspace, workspace_bytes, stream);
+}
+
+extern "C" int va_vgg16_train_step_multitask(va_vgg16* m, const void* x, int x_is_u8, const void* labels, const void* tasks, int n, int k,
+                                             int n_heads, const int* head_sizes, float lr, float momentum, unsigned long long dropout_seed,
+                                             void* desc, void* loss_out, void* workspace, size_t workspace_bytes, void* stream)
+{
+    const char* who = "va_vgg16_train_step_multitask";
+    VA_CHECK_ARG(m != nullptr && tasks != nullptr, "%s: NULL argument", who);
+    VA_CHECK_ARG(n >= 1 && k >= 1 && (long long)n * k <= 64, "%s: %d videos x %d snippets out of range (n*k in [1,64])", who, n, k);
+    MultiTask mt{(const int*)tasks, {}};
+    if (int rc = va_heads_from_sizes(who, n_heads, head_sizes, m->n_classes, &mt.heads)) return rc;
+    return train_step(who, m, x, x_is_u8, labels, n * k, k, lr, momentum, dropout_seed, desc, loss_out, workspace, workspace_bytes, stream, &mt);
 }
 
 // which = 0: parameters, 1: momentum buffers.  Destination tensors in the reference's layouts (conv OIHW
@@ -1057,7 +1080,24 @@ extern "C" int va_train_loss(va_ctx* ctx, const float* logits, const void* label
     VA_CHECK_ARG(n >= 1 && k >= 0 && (long long)n * (k > 0 ? k : 1) <= 64, "%s: %d rows x %d snippets out of range (n * max(k, 1) in [1,64])", who, n, k);
     VA_CHECK_ARG(c >= 1 && c <= (1 << 20), "%s: c %d out of range", who, c);
     VA_CHECK_ARG(logits && labels && dlogits && out, "%s: NULL argument", who);
-    loss_layer(logits, (const long long*)labels, n * (k > 0 ? k : 1), k, c, dlogits, out, (hipStream_t)stream);
+    if (int rc = loss_layer(logits, (const long long*)labels, n * (k > 0 ? k : 1), k, c, dlogits, out, (hipStream_t)stream)) return rc;
+    VA_LAUNCH_CHECK();
+    return VA_OK;
+}
+
+extern "C" int va_train_loss_multitask(va_ctx* ctx, const float* logits, const void* labels, const void* tasks, int n, int k, int n_heads,
+                                       const int* head_sizes, float* dlogits, float* out, void* stream)
+{
+    const char* who = "va_train_loss_multitask";
+    VA_CHECK_ARG(ctx != nullptr, "%s: ctx is NULL", who);
+    VA_USE_DEVICE(ctx);
+    VA_CHECK_ARG(n >= 1 && k >= 0 && (long long)n * (k > 0 ? k : 1) <= 64, "%s: %d rows x %d snippets out of range (n * max(k, 1) in [1,64])", who, n, k);
+    MultiTask mt{(const int*)tasks, {}};
+    if (int rc = va_heads_from_sizes(who, n_heads, head_sizes, -1, &mt.heads)) return rc;
+    const int c = mt.heads.off[n_heads];
+    VA_CHECK_ARG(c >= 1 && c <= (1 << 20), "%s: c %d out of range", who, c);
+    VA_CHECK_ARG(logits && labels && tasks && dlogits && out, "%s: NULL argument", who);
+    if (int rc = loss_layer(logits, (const long long*)labels, n * (k > 0 ? k : 1), k, c, dlogits, out, (hipStream_t)stream, &mt)) return rc;
     VA_LAUNCH_CHECK();
     return VA_OK;
 }

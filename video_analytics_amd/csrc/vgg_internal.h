@@ -48,3 +48,16 @@ int va_fc_f32(const float* A, const float* Wt, const float* bias, float* out, fl
 size_t va_fc_slab_floats(int M, int N, int K);
 // x NCHW (f32 or u8 + ToTensor/Normalize) -> NHWC f32 with c_in_pad channels
 int va_input_to_nhwc_f32(const va_vgg16* m, const void* x, int x_is_u8, int B, float* out, hipStream_t st);
+
+// Multi-task loss (multitask.hip): the heads of one concatenated last layer, head t = columns [off[t], off[t+1])
+#define VA_MAX_HEADS 8
+struct va_heads {
+    int n;
+    int off[VA_MAX_HEADS + 1];  // off[0] = 0, off[n] = the layer's outputs; entries above n repeat off[n]
+};
+// head_sizes: HOST int[n_heads], 1 <= n_heads <= 8, every size >= 1; n_classes >= 0: their sum must equal it.  VA_ERR_INVALID otherwise.
+int va_heads_from_sizes(const char* who, int n_heads, const int* head_sizes, int n_classes, va_heads* out);
+// k_ce_multitask_fwd_bwd: logits / dlogits [videos][segments][off[n]], labels i64 [videos] local to the head, tasks i32 [videos],
+// out f32 [2 + 2n]; segments >= 1, videos * segments <= 64
+int va_ce_multitask(const float* logits, const long long* labels, const int* tasks, int videos, int segments, const va_heads& h,
+                    float* dlogits, float* out, hipStream_t st);

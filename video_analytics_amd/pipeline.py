@@ -17,9 +17,10 @@ from .parameters import (NACTION_CLASSES, NORM_MEANS_TF, NORM_STDS_TF, VIDEO_DES
                          VIDEO_INPUT_FLOW_COUNT)
 
 
-def build_stream_weights(c_in, seed, device):
-    """Random-init weights of one stream; the temporal first layer follows ``__copyFirstLayer__``."""
-    w = synth.synth_vgg16_weights(c_in=c_in, n_classes=NACTION_CLASSES, desc_dim=VIDEO_DESCRIPTOR_DIM, seed=seed,
+def build_stream_weights(c_in, seed, device, n_classes=NACTION_CLASSES):
+    """Random-init weights of one stream; the temporal first layer follows ``__copyFirstLayer__``.  ``n_classes``: the
+    outputs of the last layer (a multi-task pipeline: the sum of its heads)."""
+    w = synth.synth_vgg16_weights(c_in=c_in, n_classes=n_classes, desc_dim=VIDEO_DESCRIPTOR_DIM, seed=seed,
                                   device=device)
     if c_in != 3:
         w["conv_w"][0] = vgg.copy_first_layer(w["conv_w"][0].to(device), c_in)
@@ -92,11 +93,22 @@ class TwoStreamPipeline(object):
     ``3 * rgb_diff_count`` input channels (seed ``diff_seed`` or ``weights[2]``; its first layer is the cross-modality copy of
     an RGB one) that ``submit_video`` / ``run_video`` and ``train_videos`` feed with the differences of each snippet's first
     ``rgb_diff_count + 1`` RGB frames.  ``submit`` / ``run_batch`` receive one RGB frame per clip: they ignore the third
-    stream.  With the default nothing is allocated and every result keeps its bits."""
+    stream.  With the default nothing is allocated and every result keeps its bits.
+
+    ``heads``: a tuple of 1 to 8 class counts, one per dataset, builds every stream as a multi-task model: one
+    shared network whose last layer holds ``sum(heads)`` outputs, head t the columns ``vgg.head_logits(., heads, t)``.
+    ``train_videos`` then takes ``tasks=`` (one head per video, labels local to it) and ``submit_video`` / ``run_video``
+    ``task=``; ``submit`` / ``run_batch`` return the logits of all heads side by side.  None (the default) builds exactly
+    the single-head pipeline of ``NACTION_CLASSES`` classes."""
 
     def __init__(self, device=None, spatial_seed=1, temporal_seed=2, flow_count=VIDEO_INPUT_FLOW_COUNT,
                  tvl1_params=None, weights=None, flow_streams=2, cnn_dtype="f32", depth=2, motion="stack", mean_flow=False,
-                 rgb_diff=False, rgb_diff_count=rgbdiff.RGB_DIFF_COUNT, diff_seed=3, camera="none"):
+                 rgb_diff=False, rgb_diff_count=rgbdiff.RGB_DIFF_COUNT, diff_seed=3, heads=None, camera="none"):
+        self.heads = None
+        if heads is not None:
+            vgg.check_heads(heads, None, "TwoStreamPipeline")
+            self.heads = tuple(int(h) for h in heads)
+        n_classes = NACTION_CLASSES if self.heads is None else sum(self.heads)
         vflow.check_motion(motion, mean_flow, flow_count, "TwoStreamPipeline", camera=camera)
         self.D = rgbdiff.check_diff_count(rgb_diff_count, flow_count, "TwoStreamPipeline") if rgb_diff else 0
         if weights and len(weights) != (3 if rgb_diff and len(weights) > 2 else 2):
@@ -107,17 +119,17 @@ class TwoStreamPipeline(object):
         self.L = flow_count
         self.motion, self.mean_flow, self.camera = motion, mean_flow, camera
         with torch.cuda.device(dev):
-            ws = weights[0] if weights else build_stream_weights(3, spatial_seed, dev)
-            wt = weights[1] if weights else build_stream_weights(2 * flow_count, temporal_seed, dev)
-            self.spatial = vgg.Vgg16Stream(ws["conv_w"], ws["conv_b"], ws["fc_w"], ws["fc_b"], NACTION_CLASSES,
+            ws = weights[0] if weights else build_stream_weights(3, spatial_seed, dev, n_classes)
+            wt = weights[1] if weights else build_stream_weights(2 * flow_count, temporal_seed, dev, n_classes)
+            self.spatial = vgg.Vgg16Stream(ws["conv_w"], ws["conv_b"], ws["fc_w"], ws["fc_b"], n_classes,
                                            VIDEO_DESCRIPTOR_DIM, NORM_MEANS_TF, NORM_STDS_TF, device=dev.index, ws_slot=1,
                                            dtype=cnn_dtype)
-            self.temporal = vgg.Vgg16Stream(wt["conv_w"], wt["conv_b"], wt["fc_w"], wt["fc_b"], NACTION_CLASSES,
+            self.temporal = vgg.Vgg16Stream(wt["conv_w"], wt["conv_b"], wt["fc_w"], wt["fc_b"], n_classes,
                                             VIDEO_DESCRIPTOR_DIM, device=dev.index, dtype=cnn_dtype)
             self.diff = None
             if rgb_diff:  # float input (the differences are normalised by the gather), a workspace of its own
-                wd = weights[2] if weights and len(weights) > 2 else build_stream_weights(3 * self.D, diff_seed, dev)
-                self.diff = vgg.Vgg16Stream(wd["conv_w"], wd["conv_b"], wd["fc_w"], wd["fc_b"], NACTION_CLASSES,
+                wd = weights[2] if weights and len(weights) > 2 else build_stream_weights(3 * self.D, diff_seed, dev, n_classes)
+                self.diff = vgg.Vgg16Stream(wd["conv_w"], wd["conv_b"], wd["fc_w"], wd["fc_b"], n_classes,
                                             VIDEO_DESCRIPTOR_DIM, device=dev.index, ws_slot=2, dtype=cnn_dtype)
         self.tvl1_params = tvl1_params
         self.flow_streams = max(1, int(flow_streams))
@@ -244,7 +256,8 @@ class TwoStreamPipeline(object):
         ``q -> 255 - q`` (with ``views=`` or ``crops=``; the default mirrors without inverting, as the reference).
         The pipeline's ``motion`` / ``mean_flow`` apply with and without ``crops=`` / ``views=``; they need gray frames.
         A batch holds one RGB frame per clip, so an ``rgb_diff=True`` pipeline ignores its third stream here: the results
-        are those of a plain pipeline."""
+        are those of a plain pipeline.  On a pipeline with ``heads`` the logits are full width, all heads side by side:
+        ``vgg.head_logits(logits, heads, task)`` takes one head's columns."""
         if flow_stack is not None and (self.motion != "stack" or self.mean_flow):
             raise ValueError("submit: motion=%r / mean_flow=%r need gray frames; flow_stack= is already quantised"
                              % (self.motion, self.mean_flow))
@@ -359,6 +372,17 @@ class TwoStreamPipeline(object):
         out["done"] = finished
         return out
 
+    def _check_task(self, task, who):
+        """``task=`` against the pipeline's ``heads`` -> the head's index, or None on a pipeline without heads."""
+        heads = getattr(self, "heads", None)
+        if heads is None:
+            if task is not None:
+                raise ValueError("%s: task= needs a pipeline built with heads=" % who)
+            return None
+        if task is None:
+            raise ValueError("%s: this pipeline has the heads %s; task= must name the video's head" % (who, heads))
+        return vgg.check_task(task, heads, who)
+
     def _check_video(self, rgb, gray, n_snippets, views, consensus, fusion_weights, crops):
         """Host-side checks of ``submit_video`` before anything is enqueued -> (plan, rgb_views, flow_views, mode, weights):
         one fusion weight per stream, None meaning all ones."""
@@ -385,7 +409,7 @@ class TwoStreamPipeline(object):
         return plan, rgb_views, flow_views, mode, ws
 
     def submit_video(self, rgb, gray, n_snippets=video.N_SNIPPETS, views=None, invert_flow_x=False, consensus="softmax",
-                     fusion_weights=None, crops=None):
+                     fusion_weights=None, crops=None, task=None):
         """Enqueue one whole video (the test protocol of Sheet03/notes.txt:113-116 and 225-230):
         rgb u8 ``[T,3,H,W]``, gray u8 or f32 ``[T,H,W]``, the frames of one video on the device.  ``n_snippets`` snippets
         are placed by ``video.snippetStarts``; the frame pairs they share go through TV-L1 once each
@@ -405,7 +429,13 @@ class TwoStreamPipeline(object):
         ``done``.  The stream layout is ``submit(views=)``'s: the TV-L1 of the next video queues behind this one's.
         ``mean_flow=True`` subtracts every planned field's own mean and ``camera="homography"`` compensates every planned
         field (the result gains ``homography`` and ``camera_share``, one entry per planned pair); trajectory and
-        bi-directional pipelines raise ValueError, as do bad shapes, a video shorter than one snippet and ``crops=``, before anything is enqueued."""
+        bi-directional pipelines raise ValueError, as do bad shapes, a video shorter than one snippet and ``crops=``, before anything is enqueued.
+
+        On a pipeline with ``heads`` ``task`` names the video's head and is required: every stream's item
+        logits go through ``vgg.head_logits(., heads, task)`` before the consensus and the fusion, so ``scores*`` hold the
+        ``heads[task]`` classes of that head and ``pred`` is local to it; ``logits_*_items`` stay full width, and the result
+        gains ``task``.  ``task=`` on a pipeline without heads raises ValueError."""
+        task = self._check_task(task, "submit_video")
         plan, rgb_views, flow_views, mode, fw = self._check_video(rgb, gray, n_snippets, views, consensus, fusion_weights, crops)
         dev = self.device
         n, U = plan.n, len(plan.pairs)
@@ -448,14 +478,15 @@ class TwoStreamPipeline(object):
             _, _, desc_tv, logits_tv = self.temporal.forward_views(stack)
             self._t_done = torch.cuda.Event()
             self._t_done.record(self._cnn)
-            scores_s = fusion.score_consensus(logits_sv.unsqueeze(0), consensus)
-            scores_t = fusion.score_consensus(logits_tv.unsqueeze(0), consensus)
+            own = (lambda t: t) if task is None else (lambda t: vgg.head_logits(t, self.heads, task))  # S26: the video's head
+            scores_s = fusion.score_consensus(own(logits_sv).unsqueeze(0), consensus)
+            scores_t = fusion.score_consensus(own(logits_tv).unsqueeze(0), consensus)
             desc_s = vgg.view_mean(desc_sv.view(1, -1, desc_sv.shape[-1]))
             desc_t = vgg.view_mean(desc_tv.view(1, -1, desc_tv.shape[-1]))
             if self.diff is None:
                 scores, pred = fusion.fuse_scores(scores_s, scores_t, fw)
             else:
-                scores_d = fusion.score_consensus(logits_dv.unsqueeze(0), consensus)
+                scores_d = fusion.score_consensus(own(logits_dv).unsqueeze(0), consensus)
                 scores, pred = fusion.fuse_scores_n([scores_s, scores_t, scores_d], fw)
                 desc_d = vgg.view_mean(desc_dv.view(1, -1, desc_dv.shape[-1]))
                 extra.update(scores_d=scores_d[0], desc_d=desc_d[0], logits_d_items=logits_dv)
@@ -466,25 +497,35 @@ class TwoStreamPipeline(object):
         self._handed_out.extend(out.values())
         out["starts"] = list(plan.starts)
         out["plan"] = plan
+        if task is not None:
+            out["task"] = task
         out["done"] = finished
         return out
 
     def run_video(self, rgb, gray, n_snippets=video.N_SNIPPETS, views=None, invert_flow_x=False, consensus="softmax",
-                  fusion_weights=None, crops=None):
+                  fusion_weights=None, crops=None, task=None):
         """``submit_video`` + ``wait()``: the results are ready on the current stream."""
-        out = self.submit_video(rgb, gray, n_snippets, views, invert_flow_x, consensus, fusion_weights, crops)
+        out = self.submit_video(rgb, gray, n_snippets, views, invert_flow_x, consensus, fusion_weights, crops, task)
         self.wait()
         return out
 
-    def _check_train_videos(self, videos, labels, k, starts, crops, rng):
-        """Host-side checks and draws of ``train_videos`` before anything is enqueued -> (videos, labels, plans, crops)."""
+    def _check_train_videos(self, videos, labels, k, starts, crops, rng, tasks=None):
+        """Host-side checks and draws of ``train_videos`` before anything is enqueued -> (videos, labels, plans, crops, tasks);
+        ``tasks`` is None on a pipeline without heads."""
         who = "train_videos"
+        heads = getattr(self, "heads", None)
+        if heads is None and tasks is not None:
+            raise ValueError("%s: tasks= needs a pipeline built with heads=" % who)
+        if heads is not None and tasks is None:
+            raise ValueError("%s: this pipeline has the heads %s; tasks= must name every video's head" % (who, heads))
         if self.spatial.dtype != "f32" or self.temporal.dtype != "f32":
             raise ValueError("%s: training is fp32 only; this pipeline was built with cnn_dtype=%r" % (who, self.spatial.dtype))
         videos = list(videos)
         n, k = len(videos), int(k)
         if n < 1 or k < 1 or n * k > 64:
             raise ValueError("%s: %d videos x %d snippets out of range (n*k in 1..64)" % (who, n, k))
+        if heads is not None:  # S26: one head per video, labels local to it
+            labels, tasks = vgg.check_tasks(labels, tasks, heads, n, who)
         for v in videos:
             if not isinstance(v, (tuple, list)) or len(v) != 2:
                 raise ValueError("%s: videos must be a list of (rgb u8 [T,3,H,W], gray [T,H,W]) pairs" % who)
@@ -530,10 +571,10 @@ class TwoStreamPipeline(object):
         if crops is None:
             crops = augment.draw_scale_jitter_crops(n * k, H, W, rng)
         augment.check_jitter_crops(crops, n * k, H, W, who)
-        return videos, labels, plans, crops
+        return videos, labels, plans, crops, tasks
 
     def train_videos(self, videos, labels, k=video.N_SEGMENTS, starts=None, crops=None, lr=1e-3, momentum=0.9, dropout_seed=0,
-                     invert_flow_x=False, rng=None):
+                     invert_flow_x=False, rng=None, tasks=None):
         """One TSN training step of both streams on whole videos (Sheet03/notes.txt:165-185, 212-223).
         ``videos``: a list of n ``(rgb u8 [T,3,H,W], gray [T,H,W])`` pairs on the device, one frame size, any lengths;
         ``labels``: their n class indices; ``n*k <= 64``.
@@ -556,8 +597,18 @@ class TwoStreamPipeline(object):
 
         On an ``rgb_diff=True`` pipeline the third stream takes the same step on the differences of each
         snippet's first ``rgb_diff_count + 1`` RGB frames, seen through the snippet's crop (``rgbdiff.rgb_diff_stack``);
-        the result gains ``stats_d`` and ``desc_d``."""
-        videos, labels, plans, crops = self._check_train_videos(videos, labels, k, starts, crops, rng)
+        the result gains ``stats_d`` and ``desc_d``.
+
+        On a pipeline with ``heads`` ``tasks`` gives one head per video and is required, ``labels`` are local
+        to the video's head, every stream takes ``Vgg16Stream.train_step_multitask`` instead, and ``stats_*`` are f32
+        ``[2+2H]`` = (loss, hits, loss of every head, hits of every head).  ``tasks=`` on a pipeline without heads, a missing
+        ``tasks=`` on one with heads, a task outside the heads and a label outside its head raise ValueError before anything
+        is enqueued."""
+        videos, labels, plans, crops, tasks = self._check_train_videos(videos, labels, k, starts, crops, rng, tasks)
+        if tasks is None:
+            step = lambda m, x: m.train_step_consensus(x, labels, k, lr, momentum, dropout_seed)
+        else:
+            step = lambda m, x: m.train_step_multitask(x, labels, tasks, self.heads, k, lr, momentum, dropout_seed)
         dev, L, n, k = self.device, self.L, len(videos), int(k)
         cur = torch.cuda.current_stream(dev)
         frames = torch.cat([rgb[augment.crops_to_device(torch.tensor(p.starts, dtype=torch.int64), dev)]
@@ -591,15 +642,15 @@ class TwoStreamPipeline(object):
         xt = vflow.resize_flow_to_stack(src, flow_table, invert_x_on_flip=bool(invert_flow_x)).view(n * k, 2 * L, 224, 224)
         cur.wait_stream(self._cnn)   # forwards submitted earlier read the weights this step updates
         cur.wait_stream(self._cnn2)
-        stats_s, desc_s = self.spatial.train_step_consensus(xs, labels, k, lr, momentum, dropout_seed)
-        stats_t, desc_t = self.temporal.train_step_consensus(xt, labels, k, lr, momentum, dropout_seed)
+        stats_s, desc_s = step(self.spatial, xs)
+        stats_t, desc_t = step(self.temporal, xt)
         if self.diff is not None:  # S25: the windows' frames one after the other, one S23 call on the snippets' crops
             D = self.D
             win = torch.cat([rgb[augment.crops_to_device(torch.tensor([s + f for s in p.starts for f in range(D + 1)],
                                                                        dtype=torch.int64), dev)]
                              for (rgb, _), p in zip(videos, plans)])  # [n*k*(D+1),3,H,W]
             xd = rgbdiff.rgb_diff_stack(win, rgbdiff.window_table([i * (D + 1) for i in range(n * k)], crops), D)
-            extra["stats_d"], extra["desc_d"] = self.diff.train_step_consensus(xd, labels, k, lr, momentum, dropout_seed)
+            extra["stats_d"], extra["desc_d"] = step(self.diff, xd)
         self._cnn.wait_stream(cur)
         self._cnn2.wait_stream(cur)
         return dict(stats_s=stats_s, desc_s=desc_s, stats_t=stats_t, desc_t=desc_t, starts=[list(p.starts) for p in plans],

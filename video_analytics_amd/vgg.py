@@ -297,6 +297,46 @@ class Vgg16Stream(object):
                                                    _ffi.stream_ptr(self.device)))
         return stats, desc
 
+    def train_step_multitask(self, x, labels, tasks, heads, k, lr, momentum, dropout_seed):
+        """``train_step_consensus`` with one loss per dataset (multi-task learning, Sheet03/notes.txt:88-96):
+        the model's ``n_classes`` outputs are the concatenated heads ``heads = (C_0, ..., C_{H-1})``, 1 to 8 of them; x
+        ``[n*k,C,224,224]``, video-major, ``n*k <= 64``; ``tasks [n]`` names each video's head and ``labels [n]`` are local
+        to it (``0 <= label < C_task``).  Each head's loss is the consensus loss of its own videos on its own outputs; the
+        step descends their sum, and a head without a video in the batch moves by its momentum alone.  Returns (stats,
+        descriptors): ``stats`` f32 ``[2+2H]`` = (loss, hits, loss of every head, hits of every head), ``descriptors``
+        ``[n*k,D]``.  One head is ``train_step_consensus`` bit for bit.  Labels and tasks still on the host are checked here
+        (ValueError); on the device a bad row gives a NaN loss."""
+        if not getattr(self, "_train_ready", False):
+            self.train_init()
+        who = "Vgg16Stream.train_step_multitask"
+        if not isinstance(x, torch.Tensor) or not x.is_cuda or x.dtype not in (torch.float32, torch.uint8):
+            raise ValueError("%s: x must be a CUDA float32/uint8 tensor" % who)
+        if x.dim() != 4 or tuple(x.shape[1:]) != (self.c_in, 224, 224):
+            raise ValueError("%s: x must be [n*k,%d,224,224], got %s" % (who, self.c_in, tuple(x.shape)))
+        self._on_my_device(x, "train_step_multitask")
+        check_heads(heads, self.n_classes, who)
+        heads = [int(h) for h in heads]
+        B, k = int(x.shape[0]), int(k)
+        if k < 1 or B < 1 or B % k:
+            raise ValueError("%s: %d images are not a whole number of videos of k=%d snippets" % (who, B, k))
+        n = B // k
+        labels, tasks = check_tasks(labels, tasks, heads, n, who)
+        labels = labels.to(device=x.device, dtype=torch.int64).contiguous()
+        tasks = tasks.to(device=x.device, dtype=torch.int32).contiguous()
+        x = x.contiguous()
+        L = _ffi.lib()
+        nbytes = L.va_vgg16_train_workspace_bytes(self._h, B)
+        if nbytes == 0:
+            raise ValueError("%s: %d videos x %d snippets unsupported (n*k in 1..64, fp32 model)" % (who, n, k))
+        ws = _workspace(nbytes, x.device, ("train", self.ws_slot))
+        stats = torch.empty(2 + 2 * len(heads), dtype=torch.float32, device=x.device)
+        desc = torch.empty((B, self.desc_dim), dtype=torch.float32, device=x.device)
+        _ffi.check(L.va_vgg16_train_step_multitask(self._h, _ffi.ptr(x), int(x.dtype == torch.uint8), _ffi.ptr(labels), _ffi.ptr(tasks),
+                                                   n, k, len(heads), (ctypes.c_int * len(heads))(*heads), float(lr), float(momentum),
+                                                   int(dropout_seed) & 0xFFFFFFFFFFFFFFFF, _ffi.ptr(desc), _ffi.ptr(stats),
+                                                   _ffi.ptr(ws), ws.numel(), _ffi.stream_ptr(self.device)))
+        return stats, desc
+
     def _state_tensors(self, device):
         cin = self.c_in
         cw, cb = [], []
@@ -572,6 +612,24 @@ def train_loss(logits, labels, dlogits, out, k=0):
                                         _ffi.ptr(out), _ffi.stream_ptr(logits.device)))
 
 
+def train_loss_multitask(logits, labels, tasks, heads, dlogits, out, k=0):
+    """``va_train_loss_multitask``: logits [n][c] (k = 0) or [n][k][c] with c = sum(heads); labels int64 [n],
+    local to the video's head, and tasks int32 [n], both on the device; dlogits like logits; out float32 [2 + 2 len(heads)] =
+    loss, hits, the loss of every head, the hits of every head."""
+    who = "train_loss_multitask"
+    _f32_cuda(who, logits, logits=logits, dlogits=dlogits, out=out)
+    n, c = logits.shape[0], logits.shape[-1]
+    check_heads(heads, c, who)
+    heads = [int(h) for h in heads]
+    if (tuple(logits.shape) != ((n, c) if k == 0 else (n, k, c)) or dlogits.shape != logits.shape or out.numel() < 2 + 2 * len(heads)
+            or labels.dtype != torch.int64 or tuple(labels.shape) != (n,) or labels.device != logits.device or not labels.is_contiguous()
+            or tasks.dtype != torch.int32 or tuple(tasks.shape) != (n,) or tasks.device != logits.device or not tasks.is_contiguous()):
+        raise ValueError("%s: logits / labels / tasks / dlogits / out do not match" % who)
+    _ffi.check(_ffi.lib().va_train_loss_multitask(_ffi.ctx(logits.device.index), _ffi.ptr(logits), _ffi.ptr(labels), _ffi.ptr(tasks), n, int(k),
+                                                  len(heads), (ctypes.c_int * len(heads))(*heads), _ffi.ptr(dlogits), _ffi.ptr(out),
+                                                  _ffi.stream_ptr(logits.device)))
+
+
 def train_dropout(x, seed, layer):
     """``va_train_dropout``: the step's Dropout(0.5) of classifier layer ``layer`` (0..2) in place on float32 x."""
     _f32_cuda("train_dropout", x, x=x)
@@ -592,6 +650,82 @@ def _check_labels(labels, n_classes, who):
         lo, hi = int(labels.min()), int(labels.max())
         if lo < 0 or hi >= n_classes:
             raise ValueError("%s: Target %d is out of bounds for %d classes" % (who, hi if hi >= n_classes else lo, n_classes))
+
+
+MAX_HEADS = 8  # VA_MAX_HEADS of the library
+
+
+def check_heads(heads, n_classes, who):
+    """The heads of a multi-task model: ``heads`` = 1 to 8 positive integers, the class counts of the datasets,
+    whose sum is ``n_classes``, the outputs of the shared last layer (``None``: any sum).  -> the tuple of their offsets:
+    head t owns the logit columns ``[off[t], off[t] + heads[t])``.  ValueError otherwise."""
+    import numbers
+    try:
+        hs = list(heads)
+    except TypeError:
+        raise ValueError("%s: heads must be a sequence of 1..%d class counts, got %r" % (who, MAX_HEADS, heads))
+    if not 1 <= len(hs) <= MAX_HEADS:
+        raise ValueError("%s: 1..%d heads, got %d" % (who, MAX_HEADS, len(hs)))
+    for h in hs:
+        if isinstance(h, bool) or not isinstance(h, numbers.Integral) or h < 1:
+            raise ValueError("%s: every head needs a positive integer class count, got %r" % (who, h))
+    if n_classes is not None and sum(int(h) for h in hs) != int(n_classes):
+        raise ValueError("%s: the heads %s hold %d classes, the last layer %d" % (who, tuple(hs), sum(int(h) for h in hs), n_classes))
+    offs, o = [], 0
+    for h in hs:
+        offs.append(o)
+        o += int(h)
+    return tuple(offs)
+
+
+def check_task(task, heads, who):
+    """-> ``task`` as an int in ``[0, len(heads))``; ValueError otherwise."""
+    import numbers
+    if isinstance(task, bool) or not isinstance(task, numbers.Integral) or not 0 <= task < len(heads):
+        raise ValueError("%s: task must be the index of one of the %d heads, got %r" % (who, len(heads), task))
+    return int(task)
+
+
+def head_logits(t, heads, task):
+    """The class scores of head ``task``: the columns ``[o_task, o_task + heads[task])`` of the last dimension of a logits
+    tensor of ``sum(heads)`` columns (``submit`` / ``run_batch`` and ``Vgg16Stream.forward`` return all heads side by
+    side), as a contiguous tensor."""
+    if not isinstance(t, torch.Tensor) or t.dim() < 1:
+        raise ValueError("head_logits: a logits tensor [..., sum(heads)] is needed")
+    offs = check_heads(heads, int(t.shape[-1]), "head_logits")
+    task = check_task(task, list(heads), "head_logits")
+    return t[..., offs[task]:offs[task] + int(list(heads)[task])].contiguous()
+
+
+def check_tasks(labels, tasks, heads, n, who):
+    """The host-side checks of a multi-task batch -> (labels, tasks) as tensors ``[n]`` (lists become CPU tensors).  What is
+    still on the host is checked without touching the GPU: every task in ``[0, len(heads))`` and, head by head,
+    ``_check_labels`` of that head's videos against its class count.  Tensors already on the device are not copied back:
+    for those the kernel reads nothing out of bounds and returns a NaN loss."""
+    def as_tensor(v, name, dtype):
+        if isinstance(v, torch.Tensor):
+            if v.dtype not in (torch.int32, torch.int64):
+                raise ValueError("%s: %s must be an integer tensor, got %s" % (who, name, v.dtype))
+            return v
+        try:
+            return torch.tensor([int(e) for e in v], dtype=dtype)
+        except (TypeError, ValueError):
+            raise ValueError("%s: %s must be a tensor or a list of %d integers" % (who, name, n))
+    labels = as_tensor(labels, "labels", torch.int64)
+    tasks = as_tensor(tasks, "tasks", torch.int32)
+    if labels.dim() != 1 or labels.shape[0] != n:
+        raise ValueError("%s: labels must be [%d], one per video, got %s" % (who, n, tuple(labels.shape)))
+    if tasks.dim() != 1 or tasks.shape[0] != n:
+        raise ValueError("%s: tasks must be [%d], one head per video, got %s" % (who, n, tuple(tasks.shape)))
+    heads = [int(h) for h in heads]
+    if not tasks.is_cuda and n > 0:
+        lo, hi = int(tasks.min()), int(tasks.max())
+        if lo < 0 or hi >= len(heads):
+            raise ValueError("%s: task %d is not one of the %d heads" % (who, hi if hi >= len(heads) else lo, len(heads)))
+        if not labels.is_cuda:
+            for t, c in enumerate(heads):
+                _check_labels(labels[tasks == t], c, "%s (head %d)" % (who, t))
+    return labels, tasks
 
 
 def view_mean(x):

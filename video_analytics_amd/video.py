@@ -128,7 +128,10 @@ def evaluateVideos(pipe, videos, labels, **kw):
 
     On a pipeline with the RGB-difference stream (``rgb_diff=True``) the result is
     ``(acc_spatial, acc_temporal, acc_fused, descriptors, acc_difference)`` with descriptors ``[N,768]`` (spatial, temporal,
-    difference) and ``fusion_weights`` of three entries."""
+    difference) and ``fusion_weights`` of three entries.
+
+    On a pipeline with ``heads`` ``task=`` travels through ``kw`` to ``submit_video``: the videos of one
+    call belong to one dataset, the scores are that head's and ``labels`` are local to it."""
     labels = [int(l) for l in labels]
     rows, pending, n = [], None, 0
     third = getattr(pipe, "diff", None) is not None

@@ -40,6 +40,7 @@
  *                     Sheet03/utils.py:154-171, Sheet03/spatialModel.py:223-228.
  *   va_linear_svm_predict   LinearSVC.predict on the joined descriptors:
  *                     Sheet03/combinedModel.py:38.
+ *   va_linear_svm_fit*      LinearSVC().fit on the same descriptors: Sheet03/combinedModel.py:34-35.
  *   va_vgg16_train_*  the batch-loop body of train(): Sheet03/spatialModel.py:165-182;
  *   va_vgg16_export/import_state   checkpoint contents: Sheet03/spatialModel.py:234-260.
  *
@@ -502,11 +503,39 @@ int va_meter_average(va_ctx* ctx, const void* sums, const void* counts, int n_sl
  * intercept f64 [n_class_rows] (sklearn's coef_ / intercept_; n_class_rows == 1 for a binary problem)
  * -> scores f64 [n][n_class_rows] = x coef^T + intercept (sum over dim in ascending order, double
  * multiply then add), pred i32 [n] = index into classes_: arg-max (first maximum), or score > 0 for
- * the binary case.  Fitting the SVM stays on the CPU (liblinear).
+ * the binary case.  The model is a fitted LinearSVC's or va_linear_svm_fit's.
  */
 int va_linear_svm_predict(va_ctx* ctx, const void* x, int n, int dim, const void* coef,
                           const void* intercept, int n_class_rows, void* scores, void* pred,
                           void* stream);
+
+/*
+ * LinearSVC().fit of the fusion step (Sheet03/combinedModel.py:34-35): liblinear's L2R_L2LOSS_SVC,
+ * one-vs-rest.  Class row r minimises f_r(w) = 1/2 |w|^2 + C sum_i max(0, 1 - y_i w.[x_i, s])^2 over w in R^(dim+1), with
+ * y_i = +1 where y[i] is the row's class and -1 elsewhere and s = intercept_scaling (the bias is regularised, as in
+ * liblinear; s = 0: no intercept); coef[r] = w[0..dim), intercept[r] = s w[dim].  rows = n_classes == 2 ? 1 : n_classes,
+ * the single row of a binary problem being class 1's (sklearn's convention, which va_linear_svm_predict reads).
+ *
+ * x f64 [n][dim], y i32 [n] with values in [0, n_classes).  The solver is a primal Newton-CG in float64 over all rows at
+ * once; a row stops, and is frozen, when |grad f_r(w)| <= tol |grad f_r(0)|.  The call enqueues newton_iters Newton steps
+ * on the caller's stream and then writes coef f64 [rows][dim], intercept f64 [rows] and stats f64 [rows][4] = f_r,
+ * |grad f_r|, |grad f_r(0)|, Newton steps taken so far; it allocates nothing and does not synchronise.  restart = 1 starts
+ * from w = 0; restart = 0 continues from the state a previous call left in the workspace (same x, y, sizes and scalars), so
+ * that a caller may enqueue a few steps, read stats, and go on until every row has stopped: the steps of one long call and
+ * of several short ones are the same operations and give the same bits.  No atomics: two fits of the same input agree
+ * bit for bit.  workspace: va_linear_svm_fit_workspace_bytes(n, dim, rows) bytes, 8-byte aligned (too small:
+ * VA_ERR_WORKSPACE).  n >= 2, 1 <= dim <= 8192, 2 <= n_classes <= 4096, C > 0, tol > 0, intercept_scaling >= 0, all
+ * finite, 0 <= newton_iters <= 1000, else VA_ERR_INVALID before anything is launched.  The size query answers 0 and sets
+ * va_last_error for sizes out of range (n_class_rows is 1 or 3 .. 4096).
+ */
+size_t va_linear_svm_fit_workspace_bytes(int n, int dim, int n_class_rows);
+int va_linear_svm_fit(va_ctx* ctx, const void* x, const void* y, int n, int dim, int n_classes, double C,
+                      double intercept_scaling, double tol, int newton_iters, int restart, void* coef, void* intercept,
+                      void* stats, void* workspace, size_t workspace_bytes, void* stream);
+/* cg_steps f64 [n_class_rows]: the CG steps every row has taken since restart = 1, read from the workspace of a fit of the
+ * same sizes (a measurement for tools/bench_svm_fit.py and the info of linear_svm_fit; asynchronous, on the stream). */
+int va_linear_svm_fit_cg_steps(va_ctx* ctx, int n, int dim, int n_class_rows, const void* workspace,
+                               size_t workspace_bytes, void* cg_steps, void* stream);
 
 /*
  * The consensus over the k items (snippets x views, snippet-major) of each of n videos:

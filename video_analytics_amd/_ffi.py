@@ -32,6 +32,7 @@ EXPORTS = [
     "va_rgbdiff_to_stack", "va_fuse_scores_n",
     "va_train_conv_backward_layer", "va_train_fc_backward_layer", "va_train_pool_layer", "va_train_loss", "va_train_dropout",
     "va_vgg16_train_step_multitask", "va_train_loss_multitask",
+    "va_linear_svm_fit_workspace_bytes", "va_linear_svm_fit", "va_linear_svm_fit_cg_steps",
 ]
 
 
@@ -209,6 +210,13 @@ def lib():
     L.va_vgg16_train_step_multitask.restype = ci
     L.va_train_loss_multitask.argtypes = [vp, vp, vp, vp, ci, ci, ci, pi, vp, vp, vp]
     L.va_train_loss_multitask.restype = ci
+    cd = ctypes.c_double
+    L.va_linear_svm_fit_workspace_bytes.argtypes = [ci, ci, ci]
+    L.va_linear_svm_fit_workspace_bytes.restype = sz
+    L.va_linear_svm_fit.argtypes = [vp, vp, vp, ci, ci, ci, cd, cd, cd, ci, ci, vp, vp, vp, vp, sz, vp]
+    L.va_linear_svm_fit.restype = ci
+    L.va_linear_svm_fit_cg_steps.argtypes = [vp, ci, ci, ci, vp, sz, vp, vp]
+    L.va_linear_svm_fit_cg_steps.restype = ci
     _lib = L
     return L
 

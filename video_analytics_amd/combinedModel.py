@@ -1,8 +1,10 @@
 """Fusion of the two streams: the reference's ``Sheet03/combinedModel.py`` call surface.
 
 ``combineDescriptors`` is the inner join of the two per-video descriptor CSVs (Sheet03/combinedModel.py:9-26).
-The reference then fits ``svm.LinearSVC`` on the CPU (``:34-35``, liblinear training: out of scope) and
-calls ``predict`` (``:38``); ``linearSvmPredict`` is that predict as argmax(X W^T + b).
+The reference then fits ``svm.LinearSVC`` on the CPU (``:34-35``, liblinear) and calls ``predict`` (``:38``);
+``linearSvmPredict`` is that predict as argmax(X W^T + b), and ``linearSvmFit`` is the fit on the device: the same
+problem (L2-regularised squared hinge, one-vs-rest, regularised bias) solved by a float64 Newton-CG.
+``main()`` keeps the reference's liblinear fit by default; ``main(fit="device")`` fits on the GPU and needs no sklearn.
 """
 import numpy as np
 import pandas as pd
@@ -36,9 +38,18 @@ def combineDescriptors(spatialCsv, temporalCsv):
 def linearSvmPredict(descriptors, coef, intercept, classes):
     """``LinearSVC.predict`` (Sheet03/combinedModel.py:38) on the GPU: classes[argmax(X coef^T + intercept)]
     (one-vs-rest; a single coefficient row is the binary case).  ``coef`` / ``intercept`` / ``classes``
-    are a fitted ``LinearSVC``'s ``coef_`` / ``intercept_`` / ``classes_`` (fitting stays on the CPU)."""
+    are a fitted ``LinearSVC``'s ``coef_`` / ``intercept_`` / ``classes_``, or what ``linearSvmFit`` returns."""
     from . import fusion
     return fusion.linear_svm_predict(descriptors, coef, intercept, classes)
+
+
+def linearSvmFit(descriptors, labels, **kw):
+    """``LinearSVC().fit`` (Sheet03/combinedModel.py:34-35) on the GPU: ``fusion.linear_svm_fit`` with its keywords
+    (C, tol, max_iter, fit_intercept, intercept_scaling, device, return_info) -> ``(coef, intercept, classes)``, the
+    arguments of ``linearSvmPredict``.  On the joined descriptors ``[N,512]`` or on stacked scores ``[N,2C]`` alike.
+    Not offered: hinge loss, L1 penalty, Crammer-Singer, class or sample weights, sparse input."""
+    from . import fusion
+    return fusion.linear_svm_fit(descriptors, labels, **kw)
 
 
 def accuracy(preds, labels):
@@ -50,17 +61,27 @@ def accuracy(preds, labels):
     return (acc * 100.0) / len(labels)
 
 
-def main():
+def main(fit="sklearn"):
     """The fusion script (Sheet03/combinedModel.py:29-43): join the train and the test descriptor CSVs of both
-    streams, fit ``LinearSVC`` on the CPU (liblinear; fitting is outside the GPU path), keep the fitted model in
-    ``SVM_FILE``, predict the test videos on the GPU and print the accuracy."""
+    streams, fit the SVM, keep the fitted model in ``SVM_FILE``, predict the test videos on the GPU and print the
+    accuracy.  ``fit="sklearn"``: ``LinearSVC()`` on the CPU (liblinear), the fitted estimator in ``SVM_FILE``, as the
+    reference.  ``fit="device"``: ``linearSvmFit`` on the GPU, ``{"coef_", "intercept_", "classes_"}`` in ``SVM_FILE``;
+    sklearn is not imported."""
+    if fit not in ("sklearn", "device"):
+        raise ValueError("combinedModel.main: fit must be 'sklearn' or 'device', got %r" % (fit,))
     import joblib  # (the reference's ``sklearn.externals.joblib`` no longer exists)
-    from sklearn import svm
 
     from .parameters import (SPATIAL_TEST_CSV_LOC, SPATIAL_TRAIN_CSV_LOC, SVM_FILE, TEMPORAL_TEST_CSV_LOC,
                              TEMPORAL_TRAIN_CSV_LOC)
     trainX, trainY = combineDescriptors(SPATIAL_TRAIN_CSV_LOC, TEMPORAL_TRAIN_CSV_LOC)
     testX, testY = combineDescriptors(SPATIAL_TEST_CSV_LOC, TEMPORAL_TEST_CSV_LOC)
+    if fit == "device":
+        coef, intercept, classes = linearSvmFit(trainX, trainY)
+        joblib.dump({"coef_": coef, "intercept_": intercept, "classes_": classes}, SVM_FILE)
+        preds = linearSvmPredict(testX, coef, intercept, classes)
+        print("accuracy = %f percent" % accuracy(preds, testY))
+        return
+    from sklearn import svm
     clf = svm.LinearSVC()
     clf.fit(trainX, trainY)
     joblib.dump(clf, SVM_FILE)

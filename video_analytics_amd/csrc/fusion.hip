@@ -3,7 +3,8 @@
 // and LinearSVC.predict of the fusion step (Sheet03/combinedModel.py:38); the consensus over a video's snippets and
 // views and the weighted average of the two streams' scores (the test protocols of
 // Sheet03/notes.txt:113-116,121-124,225-230).  All are small,
-// HBM/latency-bound byte-and-index work: plain coalesced kernels, no MFMA.
+// HBM/latency-bound byte-and-index work: plain coalesced kernels, no MFMA.  (The fit of the SVM, which does use the f64
+// MFMA, is in svm.hip.)
 #include "va_internal.h"
 
 namespace {

@@ -6,9 +6,11 @@ needs no device-to-host copy; ``linear_svm_predict`` is ``LinearSVC.predict`` of
 (Sheet03/combinedModel.py:38) on the joined descriptors.  ``score_consensus`` and ``fuse_scores`` are the video-level
 half of the papers' test protocol (Sheet03/notes.txt:113-116, 121-124, 225-230): the class scores of a
 video's snippets and views averaged, then the two streams' scores fused by a weighted average (``fuse_scores_n``: any
-number of streams up to eight).
+number of streams up to eight).  ``linear_svm_fit`` is ``LinearSVC().fit`` of the same step
+(Sheet03/combinedModel.py:34-35) as a float64 Newton-CG on the device.
 """
 import ctypes
+import warnings
 
 import numpy as np
 import torch
@@ -224,3 +226,119 @@ def linear_svm_predict(descriptors, coef, intercept, classes, device=None, retur
                                                     _ffi.ptr(scores), _ffi.ptr(pred), _ffi.stream_ptr(dev)))
     out = classes[pred.cpu().numpy()]
     return (out, scores.cpu().numpy()) if return_scores else out
+
+
+SVM_FIT_NEWTON_CHUNK = 4  # Newton steps enqueued between two reads of the solver's statistics
+
+
+def check_svm_fit_args(descriptors, labels, C=1.0, tol=1e-8, max_iter=100, fit_intercept=True, intercept_scaling=1.0):
+    """The argument check of ``linear_svm_fit``, on the host alone (no GPU needed): ValueError for descriptors that are not
+    2-D ``[n >= 2, 1 <= d <= 8192]`` or hold non-finite values, labels of another length, fewer than two (or more than 4096)
+    distinct labels, and C, tol, max_iter or intercept_scaling out of range.  -> ``(classes, y)``: ``np.unique(labels)`` and
+    every label's index into it as int32."""
+    who = "linear_svm_fit"
+    for name, v, positive in (("C", C, True), ("tol", tol, True), ("intercept_scaling", intercept_scaling, bool(fit_intercept))):
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v) \
+                or (v <= 0 if positive else v < 0):
+            raise ValueError("%s: %s must be a finite number %s 0, got %r" % (who, name, ">" if positive else ">=", v))
+    if isinstance(max_iter, bool) or not isinstance(max_iter, (int, np.integer)) or max_iter < 1:
+        raise ValueError("%s: max_iter must be an integer >= 1 (Newton steps), got %r" % (who, max_iter))
+    if isinstance(descriptors, torch.Tensor):
+        if descriptors.dtype not in (torch.float32, torch.float64):
+            raise ValueError("%s: a descriptor tensor must be float32 or float64, got %s" % (who, descriptors.dtype))
+        shape = tuple(descriptors.shape)
+    else:
+        try:
+            descriptors = np.asarray(descriptors, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError("%s: descriptors must be numbers [n, d]" % who)
+        shape = descriptors.shape
+    if len(shape) != 2:
+        raise ValueError("%s: descriptors must be 2-D [n, d], got shape %s" % (who, tuple(shape)))
+    n, d = int(shape[0]), int(shape[1])
+    if n < 2 or d < 1 or d > 8192:
+        raise ValueError("%s: need n >= 2 rows and 1 <= d <= 8192 columns, got [%d, %d]" % (who, n, d))
+    finite = bool(torch.isfinite(descriptors).all()) if isinstance(descriptors, torch.Tensor) else bool(np.isfinite(descriptors).all())
+    if not finite:
+        raise ValueError("%s: descriptors hold non-finite values" % who)
+    labels = np.asarray(labels.cpu() if isinstance(labels, torch.Tensor) else labels)
+    if labels.ndim != 1 or labels.shape[0] != n:
+        raise ValueError("%s: %d descriptors but labels of shape %s" % (who, n, tuple(labels.shape)))
+    if labels.dtype.kind == "f" and not np.isfinite(labels).all():
+        raise ValueError("%s: labels hold non-finite values" % who)
+    classes, y = np.unique(labels, return_inverse=True)
+    if len(classes) < 2 or len(classes) > 4096:
+        raise ValueError("%s: need 2 .. 4096 distinct labels, got %d" % (who, len(classes)))
+    return classes, np.ascontiguousarray(y.reshape(-1), dtype=np.int32)
+
+
+def linear_svm_fit(descriptors, labels, C=1.0, tol=1e-8, max_iter=100, fit_intercept=True, intercept_scaling=1.0, device=None,
+                   return_info=False):
+    """``LinearSVC().fit`` (Sheet03/combinedModel.py:34-35) on the device: ``va_linear_svm_fit``, DESIGN.md S27 and S28.
+
+    The problem is ``LinearSVC``'s with its defaults, liblinear's L2R_L2LOSS_SVC one-vs-rest: row r minimises
+    ``1/2 |w|^2 + C sum_i max(0, 1 - y_i w.[x_i, s])^2`` with ``y_i = +1`` where ``labels[i] == classes[r]``, else ``-1``,
+    and ``s = intercept_scaling`` (the bias is regularised, as in liblinear); ``coef[r] = w[:d]``, ``intercept[r] = s w[d]``.
+    The objective is strongly convex, so the optimum is liblinear's; the solver is a float64 Newton-CG over all rows at once
+    and a row stops when ``|grad f_r(w)| <= tol |grad f_r(0)|``.  Two calls give the same bits.
+
+    ``descriptors``: an array-like ``[n, d]``, or a CUDA float32 / float64 tensor (float32 is widened on the device: what
+    ``video.evaluateVideos`` returns never visits the host); ``labels``: ``[n]``.  -> ``(coef [rows, d] f64, intercept [rows]
+    f64, classes)`` as numpy, ready for ``linear_svm_predict``; ``classes = np.unique(labels)``, and two classes give ONE
+    row, for ``classes[1]`` (sklearn's convention).  ``return_info=True`` adds ``{"n_iter", "rel_grad" [rows], "objective"
+    [rows], "converged", "steps" [rows], "cg_steps" [rows]}`` (Newton and CG steps of every row).  ``max_iter`` counts Newton steps; reaching it with a row not converged is a
+    ``RuntimeWarning`` and the iterate is returned.  ``fit_intercept=False``: no bias, ``intercept == 0``.
+
+    Fusion by an SVM on the streams' scores (Sheet03/notes.txt:124) is the same call on the stacked scores ``[N, 2C]``,
+    as for ``linear_svm_predict``.  Not offered: the hinge (L1) loss, the L1 penalty, Crammer-Singer, class or sample
+    weights, sparse input."""
+    classes, y = check_svm_fit_args(descriptors, labels, C, tol, max_iter, fit_intercept, intercept_scaling)
+    if not torch.cuda.is_available():
+        raise RuntimeError("linear_svm_fit: no GPU visible; the hot path has no CPU fallback")
+    if isinstance(descriptors, torch.Tensor) and descriptors.is_cuda:
+        dev = descriptors.device if device is None else torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
+        if dev.index is None:
+            dev = torch.device("cuda", torch.cuda.current_device())
+        x = descriptors.to(device=dev, dtype=torch.float64).contiguous()
+    else:
+        dev = torch.device("cuda", torch.cuda.current_device() if device is None else device)
+        src = descriptors.to(torch.float64).numpy() if isinstance(descriptors, torch.Tensor) else np.asarray(descriptors, dtype=np.float64)
+        x = torch.as_tensor(np.ascontiguousarray(src)).to(dev)
+    n, d = int(x.shape[0]), int(x.shape[1])
+    rows = 1 if len(classes) == 2 else len(classes)
+    scale = float(intercept_scaling) if fit_intercept else 0.0
+    L = _ffi.lib()
+    need = L.va_linear_svm_fit_workspace_bytes(n, d, rows)
+    if need == 0:
+        raise ValueError(L.va_last_error().decode("utf-8", "replace"))
+    yd = torch.as_tensor(y).to(dev)
+    work = torch.empty((need // 8,), dtype=torch.float64, device=dev)
+    coef = torch.empty((rows, d), dtype=torch.float64, device=dev)
+    intercept = torch.empty((rows,), dtype=torch.float64, device=dev)
+    stats = torch.empty((rows, 4), dtype=torch.float64, device=dev)
+    enqueued, restart = 0, 1
+    with torch.cuda.device(dev):
+        while True:
+            steps = min(int(SVM_FIT_NEWTON_CHUNK), int(max_iter) - enqueued)
+            _ffi.check(L.va_linear_svm_fit(_ffi.ctx(dev.index), _ffi.ptr(x), _ffi.ptr(yd), n, d, len(classes), float(C), scale, float(tol),
+                                           steps, restart, _ffi.ptr(coef), _ffi.ptr(intercept), _ffi.ptr(stats), _ffi.ptr(work), need,
+                                           _ffi.stream_ptr(dev)))
+            enqueued, restart = enqueued + steps, 0
+            st = stats.cpu().numpy()  # the one synchronisation of a round
+            converged = bool((st[:, 1] <= float(tol) * st[:, 2]).all())
+            if converged or enqueued >= int(max_iter):
+                break
+    if not converged:
+        warnings.warn("linear_svm_fit: %d of %d class rows not converged after max_iter = %d Newton steps"
+                      % (int((st[:, 1] > float(tol) * st[:, 2]).sum()), rows, int(max_iter)), RuntimeWarning)
+    out = (coef.cpu().numpy(), intercept.cpu().numpy(), classes)
+    if not return_info:
+        return out
+    with np.errstate(invalid="ignore", divide="ignore"):
+        rel = np.where(st[:, 2] > 0, st[:, 1] / st[:, 2], 0.0)
+    cg = torch.empty((rows,), dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        _ffi.check(L.va_linear_svm_fit_cg_steps(_ffi.ctx(dev.index), n, d, rows, _ffi.ptr(work), need, _ffi.ptr(cg), _ffi.stream_ptr(dev)))
+    info = {"n_iter": int(st[:, 3].max()), "rel_grad": rel, "objective": st[:, 0].copy(), "converged": converged,
+            "steps": st[:, 3].astype(np.int64), "cg_steps": cg.cpu().numpy().astype(np.int64)}
+    return out + (info,)

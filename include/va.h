@@ -79,9 +79,7 @@ extern "C" {
 typedef struct va_ctx va_ctx;
 typedef struct va_vgg16 va_vgg16;
 
-/* version number (currently 6) + VA_VERSION_EXPERIMENTS when the library was built with -DVA_EXPERIMENTS, i.e. when it
- * also holds the measured-slower kernel families behind va_tvl1_params.tuning / VA_OPT_BF16_VARIANT 6 */
-#define VA_VERSION_EXPERIMENTS 0x10000
+/* version number (currently 6; bit 0x10000, which marked a build flavour that no longer exists, is never set) */
 int va_version(void);
 const char* va_last_error(void);
 int va_ctx_create(int device, va_ctx** out);
@@ -115,9 +113,9 @@ size_t va_vgg16_workspace_bytes(const va_vgg16* model, int batch);
  *                           tiles with one LDS buffer on every layer; 2 = the LDS-DMA ring on every layer; 5 = the
  *                           two-group kernel (k_conv3x3_pp_bf16) on every layer with >= 128 output channels and >= 28x28
  *                           pixels (the default uses it on the 28x28 layers); 0, 1, 2, 5 and 7 add the same products in the
- *                           same order and agree bit for bit.  6 = the two-group kernel on halo bricks
- *                           (k_conv3x3_bpp_bf16; chunk-major K order: another fp32 summation order, so within bf16 noise
- *                           of the others; measured no faster).  7 = the weights-resident kernel (k_conv3x3_ws_bf16) on
+ *                           same order and agree bit for bit.  6 (a halo-brick form of the two-group kernel that
+ *                           measured no faster and was removed: DESIGN.md section 7) is refused with VA_ERR_INVALID.
+ *                           7 = the weights-resident kernel (k_conv3x3_ws_bf16) on
  *                           both layers with 64 input channels (the default uses it on conv1_2 only); bit-equal to 0, 1, 2, 5.
  *                           (3 and 4, round 2's first halo-brick kernel, are gone.)
  *   VA_OPT_BF16_FIRST_LAYER 1 (default) the first layer reads the NCHW input itself (k_conv1_fused_bf16); 0 = the input is
@@ -188,16 +186,15 @@ typedef struct va_tvl1_params {
                          per CU; bits 4-7: 256x16, 128x32, 84x48, 64x64, two 4-wave workgroups per
                          CU).  Bit 8 (256): iterate every level with the streaming kernel (a wave carries a
                          128-column strip row by row through 10 iterations per pass) instead of the
-                         register tiles; fixed-iteration mode only.  Bit 9 (512): iterate every level that fits one
-                         strip (<= 256 columns) with the persistent row pipeline k_iter_rows, the others with the
-                         streaming kernel.  Bit 10 (1024): the streaming kernel never lets the narrow last strips of two
+                         register tiles; fixed-iteration mode only.  Bit 9 (512): reserved, must be 0 (it selected a
+                         kernel that was removed; refused with VA_ERR_INVALID).  Bit 10 (1024): the streaming kernel never lets the narrow last strips of two
                          pairs share a wave (A/B switch).  0 (default) = library choice per level.  Results do not depend on it. */
-    int tuning[8];    /* the library's own tuning / experiment switches (which kernel iterates which pyramid level, chunking of
+    int tuning[8];    /* the library's own tuning switches (which kernel iterates which pyramid level, chunking of
                          rows, pipeline shapes: named in csrc/va_internal.h, VA_TUNE_*); va_tvl1_default_params fills in the
                          defaults (-1, 0, 0, 0, -1, 0, 0, 0) and callers leave them alone.  Results do not depend on any
-                         of them; the library reads no environment variable.  Several values select kernels that are
-                         only compiled with -DVA_EXPERIMENTS (measured slower, kept reproducible: DESIGN.md section 7);
-                         a default build rejects those with VA_ERR_INVALID. */
+                         of them; the library reads no environment variable.  Slots 4, 6 and 7 are reserved, must be 0 (or
+                         -1 for slot 4).  Values that selected a kernel family since removed (measured slower: DESIGN.md
+                         section 7) are rejected with VA_ERR_INVALID. */
 } va_tvl1_params;
 
 void va_tvl1_default_params(va_tvl1_params* p);

@@ -19,15 +19,16 @@ def _frames(n_seq, n_frames, H, W, seed):
 
 
 # tuning fields of va_tvl1_params the oracle has no counterpart for (results must not depend on them)
-def _needs_experiments():
-    """The measured-slower kernel families (k_iter_rows, k_iter_stream_q, k_iter_stream4, one deep wave, 3 pixels per
-    lane) are only in a library built with `make -C video_analytics_amd/csrc EXPERIMENTS=1` (va_version() says so)."""
-    from video_analytics_amd import _ffi
-    if not _ffi.has_experiments():
-        pytest.skip("libva_hip.so built without -DVA_EXPERIMENTS")
-
-
 PRODUCT_ONLY = ("block_iters", "tile_mask", "stream_levels", "stream_waves", "stream_chunks", "stream_slots", "stream_ppl", "stream_queue", "rows_levels", "rows_cfg")
+
+
+def _assert_retired(gray, **kw):
+    """The kernel families of DESIGN.md section 7 that measured slower were removed from the library.  The cases that drove
+    them stay, with their frames and switches, and hold the library to refusing those switches loudly (ValueError naming the
+    retirement) on every shape and schedule instead of silently running another kernel."""
+    from video_analytics_amd import flow as vflow
+    with pytest.raises(ValueError, match="retired"):
+        vflow.tvl1_flow(gray.cuda(), **kw)
 
 
 def _run_both(oracle_tvl1, gray, **kw):
@@ -94,10 +95,11 @@ def test_streaming_kernel_bit_exact(oracle_tvl1, H, W, nch):
 @pytest.mark.parametrize("H,W,nch", [(224, 224, 0), (224, 224, 2), (179, 179, 0), (143, 143, 1), (114, 114, 2), (100, 64, 3), (129, 225, 2),
                                      (57, 131, 1), (33, 130, 1), (17, 19, 0), (150, 300, 2)])
 def test_streaming_kernel_three_and_four_wave_forms_bit_exact(oracle_tvl1, waves, H, W, nch):
-    if waves >= 10:
-        _needs_experiments()
+    if waves >= 10:  # 3 x 5, 3 x 6, 4 x 6 waves x levels: retired
+        return _assert_retired(_frames(3, 2, H, W, seed=3 * H + W), epsilon=0.0, iters=16, warps=1, nscales=1, tile_mask=1 << 8,
+                               stream_chunks=nch, stream_waves=waves)
     # stream_waves = 0: the default choice (four waves x 4 levels, x 5 where a 20-column halo costs no third strip), 2: the
-    # two-wave form, 7 / 8 / 9: 4 x 4 / 4 x 5 / 4 x 3 wherever they fit, 10 ... 12 (experiments): 3 x 5, 3 x 6, 4 x 6.  The passes of
+    # two-wave form, 7 / 8 / 9: 4 x 4 / 4 x 5 / 4 x 3 wherever they fit.  The passes of
     # a warp step share the iterations evenly (44 = 15 + 15 + 14, 57 = 19 + 19 + 19, 29 = 15 + 14): every pass must end in the
     # last wave, otherwise the step falls back to the two-wave form (10, 23); 300 columns: three strips, where only the
     # one-wave form runs; chunks of rows; the smallest frames
@@ -137,11 +139,11 @@ def test_shared_last_strips_equal_unshared_on_many_pairs(H, W, nseq):
 @pytest.mark.parametrize("H,W,nch", [(179, 179, 0), (143, 143, 2), (100, 64, 3), (64, 300, 1), (150, 400, 3), (57, 131, 1), (33, 190, 1),
                                      (129, 225, 2), (40, 700, 1), (16, 16, 0)])
 def test_streaming_kernel_pixels_per_lane_bit_exact(oracle_tvl1, ppl, H, W, nch):
-    if ppl == 3:
-        _needs_experiments()
-    # k_iter_stream with 2 and 3 pixels per lane (strips of 128 / 192 columns; a shallower pipeline for 3):
-    # one strip without halo (179, 143, 131 columns at 3 per lane), several strips with halos that are multiples of the
-    # pixels per lane, chunks of rows, ragged widths whose pitch is padded to a multiple of 12 for 3 per lane
+    if ppl == 3:  # 192-column strips: retired
+        return _assert_retired(_frames(1, 3, H, W, seed=7 * H + W + ppl), epsilon=0.0, iters=10, warps=1, nscales=1, tile_mask=1 << 8,
+                               stream_chunks=nch, stream_ppl=ppl)
+    # k_iter_stream with an explicit stream_ppl = 2 (two pixels per lane, strips of 128 columns: what the default 0 means):
+    # one strip, several strips with halos that are multiples of the pixels per lane, chunks of rows, ragged widths
     gray = _frames(1, 3, H, W, seed=7 * H + W + ppl)
     for iters, warps, nscales in ((10, 1, 1), (29, 2, 3)):
         ref, out = _run_both(oracle_tvl1, gray, epsilon=0.0, iters=iters, warps=warps, nscales=nscales, tile_mask=1 << 8,
@@ -153,129 +155,46 @@ def test_streaming_kernel_pixels_per_lane_bit_exact(oracle_tvl1, ppl, H, W, nch)
 @pytest.mark.parametrize("H,W,nch", [(224, 224, 0), (224, 224, 3), (100, 64, 3), (129, 225, 2), (57, 131, 1), (179, 179, 2), (114, 114, 1),
                                      (48, 64, 0), (17, 19, 0), (33, 130, 1)])
 def test_streaming_kernel_two_chains_per_wave_bit_exact(oracle_tvl1, waves, H, W, nch):
-    _needs_experiments()
-    # stream_waves = 5 / 6: the levels of a wave are cut into TWO chains that are issued interleaved (the second chain takes
-    # its rows from a register latch one step later): one deep wave with 2 x 8 levels / two waves with 2 x 4 levels each.
-    # Iteration counts that do and do not fill the pipeline (16), passes that end in the first / second chain of the last
-    # wave (37 = 16 + 16 + 5; 29 = 16 + 13), chunks of rows, strips with halos, the smallest frames
-    gray = _frames(1, 3, H, W, seed=H + 5 * W)
-    for iters, warps, nscales in ((10, 1, 1), (37, 2, 3), (29, 1, 2), (48, 1, 1)):
-        ref, out = _run_both(oracle_tvl1, gray, epsilon=0.0, iters=iters, warps=warps, nscales=nscales, tile_mask=1 << 8,
-                             stream_chunks=nch, stream_waves=waves)
-        assert np.array_equal(out, ref), "max abs diff %g" % np.abs(out - ref).max()
+    # stream_waves = 5 / 6 (two interleaved chains of levels per wave, one deep wave / two waves): retired
+    _assert_retired(_frames(1, 3, H, W, seed=H + 5 * W), epsilon=0.0, iters=10, warps=1, nscales=1, tile_mask=1 << 8, stream_chunks=nch,
+                    stream_waves=waves)
 
 
 @pytest.mark.parametrize("H,W,nch", [(224, 224, 0), (100, 64, 3), (129, 225, 2), (57, 131, 1), (179, 179, 2)])
 def test_streaming_kernel_one_deep_wave_bit_exact(oracle_tvl1, H, W, nch):
-    _needs_experiments()
-    # stream_waves = 3: ONE wave carries all 16 levels (whole register file of its SIMD, no hand-over, no barrier)
-    gray = _frames(1, 3, H, W, seed=H + 3 * W)
-    for iters, warps, nscales in ((10, 1, 1), (37, 2, 3)):
-        ref, out = _run_both(oracle_tvl1, gray, epsilon=0.0, iters=iters, warps=warps, nscales=nscales, tile_mask=1 << 8,
-                             stream_chunks=nch, stream_waves=3)
-        assert np.array_equal(out, ref), "max abs diff %g" % np.abs(out - ref).max()
+    # stream_waves = 3 (one wave carrying all 16 levels): retired
+    _assert_retired(_frames(1, 3, H, W, seed=H + 3 * W), epsilon=0.0, iters=10, warps=1, nscales=1, tile_mask=1 << 8, stream_chunks=nch,
+                    stream_waves=3)
 
 
 @pytest.mark.parametrize("H,W,nch,nseq", [(224, 224, 0, 1), (224, 224, 2, 3), (100, 64, 3, 1), (129, 225, 2, 2), (57, 131, 1, 5), (179, 179, 2, 1),
                                           (114, 114, 3, 2), (40, 40, 1, 1)])
 def test_four_jobs_per_workgroup_bit_exact(oracle_tvl1, H, W, nch, nseq):
-    _needs_experiments()
-    # stream_waves = 4: k_iter_stream4 -- 512-thread workgroups run four (strip, chunk, pair) jobs each, the two waves of a job on
-    # the same SIMD; job counts that are not multiples of four (padding jobs), chunks of different lengths in one workgroup
-    # (padded step counts), several pairs per workgroup
-    gray = _frames(nseq, 3, H, W, seed=2 * H + W + nseq)
-    for iters, warps, nscales in ((10, 1, 1), (37, 2, 3)):
-        ref, out = _run_both(oracle_tvl1, gray, epsilon=0.0, iters=iters, warps=warps, nscales=nscales, tile_mask=1 << 8,
-                             stream_chunks=nch, stream_waves=4)
-        assert np.array_equal(out, ref), "max abs diff %g" % np.abs(out - ref).max()
+    # stream_waves = 4 (512-thread workgroups running four strip x chunk x pair jobs each): retired
+    _assert_retired(_frames(nseq, 3, H, W, seed=2 * H + W + nseq), epsilon=0.0, iters=10, warps=1, nscales=1, tile_mask=1 << 8,
+                    stream_chunks=nch, stream_waves=4)
 
 
 @pytest.mark.parametrize("H,W,nch,slots", [(224, 224, 0, 0), (224, 224, 2, 3), (100, 64, 3, 2), (129, 225, 2, 7), (57, 131, 1, 1), (179, 179, 2, 0),
                                            (114, 114, 3, 5)])
 def test_queued_row_pipeline_bit_exact(oracle_tvl1, H, W, nch, slots):
-    _needs_experiments()
-    # stream_queue = 1: k_iter_stream_q runs all passes of a warp step in ONE launch; persistent workgroups pull (pass,
-    # pair, strip, chunk) tasks, a pair's next pass starting when that pair's previous pass is complete (per-pair
-    # counters, agent-scope release / acquire between workgroups).  Few persistent workgroups (1..7: every hand-over is
-    # between different tasks of the same few workgroups) as well as the default; 28 = 16 + 12 and 44 = 16 + 16 + 12
-    # iterations are queued, 20 = 16 + 4 is not (its last pass could not end in the second wave) and takes the
-    # launch-per-pass path; three pairs so that pairs overtake each other
-    gray = _frames(3, 2, H, W, seed=H + 5 * W)
-    for iters, warps, nscales in ((28, 2, 1), (44, 2, 3), (20, 1, 2)):
-        ref, out = _run_both(oracle_tvl1, gray, epsilon=0.0, iters=iters, warps=warps, nscales=nscales, tile_mask=1 << 8,
-                             stream_chunks=nch, stream_queue=1, stream_slots=slots)
-        assert np.array_equal(out, ref), "iters %d: max abs diff %g" % (iters, np.abs(out - ref).max())
-
-
-def test_queued_row_pipeline_full_schedule(oracle_tvl1):
-    _needs_experiments()
-    from video_analytics_amd import flow as vflow
-    gray = _frames(4, 3, 224, 224, seed=5)
-    ref = oracle_tvl1.tvl1_flow(gray.numpy(), oracle_tvl1.default_params(epsilon=0.0), nthreads=8)
-    out = vflow.tvl1_flow(gray.cuda(), epsilon=0.0, stream_queue=1).cpu().numpy()
-    assert np.array_equal(out, ref), "max abs diff %g" % np.abs(out - ref).max()
-
-
-ROWS_SHAPES = [0, 4 * 16 + 4, 2 * 16 + 8, 3 * 16 + 5, 4 * 16 + 3, 8 * 16 + 2, 2 * 16 + 6]
+    # stream_queue = 1 (all passes of a warp step in one launch, persistent workgroups pulling tasks): retired
+    _assert_retired(_frames(3, 2, H, W, seed=H + 5 * W), epsilon=0.0, iters=28, warps=2, nscales=1, tile_mask=1 << 8, stream_chunks=nch,
+                    stream_queue=1, stream_slots=slots)
 
 
 @pytest.mark.parametrize("H,W", [(48, 64), (100, 64), (224, 224), (57, 131), (179, 179), (143, 143), (114, 114), (91, 91),
                                  (33, 130), (24, 16), (129, 225), (200, 256), (40, 190)])
 def test_persistent_row_pipeline_bit_exact(oracle_tvl1, H, W):
-    _needs_experiments()
-    # tile_mask bit 9 forces k_iter_rows (all iterations of a warp step in one launch, passes chained inside the kernel)
-    # on every level it applies to: 2, 3 and 4 pixels per lane (widths up to 128 / 192 / 256), ragged widths with pitch
-    # padding, heights just above and below the minimum for the default shape (levels that do not qualify fall back
-    # to k_iter_stream), iteration counts below one pass (10), with a short first pass (23 = 7 + 16), several full passes
-    # (50 = 2 + 3 x 16) -- bit-identical to the oracle each time
-    gray = _frames(2, 3, H, W, seed=3 * H + W)
-    for iters, warps, nscales in ((10, 1, 1), (23, 2, 3), (50, 1, 2)):
-        ref, out = _run_both(oracle_tvl1, gray, epsilon=0.0, iters=iters, warps=warps, nscales=nscales, tile_mask=1 << 9)
-        assert np.array_equal(out, ref), "iters %d: max abs diff %g" % (iters, np.abs(out - ref).max())
-
-
-@pytest.mark.parametrize("cfg", ROWS_SHAPES)
-@pytest.mark.parametrize("n", [224, 179, 91])
-def test_every_row_pipeline_shape_bit_exact(oracle_tvl1, cfg, n):
-    _needs_experiments()
-    # every compiled waves x levels shape on the benchmark's 4-, 3- and 2-pixel-per-lane levels; 37 iterations = a short
-    # first pass plus full passes for every shape's depth (8 .. 16); also the 1-ulp arithmetic variant against the
-    # register tiles' (the same operations in both kernels)
-    from video_analytics_amd import flow as vflow
-    gray = _frames(3, 2, n, n, seed=n + cfg)
-    ref, out = _run_both(oracle_tvl1, gray, epsilon=0.0, iters=37, warps=2, nscales=1, tile_mask=1 << 9, rows_cfg=cfg)
-    assert np.array_equal(out, ref), "max abs diff %g" % np.abs(out - ref).max()
-    fast = vflow.tvl1_flow(gray.cuda(), epsilon=0.0, iters=37, warps=2, nscales=1, tile_mask=1 << 9, rows_cfg=cfg, fast_math=1)
-    tiles = vflow.tvl1_flow(gray.cuda(), epsilon=0.0, iters=37, warps=2, nscales=1, tile_mask=0xFF, fast_math=1)
-    assert torch.equal(fast, tiles)
-
-
-def test_row_pipeline_full_schedule_and_mixed_levels(oracle_tvl1):
-    _needs_experiments()
-    # the benchmark schedule (5 scales x 5 warps x 300 iterations: 19 chained passes per launch) on the benchmark's
-    # frame size, all levels on k_iter_rows; then mixed with the other two kernels level by level (layouts convert at
-    # the level transitions)
-    from video_analytics_amd import flow as vflow
-    gray = _frames(2, 2, 224, 224, seed=91)
-    ref = oracle_tvl1.tvl1_flow(gray.numpy(), oracle_tvl1.default_params(epsilon=0.0), nthreads=8)
-    out = vflow.tvl1_flow(gray.cuda(), epsilon=0.0, tile_mask=1 << 9).cpu().numpy()
-    assert np.array_equal(out, ref), "max abs diff %g" % np.abs(out - ref).max()
-    ref = oracle_tvl1.tvl1_flow(gray.numpy(), oracle_tvl1.default_params(epsilon=0.0, iters=25, warps=2), nthreads=8)
-    for rows, stream in ((0b10101, 0b01000), (0b01010, 0b00001), (0b11111, 0)):
-        out = vflow.tvl1_flow(gray.cuda(), epsilon=0.0, iters=25, warps=2, rows_levels=rows, stream_levels=stream).cpu().numpy()
-        assert np.array_equal(out, ref), "rows %d stream %d: max abs diff %g" % (rows, stream, np.abs(out - ref).max())
+    # tile_mask bit 9 (the persistent row pipeline: all iterations of a warp step in one launch): retired
+    _assert_retired(_frames(2, 3, H, W, seed=3 * H + W), epsilon=0.0, iters=10, warps=1, nscales=1, tile_mask=1 << 9)
 
 
 @pytest.mark.parametrize("H,W,kw", [(100, 16, dict(rows_levels=0b10)), (120, 20, dict(rows_levels=0b10)),
                                     (100, 16, dict(stream_ppl=3, stream_levels=0b10)), (120, 20, dict(stream_ppl=3, stream_levels=0b110))])
 def test_narrow_tall_frames_with_mixed_level_layouts(oracle_tvl1, H, W, kw):
-    """A coarser level can have the LARGER plane when only it gets the 12-float pitch of k_iter_rows / three pixels per lane
-    (16 x 100: pitch 16, plane 1600 at level 0; 13 x 80 at level 1: pitch 24, plane 1920): the shared state / constants
-    buffers are sized for the largest plane of the pyramid, not for level 0's."""
-    _needs_experiments()
-    gray = _frames(3, 3, H, W, seed=H * W)
-    ref, out = _run_both(oracle_tvl1, gray, epsilon=0.0, iters=23, warps=2, nscales=3, **kw)
-    assert np.array_equal(out, ref), "max abs diff %g" % np.abs(out - ref).max()
+    # per-level choices of the persistent row pipeline / three pixels per lane (the 12-float row pitch): retired
+    _assert_retired(_frames(3, 3, H, W, seed=H * W), epsilon=0.0, iters=23, warps=2, nscales=3, **kw)
 
 
 def test_streaming_kernel_fast_math_and_mixed_levels(oracle_tvl1):

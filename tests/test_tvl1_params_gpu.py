@@ -26,14 +26,8 @@ KERNELS = [dict(), dict(tile_mask=0xFF), dict(tile_mask=STREAM), dict(tile_mask=
 # with the stopping rule every level runs on the register tiles (one iteration per launch): the library's pick and two fixed
 # candidates (128 x 64 with eight waves, 84 x 48 with four)
 EPS_KERNELS = [dict(), dict(tile_mask=1 << 1), dict(tile_mask=1 << 6)]
-# measured-slower families of an EXPERIMENTS=1 library: k_iter_rows, the 3 x 5, 3 x 6 and 4 x 6 row pipelines
-EXPERIMENT_KERNELS = [dict(tile_mask=1 << 9)] + [dict(tile_mask=STREAM, stream_waves=w) for w in (10, 11, 12)]
-
-
-def _needs_experiments():
-    from video_analytics_amd import _ffi
-    if not _ffi.has_experiments():
-        pytest.skip("libva_hip.so built without -DVA_EXPERIMENTS")
+# switches of retired kernel families (the persistent row pipeline, the 3 x 5, 3 x 6 and 4 x 6 row pipelines): refused
+RETIRED_KERNELS = [dict(tile_mask=1 << 9)] + [dict(tile_mask=STREAM, stream_waves=w) for w in (10, 11, 12)]
 
 
 def _frames(n_seq, n_frames, H, W, seed):
@@ -141,12 +135,14 @@ def test_tau_lambda_theta_bit_exact(oracle_tvl1, pset, H, W, step):
 
 @pytest.mark.parametrize("pset", PARAM_SETS, ids=_set_id)
 def test_tau_lambda_theta_experiment_kernels_bit_exact(oracle_tvl1, pset):
-    _needs_experiments()
+    # the kernel families these cases drove were removed: with every parameter set their switches
+    # are refused loudly instead of running another kernel
+    from video_analytics_amd import flow as vflow
     for H, W, step in PARAM_SHAPES:
         gray = _frames(3, 2, H, W, seed=H + W)
-        for iters, warps, nscales in ((23, 2, 3), (44, 1, 2)):
-            kw = dict(epsilon=0.0, iters=iters, warps=warps, nscales=nscales, **_set_kw(pset, step))
-            _check_kernels(_oracle(oracle_tvl1, gray, **kw), gray, EXPERIMENT_KERNELS, **kw)
+        for k in RETIRED_KERNELS:
+            with pytest.raises(ValueError, match="retired"):
+                vflow.tvl1_flow(gray.cuda(), epsilon=0.0, iters=23, warps=2, nscales=3, **_set_kw(pset, step), **k)
 
 
 EPS_SEED = 2

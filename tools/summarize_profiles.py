@@ -27,7 +27,7 @@ def bench_line(path):
 
 
 def kernel_key(name, grid):
-    for pat in ("k_iter_tile", "k_iter_stream", "k_iter_rows"):
+    for pat in ("k_iter_tile", "k_iter_stream"):
         if pat in name:
             return "%s grid=%s" % (pat, grid)
     if "conv3x3" in name:
@@ -89,7 +89,7 @@ def main(prefix, out):
         agg = collections.defaultdict(lambda: collections.defaultdict(float))
         for r in sq:
             n_ = r["Kernel_Name"]
-            name = "k_iter_stream" if "k_iter_stream" in n_ else "k_iter_tile" if "k_iter_tile" in n_ else "k_iter_rows" if "k_iter_rows" in n_ else None
+            name = "k_iter_stream" if "k_iter_stream" in n_ else "k_iter_tile" if "k_iter_tile" in n_ else None
             if name is None:
                 continue
             agg[name][r["Counter_Name"]] += float(r["Counter_Value"])
@@ -100,12 +100,12 @@ def main(prefix, out):
         plan, sizes = vflow.tile_plan(224, 224, p), vflow.pyramid_sizes(224, 224, p)
         pxit = collections.defaultdict(float)
         for lv, (w_, h_) in zip(plan, sizes):
-            kind = "k_iter_tile" if lv["tile_h"] else ("k_iter_rows" if lv["tiles_x"] == 1 and lv["tile_w"] != 128 else "k_iter_stream")
+            kind = "k_iter_tile" if lv["tile_h"] else "k_iter_stream"
             pxit[kind] += 320.0 * w_ * h_ * 1500
         dur = collections.defaultdict(float)
         tr = newest(os.path.join(prefix, "pmc_sq", "*", "*_kernel_trace.csv"))
         for r in (csv.DictReader(open(tr)) if tr else []):
-            for name in ("k_iter_stream", "k_iter_tile", "k_iter_rows"):
+            for name in ("k_iter_stream", "k_iter_tile"):
                 if name in r["Kernel_Name"]:
                     dur[name] += (int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) * 1e-9
         gui = sum(v.get("GRBM_GUI_ACTIVE", 0.0) for v in agg.values())
@@ -133,7 +133,7 @@ def main(prefix, out):
         n_ = r["Kernel_Name"]
         d = int(r["End_Timestamp"]) - int(r["Start_Timestamp"])
         g = "grid=%sx%s" % (r["Grid_Size_X"], r["Grid_Size_Y"])
-        for pat in ("k_iter_tile", "k_iter_stream", "k_iter_rows", "k_conv3x3_dma_f32", "k_conv3x3_mfma", "k_warp", "k_fc_splitk", "k_fc_reduce",
+        for pat in ("k_iter_tile", "k_iter_stream", "k_conv3x3_dma_f32", "k_conv3x3_mfma", "k_warp", "k_fc_splitk", "k_fc_reduce",
                     "k_nchw_to_nhwc_pad", "k_flow_to_stack"):
             if pat in n_:
                 tmpl = n_[n_.index(pat):].split("(")[0]

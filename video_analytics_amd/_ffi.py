@@ -36,11 +36,10 @@ EXPORTS = [
 ]
 
 
-# names of the slots of va_tvl1_params.tuning (csrc/va_internal.h, VA_TUNE_*): the library's own tuning / experiment
+# names of the slots of va_tvl1_params.tuning (csrc/va_internal.h, VA_TUNE_*): the library's own tuning
 # switches, addressed by name from tests and tools (``default_tvl1_params(stream_levels=1)``)
 TUNING_SLOTS = ("stream_levels", "stream_waves", "stream_chunks", "stream_slots", "rows_levels", "stream_ppl",
                 "stream_queue", "rows_cfg")
-VA_VERSION_EXPERIMENTS = 0x10000
 
 
 class Tvl1Params(ctypes.Structure):
@@ -67,12 +66,6 @@ def _tuning_property(i):
 
 for _i, _name in enumerate(TUNING_SLOTS):
     setattr(Tvl1Params, _name, _tuning_property(_i))
-
-
-def has_experiments():
-    """True when libva_hip.so was built with -DVA_EXPERIMENTS (`make -C video_analytics_amd/csrc EXPERIMENTS=1`): the
-    measured-slower kernel families of DESIGN.md section 7 are then compiled in and their tuning values accepted."""
-    return bool(lib().va_version() & VA_VERSION_EXPERIMENTS)
 
 
 _lib = None

@@ -332,32 +332,6 @@ __device__ __forceinline__ float dpp_from_right(float v)  // lane i <- lane i+1,
 }
 
 typedef float f2 __attribute__((ext_vector_type(2)));
-#ifndef VA_REV
-#define VA_REV 1
-#endif
-#ifndef VA_STREAM_QUEUE_DEFAULT
-#define VA_STREAM_QUEUE_DEFAULT 0  // 1: k_iter_stream_q (all passes of a warp step in one launch) wherever it applies
-#endif
-#ifndef VA_STREAM4_DEFAULT
-#define VA_STREAM4_DEFAULT 0  // 1: four jobs per 512-thread workgroup (k_iter_stream4) wherever the two-wave pipeline runs
-#endif
-#ifndef VA_STREAM_UNROLL2
-#define VA_STREAM_UNROLL2 1  // measured on the 224^2 level: 9.8 -> 9.3 ms per warp step of 320 pairs
-#endif
-#ifndef VA_CHUNK
-#define VA_CHUNK 1
-#endif
-// TIMING BUILDS ONLY (wrong results; never set in a product build): bit set of parts of k_iter_stream's steady steps to
-// leave out, for the stall accounting of profiles/README.md (round 3): 1 = the global stores of the last wave, 2 = the
-// global loads of the first wave (the rows loaded before the loop are reused), 4 = the hand-over rows (no if_put / if_get),
-// 8 = the ring reads (the first row's constants are reused), 16 = the sched_barriers, 32 = the ring writes
-#ifndef VA_TIMING_SKIP
-#define VA_TIMING_SKIP 0
-#endif
-#ifndef VA_CHUNK_MB
-#define VA_CHUNK_MB 150.0
-#endif
-
 __device__ __forceinline__ f2 pk_fma(f2 a, f2 b, f2 c) { return __builtin_elementwise_fma(a, b, c); }  // v_pk_fma_f32
 // a - b as one v_sub_f32 the vectoriser cannot re-pack (see the x differences in k_iter_tile)
 __device__ __forceinline__ float sub_s(float a, float b)
@@ -482,8 +456,7 @@ __global__ void __launch_bounds__(NW * 64) k_iter_tile(IterArgs a)
     const float* __restrict__ sin = (inbuf ? a.stB : a.stA) + (size_t)pair * kNF_STATE * a.plane;
     float* __restrict__ sout = (inbuf ? a.outA : a.outB) + (size_t)pair * kNF_STATE * a.plane;
 
-    // columns a run may touch: up to the last 4-pixel run holding a valid pixel.  The row pitch can be larger (a level
-    // laid out for k_iter_rows): those columns are never read or written here (what they hold is arbitrary).
+    // columns a run may touch: up to the last 4-pixel run holding a valid pixel
     const int xlim = (w + 3) & ~3;
     f2 u1[C][RP], u2[C][RP], p11[C][RP], p12[C][RP], p21[C][RP], p22[C][RP];
     f2 wx[C][RP], wy[C][RP], rc[C][RP], ig[C][RP];
@@ -680,9 +653,9 @@ __global__ void __launch_bounds__(NW * 64) k_iter_tile(IterArgs a)
 }
 
 // ---------------------------------------------------------------- rows of N pixels per lane ---
-// A lane's N consecutive pixels of one field (N = 2, 3, 4) as N/2 packed pairs + a scalar tail: the arithmetic of the
-// row pipelines (k_iter_stream, k_iter_rows) is written once over these; pairs issue as v_pk_*_f32, the tail as plain
-// VALU -- element by element the same IEEE operations, so results do not depend on N.
+// A lane's N consecutive pixels of one field as N/2 packed pairs + a scalar tail: the arithmetic of the row pipeline
+// (k_iter_stream, N = 2) is written once over these; pairs issue as v_pk_*_f32, the tail as plain VALU -- element by
+// element the same IEEE operations, so results do not depend on N.
 template <int N>
 struct Row {
     static constexpr int NP = N / 2, NT = N & 1;
@@ -804,16 +777,6 @@ template <> struct RowIo<2> {
     static __device__ __forceinline__ V ld(__amdgpu_buffer_rsrc_t r, int vo, int so) { return __builtin_amdgcn_raw_buffer_load_b64(r, vo, so, 0); }
     static __device__ __forceinline__ void st(V v, __amdgpu_buffer_rsrc_t r, int vo, int so) { __builtin_amdgcn_raw_buffer_store_b64(v, r, vo, so, 0); }
 };
-template <> struct RowIo<3> {
-    typedef unsigned V __attribute__((ext_vector_type(3)));
-    static __device__ __forceinline__ V ld(__amdgpu_buffer_rsrc_t r, int vo, int so) { return __builtin_amdgcn_raw_buffer_load_b96(r, vo, so, 0); }
-    static __device__ __forceinline__ void st(V v, __amdgpu_buffer_rsrc_t r, int vo, int so) { __builtin_amdgcn_raw_buffer_store_b96(v, r, vo, so, 0); }
-};
-template <> struct RowIo<4> {
-    typedef unsigned V __attribute__((ext_vector_type(4)));
-    static __device__ __forceinline__ V ld(__amdgpu_buffer_rsrc_t r, int vo, int so) { return __builtin_amdgcn_raw_buffer_load_b128(r, vo, so, 0); }
-    static __device__ __forceinline__ void st(V v, __amdgpu_buffer_rsrc_t r, int vo, int so) { __builtin_amdgcn_raw_buffer_store_b128(v, r, vo, so, 0); }
-};
 template <int N>
 __device__ __forceinline__ Row<N> row_load(__amdgpu_buffer_rsrc_t r, int vo, int so)
 {
@@ -867,21 +830,15 @@ struct StreamArgs {
 // KH-1 out of a double-buffered LDS row instead of HBM and carries them through levels KH .. 2KH-1, so that one pass
 // over the strip is worth K <= 2 KH iterations of HBM traffic; both waves share the ring of per-warp constants; one
 // workgroup barrier per step keeps them a step apart.
-// NCH chains per wave (round 3): the KH levels of a wave are cut into NCH chains of KC = KH / NCH consecutive levels.
-// Inside a chain level t + 1 consumes what level t emits in the SAME step (one long dependent sequence of ~16 operations
-// per level); from one chain to the next the row waits in registers for one step (a latch, 6 x PPL registers), exactly
-// like the hand-over between the two waves but inside one.  The chains of a step are therefore independent of each
-// other and are issued interleaved, level by level: the exact square-root / reciprocal sequences and the s_nop hazard
-// slots of one chain are covered by the other's arithmetic (tools/microbench_tvl1_chain.hip: 125 instead of 147 ns per
-// level-row on the bare arithmetic).  Every chain end costs one step of pipeline depth: global level g works at
-// pipeline position pos(g) = g + (chain ends before g), i.e. on row s - pos(g) of the strip at step s.
-// PPL pixels per lane: a strip is 64 * PPL columns wide (2: 128, the default; 3: 192, so that a 129..192-column level is
-// ONE well-filled strip without any x halo -- a tested option that measured no faster, see stream_ppl()).
-// SUBS = 4 (k_iter_stream4): a 512-thread workgroup runs FOUR jobs, job `sub` on the waves sub (first wave) and sub + 4
-// (second wave) -- the dispatcher puts waves w and w + 4 of a workgroup on the same SIMD, so the two waves of a pipeline
-// share one: while one of them waits for the other, the other has the SIMD to itself.  All eight waves meet at every
-// barrier, so every job of the workgroup runs `steps_pad` steps (a job with fewer only joins the barrier); `active` =
-// false: a padding job.
+// PPL pixels per lane: a strip is 64 * PPL columns wide.  Only PPL = 2 (128 columns) is instantiated.
+// NCH chains per wave: the KH levels of a wave cut into NCH chains of KC = KH / NCH consecutive levels; inside a chain
+// level t + 1 consumes what level t emits in the SAME step, from one chain to the next the row waits in registers for one
+// step (a latch), so that every chain end costs one step of pipeline depth: global level g works at pipeline position
+// pos(g) = g + (chain ends before g).  Only NCH = 1 is instantiated (one chain: no latch, pos(g) = g + waves before g).
+// SUBS jobs per workgroup (`sub`, `role`, `active`, `steps_pad`): only SUBS = 1 with the default arguments is instantiated.
+// These parameters served kernel forms that measured slower and were removed.  They stay in
+// stream_job because the surviving kernels are held to the machine code they had before the removal, and taking even
+// the constant arguments out changes what the compiler emits for all ten k_iter_stream instantiations.
 template <int KH, int NCH>
 struct StreamShape {
     static_assert(KH % NCH == 0, "the levels of a wave are cut into chains of equal length");
@@ -1093,31 +1050,24 @@ __device__ __forceinline__ void stream_job(const StreamArgs& a, const int pair, 
                 // next row (beyond the last row of the strip: row ye - 1 again -- finite values nobody uses, or, at the
                 // image bottom, the dummy row h whose only consumer multiplies its difference by my = 0)
                 const int rn = d_min(ys + s + 1, ye - 1);
-                if (!(STEADY && (VA_TIMING_SKIP & 2))) {
 #pragma clang loop unroll(full)
-                    for (int f = 0; f < kNF_STATE; ++f) nst[f] = ld(rs_in, f, rn);
+                for (int f = 0; f < kNF_STATE; ++f) nst[f] = ld(rs_in, f, rn);
 #pragma clang loop unroll(full)
-                    for (int f = 0; f < kNF_RO; ++f) nro[f] = ld_ro(f, rn);
-                }
+                for (int f = 0; f < kNF_RO; ++f) nro[f] = ld_ro(f, rn);
                 if constexpr (NWV > 1) {  // the constants of row s - 1 go into the ring now that the barrier has passed
                     const int sl = s0 == 0 ? NRING - 1 : s0 - 1;
-                    if (!(STEADY && (VA_TIMING_SKIP & 32)))
 #pragma clang loop unroll(full)
-                        for (int f = 0; f < kNF_RO; ++f) ring_put(sl, f, rprev[f]);
+                    for (int f = 0; f < kNF_RO; ++f) ring_put(sl, f, rprev[f]);
                 }
-                if (!(VA_TIMING_SKIP & 16)) __builtin_amdgcn_sched_barrier(0);  // the loads stay at the top of the step: a whole step hides their latency
+                __builtin_amdgcn_sched_barrier(0);  // the loads stay at the top of the step: a whole step hides their latency
             } else {
                 const int bsel = (s + 1) & 1;  // what the wave before wrote in step s - 1
-                if (STEADY && (VA_TIMING_SKIP & 4)) {
-                    cc[0] = SR{U1[0], U2[0], P11[0], P12[0], P21[0], P22[0]};
-                } else {
-                    cc[0].u1 = if_get(W - 1, bsel, 0);
-                    cc[0].u2 = if_get(W - 1, bsel, 1);
-                    cc[0].p11 = if_get(W - 1, bsel, 2);
-                    cc[0].p12 = if_get(W - 1, bsel, 3);
-                    cc[0].p21 = if_get(W - 1, bsel, 4);
-                    cc[0].p22 = if_get(W - 1, bsel, 5);
-                }
+                cc[0].u1 = if_get(W - 1, bsel, 0);
+                cc[0].u2 = if_get(W - 1, bsel, 1);
+                cc[0].p11 = if_get(W - 1, bsel, 2);
+                cc[0].p12 = if_get(W - 1, bsel, 3);
+                cc[0].p21 = if_get(W - 1, bsel, 4);
+                cc[0].p22 = if_get(W - 1, bsel, 5);
             }
 #pragma clang loop unroll(full)
             for (int c = 1; c < NCH; ++c) cc[c] = latch[c - 1];
@@ -1136,9 +1086,6 @@ __device__ __forceinline__ void stream_job(const StreamArgs& a, const int pair, 
                     if (FIRST && c == 0) {
 #pragma clang loop unroll(full)
                         for (int f = 0; f < kNF_RO; ++f) q[c][f] = r0[f];
-                    } else if (VA_TIMING_SKIP & 8) {
-#pragma clang loop unroll(full)
-                        for (int f = 0; f < kNF_RO; ++f) q[c][f] = rprev[f];
                     } else {
                         const int slot = slot_of(c * KC);
 #pragma clang loop unroll(full)
@@ -1161,10 +1108,10 @@ __device__ __forceinline__ void stream_job(const StreamArgs& a, const int pair, 
                             } else {
                                 const int slot = slot_of(c * KC + i + 1);
 #pragma clang loop unroll(full)
-                                for (int f = 0; f < kNF_RO; ++f) nq[c][f] = (VA_TIMING_SKIP & 8) ? q[c][f] : ring_get(slot, f);
+                                for (int f = 0; f < kNF_RO; ++f) nq[c][f] = ring_get(slot, f);
                             }
                         }
-                        if (!(VA_TIMING_SKIP & 16)) __builtin_amdgcn_sched_barrier(0);
+                        __builtin_amdgcn_sched_barrier(0);
                     }
                     if (KEEP && i == KH - 2) {
 #pragma clang loop unroll(full)
@@ -1209,7 +1156,7 @@ __device__ __forceinline__ void stream_job(const StreamArgs& a, const int pair, 
             if constexpr (LAST) {
                 // the row that leaves the pipeline in this step: K iterations on, one step later per chain end on its way
                 const int rout = ys + s - K - (NWV * NCH - 1);
-                if (stok && rout >= a0 && rout < b0 && !(STEADY && (VA_TIMING_SKIP & 1))) {
+                if (stok && rout >= a0 && rout < b0) {
                     st(co.u1, 0, rout);
                     st(co.u2, 1, rout);
                     st(co.p11, 2, rout);
@@ -1219,14 +1166,12 @@ __device__ __forceinline__ void stream_job(const StreamArgs& a, const int pair, 
                 }
             } else {
                 const int bsel = s & 1;
-                if (!(STEADY && (VA_TIMING_SKIP & 4))) {
-                    if_put(W, bsel, 0, co.u1);
-                    if_put(W, bsel, 1, co.u2);
-                    if_put(W, bsel, 2, co.p11);
-                    if_put(W, bsel, 3, co.p12);
-                    if_put(W, bsel, 4, co.p21);
-                    if_put(W, bsel, 5, co.p22);
-                }
+                if_put(W, bsel, 0, co.u1);
+                if_put(W, bsel, 1, co.u2);
+                if_put(W, bsel, 2, co.p11);
+                if_put(W, bsel, 3, co.p12);
+                if_put(W, bsel, 4, co.p21);
+                if_put(W, bsel, 5, co.p22);
             }
             if constexpr (FIRST) {
                 if constexpr (NWV == 1) {
@@ -1252,17 +1197,15 @@ __device__ __forceinline__ void stream_job(const StreamArgs& a, const int pair, 
         if (K < G0 + KH || s_a > s_b || !active) s_a = s_b = 0;
         int s = 0;
         for (; s < s_a; ++s) step(s, std::false_type{});
-#if VA_STREAM_UNROLL2
         // two steady steps per loop trip: the rows a level hands on and keeps (c_* -> P[t], n -> U[t]) change registers
-        // by renaming between the two copies instead of by v_mov (5 per level and step otherwise).  Not in the one-wave
-        // form at two waves per SIMD: with ten levels in one wave's 256 registers the second copy spills (19-21 registers;
-        // 1280x720: 62 instead of 114 pairs/s)
-        if constexpr (NWV > 1 || KH > 10)
+        // by renaming between the two copies instead of by v_mov (5 per level and step otherwise; measured on the 224^2
+        // level: 9.8 -> 9.3 ms per warp step of 320 pairs).  Not in the one-wave form: with ten levels in one wave's 256
+        // registers the second copy spills (19-21 registers; 1280x720: 62 instead of 114 pairs/s)
+        if constexpr (NWV > 1)
             for (; s + 1 < s_b; s += 2) {
                 step(s, std::true_type{});
                 step(s + 1, std::true_type{});
             }
-#endif
         for (; s < s_b; ++s) step(s, std::true_type{});
         for (; s < nsteps; ++s) step(s, std::false_type{});
         if constexpr (SUBS > 1)  // the other jobs of the workgroup may have more steps: join their barriers
@@ -1289,7 +1232,7 @@ __device__ __forceinline__ void stream_job(const StreamArgs& a, const int pair, 
 // One launch = one pass (a.K iterations) of every pair of the call: the grid is (strips x chunks, pairs).
 template <int PPL, int KH, int NWV, bool FAST, int NCH = 1>
 __global__ void __launch_bounds__(NWV * 64)
-    __attribute__((amdgpu_waves_per_eu((NWV == 1 && KH > 10) ? 1 : 2, (NWV == 1 && KH > 10) ? 1 : NWV >= 3 ? 4 : 2)))
+    __attribute__((amdgpu_waves_per_eu(2, NWV >= 3 ? 4 : 2)))
     k_iter_stream(StreamArgs a)
 {
     unsigned lid = blockIdx.y * gridDim.x + blockIdx.x;
@@ -1314,10 +1257,6 @@ __global__ void __launch_bounds__(NWV * 64)
     }
     stream_job<PPL, KH, NWV, FAST, 1, NCH>(a, a.pair0 + first + which, ch * a.nsx + sx, a.K, a.sin, a.sout, 0, -1, true, 0, half);
 }
-
-#ifdef VA_EXPERIMENTS  // measured-slower kernel families: k_iter_stream4, k_iter_stream_q, k_iter_rows
-#include "tvl1_experiments.inc"
-#endif  // VA_EXPERIMENTS
 
 // ---------------------------------------------------------------- host side -------------------
 
@@ -1430,48 +1369,26 @@ void launch_iter(const TilePick& tp, const IterArgs& a, int npairs, hipStream_t 
 }
 
 // ---- k_iter_stream: strips x chunks of a level
-constexpr int kStreamK1 = 10;       // one-wave pipeline: iterations per pass (2 pixels per lane)
-constexpr int kStreamKH2 = 8;       // two-wave pipeline: levels per wave (16 iterations per pass; 2 pixels per lane)
-static_assert(kStreamKH2 == 8, "k_iter_stream4 instantiates stream_job<2, 8, 2>");
-// A level keeps 6 x PPL registers per lane: with 3 pixels per lane the pipelines are shallower (5 levels per wave), so
-// that two waves per SIMD still fit the register file (8 and 6 levels spill, seen at compile time and in the timings)
-constexpr int stream_k1(int ppl) { return ppl == 2 ? kStreamK1 : 5; }
-constexpr int stream_kh2(int ppl) { return ppl == 2 ? kStreamKH2 : 5; }
+constexpr int kStreamSW = 128;      // columns of a strip: 64 lanes x 2 pixels
+constexpr int kStreamK1 = 10;       // one-wave pipeline: iterations per pass
+constexpr int kStreamKH2 = 8;       // two-wave pipeline: levels per wave (16 iterations per pass)
 constexpr int kStreamBit = 1 << 8;  // va_tvl1_params.tile_mask bit: iterate with k_iter_stream
+constexpr int kRetiredRowsBit = 1 << 9;  // va_tvl1_params.tile_mask bit of a retired kernel family: refused (check_params)
 constexpr int kNoNarrowBit = 1 << 10;  // va_tvl1_params.tile_mask bit: no shared last strips (StreamArgs.narrow) -- A/B and tests
 struct StreamPick {
-    int nsx, nch, R, HX, two, ppl, deep1;
-    int chains;  // chains of levels per wave (stream_job, NCH): 1, or 2 with stream_waves = 5 (one deep wave) / 6 (two waves)
-    int mw_nwv, mw_kh;  // > 0: the pipeline of mw_nwv waves x mw_kh levels (3 or 4 waves; stream_waves >= 7)
+    int nsx, nch, R, HX, two;
+    int mw_nwv, mw_kh;  // > 0: the pipeline of four waves x mw_kh levels
     int narrow;         // the last strip of a row fits 32 lanes: two pairs' last strips share a wave (StreamArgs.narrow)
 };
-// stream_waves >= 7: pipelines of three or four waves (waves x levels per wave)
-constexpr int kMwShapes[][2] = {{4, 4}, {4, 5}, {4, 3}, {3, 5}, {3, 6}, {4, 6}};  // 7, 8, 9: compiled always; 10 ... 12: VA_EXPERIMENTS
+// stream_waves 7, 8, 9: pipelines of four waves (waves x levels per wave)
+constexpr int kMwShapes[][2] = {{4, 4}, {4, 5}, {4, 3}};
 constexpr int kNumMwShapes = (int)(sizeof(kMwShapes) / sizeof(kMwShapes[0]));
 constexpr int kMwFirst = 7;
-// Pixels per lane of k_iter_stream: 2 (128-column strips) unless va_tvl1_params.stream_ppl asks for 3 (192-column
-// strips: a 129..192-column level then is ONE strip without x halo -- 179^2 fills 93 % of the lanes instead of 70 % of
-// two 128-column strips).  Measured on the benchmark's 179^2 / 143^2 levels (320 pairs, two streams): 33.6 / 25.6 ms
-// with 3 per lane (best of 5 or 4 levels per wave and 2..4 chunks of rows) against 32.9 / 25.5 ms with 2: the better
-// fill is paid back by the shallower pipeline (6 x 3 registers per level: 10 instead of 16 iterations per pass) and by
-// half as many strip x chunk jobs.  So 2 stays the default; 3 is kept as a tested option.
-int stream_ppl(const va_tvl1_params* p, int w)
-{
-    (void)w;
-    return p->tuning[VA_TUNE_STREAM_PPL] == 3 ? 3 : 2;
-}
 template <bool TWO, bool FAST>
-void launch_stream(int ppl, dim3 grid, hipStream_t st, const StreamArgs& sa)
+void launch_stream(dim3 grid, hipStream_t st, const StreamArgs& sa)
 {
     constexpr int NWV = TWO ? 2 : 1;
-#ifdef VA_EXPERIMENTS
-    if (ppl == 3) {
-        k_iter_stream<3, TWO ? stream_kh2(3) : stream_k1(3), NWV, FAST><<<grid, NWV * 64, 0, st>>>(sa);
-        return;
-    }
-#endif
-    (void)ppl;
-    k_iter_stream<2, TWO ? stream_kh2(2) : stream_k1(2), NWV, FAST><<<grid, NWV * 64, 0, st>>>(sa);
+    k_iter_stream<2, TWO ? kStreamKH2 : kStreamK1, NWV, FAST><<<grid, NWV * 64, 0, st>>>(sa);
 }
 template <int NWV, int KH>
 void launch_stream_mw1(bool fast, dim3 grid, hipStream_t st, const StreamArgs& sa)
@@ -1479,17 +1396,10 @@ void launch_stream_mw1(bool fast, dim3 grid, hipStream_t st, const StreamArgs& s
     if (fast) k_iter_stream<2, KH, NWV, true><<<grid, NWV * 64, 0, st>>>(sa);
     else k_iter_stream<2, KH, NWV, false><<<grid, NWV * 64, 0, st>>>(sa);
 }
-void launch_stream_mw(int nwv, int kh, bool fast, dim3 grid, hipStream_t st, const StreamArgs& sa)
+void launch_stream_mw(int kh, bool fast, dim3 grid, hipStream_t st, const StreamArgs& sa)
 {
-    if (nwv == 4 && kh == 5) return launch_stream_mw1<4, 5>(fast, grid, st, sa);
-    if (nwv == 4 && kh == 3) return launch_stream_mw1<4, 3>(fast, grid, st, sa);
-#ifdef VA_EXPERIMENTS
-    if (nwv == 3 && kh == 5) return launch_stream_mw1<3, 5>(fast, grid, st, sa);
-    if (nwv == 3 && kh == 6) return launch_stream_mw1<3, 6>(fast, grid, st, sa);
-    if (nwv == 4 && kh == 6) return launch_stream_mw1<4, 6>(fast, grid, st, sa);
-#endif
-    (void)nwv;
-    (void)kh;
+    if (kh == 5) return launch_stream_mw1<4, 5>(fast, grid, st, sa);
+    if (kh == 3) return launch_stream_mw1<4, 3>(fast, grid, st, sa);
     launch_stream_mw1<4, 4>(fast, grid, st, sa);
 }
 // Strips of a level and the shape of the pipeline that carries them (see the comment on the four-wave forms below).  The
@@ -1498,17 +1408,12 @@ void launch_stream_mw(int nwv, int kh, bool fast, dim3 grid, hipStream_t st, con
 // (halo 10) on wider levels.  va_tvl1_params.stream_waves = 1: one wave everywhere; 2: these two.
 void stream_strips(const va_tvl1_params* p, int w, StreamPick& sp)
 {
-    sp.ppl = stream_ppl(p, w);
-    const int SW = 64 * sp.ppl, hq = sp.ppl == 3 ? 3 : 2;  // strip origins stay multiples of the pixels per lane
-    sp.two = p->tuning[VA_TUNE_STREAM_WAVES] != 1 && tiles_1d(w, SW, va_cdiv(2 * stream_kh2(sp.ppl), hq) * hq) <= 2;
-    // stream_waves == 3 (experiment): where the two-wave pipeline would run, ONE wave with all 16 levels and the whole
-    // register file of its SIMD (no hand-over, no barrier)
-    sp.deep1 = sp.two && (p->tuning[VA_TUNE_STREAM_WAVES] == 3 || p->tuning[VA_TUNE_STREAM_WAVES] == 5) && sp.ppl == 2;
-    sp.chains = sp.two && sp.ppl == 2 && (p->tuning[VA_TUNE_STREAM_WAVES] == 5 || p->tuning[VA_TUNE_STREAM_WAVES] == 6) ? 2 : 1;
+    constexpr int SW = kStreamSW;
+    sp.two = p->tuning[VA_TUNE_STREAM_WAVES] != 1 && tiles_1d(w, SW, 2 * kStreamKH2) <= 2;
     // (Also measured, round 2, and removed again: THREE waves of 4 / 5 levels each -- 12 / 15 iterations per pass at 144 /
     // 168 registers, i.e. three resident waves per SIMD instead of two: 45.2 / 43.9 ms on the 224^2 level and 35.3 / 34.8
     // on 179^2 against 41.6 / 32.9 for the two-wave form: more resident waves do not fill the idle issue slots.)
-    sp.HX = va_cdiv(sp.two ? 2 * stream_kh2(sp.ppl) : stream_k1(sp.ppl), hq) * hq;
+    sp.HX = sp.two ? 2 * kStreamKH2 : kStreamK1;  // (even: strip origins stay multiples of the two pixels per lane)
     sp.nsx = tiles_1d(w, SW, sp.HX);
     // Pipelines of FOUR waves (round 3): 4 x 4 levels (16 iterations per pass, 143 registers: three waves per SIMD) or, where
     // a 20-column halo still costs no third strip, 4 x 5 levels (20 per pass, 167 registers).  Measured per level on the
@@ -1519,12 +1424,12 @@ void stream_strips(const va_tvl1_params* p, int w, StreamPick& sp)
     // Levels with more than two strips (the 1280x720 pyramid): 4 x 3 levels (12 per pass, halo 12, 119 registers: four waves
     // per SIMD, three workgroups per CU) -- 138 against 118 pairs/s for the one-wave form with 10 per pass (16 pairs).
     // stream_waves: 0 = this choice, 2 = two waves where they fit (rounds 1-2), 1 = one wave everywhere, 7 / 8 / 9 = 4 x 4 /
-    // 4 x 5 / 4 x 3 wherever a strip keeps valid columns, (VA_EXPERIMENTS) 10 ... 12 = 3 x 5, 3 x 6, 4 x 6.
+    // 4 x 5 / 4 x 3 wherever a strip keeps valid columns.
     const int sw = p->tuning[VA_TUNE_STREAM_WAVES];
     int shape = -1;
     if (sw >= kMwFirst && sw < kMwFirst + kNumMwShapes) shape = sw - kMwFirst;
     else if (sw == 0) shape = !sp.two ? 2 : (w > SW && tiles_1d(w, SW, 20) <= 2) ? 1 : 0;
-    if (shape >= 0 && sp.ppl == 2) {
+    if (shape >= 0) {
         const int nwv = kMwShapes[shape][0], kh = kMwShapes[shape][1], hx = va_cdiv(nwv * kh, 2) * 2;
         // the default choice: like the two-wave form only where the deeper x halo costs no third strip; an explicit
         // stream_waves >= 7 takes the shape wherever a strip keeps valid columns
@@ -1568,147 +1473,49 @@ bool level_streams(const va_tvl1_params* p, bool eps, int s, int w, int h, size_
     if (p->tile_mask & kStreamBit) return true;
     if ((p->tile_mask & ~kNoNarrowBit) != 0) return false;
     if (p->tuning[VA_TUNE_STREAM_LEVELS] >= 0) return ((p->tuning[VA_TUNE_STREAM_LEVELS] >> s) & 1) != 0;
+    if (p->tuning[VA_TUNE_ROWS_LEVELS] >= 0) return false;  // the reserved slot's 0 has always meant "explicit choice": tiles
     StreamPick sp{};
     stream_strips(p, w, sp);
     // measured per level of the 224x224 pyramid (320 pairs, two streams; profiles/README.md): the row pipeline wins on 224^2
     // (two strips 88 % full), 179^2 (70 %) and 114^2 (one strip, 89 %), the register tiles on 143^2 (56 %) and 91^2 (71 %
     // of one strip, too few jobs); every level of the 1280x720 pyramid (80..85 %) streams
     // (round 3: with the last strips of two pairs sharing a wave 143^2 fills 74 % of 1.5 strips: 18.9 ms against 21.6 on tiles)
-    const double fill = (double)w / (64.0 * sp.ppl * (sp.nsx - (sp.narrow ? 0.5 : 0.0))), px = (double)w * h;
+    const double fill = (double)w / ((double)kStreamSW * (sp.nsx - (sp.narrow ? 0.5 : 0.0))), px = (double)w * h;
     return (fill >= 0.85 && px >= 10000.0) || (fill >= 0.69 && px >= 20000.0);
 }
-
-// ---- k_iter_rows: which levels, which pipeline shape
-constexpr int kRowsBit = 1 << 9;  // va_tvl1_params.tile_mask bit: iterate with k_iter_rows wherever it applies
-struct RowsPick {
-    int ppl, nwv, kh, K, K0, N;
-};
-#ifdef VA_EXPERIMENTS
-// pipeline shapes compiled in (waves x levels per wave); rows_cfg = waves * 16 + levels per wave, 0 = the default
-constexpr int kRowsShapes[][2] = {{4, 4}, {2, 8}, {3, 5}, {4, 3}, {8, 2}, {2, 6}};
-constexpr int kNumRowsShapes = (int)(sizeof(kRowsShapes) / sizeof(kRowsShapes[0]));
-// LDS of one k_iter_rows workgroup: the ring of per-warp constants (K + NWV rows) + the double-buffered hand-over rows
-constexpr int rows_lds_bytes(int ppl, int nwv, int kh)
-{
-    return (nwv * kh + nwv) * kNF_RO * ppl * 256 + (nwv > 1 ? nwv - 1 : 1) * 2 * (kNF_STATE * ppl * 256 + 4);
-}
-constexpr int kRowsLdsMax = 160 * 1024 - 512;
-#endif
-bool pick_rows(const va_tvl1_params* p, int h, int pitch, RowsPick& rp)
-{
-#ifndef VA_EXPERIMENTS
-    (void)p, (void)h, (void)pitch, (void)rp;
-    return false;  // k_iter_rows is not compiled in
-#else
-    int nwv = kRowsShapes[0][0], kh = kRowsShapes[0][1];
-    if (p->tuning[VA_TUNE_ROWS_CFG] > 0) {
-        nwv = p->tuning[VA_TUNE_ROWS_CFG] >> 4;
-        kh = p->tuning[VA_TUNE_ROWS_CFG] & 15;
-    }
-    bool known = false;
-    for (int i = 0; i < kNumRowsShapes; ++i) known = known || (kRowsShapes[i][0] == nwv && kRowsShapes[i][1] == kh);
-    if (!known) return false;
-    rp.ppl = pitch <= 128 ? 2 : pitch <= 192 ? 3 : 4;
-    if (pitch > 256) return false;
-    rp.nwv = nwv;
-    rp.kh = kh;
-    if (rows_lds_bytes(rp.ppl, nwv, kh) > kRowsLdsMax) return false;
-    const int Kfull = nwv * kh;
-    rp.K = p->iters < Kfull ? p->iters : Kfull;
-    rp.N = va_cdiv(p->iters, rp.K);
-    rp.K0 = p->iters - (rp.N - 1) * rp.K;
-    if (rp.N >= 2047 || pitch % rp.ppl != 0) return false;  // the pass index must fit the row identity; whole lanes per row
-    // pass n + 1 reads a row back at least two steps after pass n stored it
-    return h >= Kfull + nwv + 4 && h < (1 << kRowIdRowBits);
-#endif
-}
-
-enum { LK_TILE = 0, LK_STREAM = 1, LK_ROWS = 2 };
-bool level_streams(const va_tvl1_params* p, bool eps, int s, int w, int h, size_t plane);
-// Which kernel iterates level s.  Explicit choices first (tests, experiments), then the measured default.
-int level_kernel(const va_tvl1_params* p, bool eps, int s, int w, int h, int pitch, size_t plane, RowsPick* rp)
-{
-    RowsPick tmp{};
-    if (!rp) rp = &tmp;
-    if (eps || (double)plane * kNF_STATE * sizeof(float) >= 2147483648.0) return LK_TILE;
-    const bool rows_ok = pick_rows(p, h, pitch, *rp);
-    if (p->tile_mask & kRowsBit) return rows_ok ? LK_ROWS : LK_STREAM;
-    if ((p->tile_mask & ~kNoNarrowBit) != 0) return level_streams(p, eps, s, w, h, plane) ? LK_STREAM : LK_TILE;
-    if (p->tuning[VA_TUNE_ROWS_LEVELS] >= 0 || p->tuning[VA_TUNE_STREAM_LEVELS] >= 0) {
-        if (p->tuning[VA_TUNE_ROWS_LEVELS] >= 0 && ((p->tuning[VA_TUNE_ROWS_LEVELS] >> s) & 1) && rows_ok) return LK_ROWS;
-        return p->tuning[VA_TUNE_STREAM_LEVELS] >= 0 && ((p->tuning[VA_TUNE_STREAM_LEVELS] >> s) & 1) ? LK_STREAM : LK_TILE;
-    }
-    return level_streams(p, eps, s, w, h, plane) ? LK_STREAM : LK_TILE;
-}
-
-#ifdef VA_EXPERIMENTS
-template <int PPL, bool FAST>
-int launch_rows(const RowsPick& rp, const RowsArgs& a, int npairs, hipStream_t st)
-{
-#define VA_ROWS_CASE(NWV_, KH_)                                                           \
-    if constexpr (rows_lds_bytes(PPL, NWV_, KH_) <= kRowsLdsMax) {                        \
-        if (rp.nwv == NWV_ && rp.kh == KH_) {                                             \
-            k_iter_rows<PPL, KH_, NWV_, FAST><<<npairs, NWV_ * 64, 0, st>>>(a);           \
-            return VA_OK;                                                                 \
-        }                                                                                 \
-    }
-    VA_ROWS_CASE(4, 4)
-    VA_ROWS_CASE(2, 8)
-    VA_ROWS_CASE(3, 5)
-    VA_ROWS_CASE(4, 3)
-    VA_ROWS_CASE(8, 2)
-    VA_ROWS_CASE(2, 6)
-#undef VA_ROWS_CASE
-    va_set_error("va_tvl1_flow: row pipeline shape %dx%d is not compiled in", rp.nwv, rp.kh);
-    return VA_ERR_INVALID;
-}
-#endif
 
 // Pairs per chunk of a level: the iteration launches of a chunk re-read what the previous launch wrote, so a chunk
 // whose state (64 B per pixel) stays within ~150 MB (70, 110, 200 MB measured slower) is served largely by the Infinity Cache (measured on the 179^2
 // and 143^2 levels of the benchmark: -4 % each).  No chunking where a chunk could not fill the GPU.
+constexpr double kChunkMB = 150.0;
 int chunk_pairs(int lw, int lh, const TilePick& tp, int NP)
 {
     const int tiles = tp.ntx * tp.nty;
     const bool w8 = kCfgs[tp.cfg].NW == 8;
     const int cp_min = (int)std::ceil((w8 ? 2.0 * 256 : 1.25 * 512) / tiles);
-    const int cp_mem = (int)(VA_CHUNK_MB * 1.0e6 / ((double)lw * lh * 64.0));
+    const int cp_mem = (int)(kChunkMB * 1.0e6 / ((double)lw * lh * 64.0));
     if (cp_mem < cp_min || cp_mem >= NP) return NP;
     const int n = va_cdiv(NP, cp_mem);
     return va_cdiv(NP, n);
 }
 
-// Row pitch in floats: the width rounded up to 4 (rows start 16-byte aligned: k_iter_tile's 4-pixel runs); a level that
-// k_iter_rows iterates gets a multiple of 12 instead, so that a lane's 2, 3 or 4 consecutive pixels never straddle the
-// end of a row.
-int level_pitch(int w, bool rows) { return rows ? (w + 11) / 12 * 12 : (w + 3) / 4 * 4; }
-// kernel and layout of level s: decided once, on the k_iter_rows layout (if the level does not qualify it keeps the
-// plain one)
-int plan_level(const va_tvl1_params* p, int s, int w, int h, int* pitch, size_t* plane, RowsPick* rp)
+enum { LK_TILE = 0, LK_STREAM = 1 };
+// Row pitch in floats: the width rounded up to 4 (rows start 16-byte aligned: k_iter_tile's 4-pixel runs)
+int level_pitch(int w) { return (w + 3) / 4 * 4; }
+// kernel and layout of level s.  Explicit choices first (tests), then the measured default: level_streams.
+int plan_level(const va_tvl1_params* p, int s, int w, int h, int* pitch, size_t* plane)
 {
-    const bool eps = p->epsilon > 0.0f;
-    const int p12 = level_pitch(w, true);
-    int lk = level_kernel(p, eps, s, w, h, p12, va_align_up((size_t)p12 * h, 64), rp);
-    *pitch = level_pitch(w, lk == LK_ROWS);
+    *pitch = level_pitch(w);
     *plane = va_align_up((size_t)*pitch * h, 64);
-    if (lk != LK_ROWS) {
-        lk = level_kernel(p, eps, s, w, h, *pitch, *plane, nullptr) == LK_STREAM ? LK_STREAM : LK_TILE;
-        if (lk == LK_STREAM && stream_ppl(p, w) == 3) {  // three pixels per lane: whole lanes per row need a pitch % 3 == 0
-            *pitch = p12;
-            *plane = va_align_up((size_t)p12 * h, 64);
-        }
-    }
-    return lk;
+    return level_streams(p, p->epsilon > 0.0f, s, w, h, *plane) ? LK_STREAM : LK_TILE;
 }
 
 struct Plan {
     int ns, ws[kMaxScales], hs[kMaxScales], pitch[kMaxScales];
-    int lk[kMaxScales];        // LK_TILE / LK_STREAM / LK_ROWS per level
-    RowsPick rows[kMaxScales];
+    int lk[kMaxScales];        // LK_TILE / LK_STREAM per level
     size_t plane[kMaxScales], plane_max;
     int NF, NP, F;
-    size_t off_pyr[kMaxScales], off_tmp, off_state[2], off_ro, off_err, off_sel, off_ctl, total;
-    int ctl_words;  // k_iter_stream_q: head, abort flag and one completion counter per (pair, pass)
+    size_t off_pyr[kMaxScales], off_tmp, off_state[2], off_ro, off_err, off_sel, total;
 };
 
 int zoom_taps(float step, Taps* t)
@@ -1738,22 +1545,19 @@ int check_params(const va_tvl1_params* p, int w, int h, int n_seq, int fps)
     VA_CHECK_ARG(p->block_iters >= 0 && p->block_iters <= 64, "va_tvl1: block_iters must be in [0,64]");
     VA_CHECK_ARG(p->fast_math == 0 || p->fast_math == 1, "va_tvl1: fast_math must be 0 or 1");
     VA_CHECK_ARG(p->tile_mask >= 0 && p->tile_mask < (1 << (kNumCfgs + 3)), "va_tvl1: tile_mask must be in [0, %d]", (1 << (kNumCfgs + 3)) - 1);
-    VA_CHECK_ARG(p->tuning[VA_TUNE_ROWS_LEVELS] >= -1 && p->tuning[VA_TUNE_ROWS_LEVELS] < (1 << kMaxScales) && p->tuning[VA_TUNE_ROWS_CFG] >= 0 && p->tuning[VA_TUNE_ROWS_CFG] < 256,
-                 "va_tvl1: rows_levels must be -1 or a level bit set, rows_cfg in [0,255]");
-    VA_CHECK_ARG(p->tuning[VA_TUNE_STREAM_PPL] == 0 || p->tuning[VA_TUNE_STREAM_PPL] == 2 || p->tuning[VA_TUNE_STREAM_PPL] == 3, "va_tvl1: stream_ppl must be 0 (default), 2 or 3");
-    VA_CHECK_ARG(p->tuning[VA_TUNE_STREAM_QUEUE] >= 0 && p->tuning[VA_TUNE_STREAM_QUEUE] <= 2, "va_tvl1: stream_queue must be 0 (default), 1 (queued) or 2 (a launch per pass)");
-    VA_CHECK_ARG(p->tuning[VA_TUNE_STREAM_LEVELS] >= -1 && p->tuning[VA_TUNE_STREAM_LEVELS] < (1 << kMaxScales) && (p->tuning[VA_TUNE_STREAM_WAVES] >= 0 && p->tuning[VA_TUNE_STREAM_WAVES] < kMwFirst + kNumMwShapes) &&
+    const int sw = p->tuning[VA_TUNE_STREAM_WAVES];
+    VA_CHECK_ARG(!((sw >= 3 && sw <= 6) || (sw >= 10 && sw <= 12)) && p->tuning[VA_TUNE_STREAM_PPL] != 3 && p->tuning[VA_TUNE_STREAM_QUEUE] != 1 &&
+                     (p->tuning[VA_TUNE_ROWS_LEVELS] == -1 || p->tuning[VA_TUNE_ROWS_LEVELS] == 0) && p->tuning[VA_TUNE_ROWS_CFG] == 0 &&
+                     !(p->tile_mask & kRetiredRowsBit),
+                 "va_tvl1: this tuning value selected a retired VA_EXPERIMENTS kernel family (k_iter_rows, k_iter_stream_q, k_iter_stream4, one "
+                 "deep wave, two chains per wave, 3 x 5 / 3 x 6 / 4 x 6 waves x levels, 3 pixels per lane): measured slower and removed, see "
+                 "DESIGN.md section 7; commit eebd154 is the last one that contains them");
+    VA_CHECK_ARG(p->tuning[VA_TUNE_STREAM_PPL] == 0 || p->tuning[VA_TUNE_STREAM_PPL] == 2, "va_tvl1: stream_ppl must be 0 (default) or 2");
+    VA_CHECK_ARG(p->tuning[VA_TUNE_STREAM_QUEUE] == 0 || p->tuning[VA_TUNE_STREAM_QUEUE] == 2, "va_tvl1: stream_queue must be 0 (default) or 2 (a launch per pass)");
+    VA_CHECK_ARG(p->tuning[VA_TUNE_STREAM_LEVELS] >= -1 && p->tuning[VA_TUNE_STREAM_LEVELS] < (1 << kMaxScales) && (sw >= 0 && sw < kMwFirst + kNumMwShapes) &&
                      p->tuning[VA_TUNE_STREAM_CHUNKS] >= 0 && p->tuning[VA_TUNE_STREAM_SLOTS] >= 0,
-                 "va_tvl1: stream_levels must be -1 or a level bit set, stream_waves in [0, 12], stream_chunks and stream_slots >= 0");
+                 "va_tvl1: stream_levels must be -1 or a level bit set, stream_waves in [0, 9], stream_chunks and stream_slots >= 0");
     VA_CHECK_ARG(p->tau / p->theta <= 1000.0f && p->lambda * p->theta <= 1000.0f, "va_tvl1: tau/theta and lambda*theta must be <= 1000");
-    VA_CHECK_ARG(!(p->tuning[VA_TUNE_STREAM_WAVES] == 3 && p->fast_math), "va_tvl1: stream_waves = 3 (one deep wave) is compiled for the exact arithmetic only");
-    if (!kVaExperiments) {
-        const int sw = p->tuning[VA_TUNE_STREAM_WAVES];
-        VA_CHECK_ARG(sw != 3 && sw != 4 && sw != 5 && sw != 6 && sw <= kMwFirst + 2 && p->tuning[VA_TUNE_STREAM_PPL] != 3 && p->tuning[VA_TUNE_STREAM_QUEUE] != 1 &&
-                         p->tuning[VA_TUNE_ROWS_LEVELS] <= 0 && p->tuning[VA_TUNE_ROWS_CFG] == 0 && !(p->tile_mask & kRowsBit),
-                     "va_tvl1: this tuning value selects an experiment kernel (k_iter_rows, k_iter_stream_q, k_iter_stream4, one deep "
-                     "wave, two chains per wave, four waves x four levels, 3 pixels per lane); build the library with -DVA_EXPERIMENTS (make EXPERIMENTS=1) to get them");
-    }
     return VA_OK;
 }
 
@@ -1782,13 +1586,11 @@ void make_plan(Plan& P, int w, int h, int n_seq, int fps, const va_tvl1_params* 
     P.NP = n_seq * (fps - 1);
     size_t off = 0;
     for (int s = 0; s < P.ns; ++s) {
-        P.lk[s] = plan_level(p, s, P.ws[s], P.hs[s], &P.pitch[s], &P.plane[s], &P.rows[s]);
+        P.lk[s] = plan_level(p, s, P.ws[s], P.hs[s], &P.pitch[s], &P.plane[s]);
         P.off_pyr[s] = off;
         off += va_align_up((size_t)P.NF * 3 * P.plane[s] * sizeof(float), 256);
     }
-    // the buffers every level shares are sized for the LARGEST plane: a coarser level can have the larger one when the
-    // levels' pitches are padded differently (a 12-float pitch on a narrow, tall level: 16 x 100 -> pitch 16, plane 1600
-    // at level 0, but pitch 24, plane 1920 at level 1 when only that level is iterated by k_iter_rows)
+    // the buffers every level shares are sized for the LARGEST plane of the pyramid
     P.plane_max = 0;
     for (int s = 0; s < P.ns; ++s) P.plane_max = P.plane[s] > P.plane_max ? P.plane[s] : P.plane_max;
     P.off_tmp = off;
@@ -1797,20 +1599,15 @@ void make_plan(Plan& P, int w, int h, int n_seq, int fps, const va_tvl1_params* 
         P.off_state[b] = off;
         off += va_align_up((size_t)P.NP * kNF_STATE * P.plane_max * sizeof(float), 256);
     }
-    // k_iter_rows reaches both state buffers through one 32-bit buffer resource; a batch too large for that streams instead
-    // (same plain row order, any even pitch)
-    for (int s = 0; s < P.ns; ++s)
-        if (P.lk[s] == LK_ROWS && (P.off_state[1] - P.off_state[0]) + (size_t)kNF_STATE * P.plane[s] * sizeof(float) >= 2147483648ull)
-            P.lk[s] = LK_STREAM;
     P.off_ro = off;
     off += va_align_up((size_t)P.NP * kNF_RO * P.plane_max * sizeof(float), 256);
     P.off_err = off;
     if (p->epsilon > 0.0f) off += va_align_up((size_t)P.NP * p->iters * sizeof(unsigned long long), 256);
     P.off_sel = off;
     off += va_align_up((size_t)P.NP * 2 * sizeof(int), 256);
-    P.off_ctl = off;
-    P.ctl_words = 2 + P.NP * (p->iters / (2 * kStreamKH2) + 2);
-    off += va_align_up((size_t)P.ctl_words * sizeof(unsigned), 256);
+    // unused tail, kept so that the total callers allocate by does not move: the task counters of a retired kernel
+    // (2 + pairs x (iters / 16 + 2) words) were part of it
+    off += va_align_up((size_t)(2 + P.NP * (p->iters / 16 + 2)) * sizeof(unsigned), 256);
     P.total = off;
 }
 
@@ -1874,18 +1671,11 @@ extern "C" int va_tvl1_tile_plan(int w, int h, const va_tvl1_params* p, int* out
         const TileCfg& c = kCfgs[tp.cfg];
         int lp;
         size_t lplane;
-        RowsPick rp{};
-        const int lk = plan_level(p, s, ws[s], hs[s], &lp, &lplane, &rp);
-        if (lk == LK_ROWS) {
-            const int plan[6] = {64 * rp.ppl, 0, rp.nwv, rp.K, 1, 0};
-            memcpy(out + 6 * s, plan, sizeof(plan));
-            continue;
-        }
-        if (lk == LK_STREAM) {
+        if (plan_level(p, s, ws[s], hs[s], &lp, &lplane) == LK_STREAM) {
             StreamPick sp{};
             stream_strips(p, ws[s], sp);
-            const int plan[6] = {64 * sp.ppl, 0, sp.mw_nwv ? sp.mw_nwv : sp.two ? 2 : 1,
-                                 sp.mw_nwv ? sp.mw_nwv * sp.mw_kh : sp.two ? 2 * stream_kh2(sp.ppl) : stream_k1(sp.ppl), sp.nsx, 0};
+            const int plan[6] = {kStreamSW, 0, sp.mw_nwv ? sp.mw_nwv : sp.two ? 2 : 1,
+                                 sp.mw_nwv ? sp.mw_nwv * sp.mw_kh : sp.two ? 2 * kStreamKH2 : kStreamK1, sp.nsx, 0};
             memcpy(out + 6 * s, plan, sizeof(plan));
             continue;
         }
@@ -1975,24 +1765,15 @@ extern "C" int va_tvl1_flow(va_ctx* ctx, const void* frames, int frames_are_u8, 
         const size_t plane = P.plane[s];
         const unsigned tmask = (unsigned)p->tile_mask & (unsigned)(kStreamBit - 1);
         const TilePick tp = K0 > 0 ? pick_tiles(lw, lh, K0, tmask) : pick_tiles_auto(lw, lh, p->iters, tmask);
-        const RowsPick rp = P.rows[s];
-        const int lk = P.lk[s];
-        // k_iter_rows addresses both state buffers through one 32-bit buffer resource
-        const size_t st_lo = state[0] < state[1] ? 0 : 1;
-        const size_t st_span = (size_t)((char*)state[st_lo ^ 1] - (char*)state[st_lo]) + (size_t)kNF_STATE * plane * sizeof(float);
-        if (lk == LK_ROWS && st_span >= 2147483648ull) {
-            va_set_error("va_tvl1_flow: internal error: state buffers too far apart for k_iter_rows");
-            return VA_ERR_INVALID;
-        }
-        const bool strm = lk == LK_STREAM, rows = lk == LK_ROWS;
-        const int perm = (strm || rows) ? 0 : 1;
+        const bool strm = P.lk[s] == LK_STREAM;
+        const int perm = strm ? 0 : 1;
         if (lp != lw) {
             k_zero_pad<<<dim3(va_cdiv((lp - lw) * lh * kNF_RO, TPB), P.NP), TPB, 0, st>>>(ro, kNF_RO, lw, lh, lp, plane, perm);
             VA_LAUNCH_CHECK();
         }
         // the pairs of a level go through its warps x iterations in chunks (cache residency: chunk_pairs); every chunk
         // starts from the level's entry buffer index and ends on the same one
-        const int cp = (eps || !VA_CHUNK || strm || rows) ? P.NP : chunk_pairs(lw, lh, tp, P.NP);
+        const int cp = (eps || strm) ? P.NP : chunk_pairs(lw, lh, tp, P.NP);
         const int cur_in = cur;
         for (int c0 = 0; c0 < P.NP; c0 += cp) {
         const int nc = P.NP - c0 < cp ? P.NP - c0 : cp;
@@ -2032,36 +1813,6 @@ extern "C" int va_tvl1_flow(va_ctx* ctx, const void* frames, int frames_are_u8, 
             a.theta = p->theta;
             a.pair0 = c0;
             int launches = 0;
-#ifdef VA_EXPERIMENTS
-            if (rows) {
-                RowsArgs ra{};
-                ra.ro = ro;
-                ra.st = state[st_lo];
-                ra.delta[st_lo] = 0u;
-                ra.delta[st_lo ^ 1] = (unsigned)((char*)state[st_lo ^ 1] - (char*)state[st_lo]);
-                ra.plane = plane;
-                ra.w = lw;
-                ra.h = lh;
-                ra.pitch = lp;
-                ra.K = rp.K;
-                ra.K0 = rp.K0;
-                ra.N = rp.N;
-                ra.cur = cur;
-                ra.pair0 = c0;
-                ra.l_t = a.l_t;
-                ra.taut = a.taut;
-                ra.theta = a.theta;
-                int rc;
-                if (rp.ppl == 2) rc = p->fast_math ? launch_rows<2, true>(rp, ra, nc, st) : launch_rows<2, false>(rp, ra, nc, st);
-                else if (rp.ppl == 3) rc = p->fast_math ? launch_rows<3, true>(rp, ra, nc, st) : launch_rows<3, false>(rp, ra, nc, st);
-                else rc = p->fast_math ? launch_rows<4, true>(rp, ra, nc, st) : launch_rows<4, false>(rp, ra, nc, st);
-                if (rc) return rc;
-                cur ^= rp.N & 1;
-                launches = 1;
-            }
-#else
-            (void)rp, (void)st_lo;
-#endif
             if (strm) {
                 const StreamPick sp = pick_stream(p, lw, lh, nc);
                 StreamArgs sa{};
@@ -2084,43 +1835,10 @@ extern "C" int va_tvl1_flow(va_ctx* ctx, const void* frames, int frames_are_u8, 
                 const dim3 grid_mw = narrow ? dim3((2 * sp.nsx - 1) * sp.nch, va_cdiv(nc, 2)) : grid;
                 sa.npairs = nc;
                 const bool two = sp.two != 0;
-                bool queued = false;
-#ifdef VA_EXPERIMENTS
-                // the queued form (all passes in one launch): two-wave pipeline, 2 pixels per lane, and a last pass deep
-                // enough to end in the second wave
-                const int qK = 2 * kStreamKH2, qn = va_cdiv(p->iters, qK), qlast = p->iters - (qn - 1) * qK;
-                queued = two && sp.ppl == 2 && !sp.deep1 && qlast > kStreamKH2 &&
-                         (p->tuning[VA_TUNE_STREAM_QUEUE] == 1 || (p->tuning[VA_TUNE_STREAM_QUEUE] == 0 && VA_STREAM_QUEUE_DEFAULT));
-                if (queued) {
-                    unsigned* ctl = (unsigned*)(ws + P.off_ctl);
-                    VA_HIP(hipMemsetAsync(ctl, 0, (size_t)P.ctl_words * sizeof(unsigned), st));
-                    StreamQArgs qa{};
-                    qa.base = sa;
-                    qa.st[0] = state[0];
-                    qa.st[1] = state[1];
-                    qa.ctl = ctl;
-                    qa.cur = cur;
-                    qa.npass = qn;
-                    qa.K = qK;
-                    qa.Klast = qlast;
-                    qa.npairs = nc;
-                    qa.tpp = sp.nsx * sp.nch;
-                    const int want = p->tuning[VA_TUNE_STREAM_SLOTS] > 0 ? p->tuning[VA_TUNE_STREAM_SLOTS] : 512;  // persistent workgroups: half the GPU's 1024 slots per call
-                    const int nwg = qa.npairs * qa.tpp < want ? qa.npairs * qa.tpp : want;
-                    if (p->fast_math) k_iter_stream_q<2, kStreamKH2, 2, true><<<nwg, 128, 0, st>>>(qa);
-                    else k_iter_stream_q<2, kStreamKH2, 2, false><<<nwg, 128, 0, st>>>(qa);
-                    VA_LAUNCH_CHECK();
-                    k_poison_if_aborted<<<nc, 64, 0, st>>>(ctl, state[0] + (size_t)c0 * kNF_STATE * plane, state[1] + (size_t)c0 * kNF_STATE * plane,
-                                                            (size_t)kNF_STATE * plane, lw);
-                    cur ^= qn & 1;
-                    launches = 1;
-                }
-                const bool four = sp.ppl == 2 && (p->tuning[VA_TUNE_STREAM_WAVES] == 4 || (p->tuning[VA_TUNE_STREAM_WAVES] == 0 && VA_STREAM4_DEFAULT));
-#endif
-                // pipelines of three or four waves: the passes share the iterations as evenly as possible, so that every pass
+                // pipelines of four waves: the passes share the iterations as evenly as possible, so that every pass
                 // is deep enough to end in the last wave (K > (waves - 1) x levels per wave); otherwise the forms below run
                 int mw_n = 0, mw_base = 0, mw_extra = 0;
-                if (sp.mw_nwv && !queued) {
+                if (sp.mw_nwv) {
                     const int kmax = sp.mw_nwv * sp.mw_kh, kmin = (sp.mw_nwv - 1) * sp.mw_kh + 1;
                     mw_n = va_cdiv(p->iters, kmax);
                     mw_base = p->iters / mw_n;
@@ -2131,49 +1849,33 @@ extern "C" int va_tvl1_flow(va_ctx* ctx, const void* frames, int frames_are_u8, 
                     sa.K = mw_base + (i < mw_extra ? 1 : 0);
                     sa.sin = state[cur];
                     sa.sout = state[cur ^ 1];
-                    sa.rev = VA_REV ? (launches & 1) : 0;
+                    sa.rev = launches & 1;
                     sa.narrow = narrow ? 1 : 0;
-                    launch_stream_mw(sp.mw_nwv, sp.mw_kh, p->fast_math != 0, grid_mw, st, sa);
+                    launch_stream_mw(sp.mw_kh, p->fast_math != 0, grid_mw, st, sa);
                     sa.narrow = 0;
                     cur ^= 1;
                     ++launches;
                 }
-                for (int it = (queued || mw_n) ? p->iters : 0; it < p->iters;) {
+                for (int it = mw_n ? p->iters : 0; it < p->iters;) {
                     const int rem = p->iters - it;
-                    const int kh2 = stream_kh2(sp.ppl), k1 = stream_k1(sp.ppl);
-                    const bool w2 = two && rem > kh2 && !sp.deep1;  // the two-wave kernel needs its last level in the second wave
-                    sa.K = sp.deep1 ? (rem < 16 ? rem : 16) : w2 ? (rem < 2 * kh2 ? rem : 2 * kh2) : (rem < k1 ? rem : k1);
+                    const bool w2 = two && rem > kStreamKH2;  // the two-wave kernel needs its last level in the second wave
+                    sa.K = w2 ? (rem < 2 * kStreamKH2 ? rem : 2 * kStreamKH2) : (rem < kStreamK1 ? rem : kStreamK1);
                     sa.sin = state[cur];
                     sa.sout = state[cur ^ 1];
-                    sa.rev = VA_REV ? (launches & 1) : 0;
-#ifdef VA_EXPERIMENTS
-                    if (sp.deep1 && sp.chains == 2) {  // round 3: two interleaved chains of levels per wave (measured slower)
-                        if (p->fast_math) k_iter_stream<2, 16, 1, true, 2><<<grid, 64, 0, st>>>(sa);
-                        else k_iter_stream<2, 16, 1, false, 2><<<grid, 64, 0, st>>>(sa);
-                    } else if (w2 && sp.chains == 2) {
-                        if (p->fast_math) k_iter_stream<2, kStreamKH2, 2, true, 2><<<grid, 128, 0, st>>>(sa);
-                        else k_iter_stream<2, kStreamKH2, 2, false, 2><<<grid, 128, 0, st>>>(sa);
-                    } else if (sp.deep1) {
-                        k_iter_stream<2, 16, 1, false><<<grid, 64, 0, st>>>(sa);
-                    } else if (w2 && four) {
-                        const int njobs = (int)(grid.x * grid.y), g4 = va_cdiv(njobs, 4);
-                        if (p->fast_math) k_iter_stream4<true><<<g4, 512, 0, st>>>(sa, (int)grid.x, njobs);
-                        else k_iter_stream4<false><<<g4, 512, 0, st>>>(sa, (int)grid.x, njobs);
-                    } else
-#endif
+                    sa.rev = launches & 1;
                     if (w2) {
-                        if (p->fast_math) launch_stream<true, true>(sp.ppl, grid, st, sa);
-                        else launch_stream<true, false>(sp.ppl, grid, st, sa);
+                        if (p->fast_math) launch_stream<true, true>(grid, st, sa);
+                        else launch_stream<true, false>(grid, st, sa);
                     } else {
-                        if (p->fast_math) launch_stream<false, true>(sp.ppl, grid, st, sa);
-                        else launch_stream<false, false>(sp.ppl, grid, st, sa);
+                        if (p->fast_math) launch_stream<false, true>(grid, st, sa);
+                        else launch_stream<false, false>(grid, st, sa);
                     }
                     cur ^= 1;
                     it += sa.K;
                     ++launches;
                 }
             }
-            for (int it = (strm || rows) ? p->iters : 0; it < p->iters;) {
+            for (int it = strm ? p->iters : 0; it < p->iters;) {
                 // the tile grid depends on the halo depth: a shorter last launch gets its own grid
                 const int k = (p->iters - it) < tp.K ? (p->iters - it) : tp.K;
                 const TilePick tk = (k == tp.K) ? tp : pick_tiles(lw, lh, k, tmask);
@@ -2183,7 +1885,7 @@ extern "C" int va_tvl1_flow(va_ctx* ctx, const void* frames, int frames_are_u8, 
                 a.cur = cur;
                 a.K = tk.K;
                 a.it = it;
-                a.rev = VA_REV ? (launches & 1) : 0;
+                a.rev = launches & 1;
                 if (eps) {
                     if (p->fast_math) launch_iter<true, true>(tk, a, nc, st);
                     else launch_iter<true, false>(tk, a, nc, st);

@@ -14,7 +14,7 @@ void va_set_error(const char* fmt, ...)
 
 extern "C" const char* va_last_error(void) { return g_err; }
 
-extern "C" int va_version(void) { return 6 | (kVaExperiments ? VA_VERSION_EXPERIMENTS : 0); }
+extern "C" int va_version(void) { return 6; }
 
 extern "C" int va_ctx_create(int device, va_ctx** out)
 {

@@ -194,20 +194,13 @@ struct ConvArgs {
     const float* zeros; // DMA kernel: >= 16 zero bytes, the source of every out-of-image tap
 };
 
-#ifndef VA_XCD_REMAP
-#define VA_XCD_REMAP 1
-#endif
 // XCD-aware workgroup order: consecutive workgroup ids are dealt round-robin to the 8 XCDs (each with its own L2), so
 // the channel tiles of one pixel tile and its neighbours (which share the A operand and its halo) would land on
 // different L2s.  This bijective remap gives every XCD a contiguous run of tiles instead.
 __device__ __forceinline__ int xcd_remap(unsigned bid, unsigned nb)
 {
-#if VA_XCD_REMAP
     const unsigned q = nb / 8, r = nb % 8, xcd = bid % 8, k = bid / 8;
     return (int)((xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + k);
-#else
-    return (int)bid;
-#endif
 }
 
 __device__ __forceinline__ void brick_coords(int m, int lgTW, int lgTH, int& xl, int& yl, int& bl)
@@ -1075,200 +1068,6 @@ __global__ void __launch_bounds__(512) k_conv3x3_pp_bf16(ConvArgsBf a)
     conv3x3_pp_body<NT, POOL>(a);
 }
 
-#ifdef VA_EXPERIMENTS
-// ---------------------------------------------------------------- bf16 conv3x3, two wave groups + halo brick -------
-//
-// An experiment kept as a tested option (VA_OPT_BF16_VARIANT 6), not a default.  Tap-major staging moves (pixels +
-// channels) x 64 B per 32-channel step: 32 KB per step of the 256 x 256 tile, and a CU took in 27..29 B/clk when every
-// CU staged and did nothing else (k_conv3x3_pp_bf16 with its reads and MFMAs removed; LDS-DMA and register loads alike).
-// k_conv3x3_bpp_bf16 keeps the two-group schedule and removes most of the activation traffic: per 32-channel CHUNK the
-// workgroup stages the halo brick of its 256 output pixels ONCE -- TB images x (TH + 2) x (TW + 2) pixels, one 64-byte
-// LDS row each, double-buffered -- and runs the nine taps on it by shifting the fragment's row index; only the weights
-// (NT * 4 KB per step, ring of four) are staged per step: 18 KB instead of 32 KB per step (16 x 16 bricks).
-// Measured (B = 32, us per layer, this kernel / the defaults): 28 x 28: 94 / 85 and 120 / 109 (pooled); 56 x 56: 102 / 95
-// and 126 / 117; 112 x 112: 80 / 80 and 128 / 118 -- 43 % fewer staged bytes and no gain: the steps are not bound by
-// the bytes taken in but by the serial parts of a phase (fragment reads -> barrier, the phase's skew), DESIGN.md.
-//   * K order: chunk-major (32 channels), the nine taps inside -- not the summation order of the tap-major kernels:
-//     agreement at the bf16 level (tested), not bit for bit;
-//   * waits: the brick of chunk c + 1 is issued at tap 0 of chunk c, BEFORE that step's weight tile; loads complete in
-//     issue order, so the counted waits of the weight ring cover it (it must have landed by tap 2; the two steps in
-//     between allow NA more operations in flight);
-//   * the bank swizzle is keyed on the LDS row as above (chunk c of row r at slot c ^ ((r >> 2) & 3)); a fragment's 32
-//     rows are brick-ordered pixels shifted by the tap, not 32 consecutive rows: two of the sixteen lanes of a read group
-//     can share a bank position (2-way on those; measured, not modelled).
-template <int LGTW, int LGTH, int NT, bool POOL>
-__device__ __forceinline__ void conv3x3_bpp_body(const ConvArgsBf& a)
-{
-    constexpr int TW = 1 << LGTW, TH = 1 << LGTH, BM = 256, TB = BM / (TW * TH), PW = TW + 2, PH = TH + 2;
-    static_assert(TW * TH * TB == BM && TB >= 1, "the brick must hold 256 output pixels");
-    constexpr int BN = NT * 64, MT = 2, KB = 32, NB = 4, D = 3, ROWB = KB * 2;
-    constexpr int NR = TB * PH * PW;                    // halo brick rows (one pixel each)
-    constexpr int NA = (NR + 127) / 128;                // brick pieces (16 rows) per wave and chunk
-    constexpr int A_ROWS = 8 * NA * 16;                 // rows of one brick buffer (rows >= NR: zero filler)
-    constexpr int A_BYTES = A_ROWS * ROWB, B_BYTES = BN * ROWB;
-    constexpr int BPW = BN / 128;                       // weight pieces per wave and step
-    static_assert(BN % 128 == 0, "every wave stages whole pieces of the weight tile");
-    constexpr int RING_BYTES = 2 * A_BYTES + NB * B_BYTES, EPI_BYTES = 8 * 64 * NT * 64;  // (the epilogue's staging tiles reuse the ring)
-    __shared__ __attribute__((aligned(1024))) char smem[RING_BYTES > EPI_BYTES ? RING_BYTES : EPI_BYTES];
-    char* const sAbuf = smem;
-    char* const sBbuf = smem + 2 * A_BYTES;
-
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int g = wave >> 2, q = wave & 3, wm = q >> 1, wn = q & 1;
-    int bid = xcd_remap(blockIdx.x, gridDim.x);
-    const int n_tile = bid % a.tiles_n;
-    bid /= a.tiles_n;
-    const int tile_x = bid % a.tiles_x;
-    bid /= a.tiles_x;
-    const int tile_y = bid % a.tiles_y;
-    const int tile_b = bid / a.tiles_y;
-    const int n0 = n_tile * BN;
-    const int H = a.H, W = a.W, Cin = a.Cin;
-    const int X0 = tile_x << LGTW, Y0 = tile_y << LGTH, B0 = tile_b * TB;
-
-    // loader role: row (lane >> 2) of a 16-row piece, slot (lane & 3).  Buffer loads to LDS; a brick row outside the image
-    // (or beyond the brick) carries an out-of-range offset, for which the load writes zeros
-    const int lrow = lane >> 2, lchunk = (lane & 3) ^ ((lrow >> 2) & 3);
-    const __amdgpu_buffer_rsrc_t rs_a =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<__bf16*>(a.in), 0, (int)((long)a.B * H * W * Cin * 2), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_b =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<__bf16*>(a.wp), 0, (int)((long)a.Cout * 9 * Cin * 2), 0x00020000);
-    int aoff[NA];
-#pragma unroll
-    for (int i = 0; i < NA; ++i) {
-        const int R = (wave * NA + i) * 16 + lrow;
-        const int b = R / (PH * PW), rem = R - b * (PH * PW);
-        const int yy = rem / PW, xx = rem - yy * PW;
-        const int y = Y0 + yy - 1, x = X0 + xx - 1, bb = B0 + b;
-        const bool ok = R < NR && bb < a.B && y >= 0 && y < H && x >= 0 && x < W;
-        aoff[i] = ok ? (int)(((((long)bb * H + y) * W + x) * Cin + 8 * lchunk) * 2) : 0x7fffffff;
-    }
-    int boff[BPW];
-#pragma unroll
-    for (int i = 0; i < BPW; ++i) boff[i] = (int)(((long)(n0 + (wave * BPW + i) * 16 + lrow) * 9 * Cin + 8 * lchunk) * 2);
-
-    // fragment role: brick row of this lane's pixel at tap (0, 0)
-    const int r31 = lane & 31, hh = lane >> 5, fswb = (r31 >> 2) & 3;
-    int idx0[MT];
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt) {
-        int xl, yl, bl;
-        brick_coords(128 * g + (wm * MT + mt) * 32 + r31, LGTW, LGTH, xl, yl, bl);
-        idx0[mt] = (bl * PH + yl + 1) * PW + xl + 1;
-    }
-
-    f32x16 acc[MT][NT];
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[mt][nt][r] = 0.0f;
-
-    const int nchunks = Cin / KB, T = 9 * nchunks;
-    // the next weight tile to stage: tap, chunk, ring slot
-    int stap = 0, schunk = 0, sbuf = 0;
-    auto stage_b = [&]() {
-        char* const sB = sBbuf + sbuf * B_BYTES;
-        const int so = (stap * Cin + schunk * KB) * 2;
-        static_for<BPW>([&](auto I) {
-            constexpr int i = decltype(I)::value;
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_b, (lds_ptr_t)(sB + (wave * BPW + i) * 16 * ROWB), 16, boff[i], so, 0, 0);
-        });
-        ++stap;
-        if (stap == 9) {
-            stap = 0;
-            ++schunk;
-        }
-        sbuf = sbuf + 1 == NB ? 0 : sbuf + 1;
-    };
-    auto stage_a = [&](int chunk) {
-        char* const sA = sAbuf + (chunk & 1) * A_BYTES;
-        static_for<NA>([&](auto I) {
-            constexpr int i = decltype(I)::value;
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_a, (lds_ptr_t)(sA + (wave * NA + i) * 16 * ROWB), 16, aoff[i], chunk * KB * 2, 0, 0);
-        });
-    };
-    // wait until at most `ops` of this wave's loads are still in flight, and its LDS reads are done; then the barrier
-    auto sync = [&](int ops) {
-        if (ops < 0) asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-        else if (ops == 2 * BPW + NA) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(2 * BPW + NA) : "memory");
-        else if (ops == 2 * BPW) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(2 * BPW) : "memory");
-        else if (ops == BPW) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(BPW) : "memory");
-        else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-    };
-
-    stage_a(0);
-    for (int j = 0; j < D; ++j) stage_b();  // (T >= 18 > D)
-    sync(2 * BPW);                          // the first brick and step 0's weights have landed
-    if (g == 1) sync(-1);                   // group 1 starts half a step later
-
-    bf16x8 fa[MT][KB / 16] = {}, fb[NT][KB / 16] = {};
-    int rbuf = 0, tap = 0, chunk = 0;
-    auto step = [&](const int t, auto main_tag) __attribute__((always_inline)) {
-        constexpr bool MAIN = decltype(main_tag)::value;
-        {
-            const char* const sA = sAbuf + (chunk & 1) * A_BYTES;
-            const char* const sB = sBbuf + rbuf * B_BYTES;
-            const int ky = tap / 3, toff = (ky - 1) * PW + (tap - 3 * ky) - 1;
-            int arow[MT], asw[MT];
-#pragma unroll
-            for (int mt = 0; mt < MT; ++mt) {
-                arow[mt] = idx0[mt] + toff;
-                asw[mt] = (arow[mt] >> 2) & 3;
-            }
-#pragma unroll
-            for (int ks = 0; ks < KB / 16; ++ks) {
-#pragma unroll
-                for (int mt = 0; mt < MT; ++mt)
-                    fa[mt][ks] = *reinterpret_cast<const bf16x8*>(sA + arow[mt] * ROWB + ((2 * ks + hh) ^ asw[mt]) * 16);
-#pragma unroll
-                for (int nt = 0; nt < NT; ++nt)
-                    fb[nt][ks] = *reinterpret_cast<const bf16x8*>(sB + ((wn * NT + nt) * 32 + r31) * ROWB + ((2 * ks + hh) ^ fswb) * 16);
-            }
-            rbuf = rbuf + 1 == NB ? 0 : rbuf + 1;
-        }
-        const bool brick = tap == 0 && chunk + 1 < nchunks;
-        if (brick) stage_a(chunk + 1);  // (before this step's weight tile: loads complete in issue order)
-        if (MAIN || t + D < T) stage_b();
-        // loads that may stay in flight at the barrier before the ring's next reader: the weight tiles t + 2 .. min(t + D,
-        // T - 1), plus the brick while it is younger than the tile the reader needs (taps 0 and 1)
-        const int steps = MAIN ? D - 1 : (t + D < T ? D - 1 : T - 2 - t < 0 ? 0 : T - 2 - t);
-        const int inflight = steps * BPW + ((tap < 2 && chunk + 1 < nchunks) ? NA : 0);
-        if (g == 0) sync(-1);
-        else sync(inflight);
-#pragma unroll
-        for (int ks = 0; ks < KB / 16; ++ks)
-#pragma unroll
-            for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-                for (int nt = 0; nt < NT; ++nt)
-                    acc[mt][nt] = kWeightsFirst<POOL> ? __builtin_amdgcn_mfma_f32_32x32x16_bf16(fb[nt][ks], fa[mt][ks], acc[mt][nt], 0, 0, 0)
-                                                      : __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[mt][ks], fb[nt][ks], acc[mt][nt], 0, 0, 0);
-        if (g == 0) sync(inflight);
-        else if (MAIN || t + 1 < T) sync(-1);
-        ++tap;
-        if (tap == 9) {
-            tap = 0;
-            ++chunk;
-        }
-    };
-    int t = 0;
-    for (; t < T - D; ++t) step(t, std::true_type{});
-    for (; t < T; ++t) step(t, std::false_type{});
-
-    // epilogue (after barrier 2T nobody reads the LDS tiles any more): whole lines through this wave's share of them
-    epilogue_lines_bf16<NT, POOL>(acc, (__bf16*)smem + wave * 64 * NT * 32, a, 128 * g + wm * MT * 32, n0 + wn * NT * 32, X0, Y0, B0, lane);
-}
-
-template <int LGTW, int LGTH, int NT, bool POOL>
-__global__ void __launch_bounds__(512) k_conv3x3_bpp_bf16(ConvArgsBf a)
-{
-    conv3x3_bpp_body<LGTW, LGTH, NT, POOL>(a);
-}
-#endif  // VA_EXPERIMENTS
-
 // ---------------------------------------------------------------- bf16 conv3x3 with 64 input channels: weights resident ----
 //
 // conv1_2 (64 -> 64 at 224 x 224) and conv2_1 (64 -> 128 at 112 x 112) have K = 576: nine tap-major steps of the kernels
@@ -1449,11 +1248,6 @@ __global__ void __launch_bounds__(256) k_conv3x3_ws_bf16(ConvArgsWs a)
 //   * K order is chunk-major (64-channel chunk outside, tap inside): another fp32 summation order than the tap-major
 //     kernels, so its results agree with theirs at the bf16 noise level, not bit for bit (like the first-layer paths).
 // POOLF32 = false: bf16 NHWC output (conv5_1, conv5_2); true: bias + ReLU + 2 x 2 max-pool, fp32 NHWC [B][7][7][Cout] (conv5_3).
-// TIMING BUILDS ONLY (wrong results): parts of k_conv3x3_img14's steps to leave out -- 1 = the MFMAs, 2 = the fragment
-// reads, 4 = the LDS-DMA refills inside the loop
-#ifndef VA_I14_SKIP
-#define VA_I14_SKIP 0
-#endif
 struct Img14Args {
     const void* in;     // NHWC [B][14][14][Cin] of T, Cin % (128 / sizeof(T)) == 0
     const void* wp;     // [Cout][9][Cin] of T
@@ -1553,9 +1347,9 @@ __device__ __forceinline__ void conv3x3_img14_body(const Img14Args& a)
             __builtin_amdgcn_s_barrier();  // step t is complete in LDS; the computing waves have read step t - 1
             // refills: the NEXT chunk's brick at the first row of this one (its buffer was last read in step t - 1), then the
             // weight tile of step t + 2 (its slot held step t - 1)
-            brick_prev = ky == 0 && chunk + 1 < nchunks && !(VA_I14_SKIP & 4);
+            brick_prev = ky == 0 && chunk + 1 < nchunks;
             if (brick_prev) stage_brick(chunk + 1);
-            if (t + 2 < NT_STEPS && !(VA_I14_SKIP & 4)) stage_w(t + 2);
+            if (t + 2 < NT_STEPS) stage_w(t + 2);
         }
         return;
     }
@@ -1627,9 +1421,8 @@ __device__ __forceinline__ void conv3x3_img14_body(const Img14Args& a)
         fetch(std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{});
         static_for<6>([&](auto SS) {
             constexpr int ss = decltype(SS)::value, cur = ss & 1;
-            if constexpr (ss + 1 < 6 && !(VA_I14_SKIP & 2)) fetch(std::integral_constant<int, ss + 1>{}, std::integral_constant<int, cur ^ 1>{});
+            if constexpr (ss + 1 < 6) fetch(std::integral_constant<int, ss + 1>{}, std::integral_constant<int, cur ^ 1>{});
             __builtin_amdgcn_sched_barrier(0);
-            if constexpr (!(VA_I14_SKIP & 1))
 #pragma unroll
             for (int h = 0; h < 2; ++h)
 #pragma unroll
@@ -2064,21 +1857,10 @@ constexpr long VA_WIDE_MIN = 512;           // register-staged fp32 kernel: 128-
 constexpr int VA_RING = 3;                  // depth of the LDS-DMA ring (two workgroups per CU)
 constexpr long VA_RING_MAXGRID = 1024;      // bf16: ring + 64-channel tiles below this many workgroups (the 14x14 layers)
 constexpr long VA_RING_MAXGRID_F32 = 1024;  // fp32: the same threshold (0 and 4096 measured 2-4 % slower)
-#ifndef VA_WS_DEFAULT
-#define VA_WS_DEFAULT 1     // bf16: the weights-resident kernel on the layers with 64 input channels
-#endif
-#ifndef VA_IMG14_F32_DEFAULT
-#define VA_IMG14_F32_DEFAULT 1  // fp32: the same kernel (T = float) on the 14 x 14 layers of the inference path
-#endif
-#ifndef VA_IMG14_DEFAULT
-#define VA_IMG14_DEFAULT 1  // bf16: the one-image-per-workgroup kernel on the 14 x 14 layers (k_conv3x3_img14)
-#endif
-#ifndef VA_BPP_DEFAULT
-#define VA_BPP_DEFAULT 0    // bf16: 1 = the two-group halo-brick kernel wherever it applies (set after measurement)
-#endif
-#ifndef VA_PP_DEFAULT
-#define VA_PP_DEFAULT 1     // bf16: the two-group kernel where launch_conv_bf16 measured it faster (0: never by default)
-#endif
+// VA_OPT_BF16_VARIANT 6 (the two-group kernel on halo bricks) is refused with this text
+constexpr const char* kRetiredVariant6 =
+    "6 selected a retired VA_EXPERIMENTS kernel family (k_conv3x3_bpp_bf16): measured no faster and removed, see DESIGN.md section 7; commit "
+    "eebd154 is the last one that contains it";
 constexpr int VA_F32_CONV_DEFAULT = 1;      // 1: LDS-DMA fp32 kernel where Cin % 32 == 0; va_vgg16_set_option(VA_OPT_F32_CONV_KERNEL, 0) selects the register-staged one (A/B)
 constexpr int VA_CIN_ALIGN = 16;            // fp32 first-layer channel padding (3 -> 16: register-staged kernel; 20 -> 32: DMA kernel)
 
@@ -2131,7 +1913,7 @@ int launch_conv_ex(int hw, int cin_pad, int cout, const float* wp, const float* 
     const int tiles_b = va_cdiv(B, a.TB);
     // 14 x 14 layers (conv5_x) of the inference path: one image x 64 output channels per workgroup (k_conv3x3_img14<float>,
     // round 3): 256 workgroups at batch 32 = one round of the CUs instead of 392 tap-major tiles (53 % MFMA utilisation)
-    if (f32_conv == 1 && VA_IMG14_F32_DEFAULT && hw == 14 && mask == nullptr && !linear && cin_pad % 32 == 0 && cout % 64 == 0) {
+    if (f32_conv == 1 && hw == 14 && mask == nullptr && !linear && cin_pad % 32 == 0 && cout % 64 == 0) {
         const Img14Args ia{in, wp, bias, out, B, cin_pad, cout};
         const unsigned gridi = (unsigned)(B * (cout / 64));
         if (pool) k_conv3x3_img14<float, true><<<gridi, 512, 0, st>>>(ia);
@@ -2223,7 +2005,7 @@ int launch_conv_bf16(const ConvLayer& L, const __bf16* zeros, int variant, const
         pick_brick(L.hw, L.hw, B, lw, lh, tb, 8);
         const bool nt4 = L.cout % 256 == 0;
         const long gridp = (long)(L.cout / (nt4 ? 256 : 128)) * va_cdiv(L.hw, 1 << lw) * va_cdiv(L.hw, 1 << lh) * va_cdiv(B, tb);
-        if (variant == 0) pp = VA_PP_DEFAULT && nt4 && ((gridp >= 160 && gridp <= 256) || gridp >= 1024);
+        if (variant == 0) pp = nt4 && ((gridp >= 160 && gridp <= 256) || gridp >= 1024);
     }
     if (pp) {
         pick_brick(L.hw, L.hw, B, a.lgTW, a.lgTH, a.TB, 8);
@@ -2246,7 +2028,7 @@ int launch_conv_bf16(const ConvLayer& L, const __bf16* zeros, int variant, const
     }
     // 14 x 14 layers (conv5_x): one image x 64 output channels per workgroup, the image's halo brick staged once per
     // 64-channel chunk (k_conv3x3_img14): the default there; variants 1, 2 keep the tap-major kernels for A/B and tests
-    if ((variant == 0 || variant >= 5) && VA_IMG14_DEFAULT && !L.xcol && L.hw == 14 && a.Cin % 64 == 0 && L.cout % 64 == 0 &&
+    if ((variant == 0 || variant >= 5) && !L.xcol && L.hw == 14 && a.Cin % 64 == 0 && L.cout % 64 == 0 &&
         (long)B * (L.cout / 64) <= 65535L * 16 && ((out_f32 && L.pool) || (!out_f32 && !L.pool))) {
         const unsigned gridi = (unsigned)(B * (L.cout / 64));
         const Img14Args ia{a.in, a.wp, a.bias, a.out, B, a.Cin, a.Cout};
@@ -2259,7 +2041,7 @@ int launch_conv_bf16(const ConvLayer& L, const __bf16* zeros, int variant, const
     // The weights-resident kernel (k_conv3x3_ws_bf16) on the layers with 64 input channels: variant 7 forces it (conv1_2
     // and conv2_1), the default uses it where it measured faster: 64 output channels (conv1_2: 135 against 162 us; conv2_1
     // with its two channel halves: 84 against 80).  Same products in the same order as the tap-major kernel: bit-equal
-    if ((variant == 7 || (variant == 0 && VA_WS_DEFAULT && L.cout == 64)) && !L.xcol && !out_f32 && a.Cin == 64 && L.cout % 64 == 0 &&
+    if ((variant == 7 || (variant == 0 && L.cout == 64)) && !L.xcol && !out_f32 && a.Cin == 64 && L.cout % 64 == 0 &&
         L.cout <= 256 && L.hw % 16 == 0 && n_cu >= L.cout / 64) {
         ConvArgsWs w{};
         w.c = a;
@@ -2275,39 +2057,9 @@ int launch_conv_bf16(const ConvLayer& L, const __bf16* zeros, int variant, const
         VA_LAUNCH_CHECK();
         return VA_OK;
     }
-#ifdef VA_EXPERIMENTS
-    // variant 6: the two-group kernel on halo bricks (k_conv3x3_bpp_bf16) on the layers with >= 128 output channels and
-    // 28 x 28 pixels or more (16 x 16 bricks; 8 x 8 of four images; 4 x 4 of sixteen)
-    if ((variant == 6 || (variant == 0 && VA_BPP_DEFAULT)) && !L.xcol && !out_f32 && a.Cin % 32 == 0 && L.cout % 128 == 0 &&
-        (L.hw == 224 || L.hw == 112 || L.hw == 56 || L.hw == 28)) {
-        const int lg = L.hw >= 112 ? 4 : L.hw == 56 ? 3 : 2;
-        a.lgTW = a.lgTH = lg;
-        a.TB = 256 >> (2 * lg);
-        a.tiles_x = a.tiles_y = L.hw >> lg;
-        const bool nt4 = L.cout % 256 == 0;
-        a.tiles_n = L.cout / (nt4 ? 256 : 128);
-        const unsigned gridb = (unsigned)(a.tiles_n * a.tiles_x * a.tiles_y * va_cdiv(B, a.TB));
-#define VA_LAUNCH_BPP(LG_, NT_)                                                              \
-    {                                                                                        \
-        if (L.pool) k_conv3x3_bpp_bf16<LG_, LG_, NT_, true><<<gridb, 512, 0, st>>>(a);       \
-        else k_conv3x3_bpp_bf16<LG_, LG_, NT_, false><<<gridb, 512, 0, st>>>(a);             \
-        VA_LAUNCHED(L.pool ? "k_conv3x3_bpp_bf16<" #LG_ "," #LG_ "," #NT_ ",true>"            \
-                           : "k_conv3x3_bpp_bf16<" #LG_ "," #LG_ "," #NT_ ",false>");         \
-    }
-        if (lg == 4 && nt4) VA_LAUNCH_BPP(4, 4)
-        else if (lg == 4) VA_LAUNCH_BPP(4, 2)
-        else if (lg == 3 && nt4) VA_LAUNCH_BPP(3, 4)
-        else if (lg == 3) VA_LAUNCH_BPP(3, 2)
-        else if (nt4) VA_LAUNCH_BPP(2, 4)
-        else VA_LAUNCH_BPP(2, 2)
-#undef VA_LAUNCH_BPP
-        VA_LAUNCH_CHECK();
-        return VA_OK;
-    }
-#endif
     const long grid64 = (long)(L.cout / 64) * a.tiles_x * a.tiles_y * tiles_b;
     const int ksteps = 3 * a.taps_x * (a.Cin / 64);
-    const bool autosel = variant == 0 || variant >= 5;  // (variants 5 .. 7 fall through to the automatic choice where they do not apply)
+    const bool autosel = variant == 0 || variant >= 5;  // (variants 5 and 7 fall through to the automatic choice where they do not apply)
     const bool ring = autosel ? (grid64 < VA_RING_MAXGRID && ksteps >= VA_RING) : (variant == 2 && ksteps >= VA_RING);
     const bool wide = autosel && !ring && L.cout % 128 == 0;
     a.tiles_n = L.cout / (wide ? 128 : 64);
@@ -2425,9 +2177,10 @@ extern "C" int va_conv3x3_layer(va_ctx* ctx, int dtype, int kernel_opt, int hw, 
                  "va_conv3x3_layer: every pointer must be 16-byte aligned (16-byte vector accesses)");
     VA_CHECK_ARG(dtype == VA_DTYPE_F32 || dtype == VA_DTYPE_BF16, "va_conv3x3_layer: dtype must be VA_DTYPE_F32 or VA_DTYPE_BF16");
     const bool bf = dtype == VA_DTYPE_BF16;
+    VA_CHECK_ARG(!(bf && kernel_opt == 6), "va_conv3x3_layer: bf16 kernel_opt %s", kRetiredVariant6);
     if (bf)
-        VA_CHECK_ARG((kernel_opt >= 0 && kernel_opt <= 2) || kernel_opt == 5 || kernel_opt == 7 || (kernel_opt == 6 && kVaExperiments),
-                     "va_conv3x3_layer: bf16 kernel_opt (VA_OPT_BF16_VARIANT) must be 0, 1, 2, 5 or 7 (6: -DVA_EXPERIMENTS builds)");
+        VA_CHECK_ARG((kernel_opt >= 0 && kernel_opt <= 2) || kernel_opt == 5 || kernel_opt == 7,
+                     "va_conv3x3_layer: bf16 kernel_opt (VA_OPT_BF16_VARIANT) must be 0, 1, 2, 5 or 7");
     else
         VA_CHECK_ARG(kernel_opt == 0 || kernel_opt == 1, "va_conv3x3_layer: fp32 kernel_opt (VA_OPT_F32_CONV_KERNEL) must be 0 or 1");
     VA_CHECK_ARG(batch >= 1, "va_conv3x3_layer: batch %d < 1", batch);
@@ -2702,8 +2455,8 @@ extern "C" int va_vgg16_set_option(va_vgg16* m, int option, int value)
     VA_CHECK_ARG(m != nullptr, "va_vgg16_set_option: model is NULL");
     switch (option) {
         case VA_OPT_BF16_VARIANT:
-            VA_CHECK_ARG((value >= 0 && value <= 2) || (value >= 5 && value <= 7), "va_vgg16_set_option: VA_OPT_BF16_VARIANT must be 0, 1, 2, 5, 6 or 7");
-            VA_CHECK_ARG(value != 6 || kVaExperiments, "va_vgg16_set_option: VA_OPT_BF16_VARIANT 6 (k_conv3x3_bpp_bf16) needs a library built with -DVA_EXPERIMENTS");
+            VA_CHECK_ARG(value != 6, "va_vgg16_set_option: VA_OPT_BF16_VARIANT %s", kRetiredVariant6);
+            VA_CHECK_ARG((value >= 0 && value <= 2) || value == 5 || value == 7, "va_vgg16_set_option: VA_OPT_BF16_VARIANT must be 0, 1, 2, 5 or 7");
             m->bf16_variant = value;
             return VA_OK;
         case VA_OPT_BF16_FIRST_LAYER:

@@ -154,6 +154,26 @@ def test_tile_plan_of_the_benchmark_pyramid():
     assert all((d["tile_w"], d["tile_h"], d["block_iters"]) == (128, 32, 6) for d in forced)
 
 
+def test_tvl1_plans_equal_the_recorded_ones(lib):
+    """tile_plan and va_tvl1_workspace_bytes over a grid of frame sizes, pair counts and tuning values reproduce
+    tests/golden/tvl1_plans.npz exactly: the file was recorded from the library before the row pipeline's host side was
+    reduced to one launch helper and one description of the pipeline shape (tests/golden/make_tvl1_plan_golden.py)."""
+    import importlib.util
+    import numpy as np
+    path = os.path.join(ROOT, "tests", "golden", "make_tvl1_plan_golden.py")
+    spec = importlib.util.spec_from_file_location("make_tvl1_plan_golden", path)
+    gen = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(gen)
+    assert os.path.getsize(gen.OUT) < 100 * 1024
+    want, got = np.load(gen.OUT), gen.compute()
+    assert sorted(want.files) == sorted(got)
+    for name in want.files:
+        assert want[name].dtype == got[name].dtype and want[name].shape == got[name].shape, name
+        bad = np.argwhere(want[name] != got[name])
+        assert len(bad) == 0, "%s differs at %d places, first at index %s" % (name, len(bad), bad[0])
+    assert int(got["levels"].min()) >= 1 and int(got["workspace"].min()) > 0  # every case of the grid is an accepted one
+
+
 def test_public_header_is_plain_c(tmp_path):
     """include/va.h is a C ABI: it must compile as C99 (no C++ or torch types) with the system compiler."""
     import shutil

@@ -213,6 +213,25 @@ def test_streaming_kernel_fast_math_and_mixed_levels(oracle_tvl1):
     assert (fast - exact).abs().max().item() < 1e-3
 
 
+@pytest.mark.parametrize("iters", [23, 44])
+@pytest.mark.parametrize("H,W,nch", [(57, 131, 1), (150, 300, 2), (33, 130, 1)])
+def test_streaming_kernel_one_wave_exact_and_every_form_fast_math(oracle_tvl1, H, W, nch, iters):
+    # stream_waves = 1 (one wave x 10 levels on every level) against the oracle, and fast_math = 1 on every form of the row
+    # pipeline (stream_waves 1, 2, 7, 8, 9 = 1 x 10, 2 x 8, 4 x 4, 4 x 5, 4 x 3) against the register tiles, which run the
+    # same 1-ulp arithmetic.  131 columns: two strips, a narrow last one, pitch padding; 300: three strips with interior
+    # halos, two chunks of rows; 33 rows: a chunk shorter than a pass is deep.  Three pairs: a couple that shares a narrow
+    # last strip and a single one.  23 iterations: passes fall back to the shallower forms; 44: an even split
+    from video_analytics_amd import flow as vflow
+    gray = _frames(3, 2, H, W, seed=5 * H + W)
+    kw = dict(epsilon=0.0, iters=iters, warps=1, nscales=2)
+    ref, out = _run_both(oracle_tvl1, gray, tile_mask=1 << 8, stream_chunks=nch, stream_waves=1, **kw)
+    assert np.array_equal(out, ref), "stream_waves=1: max abs diff %g" % np.abs(out - ref).max()
+    tiles = vflow.tvl1_flow(gray.cuda(), tile_mask=0xFF, fast_math=1, **kw)
+    for waves in (1, 2, 7, 8, 9):
+        fast = vflow.tvl1_flow(gray.cuda(), tile_mask=1 << 8, stream_chunks=nch, stream_waves=waves, fast_math=1, **kw)
+        assert torch.equal(fast, tiles), "fast_math, stream_waves=%d: max abs diff %g" % (waves, (fast - tiles).abs().max().item())
+
+
 @pytest.mark.parametrize("fill", [0xFF, 0x7F])
 def test_result_does_not_depend_on_what_the_workspace_held(oracle_tvl1, fill):
     # the caller owns the workspace and may hand over anything: NaN (0xFFFFFFFF) and huge (0x7F7F7F7F)

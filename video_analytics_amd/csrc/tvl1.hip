@@ -835,10 +835,9 @@ struct StreamArgs {
 // level t + 1 consumes what level t emits in the SAME step, from one chain to the next the row waits in registers for one
 // step (a latch), so that every chain end costs one step of pipeline depth: global level g works at pipeline position
 // pos(g) = g + (chain ends before g).  Only NCH = 1 is instantiated (one chain: no latch, pos(g) = g + waves before g).
-// SUBS jobs per workgroup (`sub`, `role`, `active`, `steps_pad`): only SUBS = 1 with the default arguments is instantiated.
-// These parameters served kernel forms that measured slower and were removed.  They stay in
-// stream_job because the surviving kernels are held to the machine code they had before the removal, and taking even
-// the constant arguments out changes what the compiler emits for all ten k_iter_stream instantiations.
+// These two parameters served kernel forms that measured slower and were removed.  They stay in
+// stream_job because taking either out changes the register allocation of the one-wave form (234 -> 203 registers, more
+// moves), which then measures 1-3 % slower; the parameters of the several-jobs-per-workgroup form went without that cost.
 template <int KH, int NCH>
 struct StreamShape {
     static_assert(KH % NCH == 0, "the levels of a wave are cut into chains of equal length");
@@ -860,10 +859,9 @@ struct StreamRow {  // the six state fields of one row of a strip
     Row<PPL> u1, u2, p11, p12, p21, p22;
 };
 
-template <int PPL, int KH, int NWV, bool FAST, int SUBS = 1, int NCH = 1>
+template <int PPL, int KH, int NWV, bool FAST, int NCH = 1>
 __device__ __forceinline__ void stream_job(const StreamArgs& a, const int pair, const int job, const int K,
-                                           const float* __restrict__ sin_all, float* __restrict__ sout_all, const int sub = 0,
-                                           const int role = -1, const bool active = true, const int steps_pad = 0, const int half = 0)
+                                           const float* __restrict__ sin_all, float* __restrict__ sout_all, const int half = 0)
 {   // half: 0 = a whole-wave strip of `pair`; 1 = the shared last strip of `pair` (lanes 0..31) and `pair + 1` (lanes 32..63);
     // 2 = the same without a second pair (lanes 32..63 idle)
     typedef Row<PPL> R;
@@ -874,19 +872,15 @@ __device__ __forceinline__ void stream_job(const StreamArgs& a, const int pair, 
     // wave writes row s - 1 at the start of step s (after the barrier), the oldest row read in step s is
     // s - (NWV * SPAN - 2), whose slot is that of row s (written in step s + 1).
     constexpr int NRING = stream_ring_rows<KH, NWV, NCH>() > 0 ? stream_ring_rows<KH, NWV, NCH>() : 1;
-    __shared__ f2 ringP_[SUBS][NRING][kNF_RO][NP][64];
-    __shared__ float ringT_[SUBS][NRING][kNF_RO][NT ? 64 : 1];
-    __shared__ f2 ifaceP_[SUBS][NWV > 1 ? NWV - 1 : 1][2][kNF_STATE][NP][64];
-    __shared__ float ifaceT_[SUBS][NWV > 1 ? NWV - 1 : 1][2][kNF_STATE][NT ? 64 : 1];
-    auto& ringP = ringP_[sub];
-    auto& ringT = ringT_[sub];
-    auto& ifaceP = ifaceP_[sub];
-    auto& ifaceT = ifaceT_[sub];
+    __shared__ f2 ringP[NRING][kNF_RO][NP][64];
+    __shared__ float ringT[NRING][kNF_RO][NT ? 64 : 1];
+    __shared__ f2 ifaceP[NWV > 1 ? NWV - 1 : 1][2][kNF_STATE][NP][64];
+    __shared__ float ifaceT[NWV > 1 ? NWV - 1 : 1][2][kNF_STATE][NT ? 64 : 1];
 
     const int sx = job % a.nsx, ch = job / a.nsx;
     const int w = a.w, h = a.h, pitch = a.pitch;
     const int lane = threadIdx.x & 63;
-    const int wv = NWV == 1 ? 0 : role >= 0 ? role : __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int wv = NWV == 1 ? 0 : __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int ox = sx * (SW - 2 * a.HX);
     const int vx0 = ox + (sx > 0 ? a.HX : 0), vx1 = (sx == a.nsx - 1) ? pitch : ox + SW - a.HX;
     const int x0 = ox + PPL * (half ? (lane & 31) : lane);  // (the pitch, the halo and so every strip origin are multiples of PPL)
@@ -963,7 +957,7 @@ __device__ __forceinline__ void stream_job(const StreamArgs& a, const int pair, 
 
     // the last valid row b0 - 1 leaves the last ACTIVE level (K - 1) when row b0 (or the dummy row h) comes in, and then
     // waits one step at every chain end on its way to the last wave's output: NWV * NCH - 1 of them
-    const int nsteps = active ? b0 - ys + K + (NWV * NCH - 1) : 0;
+    const int nsteps = b0 - ys + K + (NWV * NCH - 1);
 
     auto run = [&](auto wave_tag) __attribute__((always_inline)) {
         constexpr int W = decltype(wave_tag)::value;
@@ -1194,7 +1188,7 @@ __device__ __forceinline__ void stream_job(const StreamArgs& a, const int pair, 
             s_a = d_max(s_a, d_max(0, a0 - (K - g)) + p);
             s_b = d_min(s_b, d_min(h - 1, d_min(h, b0 + (K - g) - 1)) + p + 1);
         }
-        if (K < G0 + KH || s_a > s_b || !active) s_a = s_b = 0;
+        if (K < G0 + KH || s_a > s_b) s_a = s_b = 0;
         int s = 0;
         for (; s < s_a; ++s) step(s, std::false_type{});
         // two steady steps per loop trip: the rows a level hands on and keeps (c_* -> P[t], n -> U[t]) change registers
@@ -1208,8 +1202,6 @@ __device__ __forceinline__ void stream_job(const StreamArgs& a, const int pair, 
             }
         for (; s < s_b; ++s) step(s, std::true_type{});
         for (; s < nsteps; ++s) step(s, std::false_type{});
-        if constexpr (SUBS > 1)  // the other jobs of the workgroup may have more steps: join their barriers
-            for (; s < steps_pad; ++s) asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
     };
     if constexpr (NWV == 1) {
         run(std::integral_constant<int, 0>{});
@@ -1242,7 +1234,7 @@ __global__ void __launch_bounds__(NWV * 64)
         if (a.rev) lid = nb - 1 - lid;
     }
     if (!a.narrow) {
-        stream_job<PPL, KH, NWV, FAST, 1, NCH>(a, a.pair0 + (int)(lid / gridDim.x), (int)(lid % gridDim.x), a.K, a.sin, a.sout);
+        stream_job<PPL, KH, NWV, FAST, NCH>(a, a.pair0 + (int)(lid / gridDim.x), (int)(lid % gridDim.x), a.K, a.sin, a.sout);
         return;
     }
     // shared last strips: per couple of pairs and chunk 2 (nsx - 1) whole-wave strips and ONE wave for both last strips
@@ -1255,7 +1247,7 @@ __global__ void __launch_bounds__(NWV * 64)
         half = 0;
         if (first + which >= a.npairs) return;  // an odd number of pairs: the last couple has no second one
     }
-    stream_job<PPL, KH, NWV, FAST, 1, NCH>(a, a.pair0 + first + which, ch * a.nsx + sx, a.K, a.sin, a.sout, 0, -1, true, 0, half);
+    stream_job<PPL, KH, NWV, FAST, NCH>(a, a.pair0 + first + which, ch * a.nsx + sx, a.K, a.sin, a.sout, half);
 }
 
 // ---------------------------------------------------------------- host side -------------------
@@ -1376,31 +1368,32 @@ constexpr int kStreamBit = 1 << 8;  // va_tvl1_params.tile_mask bit: iterate wit
 constexpr int kRetiredRowsBit = 1 << 9;  // va_tvl1_params.tile_mask bit of a retired kernel family: refused (check_params)
 constexpr int kNoNarrowBit = 1 << 10;  // va_tvl1_params.tile_mask bit: no shared last strips (StreamArgs.narrow) -- A/B and tests
 struct StreamPick {
-    int nsx, nch, R, HX, two;
-    int mw_nwv, mw_kh;  // > 0: the pipeline of four waves x mw_kh levels
+    int nsx, nch, R, HX;
+    int nwv, kh;        // the pipeline of four waves x kh levels for the passes deep enough to end in its last wave; nwv = 0: none
+    int fb_nwv, fb_kh;  // the fallback shape of every other pass: 2 x 8, or 1 x 10 (which also takes what is too short for 2 x 8)
     int narrow;         // the last strip of a row fits 32 lanes: two pairs' last strips share a wave (StreamArgs.narrow)
 };
 // stream_waves 7, 8, 9: pipelines of four waves (waves x levels per wave)
 constexpr int kMwShapes[][2] = {{4, 4}, {4, 5}, {4, 3}};
 constexpr int kNumMwShapes = (int)(sizeof(kMwShapes) / sizeof(kMwShapes[0]));
 constexpr int kMwFirst = 7;
-template <bool TWO, bool FAST>
-void launch_stream(dim3 grid, hipStream_t st, const StreamArgs& sa)
+// One pass of the row pipeline in one of the five shapes (waves x levels per wave) that exist
+int launch_stream(int nwv, int kh, bool fast, dim3 grid, hipStream_t st, const StreamArgs& sa)
 {
-    constexpr int NWV = TWO ? 2 : 1;
-    k_iter_stream<2, TWO ? kStreamKH2 : kStreamK1, NWV, FAST><<<grid, NWV * 64, 0, st>>>(sa);
-}
-template <int NWV, int KH>
-void launch_stream_mw1(bool fast, dim3 grid, hipStream_t st, const StreamArgs& sa)
-{
-    if (fast) k_iter_stream<2, KH, NWV, true><<<grid, NWV * 64, 0, st>>>(sa);
-    else k_iter_stream<2, KH, NWV, false><<<grid, NWV * 64, 0, st>>>(sa);
-}
-void launch_stream_mw(int kh, bool fast, dim3 grid, hipStream_t st, const StreamArgs& sa)
-{
-    if (kh == 5) return launch_stream_mw1<4, 5>(fast, grid, st, sa);
-    if (kh == 3) return launch_stream_mw1<4, 3>(fast, grid, st, sa);
-    launch_stream_mw1<4, 4>(fast, grid, st, sa);
+    auto go = [&](auto nwv_tag, auto kh_tag) {
+        constexpr int NWV = decltype(nwv_tag)::value, KH = decltype(kh_tag)::value;
+        if (fast) k_iter_stream<2, KH, NWV, true><<<grid, NWV * 64, 0, st>>>(sa);
+        else k_iter_stream<2, KH, NWV, false><<<grid, NWV * 64, 0, st>>>(sa);
+        return VA_OK;
+    };
+    using std::integral_constant;
+    if (nwv == 1 && kh == kStreamK1) return go(integral_constant<int, 1>{}, integral_constant<int, kStreamK1>{});
+    if (nwv == 2 && kh == kStreamKH2) return go(integral_constant<int, 2>{}, integral_constant<int, kStreamKH2>{});
+    if (nwv == 4 && kh == 3) return go(integral_constant<int, 4>{}, integral_constant<int, 3>{});
+    if (nwv == 4 && kh == 4) return go(integral_constant<int, 4>{}, integral_constant<int, 4>{});
+    if (nwv == 4 && kh == 5) return go(integral_constant<int, 4>{}, integral_constant<int, 5>{});
+    va_set_error("va_tvl1: no row pipeline of %d waves x %d levels", nwv, kh);
+    return VA_ERR_INVALID;
 }
 // Strips of a level and the shape of the pipeline that carries them (see the comment on the four-wave forms below).  The
 // forms of rounds 1-2 remain as explicit choices and as fallbacks for passes too short for four waves: two waves x 8
@@ -1409,11 +1402,13 @@ void launch_stream_mw(int kh, bool fast, dim3 grid, hipStream_t st, const Stream
 void stream_strips(const va_tvl1_params* p, int w, StreamPick& sp)
 {
     constexpr int SW = kStreamSW;
-    sp.two = p->tuning[VA_TUNE_STREAM_WAVES] != 1 && tiles_1d(w, SW, 2 * kStreamKH2) <= 2;
+    const bool two = p->tuning[VA_TUNE_STREAM_WAVES] != 1 && tiles_1d(w, SW, 2 * kStreamKH2) <= 2;
+    sp.fb_nwv = two ? 2 : 1;
+    sp.fb_kh = two ? kStreamKH2 : kStreamK1;
     // (Also measured, round 2, and removed again: THREE waves of 4 / 5 levels each -- 12 / 15 iterations per pass at 144 /
     // 168 registers, i.e. three resident waves per SIMD instead of two: 45.2 / 43.9 ms on the 224^2 level and 35.3 / 34.8
     // on 179^2 against 41.6 / 32.9 for the two-wave form: more resident waves do not fill the idle issue slots.)
-    sp.HX = sp.two ? 2 * kStreamKH2 : kStreamK1;  // (even: strip origins stay multiples of the two pixels per lane)
+    sp.HX = sp.fb_nwv * sp.fb_kh;  // (16 or 10, even: strip origins stay multiples of the two pixels per lane)
     sp.nsx = tiles_1d(w, SW, sp.HX);
     // Pipelines of FOUR waves (round 3): 4 x 4 levels (16 iterations per pass, 143 registers: three waves per SIMD) or, where
     // a 20-column halo still costs no third strip, 4 x 5 levels (20 per pass, 167 registers).  Measured per level on the
@@ -1428,14 +1423,14 @@ void stream_strips(const va_tvl1_params* p, int w, StreamPick& sp)
     const int sw = p->tuning[VA_TUNE_STREAM_WAVES];
     int shape = -1;
     if (sw >= kMwFirst && sw < kMwFirst + kNumMwShapes) shape = sw - kMwFirst;
-    else if (sw == 0) shape = !sp.two ? 2 : (w > SW && tiles_1d(w, SW, 20) <= 2) ? 1 : 0;
+    else if (sw == 0) shape = !two ? 2 : (w > SW && tiles_1d(w, SW, 20) <= 2) ? 1 : 0;
     if (shape >= 0) {
         const int nwv = kMwShapes[shape][0], kh = kMwShapes[shape][1], hx = va_cdiv(nwv * kh, 2) * 2;
         // the default choice: like the two-wave form only where the deeper x halo costs no third strip; an explicit
         // stream_waves >= 7 takes the shape wherever a strip keeps valid columns
-        if (2 * hx < SW && (sw >= kMwFirst || !sp.two || tiles_1d(w, SW, hx) <= 2)) {
-            sp.mw_nwv = nwv;
-            sp.mw_kh = kh;
+        if (2 * hx < SW && (sw >= kMwFirst || !two || tiles_1d(w, SW, hx) <= 2)) {
+            sp.nwv = nwv;
+            sp.kh = kh;
             if (hx > sp.HX) sp.HX = hx;  // (a pass that falls back to the two-wave form runs with this halo too)
             sp.nsx = tiles_1d(w, SW, sp.HX);
             // the last strip starts at (nsx - 1) (SW - 2 HX); if the level (with its pitch padding) ends within 64 columns of
@@ -1455,7 +1450,7 @@ StreamPick pick_stream(const va_tvl1_params* p, int w, int h, int npairs)
     // (four-wave jobs: 320 per call on the levels of at most two strips -- 256 ... 400 measured equal, 480 and more 5 % slower
     // in the whole benchmark --, 1024 on the wide levels: 512 ... 1280 within 2 %, 2048 8 % slower)
     const int slots = p->tuning[VA_TUNE_STREAM_SLOTS] > 0 ? p->tuning[VA_TUNE_STREAM_SLOTS]
-                      : sp.mw_nwv ? (sp.nsx <= 2 ? 320 : 1024) : (sp.two ? 640 : 1024);
+                      : sp.nwv ? (sp.nsx <= 2 ? 320 : 1024) : (sp.fb_nwv == 2 ? 640 : 1024);
     int nch = p->tuning[VA_TUNE_STREAM_CHUNKS];
     if (nch <= 0) nch = (int)((double)slots / ((double)npairs * sp.nsx) + 0.5);
     if (nch > h / 32) nch = h / 32;
@@ -1674,8 +1669,8 @@ extern "C" int va_tvl1_tile_plan(int w, int h, const va_tvl1_params* p, int* out
         if (plan_level(p, s, ws[s], hs[s], &lp, &lplane) == LK_STREAM) {
             StreamPick sp{};
             stream_strips(p, ws[s], sp);
-            const int plan[6] = {kStreamSW, 0, sp.mw_nwv ? sp.mw_nwv : sp.two ? 2 : 1,
-                                 sp.mw_nwv ? sp.mw_nwv * sp.mw_kh : sp.two ? 2 * kStreamKH2 : kStreamK1, sp.nsx, 0};
+            const int nwv = sp.nwv ? sp.nwv : sp.fb_nwv, kh = sp.nwv ? sp.kh : sp.fb_kh;
+            const int plan[6] = {kStreamSW, 0, nwv, nwv * kh, sp.nsx, 0};
             memcpy(out + 6 * s, plan, sizeof(plan));
             continue;
         }
@@ -1834,12 +1829,11 @@ extern "C" int va_tvl1_flow(va_ctx* ctx, const void* frames, int frames_are_u8, 
                 const bool narrow = sp.narrow != 0;
                 const dim3 grid_mw = narrow ? dim3((2 * sp.nsx - 1) * sp.nch, va_cdiv(nc, 2)) : grid;
                 sa.npairs = nc;
-                const bool two = sp.two != 0;
                 // pipelines of four waves: the passes share the iterations as evenly as possible, so that every pass
                 // is deep enough to end in the last wave (K > (waves - 1) x levels per wave); otherwise the forms below run
                 int mw_n = 0, mw_base = 0, mw_extra = 0;
-                if (sp.mw_nwv) {
-                    const int kmax = sp.mw_nwv * sp.mw_kh, kmin = (sp.mw_nwv - 1) * sp.mw_kh + 1;
+                if (sp.nwv) {
+                    const int kmax = sp.nwv * sp.kh, kmin = (sp.nwv - 1) * sp.kh + 1;
                     mw_n = va_cdiv(p->iters, kmax);
                     mw_base = p->iters / mw_n;
                     mw_extra = p->iters % mw_n;
@@ -1851,25 +1845,21 @@ extern "C" int va_tvl1_flow(va_ctx* ctx, const void* frames, int frames_are_u8, 
                     sa.sout = state[cur ^ 1];
                     sa.rev = launches & 1;
                     sa.narrow = narrow ? 1 : 0;
-                    launch_stream_mw(sp.mw_kh, p->fast_math != 0, grid_mw, st, sa);
+                    if (int rc = launch_stream(sp.nwv, sp.kh, p->fast_math != 0, grid_mw, st, sa)) return rc;
                     sa.narrow = 0;
                     cur ^= 1;
                     ++launches;
                 }
                 for (int it = mw_n ? p->iters : 0; it < p->iters;) {
                     const int rem = p->iters - it;
-                    const bool w2 = two && rem > kStreamKH2;  // the two-wave kernel needs its last level in the second wave
-                    sa.K = w2 ? (rem < 2 * kStreamKH2 ? rem : 2 * kStreamKH2) : (rem < kStreamK1 ? rem : kStreamK1);
+                    // the two-wave kernel needs its last level in the second wave: a shorter remainder runs in one wave
+                    const bool fb = rem > (sp.fb_nwv - 1) * sp.fb_kh;
+                    const int nwv = fb ? sp.fb_nwv : 1, kh = fb ? sp.fb_kh : kStreamK1;
+                    sa.K = rem < nwv * kh ? rem : nwv * kh;
                     sa.sin = state[cur];
                     sa.sout = state[cur ^ 1];
                     sa.rev = launches & 1;
-                    if (w2) {
-                        if (p->fast_math) launch_stream<true, true>(grid, st, sa);
-                        else launch_stream<true, false>(grid, st, sa);
-                    } else {
-                        if (p->fast_math) launch_stream<false, true>(grid, st, sa);
-                        else launch_stream<false, false>(grid, st, sa);
-                    }
+                    if (int rc = launch_stream(nwv, kh, p->fast_math != 0, grid, st, sa)) return rc;
                     cur ^= 1;
                     it += sa.K;
                     ++launches;

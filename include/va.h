@@ -434,6 +434,20 @@ int va_train_fc_backward_layer(va_ctx* ctx, int batch, int out_f, int in_f, cons
                                float* bias, float* mom_w, float* mom_b, float lr, float momentum, float* dx,
                                const float* mask, float scale, char* info, int info_len, void* stream);
 /*
+ * The STORE and ADD forms of the two entry points above: the same launches with the finishing kernels in
+ * the form va_vgg16_train_accumulate uses.  grad_w ([cout][9][cin_pad] / [out_f][in_f]) and grad_b receive the gradient
+ * (add = 0: G = g) or have it added (add != 0: G = G + g, one rounding); the weights are only read (dx), no bias, momentum
+ * buffer, lr or momentum takes part.  Everything else, scratch and info included, as above.
+ */
+int va_train_conv_backward_layer_grad(va_ctx* ctx, int kernel_opt, int batch, int hw, int cin, int cin_pad, int cout,
+                                      const float* dy, const float* x, const float* w_packed, int add, float* grad_w,
+                                      float* grad_b, float* dx, const float* mask, const float* zeros, float* slab,
+                                      float* wt, float* bpart, size_t* scratch_floats, char* info, int info_len,
+                                      void* stream);
+int va_train_fc_backward_layer_grad(va_ctx* ctx, int batch, int out_f, int in_f, const float* dz, const float* x,
+                                    const float* w, int add, float* grad_w, float* grad_b, float* dx, const float* mask,
+                                    float scale, char* info, int info_len, void* stream);
+/*
  * 2x2/2 max-pool of y NHWC [batch][hw][hw][c] into p [batch][hw/2][hw/2][c] (k_maxpool) and, when dp != NULL, its
  * backward fused with the ReLU mask of the pooled value (k_unpool): dy gets dp at the FIRST maximum of each window in
  * row-major order where p > 0, and 0 everywhere else.  hw even, c a multiple of 4.
@@ -613,6 +627,47 @@ int va_vgg16_train_step_multitask(va_vgg16* model, const void* x, int x_is_u8, c
                                   int n, int k, int n_heads, const int* head_sizes, float lr, float momentum,
                                   unsigned long long dropout_seed, void* desc, void* loss_out, void* workspace,
                                   size_t workspace_bytes, void* stream);
+/*
+ * The step split into "produce the gradient" and "apply it" (DESIGN.md S29, S30): gradient accumulation over micro-batches,
+ * torch.nn.utils.clip_grad_norm_ on the whole gradient, and a gradient to all-reduce for data-parallel training.
+ *
+ * The gradient buffer is the caller's: one flat device f32 buffer of va_vgg16_train_grad_floats(model) floats (about 135 M,
+ * 540 MB), 16-byte aligned, holding the 34 parameter tensors in the order conv 0..12 as (weight, bias), then fc 0..3 as
+ * (weight, bias), each in the layout of its parameter and momentum buffer (conv weights packed [cout][9][cin_pad], FC1 in
+ * NHWC-flatten order).  va_vgg16_train_grad_layout: offsets / counts (HOST size_t[34], in floats) of the segments; every
+ * segment starts on a multiple of 64 floats, and the storing call writes zeros into the gaps, which no norm ever reads.
+ *
+ * va_vgg16_train_accumulate: forward and backward of one micro-batch; weights and momentum buffers are left untouched.
+ *   k = 0: va_vgg16_train_step's loss on n images; k >= 1, tasks == NULL (n_heads = 0, head_sizes ignored):
+ *   va_vgg16_train_step_consensus's on n videos of k snippets; tasks != NULL: va_vgg16_train_step_multitask's.  Batch limits
+ *   (n * max(k, 1) <= 64), workspace (va_vgg16_train_workspace_bytes), the dropout hash, desc and loss_out as there.
+ *   scales: HOST f32 [max(n_heads, 1)], finite: after the loss launch the gradient at the logits is multiplied by its head's
+ *   scale on that head's columns (one launch; none when every scale is exactly 1).  A ragged micro-batch gets its share of
+ *   the full batch's mean with scale = n_micro / n_full (per head: that head's videos).  loss_out is NOT scaled.
+ *   first != 0: G = g (and zeros into the gaps); first = 0: G = G + g, one rounding per element.
+ *   Forward, data gradients, the weight-gradient slabs and every sum are the fused step's code: g has the bits of the
+ *   gradient the fused step would have applied.
+ * va_vgg16_train_apply: V = fmaf(momentum, V, c G), W = fmaf(-lr, V, W) over all 34 tensors in one launch, the fused step's
+ *   two fused multiply-adds.  clip_norm <= 0: c is absent (G is used as it is).  clip_norm > 0: the norm of G first, a float64
+ *   sum of squares in a fixed order (1024 partial sums in the workspace, one workgroup adds them; no atomics), then
+ *   c = min(1, clip_norm / (norm + 1e-6)), torch's rule, read by the update on the device: the host never waits.
+ *   norm_out: device f64 [1] or NULL (non-NULL with clip_norm <= 0: the norm is computed and reported, not used).
+ *   workspace: va_vgg16_train_apply_workspace_bytes() bytes, 8-byte aligned, needed when the norm is (the training workspace
+ *   serves); too small: VA_ERR_WORKSPACE.
+ * va_vgg16_unpack_grad: the gradient in the reference's layouts (as va_vgg16_export_state): what p.grad holds.
+ * Argument errors are VA_ERR_INVALID / VA_ERR_WORKSPACE before anything is written.
+ */
+size_t va_vgg16_train_grad_floats(const va_vgg16* model);
+int va_vgg16_train_grad_layout(const va_vgg16* model, size_t* offsets, size_t* counts);
+int va_vgg16_train_accumulate(va_vgg16* model, const void* x, int x_is_u8, const void* labels, const void* tasks, int n,
+                              int k, int n_heads, const int* head_sizes, const float* scales, int first,
+                              unsigned long long dropout_seed, void* desc, void* loss_out, void* grad, size_t grad_floats,
+                              void* workspace, size_t workspace_bytes, void* stream);
+size_t va_vgg16_train_apply_workspace_bytes(void);
+int va_vgg16_train_apply(va_vgg16* model, const void* grad, size_t grad_floats, float lr, float momentum, float clip_norm,
+                         void* norm_out, void* workspace, size_t workspace_bytes, void* stream);
+int va_vgg16_unpack_grad(va_vgg16* model, const void* grad, void* const* conv_w, void* const* conv_b, void* const* fc_w,
+                         void* const* fc_b, void* stream);
 /*
  * Checkpoints (Sheet03/spatialModel.py:234-260, Sheet03/utils.py:29-35): copy the parameters (which = 0) or the
  * momentum buffers (which = 1) out to / in from device tensors in the reference's layouts -- conv OIHW

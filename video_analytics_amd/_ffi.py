@@ -33,6 +33,8 @@ EXPORTS = [
     "va_train_conv_backward_layer", "va_train_fc_backward_layer", "va_train_pool_layer", "va_train_loss", "va_train_dropout",
     "va_vgg16_train_step_multitask", "va_train_loss_multitask",
     "va_linear_svm_fit_workspace_bytes", "va_linear_svm_fit", "va_linear_svm_fit_cg_steps",
+    "va_vgg16_train_grad_floats", "va_vgg16_train_grad_layout", "va_vgg16_train_accumulate", "va_vgg16_train_apply_workspace_bytes",
+    "va_vgg16_train_apply", "va_vgg16_unpack_grad", "va_train_conv_backward_layer_grad", "va_train_fc_backward_layer_grad",
 ]
 
 
@@ -210,6 +212,24 @@ def lib():
     L.va_linear_svm_fit.restype = ci
     L.va_linear_svm_fit_cg_steps.argtypes = [vp, ci, ci, ci, vp, sz, vp, vp]
     L.va_linear_svm_fit_cg_steps.restype = ci
+    psz = ctypes.POINTER(sz)
+    L.va_vgg16_train_grad_floats.argtypes = [vp]
+    L.va_vgg16_train_grad_floats.restype = sz
+    L.va_vgg16_train_grad_layout.argtypes = [vp, psz, psz]
+    L.va_vgg16_train_grad_layout.restype = ci
+    L.va_vgg16_train_accumulate.argtypes = [vp, vp, ci, vp, vp, ci, ci, ci, pi, fpp, ci, ctypes.c_ulonglong, vp, vp, vp, sz, vp, sz, vp]
+    L.va_vgg16_train_accumulate.restype = ci
+    L.va_vgg16_train_apply_workspace_bytes.argtypes = []
+    L.va_vgg16_train_apply_workspace_bytes.restype = sz
+    L.va_vgg16_train_apply.argtypes = [vp, vp, sz, cf, cf, cf, vp, vp, sz, vp]
+    L.va_vgg16_train_apply.restype = ci
+    L.va_vgg16_unpack_grad.argtypes = [vp, vp, pp, pp, pp, pp, vp]
+    L.va_vgg16_unpack_grad.restype = ci
+    L.va_train_conv_backward_layer_grad.argtypes = [vp, ci, ci, ci, ci, ci, ci, vp, vp, vp, ci, vp, vp, vp, vp, vp, vp, vp, vp,
+                                                    psz, ctypes.c_char_p, ci, vp]
+    L.va_train_conv_backward_layer_grad.restype = ci
+    L.va_train_fc_backward_layer_grad.argtypes = [vp, ci, ci, ci, vp, vp, vp, ci, vp, vp, vp, vp, cf, ctypes.c_char_p, ci, vp]
+    L.va_train_fc_backward_layer_grad.restype = ci
     _lib = L
     return L
 

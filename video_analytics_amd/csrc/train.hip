@@ -184,6 +184,27 @@ __global__ void k_ce_consensus_fwd_bwd(const float* __restrict__ logits, const l
     }
 }
 
+// ---------------------------------------------------------------- the finishing statement -----
+
+// What the four kernels that complete a gradient element g do with it.  UPD_SGD: the fused momentum-SGD
+// update of va_vgg16_train_step, V = mu*V + g; W -= lr*V.  UPD_STORE / UPD_ADD (va_vgg16_train_accumulate): `v` is the
+// element's place in the caller's gradient buffer, G = g or G = G + g (one rounding); `w` is not touched.
+enum { UPD_SGD = 0, UPD_STORE = 1, UPD_ADD = 2 };
+
+template <int MODE>
+__device__ __forceinline__ void finish_grad(float g, size_t idx, float* __restrict__ w, float* __restrict__ v, float lr, float mu)
+{
+    if (MODE == UPD_SGD) {
+        const float nv = fmaf(mu, v[idx], g);
+        v[idx] = nv;
+        w[idx] = fmaf(-lr, nv, w[idx]);
+    } else if (MODE == UPD_STORE) {
+        v[idx] = g;
+    } else {
+        v[idx] = v[idx] + g;
+    }
+}
+
 // ---------------------------------------------------------------- classifier backward ----------
 
 // dX[b][i] = sum_o dZ[b][o] * W[o][i], then * scale where mask[b][i] > 0, else 0 (mask may be NULL).
@@ -239,8 +260,8 @@ __global__ void __launch_bounds__(256) k_fc_dx(const float* __restrict__ dz, con
 }
 
 // g[o][i] = sum_b dZ[b][o] * X[b][i] (b ascending); V = mu*V + g; W -= lr*V.  One thread per column i keeps X[:, i]
-// in registers and walks a slice of the output rows; blockIdx.y selects the slice.
-template <int BMAX>
+// in registers and walks a slice of the output rows; blockIdx.y selects the slice.  MODE: finish_grad.
+template <int BMAX, int MODE>
 __global__ void __launch_bounds__(256) k_fc_wgrad_sgd(const float* __restrict__ dz, const float* __restrict__ x, float* __restrict__ w,
                                                       float* __restrict__ v, int B, int O, int I, int orows, float lr, float mu)
 {
@@ -265,23 +286,19 @@ __global__ void __launch_bounds__(256) k_fc_wgrad_sgd(const float* __restrict__ 
 #pragma unroll
             for (int j = 0; j < 4; ++j) g = fmaf(d[j], xr[4 * b4 + j], g);
         }
-        const size_t idx = (size_t)(o0 + oo) * I + i;
-        const float nv = fmaf(mu, v[idx], g);
-        v[idx] = nv;
-        w[idx] = fmaf(-lr, nv, w[idx]);
+        finish_grad<MODE>(g, (size_t)(o0 + oo) * I + i, w, v, lr, mu);
     }
 }
 
-// bias: g[o] = sum_b dZ[b][o]; momentum-SGD
+// bias: g[o] = sum_b dZ[b][o]; momentum-SGD (MODE: finish_grad)
+template <int MODE>
 __global__ void k_fc_bgrad_sgd(const float* __restrict__ dz, float* __restrict__ bias, float* __restrict__ vb, int B, int O, float lr, float mu)
 {
     const int o = blockIdx.x * blockDim.x + threadIdx.x;
     if (o >= O) return;
     float g = 0.0f;
     for (int b = 0; b < B; ++b) g += dz[(size_t)b * O + o];
-    const float nv = fmaf(mu, vb[o], g);
-    vb[o] = nv;
-    bias[o] = fmaf(-lr, nv, bias[o]);
+    finish_grad<MODE>(g, (size_t)o, bias, vb, lr, mu);
 }
 
 // ---------------------------------------------------------------- convolution backward ---------
@@ -421,7 +438,8 @@ __global__ void __launch_bounds__(WM * WN * 64) k_conv_wgrad(WgradArgs a)
 // A block = 32 weights x 8 groups of consecutive slabs: a thread adds its group's slabs (four interleaved partial sums, so
 // that four loads are in flight; combined as (a0 + a1) + (a2 + a3)), the eight group sums are added ascending.  One thread
 // per weight walking all S slabs (round 1) was a chain of S dependent-latency loads on 9 216 ... 36 864 threads: 804 us
-// for the first layer's 256 slabs, 267 us for conv1_2's.
+// for the first layer's 256 slabs, 267 us for conv1_2's.  MODE: finish_grad.
+template <int MODE>
 __global__ void __launch_bounds__(256) k_wgrad_reduce_sgd(const float* __restrict__ slab, float* __restrict__ w, float* __restrict__ v,
                                                           int M, int N, int Mpad, int Npad, int S, float lr, float mu)
 {
@@ -456,9 +474,7 @@ __global__ void __launch_bounds__(256) k_wgrad_reduce_sgd(const float* __restric
         float g = part[0][o];
 #pragma unroll
         for (int k = 1; k < 8; ++k) g += part[k][o];
-        const float nv = fmaf(mu, v[idx], g);
-        v[idx] = nv;
-        w[idx] = fmaf(-lr, nv, w[idx]);
+        finish_grad<MODE>(g, idx, w, v, lr, mu);
     }
 }
 
@@ -495,7 +511,8 @@ __global__ void __launch_bounds__(256) k_conv_bgrad_partial(const float* __restr
     }
 }
 
-// pass 2 + momentum SGD: 64 channels per workgroup, four 64-thread groups each add a quarter of the partials
+// pass 2 + momentum SGD (MODE: finish_grad): 64 channels per workgroup, four 64-thread groups each add a quarter of the partials
+template <int MODE>
 __global__ void __launch_bounds__(256) k_conv_bgrad_sgd(const float* __restrict__ part, int nblk, float* __restrict__ bias, float* __restrict__ vb,
                                                         int Cout, float lr, float mu)
 {
@@ -509,9 +526,7 @@ __global__ void __launch_bounds__(256) k_conv_bgrad_sgd(const float* __restrict_
     __syncthreads();
     if (grp != 0 || c >= Cout) return;
     g = ((g + red[0][col]) + red[1][col]) + red[2][col];
-    const float nv = fmaf(mu, vb[c], g);
-    vb[c] = nv;
-    bias[c] = fmaf(-lr, nv, bias[c]);
+    finish_grad<MODE>(g, (size_t)c, bias, vb, lr, mu);
 }
 
 // ---------------------------------------------------------------- export / import --------------
@@ -651,6 +666,14 @@ int fc_backward_dispatch(int B, F&& f)
     return f(std::integral_constant<int, 64>());
 }
 
+template <typename F>
+int update_dispatch(int mode, F&& f)
+{
+    if (mode == UPD_STORE) return f(std::integral_constant<int, UPD_STORE>());
+    if (mode == UPD_ADD) return f(std::integral_constant<int, UPD_ADD>());
+    return f(std::integral_constant<int, UPD_SGD>());
+}
+
 // ---- the per-layer bodies of the step: train_step and the testing entry points (va_train_*) call these ----
 
 void pool_forward(const float* y, float* p, int B, int hw, int C, hipStream_t st)
@@ -689,22 +712,26 @@ int loss_layer(const float* logits, const long long* labels, int B, int segments
     return VA_OK;
 }
 
-// dx (with mask and scale), then the weight and bias updates in place; *inst (may be NULL): the batch instantiation, 32 or 64
+// dx (with mask and scale), then the weight and bias updates in place; *inst (may be NULL): the batch instantiation, 32 or 64.
+// mode UPD_STORE / UPD_ADD: vw / vb are the layer's places in the gradient buffer, w is only read (dx), bias not at all.
 int fc_backward_layer(int B, int O, int I, const float* dz, const float* x, float* w, float* bias, float* vw, float* vb, float* dx,
-                      const float* mask, float scale, float lr, float mu, hipStream_t st, int* inst)
+                      const float* mask, float scale, float lr, float mu, hipStream_t st, int* inst, int mode = UPD_SGD)
 {
-    int rc = fc_backward_dispatch(B, [&](auto BM) {
-        constexpr int bm = decltype(BM)::value;
-        if (inst) *inst = bm;
-        k_fc_dx<bm><<<va_cdiv(I, 64), 256, 0, st>>>(dz, w, dx, B, O, I, mask, scale);
-        const int orows = 16;
-        k_fc_wgrad_sgd<bm><<<dim3(va_cdiv(I, 256), va_cdiv(O, orows)), 256, (size_t)orows * bm * sizeof(float), st>>>(
-            dz, x, w, vw, B, O, I, orows, lr, mu);
+    return update_dispatch(mode, [&](auto MD) {
+        constexpr int md = decltype(MD)::value;
+        int rc = fc_backward_dispatch(B, [&](auto BM) {
+            constexpr int bm = decltype(BM)::value;
+            if (inst) *inst = bm;
+            k_fc_dx<bm><<<va_cdiv(I, 64), 256, 0, st>>>(dz, w, dx, B, O, I, mask, scale);
+            const int orows = 16;
+            k_fc_wgrad_sgd<bm, md><<<dim3(va_cdiv(I, 256), va_cdiv(O, orows)), 256, (size_t)orows * bm * sizeof(float), st>>>(
+                dz, x, w, vw, B, O, I, orows, lr, mu);
+            return VA_OK;
+        });
+        if (rc) return rc;
+        k_fc_bgrad_sgd<md><<<va_cdiv(O, 256), 256, 0, st>>>(dz, bias, vb, B, O, lr, mu);
         return VA_OK;
     });
-    if (rc) return rc;
-    k_fc_bgrad_sgd<<<va_cdiv(O, 256), 256, 0, st>>>(dz, bias, vb, B, O, lr, mu);
-    return VA_OK;
 }
 
 // bias gradient, pass 1: pixels per block and the number of blocks (at most kBgradBlocks)
@@ -713,10 +740,11 @@ int bgrad_blocks(long P) { return (int)((P + bgrad_chunk(P) - 1) / bgrad_chunk(P
 
 // Backward of one conv layer.  dx != NULL: the data gradient first (it needs this step's weights): k_pack_dgrad_w into wt,
 // then a linear 3x3 convolution of dy through the forward dispatch, zeroed where mask <= 0 (mask may be NULL).  Then the
-// weight and bias gradients with the momentum-SGD update in place (dy stays intact).
+// weight and bias gradients with the momentum-SGD update in place (dy stays intact).  mode UPD_STORE / UPD_ADD: vw / vb are
+// the layer's places in the gradient buffer, w is only read (dx), bias not at all.
 int conv_backward_layer(int B, int hw, int cin, int cin_pad, int cout, const float* dy, const float* x, float* w, float* bias, float* vw,
                         float* vb, float* dx, const float* mask, const float* zeros, int f32_conv, float* wt, float* slab, float* bpart,
-                        float lr, float mu, hipStream_t st, const char** dgrad_launched = nullptr)
+                        float lr, float mu, hipStream_t st, const char** dgrad_launched = nullptr, int mode = UPD_SGD)
 {
     if (dx) {
         const size_t nwt = (size_t)cin * 9 * cout;
@@ -740,12 +768,15 @@ int conv_backward_layer(int B, int hw, int cin, int cin_pad, int cout, const flo
     if (wp.BM == 64) k_conv_wgrad<1, 3><<<dim3(wp.Npad / 192, wp.Mpad / 64, wp.S), 192, 0, st>>>(a);
     else k_conv_wgrad<2, 2><<<dim3(wp.Npad / 128, wp.Mpad / 128, wp.S), 256, 0, st>>>(a);
     const size_t nw = (size_t)cout * a.N;
-    k_wgrad_reduce_sgd<<<(unsigned)((nw + 31) / 32), 256, 0, st>>>(slab, w, vw, cout, a.N, wp.Mpad, wp.Npad, wp.S, lr, mu);
     const int nblk = bgrad_blocks(a.P);
-    k_conv_bgrad_partial<<<nblk, 256, 0, st>>>(dy, bpart, a.P, cout, bgrad_chunk(a.P));
-    k_conv_bgrad_sgd<<<va_cdiv(cout, 64), 256, 0, st>>>(bpart, nblk, bias, vb, cout, lr, mu);
-    VA_LAUNCH_CHECK();
-    return VA_OK;
+    return update_dispatch(mode, [&](auto MD) {
+        constexpr int md = decltype(MD)::value;
+        k_wgrad_reduce_sgd<md><<<(unsigned)((nw + 31) / 32), 256, 0, st>>>(slab, w, vw, cout, a.N, wp.Mpad, wp.Npad, wp.S, lr, mu);
+        k_conv_bgrad_partial<<<nblk, 256, 0, st>>>(dy, bpart, a.P, cout, bgrad_chunk(a.P));
+        k_conv_bgrad_sgd<md><<<va_cdiv(cout, 64), 256, 0, st>>>(bpart, nblk, bias, vb, cout, lr, mu);
+        VA_LAUNCH_CHECK();
+        return VA_OK;
+    });
 }
 
 }  // namespace
@@ -786,9 +817,18 @@ extern "C" size_t va_vgg16_train_workspace_bytes(const va_vgg16* m, int batch)
 // segments = K >= 1: va_vgg16_train_step_consensus, `batch` = videos * K images, video-major, and the loss of the videos'
 // consensus (k_ce_consensus_fwd_bwd); mt != NULL: va_vgg16_train_step_multitask, the consensus loss of every head on its own
 // videos and columns (k_ce_multitask_fwd_bwd, loss_out f32 [2 + 2H]).  Everything but that one launch is the same code.
+// acc != NULL: va_vgg16_train_accumulate -- the same forward and backward with the gradient stored in, or
+// added to, the caller's buffer (va_grad_layout_of) by the finishing kernels' UPD_STORE / UPD_ADD forms; weights and momentum
+// buffers are only read, lr and momentum are not used.
+struct Accum {
+    float* grad;
+    int first;            // != 0: G = g (and zeros into the alignment gaps), else G = G + g
+    const float* scales;  // HOST, max(heads, 1) entries: dlogits *= scales[head of the column] after the loss launch
+};
+
 static int train_step(const char* who, va_vgg16* m, const void* x, int x_is_u8, const void* labels, int batch, int segments, float lr,
                       float momentum, unsigned long long dropout_seed, void* desc, void* loss_out, void* workspace,
-                      size_t workspace_bytes, void* stream, const MultiTask* mt = nullptr)
+                      size_t workspace_bytes, void* stream, const MultiTask* mt = nullptr, const Accum* acc = nullptr)
 {
     VA_CHECK_ARG(m != nullptr && x != nullptr && labels != nullptr && loss_out != nullptr, "%s: NULL argument", who);
     VA_USE_DEVICE(m->ctx);
@@ -803,6 +843,16 @@ static int train_step(const char* who, va_vgg16* m, const void* x, int x_is_u8, 
     }
     hipStream_t st = (hipStream_t)stream;
     const int B = batch;
+    const int mode = !acc ? UPD_SGD : acc->first ? UPD_STORE : UPD_ADD;
+    va_grad_layout GL{};
+    if (acc) {
+        GL = va_grad_layout_of(m);
+        if (acc->first)  // the gaps between the segments hold zeros: a sum across ranks or a norm over the whole buffer sees nothing
+            for (int s = 0; s < 34; ++s) {
+                const size_t end = s < 33 ? GL.off[s + 1] : GL.total, gap = end - (GL.off[s] + GL.cnt[s]);
+                if (gap) VA_HIP(hipMemsetAsync(acc->grad + GL.off[s] + GL.cnt[s], 0, gap * sizeof(float), st));
+            }
+    }
     char* ws = (char*)workspace;
     auto F = [&](size_t off) { return (float*)(ws + off); };
     float* slab = F(T.slab);
@@ -829,6 +879,12 @@ static int train_step(const char* who, va_vgg16* m, const void* x, int x_is_u8, 
     }
     if (desc) VA_HIP(hipMemcpyAsync(desc, F(T.a_d[2]), (size_t)B * m->desc_dim * sizeof(float), hipMemcpyDeviceToDevice, st));
     if (int rc = loss_layer(F(T.logits), (const long long*)labels, B, segments, m->n_classes, F(T.dlogits), (float*)loss_out, st, mt)) return rc;
+    if (acc) {  // a micro-batch's share of the full batch's mean: every head's columns times its scale (nothing when all are 1)
+        va_heads one{};
+        one.n = 1;
+        for (int t = 1; t <= VA_MAX_HEADS; ++t) one.off[t] = m->n_classes;
+        if (int rc = va_scale_dlogits(F(T.dlogits), B, mt ? mt->heads : one, acc->scales, st)) return rc;
+    }
     VA_LAUNCH_CHECK();
 
     // ---------------- classifier backward + update ----------------
@@ -839,8 +895,9 @@ static int train_step(const char* who, va_vgg16* m, const void* x, int x_is_u8, 
     for (int l = 3; l >= 0; --l) {
         const int O = m->fc_out[l], I = m->fc_in[l];
         const float* mask = l > 0 ? fin[l] : nullptr;  // fin[l] = post-dropout activation of layer l-1
-        if (int rc = fc_backward_layer(B, O, I, dz[l], fin[l], m->fcw[l], m->fcb[l], m->fc_mom_w[l], m->fc_mom_b[l], dxo[l], mask, 2.0f, lr,
-                                       momentum, st, nullptr))
+        float* vw = acc ? acc->grad + GL.off[26 + 2 * l] : m->fc_mom_w[l];
+        float* vb = acc ? acc->grad + GL.off[27 + 2 * l] : m->fc_mom_b[l];
+        if (int rc = fc_backward_layer(B, O, I, dz[l], fin[l], m->fcw[l], m->fcb[l], vw, vb, dxo[l], mask, 2.0f, lr, momentum, st, nullptr, mode))
             return rc;
     }
     VA_LAUNCH_CHECK();
@@ -862,8 +919,10 @@ static int train_step(const char* who, va_vgg16* m, const void* x, int x_is_u8, 
         // data gradient (not for the first layer) into the other gradient buffer, then the weight and bias updates
         float* g = i > 0 ? F(T.g[1 - cur]) : nullptr;
         const float* mask = i > 0 && !m->conv[i - 1].pool ? F(T.y[i - 1]) : nullptr;
-        if (int rc = conv_backward_layer(B, L.hw, L.cin, L.cin_pad, L.cout, dyr, lin, L.wp, L.bias, L.mom_w, L.mom_b, g, mask, m->zeros_f32,
-                                         m->f32_conv, F(T.wt), slab, F(T.bpart), lr, momentum, st))
+        float* vw = acc ? acc->grad + GL.off[2 * i] : L.mom_w;
+        float* vb = acc ? acc->grad + GL.off[2 * i + 1] : L.mom_b;
+        if (int rc = conv_backward_layer(B, L.hw, L.cin, L.cin_pad, L.cout, dyr, lin, L.wp, L.bias, vw, vb, g, mask, m->zeros_f32, m->f32_conv,
+                                         F(T.wt), slab, F(T.bpart), lr, momentum, st, nullptr, mode))
             return rc;
         if (i > 0) dout = g;
         if (i > 0) cur = 1 - cur;
@@ -905,6 +964,71 @@ extern "C" int va_vgg16_train_step_multitask(va_vgg16* m, const void* x, int x_i
     return train_step(who, m, x, x_is_u8, labels, n * k, k, lr, momentum, dropout_seed, desc, loss_out, workspace, workspace_bytes, stream, &mt);
 }
 
+extern "C" size_t va_vgg16_train_grad_floats(const va_vgg16* m)
+{
+    if (!m || m->dtype != VA_DTYPE_F32) return 0;
+    return va_grad_layout_of(m).total;
+}
+
+extern "C" int va_vgg16_train_grad_layout(const va_vgg16* m, size_t* offsets, size_t* counts)
+{
+    VA_CHECK_ARG(m != nullptr && offsets != nullptr && counts != nullptr, "va_vgg16_train_grad_layout: NULL argument");
+    VA_CHECK_ARG(m->dtype == VA_DTYPE_F32, "va_vgg16_train_grad_layout: training is fp32 only");
+    const va_grad_layout GL = va_grad_layout_of(m);
+    for (int s = 0; s < 34; ++s) {
+        offsets[s] = GL.off[s];
+        counts[s] = GL.cnt[s];
+    }
+    return VA_OK;
+}
+
+extern "C" int va_vgg16_train_accumulate(va_vgg16* m, const void* x, int x_is_u8, const void* labels, const void* tasks, int n, int k,
+                                         int n_heads, const int* head_sizes, const float* scales, int first,
+                                         unsigned long long dropout_seed, void* desc, void* loss_out, void* grad, size_t grad_floats,
+                                         void* workspace, size_t workspace_bytes, void* stream)
+{
+    const char* who = "va_vgg16_train_accumulate";
+    VA_CHECK_ARG(m != nullptr && grad != nullptr && scales != nullptr, "%s: NULL argument", who);
+    VA_CHECK_ARG(m->dtype == VA_DTYPE_F32, "%s: training is fp32 only", who);
+    VA_CHECK_ARG(n >= 1 && k >= 0 && (long long)n * (k > 0 ? k : 1) <= 64, "%s: %d videos x %d snippets out of range (n * max(k, 1) in [1,64])",
+                 who, n, k);
+    VA_CHECK_ARG(tasks == nullptr || k >= 1, "%s: the multi-task loss needs k >= 1", who);
+    VA_CHECK_ARG(((uintptr_t)grad & 15) == 0, "%s: grad must be 16-byte aligned", who);
+    const size_t need = va_grad_layout_of(m).total;
+    VA_CHECK_ARG(grad_floats >= need, "%s: gradient buffer of %zu floats needed (va_vgg16_train_grad_floats), %zu given", who, need, grad_floats);
+    MultiTask mt{(const int*)tasks, {}};
+    if (tasks) {
+        if (int rc = va_heads_from_sizes(who, n_heads, head_sizes, m->n_classes, &mt.heads)) return rc;
+    } else {
+        VA_CHECK_ARG(n_heads == 0, "%s: %d heads without tasks", who, n_heads);
+    }
+    for (int t = 0; t < (tasks ? n_heads : 1); ++t)
+        VA_CHECK_ARG(scales[t] - scales[t] == 0.0f, "%s: scale %d is not finite", who, t);
+    const Accum acc{(float*)grad, first, scales};
+    return train_step(who, m, x, x_is_u8, labels, n * (k > 0 ? k : 1), k, 0.0f, 0.0f, dropout_seed, desc, loss_out, workspace, workspace_bytes,
+                      stream, tasks ? &mt : nullptr, &acc);
+}
+
+// src: the 34 tensors in the packed layouts, conv 0..12 as (weight, bias), then fc 0..3 as (weight, bias) -> the reference's layouts
+static int unpack_tensors(const va_vgg16* m, const float* const* src, void* const* conv_w, void* const* conv_b, void* const* fc_w,
+                          void* const* fc_b, hipStream_t st)
+{
+    for (int i = 0; i < 13; ++i) {
+        const ConvLayer& L = m->conv[i];
+        const size_t n = (size_t)L.cout * L.cin * 9;
+        k_unpack_conv_w<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(src[2 * i], (float*)conv_w[i], L.cout, L.cin, L.cin_pad);
+        VA_HIP(hipMemcpyAsync(conv_b[i], src[2 * i + 1], L.cout * sizeof(float), hipMemcpyDeviceToDevice, st));
+    }
+    for (int i = 0; i < 4; ++i) {
+        const size_t n = (size_t)m->fc_out[i] * m->fc_in[i];
+        if (i == 0) k_unpack_fc1<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(src[26], (float*)fc_w[0], m->fc_out[0], 512, 49);
+        else VA_HIP(hipMemcpyAsync(fc_w[i], src[26 + 2 * i], n * sizeof(float), hipMemcpyDeviceToDevice, st));
+        VA_HIP(hipMemcpyAsync(fc_b[i], src[27 + 2 * i], m->fc_out[i] * sizeof(float), hipMemcpyDeviceToDevice, st));
+    }
+    VA_LAUNCH_CHECK();
+    return VA_OK;
+}
+
 // which = 0: parameters, 1: momentum buffers.  Destination tensors in the reference's layouts (conv OIHW
 // [cout][cin][3][3], fc [out][in] with FC1's input CHW-major): what model.state_dict() / optimizer.state_dict() hold.
 extern "C" int va_vgg16_export_state(va_vgg16* m, int which, void* const* conv_w, void* const* conv_b, void* const* fc_w,
@@ -914,22 +1038,29 @@ extern "C" int va_vgg16_export_state(va_vgg16* m, int which, void* const* conv_w
     VA_USE_DEVICE(m->ctx);
     VA_CHECK_ARG(m->dtype == VA_DTYPE_F32, "va_vgg16_export_state: fp32 models only");
     VA_CHECK_ARG(which == 0 || (which == 1 && m->conv[0].mom_w), "va_vgg16_export_state: which must be 0, or 1 after va_vgg16_train_init");
-    hipStream_t st = (hipStream_t)stream;
+    const float* src[34];
     for (int i = 0; i < 13; ++i) {
-        const ConvLayer& L = m->conv[i];
-        const size_t n = (size_t)L.cout * L.cin * 9;
-        k_unpack_conv_w<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(which ? L.mom_w : L.wp, (float*)conv_w[i], L.cout, L.cin, L.cin_pad);
-        VA_HIP(hipMemcpyAsync(conv_b[i], which ? L.mom_b : L.bias, L.cout * sizeof(float), hipMemcpyDeviceToDevice, st));
+        src[2 * i] = which ? m->conv[i].mom_w : m->conv[i].wp;
+        src[2 * i + 1] = which ? m->conv[i].mom_b : m->conv[i].bias;
     }
     for (int i = 0; i < 4; ++i) {
-        const size_t n = (size_t)m->fc_out[i] * m->fc_in[i];
-        const float* src = which ? m->fc_mom_w[i] : m->fcw[i];
-        if (i == 0) k_unpack_fc1<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(src, (float*)fc_w[0], m->fc_out[0], 512, 49);
-        else VA_HIP(hipMemcpyAsync(fc_w[i], src, n * sizeof(float), hipMemcpyDeviceToDevice, st));
-        VA_HIP(hipMemcpyAsync(fc_b[i], which ? m->fc_mom_b[i] : m->fcb[i], m->fc_out[i] * sizeof(float), hipMemcpyDeviceToDevice, st));
+        src[26 + 2 * i] = which ? m->fc_mom_w[i] : m->fcw[i];
+        src[27 + 2 * i] = which ? m->fc_mom_b[i] : m->fcb[i];
     }
-    VA_LAUNCH_CHECK();
-    return VA_OK;
+    return unpack_tensors(m, src, conv_w, conv_b, fc_w, fc_b, (hipStream_t)stream);
+}
+
+// The gradient buffer of va_vgg16_train_accumulate in the reference's layouts: what p.grad holds after loss.backward().
+extern "C" int va_vgg16_unpack_grad(va_vgg16* m, const void* grad, void* const* conv_w, void* const* conv_b, void* const* fc_w,
+                                    void* const* fc_b, void* stream)
+{
+    VA_CHECK_ARG(m != nullptr && grad != nullptr && conv_w && conv_b && fc_w && fc_b, "va_vgg16_unpack_grad: NULL argument");
+    VA_USE_DEVICE(m->ctx);
+    VA_CHECK_ARG(m->dtype == VA_DTYPE_F32, "va_vgg16_unpack_grad: fp32 models only");
+    const va_grad_layout GL = va_grad_layout_of(m);
+    const float* src[34];
+    for (int s = 0; s < 34; ++s) src[s] = (const float*)grad + GL.off[s];
+    return unpack_tensors(m, src, conv_w, conv_b, fc_w, fc_b, (hipStream_t)stream);
 }
 
 // The inverse: load parameters (which = 0) or momentum buffers (which = 1) from tensors in the reference's layouts.
@@ -987,12 +1118,12 @@ static uintptr_t va_or_ptrs(std::initializer_list<const void*> ps)
     return v;
 }
 
-extern "C" int va_train_conv_backward_layer(va_ctx* ctx, int kernel_opt, int batch, int hw, int cin, int cin_pad, int cout, const float* dy,
-                                            const float* x, float* w_packed, float* bias, float* mom_w, float* mom_b, float lr,
-                                            float momentum, float* dx, const float* mask, const float* zeros, float* slab, float* wt,
-                                            float* bpart, size_t* scratch_floats, char* info, int info_len, void* stream)
+// mode UPD_SGD: va_train_conv_backward_layer; UPD_STORE / UPD_ADD: va_train_conv_backward_layer_grad (bias = w_packed, unused)
+static int conv_backward_entry(const char* who, int mode, va_ctx* ctx, int kernel_opt, int batch, int hw, int cin, int cin_pad, int cout,
+                               const float* dy, const float* x, float* w_packed, float* bias, float* mom_w, float* mom_b, float lr,
+                               float momentum, float* dx, const float* mask, const float* zeros, float* slab, float* wt, float* bpart,
+                               size_t* scratch_floats, char* info, int info_len, void* stream)
 {
-    const char* who = "va_train_conv_backward_layer";
     VA_CHECK_ARG(ctx != nullptr, "%s: ctx is NULL", who);
     VA_USE_DEVICE(ctx);
     if (info && info_len > 0) info[0] = 0;
@@ -1029,17 +1160,35 @@ extern "C" int va_train_conv_backward_layer(va_ctx* ctx, int kernel_opt, int bat
     }
     const char* dname = nullptr;
     if (int rc = conv_backward_layer(batch, hw, cin, cin_pad, cout, dy, x, w_packed, bias, mom_w, mom_b, dx, mask, zeros, kernel_opt, wt, slab,
-                                     bpart, lr, momentum, (hipStream_t)stream, &dname))
+                                     bpart, lr, momentum, (hipStream_t)stream, &dname, mode))
         return rc;
     if (info && info_len > 0) snprintf(info, (size_t)info_len, "%s dgrad=%s", plan, dname ? dname : "none");
     return VA_OK;
 }
 
-extern "C" int va_train_fc_backward_layer(va_ctx* ctx, int batch, int out_f, int in_f, const float* dz, const float* x, float* w, float* bias,
-                                          float* mom_w, float* mom_b, float lr, float momentum, float* dx, const float* mask, float scale,
-                                          char* info, int info_len, void* stream)
+extern "C" int va_train_conv_backward_layer(va_ctx* ctx, int kernel_opt, int batch, int hw, int cin, int cin_pad, int cout, const float* dy,
+                                            const float* x, float* w_packed, float* bias, float* mom_w, float* mom_b, float lr,
+                                            float momentum, float* dx, const float* mask, const float* zeros, float* slab, float* wt,
+                                            float* bpart, size_t* scratch_floats, char* info, int info_len, void* stream)
 {
-    const char* who = "va_train_fc_backward_layer";
+    return conv_backward_entry("va_train_conv_backward_layer", UPD_SGD, ctx, kernel_opt, batch, hw, cin, cin_pad, cout, dy, x, w_packed, bias,
+                               mom_w, mom_b, lr, momentum, dx, mask, zeros, slab, wt, bpart, scratch_floats, info, info_len, stream);
+}
+
+extern "C" int va_train_conv_backward_layer_grad(va_ctx* ctx, int kernel_opt, int batch, int hw, int cin, int cin_pad, int cout,
+                                                 const float* dy, const float* x, const float* w_packed, int add, float* grad_w,
+                                                 float* grad_b, float* dx, const float* mask, const float* zeros, float* slab, float* wt,
+                                                 float* bpart, size_t* scratch_floats, char* info, int info_len, void* stream)
+{
+    float* w = const_cast<float*>(w_packed);  // UPD_STORE / UPD_ADD only read it (k_pack_dgrad_w)
+    return conv_backward_entry("va_train_conv_backward_layer_grad", add ? UPD_ADD : UPD_STORE, ctx, kernel_opt, batch, hw, cin, cin_pad, cout, dy,
+                               x, w, w, grad_w, grad_b, 0.0f, 0.0f, dx, mask, zeros, slab, wt, bpart, scratch_floats, info, info_len, stream);
+}
+
+static int fc_backward_entry(const char* who, int mode, va_ctx* ctx, int batch, int out_f, int in_f, const float* dz, const float* x, float* w,
+                             float* bias, float* mom_w, float* mom_b, float lr, float momentum, float* dx, const float* mask, float scale,
+                             char* info, int info_len, void* stream)
+{
     VA_CHECK_ARG(ctx != nullptr, "%s: ctx is NULL", who);
     VA_USE_DEVICE(ctx);
     if (info && info_len > 0) info[0] = 0;
@@ -1049,11 +1198,28 @@ extern "C" int va_train_fc_backward_layer(va_ctx* ctx, int batch, int out_f, int
     VA_CHECK_ARG(dz && x && w && bias && mom_w && mom_b && dx, "%s: NULL argument", who);
     VA_CHECK_ARG(VA_ALIGNED16(dz, x, w, bias, mom_w, mom_b, dx, mask), "%s: every pointer must be 16-byte aligned", who);
     int inst = 0;
-    if (int rc = fc_backward_layer(batch, out_f, in_f, dz, x, w, bias, mom_w, mom_b, dx, mask, scale, lr, momentum, (hipStream_t)stream, &inst))
+    if (int rc = fc_backward_layer(batch, out_f, in_f, dz, x, w, bias, mom_w, mom_b, dx, mask, scale, lr, momentum, (hipStream_t)stream, &inst, mode))
         return rc;
     VA_LAUNCH_CHECK();
     if (info && info_len > 0) snprintf(info, (size_t)info_len, "k_fc_dx<%d>", inst);
     return VA_OK;
+}
+
+extern "C" int va_train_fc_backward_layer(va_ctx* ctx, int batch, int out_f, int in_f, const float* dz, const float* x, float* w, float* bias,
+                                          float* mom_w, float* mom_b, float lr, float momentum, float* dx, const float* mask, float scale,
+                                          char* info, int info_len, void* stream)
+{
+    return fc_backward_entry("va_train_fc_backward_layer", UPD_SGD, ctx, batch, out_f, in_f, dz, x, w, bias, mom_w, mom_b, lr, momentum, dx, mask,
+                             scale, info, info_len, stream);
+}
+
+extern "C" int va_train_fc_backward_layer_grad(va_ctx* ctx, int batch, int out_f, int in_f, const float* dz, const float* x, const float* w,
+                                               int add, float* grad_w, float* grad_b, float* dx, const float* mask, float scale, char* info,
+                                               int info_len, void* stream)
+{
+    float* wr = const_cast<float*>(w);  // UPD_STORE / UPD_ADD only read it (k_fc_dx)
+    return fc_backward_entry("va_train_fc_backward_layer_grad", add ? UPD_ADD : UPD_STORE, ctx, batch, out_f, in_f, dz, x, wr, wr, grad_w, grad_b,
+                             0.0f, 0.0f, dx, mask, scale, info, info_len, stream);
 }
 
 extern "C" int va_train_pool_layer(va_ctx* ctx, int batch, int hw, int c, const float* y, float* p, const float* dp, float* dy, void* stream)

@@ -61,3 +61,14 @@ int va_heads_from_sizes(const char* who, int n_heads, const int* head_sizes, int
 // out f32 [2 + 2n]; segments >= 1, videos * segments <= 64
 int va_ce_multitask(const float* logits, const long long* labels, const int* tasks, int videos, int segments, const va_heads& h,
                     float* dlogits, float* out, hipStream_t st);
+
+// Gradient accumulation (accum.hip).  The caller's flat f32 gradient buffer holds the 34 parameter tensors
+// in the order conv 0..12 as (weight, bias), then fc 0..3 as (weight, bias), each in the layout of its parameter and momentum
+// buffer (conv weights packed [cout][9][cin_pad], FC1 in NHWC-flatten order); a segment starts on a multiple of 64 floats
+// (256 bytes: 16-byte accesses from every segment's first element) and the gap behind it holds zeros.
+struct va_grad_layout {
+    size_t off[34], cnt[34], total;
+};
+va_grad_layout va_grad_layout_of(const va_vgg16* m);
+// dlogits [rows][h.off[h.n]] *= scales[head of the column] (HOST float[h.n]); no launch when every scale is exactly 1
+int va_scale_dlogits(float* dlogits, int rows, const va_heads& h, const float* scales, hipStream_t st);

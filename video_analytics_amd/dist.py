@@ -75,6 +75,39 @@ def gather_scores(local, n_items, world=None):
     return out[:n_items]
 
 
+def rank_world():
+    """(rank, world size) of the default process group; (0, 1) without one."""
+    return (dist.get_rank(), dist.get_world_size()) if dist.is_initialized() else (0, 1)
+
+
+def all_reduce_sum(t):
+    """SUM all-reduce of ``t`` in place over the default group -> t (the identity without a group).  Under gloo a CUDA tensor
+    is staged through the host, as ``gather_scores`` does (the rehearsal of several ranks on one GPU)."""
+    if not dist.is_initialized() or dist.get_world_size() == 1:
+        return t
+    if dist.get_backend() == "gloo" and t.is_cuda:
+        host = t.cpu()
+        dist.all_reduce(host, op=dist.ReduceOp.SUM)
+        t.copy_(host)
+    elif dist.get_backend() == "nccl" and not t.is_cuda:  # RCCL reduces device tensors only (the step's few counts)
+        dev = t.cuda()
+        dist.all_reduce(dev, op=dist.ReduceOp.SUM)
+        t.copy_(dev)
+    else:
+        dist.all_reduce(t, op=dist.ReduceOp.SUM)
+    return t
+
+
+def all_reduce_gradients(grad):
+    """The exchange of a data-parallel training step: ONE SUM all-reduce of a stream's flat gradient buffer
+    (``Vgg16Stream.grad()``, about 540 MB) between the last ``train_accumulate`` and ``train_apply``; every rank scaled its
+    micro-batches by the full batch's size, so the sum is the full batch's mean gradient.  The gaps of the buffer hold zeros
+    on every rank and stay zeros.  ``nccl`` is RCCL on the device; ``gloo`` with a CUDA tensor goes through the host."""
+    if not isinstance(grad, torch.Tensor) or grad.dtype != torch.float32 or grad.dim() != 1 or not grad.is_contiguous():
+        raise ValueError("all_reduce_gradients: a flat contiguous float32 tensor is needed")
+    return all_reduce_sum(grad)
+
+
 def ranks_seen():
     """World size as the process group itself reports it (1 without a group): what actually took part."""
     return dist.get_world_size() if dist.is_initialized() else 1

@@ -509,9 +509,37 @@ class TwoStreamPipeline(object):
         self.wait()
         return out
 
-    def _check_train_videos(self, videos, labels, k, starts, crops, rng, tasks=None):
+    @staticmethod
+    def _check_accumulate(n, k, micro_videos, clip_norm, data_parallel):
+        """The accumulate arguments of ``train_videos`` -> videos per micro-batch, or None for the fused
+        step (all three at their defaults).  ValueError for a bad value or combination; nothing touches a device."""
+        import numbers
+        who = "train_videos"
+        vgg.check_clip_norm(clip_norm, who)
+        if not isinstance(data_parallel, bool):
+            raise ValueError("%s: data_parallel must be True or False, got %r" % (who, data_parallel))
+        if data_parallel:
+            import torch.distributed as tdist
+            if not (tdist.is_available() and tdist.is_initialized()):
+                raise ValueError("%s: data_parallel=True needs an initialised process group (dist.init)" % who)
+        if micro_videos is None:
+            if clip_norm is None and not data_parallel:
+                return None
+            if n < 1 or k < 1 or n * k > 64:
+                raise ValueError("%s: %d videos x %d snippets out of range (n*k in 1..64); micro_videos= takes larger batches" % (who, n, k))
+            return n
+        if isinstance(micro_videos, bool) or not isinstance(micro_videos, numbers.Integral) or micro_videos < 1:
+            raise ValueError("%s: micro_videos must be a positive integer, got %r" % (who, micro_videos))
+        if k < 1 or micro_videos * k > 64:
+            raise ValueError("%s: micro-batches of %d videos x %d snippets out of range (micro_videos*k in 1..64)" % (who, micro_videos, k))
+        if n < 1:
+            raise ValueError("%s: no videos" % who)
+        return int(micro_videos)
+
+    def _check_train_videos(self, videos, labels, k, starts, crops, rng, tasks=None, micro=None):
         """Host-side checks and draws of ``train_videos`` before anything is enqueued -> (videos, labels, plans, crops, tasks);
-        ``tasks`` is None on a pipeline without heads."""
+        ``tasks`` is None on a pipeline without heads.  ``micro``: videos per micro-batch (``_check_accumulate``), which lifts
+        the limit on ``n*k``."""
         who = "train_videos"
         heads = getattr(self, "heads", None)
         if heads is None and tasks is not None:
@@ -522,7 +550,7 @@ class TwoStreamPipeline(object):
             raise ValueError("%s: training is fp32 only; this pipeline was built with cnn_dtype=%r" % (who, self.spatial.dtype))
         videos = list(videos)
         n, k = len(videos), int(k)
-        if n < 1 or k < 1 or n * k > 64:
+        if n < 1 or k < 1 or (micro is None and n * k > 64):
             raise ValueError("%s: %d videos x %d snippets out of range (n*k in 1..64)" % (who, n, k))
         if heads is not None:  # S26: one head per video, labels local to it
             labels, tasks = vgg.check_tasks(labels, tasks, heads, n, who)
@@ -573,8 +601,41 @@ class TwoStreamPipeline(object):
         augment.check_jitter_crops(crops, n * k, H, W, who)
         return videos, labels, plans, crops, tasks
 
+    def _accumulate_step(self, n, k, micro, labels, tasks, lr, momentum, dropout_seed, clip_norm, data_parallel):
+        """-> step(model, x) of ``train_videos`` in its accumulate form: the micro-batches of x ``[n*k,C,224,224]`` through
+        ``train_accumulate``, the all-reduce of a data-parallel step, ``train_apply`` -> (stats, descriptors); ``step.norms``
+        maps each model to the norm its apply reported."""
+        from . import dist as vdist
+        heads = self.heads if tasks is not None else None
+        H = len(heads) if heads is not None else 0
+        slices = vgg.micro_slices(n, micro)
+        host_tasks = [int(t) for t in tasks.tolist()] if tasks is not None else None  # a device tensor is read back once
+        first_micro, n_total, head_totals = 0, n, None
+        if data_parallel:  # one small all-reduce: videos, videos per head, micro-batches of every rank
+            rank, world = vdist.rank_world()
+            counts = [n] + [sum(1 for t in host_tasks if t == h) for h in range(H)] + [len(slices) if r == rank else 0 for r in range(world)]
+            counts = [int(v) for v in vdist.all_reduce_sum(torch.tensor(counts, dtype=torch.int64)).tolist()]
+            n_total, head_totals, first_micro = counts[0], counts[1:1 + H] if H else None, sum(counts[1 + H:1 + H + rank])
+        scales = vgg.micro_scales(slices, n_total, host_tasks, H, head_totals)
+
+        def step(model, x):
+            stats, descs = [], []
+            for j, (lo, hi) in enumerate(slices):
+                st, d = model.train_accumulate(x[lo * k:hi * k], labels[lo:hi], k=k, tasks=None if tasks is None else tasks[lo:hi],
+                                               heads=heads, scales=scales[j], first=(j == 0), dropout_seed=dropout_seed + first_micro + j)
+                stats.append(st)
+                descs.append(d)
+            out = vgg.combine_micro_stats(stats, scales, H)
+            if data_parallel:
+                vdist.all_reduce_gradients(model.grad())
+                out = vdist.all_reduce_sum(out)
+            step.norms[model] = model.train_apply(lr, momentum, clip_norm)
+            return out, torch.cat(descs)
+        step.norms = {}  # model -> the norm its apply reported (None without clip_norm)
+        return step
+
     def train_videos(self, videos, labels, k=video.N_SEGMENTS, starts=None, crops=None, lr=1e-3, momentum=0.9, dropout_seed=0,
-                     invert_flow_x=False, rng=None, tasks=None):
+                     invert_flow_x=False, rng=None, tasks=None, micro_videos=None, clip_norm=None, data_parallel=False):
         """One TSN training step of both streams on whole videos (Sheet03/notes.txt:165-185, 212-223).
         ``videos``: a list of n ``(rgb u8 [T,3,H,W], gray [T,H,W])`` pairs on the device, one frame size, any lengths;
         ``labels``: their n class indices; ``n*k <= 64``.
@@ -603,9 +664,28 @@ class TwoStreamPipeline(object):
         to the video's head, every stream takes ``Vgg16Stream.train_step_multitask`` instead, and ``stats_*`` are f32
         ``[2+2H]`` = (loss, hits, loss of every head, hits of every head).  ``tasks=`` on a pipeline without heads, a missing
         ``tasks=`` on one with heads, a task outside the heads and a label outside its head raise ValueError before anything
-        is enqueued."""
-        videos, labels, plans, crops, tasks = self._check_train_videos(videos, labels, k, starts, crops, rng, tasks)
-        if tasks is None:
+        is enqueued.
+
+        Gradient accumulation.  With ``micro_videos``, ``clip_norm`` and ``data_parallel`` at their
+        defaults every stream takes the fused step above.  ``micro_videos=m`` (``m*k <= 64``) lifts the limit on ``n``: the
+        inputs are built for all n videos as above (one TV-L1 plan, one gather per stream), then each stream runs
+        ``ceil(n/m)`` ``Vgg16Stream.train_accumulate`` calls on slices of m videos -- dropout seed ``dropout_seed + j`` and
+        scale ``n_j / n`` for micro-batch j (with heads: per head, its videos in the slice over its videos in the batch) --
+        and one ``train_apply``.  ``clip_norm``: ``torch.nn.utils.clip_grad_norm_`` on each stream's whole gradient before its
+        update (alone, with ``n*k <= 64``: one accumulate and one apply); the result gains ``norm_s``, ``norm_t``
+        (``norm_d``), CUDA float64 ``[1]``.  ``stats_*`` are the scale-weighted sum of the micro-batches' losses and the
+        sum of their hits (``vgg.combine_micro_stats``), on the device.  ``data_parallel=True`` under an initialised process
+        group: ``videos`` is this rank's shard; the denominators of the scales (videos, videos per head) and the numbering of
+        the micro-batches (rank-major, for the dropout seeds) come from one small all-reduce, each stream's gradient is
+        all-reduced once between its last accumulate and its apply (``dist.all_reduce_gradients``), loss and hits are
+        all-reduced too, and every rank ends with the same weights.  A bad value or combination raises ValueError before
+        anything is enqueued."""
+        videos = list(videos)
+        micro = self._check_accumulate(len(videos), int(k), micro_videos, clip_norm, data_parallel)
+        videos, labels, plans, crops, tasks = self._check_train_videos(videos, labels, k, starts, crops, rng, tasks, micro)
+        if micro is not None:
+            step = self._accumulate_step(len(videos), int(k), micro, labels, tasks, lr, momentum, dropout_seed, clip_norm, data_parallel)
+        elif tasks is None:
             step = lambda m, x: m.train_step_consensus(x, labels, k, lr, momentum, dropout_seed)
         else:
             step = lambda m, x: m.train_step_multitask(x, labels, tasks, self.heads, k, lr, momentum, dropout_seed)
@@ -644,6 +724,8 @@ class TwoStreamPipeline(object):
         cur.wait_stream(self._cnn2)
         stats_s, desc_s = step(self.spatial, xs)
         stats_t, desc_t = step(self.temporal, xt)
+        if micro is not None and clip_norm is not None:
+            extra["norm_s"], extra["norm_t"] = step.norms[self.spatial], step.norms[self.temporal]
         if self.diff is not None:  # S25: the windows' frames one after the other, one S23 call on the snippets' crops
             D = self.D
             win = torch.cat([rgb[augment.crops_to_device(torch.tensor([s + f for s in p.starts for f in range(D + 1)],
@@ -651,6 +733,8 @@ class TwoStreamPipeline(object):
                              for (rgb, _), p in zip(videos, plans)])  # [n*k*(D+1),3,H,W]
             xd = rgbdiff.rgb_diff_stack(win, rgbdiff.window_table([i * (D + 1) for i in range(n * k)], crops), D)
             extra["stats_d"], extra["desc_d"] = step(self.diff, xd)
+            if micro is not None and clip_norm is not None:
+                extra["norm_d"] = step.norms[self.diff]
         self._cnn.wait_stream(cur)
         self._cnn2.wait_stream(cur)
         return dict(stats_s=stats_s, desc_s=desc_s, stats_t=stats_t, desc_t=desc_t, starts=[list(p.starts) for p in plans],

@@ -337,6 +337,117 @@ class Vgg16Stream(object):
                                                    _ffi.ptr(ws), ws.numel(), _ffi.stream_ptr(self.device)))
         return stats, desc
 
+    # ---- the step in two halves: accumulate the gradient, then apply it ----
+
+    def grad(self):
+        """The flat float32 gradient buffer of ``train_accumulate`` / ``train_apply`` (``va_vgg16_train_grad_floats``, about
+        540 MB), allocated on first use and owned by this object.  ``grad_layout()`` names its 34 segments."""
+        g = getattr(self, "_grad", None)
+        if g is None:
+            n = int(_ffi.lib().va_vgg16_train_grad_floats(self._h))
+            if n == 0:
+                raise ValueError("Vgg16Stream.grad: training is fp32 only")
+            self._grad = g = torch.empty(n, dtype=torch.float32, device=self.device)
+        return g
+
+    def grad_layout(self):
+        """-> (offsets, counts), 34 ints each, in floats: conv 0..12 as (weight, bias), then fc 0..3 as (weight, bias), every
+        tensor in the layout of its parameter (conv weights packed ``[cout][9][cin_pad]``, FC1 in NHWC-flatten order)."""
+        off, cnt = (ctypes.c_size_t * 34)(), (ctypes.c_size_t * 34)()
+        _ffi.check(_ffi.lib().va_vgg16_train_grad_layout(self._h, off, cnt))
+        return [int(v) for v in off], [int(v) for v in cnt]
+
+    def train_accumulate(self, x, labels, *, k=0, tasks=None, heads=None, scales=None, first, dropout_seed):
+        """Forward and backward of one micro-batch into ``grad()``; weights and momentum buffers stay as they are
+        (``va_vgg16_train_accumulate``).  ``k = 0``: ``train_step``'s loss on the images of x; ``k >= 1``:
+        ``train_step_consensus``'s on ``n = len(x) / k`` videos; ``tasks`` and ``heads``: ``train_step_multitask``'s.
+        ``scales``: None (1), a number, or with heads one number per head: the gradient at the logits is multiplied by its
+        head's scale, ``n_micro / n_full`` for a micro-batch's share of a full batch's mean.  ``first``: True stores the
+        gradient, False adds it to what ``grad()`` holds.  Returns (stats, descriptors) as the fused steps do; the loss
+        in ``stats`` is the micro-batch's own mean, not scaled."""
+        who = "Vgg16Stream.train_accumulate"
+        if (tasks is None) != (heads is None):
+            raise ValueError("%s: tasks= and heads= go together" % who)
+        k = int(k)
+        if k < 0 or (tasks is not None and k < 1):
+            raise ValueError("%s: k must be >= 0 (>= 1 with tasks=), got %d" % (who, k))
+        n_heads = 0
+        if heads is not None:
+            check_heads(heads, self.n_classes, who)
+            heads = [int(h) for h in heads]
+            n_heads = len(heads)
+        scales = check_scales(scales, max(n_heads, 1), who)
+        if not isinstance(x, torch.Tensor) or not x.is_cuda or x.dtype not in (torch.float32, torch.uint8):
+            raise ValueError("%s: x must be a CUDA float32/uint8 tensor" % who)
+        if x.dim() != 4 or tuple(x.shape[1:]) != (self.c_in, 224, 224):
+            raise ValueError("%s: x must be [B,%d,224,224], got %s" % (who, self.c_in, tuple(x.shape)))
+        self._on_my_device(x, "train_accumulate")
+        B = int(x.shape[0])
+        if B < 1 or B % max(k, 1):
+            raise ValueError("%s: %d images are not a whole number of videos of k=%d snippets" % (who, B, k))
+        n = B // max(k, 1)
+        if tasks is not None:
+            labels, tasks = check_tasks(labels, tasks, heads, n, who)
+            tasks = tasks.to(device=x.device, dtype=torch.int32).contiguous()
+        else:
+            _check_labels(labels, self.n_classes, who)
+            if not isinstance(labels, torch.Tensor):
+                raise ValueError("%s: labels must be a tensor [%d]" % (who, n))
+        labels = labels.to(device=x.device, dtype=torch.int64).contiguous()
+        if labels.dim() != 1 or labels.shape[0] != n:
+            raise ValueError("%s: labels must be [%d]" % (who, n))
+        if not getattr(self, "_train_ready", False):
+            self.train_init()
+        x = x.contiguous()
+        L = _ffi.lib()
+        nbytes = L.va_vgg16_train_workspace_bytes(self._h, B)
+        if nbytes == 0:
+            raise ValueError("%s: %d images unsupported (1..64 per micro-batch, fp32 model)" % (who, B))
+        g = self.grad()
+        ws = _workspace(nbytes, x.device, ("train", self.ws_slot))
+        stats = torch.empty(2 + 2 * n_heads if n_heads else 2, dtype=torch.float32, device=x.device)
+        desc = torch.empty((B, self.desc_dim), dtype=torch.float32, device=x.device)
+        _ffi.check(L.va_vgg16_train_accumulate(
+            self._h, _ffi.ptr(x), int(x.dtype == torch.uint8), _ffi.ptr(labels), _ffi.ptr(tasks), n, k, n_heads,
+            (ctypes.c_int * n_heads)(*heads) if n_heads else None, (ctypes.c_float * len(scales))(*scales), int(bool(first)),
+            int(dropout_seed) & 0xFFFFFFFFFFFFFFFF, _ffi.ptr(desc), _ffi.ptr(stats), _ffi.ptr(g), g.numel(), _ffi.ptr(ws), ws.numel(),
+            _ffi.stream_ptr(self.device)))
+        return stats, desc
+
+    def train_apply(self, lr, momentum, clip_norm=None):
+        """The momentum-SGD update of every parameter from ``grad()`` (``va_vgg16_train_apply``):
+        ``V = momentum V + c G; W -= lr V`` with the fused step's two fused multiply-adds.  ``clip_norm``: None (no clipping,
+        ``c`` absent) or a positive number: ``c = min(1, clip_norm / (|G| + 1e-6))``, ``torch.nn.utils.clip_grad_norm_``'s rule,
+        with the norm a float64 sum in a fixed order, all on the device.  Returns the norm as a CUDA float64 ``[1]`` tensor,
+        or None without clipping; nothing synchronises the host."""
+        who = "Vgg16Stream.train_apply"
+        clip = check_clip_norm(clip_norm, who)
+        if getattr(self, "_grad", None) is None:
+            raise ValueError("%s: nothing was accumulated (call train_accumulate first)" % who)
+        if not getattr(self, "_train_ready", False):
+            self.train_init()
+        L = _ffi.lib()
+        g = self._grad
+        norm = ws = None
+        if clip > 0.0:
+            norm = torch.empty(1, dtype=torch.float64, device=self.device)
+            ws = _workspace(int(L.va_vgg16_train_apply_workspace_bytes()), self.device, ("train", self.ws_slot))
+        _ffi.check(L.va_vgg16_train_apply(self._h, _ffi.ptr(g), g.numel(), float(lr), float(momentum), clip, _ffi.ptr(norm), _ffi.ptr(ws),
+                                          ws.numel() if ws is not None else 0, _ffi.stream_ptr(self.device)))
+        return norm
+
+    def export_grad(self):
+        """-> dict(conv_w, conv_b, fc_w, fc_b) like ``export_state``: the accumulated gradient in the reference's layouts,
+        what ``p.grad`` holds after ``loss.backward()`` (``va_vgg16_unpack_grad``)."""
+        if getattr(self, "_grad", None) is None:
+            raise ValueError("Vgg16Stream.export_grad: nothing was accumulated (call train_accumulate first)")
+        cw, cb, fw, fb = self._state_tensors(self.device)
+        arr, arr4 = ctypes.c_void_p * 13, ctypes.c_void_p * 4
+        _ffi.check(_ffi.lib().va_vgg16_unpack_grad(self._h, _ffi.ptr(self._grad), arr(*[t.data_ptr() for t in cw]),
+                                                   arr(*[t.data_ptr() for t in cb]), arr4(*[t.data_ptr() for t in fw]),
+                                                   arr4(*[t.data_ptr() for t in fb]), _ffi.stream_ptr(self.device)))
+        return dict(conv_w=cw, conv_b=cb, fc_w=fw, fc_b=fb)
+
     def _state_tensors(self, device):
         cin = self.c_in
         cw, cb = [], []
@@ -585,6 +696,53 @@ def train_fc_backward_layer(dz, x, w, bias, mom_w, mom_b, lr, momentum, dx, mask
     return info.value.decode()
 
 
+def train_conv_backward_layer_grad(dy, x, w_packed, grad_w, grad_b, cin, add, dx=None, mask=None, kernel_opt=1, zeros=None, scratch=None):
+    """``train_conv_backward_layer`` in the forms ``train_accumulate`` uses (``va_train_conv_backward_layer_grad``, DESIGN.md
+    S29): grad_w ``[cout][9][cin_pad]`` and grad_b ``[cout]`` receive the gradient (``add`` False) or have it added (True);
+    w_packed is only read.  Returns the plan that ran."""
+    who = "train_conv_backward_layer_grad"
+    if dy.dim() != 4 or x.dim() != 4 or dy.shape[:3] != x.shape[:3] or dy.shape[1] != dy.shape[2]:
+        raise ValueError("%s: dy / x must be NHWC [B][hw][hw][cout] / [B][hw][hw][cin_pad]" % who)
+    B, hw, _, cout = dy.shape
+    cin_pad = x.shape[3]
+    _f32_cuda(who, dy, dy=dy, x=x, w_packed=w_packed, grad_w=grad_w, grad_b=grad_b, dx=dx, mask=mask, zeros=zeros)
+    if (tuple(w_packed.shape) != (cout, 9, cin_pad) or grad_w.shape != w_packed.shape or tuple(grad_b.shape) != (cout,)
+            or (dx is not None and tuple(dx.shape) != (B, hw, hw, cin)) or (mask is not None and (dx is None or mask.shape != dx.shape))):
+        raise ValueError("%s: w_packed / grad_w / grad_b / dx / mask do not match dy and x" % who)
+    if zeros is None:
+        zeros = torch.zeros(max(512, cin), dtype=torch.float32, device=dy.device)
+    if scratch is None:
+        sizes, _ = train_conv_backward_scratch(B, hw, cin, cin_pad, cout, dy.device.index)
+        scratch = tuple(torch.empty(n, dtype=torch.float32, device=dy.device) for n in sizes)
+    slab, wt, bpart = scratch
+    _f32_cuda(who, dy, slab=slab, wt=wt, bpart=bpart)
+    have = (ctypes.c_size_t * 3)(slab.numel(), wt.numel() if wt is not None else 0, bpart.numel())
+    info = ctypes.create_string_buffer(192)
+    _ffi.check(_ffi.lib().va_train_conv_backward_layer_grad(
+        _ffi.ctx(dy.device.index), int(kernel_opt), B, hw, int(cin), cin_pad, cout, _ffi.ptr(dy), _ffi.ptr(x), _ffi.ptr(w_packed),
+        int(bool(add)), _ffi.ptr(grad_w), _ffi.ptr(grad_b), _ffi.ptr(dx), _ffi.ptr(mask), _ffi.ptr(zeros), _ffi.ptr(slab), _ffi.ptr(wt),
+        _ffi.ptr(bpart), have, info, len(info), _ffi.stream_ptr(dy.device)))
+    return _parse_plan(info.value.decode())
+
+
+def train_fc_backward_layer_grad(dz, x, w, grad_w, grad_b, add, dx, mask=None, scale=1.0):
+    """``train_fc_backward_layer`` in the forms ``train_accumulate`` uses (``va_train_fc_backward_layer_grad``): grad_w
+    ``[O][I]`` and grad_b ``[O]`` receive the gradient (``add`` False) or have it added (True); w is only read."""
+    who = "train_fc_backward_layer_grad"
+    if dz.dim() != 2 or x.dim() != 2 or dz.shape[0] != x.shape[0]:
+        raise ValueError("%s: dz / x must be [B][O] / [B][I]" % who)
+    (B, O), I = dz.shape, x.shape[1]
+    _f32_cuda(who, dz, dz=dz, x=x, w=w, grad_w=grad_w, grad_b=grad_b, dx=dx, mask=mask)
+    if (tuple(w.shape) != (O, I) or grad_w.shape != w.shape or tuple(grad_b.shape) != (O,) or dx.shape != x.shape
+            or (mask is not None and mask.shape != x.shape)):
+        raise ValueError("%s: w / grad_w / grad_b / dx / mask do not match dz and x" % who)
+    info = ctypes.create_string_buffer(64)
+    _ffi.check(_ffi.lib().va_train_fc_backward_layer_grad(
+        _ffi.ctx(dz.device.index), B, O, I, _ffi.ptr(dz), _ffi.ptr(x), _ffi.ptr(w), int(bool(add)), _ffi.ptr(grad_w), _ffi.ptr(grad_b),
+        _ffi.ptr(dx), _ffi.ptr(mask), float(scale), info, len(info), _ffi.stream_ptr(dz.device)))
+    return info.value.decode()
+
+
 def train_pool_layer(y, p, dp=None, dy=None):
     """``va_train_pool_layer``: p = 2x2/2 max-pool of y (NHWC float32) and, with dp and dy, the step's max-pool backward
     (first maximum in row-major order, nothing where the pooled value is <= 0)."""
@@ -653,6 +811,85 @@ def _check_labels(labels, n_classes, who):
 
 
 MAX_HEADS = 8  # VA_MAX_HEADS of the library
+
+
+# ---- gradient accumulation, host side: no device is touched here ----
+
+def check_scales(scales, n, who):
+    """``scales`` of ``train_accumulate`` -> a list of n finite floats (None: ones; a number: that number n times)."""
+    import math
+    import numbers
+    if scales is None:
+        return [1.0] * n
+    if isinstance(scales, numbers.Real) and not isinstance(scales, bool):
+        scales = [scales] * n
+    try:
+        out = [float(v) for v in scales]
+    except (TypeError, ValueError):
+        raise ValueError("%s: scales must be None, a number or %d numbers, got %r" % (who, n, scales))
+    if len(out) != n or not all(math.isfinite(v) for v in out):
+        raise ValueError("%s: scales must be %d finite numbers, got %r" % (who, n, scales))
+    return out
+
+
+def check_clip_norm(clip_norm, who):
+    """None -> 0.0 (no clipping); a finite positive number -> float; ValueError otherwise."""
+    import math
+    import numbers
+    if clip_norm is None:
+        return 0.0
+    if isinstance(clip_norm, bool) or not isinstance(clip_norm, numbers.Real) or not math.isfinite(clip_norm) or clip_norm <= 0:
+        raise ValueError("%s: clip_norm must be None or a finite positive number, got %r" % (who, clip_norm))
+    return float(clip_norm)
+
+
+def micro_slices(n, m):
+    """The micro-batches of n videos, at most m each, in order: [(lo, hi), ...]; ``ceil(n/m)`` of them, the last one ragged."""
+    n, m = int(n), int(m)
+    if n < 1 or m < 1:
+        raise ValueError("micro_slices: need n >= 1 and m >= 1, got n=%d m=%d" % (n, m))
+    return [(lo, min(lo + m, n)) for lo in range(0, n, m)]
+
+
+def micro_scales(slices, n_total=None, tasks=None, n_heads=0, head_totals=None):
+    """The scales of the micro-batches ``slices``: what makes the sum of their mean losses the full batch's mean.  Without
+    heads: ``[(hi - lo) / n_total]`` per slice (n_total None: the videos of the slices).  With ``tasks`` (one head index per
+    video, on the host) and ``n_heads``: per slice one scale per head, the head's videos in the slice over its videos in the
+    batch (``head_totals``; None: counted from tasks).  A head absent from the slice, or from the whole batch, gets 0: its
+    columns' gradient is exactly zero anyway.  Data-parallel steps pass the totals over all ranks."""
+    if tasks is None:
+        total = sum(hi - lo for lo, hi in slices) if n_total is None else int(n_total)
+        return [[float(hi - lo) / float(total)] for lo, hi in slices]
+    tasks = [int(t) for t in tasks]
+    if head_totals is None:
+        head_totals = [sum(1 for t in tasks if t == h) for h in range(n_heads)]
+    out = []
+    for lo, hi in slices:
+        cnt = [sum(1 for t in tasks[lo:hi] if t == h) for h in range(n_heads)]
+        out.append([float(c) / float(tot) if tot > 0 else 0.0 for c, tot in zip(cnt, head_totals)])
+    return out
+
+
+def combine_micro_stats(stats, scales, n_heads=0):
+    """The ``stats`` of a step of several micro-batches from theirs, on their device in float32: without heads
+    (loss, hits) = (sum_j scale_j loss_j, sum_j hits_j), added in micro-batch order from 0; with heads every head's loss is
+    weighted by that head's scale, the total loss is the heads' sum in head order, hits add up."""
+    dev = stats[0].device
+    if n_heads == 0:
+        w = torch.tensor([[s[0], 1.0] for s in scales], dtype=torch.float32, device=dev)
+        out = torch.zeros(2, dtype=torch.float32, device=dev)
+        for j, st in enumerate(stats):
+            out = out + w[j] * st
+        return out
+    H = n_heads
+    w = torch.tensor([list(s) + [1.0] * H for s in scales], dtype=torch.float32, device=dev)
+    per = torch.zeros(2 * H, dtype=torch.float32, device=dev)
+    for j, st in enumerate(stats):
+        per = per + w[j] * st[2:]
+    loss = torch.zeros((), dtype=torch.float32, device=dev)
+    for h in range(H):
+        loss = loss + per[h]
+    return torch.cat([torch.stack([loss, per[H:].sum()]), per])
 
 
 def check_heads(heads, n_classes, who):

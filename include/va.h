@@ -332,6 +332,30 @@ int va_rgbdiff_to_stack(va_ctx* ctx, const void* frames, int n_frames, int w, in
                         const float* den, const void* table, int n_out, void* stack, void* stream);
 
 /*
+ * Colour jitter and PCA lighting on u8 images, in place or not: torchvision's ColorJitter in PIL's
+ * arithmetic, value for value.  src, dst u8 [n][3][h][w], any h, w >= 1 with w*h < 2^30; dst may equal src and must not
+ * overlap it otherwise.  table: DEVICE f32 [n][8], one row per image = {op0, op1, op2, op3, f_brightness, f_contrast,
+ * f_saturation, hue_shift}: the op codes in application order (0 none, 1 brightness, 2 contrast, 3 saturation, 4 hue), the
+ * three blend factors (>= 0) and the hue shift, an integer in 0..255.  Rows are validated by the host wrapper and clamped
+ * on the device (codes to 0..4, a repeated code to none, factors to [0, 1e30], the shift to 0..255).  With
+ * B(d, v, f) = d + f*(v - d) in f32 (multiply, then add), the result 0 if <= 0, 255 if >= 255, else truncated:
+ *   brightness  v <- B(0, v, f) per channel
+ *   saturation  v <- B(L, v, f) per channel, L = (19595 R + 38470 G + 7471 B + 32768) >> 16 of the pixel
+ *   contrast    v <- B(m, v, f) per channel, m = (2 S + N) / (2 N) in integers, S the sum of L over the image as it is when
+ *               contrast's turn comes (after the ops before it in the row), N = w*h
+ *   hue         RGB -> HSV, h <- (h + hue_shift) & 255, HSV -> RGB, both conversions as PIL's (S32 gives the widths)
+ * lighting: DEVICE f32 [n][3] or NULL; applied last, v <- (u8) rintf(clamp((float)v + lighting[i][c], 0, 255)).
+ * workspace: DEVICE, n * VA_COLOR_JITTER_PARTIALS uint32, owned by the caller until the call has run: launch one writes
+ * per-workgroup integer sums of L there for the images whose row has contrast, launch two adds them (integers: the result
+ * does not depend on scheduling; no atomics).  NULL: the caller states that no row has contrast; launch one is skipped and
+ * a contrast code counts as none.  table, lighting and workspace 4-byte aligned.  n <= 65535 per call.  Bad arguments:
+ * VA_ERR_INVALID before anything is enqueued.
+ */
+#define VA_COLOR_JITTER_PARTIALS 256
+int va_color_jitter_u8(va_ctx* ctx, const void* src, int n, int w, int h, const void* table, const void* lighting, void* dst,
+                       void* workspace, void* stream);
+
+/*
  * Mean flow subtraction, step one: flow f32 [n_pairs][2][h][w] -> means f32 [n_pairs][2], the mean of
  * every displacement field's component over the full frame.  Each value is clamped to [-32768, 32768] (a NaN becomes
  * -32768) and summed as the exact integer rint(a * 65536) in int64, so the result does not depend on the reduction

@@ -11,6 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libva_hip.so")
 
 VA_OK, VA_ERR_INVALID, VA_ERR_HIP, VA_ERR_WORKSPACE, VA_ERR_STOPPED = 0, 1, 2, 3, 4
+VA_COLOR_JITTER_PARTIALS = 256  # include/va.h: uint32 partial sums per image in va_color_jitter_u8's workspace
 VA_OPT_BF16_VARIANT, VA_OPT_F32_CONV_KERNEL, VA_OPT_TRAIN_STOP_AT, VA_OPT_BF16_FIRST_LAYER = 1, 2, 3, 4
 
 # every symbol include/va.h declares (tests check that the library exports exactly these)
@@ -35,6 +36,7 @@ EXPORTS = [
     "va_linear_svm_fit_workspace_bytes", "va_linear_svm_fit", "va_linear_svm_fit_cg_steps",
     "va_vgg16_train_grad_floats", "va_vgg16_train_grad_layout", "va_vgg16_train_accumulate", "va_vgg16_train_apply_workspace_bytes",
     "va_vgg16_train_apply", "va_vgg16_unpack_grad", "va_train_conv_backward_layer_grad", "va_train_fc_backward_layer_grad",
+    "va_color_jitter_u8",
 ]
 
 
@@ -143,6 +145,8 @@ def lib():
     L.va_resize_images_u8.restype = ci
     L.va_rgbdiff_to_stack.argtypes = [vp, vp, ci, ci, ci, ci, ci, fpp, vp, ci, vp, vp]
     L.va_rgbdiff_to_stack.restype = ci
+    L.va_color_jitter_u8.argtypes = [vp, vp, ci, ci, ci, vp, vp, vp, vp, vp]
+    L.va_color_jitter_u8.restype = ci
     L.va_score_consensus.argtypes = [vp, vp, ci, ci, ci, ci, vp, vp]
     L.va_score_consensus.restype = ci
     L.va_fuse_scores.argtypes = [vp, vp, vp, ci, ci, cf, cf, vp, vp, vp]

@@ -13,12 +13,17 @@ TSN's training augmentations (Sheet03/notes.txt:212-223), cor
 crop size as well: ``draw_scale_jitter_crops`` gives rows ``{top, left, ch, cw, flip}``, one per snippet, and
 ``snippet_tables`` expands them into the ``{src, top, left, ch, cw, flip}`` tables of the crop-resize gathers
 (``resize_images``, ``flow.resize_flow_to_stack``), which resample every crop to 224x224.
+
+Colour jitter: ``draw_color_jitter`` gives one row ``{op0, op1, op2, op3, f_brightness, f_contrast,
+f_saturation, hue_shift}`` per image of a CPU float32 ``[n,8]`` table, ``color_jitter`` applies it on the device
+(``va_color_jitter_u8``) with the optional PCA lighting offsets of ``draw_lighting``.
 """
 import random
 
 import torch
 
 from . import _ffi
+from . import utils
 
 CROP_SIZE = 224  # the literal RandomCrop(224) of Sheet03/utils.py:143
 
@@ -313,3 +318,136 @@ def resize_images(x_u8, table, layout="NCHW", out=None):
     _ffi.check(_ffi.lib().va_resize_images_u8(_ffi.ctx(dev.index), _ffi.ptr(x_u8), n, c, w, h, int(layout == "NHWC"),
                                               _ffi.ptr(dtable), n_out, _ffi.ptr(out), _ffi.stream_ptr(dev)))
     return out.view(n_out, c, CROP_SIZE, CROP_SIZE)
+
+
+# ---- colour jitter and PCA lighting ----
+
+IDENTITY_JITTER_ROW = (0, 0, 0, 0, 1.0, 1.0, 1.0, 0)  # no op; the factors of the identity blend, no shift
+
+
+def _jitter_row(ops):
+    """``[(op, value), ...]`` in application order (``utils.drawColorJitter``) -> one table row."""
+    row = list(IDENTITY_JITTER_ROW)
+    for k, (op, value) in enumerate(ops):
+        row[k] = op
+        row[3 + op if op != utils.JITTER_HUE else 7] = value
+    return row
+
+
+def draw_color_jitter(n, brightness, contrast, saturation, hue, rng=None):
+    """The jitter of ``n`` images -> CPU float32 ``[n,8]`` rows ``{op0, op1, op2, op3, f_brightness, f_contrast,
+    f_saturation, hue_shift}``: the op codes (0 none, 1 brightness, 2 contrast, 3 saturation, 4 hue) in application order,
+    the blend factors as float32 (what PIL's blend computes with) and the integer hue shift.  Per image the draws of
+    ``utils.ColorJitter`` (``utils.drawColorJitter``): nothing is drawn for all-zero parameters."""
+    utils.checkColorJitter(brightness, contrast, saturation, hue)
+    rng = random if rng is None else rng
+    rows = [_jitter_row(utils.drawColorJitter(rng, brightness, contrast, saturation, hue)) for _ in range(int(n))]
+    return torch.tensor(rows, dtype=torch.float32).view(int(n), 8)
+
+
+def check_color_jitter(params, n, who="color_jitter"):
+    """Host-side validation (ValueError) of a jitter table for ``n`` images, before anything reaches the GPU: CPU float32
+    ``[n,8]``; op codes integers in 0..4, each op at most once in a row; finite factors >= 0; the shift an integer in
+    0..255."""
+    if not isinstance(params, torch.Tensor) or params.is_cuda or params.dtype != torch.float32:
+        raise ValueError("%s: the jitter table must be a CPU float32 tensor (augment.draw_color_jitter)" % who)
+    if params.dim() != 2 or tuple(params.shape) != (n, 8):
+        raise ValueError("%s: the jitter table must be [%d,8], got %s" % (who, n, tuple(params.shape)))
+    if not bool(torch.isfinite(params).all()):
+        raise ValueError("%s: the jitter table holds a value that is not finite" % who)
+    ops, fac, shift = params[:, :4], params[:, 4:7], params[:, 7]
+    if bool((ops != ops.round()).any()) or bool((ops < 0).any()) or bool((ops > 4).any()):
+        raise ValueError("%s: op codes must be integers in 0..4" % who)
+    for op in (1, 2, 3, 4):
+        if bool(((ops == op).sum(dim=1) > 1).any()):
+            raise ValueError("%s: op %d appears twice in a row" % (who, op))
+    if bool((fac < 0).any()):
+        raise ValueError("%s: blend factors must be >= 0" % who)
+    if bool((shift != shift.round()).any()) or bool((shift < 0).any()) or bool((shift > 255).any()):
+        raise ValueError("%s: the hue shift must be an integer in 0..255" % who)
+
+
+def check_lighting(lighting, n, who="color_jitter"):
+    """ValueError unless ``lighting`` is a CPU float32 ``[n,3]`` tensor of finite offsets (``draw_lighting``)."""
+    if (not isinstance(lighting, torch.Tensor) or lighting.is_cuda or lighting.dtype != torch.float32
+            or tuple(lighting.shape) != (n, 3) or not bool(torch.isfinite(lighting).all())):
+        raise ValueError("%s: lighting must be a finite CPU float32 [%d,3] tensor (augment.draw_lighting)" % (who, n))
+
+
+def color_jitter(x_u8, params, lighting=None, out=None):
+    """x_u8: CUDA uint8 ``[n,3,h,w]``; params: CPU float32 ``[n,8]`` (``draw_color_jitter``); lighting: CPU float32 ``[n,3]``
+    channel offsets (``draw_lighting``) or None -> CUDA uint8 ``[n,3,h,w]``: every image through its own row, then the
+    lighting (``va_color_jitter_u8``).  ``out`` may be ``x_u8`` itself (in place)."""
+    if not isinstance(x_u8, torch.Tensor) or not x_u8.is_cuda or x_u8.dtype != torch.uint8 or x_u8.dim() != 4 or x_u8.shape[1] != 3:
+        raise ValueError("color_jitter: x must be a CUDA uint8 [n,3,h,w] tensor")
+    n, _, h, w = x_u8.shape
+    check_color_jitter(params, n)
+    if lighting is not None:
+        check_lighting(lighting, n)
+    if out is x_u8:
+        if not x_u8.is_contiguous():
+            raise ValueError("color_jitter: in place needs a contiguous x")
+    else:
+        x_u8 = x_u8.contiguous()
+    dev = x_u8.device
+    if out is None:
+        out = torch.empty_like(x_u8)
+    elif out.numel() != x_u8.numel() or out.dtype != torch.uint8 or not out.is_contiguous() or out.device != dev:
+        raise ValueError("color_jitter: out must be a contiguous uint8 tensor of %d elements on x's device" % x_u8.numel())
+    dparams = crops_to_device(params, dev)
+    dlight = crops_to_device(lighting, dev) if lighting is not None else None
+    # the partial sums of the gray level live in a workspace of this call (stream-ordered: the allocator hands the block
+    # out again only to work enqueued after launch two); no row with contrast: no workspace, one launch
+    work = None
+    if bool((params[:, :4] == utils.JITTER_CONTRAST).any()):
+        work = torch.empty((n, _ffi.VA_COLOR_JITTER_PARTIALS), dtype=torch.int32, device=dev)
+    _ffi.check(_ffi.lib().va_color_jitter_u8(_ffi.ctx(dev.index), _ffi.ptr(x_u8), n, w, h, _ffi.ptr(dparams), _ffi.ptr(dlight),
+                                             _ffi.ptr(out), _ffi.ptr(work), _ffi.stream_ptr(dev)))
+    return out.view(n, 3, h, w)
+
+
+def draw_image_transforms(n, h, w, jitter, size=CROP_SIZE, rng=None):
+    """The draws of ``utils.getTransforms(jitter=jitter)`` for ``n`` images of ``h x w`` pixels, image by image in its order
+    (crop, flip, jitter) -> ``(crops [n,3], params [n,8])`` for ``crop_images`` and ``color_jitter``: a seeded host
+    transform and the two device calls see the same numbers."""
+    _check_frame(h, w, size, "draw_image_transforms")
+    b, c, s, hue = jitter if jitter else (0, 0, 0, 0)
+    utils.checkColorJitter(b, c, s, hue)
+    rng = random if rng is None else rng
+    crops, rows = [], []
+    for _ in range(int(n)):
+        crops.append(_draw(rng, h, w, size))
+        rows.append(_jitter_row(utils.drawColorJitter(rng, b, c, s, hue)))
+    return torch.tensor(crops, dtype=torch.int32).view(int(n), 3), torch.tensor(rows, dtype=torch.float32).view(int(n), 8)
+
+
+def rgb_pca(frames_u8):
+    """The PCA of the RGB values of ``frames_u8``, uint8 ``[..., 3, h, w]`` on any device -> ``(eigval [3], eigvec [3,3])``,
+    CPU float64, ``torch.linalg.eigh`` of the 3x3 covariance (over all N pixels, divided by N) in u8 units: ascending
+    eigenvalues, eigenvector j in column j.  The sums of values and of products are exact integers (int64, accumulated
+    with torch on the frames' device); the covariance is formed from them once."""
+    if not isinstance(frames_u8, torch.Tensor) or frames_u8.dtype != torch.uint8 or frames_u8.dim() < 3 or frames_u8.shape[-3] != 3:
+        raise ValueError("rgb_pca: frames must be a uint8 [...,3,h,w] tensor")
+    x = frames_u8.reshape(-1, 3, frames_u8.shape[-2] * frames_u8.shape[-1])
+    N = x.shape[0] * x.shape[2]
+    if N < 1:
+        raise ValueError("rgb_pca: no pixels")
+    ch = [x[:, c].to(torch.int64) for c in range(3)]
+    s1 = [int(c.sum()) for c in ch]
+    cov = torch.empty((3, 3), dtype=torch.float64)
+    for i in range(3):
+        for j in range(i, 3):
+            s2 = int((ch[i] * ch[j]).sum())
+            cov[i, j] = cov[j, i] = (s2 * N - s1[i] * s1[j]) / (N * N)  # exact integers, one rounding
+    return torch.linalg.eigh(cov)
+
+
+def draw_lighting(n, eigval, eigvec, alphastd=0.1, rng=None):
+    """AlexNet's PCA lighting noise for ``n`` images -> CPU float32 ``[n,3]`` channel offsets
+    ``eigvec @ (alpha * eigval)``, ``alpha_j = rng.gauss(0, alphastd)`` drawn in j order per image; computed in float64
+    and rounded to float32 once.  ``eigval [3]``, ``eigvec [3,3]`` (column j the j-th eigenvector): ``rgb_pca``."""
+    rng = random if rng is None else rng
+    ev = torch.as_tensor(eigval, dtype=torch.float64).reshape(3)
+    evec = torch.as_tensor(eigvec, dtype=torch.float64).reshape(3, 3)
+    alpha = torch.tensor([[rng.gauss(0, alphastd) for _ in range(3)] for _ in range(int(n))], dtype=torch.float64).view(int(n), 3)
+    return ((alpha * ev) @ evec.t()).to(torch.float32).contiguous()

@@ -8,6 +8,7 @@
 // same contiguous source segment in reverse order.  A wave whose elements straddle two output rows reads two such
 // segments.  No LDS.  Ten-crop evaluation uses the same kernels with V views per source plane.
 #include "va_internal.h"
+#include <algorithm>
 
 // A crop triple as the kernels use it: offsets clamped to the frame, so that no crop value can address memory outside
 // it (the host wrappers reject such crops before they get here).
@@ -377,6 +378,230 @@ __global__ void __launch_bounds__(kResizeThreads) k_rgbdiff_stack(const unsigned
     }
 }
 
+// ---------------------------------------------------------------- S32-S34: colour jitter ------
+//
+// ColorJitter's four ops and the PCA lighting on u8 [n][3][h][w]: PIL's arithmetic, value for value.
+// One table row of 8 floats per image, {op0, op1, op2, op3, f_brightness, f_contrast, f_saturation, hue_shift}: the op codes
+// (0 none, 1 brightness, 2 contrast, 3 saturation, 4 hue) in application order.  Contrast blends with the mean gray level of
+// the image as it is when contrast's turn comes, so it needs a sum over the whole image: k_color_jitter_sums applies the ops
+// that precede contrast in registers and writes one integer partial sum per workgroup, k_color_jitter_apply adds an image's
+// partials (integers: any order gives the same sum), forms m and applies the whole row and the lighting.  Both kernels have
+// one geometry: kJitterThreads threads, a thread handles runs of 4 consecutive pixels of the plane (one 4-byte load and
+// store per channel when the planes are 4-byte aligned); an image of more than 1024 x VA_COLOR_JITTER_PARTIALS pixels gets
+// that many workgroups, which stride over it by the grid's width.  Pure element-wise work besides the sum: no LDS but the
+// reduction's, no atomics, bit-reproducible.  dst may be src: a thread reads only the pixels it writes.
+constexpr int kJitterThreads = 256;
+// one run of 4 pixels per thread, 1024 pixels a workgroup, until an image has VA_COLOR_JITTER_PARTIALS workgroups (512 x 512);
+// the hue's f64 arithmetic makes a thread's work long, and at 24 images of 224 x 224 four runs a thread left one wave per SIMD
+// with nothing to hide its latencies behind (measured: 25.9 us for k_color_jitter_apply)
+constexpr int kJitterSteps = 1;
+constexpr int kJitterPerBlock = kJitterThreads * 4 * kJitterSteps;
+enum { kJitterNone = 0, kJitterBrightness = 1, kJitterContrast = 2, kJitterSaturation = 3, kJitterHue = 4 };
+
+struct JitterRow {
+    unsigned ops;             // op k in bits 4k .. 4k+3 (no array: a run-time index would move the row out of registers)
+    float fb, fc, fs;         // the blend factors of brightness, contrast, saturation
+    int shift;
+    int contrast_at;          // the place of contrast among the four ops, 4 when the row has none
+};
+
+// a table row clamped so that no value leaves the arithmetic's domain (the host wrappers reject such rows before they get
+// here): codes to 0..4 with a repeated code becoming none, factors to [0, 1e30] (NaN: 0), the shift to 0..255; with_contrast
+// clear turns contrast into none (no workspace: the caller stated that no row has it)
+__device__ __forceinline__ JitterRow load_jitter(const float* __restrict__ table, int i, bool with_contrast)
+{
+    const float* t = table + 8 * (size_t)i;
+    JitterRow r;
+    unsigned seen = with_contrast ? 1u : 1u | (1u << kJitterContrast);
+    r.ops = 0;
+    r.contrast_at = 4;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        int c = (int)fminf(fmaxf(t[k], 0.0f), 4.0f);
+        if (seen & (1u << c)) c = kJitterNone;
+        seen |= 1u << c;
+        r.ops |= (unsigned)c << (4 * k);
+        if (c == kJitterContrast) r.contrast_at = k;
+    }
+    r.fb = fminf(fmaxf(t[4], 0.0f), 1.0e30f);
+    r.fc = fminf(fmaxf(t[5], 0.0f), 1.0e30f);
+    r.fs = fminf(fmaxf(t[6], 0.0f), 1.0e30f);
+    r.shift = (int)fminf(fmaxf(t[7], 0.0f), 255.0f);
+    return r;
+}
+
+// Image.blend: t = d + f*(v - d) in f32, multiply then add; 0 <= f <= 1 keeps t in [0, 255], so one clamped form serves
+// both of PIL's branches
+__device__ __forceinline__ int jitter_blend(int d, int v, float f)
+{
+    const float t = (float)d + f * (float)(v - d);
+    return t <= 0.0f ? 0 : (t >= 255.0f ? 255 : (int)t);
+}
+
+__device__ __forceinline__ int jitter_gray(int r, int g, int b) { return (19595 * r + 38470 * g + 7471 * b + 32768) >> 16; }
+
+// RGB -> HSV, h += shift (mod 256), HSV -> RGB with PIL's operand widths (S32): the hue expression, fmod(h/6 + 1, 1) and
+// the scalings by 255 in double, the ratios in f32; the way back in double with f, fs and fs*f rounded to f32
+__device__ __forceinline__ void jitter_hue(int& r, int& g, int& b, int shift)
+{
+    const int mx = max(r, max(g, b)), mn = min(r, min(g, b));
+    if (mx == mn) return;  // h = s = 0: the way back gives r = g = b = v whatever the shifted hue
+    const float cr = (float)(mx - mn);
+    const float s = cr / (float)mx;
+    const float rc = (float)(mx - r) / cr, gc = (float)(mx - g) / cr, bc = (float)(mx - b) / cr;
+    float h;
+    if (r == mx)
+        h = (float)((double)bc - (double)gc);
+    else if (g == mx)
+        h = (float)(2.0 + (double)rc - (double)bc);
+    else
+        h = (float)(4.0 + (double)gc - (double)rc);
+    const double x = (double)h / 6.0 + 1.0;           // in [5/6, 11/6]
+    h = (float)(x >= 1.0 ? x - 1.0 : x);              // fmod(x, 1.0), exact
+    const int uh = min(max((int)((double)h * 255.0), 0), 255);
+    const int us = min(max((int)((double)s * 255.0), 0), 255);
+    if (us == 0) {
+        r = g = b = mx;
+        return;
+    }
+    const int hh = (uh + shift) & 255;
+    const double h6 = (double)hh * 6.0 / 255.0;
+    const double fl = floor(h6);
+    const float f = (float)(h6 - fl);
+    const float fs = (float)((double)us / 255.0);
+    const double v = (double)mx;
+    const int p = min(max((int)round(v * (1.0 - (double)fs)), 0), 255);
+    const int q = min(max((int)round(v * (1.0 - (double)(fs * f))), 0), 255);
+    const int t = min(max((int)round(v * (1.0 - (double)fs * (1.0 - (double)f))), 0), 255);
+    switch ((int)fl % 6) {
+        case 0: r = mx, g = t, b = p; break;
+        case 1: r = q, g = mx, b = p; break;
+        case 2: r = p, g = mx, b = t; break;
+        case 3: r = p, g = q, b = mx; break;
+        case 4: r = t, g = p, b = mx; break;
+        default: r = mx, g = p, b = q; break;
+    }
+}
+
+// ops [first, last) of the row on one pixel; m: contrast's gray value
+__device__ __forceinline__ void jitter_ops(const JitterRow& row, int first, int last, int m, int& r, int& g, int& b)
+{
+    for (int k = first; k < last; ++k) {
+        const int op = (int)((row.ops >> (4 * k)) & 15u);  // the same for the whole workgroup
+        if (op == kJitterBrightness) {
+            r = jitter_blend(0, r, row.fb), g = jitter_blend(0, g, row.fb), b = jitter_blend(0, b, row.fb);
+        } else if (op == kJitterContrast) {
+            r = jitter_blend(m, r, row.fc), g = jitter_blend(m, g, row.fc), b = jitter_blend(m, b, row.fc);
+        } else if (op == kJitterSaturation) {
+            const int L = jitter_gray(r, g, b);
+            r = jitter_blend(L, r, row.fs), g = jitter_blend(L, g, row.fs), b = jitter_blend(L, b, row.fs);
+        } else if (op == kJitterHue) {
+            jitter_hue(r, g, b, row.shift);
+        }
+    }
+}
+
+// the run of 4 pixels at plane index i0 of an image's three planes (plane: its pixel count); pixels past the plane read 0
+__device__ __forceinline__ void jitter_load(const unsigned char* __restrict__ img, int plane, int i0, int vec4, int (&px)[3][4])
+{
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const unsigned char* __restrict__ p = img + (size_t)c * plane + i0;
+        if (vec4) {
+            const unsigned u = *reinterpret_cast<const unsigned*>(p);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) px[c][k] = (int)((u >> (8 * k)) & 255u);
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) px[c][k] = i0 + k < plane ? (int)p[k] : 0;
+        }
+    }
+}
+
+// the sum of v over the workgroup, in every thread: shuffles within a wave, then the waves' sums through LDS
+__device__ __forceinline__ unsigned long long jitter_block_sum(unsigned long long v)
+{
+    __shared__ unsigned long long wave_sum[kJitterThreads / 64];
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+    if ((threadIdx.x & 63) == 0) wave_sum[threadIdx.x >> 6] = v;
+    __syncthreads();
+    unsigned long long s = 0;
+#pragma unroll
+    for (int k = 0; k < kJitterThreads / 64; ++k) s += wave_sum[k];
+    return s;
+}
+
+// launch one: partials u32 [n][gridDim.x]; workgroup (x, img) writes the sum of the gray level, after the ops that precede
+// contrast, over its pixels of image img.  Images whose row has no contrast write nothing.
+__global__ void __launch_bounds__(kJitterThreads) k_color_jitter_sums(const unsigned char* __restrict__ src,
+                                                                      const float* __restrict__ table,
+                                                                      unsigned* __restrict__ partials, int plane, int vec4)
+{
+    const int img = blockIdx.y;
+    const JitterRow row = load_jitter(table, img, true);
+    if (row.contrast_at == 4) return;
+    const unsigned char* __restrict__ base = src + (size_t)img * 3 * plane;
+    unsigned sum = 0;  // <= 2^31 / gridDim.x pixels x 255 a workgroup (the entry point bounds the plane): no overflow
+    for (int i0 = (blockIdx.x * kJitterThreads + threadIdx.x) * 4; i0 < plane; i0 += gridDim.x * kJitterThreads * 4) {
+        int px[3][4];
+        jitter_load(base, plane, i0, vec4, px);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            jitter_ops(row, 0, row.contrast_at, 0, px[0][k], px[1][k], px[2][k]);
+            if (i0 + k < plane) sum += (unsigned)jitter_gray(px[0][k], px[1][k], px[2][k]);
+        }
+    }
+    const unsigned long long s = jitter_block_sum(sum);
+    if (threadIdx.x == 0) partials[(size_t)img * gridDim.x + blockIdx.x] = (unsigned)s;
+}
+
+// launch two: the whole row, then the lighting (lighting f32 [n][3] or null): v <- (u8) rintf(clamp((float)v + off_c, 0, 255))
+__global__ void __launch_bounds__(kJitterThreads) k_color_jitter_apply(const unsigned char* __restrict__ src,
+                                                                       const float* __restrict__ table,
+                                                                       const float* __restrict__ lighting,
+                                                                       const unsigned* __restrict__ partials,
+                                                                       unsigned char* __restrict__ dst, int plane, int vec4)
+{
+    const int img = blockIdx.y;
+    const JitterRow row = load_jitter(table, img, partials != nullptr);
+    int m = 0;
+    if (row.contrast_at < 4) {  // the same for the whole workgroup; gridDim.x <= kJitterThreads partials an image
+        const unsigned long long S = jitter_block_sum(threadIdx.x < gridDim.x ? partials[(size_t)img * gridDim.x + threadIdx.x] : 0u);
+        m = (int)((2 * S + (unsigned long long)plane) / (2 * (unsigned long long)plane));
+    }
+    float off[3] = {0.0f, 0.0f, 0.0f};
+    if (lighting != nullptr) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) off[c] = lighting[3 * (size_t)img + c];
+    }
+    const unsigned char* __restrict__ base = src + (size_t)img * 3 * plane;
+    unsigned char* __restrict__ out = dst + (size_t)img * 3 * plane;
+    for (int i0 = (blockIdx.x * kJitterThreads + threadIdx.x) * 4; i0 < plane; i0 += gridDim.x * kJitterThreads * 4) {
+        int px[3][4];
+        jitter_load(base, plane, i0, vec4, px);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) jitter_ops(row, 0, 4, m, px[0][k], px[1][k], px[2][k]);
+        if (lighting != nullptr) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c)
+#pragma unroll
+                for (int k = 0; k < 4; ++k) px[c][k] = (int)rintf(fminf(fmaxf((float)px[c][k] + off[c], 0.0f), 255.0f));
+        }
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            unsigned char* __restrict__ p = out + (size_t)c * plane + i0;
+            if (vec4) {
+                *reinterpret_cast<unsigned*>(p) = (unsigned)px[c][0] | ((unsigned)px[c][1] << 8) | ((unsigned)px[c][2] << 16) |
+                                                  ((unsigned)px[c][3] << 24);
+            } else {
+#pragma unroll
+                for (int k = 0; k < 4; ++k)
+                    if (i0 + k < plane) p[k] = (unsigned char)px[c][k];
+            }
+        }
+    }
+}
+
 // The mean over V views: x f32 [n][V][d] -> out f32 [n][d], out = (((x_0 + x_1) + ...) + x_{V-1}) / V in view order.  One
 // thread per (b, j); the loads of a wave are contiguous in j.
 __global__ void __launch_bounds__(256) k_view_mean(const float* __restrict__ x, float* __restrict__ out, int n, int n_views,
@@ -577,6 +802,33 @@ extern "C" int va_rgbdiff_to_stack(va_ctx* ctx, const void* frames, int n_frames
         k_rgbdiff_stack<false><<<g, kResizeThreads, 0, (hipStream_t)stream>>>((const unsigned char*)frames, (const int*)table,
                                                                               (float*)stack, n_frames, n_diff, w, h, vec4, den[0],
                                                                               den[1], den[2]);
+    VA_LAUNCH_CHECK();
+    return VA_OK;
+}
+
+extern "C" int va_color_jitter_u8(va_ctx* ctx, const void* src, int n, int w, int h, const void* table, const void* lighting,
+                                  void* dst, void* workspace, void* stream)
+{
+    VA_CHECK_ARG(ctx != nullptr, "va_color_jitter_u8: ctx is NULL");
+    VA_USE_DEVICE(ctx);
+    VA_CHECK_ARG(src != nullptr && table != nullptr && dst != nullptr, "va_color_jitter_u8: NULL buffer");
+    VA_CHECK_ARG(n >= 1 && w >= 1 && h >= 1 && (long long)w * h <= 0x3fffffffLL, "va_color_jitter_u8: bad shape");
+    VA_CHECK_ARG(n <= kMaxGridY, "va_color_jitter_u8: %d images exceed %d per call", n, kMaxGridY);
+    VA_CHECK_ARG(reinterpret_cast<uintptr_t>(table) % 4 == 0 && reinterpret_cast<uintptr_t>(lighting) % 4 == 0 &&
+                     reinterpret_cast<uintptr_t>(workspace) % 4 == 0,
+                 "va_color_jitter_u8: table, lighting and workspace must be 4-byte aligned");
+    const size_t bytes = (size_t)n * 3 * w * h;
+    const uintptr_t s0 = reinterpret_cast<uintptr_t>(src), d0 = reinterpret_cast<uintptr_t>(dst);
+    VA_CHECK_ARG(s0 == d0 || s0 + bytes <= d0 || d0 + bytes <= s0, "va_color_jitter_u8: dst must equal src or not overlap it");
+    const int plane = w * h;
+    const dim3 g((unsigned)std::min(va_cdiv(plane, kJitterPerBlock), VA_COLOR_JITTER_PARTIALS), (unsigned)n);
+    const int vec4 = plane % 4 == 0 && s0 % 4 == 0 && d0 % 4 == 0;
+    if (workspace != nullptr)
+        k_color_jitter_sums<<<g, kJitterThreads, 0, (hipStream_t)stream>>>((const unsigned char*)src, (const float*)table,
+                                                                           (unsigned*)workspace, plane, vec4);
+    k_color_jitter_apply<<<g, kJitterThreads, 0, (hipStream_t)stream>>>((const unsigned char*)src, (const float*)table,
+                                                                        (const float*)lighting, (const unsigned*)workspace,
+                                                                        (unsigned char*)dst, plane, vec4);
     VA_LAUNCH_CHECK();
     return VA_OK;
 }

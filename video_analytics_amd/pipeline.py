@@ -601,6 +601,25 @@ class TwoStreamPipeline(object):
         augment.check_jitter_crops(crops, n * k, H, W, who)
         return videos, labels, plans, crops, tasks
 
+    @staticmethod
+    def _check_jitter(n_snippets, color_jitter, jitter, lighting, rng):
+        """The colour-jitter arguments of ``train_videos``, checked (ValueError) and drawn before anything is enqueued -> the
+        table, CPU float32 ``[n_snippets,8]``, or None."""
+        who = "train_videos"
+        if color_jitter is not None and jitter is not None:
+            raise ValueError("%s: give color_jitter= (parameters to draw from) or jitter= (a table), not both" % who)
+        if color_jitter is not None:
+            try:
+                b, c, s, h = color_jitter
+            except (TypeError, ValueError):
+                raise ValueError("%s: color_jitter must be (brightness, contrast, saturation, hue)" % who)
+            jitter = augment.draw_color_jitter(n_snippets, b, c, s, h, rng)
+        if jitter is not None:
+            augment.check_color_jitter(jitter, n_snippets, who)
+        if lighting is not None:
+            augment.check_lighting(lighting, n_snippets, who)
+        return jitter
+
     def _accumulate_step(self, n, k, micro, labels, tasks, lr, momentum, dropout_seed, clip_norm, data_parallel):
         """-> step(model, x) of ``train_videos`` in its accumulate form: the micro-batches of x ``[n*k,C,224,224]`` through
         ``train_accumulate``, the all-reduce of a data-parallel step, ``train_apply`` -> (stats, descriptors); ``step.norms``
@@ -635,7 +654,8 @@ class TwoStreamPipeline(object):
         return step
 
     def train_videos(self, videos, labels, k=video.N_SEGMENTS, starts=None, crops=None, lr=1e-3, momentum=0.9, dropout_seed=0,
-                     invert_flow_x=False, rng=None, tasks=None, micro_videos=None, clip_norm=None, data_parallel=False):
+                     invert_flow_x=False, rng=None, tasks=None, micro_videos=None, clip_norm=None, data_parallel=False,
+                     color_jitter=None, jitter=None, lighting=None):
         """One TSN training step of both streams on whole videos (Sheet03/notes.txt:165-185, 212-223).
         ``videos``: a list of n ``(rgb u8 [T,3,H,W], gray [T,H,W])`` pairs on the device, one frame size, any lengths;
         ``labels``: their n class indices; ``n*k <= 64``.
@@ -679,10 +699,18 @@ class TwoStreamPipeline(object):
         the micro-batches (rank-major, for the dropout seeds) come from one small all-reduce, each stream's gradient is
         all-reduced once between its last accumulate and its apply (``dist.all_reduce_gradients``), loss and hits are
         all-reduced too, and every rank ends with the same weights.  A bad value or combination raises ValueError before
-        anything is enqueued."""
+        anything is enqueued.
+
+        Colour jitter acts on the spatial stream's input alone, between ``resize_images`` and the step:
+        ``color_jitter=(brightness, contrast, saturation, hue)`` draws one row per snippet from ``rng`` after the starts and
+        the crops (``augment.draw_color_jitter``); ``jitter=`` passes the table itself, CPU float32 ``[n*k,8]``, as ``crops=``
+        does; ``lighting``: CPU float32 ``[n*k,3]`` channel offsets (``augment.draw_lighting``), applied after the jitter.  The
+        result gains ``jitter`` (None when nothing was asked for).  The temporal and the RGB-difference streams are
+        untouched.  With all three at None nothing is drawn and nothing is launched."""
         videos = list(videos)
         micro = self._check_accumulate(len(videos), int(k), micro_videos, clip_norm, data_parallel)
         videos, labels, plans, crops, tasks = self._check_train_videos(videos, labels, k, starts, crops, rng, tasks, micro)
+        jitter = self._check_jitter(len(videos) * int(k), color_jitter, jitter, lighting, rng)
         if micro is not None:
             step = self._accumulate_step(len(videos), int(k), micro, labels, tasks, lr, momentum, dropout_seed, clip_norm, data_parallel)
         elif tasks is None:
@@ -719,6 +747,9 @@ class TwoStreamPipeline(object):
             src = vflow.apply_motion(flow, 1, "stack", self.mean_flow)
         rgb_table, flow_table = augment.snippet_tables(crops, list(range(n * k)), first, L)
         xs = augment.resize_images(frames, rgb_table)
+        if jitter is not None or lighting is not None:  # S35: the spatial stream's input alone, in place
+            table = jitter if jitter is not None else torch.tensor([augment.IDENTITY_JITTER_ROW] * (n * k), dtype=torch.float32)
+            xs = augment.color_jitter(xs, table, lighting, out=xs)
         xt = vflow.resize_flow_to_stack(src, flow_table, invert_x_on_flip=bool(invert_flow_x)).view(n * k, 2 * L, 224, 224)
         cur.wait_stream(self._cnn)   # forwards submitted earlier read the weights this step updates
         cur.wait_stream(self._cnn2)
@@ -738,7 +769,7 @@ class TwoStreamPipeline(object):
         self._cnn.wait_stream(cur)
         self._cnn2.wait_stream(cur)
         return dict(stats_s=stats_s, desc_s=desc_s, stats_t=stats_t, desc_t=desc_t, starts=[list(p.starts) for p in plans],
-                    crops=crops, plans=plans, flow=flow, **extra)
+                    crops=crops, plans=plans, flow=flow, jitter=jitter, **extra)
 
     def wait(self, stream=None):
         """Make ``stream`` (default: the current one) wait for every batch submitted so far."""

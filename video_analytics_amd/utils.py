@@ -4,7 +4,7 @@ Pure-Python string/indexing logic is bit-exact with the reference lines cited pe
 The image transforms restate the torchvision ~0.2 classes the reference composes
 (``getTransforms``, Sheet03/utils.py:137-151) on numpy/torch, because torchvision is not part of this
 stack; they draw from Python's global ``random`` module in the same order as that torchvision
-generation (crop top, crop left, flip).  Training bookkeeping (``makeCheckpoint``, ``savePerformance``) and
+generation (crop top, crop left, flip, then the colour jitter's numbers: DESIGN.md S32).  Training bookkeeping (``makeCheckpoint``, ``savePerformance``) and
 frame extraction (``extractEveryNthFrame``, ``convertVideosToFrames``) are provided too; the reference decodes
 with ``cv2.VideoCapture``, absent here, so ``iterVideoFrames`` reads RIFF/AVI Motion-JPEG itself and refuses
 other codecs by name.
@@ -243,15 +243,173 @@ class RandomHorizontalFlip(object):
         return img
 
 
-class ColorJitter(object):
-    """``ColorJitter(0,0,0,0)`` (Sheet03/parameters.py:21) is the identity and draws no random numbers."""
+# ---- colour jitter: PIL's arithmetic on numpy u8 arrays, op by op ----
 
-    def __init__(self, brightness=0, contrast=0, saturation=0, hue=0):
-        if brightness or contrast or saturation or hue:
-            raise NotImplementedError("only the reference's ColorJitter(0,0,0,0) (identity) is supported")
+JITTER_NONE, JITTER_BRIGHTNESS, JITTER_CONTRAST, JITTER_SATURATION, JITTER_HUE = 0, 1, 2, 3, 4
+
+
+def blendU8(d, v, f):
+    """``Image.blend(degenerate, image, f)`` on u8 values: ``t = d + f*(v - d)`` in float32, multiply then add; for
+    ``0 <= f <= 1`` the result is ``(u8)(int)t``, otherwise 0 where ``t <= 0``, 255 where ``t >= 255``, else ``(int)t``."""
+    f = np.float32(f)
+    d = np.asarray(d).astype(np.int32)
+    v = np.asarray(v).astype(np.int32)
+    t = d.astype(np.float32) + f * (v - d).astype(np.float32)
+    if not (f >= 0 and f <= 1):
+        t = np.clip(t, np.float32(0), np.float32(255))
+    return t.astype(np.int32).astype(np.uint8)
+
+
+def grayLevel(img):
+    """PIL's ``convert('L')`` of an HWC RGB u8 array: ``(19595 R + 38470 G + 7471 B + 32768) >> 16``; an HW array is its
+    own gray level."""
+    a = np.asarray(img)
+    if a.ndim == 2:
+        return a.astype(np.uint8)
+    a = a.astype(np.int64)
+    return ((19595 * a[..., 0] + 38470 * a[..., 1] + 7471 * a[..., 2] + 32768) >> 16).astype(np.uint8)
+
+
+def contrastMean(img):
+    """The gray value contrast blends with: ``(2 S + N) // (2 N)``, S the sum of ``grayLevel`` over the image and N its
+    pixel count (the mean rounded half up, in integers)."""
+    L = grayLevel(img)
+    S, N = int(L.sum(dtype=np.int64)), int(L.size)
+    return (2 * S + N) // (2 * N)
+
+
+def adjustBrightness(img, f):
+    return blendU8(0, img, f)
+
+
+def adjustContrast(img, f, m=None):
+    """``m``: the degenerate gray value; None takes the image's own ``contrastMean``."""
+    return blendU8(contrastMean(img) if m is None else int(m), img, f)
+
+
+def adjustSaturation(img, f):
+    a = np.asarray(img)
+    if a.ndim == 2:
+        return a
+    return blendU8(grayLevel(a)[..., None], a, f)
+
+
+def rgbToHsv(img):
+    """PIL's ``convert('HSV')`` of an HWC RGB u8 array, with its operand widths: the saturation and the three channel
+    ratios are float32 divisions, the hue expression and ``fmod(h/6 + 1, 1)`` are evaluated in double and rounded to
+    float32, and both scalings by 255 are double products truncated to integers."""
+    a = np.asarray(img).astype(np.int32)
+    r, g, b = a[..., 0], a[..., 1], a[..., 2]
+    mx, mn = np.maximum(r, np.maximum(g, b)), np.minimum(r, np.minimum(g, b))
+    gray = mx == mn
+    cr = np.where(gray, 1, mx - mn).astype(np.float32)
+    s = cr / np.where(gray, 1, mx).astype(np.float32)
+    rc, gc, bc = ((mx - c).astype(np.float32) / cr for c in (r, g, b))
+    rc64, gc64, bc64 = rc.astype(np.float64), gc.astype(np.float64), bc.astype(np.float64)
+    h = np.where(r == mx, bc64 - gc64, np.where(g == mx, 2.0 + rc64 - bc64, 4.0 + gc64 - rc64)).astype(np.float32)
+    h = np.fmod(h.astype(np.float64) / 6.0 + 1.0, 1.0).astype(np.float32)
+    uh = np.clip((h.astype(np.float64) * 255.0).astype(np.int32), 0, 255)
+    us = np.clip((s.astype(np.float64) * 255.0).astype(np.int32), 0, 255)
+    return np.stack([np.where(gray, 0, uh), np.where(gray, 0, us), mx], axis=-1).astype(np.uint8)
+
+
+def _roundHalfAway(x):
+    """C ``round`` of non-negative doubles."""
+    fl = np.floor(x)
+    return fl + ((x - fl) >= 0.5)
+
+
+def hsvToRgb(img):
+    """PIL's HSV -> RGB on an HWC u8 array: ``h6 = h*6/255``, ``i = floor(h6)``, ``f = h6 - i`` and ``fs = s/255`` rounded to
+    float32, the product ``fs*f`` in float32, the rest in double; ``p, q, t`` by C ``round``."""
+    a = np.asarray(img)
+    h, s, v = a[..., 0].astype(np.float64), a[..., 1].astype(np.float64), a[..., 2].astype(np.float64)
+    h6 = h * 6.0 / 255.0
+    i = np.floor(h6)
+    f = (h6 - i).astype(np.float32)
+    fs = (s / 255.0).astype(np.float32)
+    f64, fs64 = f.astype(np.float64), fs.astype(np.float64)
+    p = _roundHalfAway(v * (1.0 - fs64))
+    q = _roundHalfAway(v * (1.0 - (fs * f).astype(np.float64)))
+    t = _roundHalfAway(v * (1.0 - fs64 * (1.0 - f64)))
+    p, q, t = (np.clip(x, 0, 255).astype(np.uint8) for x in (p, q, t))
+    v8, k = a[..., 2], i.astype(np.int32) % 6
+    r = np.choose(k, [v8, q, p, p, t, v8])
+    g = np.choose(k, [t, v8, v8, q, p, p])
+    b = np.choose(k, [p, p, t, v8, v8, q])
+    flat = a[..., 1] == 0
+    return np.stack([np.where(flat, v8, r), np.where(flat, v8, g), np.where(flat, v8, b)], axis=-1).astype(np.uint8)
+
+
+def hueShift(hueFactor):
+    """``(int)(hue_factor * 255)``, truncated toward zero, modulo 256: the u8 wrap-around add of the hue plane."""
+    return int(hueFactor * 255) % 256
+
+
+def adjustHue(img, shift):
+    """``shift``: the integer of ``hueShift``."""
+    a = np.asarray(img)
+    if a.ndim == 2:
+        return a
+    hsv = rgbToHsv(a)
+    hsv[..., 0] = (hsv[..., 0].astype(np.int32) + int(shift)) & 255
+    return hsvToRgb(hsv)
+
+
+def applyLighting(img, off):
+    """PCA lighting: ``(u8) rint(clamp((float)v + off_c, 0, 255))`` with one float32 offset per channel of an HWC array."""
+    a = np.asarray(img).astype(np.float32) + np.asarray(off, dtype=np.float32)
+    return np.rint(np.clip(a, np.float32(0), np.float32(255))).astype(np.uint8)
+
+
+def checkColorJitter(brightness, contrast, saturation, hue):
+    """torchvision's parameter rules: ValueError unless brightness, contrast, saturation >= 0 and 0 <= hue <= 0.5."""
+    for name, p in (("brightness", brightness), ("contrast", contrast), ("saturation", saturation)):
+        if not p >= 0:
+            raise ValueError("ColorJitter: %s must be >= 0, got %r" % (name, p))
+    if not (hue >= 0 and hue <= 0.5):
+        raise ValueError("ColorJitter: hue must lie in [0, 0.5], got %r" % (hue,))
+
+
+def drawColorJitter(rng, brightness, contrast, saturation, hue):
+    """The draws of one image -> ``[(op, value), ...]`` in application order: in the order brightness,
+    contrast, saturation, hue every non-zero parameter draws one number (``uniform(max(0, 1-p), 1+p)``; hue
+    ``uniform(-p, p)``, kept as the integer ``hueShift``), then ``rng.shuffle`` of the active ops.  All zero: no call."""
+    ops = []
+    for op, p in ((JITTER_BRIGHTNESS, brightness), (JITTER_CONTRAST, contrast), (JITTER_SATURATION, saturation)):
+        if p:
+            ops.append((op, rng.uniform(max(0, 1 - p), 1 + p)))
+    if hue:
+        ops.append((JITTER_HUE, hueShift(rng.uniform(-hue, hue))))
+    if ops:
+        rng.shuffle(ops)
+    return ops
+
+
+def applyColorJitter(img, ops):
+    """``ops``: ``[(op, value), ...]`` as ``drawColorJitter`` gives them, applied in order to an HWC or HW u8 array."""
+    fn = {JITTER_BRIGHTNESS: adjustBrightness, JITTER_CONTRAST: adjustContrast, JITTER_SATURATION: adjustSaturation,
+          JITTER_HUE: adjustHue}
+    a = np.asarray(img)
+    for op, value in ops:
+        if op != JITTER_NONE:
+            a = fn[op](a, value)
+    return a
+
+
+class ColorJitter(object):
+    """``transforms.ColorJitter`` on HWC (RGB) or HW ('L') u8 arrays: PIL's arithmetic, this project's
+    draw order.  On an HW array brightness and contrast act on the plane, saturation and hue leave it as it is.
+    ``ColorJitter(0,0,0,0)`` (Sheet03/parameters.py:21) is the identity and draws no random numbers."""
+
+    def __init__(self, brightness=0, contrast=0, saturation=0, hue=0, rng=None):
+        checkColorJitter(brightness, contrast, saturation, hue)
+        self.params = (brightness, contrast, saturation, hue)
+        self.rng = rng
 
     def __call__(self, img):
-        return img
+        ops = drawColorJitter(random if self.rng is None else self.rng, *self.params)
+        return applyColorJitter(img, ops) if ops else img
 
 
 class ToTensor(object):

@@ -424,6 +424,31 @@ int va_conv3x3_layer(va_ctx* ctx, int dtype, int kernel_opt, int hw, int cin_pad
                      const void* zeros, void* out, char* kernel_name, int name_len, void* stream);
 
 /*
+ * The model's first stage alone -- the input conversion, where the path has one, then conv layer 0 -- through the very
+ * function va_vgg16_forward runs first (same dispatch on the model's dtype, c_in, VA_OPT_BF16_FIRST_LAYER,
+ * VA_OPT_BF16_VARIANT, VA_OPT_F32_CONV_KERNEL and the alignment of x), for tests of the layer against a reference.
+ * x, x_is_u8, batch: as va_vgg16_forward's; x needs only the alignment of its element type (a bf16 model with
+ * c_in <= 21 whose x is not 16-byte aligned takes the staged path, as in va_vgg16_forward).
+ * out: NHWC [batch][224][224][64] of the model's dtype (f32 / bf16): relu(conv(x, w0) + b0), stored by the convolution
+ * kernel itself.  staged: the converted input of the staging paths, written by the conversion kernel: fp32 models f32
+ * [batch][224*224][c_in_pad] (c_in rounded up to 16; channels >= c_in zero); bf16 models bf16 [batch][224*224][64]:
+ * c_in >= 22: the channels, zero from c_in on; c_in <= 21: channel kx*c_in + c = channel c of pixel x + kx - 1 (zero
+ * outside the row), zero from 3*c_in on.  The fused bf16 first layer (k_conv1_fused_bf16) does not touch it.
+ * info: HOST buffer of info_len bytes or NULL; receives what ran, e.g. "k_conv1_fused_bf16<u8>",
+ * "k_nchw_to_nhwc_xcol<float>+k_conv3x3_mfma_bf16<1,false,false,3>", "k_nchw_to_nhwc_pad<u8,float>+k_conv3x3_mfma<2,2,2,1,false,16>".
+ * VA_ERR_INVALID before anything is launched: NULL model/x/staged/out, batch < 1 (or beyond va_vgg16_forward's limits: 4096;
+ * bf16 models 334), u8 input to a model created without in_mean/in_std, staged or out not 16-byte aligned.
+ * Non-finite inputs: k_conv1_fused_bf16 turns a NaN or infinity in pixel (y, x) of one channel into NaN outputs at the
+ * 3 x 3 pixels around it (its ReLU keeps a NaN).  It multiplies the tail of its 16-element K blocks -- the first
+ * KROW - 3 Cp channels of the pixel after the three taps -- with zero weights, so the NaN also reaches column x - 2 of rows
+ * y - 1 .. y + 1 and, when x % 16 == 15, column x + 16 of rows y - 2 .. y (the patch row of the brick to the right
+ * wraps); every other output keeps its bits, and finite inputs are not affected.  The other conv kernels apply ReLU as
+ * fmaxf(v, 0), which answers 0 for a NaN: on the staged paths, and in every later layer, a NaN pre-activation becomes 0.
+ */
+int va_vgg16_first_layer(va_vgg16* model, const void* x, int x_is_u8, int batch,
+                         void* staged, void* out, char* info, int info_len, void* stream);
+
+/*
  * The kernels of the training step (va_vgg16_train_step), one layer at a time, through the very functions the step
  * calls, for kernel-by-kernel tests.  fp32 throughout; every pointer 16-byte aligned; shapes the kernels do not take are
  * VA_ERR_INVALID before anything is launched.  `info`: HOST buffer of info_len bytes or NULL; receives what ran.

@@ -27,7 +27,7 @@ EXPORTS = [
     "va_meter_update", "va_meter_average", "va_linear_svm_predict",
     "va_vgg16_train_init", "va_vgg16_train_workspace_bytes", "va_vgg16_train_step",
     "va_vgg16_export_state", "va_vgg16_import_state", "va_vgg16_train_plan",
-    "va_conv3x3_layer",
+    "va_conv3x3_layer", "va_vgg16_first_layer",
     "va_flow_to_stack_resize", "va_resize_images_u8", "va_vgg16_train_step_consensus",
     "va_flow_homography", "va_flow_compensate",
     "va_rgbdiff_to_stack", "va_fuse_scores_n",
@@ -193,6 +193,8 @@ def lib():
     L.va_vgg16_import_state.restype = ci
     L.va_conv3x3_layer.argtypes = [vp, ci, ci, ci, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, ctypes.c_char_p, ci, vp]
     L.va_conv3x3_layer.restype = ci
+    L.va_vgg16_first_layer.argtypes = [vp, vp, ci, ci, vp, vp, ctypes.c_char_p, ci, vp]
+    L.va_vgg16_first_layer.restype = ci
     L.va_train_conv_backward_layer.argtypes = [vp, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, cf, cf, vp, vp, vp, vp, vp, vp,
                                                ctypes.POINTER(sz), ctypes.c_char_p, ci, vp]
     L.va_train_conv_backward_layer.restype = ci

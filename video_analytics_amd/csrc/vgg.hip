@@ -727,7 +727,10 @@ __global__ void __launch_bounds__(256, NBUF == 1 ? 4 : 2) k_conv3x3_mfma_bf16(Co
 //     outside the image) to bf16 in LDS, pixel-major with Cp = C rounded up to 4 channels per pixel: the 3 Cp values of
 //     the pixels x-1, x, x+1 of one patch row are then CONTIGUOUS -- they are row ky of the pixel's im2col line
 //     (element kx Cp + c), and an MFMA fragment is 8 consecutive elements of that run (two ds_read_b64; a run is rounded
-//     up to KROW = 16-element blocks whose tail reads the next pixels' finite values against zero weights);
+//     up to KROW = 16-element blocks whose tail reads the next pixels' finite values against zero weights: the first
+//     KROW - 3 Cp channels of patch pixel x + 2, and for the brick's last column patch pixel 0 of the NEXT patch row.
+//     A NaN or infinity at image pixel (y, x) therefore makes NaN, besides the 3 x 3 outputs around it, column x - 2
+//     of rows y - 1 .. y + 1 and, when x % 16 == 15, column x + 16 of rows y - 2 .. y; finite inputs are unaffected);
 //   * holds the packed weights [64][3][KROW] in LDS (k_pack_conv_w_bf16_f1);
 //   * multiplies with the WEIGHTS as the MFMA's first operand: a lane then owns four consecutive output channels of one
 //     pixel per accumulator quad, packs them to 8 bytes, and the wave transposes its 64 pixels x 64 channels through LDS
@@ -744,6 +747,10 @@ struct Conv1Args {
 };
 
 constexpr int kF1MaxCp = 24, kF1MaxKrow = 80;
+
+// ReLU of the fused first layer: fmaxf answers its OTHER operand for a NaN, which would turn a NaN pre-activation -- a
+// non-finite input pixel -- into a plausible 0.  The same bits as fmaxf(v, 0) for every other v.
+__device__ __forceinline__ float relu_keep_nan(float v) { return v != v ? v : fmaxf(v, 0.0f); }
 
 __global__ void k_pack_conv_w_bf16_f1(const float* __restrict__ w, __bf16* __restrict__ wp, int Cout, int Cin, int Cp, int KROW)
 {
@@ -870,10 +877,10 @@ __global__ void __launch_bounds__(256) k_conv1_fused_bf16(Conv1Args a)
 #pragma unroll
             for (int mt = 0; mt < 2; ++mt) {
                 bf16x4 v;
-                v.x = (__bf16)fmaxf(acc[mt][nt][4 * g4 + 0] + bs.x, 0.0f);
-                v.y = (__bf16)fmaxf(acc[mt][nt][4 * g4 + 1] + bs.y, 0.0f);
-                v.z = (__bf16)fmaxf(acc[mt][nt][4 * g4 + 2] + bs.z, 0.0f);
-                v.w = (__bf16)fmaxf(acc[mt][nt][4 * g4 + 3] + bs.w, 0.0f);
+                v.x = (__bf16)relu_keep_nan(acc[mt][nt][4 * g4 + 0] + bs.x);
+                v.y = (__bf16)relu_keep_nan(acc[mt][nt][4 * g4 + 1] + bs.y);
+                v.z = (__bf16)relu_keep_nan(acc[mt][nt][4 * g4 + 2] + bs.z);
+                v.w = (__bf16)relu_keep_nan(acc[mt][nt][4 * g4 + 3] + bs.w);
                 *(bf16x4*)(ost + (32 * mt + r31) * OST + n) = v;
             }
         }
@@ -2382,6 +2389,71 @@ extern "C" size_t va_vgg16_workspace_bytes(const va_vgg16* m, int batch)
     return plan_ws(m, batch).total;
 }
 
+// The model's first stage: the input conversion, where the path has one, into `staged`, then conv layer 0 into `out`
+// (NHWC [B][224][224][64] of the model's dtype).  va_vgg16_forward and the testing entry point va_vgg16_first_layer both
+// run this, so a test of the entry tests the forward pass's own dispatch:
+//   bf16, c_in <= 21: k_conv1_fused_bf16 straight from the NCHW input (`staged` untouched) when VA_OPT_BF16_FIRST_LAYER is 1
+//     and x is 16-byte aligned (it loads four pixels at a time); otherwise k_nchw_to_nhwc_xcol + three K steps;
+//   bf16, c_in >= 22: k_nchw_to_nhwc_pad to 64 bf16 channels + the 64-channel convolution of VA_OPT_BF16_VARIANT;
+//   fp32: k_nchw_to_nhwc_pad to c_in_pad f32 channels + the convolution of VA_OPT_F32_CONV_KERNEL.
+// `ran` (tests): receives the names of the kernel instantiations launched, joined with '+'; NULL on the model's path.
+struct FirstStageInfo {
+    char text[160];
+};
+
+static int run_first_stage(va_vgg16* m, const void* x, int x_is_u8, int B, void* staged, void* out, hipStream_t st,
+                           FirstStageInfo* ran)
+{
+    const int HW0 = 224 * 224;
+    const unsigned pgrid = (unsigned)(B * ((HW0 + 63) / 64));  // one workgroup per 64 pixels
+    const char* conv = nullptr;
+    const char** launched = ran ? &conv : nullptr;
+    const char* stage = nullptr;
+    if (ran) ran->text[0] = 0;
+    if (m->dtype == VA_DTYPE_BF16) {
+        if (m->conv[0].xcol && m->bf16_first == 1 && m->wp_f1 != nullptr && ((uintptr_t)x & 15) == 0) {  // (it loads four pixels at a time)
+            // the first layer straight from the NCHW input (no staged 64-channel copy of the input)
+            Conv1Args c1{x, m->wp_f1, m->conv[0].bias, (__bf16*)out, m->in_mean, m->in_std, B, m->c_in, m->f1_cp, m->f1_krow};
+            const unsigned g1 = (unsigned)(B * (224 / 16) * (224 / 16));
+            if (x_is_u8) k_conv1_fused_bf16<unsigned char><<<g1, 256, 0, st>>>(c1);
+            else k_conv1_fused_bf16<float><<<g1, 256, 0, st>>>(c1);
+            VA_LAUNCH_CHECK();
+            if (ran) snprintf(ran->text, sizeof(ran->text), "%s", x_is_u8 ? "k_conv1_fused_bf16<u8>" : "k_conv1_fused_bf16<float>");
+            return VA_OK;
+        }
+        if (m->conv[0].xcol) {
+            if (x_is_u8)
+                k_nchw_to_nhwc_xcol<unsigned char><<<pgrid, 256, 0, st>>>((const unsigned char*)x, (__bf16*)staged, B, m->c_in, 224, HW0, m->in_mean, m->in_std);
+            else
+                k_nchw_to_nhwc_xcol<float><<<pgrid, 256, 0, st>>>((const float*)x, (__bf16*)staged, B, m->c_in, 224, HW0, nullptr, nullptr);
+            stage = x_is_u8 ? "k_nchw_to_nhwc_xcol<u8>" : "k_nchw_to_nhwc_xcol<float>";
+        } else if (x_is_u8) {
+            k_nchw_to_nhwc_pad<unsigned char, __bf16><<<pgrid, 256, 0, st>>>((const unsigned char*)x, (__bf16*)staged, B, m->c_in, HW0, m->c_in_pad, m->in_mean, m->in_std);
+            stage = "k_nchw_to_nhwc_pad<u8,__bf16>";
+        } else {
+            k_nchw_to_nhwc_pad<float, __bf16><<<pgrid, 256, 0, st>>>((const float*)x, (__bf16*)staged, B, m->c_in, HW0, m->c_in_pad, nullptr, nullptr);
+            stage = "k_nchw_to_nhwc_pad<float,__bf16>";
+        }
+        VA_LAUNCH_CHECK();
+        if (int rc = launch_conv_bf16(m->conv[0], m->zeros, m->bf16_variant, (const __bf16*)staged, out, false, B, m->ctx->n_cu, st, launched)) return rc;
+    } else {
+        if (x_is_u8) {
+            k_nchw_to_nhwc_pad<unsigned char, float><<<pgrid, 256, 0, st>>>((const unsigned char*)x, (float*)staged, B, m->c_in, HW0, m->c_in_pad, m->in_mean, m->in_std);
+            stage = "k_nchw_to_nhwc_pad<u8,float>";
+        } else {
+            k_nchw_to_nhwc_pad<float, float><<<pgrid, 256, 0, st>>>((const float*)x, (float*)staged, B, m->c_in, HW0, m->c_in_pad, nullptr, nullptr);
+            stage = "k_nchw_to_nhwc_pad<float,float>";
+        }
+        VA_LAUNCH_CHECK();
+        const ConvLayer& L = m->conv[0];
+        if (int rc = launch_conv_ex(L.hw, L.cin_pad, L.cout, L.wp, L.bias, (const float*)staged, (float*)out, nullptr, 0, L.pool, B,
+                                    m->zeros_f32, m->f32_conv, st, launched))
+            return rc;
+    }
+    if (ran) snprintf(ran->text, sizeof(ran->text), "%s+%s", stage, conv ? conv : "");
+    return VA_OK;
+}
+
 extern "C" int va_vgg16_forward(va_vgg16* m, const void* x, int x_is_u8, int batch, void* feat, void* desc, void* logits,
                                 void* workspace, size_t workspace_bytes, void* stream)
 {
@@ -2401,41 +2473,18 @@ extern "C" int va_vgg16_forward(va_vgg16* m, const void* x, int x_is_u8, int bat
     float* act[2] = {(float*)(ws + wp.off_act[0]), (float*)(ws + wp.off_act[1])};
     float* slab = (float*)(ws + wp.off_slab);
     float* fcbuf[2] = {(float*)(ws + wp.off_fc[0]), (float*)(ws + wp.off_fc[1])};
-    const int B = batch, HW0 = 224 * 224;
-    const unsigned pgrid = (unsigned)(B * ((HW0 + 63) / 64));  // one workgroup per 64 pixels
-    int cur = 1;
+    const int B = batch;
+    // the input conversion (act[1]) and conv layer 0 (act[0])
+    if (int rc = run_first_stage(m, x, x_is_u8, B, act[1], act[0], st, nullptr)) return rc;
+    int cur = 0;
     if (m->dtype == VA_DTYPE_BF16) {
         // bf16 activations live in the same two ping-pong buffers (half their size is used)
-        int first = 0;
-        if (m->conv[0].xcol && m->bf16_first == 1 && m->wp_f1 != nullptr && ((uintptr_t)x & 15) == 0) {  // (it loads four pixels at a time)
-            // the first layer straight from the NCHW input (no staged 64-channel copy of the input)
-            Conv1Args c1{x, m->wp_f1, m->conv[0].bias, (__bf16*)act[0], m->in_mean, m->in_std, B, m->c_in, m->f1_cp, m->f1_krow};
-            const unsigned g1 = (unsigned)(B * (224 / 16) * (224 / 16));
-            if (x_is_u8) k_conv1_fused_bf16<unsigned char><<<g1, 256, 0, st>>>(c1);
-            else k_conv1_fused_bf16<float><<<g1, 256, 0, st>>>(c1);
-            first = 1;
-            cur = 0;
-        } else if (m->conv[0].xcol) {
-            if (x_is_u8)
-                k_nchw_to_nhwc_xcol<unsigned char><<<pgrid, 256, 0, st>>>((const unsigned char*)x, (__bf16*)act[1], B, m->c_in, 224, HW0, m->in_mean, m->in_std);
-            else
-                k_nchw_to_nhwc_xcol<float><<<pgrid, 256, 0, st>>>((const float*)x, (__bf16*)act[1], B, m->c_in, 224, HW0, nullptr, nullptr);
-        } else if (x_is_u8)
-            k_nchw_to_nhwc_pad<unsigned char, __bf16><<<pgrid, 256, 0, st>>>((const unsigned char*)x, (__bf16*)act[1], B, m->c_in, HW0, m->c_in_pad, m->in_mean, m->in_std);
-        else
-            k_nchw_to_nhwc_pad<float, __bf16><<<pgrid, 256, 0, st>>>((const float*)x, (__bf16*)act[1], B, m->c_in, HW0, m->c_in_pad, nullptr, nullptr);
-        VA_LAUNCH_CHECK();
-        for (int i = first; i < 13; ++i) {
+        for (int i = 1; i < 13; ++i) {
             if (int rc = launch_conv_bf16(m->conv[i], m->zeros, m->bf16_variant, (const __bf16*)act[cur], act[cur ^ 1], i == 12, B, m->ctx->n_cu, st)) return rc;
             cur ^= 1;
         }
     } else {
-        if (x_is_u8)
-            k_nchw_to_nhwc_pad<unsigned char, float><<<pgrid, 256, 0, st>>>((const unsigned char*)x, act[1], B, m->c_in, HW0, m->c_in_pad, m->in_mean, m->in_std);
-        else
-            k_nchw_to_nhwc_pad<float, float><<<pgrid, 256, 0, st>>>((const float*)x, act[1], B, m->c_in, HW0, m->c_in_pad, nullptr, nullptr);
-        VA_LAUNCH_CHECK();
-        for (int i = 0; i < 13; ++i) {
+        for (int i = 1; i < 13; ++i) {
             if (int rc = launch_conv(m->conv[i], m->zeros_f32, act[cur], act[cur ^ 1], B, m->f32_conv, st)) return rc;
             cur ^= 1;
         }
@@ -2448,6 +2497,26 @@ extern "C" int va_vgg16_forward(va_vgg16* m, const void* x, int x_is_u8, int bat
     }
     if (desc || logits) return run_classifier(m, f, B, desc, logits, slab, fcbuf, st);
     return VA_OK;
+}
+
+extern "C" int va_vgg16_first_layer(va_vgg16* m, const void* x, int x_is_u8, int batch, void* staged, void* out, char* info,
+                                    int info_len, void* stream)
+{
+    if (info && info_len > 0) info[0] = 0;
+    VA_CHECK_ARG(m != nullptr, "va_vgg16_first_layer: model is NULL");
+    VA_USE_DEVICE(m->ctx);
+    VA_CHECK_ARG(x != nullptr && staged != nullptr && out != nullptr, "va_vgg16_first_layer: NULL x/staged/out");
+    VA_CHECK_ARG(batch >= 1 && batch <= 4096, "va_vgg16_first_layer: batch %d out of range [1,4096]", batch);
+    VA_CHECK_ARG(!x_is_u8 || (m->in_mean && m->in_std), "va_vgg16_first_layer: u8 input needs in_mean/in_std at create time");
+    VA_CHECK_ARG(x_is_u8 || ((uintptr_t)x & 3) == 0, "va_vgg16_first_layer: f32 x must be 4-byte aligned");
+    VA_CHECK_ARG((((uintptr_t)staged | (uintptr_t)out) & 15) == 0, "va_vgg16_first_layer: staged and out must be 16-byte aligned");
+    // va_vgg16_forward's bf16 limit (launch_conv_bf16: 32-bit byte offsets into a layer's activations), before the fused kernel too
+    VA_CHECK_ARG(m->dtype != VA_DTYPE_BF16 || ((long)batch * 224 * 224 + 2L * 225) * 64 * 2 < 2147483647L,
+                 "va_vgg16_first_layer (bf16): batch %d x 224x224x64 activations exceed 2 GiB of 32-bit buffer offsets: split the batch", batch);
+    FirstStageInfo ran;
+    const int rc = run_first_stage(m, x, x_is_u8, batch, staged, out, (hipStream_t)stream, &ran);
+    if (rc == VA_OK && info && info_len > 0) snprintf(info, (size_t)info_len, "%s", ran.text);
+    return rc;
 }
 
 extern "C" int va_vgg16_set_option(va_vgg16* m, int option, int value)

@@ -189,6 +189,28 @@ class Vgg16Stream(object):
                                       _ffi.ptr(ws), ws.numel(), _ffi.stream_ptr(self.device)))
         return feat
 
+    def first_layer(self, x, staged, out):
+        """The model's first stage alone (``va_vgg16_first_layer``, a testing entry point): the input conversion, where the
+        path has one, into ``staged``, then conv layer 0 into ``out``, through the function ``forward`` runs first.
+        x: CUDA float32 / uint8 ``[B,C,224,224]`` (any alignment of its element type); out: NHWC ``[B,224,224,64]`` of the
+        model's dtype; staged: ``[B,224*224,c_in_pad]`` float32 (fp32 models) or ``[B,224*224,64]`` bfloat16.  Returns the
+        names of the kernel instantiations that ran.  Enqueued on the current stream; nothing is synchronised."""
+        tdt = torch.bfloat16 if self.dtype == "bf16" else torch.float32
+        if (not isinstance(x, torch.Tensor) or not x.is_cuda or x.dim() != 4 or tuple(x.shape[1:]) != (self.c_in, 224, 224)
+                or x.dtype not in (torch.float32, torch.uint8) or not x.is_contiguous()):
+            raise ValueError("Vgg16Stream.first_layer: x must be a contiguous CUDA float32/uint8 [B,%d,224,224]" % self.c_in)
+        B = int(x.shape[0])
+        cpad = 64 if self.dtype == "bf16" else (self.c_in + 15) // 16 * 16
+        for name, t, shape in (("staged", staged, (B, 224 * 224, cpad)), ("out", out, (B, 224, 224, 64))):
+            if (not isinstance(t, torch.Tensor) or t.dtype != tdt or tuple(t.shape) != shape or not t.is_contiguous()):
+                raise ValueError("Vgg16Stream.first_layer: %s must be a contiguous %s tensor %s" % (name, tdt, shape))
+            self._on_my_device(t, "first_layer")
+        self._on_my_device(x, "first_layer")
+        info = ctypes.create_string_buffer(160)
+        _ffi.check(_ffi.lib().va_vgg16_first_layer(self._h, _ffi.ptr(x), int(x.dtype == torch.uint8), B, _ffi.ptr(staged),
+                                                   _ffi.ptr(out), info, len(info), _ffi.stream_ptr(self.device)))
+        return info.value.decode()
+
     def classify(self, feat):
         """The classifierList traversal (Sheet03/spatialModel.py:213-218): feat [B,512,7,7] ->
         (featureVectors [B,D] = output of module 8, logits [B,nClasses] = output of module 9)."""

@@ -356,6 +356,29 @@ int va_color_jitter_u8(va_ctx* ctx, const void* src, int n, int w, int h, const 
                        void* workspace, void* stream);
 
 /*
+ * Decoded frames -> the pipeline's inputs: PIL's Image.resize((out_w, out_h), BILINEAR) of every RGB
+ * frame and its convert('L'), bit for bit.  src u8 [n][3][h][w] (src_nhwc: [n][h][w][3]) -> rgb_out u8 [n][3][out_h][out_w],
+ * always planar, and gray_out u8 [n][out_h][out_w], gray = (19595 R + 38470 G + 7471 B + 32768) >> 16 of rgb_out.  The
+ * resize is PIL's 8-bit two-pass resample: the horizontal pass into a u8 intermediate, then the vertical pass, a pass whose
+ * length does not change being skipped; out = clamp((2^21 + sum_j p[lo + j] k_j) >> 22, 0, 255) in int32.
+ *   x_bounds, y_bounds: DEVICE i32 [out][2] = {lo, count} per output sample of the axis; x_taps, y_taps: DEVICE i32
+ *   [out][ksize], ksize = 2 ceil(max(in / out, 1)) + 1, the taps k_j in units of 2^-22 (built on the host in float64:
+ *   video_analytics_amd/frames.py, resample_table).  The tables of a skipped pass are NULL.  The kernels keep every read
+ *   inside the input whatever a table holds.
+ *   rgb_out may be NULL only when the size is unchanged and src is planar (the frames are their own result); non-NULL
+ *   there, it receives a copy.  No buffer needs more than byte alignment; the tables are 4-byte aligned.
+ *   workspace: DEVICE, va_frames_prepare_workspace_bytes(...) bytes, the [n][3][h][out_w] intermediate when both passes run
+ *   (0 otherwise); too small: VA_ERR_WORKSPACE.
+ * Any n that one launch holds (n is folded into the grid's x dimension); every plane below 2^31 / 3 pixels.  A downscale
+ * factor above 16 on either axis (ksize > 33), a side below 1, a NULL required buffer: VA_ERR_INVALID before anything is
+ * enqueued.  No allocation, no synchronisation; two launches at most, on the caller's stream.
+ */
+size_t va_frames_prepare_workspace_bytes(int n, int w, int h, int out_w, int out_h);
+int va_frames_prepare(va_ctx* ctx, const void* src, int n, int w, int h, int src_nhwc, int out_w, int out_h,
+                      const void* x_bounds, const void* x_taps, const void* y_bounds, const void* y_taps, void* rgb_out,
+                      void* gray_out, void* workspace, size_t workspace_bytes, void* stream);
+
+/*
  * Mean flow subtraction, step one: flow f32 [n_pairs][2][h][w] -> means f32 [n_pairs][2], the mean of
  * every displacement field's component over the full frame.  Each value is clamped to [-32768, 32768] (a NaN becomes
  * -32768) and summed as the exact integer rint(a * 65536) in int64, so the result does not depend on the reduction

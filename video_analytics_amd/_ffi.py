@@ -37,6 +37,7 @@ EXPORTS = [
     "va_vgg16_train_grad_floats", "va_vgg16_train_grad_layout", "va_vgg16_train_accumulate", "va_vgg16_train_apply_workspace_bytes",
     "va_vgg16_train_apply", "va_vgg16_unpack_grad", "va_train_conv_backward_layer_grad", "va_train_fc_backward_layer_grad",
     "va_color_jitter_u8",
+    "va_frames_prepare_workspace_bytes", "va_frames_prepare",
 ]
 
 
@@ -147,6 +148,10 @@ def lib():
     L.va_rgbdiff_to_stack.restype = ci
     L.va_color_jitter_u8.argtypes = [vp, vp, ci, ci, ci, vp, vp, vp, vp, vp]
     L.va_color_jitter_u8.restype = ci
+    L.va_frames_prepare_workspace_bytes.argtypes = [ci, ci, ci, ci, ci]
+    L.va_frames_prepare_workspace_bytes.restype = sz
+    L.va_frames_prepare.argtypes = [vp, vp, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, sz, vp]
+    L.va_frames_prepare.restype = ci
     L.va_score_consensus.argtypes = [vp, vp, ci, ci, ci, ci, vp, vp]
     L.va_score_consensus.restype = ci
     L.va_fuse_scores.argtypes = [vp, vp, vp, ci, ci, cf, cf, vp, vp, vp]

@@ -12,6 +12,7 @@ forward (Sheet03/spatialModel.py:212-218, Sheet03/temporalModel.py:241-247).
 import torch
 
 from . import flow as vflow
+from . import frames as vframes
 from . import augment, fusion, rgbdiff, synth, vgg, video
 from .parameters import (NACTION_CLASSES, NORM_MEANS_TF, NORM_STDS_TF, VIDEO_DESCRIPTOR_DIM,
                          VIDEO_INPUT_FLOW_COUNT)
@@ -383,9 +384,28 @@ class TwoStreamPipeline(object):
             raise ValueError("%s: this pipeline has the heads %s; task= must name the video's head" % (who, heads))
         return vgg.check_task(task, heads, who)
 
-    def _check_video(self, rgb, gray, n_snippets, views, consensus, fusion_weights, crops):
-        """Host-side checks of ``submit_video`` before anything is enqueued -> (plan, rgb_views, flow_views, mode, weights):
-        one fusion weight per stream, None meaning all ones."""
+    @staticmethod
+    def _prepared_shapes(rgb, gray, rescale, who):
+        """``gray=None`` / ``rescale=`` of one video, on the host (ValueError) -> None when the frames are used as they are,
+        else ``(size, rgb_like, gray_like)``: the size ``frames.prepare_frames`` takes and storage-free stand-ins with the
+        shapes it will return, for the shape checks that run before anything is enqueued."""
+        if rescale is not None and gray is not None:
+            raise ValueError("%s: rescale= derives gray from the rescaled rgb (gray=None): a gray rescaled on its own is not "
+                             "the gray of the rescaled frames" % who)
+        if gray is not None:
+            return None
+        n, _, _, oh, ow = vframes.check_frames(rgb, rescale, "NCHW", who)
+        return ((oh, ow), torch.empty((n, 3, oh, ow), dtype=torch.uint8, device="meta"),
+                torch.empty((n, oh, ow), dtype=torch.uint8, device="meta"))
+
+    def _check_video(self, rgb, gray, n_snippets, views, consensus, fusion_weights, crops, rescale=None):
+        """Host-side checks of ``submit_video`` before anything is enqueued -> (plan, rgb_views, flow_views, mode, weights,
+        size): one fusion weight per stream, None meaning all ones; ``size`` is None for frames used as they are, else what
+        ``frames.prepare_frames`` takes (``gray=None`` / ``rescale=``: the checks then see the prepared shapes)."""
+        prep = self._prepared_shapes(rgb, gray, rescale, "submit_video")
+        decoded = rgb
+        if prep is not None:
+            _, rgb, gray = prep
         m = 2 if self.diff is None else 3
         if fusion_weights is None:
             fusion_weights = (1.0,) * m
@@ -404,12 +424,15 @@ class TwoStreamPipeline(object):
             ws = fusion.check_fusion_weights_n(fusion_weights, m, "submit_video")
             plan, rgb_views, flow_views, mode, _, _ = check_video(rgb, gray, self.L, self.motion, n_snippets, views, consensus,
                                                                   (1.0, 1.0), crops)
-        if not rgb.is_cuda or not gray.is_cuda or rgb.device != self.device or gray.device != self.device:
+        if prep is not None:
+            if not decoded.is_cuda or decoded.device != self.device:
+                raise ValueError("submit_video: rgb must be on %s" % (self.device,))
+        elif not rgb.is_cuda or not gray.is_cuda or rgb.device != self.device or gray.device != self.device:
             raise ValueError("submit_video: rgb and gray must be on %s" % (self.device,))
-        return plan, rgb_views, flow_views, mode, ws
+        return plan, rgb_views, flow_views, mode, ws, None if prep is None else prep[0]
 
-    def submit_video(self, rgb, gray, n_snippets=video.N_SNIPPETS, views=None, invert_flow_x=False, consensus="softmax",
-                     fusion_weights=None, crops=None, task=None):
+    def submit_video(self, rgb, gray=None, n_snippets=video.N_SNIPPETS, views=None, invert_flow_x=False, consensus="softmax",
+                     fusion_weights=None, crops=None, task=None, rescale=None):
         """Enqueue one whole video (the test protocol of Sheet03/notes.txt:113-116 and 225-230):
         rgb u8 ``[T,3,H,W]``, gray u8 or f32 ``[T,H,W]``, the frames of one video on the device.  ``n_snippets`` snippets
         are placed by ``video.snippetStarts``; the frame pairs they share go through TV-L1 once each
@@ -434,11 +457,21 @@ class TwoStreamPipeline(object):
         On a pipeline with ``heads`` ``task`` names the video's head and is required: every stream's item
         logits go through ``vgg.head_logits(., heads, task)`` before the consensus and the fusion, so ``scores*`` hold the
         ``heads[task]`` classes of that head and ``pred`` is local to it; ``logits_*_items`` stay full width, and the result
-        gains ``task``.  ``task=`` on a pipeline without heads raises ValueError."""
+        gains ``task``.  ``task=`` on a pipeline without heads raises ValueError.
+
+        Decoded frames: ``gray=None`` derives the gray frames from ``rgb`` on the device, and
+        ``rescale=`` (an int: the short side, torchvision's ``Resize`` rule; or ``(height, width)``) first rescales every
+        frame as PIL's bilinear ``Image.resize`` does (``frames.prepare_frames``); ``views`` are then tables for the new
+        size.  Both run on the current stream ahead of everything else, so the TV-L1 and CNN streams wait for them as they
+        wait for the inputs.  ``rescale=`` with a given ``gray`` raises ValueError.  The result holds ``frame_size``, the
+        ``(height, width)`` TV-L1 and the views saw."""
         task = self._check_task(task, "submit_video")
-        plan, rgb_views, flow_views, mode, fw = self._check_video(rgb, gray, n_snippets, views, consensus, fusion_weights, crops)
+        plan, rgb_views, flow_views, mode, fw, size = self._check_video(rgb, gray, n_snippets, views, consensus, fusion_weights,
+                                                                       crops, rescale)
         dev = self.device
         n, U = plan.n, len(plan.pairs)
+        if gray is None:  # S38: on the current stream, ahead of the gathers and of `ready`
+            rgb, gray = vframes.prepare_frames(rgb, size)
         T, H, W = gray.shape
         cur = torch.cuda.current_stream(dev)
         seq = augment.crops_to_device(torch.tensor(plan.sequences, dtype=torch.int64), dev)
@@ -497,15 +530,16 @@ class TwoStreamPipeline(object):
         self._handed_out.extend(out.values())
         out["starts"] = list(plan.starts)
         out["plan"] = plan
+        out["frame_size"] = (int(H), int(W))
         if task is not None:
             out["task"] = task
         out["done"] = finished
         return out
 
-    def run_video(self, rgb, gray, n_snippets=video.N_SNIPPETS, views=None, invert_flow_x=False, consensus="softmax",
-                  fusion_weights=None, crops=None, task=None):
+    def run_video(self, rgb, gray=None, n_snippets=video.N_SNIPPETS, views=None, invert_flow_x=False, consensus="softmax",
+                  fusion_weights=None, crops=None, task=None, rescale=None):
         """``submit_video`` + ``wait()``: the results are ready on the current stream."""
-        out = self.submit_video(rgb, gray, n_snippets, views, invert_flow_x, consensus, fusion_weights, crops, task)
+        out = self.submit_video(rgb, gray, n_snippets, views, invert_flow_x, consensus, fusion_weights, crops, task, rescale)
         self.wait()
         return out
 
@@ -536,10 +570,12 @@ class TwoStreamPipeline(object):
             raise ValueError("%s: no videos" % who)
         return int(micro_videos)
 
-    def _check_train_videos(self, videos, labels, k, starts, crops, rng, tasks=None, micro=None):
-        """Host-side checks and draws of ``train_videos`` before anything is enqueued -> (videos, labels, plans, crops, tasks);
-        ``tasks`` is None on a pipeline without heads.  ``micro``: videos per micro-batch (``_check_accumulate``), which lifts
-        the limit on ``n*k``."""
+    def _check_train_videos(self, videos, labels, k, starts, crops, rng, tasks=None, micro=None, rescale=None):
+        """Host-side checks and draws of ``train_videos`` before anything is enqueued -> (videos, labels, plans, crops, tasks,
+        sizes); ``tasks`` is None on a pipeline without heads.  ``micro``: videos per micro-batch (``_check_accumulate``),
+        which lifts the limit on ``n*k``.  ``videos`` comes back as ``(rgb, gray)`` pairs, gray None where it is to be derived;
+        ``sizes[i]`` is then what ``frames.prepare_frames`` takes for video i (None for a video used as it is), and every
+        shape check has seen the prepared shapes."""
         who = "train_videos"
         heads = getattr(self, "heads", None)
         if heads is None and tasks is not None:
@@ -554,24 +590,33 @@ class TwoStreamPipeline(object):
             raise ValueError("%s: %d videos x %d snippets out of range (n*k in 1..64)" % (who, n, k))
         if heads is not None:  # S26: one head per video, labels local to it
             labels, tasks = vgg.check_tasks(labels, tasks, heads, n, who)
-        for v in videos:
+        given = [(v, None) if isinstance(v, torch.Tensor) else v for v in videos]  # a bare rgb tensor: gray is derived
+        videos, sizes, on_device = [], [], []  # what the shape checks see (S38: the prepared shapes) and how each video gets there
+        for v in given:
             if not isinstance(v, (tuple, list)) or len(v) != 2:
-                raise ValueError("%s: videos must be a list of (rgb u8 [T,3,H,W], gray [T,H,W]) pairs" % who)
+                raise ValueError("%s: videos must be a list of (rgb u8 [T,3,H,W], gray [T,H,W]) pairs, (rgb, None) or rgb "
+                                 "alone" % who)
             rgb, gray = v
             if not isinstance(rgb, torch.Tensor) or rgb.dtype != torch.uint8 or rgb.dim() != 4 or rgb.shape[1] != 3:
                 raise ValueError("%s: rgb must be a uint8 [T,3,H,W] tensor" % who)
+            prep = self._prepared_shapes(rgb, gray, rescale, who)
+            on_device += [rgb] if prep is not None else [rgb, gray]
+            if prep is not None:
+                _, rgb, gray = prep
             if not isinstance(gray, torch.Tensor) or gray.dim() != 3 or gray.dtype not in (torch.uint8, torch.float32):
                 raise ValueError("%s: gray must be a uint8 or float32 [T,H,W] tensor" % who)
             if gray.shape[0] != rgb.shape[0]:
                 raise ValueError("%s: %d rgb frames but %d gray frames" % (who, rgb.shape[0], gray.shape[0]))
-            if not rgb.is_cuda or not gray.is_cuda or rgb.device != self.device or gray.device != self.device:
-                raise ValueError("%s: rgb and gray must be on %s" % (who, self.device))
+            videos.append((rgb, gray))
+            sizes.append(None if prep is None else prep[0])
             if (tuple(rgb.shape[2:]) != tuple(videos[0][0].shape[2:]) or tuple(gray.shape[1:]) != tuple(videos[0][1].shape[1:])
                     or gray.dtype != videos[0][1].dtype):
                 raise ValueError("%s: the videos of one step must share their frame size and gray dtype" % who)
         if tuple(videos[0][0].shape[2:]) != tuple(videos[0][1].shape[1:]):
             raise ValueError("%s: one crop serves a snippet's RGB frame and flow planes: rgb and gray frames must have one "
                              "size" % who)
+        if any(not isinstance(t, torch.Tensor) or not t.is_cuda or t.device != self.device for t in on_device):
+            raise ValueError("%s: rgb and gray must be on %s" % (who, self.device))
         H, W = (int(d) for d in videos[0][1].shape[1:])
         if not isinstance(labels, torch.Tensor):
             try:
@@ -599,7 +644,7 @@ class TwoStreamPipeline(object):
         if crops is None:
             crops = augment.draw_scale_jitter_crops(n * k, H, W, rng)
         augment.check_jitter_crops(crops, n * k, H, W, who)
-        return videos, labels, plans, crops, tasks
+        return [tuple(v) for v in given], labels, plans, crops, tasks, sizes
 
     @staticmethod
     def _check_jitter(n_snippets, color_jitter, jitter, lighting, rng):
@@ -655,7 +700,7 @@ class TwoStreamPipeline(object):
 
     def train_videos(self, videos, labels, k=video.N_SEGMENTS, starts=None, crops=None, lr=1e-3, momentum=0.9, dropout_seed=0,
                      invert_flow_x=False, rng=None, tasks=None, micro_videos=None, clip_norm=None, data_parallel=False,
-                     color_jitter=None, jitter=None, lighting=None):
+                     color_jitter=None, jitter=None, lighting=None, rescale=None):
         """One TSN training step of both streams on whole videos (Sheet03/notes.txt:165-185, 212-223).
         ``videos``: a list of n ``(rgb u8 [T,3,H,W], gray [T,H,W])`` pairs on the device, one frame size, any lengths;
         ``labels``: their n class indices; ``n*k <= 64``.
@@ -706,11 +751,19 @@ class TwoStreamPipeline(object):
         the crops (``augment.draw_color_jitter``); ``jitter=`` passes the table itself, CPU float32 ``[n*k,8]``, as ``crops=``
         does; ``lighting``: CPU float32 ``[n*k,3]`` channel offsets (``augment.draw_lighting``), applied after the jitter.  The
         result gains ``jitter`` (None when nothing was asked for).  The temporal and the RGB-difference streams are
-        untouched.  With all three at None nothing is drawn and nothing is launched."""
+        untouched.  With all three at None nothing is drawn and nothing is launched.
+
+        Decoded frames: an entry of ``videos`` may be ``(rgb, None)`` or ``rgb`` alone; its gray frames
+        are then derived on the device, after ``rescale=`` (an int: the short side; or ``(height, width)``) has rescaled its
+        frames (``frames.prepare_frames``).  The crops are drawn and checked for the new size, and colour jitter still acts
+        on the spatial input alone: the gray frames come from the prepared frames, before it.  ``rescale=`` with an entry
+        that brings its own gray raises ValueError."""
         videos = list(videos)
         micro = self._check_accumulate(len(videos), int(k), micro_videos, clip_norm, data_parallel)
-        videos, labels, plans, crops, tasks = self._check_train_videos(videos, labels, k, starts, crops, rng, tasks, micro)
+        videos, labels, plans, crops, tasks, sizes = self._check_train_videos(videos, labels, k, starts, crops, rng, tasks, micro,
+                                                                               rescale)
         jitter = self._check_jitter(len(videos) * int(k), color_jitter, jitter, lighting, rng)
+        videos = [v if v[1] is not None else vframes.prepare_frames(v[0], size) for v, size in zip(videos, sizes)]  # S38
         if micro is not None:
             step = self._accumulate_step(len(videos), int(k), micro, labels, tasks, lr, momentum, dropout_seed, clip_norm, data_parallel)
         elif tasks is None:

@@ -131,7 +131,10 @@ def evaluateVideos(pipe, videos, labels, **kw):
     difference) and ``fusion_weights`` of three entries.
 
     On a pipeline with ``heads`` ``task=`` travels through ``kw`` to ``submit_video``: the videos of one
-    call belong to one dataset, the scores are that head's and ``labels`` are local to it."""
+    call belong to one dataset, the scores are that head's and ``labels`` are local to it.
+
+    Decoded frames: an entry of ``videos`` may be ``(rgb, None)`` or ``rgb`` alone, and ``rescale=`` travels
+    through ``kw``: ``submit_video`` then rescales the frames and derives the gray frames on the device."""
     labels = [int(l) for l in labels]
     rows, pending, n = [], None, 0
     third = getattr(pipe, "diff", None) is not None
@@ -141,7 +144,8 @@ def evaluateVideos(pipe, videos, labels, **kw):
         out["done"].synchronize()
         rows.append(tuple(out[key].cpu().numpy() for key in keys))
 
-    for rgb, gray in videos:
+    for v in videos:
+        rgb, gray = v if isinstance(v, (tuple, list)) else (v, None)
         out = pipe.submit_video(rgb, gray, **kw)
         n += 1
         if pending is not None:

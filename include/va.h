@@ -34,6 +34,9 @@
  *                     inputs of the two-stream paper (no reference counterpart).
  *   va_flow_homography, va_flow_compensate   warped optical flow, TSN's camera-compensated temporal input
  *                     (Sheet03/notes.txt:187-194; no reference code): DESIGN.md S21, S22.
+ *   va_flow_quantize_u8, va_flowq_to_stack_snippets, va_flowq_to_stack_resize   stored optical flow: the flow images the
+ *                     reference reads are computed once (Sheet03/temporalModel.py:76-81, Sheet03/parameters.py:27), as
+ *                     TSN's are (Sheet03/notes.txt:196-199, 245-250); these keep them on the device: DESIGN.md S39-S41.
  *   va_validate_batch the loss / argmax / correct-count lines of validate():
  *                     Sheet03/spatialModel.py:219-221.
  *   va_meter_*        the per-video AverageMeter collation of validate():
@@ -312,6 +315,34 @@ int va_flow_to_stack_resize(va_ctx* ctx, const void* flow, int n_pairs, int w, i
                             const void* table, int n_out, int invert_x_on_flip, void* stack, void* stream);
 int va_resize_images_u8(va_ctx* ctx, const void* src, int n, int c, int w, int h, int src_nhwc, const void* table, int n_out,
                         void* dst, void* stream);
+
+/*
+ * Stored optical flow: the flow of a video is computed once and kept, as float32 (the TV-L1 output
+ * itself) or as the 8-bit flow images TSN and the reference's flow JPEGs hold, flowq u8 [n_pairs][2][h][w].
+ *   va_flow_quantize_u8         S39: flow f32 [n_pairs][2][h][w] -> out u8 of the same shape,
+ *                               t = (255.0f*(v + bound)) / (2.0f*bound), q = rintf(fminf(fmaxf(t, 0), 255)): the q of
+ *                               va_flow_to_stack and every flow gather, in their order (a NaN becomes 0).  Any width; flow
+ *                               4-byte aligned, out any alignment (16-byte loads and 4-byte stores where the pointers allow).
+ *   va_flowq_to_stack_snippets  S40: va_flow_to_stack_snippets with flowq as the source: output
+ *                               ((float)q' / 255.0f - mean) / stdv, q' = 255 - q for a flipped x-flow plane under
+ *                               invert_x_on_flip and q otherwise.  Plane addressing, clamping of starts and crops and limits
+ *                               as there; on flowq = va_flow_quantize_u8(flow) the result equals
+ *                               va_flow_to_stack_snippets(flow) bit for bit.  With starts[s] = s*L it covers the views and
+ *                               crop forms as well.
+ *   va_flowq_to_stack_resize    S41: the crop-resize gather in TSN's order, the IMAGE is resampled, not the float field: with
+ *                               the table rows, taps and bilinear form of va_flow_to_stack_resize on the u8 values as floats,
+ *                               qr = rintf(clamp(val, 0, 255)) -- what va_resize_images_u8 writes for the plane, bit for bit
+ *                               -- then q' = 255 - qr under the inversion, then the normalisation.  At ch = cw = 224 it is
+ *                               va_flowq_to_stack_snippets' crop bit for bit; at other sizes it differs from
+ *                               va_flow_to_stack_resize of the float field (which quantises after resampling).
+ * Bad arguments: VA_ERR_INVALID before anything is enqueued.  No allocation, no synchronisation, no atomics.
+ */
+int va_flow_quantize_u8(va_ctx* ctx, const void* flow, int n_pairs, int w, int h, float bound, void* out, void* stream);
+int va_flowq_to_stack_snippets(va_ctx* ctx, const void* flowq, int n_pairs, const void* starts, int n_snippets, int flow_count,
+                               int n_views, int w, int h, float mean, float stdv, const void* crops, int invert_x_on_flip,
+                               int out_w, int out_h, void* stack, void* stream);
+int va_flowq_to_stack_resize(va_ctx* ctx, const void* flowq, int n_pairs, int w, int h, float mean, float stdv,
+                             const void* table, int n_out, int invert_x_on_flip, void* stack, void* stream);
 
 /*
  * The RGB-difference volume, TSN's third input modality (Sheet03/notes.txt:187-191): frames u8

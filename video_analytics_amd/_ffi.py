@@ -38,6 +38,7 @@ EXPORTS = [
     "va_vgg16_train_apply", "va_vgg16_unpack_grad", "va_train_conv_backward_layer_grad", "va_train_fc_backward_layer_grad",
     "va_color_jitter_u8",
     "va_frames_prepare_workspace_bytes", "va_frames_prepare",
+    "va_flow_quantize_u8", "va_flowq_to_stack_snippets", "va_flowq_to_stack_resize",
 ]
 
 
@@ -142,6 +143,12 @@ def lib():
     L.va_flow_to_stack_snippets.restype = ci
     L.va_flow_to_stack_resize.argtypes = [vp, vp, ci, ci, ci, cf, cf, cf, vp, ci, ci, vp, vp]
     L.va_flow_to_stack_resize.restype = ci
+    L.va_flow_quantize_u8.argtypes = [vp, vp, ci, ci, ci, cf, vp, vp]
+    L.va_flow_quantize_u8.restype = ci
+    L.va_flowq_to_stack_snippets.argtypes = [vp, vp, ci, vp, ci, ci, ci, ci, ci, cf, cf, vp, ci, ci, ci, vp, vp]
+    L.va_flowq_to_stack_snippets.restype = ci
+    L.va_flowq_to_stack_resize.argtypes = [vp, vp, ci, ci, ci, cf, cf, vp, ci, ci, vp, vp]
+    L.va_flowq_to_stack_resize.restype = ci
     L.va_resize_images_u8.argtypes = [vp, vp, ci, ci, ci, ci, ci, vp, ci, vp, vp]
     L.va_resize_images_u8.restype = ci
     L.va_rgbdiff_to_stack.argtypes = [vp, vp, ci, ci, ci, ci, ci, fpp, vp, ci, vp, vp]

@@ -9,6 +9,7 @@
 // segments.  No LDS.  Ten-crop evaluation uses the same kernels with V views per source plane.
 #include "va_internal.h"
 #include <algorithm>
+#include <type_traits>
 
 // A crop triple as the kernels use it: offsets clamped to the frame, so that no crop value can address memory outside
 // it (the host wrappers reject such crops before they get here).
@@ -48,8 +49,12 @@ constexpr int kGatherPerBlock = 256 * 4 * kGatherSteps;
 // snippet-major with the V views of a plane adjacent; a plane that the next snippet reads again was last read one
 // snippet earlier, i.e. 2L full-frame planes (6 MB at 320x240) and V*2L streamed output planes (40 MB) ago: those re-reads
 // come from the Infinity Cache, the V re-reads within a snippet from L2.  Everything after the plane's address is shared.
-template <bool SNIPPETS>
-__global__ void __launch_bounds__(256) k_flow_crop_stack(const float* __restrict__ flow, const int* __restrict__ crops,
+//
+// SRC (S40, va_flowq_to_stack_snippets): float is the flow itself; unsigned char is a STORED flow, the 8-bit flow images
+// va_flow_quantize_u8 wrote (S39), i.e. the q of the expressions below computed once and kept.  The u8 form reads q, applies
+// the inversion and the normalisation and so gives the float form's bits; its aligned source run is one 4-byte load.
+template <bool SNIPPETS, typename SRC>
+__global__ void __launch_bounds__(256) k_flow_crop_stack(const SRC* __restrict__ flow, const int* __restrict__ crops,
                                                          const int* __restrict__ starts, int n_pairs,
                                                          float* __restrict__ stack, int w, int h, int out_w, int out_h,
                                                          int chans, int n_views, int invert_x, int vec4, float bound,
@@ -62,36 +67,60 @@ __global__ void __launch_bounds__(256) k_flow_crop_stack(const float* __restrict
     const CropWin cw = load_crop(crops, o, h, w, out_h, out_w);
     const bool inv = invert_x && cw.flip && (c & 1) == 0;
     const int splane = SNIPPETS ? 2 * min(max(starts[b], 0), n_pairs - chans / 2) + c : src;
-    const float* __restrict__ plane = flow + (size_t)splane * h * w + (size_t)cw.top * w;
+    const SRC* __restrict__ plane = flow + (size_t)splane * h * w + (size_t)cw.top * w;
     float* __restrict__ dst = stack + (size_t)o * n;
-    // vec4 bit 1: 16-byte aligned flow, w and out_w multiples of 4; with a left offset of 4k too, every run of 4 outputs
-    // (never split between rows) reads one aligned float4
+    // vec4 bit 1: 16-byte aligned flow (u8: 4-byte aligned), w and out_w multiples of 4; with a left offset of 4k too, every
+    // run of 4 outputs (never split between rows) reads one aligned float4 (u8: one aligned 32-bit word)
     const bool ld4 = (vec4 & 2) && (cw.left & 3) == 0;
 #pragma unroll
     for (int s = 0; s < kGatherSteps; ++s) {
         const int i0 = ((blockIdx.x * kGatherSteps + s) * blockDim.x + threadIdx.x) * 4;
         if (i0 >= n) continue;
         int y = i0 / out_w, x = i0 - y * out_w;
-        float val[4], r[4];
-        if (ld4) {  // the 4 sources are one aligned 16-byte run of row y (reversed when flipped)
-            const int sx = cw.flip ? cw.left + out_w - 4 - x : cw.left + x;
-            const f32x4 f = *reinterpret_cast<const f32x4*>(plane + (size_t)y * w + sx);
+        float r[4];
+        if constexpr (std::is_same<SRC, float>::value) {
+            float val[4];
+            if (ld4) {  // the 4 sources are one aligned 16-byte run of row y (reversed when flipped)
+                const int sx = cw.flip ? cw.left + out_w - 4 - x : cw.left + x;
+                const f32x4 f = *reinterpret_cast<const f32x4*>(plane + (size_t)y * w + sx);
 #pragma unroll
-            for (int k = 0; k < 4; ++k) val[k] = cw.flip ? f[3 - k] : f[k];
-        } else {
+                for (int k = 0; k < 4; ++k) val[k] = cw.flip ? f[3 - k] : f[k];
+            } else {
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const int sx = cw.left + (cw.flip ? out_w - 1 - x : x);
+                    val[k] = i0 + k < n ? plane[(size_t)y * w + sx] : 0.0f;  // plane c of clip b: pair c/2, plane c%2
+                    if (++x == out_w) x = 0, ++y;
+                }
+            }
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
-                const int sx = cw.left + (cw.flip ? out_w - 1 - x : x);
-                val[k] = i0 + k < n ? plane[(size_t)y * w + sx] : 0.0f;  // plane c of clip b: pair c/2, plane c%2
-                if (++x == out_w) x = 0, ++y;
+                const float t = (255.0f * (val[k] + bound)) / (2.0f * bound);
+                float q = rintf(fminf(fmaxf(t, 0.0f), 255.0f));
+                if (inv) q = 255.0f - q;
+                r[k] = (q / 255.0f - mean) / stdv;
             }
-        }
+        } else {
+            unsigned qv[4];
+            if (ld4) {  // the 4 sources are one aligned 4-byte run of row y (reversed when flipped)
+                const int sx = cw.flip ? cw.left + out_w - 4 - x : cw.left + x;
+                const unsigned u = *reinterpret_cast<const unsigned*>(plane + (size_t)y * w + sx);
 #pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const float t = (255.0f * (val[k] + bound)) / (2.0f * bound);
-            float q = rintf(fminf(fmaxf(t, 0.0f), 255.0f));
-            if (inv) q = 255.0f - q;
-            r[k] = (q / 255.0f - mean) / stdv;
+                for (int k = 0; k < 4; ++k) qv[k] = (u >> (8 * (cw.flip ? 3 - k : k))) & 255u;
+            } else {
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const int sx = cw.left + (cw.flip ? out_w - 1 - x : x);
+                    qv[k] = i0 + k < n ? (unsigned)plane[(size_t)y * w + sx] : 0u;
+                    if (++x == out_w) x = 0, ++y;
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                float q = (float)qv[k];
+                if (inv) q = 255.0f - q;
+                r[k] = (q / 255.0f - mean) / stdv;
+            }
         }
         if (vec4 & 1) {  // 16-byte aligned stack and planes of a multiple of 4 floats: the run lies in the plane, aligned
             // streamed past the caches: the volume is written once and read by the next kernel, the flow planes are not
@@ -100,6 +129,43 @@ __global__ void __launch_bounds__(256) k_flow_crop_stack(const float* __restrict
 #pragma unroll
             for (int k = 0; k < 4; ++k)
                 if (i0 + k < n) dst[i0 + k] = r[k];
+        }
+    }
+}
+
+// S39, the stored flow: flow f32 [n] -> out u8 [n], q = rintf(fminf(fmaxf(t, 0), 255)) with k_flow_crop_stack's t (a NaN
+// becomes 0: fmaxf returns its other operand).  Element-wise over the whole array; a thread converts kGatherSteps runs of 4
+// consecutive elements: one 16-byte load when ld4 (flow 16-byte aligned), one 4-byte store when st4 (out 4-byte aligned).
+// The last run of an array that is no multiple of 4 long goes element by element.
+__global__ void __launch_bounds__(256) k_flow_quantize_u8(const float* __restrict__ flow, unsigned char* __restrict__ out,
+                                                          size_t n, int ld4, int st4, float bound)
+{
+#pragma unroll
+    for (int s = 0; s < kGatherSteps; ++s) {
+        const size_t i0 = (((size_t)blockIdx.x * kGatherSteps + s) * blockDim.x + threadIdx.x) * 4;
+        if (i0 >= n) continue;
+        const bool whole = i0 + 4 <= n;
+        float val[4];
+        if (ld4 && whole) {
+            const f32x4 f = *reinterpret_cast<const f32x4*>(flow + i0);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) val[k] = f[k];
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) val[k] = i0 + k < n ? flow[i0 + k] : 0.0f;
+        }
+        unsigned q[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const float t = (255.0f * (val[k] + bound)) / (2.0f * bound);
+            q[k] = (unsigned)rintf(fminf(fmaxf(t, 0.0f), 255.0f));
+        }
+        if (st4 && whole) {
+            *reinterpret_cast<unsigned*>(out + i0) = q[0] | (q[1] << 8) | (q[2] << 16) | (q[3] << 24);
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                if (i0 + k < n) out[i0 + k] = (unsigned char)q[k];
         }
     }
 }
@@ -198,8 +264,11 @@ __device__ __forceinline__ float resize_lerp(float A, float B, float C, float D,
     return t + ay * (b - t);
 }
 
-// flow f32 [n_src/2][2][h][w] -> stack f32 [n_out][224][224]: S17, then S9 in S9's order; TSN inversion as S10's
-__global__ void __launch_bounds__(kResizeThreads) k_flow_resize_stack(const float* __restrict__ flow, const int* __restrict__ table,
+// flow f32 [n_src/2][2][h][w] -> stack f32 [n_out][224][224]: S17, then S9 in S9's order; TSN inversion as S10's.
+// SRC = unsigned char (S41, va_flowq_to_stack_resize): a stored flow's 8-bit images are resampled as images, TSN's order:
+// qr = the value k_resize_images_u8 writes for the plane, then the inversion, then the normalisation.
+template <typename SRC>
+__global__ void __launch_bounds__(kResizeThreads) k_flow_resize_stack(const SRC* __restrict__ flow, const int* __restrict__ table,
                                                                       float* __restrict__ stack, int n_src, int w, int h,
                                                                       int invert_x, int vec4, float bound, float mean, float stdv)
 {
@@ -207,7 +276,7 @@ __global__ void __launch_bounds__(kResizeThreads) k_flow_resize_stack(const floa
     const ResizeWin r = load_resize(table, o, n_src, h, w);
     const int cg = threadIdx.x % kResizeColGroups, rg = blockIdx.x * kResizeRowGroups + threadIdx.x / kResizeColGroups;
     const bool inv = invert_x && r.flip && (r.src & 1) == 0;
-    const float* __restrict__ plane = flow + (size_t)r.src * h * w + (size_t)r.top * w + r.left;
+    const SRC* __restrict__ plane = flow + (size_t)r.src * h * w + (size_t)r.top * w + r.left;
     float* __restrict__ dst = stack + (size_t)o * (kResizeSize * kResizeSize) + 4 * cg;
     int x0[4], x1[4];
     float ax[4];
@@ -222,13 +291,13 @@ __global__ void __launch_bounds__(kResizeThreads) k_flow_resize_stack(const floa
         int y0, y1;
         float ay;
         resize_tap(y, r.ch, y0, y1, ay);
-        const float* __restrict__ ra = plane + (size_t)y0 * w;
-        const float* __restrict__ rb = plane + (size_t)y1 * w;
+        const SRC* __restrict__ ra = plane + (size_t)y0 * w;
+        const SRC* __restrict__ rb = plane + (size_t)y1 * w;
         float q4[4];
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-            const float val = resize_lerp(ra[x0[k]], ra[x1[k]], rb[x0[k]], rb[x1[k]], ax[k], ay);
-            const float t = (255.0f * (val + bound)) / (2.0f * bound);
+            const float val = resize_lerp((float)ra[x0[k]], (float)ra[x1[k]], (float)rb[x0[k]], (float)rb[x1[k]], ax[k], ay);
+            const float t = std::is_same<SRC, float>::value ? (255.0f * (val + bound)) / (2.0f * bound) : val;
             float q = rintf(fminf(fmaxf(t, 0.0f), 255.0f));
             if (inv) q = 255.0f - q;
             q4[k] = (q / 255.0f - mean) / stdv;
@@ -631,19 +700,21 @@ static int check_flow_gather(const char* who, const void* flow, const void* crop
     return VA_OK;
 }
 
-static void launch_flow_gather(const float* flow, const int* crops, float* stack, int w, int h, int out_w, int out_h,
+template <typename SRC>
+static void launch_flow_gather(const SRC* flow, const int* crops, float* stack, int w, int h, int out_w, int out_h,
                                int chans, int planes, int n_views, int invert_x, float bound, float mean, float stdv,
                                hipStream_t stream, const int* starts = nullptr, int n_pairs = 0)
 {
     const dim3 g((unsigned)va_cdiv(out_w * out_h, kGatherPerBlock), (unsigned)planes);
+    // one aligned source run of 4 elements: 16 bytes of f32, 4 bytes of u8
     const int vec4 = ((out_w * out_h) % 4 == 0 && reinterpret_cast<uintptr_t>(stack) % 16 == 0 ? 1 : 0) |
-                     (w % 4 == 0 && out_w % 4 == 0 && reinterpret_cast<uintptr_t>(flow) % 16 == 0 ? 2 : 0);
+                     (w % 4 == 0 && out_w % 4 == 0 && reinterpret_cast<uintptr_t>(flow) % (4 * sizeof(SRC)) == 0 ? 2 : 0);
     if (starts)
-        k_flow_crop_stack<true><<<g, 256, 0, stream>>>(flow, crops, starts, n_pairs, stack, w, h, out_w, out_h, chans, n_views,
-                                                       invert_x, vec4, bound, mean, stdv);
+        k_flow_crop_stack<true, SRC><<<g, 256, 0, stream>>>(flow, crops, starts, n_pairs, stack, w, h, out_w, out_h, chans,
+                                                            n_views, invert_x, vec4, bound, mean, stdv);
     else
-        k_flow_crop_stack<false><<<g, 256, 0, stream>>>(flow, crops, nullptr, 0, stack, w, h, out_w, out_h, chans, n_views,
-                                                        invert_x, vec4, bound, mean, stdv);
+        k_flow_crop_stack<false, SRC><<<g, 256, 0, stream>>>(flow, crops, nullptr, 0, stack, w, h, out_w, out_h, chans,
+                                                             n_views, invert_x, vec4, bound, mean, stdv);
 }
 
 extern "C" int va_flow_to_stack_crop(va_ctx* ctx, const void* flow, int n_pairs, int w, int h, float bound, float mean,
@@ -678,23 +749,61 @@ extern "C" int va_flow_to_stack_views(va_ctx* ctx, const void* flow, int n_clips
     return VA_OK;
 }
 
+// va_flow_to_stack_snippets and its stored-flow form (S40): the checks and the launch
+template <typename SRC>
+static int flow_snippets(const char* who, va_ctx* ctx, const void* flow, int n_pairs, const void* starts, int n_snippets,
+                         int flow_count, int n_views, int w, int h, float bound, float mean, float stdv, const void* crops,
+                         int invert_x_on_flip, int out_w, int out_h, void* stack, void* stream)
+{
+    VA_CHECK_ARG(ctx != nullptr, "%s: ctx is NULL", who);
+    VA_USE_DEVICE(ctx);
+    VA_CHECK_ARG(n_snippets >= 1 && flow_count >= 1 && n_views >= 1, "%s: bad shape", who);
+    VA_CHECK_ARG(n_pairs >= flow_count && n_pairs <= 0x3fffffff, "%s: %d flow pairs do not hold a window of %d", who, n_pairs,
+                 flow_count);
+    VA_CHECK_ARG(starts != nullptr, "%s: NULL buffer", who);
+    VA_CHECK_ARG(invert_x_on_flip == 0 || invert_x_on_flip == 1, "%s: invert_x_on_flip must be 0 or 1", who);
+    const long long planes = (long long)n_snippets * n_views * 2 * flow_count;
+    const int rc = check_flow_gather(who, flow, crops, stack, planes, w, h, out_w, out_h, bound, stdv);
+    if (rc != VA_OK) return rc;
+    launch_flow_gather((const SRC*)flow, (const int*)crops, (float*)stack, w, h, out_w, out_h, 2 * flow_count, (int)planes,
+                       n_views, invert_x_on_flip, bound, mean, stdv, (hipStream_t)stream, (const int*)starts, n_pairs);
+    VA_LAUNCH_CHECK();
+    return VA_OK;
+}
+
 extern "C" int va_flow_to_stack_snippets(va_ctx* ctx, const void* flow, int n_pairs, const void* starts, int n_snippets,
                                          int flow_count, int n_views, int w, int h, float bound, float mean, float stdv,
                                          const void* crops, int invert_x_on_flip, int out_w, int out_h, void* stack,
                                          void* stream)
 {
-    VA_CHECK_ARG(ctx != nullptr, "va_flow_to_stack_snippets: ctx is NULL");
+    return flow_snippets<float>("va_flow_to_stack_snippets", ctx, flow, n_pairs, starts, n_snippets, flow_count, n_views, w, h,
+                                bound, mean, stdv, crops, invert_x_on_flip, out_w, out_h, stack, stream);
+}
+
+extern "C" int va_flowq_to_stack_snippets(va_ctx* ctx, const void* flowq, int n_pairs, const void* starts, int n_snippets,
+                                          int flow_count, int n_views, int w, int h, float mean, float stdv, const void* crops,
+                                          int invert_x_on_flip, int out_w, int out_h, void* stack, void* stream)
+{
+    // (the images are quantised already: the bound the shared checks and the kernel take is not used)
+    return flow_snippets<unsigned char>("va_flowq_to_stack_snippets", ctx, flowq, n_pairs, starts, n_snippets, flow_count,
+                                        n_views, w, h, 1.0f, mean, stdv, crops, invert_x_on_flip, out_w, out_h, stack, stream);
+}
+
+extern "C" int va_flow_quantize_u8(va_ctx* ctx, const void* flow, int n_pairs, int w, int h, float bound, void* out,
+                                   void* stream)
+{
+    VA_CHECK_ARG(ctx != nullptr, "va_flow_quantize_u8: ctx is NULL");
     VA_USE_DEVICE(ctx);
-    VA_CHECK_ARG(n_snippets >= 1 && flow_count >= 1 && n_views >= 1, "va_flow_to_stack_snippets: bad shape");
-    VA_CHECK_ARG(n_pairs >= flow_count && n_pairs <= 0x3fffffff, "va_flow_to_stack_snippets: %d flow pairs do not hold a window of %d",
-                 n_pairs, flow_count);
-    VA_CHECK_ARG(starts != nullptr, "va_flow_to_stack_snippets: NULL buffer");
-    VA_CHECK_ARG(invert_x_on_flip == 0 || invert_x_on_flip == 1, "va_flow_to_stack_snippets: invert_x_on_flip must be 0 or 1");
-    const long long planes = (long long)n_snippets * n_views * 2 * flow_count;
-    const int rc = check_flow_gather("va_flow_to_stack_snippets", flow, crops, stack, planes, w, h, out_w, out_h, bound, stdv);
-    if (rc != VA_OK) return rc;
-    launch_flow_gather((const float*)flow, (const int*)crops, (float*)stack, w, h, out_w, out_h, 2 * flow_count, (int)planes,
-                       n_views, invert_x_on_flip, bound, mean, stdv, (hipStream_t)stream, (const int*)starts, n_pairs);
+    VA_CHECK_ARG(flow != nullptr && out != nullptr, "va_flow_quantize_u8: NULL buffer");
+    VA_CHECK_ARG(n_pairs >= 1 && w >= 1 && h >= 1, "va_flow_quantize_u8: bad shape");
+    VA_CHECK_ARG(bound > 0.0f, "va_flow_quantize_u8: bound must be > 0");
+    VA_CHECK_ARG(reinterpret_cast<uintptr_t>(flow) % 4 == 0, "va_flow_quantize_u8: flow must be 4-byte aligned");
+    const size_t n = (size_t)2 * n_pairs * w * h;
+    const size_t blocks = (n + kGatherPerBlock - 1) / kGatherPerBlock;
+    VA_CHECK_ARG(blocks <= 0x7fffffffULL, "va_flow_quantize_u8: %d pairs of %dx%d exceed one launch", n_pairs, w, h);
+    k_flow_quantize_u8<<<(unsigned)blocks, 256, 0, (hipStream_t)stream>>>((const float*)flow, (unsigned char*)out, n,
+                                                                         reinterpret_cast<uintptr_t>(flow) % 16 == 0,
+                                                                         reinterpret_cast<uintptr_t>(out) % 4 == 0, bound);
     VA_LAUNCH_CHECK();
     return VA_OK;
 }
@@ -739,21 +848,37 @@ extern "C" int va_crop_images_u8_views(va_ctx* ctx, const void* src, int n, int 
                        (hipStream_t)stream);
 }
 
+// va_flow_to_stack_resize and its stored-flow form (S41): the checks and the launch
+template <typename SRC>
+static int flow_resize(const char* who, va_ctx* ctx, const void* flow, int n_pairs, int w, int h, float bound, float mean,
+                       float stdv, const void* table, int n_out, int invert_x_on_flip, void* stack, void* stream)
+{
+    VA_CHECK_ARG(ctx != nullptr, "%s: ctx is NULL", who);
+    VA_USE_DEVICE(ctx);
+    VA_CHECK_ARG(flow != nullptr && table != nullptr && stack != nullptr, "%s: NULL buffer", who);
+    VA_CHECK_ARG(n_pairs >= 1 && n_pairs <= 0x3fffffff && w >= 1 && h >= 1 && n_out >= 1, "%s: bad shape", who);
+    VA_CHECK_ARG(n_out <= kMaxGridY, "%s: %d output planes exceed %d per call", who, n_out, kMaxGridY);
+    VA_CHECK_ARG(invert_x_on_flip == 0 || invert_x_on_flip == 1, "%s: invert_x_on_flip must be 0 or 1", who);
+    VA_CHECK_ARG(bound > 0.0f && stdv > 0.0f, "%s: bound and std must be > 0", who);
+    const int vec4 = reinterpret_cast<uintptr_t>(stack) % 16 == 0;
+    k_flow_resize_stack<SRC><<<dim3(kResizeBlocks, (unsigned)n_out), kResizeThreads, 0, (hipStream_t)stream>>>(
+        (const SRC*)flow, (const int*)table, (float*)stack, 2 * n_pairs, w, h, invert_x_on_flip, vec4, bound, mean, stdv);
+    VA_LAUNCH_CHECK();
+    return VA_OK;
+}
+
 extern "C" int va_flow_to_stack_resize(va_ctx* ctx, const void* flow, int n_pairs, int w, int h, float bound, float mean,
                                        float stdv, const void* table, int n_out, int invert_x_on_flip, void* stack, void* stream)
 {
-    VA_CHECK_ARG(ctx != nullptr, "va_flow_to_stack_resize: ctx is NULL");
-    VA_USE_DEVICE(ctx);
-    VA_CHECK_ARG(flow != nullptr && table != nullptr && stack != nullptr, "va_flow_to_stack_resize: NULL buffer");
-    VA_CHECK_ARG(n_pairs >= 1 && n_pairs <= 0x3fffffff && w >= 1 && h >= 1 && n_out >= 1, "va_flow_to_stack_resize: bad shape");
-    VA_CHECK_ARG(n_out <= kMaxGridY, "va_flow_to_stack_resize: %d output planes exceed %d per call", n_out, kMaxGridY);
-    VA_CHECK_ARG(invert_x_on_flip == 0 || invert_x_on_flip == 1, "va_flow_to_stack_resize: invert_x_on_flip must be 0 or 1");
-    VA_CHECK_ARG(bound > 0.0f && stdv > 0.0f, "va_flow_to_stack_resize: bound and std must be > 0");
-    const int vec4 = reinterpret_cast<uintptr_t>(stack) % 16 == 0;
-    k_flow_resize_stack<<<dim3(kResizeBlocks, (unsigned)n_out), kResizeThreads, 0, (hipStream_t)stream>>>(
-        (const float*)flow, (const int*)table, (float*)stack, 2 * n_pairs, w, h, invert_x_on_flip, vec4, bound, mean, stdv);
-    VA_LAUNCH_CHECK();
-    return VA_OK;
+    return flow_resize<float>("va_flow_to_stack_resize", ctx, flow, n_pairs, w, h, bound, mean, stdv, table, n_out,
+                              invert_x_on_flip, stack, stream);
+}
+
+extern "C" int va_flowq_to_stack_resize(va_ctx* ctx, const void* flowq, int n_pairs, int w, int h, float mean, float stdv,
+                                        const void* table, int n_out, int invert_x_on_flip, void* stack, void* stream)
+{
+    return flow_resize<unsigned char>("va_flowq_to_stack_resize", ctx, flowq, n_pairs, w, h, 1.0f, mean, stdv, table, n_out,
+                                      invert_x_on_flip, stack, stream);
 }
 
 extern "C" int va_resize_images_u8(va_ctx* ctx, const void* src, int n, int c, int w, int h, int src_nhwc, const void* table,

@@ -283,6 +283,101 @@ def resize_flow_to_stack(flow, table, invert_x_on_flip=False, bound=FLOW_BOUND, 
     return out.view(n_out, 224, 224)
 
 
+# ---- stored optical flow ----
+#
+# The flow of a video, computed once and kept on the device: ``[T-1,2,H,W]``, field t the flow from frame t to frame t+1,
+# as float32 (TV-L1's own output) or as uint8, the 8-bit flow images of S9 that TSN and the reference's JPEGs hold.  The
+# float32 form goes through the gathers above; the uint8 form through the two below.
+
+def _check_flowq(flowq, who):
+    if not isinstance(flowq, torch.Tensor) or not flowq.is_cuda or flowq.dtype != torch.uint8:
+        raise ValueError("%s: flowq must be a CUDA uint8 tensor (quantize_flow)" % who)
+    if flowq.dim() != 4 or flowq.shape[1] != 2:
+        raise ValueError("%s: flowq must be [N,2,H,W]" % who)
+
+
+def quantize_flow(flow, bound=FLOW_BOUND, out=None):
+    """S39: flow ``[N,2,H,W]`` CUDA float32 -> uint8 of the same shape (into ``out`` when given), the 8-bit flow images
+    ``q = rint(clamp(255*(v+bound)/(2*bound), 0, 255))`` every flow gather forms (``utils.flowToImages`` on the device; a NaN
+    becomes 0)."""
+    _check_flow(flow, "quantize_flow")
+    try:
+        bound = float(bound)
+    except (TypeError, ValueError):
+        raise ValueError("quantize_flow: bound must be a number")
+    if not 0.0 < bound < float("inf"):
+        raise ValueError("quantize_flow: bound must be finite and > 0, got %r" % bound)
+    N, _, H, W = flow.shape
+    if N < 1 or H < 1 or W < 1:
+        raise ValueError("quantize_flow: empty flow %s" % (tuple(flow.shape),))
+    flow = flow.contiguous()
+    if out is None:
+        out = torch.empty((N, 2, H, W), dtype=torch.uint8, device=flow.device)
+    elif (not isinstance(out, torch.Tensor) or out.numel() != flow.numel() or out.dtype != torch.uint8 or not out.is_contiguous()
+          or out.device != flow.device):
+        raise ValueError("quantize_flow: out must be a contiguous uint8 tensor of %d elements on the flow's device" % flow.numel())
+    _ffi.check(_ffi.lib().va_flow_quantize_u8(_ffi.ctx(flow.device.index), _ffi.ptr(flow), N, W, H, bound, _ffi.ptr(out),
+                                              _ffi.stream_ptr(flow.device)))
+    return out.view(N, 2, H, W)
+
+
+def flowq_to_stack_snippets(flowq, starts, views, flow_count, invert_x_on_flip=False, size=224, mean=NORM_MEANS_TF[0],
+                            std=NORM_STDS_TF[0], out=None):
+    """S40, ``crop_flow_to_stack_snippets`` of a uint8 stored flow: flowq ``[N,2,H,W]`` CUDA uint8 (``quantize_flow``), starts
+    and views as there -> ``[n,V,2L,size,size]`` float32.  On ``quantize_flow(flow)`` it gives the bits
+    ``crop_flow_to_stack_snippets(flow)`` gives."""
+    from . import augment
+    _check_flowq(flowq, "flowq_to_stack_snippets")
+    N, _, H, W = flowq.shape
+    L = int(flow_count)
+    if L < 1:
+        raise ValueError("flowq_to_stack_snippets: flow_count must be >= 1, got %d" % L)
+    starts = check_starts(starts, N, L, "flowq_to_stack_snippets")
+    augment.check_views(views, H, W, size, "flowq_to_stack_snippets")
+    n, V = starts.shape[0], views.shape[0]
+    flowq = flowq.contiguous()
+    out = _check_out(out, (n, V, 2 * L, size, size), flowq, "flowq_to_stack_snippets")
+    dcrops = augment.crops_to_device(augment.expand_views(views, n, 2 * L), flowq.device)
+    dstarts = augment.crops_to_device(starts, flowq.device)
+    _ffi.check(_ffi.lib().va_flowq_to_stack_snippets(_ffi.ctx(flowq.device.index), _ffi.ptr(flowq), N, _ffi.ptr(dstarts), n, L, V,
+                                                     W, H, float(mean), float(std), _ffi.ptr(dcrops),
+                                                     int(bool(invert_x_on_flip)), size, size, _ffi.ptr(out),
+                                                     _ffi.stream_ptr(flowq.device)))
+    return out.view(n, V, 2 * L, size, size)
+
+
+def resize_flowq_to_stack(flowq, table, invert_x_on_flip=False, mean=NORM_MEANS_TF[0], std=NORM_STDS_TF[0], out=None):
+    """S41, the crop-resize gather of a uint8 stored flow in TSN's order: flowq ``[N,2,H,W]`` CUDA uint8, table as
+    ``resize_flow_to_stack`` takes it -> ``[n_out,224,224]`` float32.  The 8-bit IMAGE is resampled (to the value
+    ``augment.resize_images`` gives for the plane), then inverted and normalised; at ``ch = cw = 224`` that is the plain
+    crop of ``flowq_to_stack_snippets``, at other sizes it is not ``resize_flow_to_stack`` of the float field."""
+    from . import augment
+    _check_flowq(flowq, "resize_flowq_to_stack")
+    N, _, H, W = flowq.shape
+    augment.check_resize_table(table, 2 * N, H, W, "resize_flowq_to_stack")
+    n_out = table.shape[0]
+    flowq = flowq.contiguous()
+    out = _check_out(out, (n_out, 224, 224), flowq, "resize_flowq_to_stack")
+    dtable = augment.crops_to_device(table, flowq.device)
+    _ffi.check(_ffi.lib().va_flowq_to_stack_resize(_ffi.ctx(flowq.device.index), _ffi.ptr(flowq), N, W, H, float(mean),
+                                                   float(std), _ffi.ptr(dtable), n_out, int(bool(invert_x_on_flip)),
+                                                   _ffi.ptr(out), _ffi.stream_ptr(flowq.device)))
+    return out.view(n_out, 224, 224)
+
+
+def check_stored_flow(flow, n_frames, h, w, who):
+    """Host-side validation (ValueError; nothing is enqueued) of a stored flow for a video of ``n_frames`` frames of
+    ``h x w`` pixels, short of its device: a contiguous uint8 or float32 ``[n_frames-1,2,h,w]`` tensor."""
+    if not isinstance(flow, torch.Tensor) or flow.dtype not in (torch.uint8, torch.float32) or flow.dim() != 4 or flow.shape[1] != 2:
+        raise ValueError("%s: a stored flow must be a uint8 or float32 [T-1,2,H,W] tensor (extract_flow)" % who)
+    if not flow.is_contiguous():
+        raise ValueError("%s: a stored flow must be contiguous" % who)
+    if flow.shape[0] != n_frames - 1:
+        raise ValueError("%s: %d frames need %d stored flow fields, got %d" % (who, n_frames, n_frames - 1, flow.shape[0]))
+    if tuple(flow.shape[2:]) != (h, w):
+        raise ValueError("%s: the stored flow is %dx%d but the frames are %dx%d" % (who, flow.shape[3], flow.shape[2], w, h))
+
+
 # The temporal-ConvNet inputs of the two-stream paper (DESIGN.md S11-S13): "stack" is optical-flow stacking (the default and
 # the reference's input), "trajectory" samples the flow along the trajectory that starts at each pixel of the first frame,
 # "bidirectional" stacks L/2 forward fields from the clip's centre frame on and L/2 backward ones from it back.

@@ -81,6 +81,9 @@ class TwoStreamPipeline(object):
     ``submit_video()`` / ``run_video()`` classify a whole video on the same streams: its snippets share
     one TV-L1 pass over the frame pairs they need, and the scores of snippets and views are averaged and fused on the device.
 
+    ``extract_flow()`` computes the flow of a whole video once and keeps it on the device (DESIGN.md S39-S41);
+    ``submit_video(flow=)`` / ``run_video(flow=)`` and ``train_videos(flows=)`` then run without TV-L1.
+
     ``motion`` / ``mean_flow``: the temporal model's input representation (``flow.MOTIONS``), applied
     to every batch that comes with gray frames.  Bi-directional flow reorders the gray frames on the caller's stream; the
     means and the trajectory resampling run on the CNN stream into a pipeline-owned full-frame buffer.
@@ -373,6 +376,69 @@ class TwoStreamPipeline(object):
         out["done"] = finished
         return out
 
+    def extract_flow(self, frames, rescale=None, dtype=torch.uint8, return_camera=False):
+        """The stored flow of one video: TV-L1 once on all ``T - 1`` consecutive frame pairs, kept on the
+        device for ``submit_video(flow=)``, ``train_videos(flows=)`` and ``video.evaluateVideos(flows=)``, which then launch no
+        TV-L1 at all.  ``frames``: gray ``[T,H,W]`` (uint8 or float32) or decoded RGB uint8 ``[T,3,H,W]`` on the pipeline's
+        device; for RGB the gray frames and ``rescale=`` go through ``frames.prepare_frames`` as in ``submit_video``.
+
+        The pairs are split into ``flow_streams`` contiguous chunks, each one TV-L1 sequence that includes its boundary frame
+        (every frame's pyramid is built once per chunk), with the pipeline's ``tvl1_params``; field t is the flow from frame
+        t to frame t + 1 and equals ``flow.tvl1_flow`` of those two frames bit for bit.  The pipeline's ``camera`` step (S21,
+        S22) is applied to every field before anything is stored, so the store of a ``camera="homography"`` pipeline is TSN's
+        warped flow.  ``dtype``: ``torch.float32`` keeps TV-L1's output, exact; ``torch.uint8`` (the default, a quarter of the
+        size) quantises it last to the 8-bit flow images of S9 (``flow.quantize_flow``).
+
+        Returns the store ``[T-1,2,H,W]``, ready on the current stream; with ``return_camera=True``
+        ``(store, homography, camera_share)``, the last two None without a camera step.  A bi-directional pipeline raises
+        ValueError (its backward fields are not consecutive pairs), as do frames of another type, rank or device and fewer
+        than two frames, before anything is enqueued."""
+        who = "extract_flow"
+        if self.motion == "bidirectional":
+            raise ValueError("%s: a bi-directional pipeline computes backward fields, which are not the consecutive pairs a "
+                             "stored flow holds" % who)
+        if dtype not in (torch.uint8, torch.float32):
+            raise ValueError("%s: dtype must be torch.uint8 or torch.float32, got %r" % (who, dtype))
+        if not isinstance(frames, torch.Tensor) or frames.dim() not in (3, 4):
+            raise ValueError("%s: frames must be gray [T,H,W] or rgb uint8 [T,3,H,W]" % who)
+        size = None
+        if frames.dim() == 4:
+            _, _, _, oh, ow = vframes.check_frames(frames, rescale, "NCHW", who)
+            size = (oh, ow)
+        else:
+            if rescale is not None:
+                raise ValueError("%s: rescale= acts on rgb frames (the gray of rescaled frames is not the rescaled gray)" % who)
+            if frames.dtype not in (torch.uint8, torch.float32):
+                raise ValueError("%s: gray frames must be uint8 or float32" % who)
+        if frames.shape[0] < 2:
+            raise ValueError("%s: %d frames hold no frame pair" % (who, frames.shape[0]))
+        if not frames.is_cuda or frames.device != self.device:
+            raise ValueError("%s: frames must be on %s" % (who, self.device))
+        dev = self.device
+        gray = frames.contiguous() if size is None else vframes.prepare_frames(frames, size)[1]
+        T, H, W = gray.shape
+        P = T - 1
+        n = min(self.flow_streams, P)
+        bounds = [(P * i) // n for i in range(n + 1)]
+        cur = torch.cuda.current_stream(dev)
+        flow = torch.empty((P, 2, H, W), dtype=torch.float32, device=dev)
+        if n == 1:
+            vflow.tvl1_flow(gray.unsqueeze(0), self.tvl1_params, out=flow)
+        else:
+            streams = vflow.flow_streams(dev, self.flow_streams)[:n]
+            for i, st in enumerate(streams):
+                st.wait_stream(cur)
+                with torch.cuda.stream(st):
+                    part = gray[bounds[i]:bounds[i + 1] + 1]  # pairs bounds[i] .. bounds[i+1]-1 and their boundary frame
+                    part.record_stream(st)
+                    flow.record_stream(st)
+                    vflow.tvl1_flow(part.unsqueeze(0), self.tvl1_params, ws_slot=i + 1, out=flow[bounds[i]:bounds[i + 1]])
+            for st in streams:
+                cur.wait_stream(st)
+        flow, Hm, share = vflow.apply_camera(flow, self.camera, in_place=True)
+        store = vflow.quantize_flow(flow) if dtype == torch.uint8 else flow
+        return (store, Hm, share) if return_camera else store
+
     def _check_task(self, task, who):
         """``task=`` against the pipeline's ``heads`` -> the head's index, or None on a pipeline without heads."""
         heads = getattr(self, "heads", None)
@@ -398,10 +464,13 @@ class TwoStreamPipeline(object):
         return ((oh, ow), torch.empty((n, 3, oh, ow), dtype=torch.uint8, device="meta"),
                 torch.empty((n, oh, ow), dtype=torch.uint8, device="meta"))
 
-    def _check_video(self, rgb, gray, n_snippets, views, consensus, fusion_weights, crops, rescale=None):
+    def _check_video(self, rgb, gray, n_snippets, views, consensus, fusion_weights, crops, rescale=None, flow=None):
         """Host-side checks of ``submit_video`` before anything is enqueued -> (plan, rgb_views, flow_views, mode, weights,
         size): one fusion weight per stream, None meaning all ones; ``size`` is None for frames used as they are, else what
-        ``frames.prepare_frames`` takes (``gray=None`` / ``rescale=``: the checks then see the prepared shapes)."""
+        ``frames.prepare_frames`` takes (``gray=None`` / ``rescale=``: the checks then see the prepared shapes).  ``flow``: a
+        stored flow, checked against the prepared frames."""
+        if flow is not None and gray is not None:
+            raise ValueError("submit_video: flow= replaces the gray frames and their TV-L1; pass gray=None with it")
         prep = self._prepared_shapes(rgb, gray, rescale, "submit_video")
         decoded = rgb
         if prep is not None:
@@ -424,15 +493,22 @@ class TwoStreamPipeline(object):
             ws = fusion.check_fusion_weights_n(fusion_weights, m, "submit_video")
             plan, rgb_views, flow_views, mode, _, _ = check_video(rgb, gray, self.L, self.motion, n_snippets, views, consensus,
                                                                   (1.0, 1.0), crops)
+        if flow is not None:
+            vflow.check_stored_flow(flow, int(gray.shape[0]), int(gray.shape[1]), int(gray.shape[2]), "submit_video")
+            if flow.dtype == torch.uint8 and (self.motion != "stack" or self.mean_flow):
+                raise ValueError("submit_video: motion=%r / mean_flow=%r act on the float field; a uint8 stored flow is already "
+                                 "quantised (store float32 flow for them)" % (self.motion, self.mean_flow))
         if prep is not None:
             if not decoded.is_cuda or decoded.device != self.device:
                 raise ValueError("submit_video: rgb must be on %s" % (self.device,))
         elif not rgb.is_cuda or not gray.is_cuda or rgb.device != self.device or gray.device != self.device:
             raise ValueError("submit_video: rgb and gray must be on %s" % (self.device,))
+        if flow is not None and (not flow.is_cuda or flow.device != self.device):
+            raise ValueError("submit_video: the stored flow must be on %s" % (self.device,))
         return plan, rgb_views, flow_views, mode, ws, None if prep is None else prep[0]
 
     def submit_video(self, rgb, gray=None, n_snippets=video.N_SNIPPETS, views=None, invert_flow_x=False, consensus="softmax",
-                     fusion_weights=None, crops=None, task=None, rescale=None):
+                     fusion_weights=None, crops=None, task=None, rescale=None, flow=None):
         """Enqueue one whole video (the test protocol of Sheet03/notes.txt:113-116 and 225-230):
         rgb u8 ``[T,3,H,W]``, gray u8 or f32 ``[T,H,W]``, the frames of one video on the device.  ``n_snippets`` snippets
         are placed by ``video.snippetStarts``; the frame pairs they share go through TV-L1 once each
@@ -464,26 +540,46 @@ class TwoStreamPipeline(object):
         frame as PIL's bilinear ``Image.resize`` does (``frames.prepare_frames``); ``views`` are then tables for the new
         size.  Both run on the current stream ahead of everything else, so the TV-L1 and CNN streams wait for them as they
         wait for the inputs.  ``rescale=`` with a given ``gray`` raises ValueError.  The result holds ``frame_size``, the
-        ``(height, width)`` TV-L1 and the views saw."""
+        ``(height, width)`` TV-L1 and the views saw.
+
+        Stored flow: ``flow=`` is the video's flow computed once (``extract_flow``), a contiguous float32
+        or uint8 ``[T-1,2,H,W]`` tensor on the pipeline's device, of the prepared frames' size; ``gray`` must then be None.  No
+        TV-L1 is launched and the camera step is not applied again (the store of a ``camera="homography"`` pipeline already
+        holds the warped flow; the result has no ``homography`` / ``camera_share``): snippet s reads the L fields from field
+        ``plan.starts[s]`` on through the flow views, and everything else is as above.  A float32 store goes through
+        ``mean_flow`` and the float gather and keeps the bits of the live call; a uint8 store goes through
+        ``flow.flowq_to_stack_snippets``, needs ``mean_flow=False`` and keeps the bits too.  ``flow=`` with ``gray=``, a store
+        of another type, shape, size or device and a uint8 store on a ``mean_flow`` pipeline raise ValueError before
+        anything is enqueued."""
         task = self._check_task(task, "submit_video")
+        stored = flow
         plan, rgb_views, flow_views, mode, fw, size = self._check_video(rgb, gray, n_snippets, views, consensus, fusion_weights,
-                                                                       crops, rescale)
+                                                                       crops, rescale, stored)
         dev = self.device
         n, U = plan.n, len(plan.pairs)
-        if gray is None:  # S38: on the current stream, ahead of the gathers and of `ready`
-            rgb, gray = vframes.prepare_frames(rgb, size)
-        T, H, W = gray.shape
+        if stored is not None:  # the gray frames only fed TV-L1: the frames are rescaled (S38) or used as they are
+            if size is not None and tuple(size) != tuple(rgb.shape[2:]):
+                rgb, _ = vframes.prepare_frames(rgb, size)
+            T, H, W = int(rgb.shape[0]), int(rgb.shape[2]), int(rgb.shape[3])
+        else:
+            if gray is None:  # S38: on the current stream, ahead of the gathers and of `ready`
+                rgb, gray = vframes.prepare_frames(rgb, size)
+            T, H, W = gray.shape
         cur = torch.cuda.current_stream(dev)
-        seq = augment.crops_to_device(torch.tensor(plan.sequences, dtype=torch.int64), dev)
-        tv = gray[seq]                                                     # [U,2,H,W]: one two-frame sequence per planned pair
+        if stored is None:
+            seq = augment.crops_to_device(torch.tensor(plan.sequences, dtype=torch.int64), dev)
+            tv = gray[seq]                                                 # [U,2,H,W]: one two-frame sequence per planned pair
         frames = rgb[augment.crops_to_device(torch.tensor(plan.starts, dtype=torch.int64), dev)]  # [n,3,H,W]
         ready = torch.cuda.Event()
         ready.record(cur)
         k = self._n % self.depth
         self._n += 1
-        fbuf = self._buffer(self._flow, k, (U, 2, H, W))
-        flow, evs = vflow.tvl1_flow_concurrent(tv, self.tvl1_params, self.flow_streams, out=fbuf,
-                                               after=[ready, self._flow_read[k]], join=False)
+        if stored is None:
+            fbuf = self._buffer(self._flow, k, (U, 2, H, W))
+            flow, evs = vflow.tvl1_flow_concurrent(tv, self.tvl1_params, self.flow_streams, out=fbuf,
+                                                   after=[ready, self._flow_read[k]], join=False)
+        else:  # the store is complete at `ready`; its windows start at the snippets' own pairs
+            flow, evs = stored, []
         with torch.cuda.stream(self._cnn):
             self._cnn.wait_event(ready)
             frames.record_stream(self._cnn)
@@ -498,14 +594,21 @@ class TwoStreamPipeline(object):
             for ev in evs:
                 self._cnn.wait_event(ev)
             Vt = flow_views.shape[0]
-            src = self._camera(flow, extra)  # per planned field, like the means
+            if stored is None:
+                src = self._camera(flow, extra)  # per planned field, like the means
+            else:
+                flow.record_stream(self._cnn)
+                src = flow
             if self.mean_flow:  # S11 / S12 per planned field: no chains, so the clip length does not matter
                 src = vflow.apply_motion(src, 1, "stack", True, out=self._buffer(self._motion, k, tuple(flow.shape)))
-            stack = vflow.crop_flow_to_stack_snippets(src, plan.index, flow_views, self.L, invert_x_on_flip=bool(invert_flow_x),
-                                                      out=self._buffer(self._stack, k, (n, Vt, 2 * self.L, 224, 224)))
-            done = torch.cuda.Event()
-            done.record(self._cnn)
-            self._flow_read[k] = done
+            first = plan.index if stored is None else plan.starts
+            gather = vflow.flowq_to_stack_snippets if src.dtype == torch.uint8 else vflow.crop_flow_to_stack_snippets
+            stack = gather(src, first, flow_views, self.L, invert_x_on_flip=bool(invert_flow_x),
+                           out=self._buffer(self._stack, k, (n, Vt, 2 * self.L, 224, 224)))
+            if stored is None:
+                done = torch.cuda.Event()
+                done.record(self._cnn)
+                self._flow_read[k] = done
             if self._t_done is not None:
                 self._cnn.wait_event(self._t_done)
             _, _, desc_tv, logits_tv = self.temporal.forward_views(stack)
@@ -537,9 +640,10 @@ class TwoStreamPipeline(object):
         return out
 
     def run_video(self, rgb, gray=None, n_snippets=video.N_SNIPPETS, views=None, invert_flow_x=False, consensus="softmax",
-                  fusion_weights=None, crops=None, task=None, rescale=None):
+                  fusion_weights=None, crops=None, task=None, rescale=None, flow=None):
         """``submit_video`` + ``wait()``: the results are ready on the current stream."""
-        out = self.submit_video(rgb, gray, n_snippets, views, invert_flow_x, consensus, fusion_weights, crops, task, rescale)
+        out = self.submit_video(rgb, gray, n_snippets, views, invert_flow_x, consensus, fusion_weights, crops, task, rescale,
+                                flow)
         self.wait()
         return out
 
@@ -570,12 +674,13 @@ class TwoStreamPipeline(object):
             raise ValueError("%s: no videos" % who)
         return int(micro_videos)
 
-    def _check_train_videos(self, videos, labels, k, starts, crops, rng, tasks=None, micro=None, rescale=None):
+    def _check_train_videos(self, videos, labels, k, starts, crops, rng, tasks=None, micro=None, rescale=None, flows=None):
         """Host-side checks and draws of ``train_videos`` before anything is enqueued -> (videos, labels, plans, crops, tasks,
         sizes); ``tasks`` is None on a pipeline without heads.  ``micro``: videos per micro-batch (``_check_accumulate``),
         which lifts the limit on ``n*k``.  ``videos`` comes back as ``(rgb, gray)`` pairs, gray None where it is to be derived;
         ``sizes[i]`` is then what ``frames.prepare_frames`` takes for video i (None for a video used as it is), and every
-        shape check has seen the prepared shapes."""
+        shape check has seen the prepared shapes.  ``flows``: None or one stored flow per video (DESIGN.md
+        S39-S41), checked against the prepared frames; it comes back as a list."""
         who = "train_videos"
         heads = getattr(self, "heads", None)
         if heads is None and tasks is not None:
@@ -615,8 +720,28 @@ class TwoStreamPipeline(object):
         if tuple(videos[0][0].shape[2:]) != tuple(videos[0][1].shape[1:]):
             raise ValueError("%s: one crop serves a snippet's RGB frame and flow planes: rgb and gray frames must have one "
                              "size" % who)
+        if flows is not None:
+            if self.motion == "bidirectional":
+                raise ValueError("%s: a bi-directional pipeline needs backward fields; a stored flow holds consecutive pairs" % who)
+            try:
+                flows = list(flows)
+            except TypeError:
+                raise ValueError("%s: flows must be a list of one stored flow per video" % who)
+            if len(flows) != n:
+                raise ValueError("%s: %d videos but %d stored flows" % (who, n, len(flows)))
+            if any(g is not None for _, g in given):
+                raise ValueError("%s: flows= replaces the gray frames and their TV-L1; pass (rgb, None) or rgb alone with it" % who)
+            H, W = (int(d) for d in videos[0][1].shape[1:])
+            for f, (_, gray) in zip(flows, videos):
+                vflow.check_stored_flow(f, int(gray.shape[0]), H, W, who)
+            if any(f.dtype != flows[0].dtype for f in flows):
+                raise ValueError("%s: the stored flows of one step must share their type" % who)
+            if flows[0].dtype == torch.uint8 and (self.motion != "stack" or self.mean_flow):
+                raise ValueError("%s: motion=%r / mean_flow=%r act on the float field; uint8 stored flows are already quantised "
+                                 "(store float32 flow for them)" % (who, self.motion, self.mean_flow))
+            on_device += flows
         if any(not isinstance(t, torch.Tensor) or not t.is_cuda or t.device != self.device for t in on_device):
-            raise ValueError("%s: rgb and gray must be on %s" % (who, self.device))
+            raise ValueError("%s: rgb and gray%s must be on %s" % (who, "" if flows is None else " and the stored flows", self.device))
         H, W = (int(d) for d in videos[0][1].shape[1:])
         if not isinstance(labels, torch.Tensor):
             try:
@@ -644,7 +769,7 @@ class TwoStreamPipeline(object):
         if crops is None:
             crops = augment.draw_scale_jitter_crops(n * k, H, W, rng)
         augment.check_jitter_crops(crops, n * k, H, W, who)
-        return [tuple(v) for v in given], labels, plans, crops, tasks, sizes
+        return [tuple(v) for v in given], labels, plans, crops, tasks, sizes, flows
 
     @staticmethod
     def _check_jitter(n_snippets, color_jitter, jitter, lighting, rng):
@@ -700,7 +825,7 @@ class TwoStreamPipeline(object):
 
     def train_videos(self, videos, labels, k=video.N_SEGMENTS, starts=None, crops=None, lr=1e-3, momentum=0.9, dropout_seed=0,
                      invert_flow_x=False, rng=None, tasks=None, micro_videos=None, clip_norm=None, data_parallel=False,
-                     color_jitter=None, jitter=None, lighting=None, rescale=None):
+                     color_jitter=None, jitter=None, lighting=None, rescale=None, flows=None):
         """One TSN training step of both streams on whole videos (Sheet03/notes.txt:165-185, 212-223).
         ``videos``: a list of n ``(rgb u8 [T,3,H,W], gray [T,H,W])`` pairs on the device, one frame size, any lengths;
         ``labels``: their n class indices; ``n*k <= 64``.
@@ -757,13 +882,26 @@ class TwoStreamPipeline(object):
         are then derived on the device, after ``rescale=`` (an int: the short side; or ``(height, width)``) has rescaled its
         frames (``frames.prepare_frames``).  The crops are drawn and checked for the new size, and colour jitter still acts
         on the spatial input alone: the gray frames come from the prepared frames, before it.  ``rescale=`` with an entry
-        that brings its own gray raises ValueError."""
+        that brings its own gray raises ValueError.
+
+        Stored flow: ``flows=`` is a list with one stored flow per video (``extract_flow``; float32 or
+        uint8 ``[T-1,2,H,W]``, all of one type, of the prepared frames' size), and every entry of ``videos`` then comes without
+        gray frames.  The planned fields (``plan.pairs``) are taken from the stores -- fields no snippet needs are never
+        copied -- and neither TV-L1 nor the camera step runs.  With float32 everything from the motion options on is the code
+        above and the step keeps the bits of the live one (``motion="trajectory"`` included; a bi-directional pipeline raises
+        ValueError).  With uint8 the temporal input comes from ``flow.resize_flowq_to_stack``: TSN's order, the 8-bit image is
+        resampled; equal to the live step for ``ch = cw = 224`` crops, not for resampling ones; it needs ``motion="stack"`` and
+        ``mean_flow=False``.  The result's ``flow`` holds the planned fields in the stored type."""
         videos = list(videos)
         micro = self._check_accumulate(len(videos), int(k), micro_videos, clip_norm, data_parallel)
-        videos, labels, plans, crops, tasks, sizes = self._check_train_videos(videos, labels, k, starts, crops, rng, tasks, micro,
-                                                                               rescale)
+        videos, labels, plans, crops, tasks, sizes, flows = self._check_train_videos(videos, labels, k, starts, crops, rng, tasks,
+                                                                                      micro, rescale, flows)
         jitter = self._check_jitter(len(videos) * int(k), color_jitter, jitter, lighting, rng)
-        videos = [v if v[1] is not None else vframes.prepare_frames(v[0], size) for v, size in zip(videos, sizes)]  # S38
+        if flows is None:
+            videos = [v if v[1] is not None else vframes.prepare_frames(v[0], size) for v, size in zip(videos, sizes)]  # S38
+        else:  # the gray frames only fed TV-L1: the frames are rescaled (S38) or used as they are
+            videos = [(v[0] if tuple(size) == tuple(v[0].shape[2:]) else vframes.prepare_frames(v[0], size)[0], None)
+                      for v, size in zip(videos, sizes)]
         if micro is not None:
             step = self._accumulate_step(len(videos), int(k), micro, labels, tasks, lr, momentum, dropout_seed, clip_norm, data_parallel)
         elif tasks is None:
@@ -774,7 +912,13 @@ class TwoStreamPipeline(object):
         cur = torch.cuda.current_stream(dev)
         frames = torch.cat([rgb[augment.crops_to_device(torch.tensor(p.starts, dtype=torch.int64), dev)]
                             for (rgb, _), p in zip(videos, plans)])  # [n*k,3,H,W]
-        if self.motion == "bidirectional":  # S13 per snippet window: its own forward and backward sequences, no sharing
+        if flows is not None:  # the planned fields of every store, in the order TV-L1 would have written them
+            flow = torch.cat([f[augment.crops_to_device(torch.tensor(p.pairs, dtype=torch.int64), dev)] for f, p in zip(flows, plans)])
+            first, base = [], 0
+            for p in plans:
+                first += [base + j for j in p.index]
+                base += len(p.pairs)
+        elif self.motion == "bidirectional":  # S13 per snippet window: its own forward and backward sequences, no sharing
             win = torch.cat([gray[augment.crops_to_device(torch.tensor([[s + f for f in range(L + 1)] for s in p.starts],
                                                                         dtype=torch.int64), dev)]
                              for (_, gray), p in zip(videos, plans)])  # [n*k,L+1,H,W]
@@ -787,10 +931,13 @@ class TwoStreamPipeline(object):
             for p in plans:
                 first += [base + j for j in p.index]
                 base += len(p.pairs)
-        flow = vflow.tvl1_flow_concurrent(tv, self.tvl1_params, self.flow_streams)
         extra = {}
-        flow = self._camera(flow, extra)  # per planned field, in place: everything below reads the compensated field
-        if self.motion == "trajectory":  # S12 chains follow a window: the windows are laid out one after the other
+        if flows is None:
+            flow = vflow.tvl1_flow_concurrent(tv, self.tvl1_params, self.flow_streams)
+            flow = self._camera(flow, extra)  # per planned field, in place: everything below reads the compensated field
+        if flow.dtype == torch.uint8:  # S41: the stored images themselves
+            src = flow
+        elif self.motion == "trajectory":  # S12 chains follow a window: the windows are laid out one after the other
             idx = torch.tensor([f + j for f in first for j in range(L)], dtype=torch.int64)
             src = vflow.apply_motion(flow[augment.crops_to_device(idx, dev)], L, "trajectory", self.mean_flow)
             first = [i * L for i in range(n * k)]
@@ -803,7 +950,8 @@ class TwoStreamPipeline(object):
         if jitter is not None or lighting is not None:  # S35: the spatial stream's input alone, in place
             table = jitter if jitter is not None else torch.tensor([augment.IDENTITY_JITTER_ROW] * (n * k), dtype=torch.float32)
             xs = augment.color_jitter(xs, table, lighting, out=xs)
-        xt = vflow.resize_flow_to_stack(src, flow_table, invert_x_on_flip=bool(invert_flow_x)).view(n * k, 2 * L, 224, 224)
+        gather = vflow.resize_flowq_to_stack if src.dtype == torch.uint8 else vflow.resize_flow_to_stack
+        xt = gather(src, flow_table, invert_x_on_flip=bool(invert_flow_x)).view(n * k, 2 * L, 224, 224)
         cur.wait_stream(self._cnn)   # forwards submitted earlier read the weights this step updates
         cur.wait_stream(self._cnn2)
         stats_s, desc_s = step(self.spatial, xs)

@@ -213,6 +213,38 @@ def saveFlowImages(flow, flowDir, bound=20.0, firstIndex=1, quality=95):
     return 2 * q.shape[0]
 
 
+def loadFlowImages(flowDir, first=1, count=None):
+    """The reader of what ``saveFlowImages`` and the reference's flow directory hold: ``flow_x_%04d.jpg`` /
+    ``flow_y_%04d.jpg`` from index ``first`` (1-based) on -> uint8 numpy ``[N,2,H,W]``, plane 0 x and plane 1 y, a uint8
+    stored flow once on the device.  ``count``: how many pairs to read; None reads on until an index has
+    neither file.  ValueError for a missing file, images of different sizes and an image that is not single-channel 'L'."""
+    from PIL import Image
+    from .parameters import FRAME_EXTN, X_PREFIX_FLOW, Y_PREFIX_FLOW
+    first = int(first)
+    if count is not None and int(count) < 1:
+        raise ValueError("loadFlowImages: count must be >= 1, got %r" % (count,))
+    fields, k = [], first
+    while count is None or k < first + int(count):
+        paths = [os.path.join(flowDir, flowFileName(prefix, k, FRAME_EXTN)) for prefix in (X_PREFIX_FLOW, Y_PREFIX_FLOW)]
+        there = [os.path.isfile(p) for p in paths]
+        if count is None and not any(there) and fields:
+            break
+        if not all(there):
+            raise ValueError("loadFlowImages: missing %s" % paths[there.index(False)])
+        planes = []
+        for p in paths:
+            with Image.open(p) as img:
+                if img.mode != "L":
+                    raise ValueError("loadFlowImages: %s has mode %r, not the single-channel 'L' of flow images" % (p, img.mode))
+                planes.append(np.asarray(img, dtype=np.uint8))
+        if planes[0].shape != planes[1].shape or (fields and planes[0].shape != fields[0].shape[1:]):
+            raise ValueError("loadFlowImages: %s is %dx%d, not the size of the images before it"
+                             % (paths[0], planes[1].shape[1], planes[1].shape[0]))
+        fields.append(np.stack(planes))
+        k += 1
+    return np.stack(fields)
+
+
 # ----------------------------------------------------------------------------- transforms ------
 
 class RandomCrop(object):

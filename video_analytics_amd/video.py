@@ -118,7 +118,7 @@ def segmentPlan(T, starts, L=VIDEO_INPUT_FLOW_COUNT):
     return SegmentPlan(T, starts, L)
 
 
-def evaluateVideos(pipe, videos, labels, **kw):
+def evaluateVideos(pipe, videos, labels, flows=None, **kw):
     """The test protocol over a list of videos: ``videos`` yields ``(rgb u8 [T,3,H,W], gray [T,H,W])`` pairs on the
     pipeline's device, ``labels`` their class indices; ``kw`` goes to ``TwoStreamPipeline.submit_video``.  Returns
     ``(acc_spatial, acc_temporal, acc_fused, descriptors)``: the fractions of videos whose spatial, temporal and fused
@@ -134,8 +134,14 @@ def evaluateVideos(pipe, videos, labels, **kw):
     call belong to one dataset, the scores are that head's and ``labels`` are local to it.
 
     Decoded frames: an entry of ``videos`` may be ``(rgb, None)`` or ``rgb`` alone, and ``rescale=`` travels
-    through ``kw``: ``submit_video`` then rescales the frames and derives the gray frames on the device."""
+    through ``kw``: ``submit_video`` then rescales the frames and derives the gray frames on the device.
+
+    Stored flow: ``flows`` is an iterable parallel to ``videos``, one stored flow per video
+    (``TwoStreamPipeline.extract_flow``), handed to ``submit_video(flow=)``: no TV-L1 runs, and the videos come without gray
+    frames.  Fewer or more stored flows than videos raise ValueError."""
     labels = [int(l) for l in labels]
+    stored = iter(flows) if flows is not None else None
+    missing = object()
     rows, pending, n = [], None, 0
     third = getattr(pipe, "diff", None) is not None
     keys = ("scores_s", "scores_t", "pred", "desc_s", "desc_t") + (("desc_d", "scores_d") if third else ())
@@ -146,7 +152,13 @@ def evaluateVideos(pipe, videos, labels, **kw):
 
     for v in videos:
         rgb, gray = v if isinstance(v, (tuple, list)) else (v, None)
-        out = pipe.submit_video(rgb, gray, **kw)
+        if stored is not None:
+            f = next(stored, missing)
+            if f is missing:
+                raise ValueError("evaluateVideos: fewer stored flows than videos")
+            out = pipe.submit_video(rgb, gray, flow=f, **kw)
+        else:
+            out = pipe.submit_video(rgb, gray, **kw)
         n += 1
         if pending is not None:
             collect(pending)
@@ -154,6 +166,8 @@ def evaluateVideos(pipe, videos, labels, **kw):
     if pending is not None:
         collect(pending)
     pipe.wait()
+    if stored is not None and next(stored, missing) is not missing:
+        raise ValueError("evaluateVideos: more stored flows than videos")
     if n != len(labels):
         raise ValueError("evaluateVideos: %d videos but %d labels" % (n, len(labels)))
     if n == 0:

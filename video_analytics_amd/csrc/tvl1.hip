@@ -854,6 +854,13 @@ constexpr bool stream_keep_last() { return NWV >= 3 && NCH == 1 && KH >= 2; }
 template <int KH, int NWV, int NCH>
 constexpr int stream_ring_rows() { return NWV == 1 ? KH + NCH - 2 : NWV * (KH + NCH) - 2 - (stream_keep_last<KH, NWV, NCH>() ? 1 : 0); }
 
+// Forms that have a second copy of the pipeline without the right-border multiplier (stream_job, MX1): 4 x 4 and 4 x 3.
+// The copy doubles a form's code and leaves its registers as they are.  4 x 5 measured no gain from it (179^2 equal,
+// 143^2 1 % slower: both copies of its 22 KB of steady loops run side by side on a CU); the one- and two-wave fallback
+// forms stay on one body.
+template <int KH, int NWV>
+constexpr bool kStreamMx1 = NWV >= 3 && KH <= 4;
+
 template <int PPL>
 struct StreamRow {  // the six state fields of one row of a strip
     Row<PPL> u1, u2, p11, p12, p21, p22;
@@ -872,9 +879,14 @@ __device__ __forceinline__ void stream_job(const StreamArgs& a, const int pair, 
     // wave writes row s - 1 at the start of step s (after the barrier), the oldest row read in step s is
     // s - (NWV * SPAN - 2), whose slot is that of row s (written in step s + 1).
     constexpr int NRING = stream_ring_rows<KH, NWV, NCH>() > 0 ? stream_ring_rows<KH, NWV, NCH>() : 1;
-    __shared__ f2 ringP[NRING][kNF_RO][NP][64];
+    // A lane's fields sit side by side in 16-byte units -- ring: (wx, wy), (rc, ig); hand-over: (u1, u2), (p11, p12),
+    // (p21, p22) -- so that every access is one ds_read_b128 / ds_write_b128; consecutive lanes lie 16 bytes apart
+    // (no bank conflicts), the sizes are those of field-by-field arrays
+    typedef float f4 __attribute__((ext_vector_type(4)));
+    static_assert(kNF_RO % 2 == 0 && kNF_STATE % 2 == 0, "fields pair up into 16-byte units");
+    __shared__ f4 ringP[NRING][kNF_RO / 2][NP][64];
     __shared__ float ringT[NRING][kNF_RO][NT ? 64 : 1];
-    __shared__ f2 ifaceP[NWV > 1 ? NWV - 1 : 1][2][kNF_STATE][NP][64];
+    __shared__ f4 ifaceP[NWV > 1 ? NWV - 1 : 1][2][kNF_STATE / 2][NP][64];
     __shared__ float ifaceT[NWV > 1 ? NWV - 1 : 1][2][kNF_STATE][NT ? 64 : 1];
 
     const int sx = job % a.nsx, ch = job / a.nsx;
@@ -911,43 +923,57 @@ __device__ __forceinline__ void stream_job(const StreamArgs& a, const int pair, 
     const float l_t = a.l_t, taut = a.taut, theta = a.theta;
     const R zero = row_splat<PPL>(0.0f), one = row_splat<PPL>(1.0f);
 
-    auto ring_put = [&](int slot, int f, const R& v) __attribute__((always_inline)) {
+    // one 16-byte unit: the fields f and f + 1 (f even) of a lane
+    auto unit_put = [&](f4 (*u)[64], float (*t)[NT ? 64 : 1], int f, const R& v0, const R& v1) __attribute__((always_inline)) {
 #pragma clang loop unroll(full)
-        for (int j = 0; j < NP; ++j) ringP[slot][f][j][lane] = v.p[j];
-        if constexpr (NT) ringT[slot][f][lane] = v.t;
+        for (int j = 0; j < NP; ++j) u[j][lane] = f4{v0.p[j].x, v0.p[j].y, v1.p[j].x, v1.p[j].y};
+        if constexpr (NT) {
+            t[f][lane] = v0.t;
+            t[f + 1][lane] = v1.t;
+        }
     };
-    auto ring_get = [&](int slot, int f) __attribute__((always_inline)) -> R {
-        R v;
+    auto unit_get = [&](const f4 (*u)[64], const float (*t)[NT ? 64 : 1], int f, R& v0, R& v1) __attribute__((always_inline)) {
 #pragma clang loop unroll(full)
-        for (int j = 0; j < NP; ++j) v.p[j] = ringP[slot][f][j][lane];
-        v.t = 0.0f;
-        if constexpr (NT) v.t = ringT[slot][f][lane];
-        return v;
+        for (int j = 0; j < NP; ++j) {
+            const f4 q = u[j][lane];
+            v0.p[j] = f2{q.x, q.y};
+            v1.p[j] = f2{q.z, q.w};
+        }
+        v0.t = v1.t = 0.0f;
+        if constexpr (NT) {
+            v0.t = t[f][lane];
+            v1.t = t[f + 1][lane];
+        }
     };
-    auto if_put = [&](int wb, int b, int f, const R& v) __attribute__((always_inline)) {
+    auto ring_put = [&](int slot, const R (&v)[kNF_RO]) __attribute__((always_inline)) {
 #pragma clang loop unroll(full)
-        for (int j = 0; j < NP; ++j) ifaceP[wb][b][f][j][lane] = v.p[j];
-        if constexpr (NT) ifaceT[wb][b][f][lane] = v.t;
+        for (int f = 0; f < kNF_RO; f += 2) unit_put(ringP[slot][f / 2], ringT[slot], f, v[f], v[f + 1]);
     };
-    auto if_get = [&](int wb, int b, int f) __attribute__((always_inline)) -> R {
-        R v;
+    auto ring_get = [&](int slot, R (&v)[kNF_RO]) __attribute__((always_inline)) {
 #pragma clang loop unroll(full)
-        for (int j = 0; j < NP; ++j) v.p[j] = ifaceP[wb][b][f][j][lane];
-        v.t = 0.0f;
-        if constexpr (NT) v.t = ifaceT[wb][b][f][lane];
-        return v;
+        for (int f = 0; f < kNF_RO; f += 2) unit_get(ringP[slot][f / 2], ringT[slot], f, v[f], v[f + 1]);
+    };
+    auto if_put = [&](int wb, int b, const SR& v) __attribute__((always_inline)) {
+        unit_put(ifaceP[wb][b][0], ifaceT[wb][b], 0, v.u1, v.u2);
+        unit_put(ifaceP[wb][b][1], ifaceT[wb][b], 2, v.p11, v.p12);
+        unit_put(ifaceP[wb][b][2], ifaceT[wb][b], 4, v.p21, v.p22);
+    };
+    auto if_get = [&](int wb, int b, SR& v) __attribute__((always_inline)) {
+        unit_get(ifaceP[wb][b][0], ifaceT[wb][b], 0, v.u1, v.u2);
+        unit_get(ifaceP[wb][b][1], ifaceT[wb][b], 2, v.p11, v.p12);
+        unit_get(ifaceP[wb][b][2], ifaceT[wb][b], 4, v.p21, v.p22);
     };
 
-    for (int r = wv; r < NRING; r += NWV)
-#pragma clang loop unroll(full)
-        for (int f = 0; f < kNF_RO; ++f) ring_put(r, f, zero);
+    {
+        const R zro[kNF_RO] = {zero, zero, zero, zero};
+        for (int r = wv; r < NRING; r += NWV) ring_put(r, zro);
+    }
     if constexpr (NWV > 1) {
-        if (wv < NWV - 1)  // wave w zeroes the hand-over rows it will write
-#pragma clang loop unroll(full)
-            for (int f = 0; f < kNF_STATE; ++f) {
-                if_put(wv, 0, f, zero);
-                if_put(wv, 1, f, zero);
-            }
+        if (wv < NWV - 1) {  // wave w zeroes the hand-over rows it will write
+            const SR zst{zero, zero, zero, zero, zero, zero};
+            if_put(wv, 0, zst);
+            if_put(wv, 1, zst);
+        }
         __syncthreads();
     }
 
@@ -959,8 +985,11 @@ __device__ __forceinline__ void stream_job(const StreamArgs& a, const int pair, 
     // waits one step at every chain end on its way to the last wave's output: NWV * NCH - 1 of them
     const int nsteps = b0 - ys + K + (NWV * NCH - 1);
 
-    auto run = [&](auto wave_tag) __attribute__((always_inline)) {
+    // MX1: no lane of the strip holds the image's last column or a column beyond it (mx = 1 in every lane): the x
+    // differences need no multiplier (x * 1 = x exactly)
+    auto run = [&](auto wave_tag, auto mx1_tag) __attribute__((always_inline)) {
         constexpr int W = decltype(wave_tag)::value;
+        constexpr bool MX1 = decltype(mx1_tag)::value;
         constexpr bool FIRST = W == 0, LAST = W == NWV - 1;
         constexpr int G0 = W * KH, LAG = W * SH::SPAN;  // first level of this wave; steps it runs behind the first wave
 
@@ -998,8 +1027,8 @@ __device__ __forceinline__ void stream_job(const StreamArgs& a, const int pair, 
             const R n1 = r_fma_s(theta, div1, v1);
             const R n2 = r_fma_s(theta, div2, v2);
             const R d1x = r_diff_fwd(U1[t]), d2x = r_diff_fwd(U2[t]);
-            const R u1x = r_mul(d1x, mx), u1y = MY1 ? r_sub(n1, U1[t]) : r_mul_s(r_sub(n1, U1[t]), my);
-            const R u2x = r_mul(d2x, mx), u2y = MY1 ? r_sub(n2, U2[t]) : r_mul_s(r_sub(n2, U2[t]), my);
+            const R u1x = MX1 ? d1x : r_mul(d1x, mx), u1y = MY1 ? r_sub(n1, U1[t]) : r_mul_s(r_sub(n1, U1[t]), my);
+            const R u2x = MX1 ? d2x : r_mul(d2x, mx), u2y = MY1 ? r_sub(n2, U2[t]) : r_mul_s(r_sub(n2, U2[t]), my);
             const R s1 = r_fma(u1y, u1y, r_fma_c(u1x, u1x, kSqrtReg));
             const R s2 = r_fma(u2y, u2y, r_fma_c(u2x, u2x, kSqrtReg));
             const R d1 = r_fma_s(taut, r_sqrt<PPL, FAST>(s1), one);
@@ -1050,18 +1079,12 @@ __device__ __forceinline__ void stream_job(const StreamArgs& a, const int pair, 
                 for (int f = 0; f < kNF_RO; ++f) nro[f] = ld_ro(f, rn);
                 if constexpr (NWV > 1) {  // the constants of row s - 1 go into the ring now that the barrier has passed
                     const int sl = s0 == 0 ? NRING - 1 : s0 - 1;
-#pragma clang loop unroll(full)
-                    for (int f = 0; f < kNF_RO; ++f) ring_put(sl, f, rprev[f]);
+                    ring_put(sl, rprev);
                 }
                 __builtin_amdgcn_sched_barrier(0);  // the loads stay at the top of the step: a whole step hides their latency
             } else {
                 const int bsel = (s + 1) & 1;  // what the wave before wrote in step s - 1
-                cc[0].u1 = if_get(W - 1, bsel, 0);
-                cc[0].u2 = if_get(W - 1, bsel, 1);
-                cc[0].p11 = if_get(W - 1, bsel, 2);
-                cc[0].p12 = if_get(W - 1, bsel, 3);
-                cc[0].p21 = if_get(W - 1, bsel, 4);
-                cc[0].p22 = if_get(W - 1, bsel, 5);
+                if_get(W - 1, bsel, cc[0]);
             }
 #pragma clang loop unroll(full)
             for (int c = 1; c < NCH; ++c) cc[c] = latch[c - 1];
@@ -1081,9 +1104,7 @@ __device__ __forceinline__ void stream_job(const StreamArgs& a, const int pair, 
 #pragma clang loop unroll(full)
                         for (int f = 0; f < kNF_RO; ++f) q[c][f] = r0[f];
                     } else {
-                        const int slot = slot_of(c * KC);
-#pragma clang loop unroll(full)
-                        for (int f = 0; f < kNF_RO; ++f) q[c][f] = ring_get(slot, f);
+                        ring_get(slot_of(c * KC), q[c]);
                     }
                 }
 #pragma clang loop unroll(full)
@@ -1100,9 +1121,7 @@ __device__ __forceinline__ void stream_job(const StreamArgs& a, const int pair, 
 #pragma clang loop unroll(full)
                                 for (int f = 0; f < kNF_RO; ++f) nq[c][f] = keep[f];
                             } else {
-                                const int slot = slot_of(c * KC + i + 1);
-#pragma clang loop unroll(full)
-                                for (int f = 0; f < kNF_RO; ++f) nq[c][f] = ring_get(slot, f);
+                                ring_get(slot_of(c * KC + i + 1), nq[c]);
                             }
                         }
                         __builtin_amdgcn_sched_barrier(0);
@@ -1133,15 +1152,14 @@ __device__ __forceinline__ void stream_job(const StreamArgs& a, const int pair, 
                         } else if (KEEP && t == KH - 1) {
                             level(t, cc[t / KC], keep[0], keep[1], keep[2], keep[3], my, std::false_type{});
                         } else {
-                            const int slot = slot_of(t);
-                            level(t, cc[t / KC], ring_get(slot, 0), ring_get(slot, 1), ring_get(slot, 2), ring_get(slot, 3), my, std::false_type{});
+                            R q[kNF_RO];
+                            ring_get(slot_of(t), q);
+                            level(t, cc[t / KC], q[0], q[1], q[2], q[3], my, std::false_type{});
                         }
                     }
                 }
                 if constexpr (KEEP) {  // whether or not level KH - 2 worked in this step: the row it stands at is level KH - 1's next one
-                    const int slot = slot_of(KH - 2);
-#pragma clang loop unroll(full)
-                    for (int f = 0; f < kNF_RO; ++f) keep[f] = ring_get(slot, f);
+                    ring_get(slot_of(KH - 2), keep);
                 }
             }
 #pragma clang loop unroll(full)
@@ -1159,18 +1177,11 @@ __device__ __forceinline__ void stream_job(const StreamArgs& a, const int pair, 
                     st(co.p22, 5, rout);
                 }
             } else {
-                const int bsel = s & 1;
-                if_put(W, bsel, 0, co.u1);
-                if_put(W, bsel, 1, co.u2);
-                if_put(W, bsel, 2, co.p11);
-                if_put(W, bsel, 3, co.p12);
-                if_put(W, bsel, 4, co.p21);
-                if_put(W, bsel, 5, co.p22);
+                if_put(W, s & 1, co);
             }
             if constexpr (FIRST) {
                 if constexpr (NWV == 1) {
-#pragma clang loop unroll(full)
-                    for (int f = 0; f < kNF_RO; ++f) ring_put(s0, f, r0[f]);
+                    ring_put(s0, r0);
                 } else {
 #pragma clang loop unroll(full)
                     for (int f = 0; f < kNF_RO; ++f) rprev[f] = r0[f];
@@ -1203,21 +1214,31 @@ __device__ __forceinline__ void stream_job(const StreamArgs& a, const int pair, 
         for (; s < s_b; ++s) step(s, std::true_type{});
         for (; s < nsteps; ++s) step(s, std::false_type{});
     };
-    if constexpr (NWV == 1) {
-        run(std::integral_constant<int, 0>{});
-    } else if constexpr (NWV == 2) {
-        if (wv == 0) run(std::integral_constant<int, 0>{});
-        else run(std::integral_constant<int, NWV - 1>{});
-    } else if constexpr (NWV == 3) {
-        if (wv == 0) run(std::integral_constant<int, 0>{});
-        else if (wv == 1) run(std::integral_constant<int, 1>{});
-        else run(std::integral_constant<int, 2>{});
+    auto waves = [&](auto mx1_tag) __attribute__((always_inline)) {
+        if constexpr (NWV == 1) {
+            run(std::integral_constant<int, 0>{}, mx1_tag);
+        } else if constexpr (NWV == 2) {
+            if (wv == 0) run(std::integral_constant<int, 0>{}, mx1_tag);
+            else run(std::integral_constant<int, NWV - 1>{}, mx1_tag);
+        } else if constexpr (NWV == 3) {
+            if (wv == 0) run(std::integral_constant<int, 0>{}, mx1_tag);
+            else if (wv == 1) run(std::integral_constant<int, 1>{}, mx1_tag);
+            else run(std::integral_constant<int, 2>{}, mx1_tag);
+        } else {
+            static_assert(NWV == 4, "pipelines of one to four waves");
+            if (wv == 0) run(std::integral_constant<int, 0>{}, mx1_tag);
+            else if (wv == 1) run(std::integral_constant<int, 1>{}, mx1_tag);
+            else if (wv == 2) run(std::integral_constant<int, 2>{}, mx1_tag);
+            else run(std::integral_constant<int, 3>{}, mx1_tag);
+        }
+    };
+    // a strip that ends before the image's last column (never the last strip of a row, never a shared one) runs the copy
+    // without the x multiplier; the choice is uniform over the workgroup and made once per job
+    if constexpr (kStreamMx1<KH, NWV>) {
+        if (half == 0 && ox + SW < w) waves(std::true_type{});
+        else waves(std::false_type{});
     } else {
-        static_assert(NWV == 4, "pipelines of one to four waves");
-        if (wv == 0) run(std::integral_constant<int, 0>{});
-        else if (wv == 1) run(std::integral_constant<int, 1>{});
-        else if (wv == 2) run(std::integral_constant<int, 2>{});
-        else run(std::integral_constant<int, 3>{});
+        waves(std::false_type{});
     }
 }
 

@@ -191,7 +191,7 @@ struct ConvArgs {
     int tiles_x, tiles_y, tiles_n;
     const float* mask;  // training (dgrad): zero the output where mask[same index] <= 0 (NULL: no mask; not with POOL)
     int linear;         // 1: no ReLU (training: dgrad)
-    const float* zeros; // DMA kernel: >= 16 zero bytes, the source of every out-of-image tap
+    const float* zeros; // >= 16 zero bytes (the DMA kernel's dispatch asks for them; its out-of-image taps are out-of-range buffer loads now)
 };
 
 // XCD-aware workgroup order: consecutive workgroup ids are dealt round-robin to the 8 XCDs (each with its own L2), so
@@ -1521,17 +1521,23 @@ __global__ void __launch_bounds__(512) k_conv3x3_img14(Img14Args a)
 // the DMA ring for small grids) with fp32 data: K step = 32 channels (a 128-byte line per pixel), 16-byte
 // fragment reads feed four v_mfma_f32_32x32x2_f32 each (lane half hh holds k = 8*ks + 4*hh + j for both
 // operands).  Needs Cin % 32 == 0.
+// What a K step costs a wave beside its 64 (NT = 1: 32) MFMAs is the serial part in front of them: forming the DMA
+// addresses, issuing the pieces, waiting for them.  With 64-bit pointer selects behind a branch per piece that part
+// held the 224^2 .. 28^2 layers at 64-78 % MFMA utilisation; with buffer offsets formed one step ahead it is eight
+// (six) buffer loads on scalar LDS addresses: 6-12 % less time per layer (profiles/r04).
 constexpr int kDmaBK = 32;
 
+// (the body is a __device__ function: see k_conv3x3_pp_bf16)
 template <int NT, bool POOL, int NBUF>
-__global__ void __launch_bounds__(256, NBUF == 1 ? 4 : 2) k_conv3x3_dma_f32(ConvArgs a)
+__device__ __forceinline__ void conv3x3_dma_f32_body(const ConvArgs& a)
 {
     constexpr int BM = 128, BN = NT * 64, MT = 2;
     constexpr int A_INSTR = BM / 32, B_INSTR = BN / 32;  // LDS-DMA instructions per wave and K step (8 rows each)
-    constexpr int TILE = (BM + BN) * kDmaBK;  // bf16 elements of one K step's A and B tiles
+    constexpr int TILE = (BM + BN) * kDmaBK;  // floats of one K step's A and B tiles
     __shared__ __attribute__((aligned(1024))) float smem[NBUF * TILE];
 
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);  // (scalar: the DMA pieces' LDS addresses stay out of the vector registers)
     const int wm = wave >> 1, wn = wave & 1;
     int bid = xcd_remap(blockIdx.x, gridDim.x);
     const int n_tile = bid % a.tiles_n;
@@ -1544,28 +1550,43 @@ __global__ void __launch_bounds__(256, NBUF == 1 ? 4 : 2) k_conv3x3_dma_f32(Conv
     const int H = a.H, W = a.W, Cin = a.Cin;
     const int X0 = tile_x << a.lgTW, Y0 = tile_y << a.lgTH, B0 = tile_b * a.TB;
 
-    // loader role: row (lane >> 3) of the 8-row group, slot (lane & 7)
+    // loader role: row (lane >> 3) of the 8-row group, slot (lane & 7).
+    // Addressing: buffer loads to LDS, as in k_conv3x3_mfma_bf16, but with one activation resource PER BRICK (no limit on
+    // the batch): it starts (W + 1) pixels before the brick's first pixel, so that the tap offset
+    // ((ky + 1) W + kx + 1) Cin + c0 is a non-negative scalar (soffset) and a lane's own offset is the one of its pixel
+    // from the brick's first; a lane whose tap falls outside the image gets an out-of-range offset, for which the buffer
+    // load writes zeros.  A lane's nine in-image decisions are nine bits.  Per DMA piece that is two registers for the
+    // activations and one for the weights: the K loop keeps 128 registers per wave (four workgroups per CU) with TWO
+    // fragment sets beside the 64 accumulator registers, and a 64-bit pointer and two coordinates per piece do not fit.
+    // (Byte offsets inside a brick stay below 2^31 - 1: launch_conv_ex checks it.)
     const int lrow = lane >> 3, lslot = lane & 7;
-    int ax[A_INSTR], ay[A_INSTR];
-    long apix[A_INSTR];
-    bool aok[A_INSTR];
+    const __amdgpu_buffer_rsrc_t rs_a = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<float*>(a.in) + ((((long)B0 * H + Y0) * W + X0) - (W + 1)) * Cin, 0, 0x7fffffff, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_b = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<float*>(a.wp) + (size_t)n0 * 9 * Cin, 0, BN * 9 * Cin * 4, 0x00020000);
+    int arel[A_INSTR], amask[A_INSTR];
 #pragma unroll
     for (int i = 0; i < A_INSTR; ++i) {
         const int row = (wave * A_INSTR + i) * 8 + lrow;
         const int c = lslot ^ ((row >> 1) & 7);
         int xl, yl, bl;
         brick_coords(row, a.lgTW, a.lgTH, xl, yl, bl);
-        ax[i] = X0 + xl;
-        ay[i] = Y0 + yl;
-        const int b = B0 + bl;
-        aok[i] = b < a.B && ax[i] < W && ay[i] < H;
-        apix[i] = (((long)b * H + ay[i]) * W + ax[i]) * Cin + 4 * c;
+        const int x = X0 + xl, y = Y0 + yl;
+        const bool ok = B0 + bl < a.B && x < W && y < H;
+        arel[i] = ok ? (((bl * H + yl) * W + xl) * Cin + 4 * c) * 4 : 0;
+        int m = 0;
+#pragma unroll
+        for (int k = 0; k < 9; ++k) {
+            const int yy = y + k / 3 - 1, xx = x + k % 3 - 1;
+            if (ok && yy >= 0 && yy < H && xx >= 0 && xx < W) m |= 1 << k;
+        }
+        amask[i] = m;
     }
-    const float* wrow[B_INSTR];
+    int woff[B_INSTR];
 #pragma unroll
     for (int i = 0; i < B_INSTR; ++i) {
         const int row = (wave * B_INSTR + i) * 8 + lrow;
-        wrow[i] = a.wp + (size_t)(n0 + row) * 9 * Cin + 4 * (lslot ^ ((row >> 1) & 7));
+        woff[i] = (row * 9 * Cin + 4 * (lslot ^ ((row >> 1) & 7))) * 4;
     }
 
     f32x16 acc[MT][NT];
@@ -1581,64 +1602,92 @@ __global__ void __launch_bounds__(256, NBUF == 1 ? 4 : 2) k_conv3x3_dma_f32(Conv
     const int r31 = lane & 31, hh = lane >> 5;
     const int fsw = (r31 >> 1) & 7;  // fragment rows are (multiple of 32) + r31
     int kp = 0, c0 = 0;
-    // LDS-DMA of K step (kp, c0) into ring slot `buf`; advances (kp, c0)
-    auto stage = [&](int buf) {
-        float* const sA = smem + buf * TILE;
-        float* const sB = sA + BM * kDmaBK;
-        const int ky = kp / 3 - 1, kx = kp % 3 - 1;
-        const long tap = ((long)ky * W + kx) * Cin + c0;
-        static_for<A_INSTR>([&](auto I) {
-            constexpr int i = decltype(I)::value;
-            const int yy = ay[i] + ky, xx = ax[i] + kx;
-            const bool ok = aok[i] && yy >= 0 && yy < H && xx >= 0 && xx < W;
-            const float* src = ok ? a.in + apix[i] + tap : a.zeros;
-            __builtin_amdgcn_global_load_lds((gbl_ptr_t)src, (lds_ptr_t)(sA + (wave * A_INSTR + i) * 8 * kDmaBK), 16, 0, 0);
-        });
-        static_for<B_INSTR>([&](auto I) {
-            constexpr int i = decltype(I)::value;
-            __builtin_amdgcn_global_load_lds((gbl_ptr_t)(wrow[i] + (size_t)kp * Cin + c0),
-                                             (lds_ptr_t)(sB + (wave * B_INSTR + i) * 8 * kDmaBK), 16, 0, 0);
-        });
+    // The DMA offsets of K step (kp, c0): per activation piece the lane's offset or the out-of-range one, and the scalar
+    // byte offsets ((ky + 1) W + kx + 1) Cin + c0 (activations, biased) and kp Cin + c0 (weights); advances (kp, c0).
+    // (Past the last step: offsets nobody loads from.)
+    int avo[A_INSTR], so_a, so_b;
+    auto prep = [&]() __attribute__((always_inline)) {
+#pragma unroll
+        for (int i = 0; i < A_INSTR; ++i) avo[i] = arel[i] | (int)(((unsigned)amask[i] >> kp & 1u) - 1u);  // (all ones: out of range)
+        so_a = (((kp / 3) * W + kp % 3) * Cin + c0) * 4;
+        so_b = (kp * Cin + c0) * 4;
         c0 += kDmaBK;
         if (c0 == Cin) {
             c0 = 0;
             ++kp;
         }
     };
-    auto compute = [&](int buf) {
-        const float* const sA = smem + buf * TILE;
-        const float* const sB = sA + BM * kDmaBK;
+    // LDS-DMA of the prepared K step into ring slot `buf`
+    auto issue = [&](int buf) __attribute__((always_inline)) {
+        float* const sA = smem + buf * TILE;
+        float* const sB = sA + BM * kDmaBK;
+        static_for<A_INSTR>([&](auto I) {
+            constexpr int i = decltype(I)::value;
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_a, (lds_ptr_t)(sA + (wave * A_INSTR + i) * 8 * kDmaBK), 16, avo[i], so_a, 0, 0);
+        });
+        static_for<B_INSTR>([&](auto I) {
+            constexpr int i = decltype(I)::value;
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_b, (lds_ptr_t)(sB + (wave * B_INSTR + i) * 8 * kDmaBK), 16, woff[i], so_b, 0, 0);
+        });
+    };
+    // Fragments: two register sets.  The reads of sub-step ks + 1 are issued BEFORE the sixteen (NT = 1: eight) MFMAs of
+    // sub-step ks and waited for only when ks + 1 starts (sched_barrier pins that order, as in k_conv3x3_img14); left to
+    // itself the compiler reads one set and waits for it in front of every MFMA group.  Sub-step ks reads slot
+    // (2 ks + hh) ^ fsw of its rows' 128-byte lines: byte offset (the one of ks = 0) ^ 32 ks.  Product order per
+    // accumulator as before: ks, then j, for every K step.  Measured on the layer table: 1.4 % on the 28^2 layers (three
+    // workgroups per CU on average: the fewest other waves to cover a read), within 1 % elsewhere.
+    constexpr int KS = kDmaBK / 8;
+    int fa0 = (((wm * MT) * 32 + r31) * kDmaBK + (hh ^ fsw) * 4) * 4, fb0 = (((wn * NT) * 32 + r31) * kDmaBK + (hh ^ fsw) * 4) * 4;
+    f32x4 fa[2][MT], fb[2][NT];
+    auto fetch = [&](int buf, auto KSI) __attribute__((always_inline)) {
+        constexpr int ks = decltype(KSI)::value, set = ks & 1;
+        const char* const sA = (const char*)(smem + buf * TILE);
+        const char* const sB = sA + BM * kDmaBK * 4;
 #pragma unroll
-        for (int ks = 0; ks < kDmaBK / 8; ++ks) {
-            f32x4 fa[MT], fb[NT];
-            const int slot = ((2 * ks + hh) ^ fsw) * 4;
+        for (int mt = 0; mt < MT; ++mt) fa[set][mt] = *reinterpret_cast<const f32x4*>(sA + (fa0 ^ (32 * ks)) + mt * 32 * kDmaBK * 4);
 #pragma unroll
-            for (int mt = 0; mt < MT; ++mt)
-                fa[mt] = *reinterpret_cast<const f32x4*>(&sA[((wm * MT + mt) * 32 + r31) * kDmaBK + slot]);
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt)
-                fb[nt] = *reinterpret_cast<const f32x4*>(&sB[((wn * NT + nt) * 32 + r31) * kDmaBK + slot]);
+        for (int nt = 0; nt < NT; ++nt) fb[set][nt] = *reinterpret_cast<const f32x4*>(sB + (fb0 ^ (32 * ks)) + nt * 32 * kDmaBK * 4);
+    };
+    // the MFMAs of one K step; fetch(buf, 0) has been issued.  `early` runs in front of the last sub-step's MFMAs.
+    auto compute = [&](int buf, auto&& early) __attribute__((always_inline)) {
+        static_for<KS>([&](auto KSI) {
+            constexpr int ks = decltype(KSI)::value, set = ks & 1;
+            if constexpr (ks + 1 < KS) fetch(buf, std::integral_constant<int, ks + 1>{});
+            if constexpr (ks + 1 == KS) early();
+            __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int j = 0; j < 4; ++j)
 #pragma unroll
                 for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
                     for (int nt = 0; nt < NT; ++nt)
-                        acc[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[mt][j], fb[nt][j], acc[mt][nt], 0, 0, 0);
-        }
+                        acc[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[set][mt][j], fb[set][nt][j], acc[mt][nt], 0, 0, 0);
+            __builtin_amdgcn_sched_barrier(0);
+        });
     };
     if constexpr (NBUF == 1) {
+        // Per K step: DMA, wait for it, barrier (the tile is published), MFMAs, barrier (the tile may be overwritten).
+        // Each barrier sits in one asm statement with its wait, so that no LDS access can move between the two; the
+        // second one waits for this wave's LDS reads only (the hazard is "every wave has read the tile").  The next
+        // step's DMA offsets are computed beside the last sub-step's MFMAs, in front of that barrier (its operand list
+        // keeps them there): behind it the wave only issues its eight or six pieces.
+        static_assert(A_INSTR == 4, "the second barrier's operand list");
+        prep();
         for (int t = 0; t < T; ++t) {
-            stage(0);
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __syncthreads();
-            compute(0);
-            __syncthreads();  // every wave has read the tile before the next DMA overwrites it
+            issue(0);
+            asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
+            asm volatile("" : "+v"(fa0), "+v"(fb0));  // (keeps the eight fragment addresses out of loop-invariant registers)
+            fetch(0, std::integral_constant<int, 0>{});
+            compute(0, [&]() __attribute__((always_inline)) { prep(); });
+            asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" : "+v"(avo[0]), "+v"(avo[1]), "+v"(avo[2]), "+v"(avo[3])::"memory");
         }
     } else {
         constexpr int LOADS = A_INSTR + B_INSTR;  // this wave's DMA instructions per K step
         // prologue: NBUF-1 steps in flight (T >= 3 >= NBUF-1 is not guaranteed for NBUF > 4: launch only NBUF <= 4)
-        for (int j = 0; j < NBUF - 1 && j < T; ++j) stage(j);
+        for (int j = 0; j < NBUF - 1 && j < T; ++j) {
+            prep();
+            issue(j);
+        }
         int slot = 0;
         for (int t = 0; t < T; ++t) {
             // wait until this wave's DMAs of step t have landed: steps t+1 .. t+NBUF-2 may stay in flight
@@ -1652,10 +1701,13 @@ __global__ void __launch_bounds__(256, NBUF == 1 ? 4 : 2) k_conv3x3_dma_f32(Conv
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             }
             // all waves: step t's tile is complete, and step t-1's reads are done, so its slot can be refilled
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();
-            if (t + NBUF - 1 < T) stage(slot == 0 ? NBUF - 1 : slot - 1);
-            compute(slot);
+            asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+            fetch(slot, std::integral_constant<int, 0>{});  // first: the refill's issue then covers their latency
+            if (t + NBUF - 1 < T) {
+                prep();
+                issue(slot == 0 ? NBUF - 1 : slot - 1);
+            }
+            compute(slot, []() {});
             slot = slot + 1 == NBUF ? 0 : slot + 1;
         }
     }
@@ -1699,6 +1751,12 @@ __global__ void __launch_bounds__(256, NBUF == 1 ? 4 : 2) k_conv3x3_dma_f32(Conv
             }
         }
     }
+}
+
+template <int NT, bool POOL, int NBUF>
+__global__ void __launch_bounds__(256, NBUF == 1 ? 4 : 2) k_conv3x3_dma_f32(ConvArgs a)
+{
+    conv3x3_dma_f32_body<NT, POOL, NBUF>(a);
 }
 
 
@@ -1930,6 +1988,8 @@ int launch_conv_ex(int hw, int cin_pad, int cout, const float* wp, const float* 
         return VA_OK;
     }
     if (f32_conv == 1 && zeros != nullptr && cin_pad % kDmaBK == 0) {
+        // the kernel's 32-bit byte offsets inside a brick and its taps (bricks that span images only arise on small frames)
+        if (((long)a.TB * hw + (1L << a.lgTH) + 4) * (hw + 32) * cin_pad * 4 >= 2147483647L) return VA_ERR_INVALID;
         const long grid64 = (long)(cout / 64) * a.tiles_x * a.tiles_y * tiles_b;
         const int ksteps = 9 * (cin_pad / kDmaBK);
         const bool ring = grid64 < VA_RING_MAXGRID_F32 && ksteps >= VA_RING;

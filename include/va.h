@@ -496,8 +496,8 @@ int va_conv3x3_layer(va_ctx* ctx, int dtype, int kernel_opt, int hw, int cin_pad
  * 3 x 3 pixels around it (its ReLU keeps a NaN).  It multiplies the tail of its 16-element K blocks -- the first
  * KROW - 3 Cp channels of the pixel after the three taps -- with zero weights, so the NaN also reaches column x - 2 of rows
  * y - 1 .. y + 1 and, when x % 16 == 15, column x + 16 of rows y - 2 .. y (the patch row of the brick to the right
- * wraps); every other output keeps its bits, and finite inputs are not affected.  The other conv kernels apply ReLU as
- * fmaxf(v, 0), which answers 0 for a NaN: on the staged paths, and in every later layer, a NaN pre-activation becomes 0.
+ * wraps); every other output keeps its bits, and finite inputs are not affected.  Every other conv kernel, the staged
+ * paths included, keeps a NaN through ReLU and the 2 x 2 max as well (IEEE maximum) and confines it to the 3 x 3 pixels.
  */
 int va_vgg16_first_layer(va_vgg16* model, const void* x, int x_is_u8, int batch,
                          void* staged, void* out, char* info, int info_len, void* stream);

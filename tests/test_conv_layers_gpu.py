@@ -288,8 +288,9 @@ def _make_inputs(case, seed):
     return dict(x=x.to(dev), w=w.to(dev), b=b.to(dev), mask=mask, in_buf=in_buf, xin=xin.view(B, hw, hw, cin), gi=gi)
 
 
-def _run(case, inp, opt, zeros):
-    """One launch into a NaN-filled output between canaries; returns (name, out copy) after checking the canaries."""
+def _run(case, inp, opt, zeros, finite=True):
+    """One launch into a NaN-filled output between canaries; returns (name, out copy) after checking the canaries.
+    ``finite=False`` (tests/test_nonfinite_gpu.py plants NaN / infinity on purpose) skips only the last assertion."""
     from video_analytics_amd import vgg
     B, hw, cout = case["B"], case["hw"], case["cout"]
     hwo = hw // 2 if case["pool"] else hw
@@ -310,7 +311,7 @@ def _run(case, inp, opt, zeros):
     torch.cuda.synchronize()
     assert torch.equal(ibuf[:go], canary[:go]) and torch.equal(ibuf[go + n:], canary[go:]), (name, "write outside out")
     assert torch.equal(inp["in_buf"].view(ity), in_before), (name, "write into `in` or its guards")
-    assert bool(torch.isfinite(out).all()), (name, "output not written everywhere (or NaN read from outside `in`)")
+    assert not finite or bool(torch.isfinite(out).all()), (name, "output not written everywhere (or NaN read from outside `in`)")
     return name, out.clone()
 
 

@@ -28,7 +28,8 @@ Measured on the MI355X: worst normalised fp32 error r = 12.0 (f32_c33; 4.1 .. 12
 
 Findings pinned here:
   * ReLU by fmaxf(v, 0) answers 0 for a NaN: a NaN input pixel left k_conv1_fused_bf16 as a plausible 0.  The kernel now
-    keeps the NaN (same bits otherwise); ``test_fused_first_layer_confines_a_nan`` holds the 3 x 3 NaN outputs.
+    keeps the NaN (same bits otherwise); ``test_fused_first_layer_confines_a_nan`` holds the 3 x 3 NaN outputs.  The
+    staged path's kernels keep it too (tests/test_nonfinite_gpu.py: every conv epilogue); the same test holds its reach.
   * k_conv1_fused_bf16 multiplies the tail of a 16-element K block -- channels of the pixel AFTER the three taps --
     with zero weights.  Finite inputs are unaffected; a NaN / infinity at (y, x) also turns column x - 2 of rows
     y - 1 .. y + 1 into NaN and, when x % 16 == 15 (patch column 0 of the brick to the right, which follows patch column
@@ -409,7 +410,8 @@ def test_unaligned_input_takes_the_staged_path(cin, rest):
 def test_fused_first_layer_confines_a_nan(cin, rest):
     """One NaN in one interior pixel of channel 0 of image 1.  Outside rows y - 1 .. y + 1 and columns x - 2 .. x + 2 of
     that image the output is bit-identical to the clean run, inside the 3 x 3 neighbourhood it is NaN (x % 16 = 5).  At
-    x % 16 == 15 the zero-weight tail of the brick to the right also reads it: column x + 16 of rows y - 2 .. y."""
+    x % 16 == 15 the zero-weight tail of the brick to the right also reads it: column x + 16 of rows y - 2 .. y.
+    The staged path (unaligned x) confines the same NaN to exactly the 3 x 3 neighbourhood."""
     w, b = _weights(cin, 400 + cin)
     m = _model(rest, "bf16", w, b)
     xc = _f32_image(2, cin, 410 + cin)
@@ -429,6 +431,22 @@ def test_fused_first_layer_confines_a_nan(cin, rest):
             allowed[1, y - 2:y + 1, xx + 16] = True
         same = (_bits(got).view(2, HW, HW, 128) == _bits(clean).view(2, HW, HW, 128)).all(dim=3)
         assert bool((same | allowed).all()), (cin, y, xx, torch.nonzero(~(same | allowed))[:8].tolist())
+    # The staged path (x 4 bytes past alignment: k_nchw_to_nhwc_xcol + the tap-major kernel) pads K with zeros of its own,
+    # never with a neighbour's channels: its reach is exactly the 3 x 3 neighbourhood, every channel of it NaN.
+    sbuf, xs = _place(xc, shift=1)
+    info, clean_s, _ = _run(m, sbuf, xs, 64)
+    assert info == (XCOL + BF_RING) % "float" and bool(torch.isfinite(clean_s).all())
+    for (y, xx) in ((100, 37), (100, 47)):
+        xn = xc.clone()
+        xn[1, 0, y, xx] = float("nan")
+        nbuf, xd = _place(xn, shift=1)
+        info, got, _ = _run(m, nbuf, xd, 64)
+        assert info == (XCOL + BF_RING) % "float"
+        hit = torch.zeros(2, HW, HW, dtype=torch.bool, device="cuda")
+        hit[1, y - 1:y + 2, xx - 1:xx + 2] = True
+        assert bool(got[hit].isnan().all()), (cin, y, xx, "staged path: the NaN was dropped")
+        same = (_bits(got).view(2, HW, HW, 128) == _bits(clean_s).view(2, HW, HW, 128)).all(dim=3)
+        assert torch.equal(~same, hit), (cin, y, xx, torch.nonzero(same == hit)[:8].tolist())
     m.close()
 
 

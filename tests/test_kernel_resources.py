@@ -53,3 +53,16 @@ def test_the_hot_kernels_keep_their_occupancy(kernels):
     assert by["k_iter_stream<2, 8, 2, false, 1>"]["lds"] <= 40960 and by["k_fc_splitk"]["vgpr"] + by["k_fc_splitk"]["agpr"] <= 128
     # LDS budgets: one 160 KB CU
     assert max(r["lds"] for r in kernels) <= 163840
+
+
+def test_the_fp32_dma_conv_kernel_keeps_its_occupancy(kernels):
+    by = {r["name"]: r for r in kernels}
+    # the fp32 LDS-DMA kernel.  Single buffer (NBUF = 1): four workgroups per CU, i.e. four waves per SIMD of 512 registers
+    # (<= 128) and a quarter of the 160 KB of LDS (<= 40 KB); the ring (NBUF = 3): two workgroups per CU (<= 256, <= 80 KB)
+    for nt in (1, 2):
+        for pool in ("true", "false"):
+            r = by["k_conv3x3_dma_f32<%d, %s, 1>" % (nt, pool)]
+            assert r["vgpr"] + r["agpr"] <= 128 and r["lds"] <= 40960 and r["max_wg"] == 256, r
+    for pool in ("true", "false"):
+        r = by["k_conv3x3_dma_f32<1, %s, 3>" % pool]
+        assert r["vgpr"] + r["agpr"] <= 256 and r["lds"] <= 81920 and r["max_wg"] == 256, r

@@ -37,7 +37,8 @@ __global__ void k_maxpool(const float* __restrict__ y, float* __restrict__ p, in
     const f32x4 a0 = src[0], a1 = src[C4], a2 = src[(size_t)H * C4], a3 = src[(size_t)H * C4 + C4];
     f32x4 m;
 #pragma unroll
-    for (int j = 0; j < 4; ++j) m[j] = fmaxf(fmaxf(a0[j], a1[j]), fmaxf(a2[j], a3[j]));
+    for (int j = 0; j < 4; ++j)  // IEEE maximum, as max_pool2d: a NaN in the window gives NaN (fmaxf would skip it)
+        m[j] = __builtin_elementwise_maximum(__builtin_elementwise_maximum(a0[j], a1[j]), __builtin_elementwise_maximum(a2[j], a3[j]));
     reinterpret_cast<f32x4*>(p)[idx] = m;
 }
 

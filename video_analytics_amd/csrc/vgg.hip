@@ -33,6 +33,15 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));       // native vectors for the staging registers:
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));    // arrays of HIP's float4/uint4 structs were kept in scratch
 
+// ReLU and the 2x2 max of every conv / FC epilogue, as IEEE 754-2019 maximum (torch's relu / amax / max_pool2d): a NaN
+// operand gives NaN.  fmaxf answers its OTHER operand for a NaN, which would turn a NaN pre-activation -- a non-finite input
+// pixel or weight -- into a plausible 0 one layer later.  One v_maximum3_f32 each on gfx950 (fmaxf: two v_max_f32, the first
+// of them quieting the operand); the same bits as fmaxf for every other pair of operands (an accumulator that starts at
+// +0 never sums to -0, so ReLU never sees the -0 / +0 pair either).
+__device__ __forceinline__ float max_keep_nan(float a, float b) { return __builtin_elementwise_maximum(a, b); }
+__device__ __forceinline__ float relu_keep_nan(float v) { return __builtin_elementwise_maximum(v, 0.0f); }
+__device__ __forceinline__ float max4_keep_nan(float a, float b, float c, float d) { return max_keep_nan(max_keep_nan(a, b), max_keep_nan(c, d)); }
+
 // Compile-time loop: the body sees its index as a constant expression, so register arrays indexed by it can
 // never be demoted to scratch (a `#pragma unroll` loop over rb[] in the conv kernels was: hipcc kept the
 // prefetched weight tile in private memory and waited for every global load right after issuing it).
@@ -353,11 +362,11 @@ __global__ void __launch_bounds__(WM * WN * 64) k_conv3x3_mfma(ConvArgs a)
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     v[j] = acc[mt][nt][4 * g4 + j] + bias;
-                    if (!a.linear) v[j] = fmaxf(v[j], 0.0f);
+                    if (!a.linear) v[j] = relu_keep_nan(v[j]);
                 }
                 if constexpr (POOL) {
                     if (x < W && y < H) {
-                        const float mx = fmaxf(fmaxf(v[0], v[1]), fmaxf(v[2], v[3]));
+                        const float mx = max4_keep_nan(v[0], v[1], v[2], v[3]);
                         a.out[((((size_t)b * (H >> 1)) + (y >> 1)) * (W >> 1) + (x >> 1)) * a.Cout + n] = mx;
                     }
                 } else {
@@ -446,10 +455,10 @@ __device__ __forceinline__ void epilogue_lines_bf16(const f32x16 (&acc)[2][NT], 
                 for (int g4 = 0; g4 < 4; ++g4) {
                     float v[4];
 #pragma unroll
-                    for (int j = 0; j < 4; ++j) v[j] = fmaxf(acc[mt][nt][4 * g4 + j] + bias, 0.0f);
+                    for (int j = 0; j < 4; ++j) v[j] = relu_keep_nan(acc[mt][nt][4 * g4 + j] + bias);
                     const int row = 8 * mt + 2 * g4 + hh;  // pooled pixel (32 mt + 8 g4 + 4 hh) / 4
                     const int col = (((n >> 3) ^ ((row / RPL) & (CH8 - 1))) << 3) | (n & 7);
-                    stage[row * ROW + col] = (__bf16)fmaxf(fmaxf(v[0], v[1]), fmaxf(v[2], v[3]));
+                    stage[row * ROW + col] = (__bf16)max4_keep_nan(v[0], v[1], v[2], v[3]);
                 }
         }
     } else {
@@ -462,10 +471,10 @@ __device__ __forceinline__ void epilogue_lines_bf16(const f32x16 (&acc)[2][NT], 
 #pragma unroll
                 for (int mt = 0; mt < 2; ++mt) {
                     bf16x4 v;
-                    v.x = (__bf16)fmaxf(acc[mt][nt][4 * g4 + 0] + bs.x, 0.0f);
-                    v.y = (__bf16)fmaxf(acc[mt][nt][4 * g4 + 1] + bs.y, 0.0f);
-                    v.z = (__bf16)fmaxf(acc[mt][nt][4 * g4 + 2] + bs.z, 0.0f);
-                    v.w = (__bf16)fmaxf(acc[mt][nt][4 * g4 + 3] + bs.w, 0.0f);
+                    v.x = (__bf16)relu_keep_nan(acc[mt][nt][4 * g4 + 0] + bs.x);
+                    v.y = (__bf16)relu_keep_nan(acc[mt][nt][4 * g4 + 1] + bs.y);
+                    v.z = (__bf16)relu_keep_nan(acc[mt][nt][4 * g4 + 2] + bs.z);
+                    v.w = (__bf16)relu_keep_nan(acc[mt][nt][4 * g4 + 3] + bs.w);
                     const int row = 32 * mt + r31;
                     const int col = (((n >> 3) ^ ((row / RPL) & (CH8 - 1))) << 3) | (n & 4);
                     *(bf16x4*)(stage + row * ROW + col) = v;
@@ -685,10 +694,10 @@ __device__ __forceinline__ void conv3x3_mfma_bf16_body(const ConvArgsBf& a)
                 if (b >= a.B) continue;
                 float v[4];
 #pragma unroll
-                for (int j = 0; j < 4; ++j) v[j] = fmaxf(acc[mt][nt][4 * g4 + j] + bias, 0.0f);
+                for (int j = 0; j < 4; ++j) v[j] = relu_keep_nan(acc[mt][nt][4 * g4 + j] + bias);
                 if constexpr (POOL) {
                     if (x < W && y < H) {
-                        const float mx = fmaxf(fmaxf(v[0], v[1]), fmaxf(v[2], v[3]));
+                        const float mx = max4_keep_nan(v[0], v[1], v[2], v[3]);
                         const size_t o = ((((size_t)b * (H >> 1)) + (y >> 1)) * (W >> 1) + (x >> 1)) * a.Cout + n;
                         if constexpr (OUT_F32) ((float*)a.out)[o] = mx;
                         else ((__bf16*)a.out)[o] = (__bf16)mx;
@@ -747,10 +756,6 @@ struct Conv1Args {
 };
 
 constexpr int kF1MaxCp = 24, kF1MaxKrow = 80;
-
-// ReLU of the fused first layer: fmaxf answers its OTHER operand for a NaN, which would turn a NaN pre-activation -- a
-// non-finite input pixel -- into a plausible 0.  The same bits as fmaxf(v, 0) for every other v.
-__device__ __forceinline__ float relu_keep_nan(float v) { return v != v ? v : fmaxf(v, 0.0f); }
 
 __global__ void k_pack_conv_w_bf16_f1(const float* __restrict__ w, __bf16* __restrict__ wp, int Cout, int Cin, int Cp, int KROW)
 {
@@ -1457,8 +1462,9 @@ __device__ __forceinline__ void conv3x3_img14_body(const Img14Args& a)
                     const int qy = wave + 4 * i, qx = 2 * g4 + hh;
                     if (qx >= 7 || qy >= 7) continue;
                     const int quad = 7 * qy + qx;
-                    const float m01 = fmaxf(acc[i][j][4 * g4 + 0], acc[i][j][4 * g4 + 1]), m23 = fmaxf(acc[i][j][4 * g4 + 2], acc[i][j][4 * g4 + 3]);
-                    out[(size_t)quad * a.Cout + n] = fmaxf(fmaxf(m01, m23) + bias, 0.0f);  // max(relu(v + b)) = relu(max(v) + b)
+                    const float mx = max4_keep_nan(acc[i][j][4 * g4 + 0], acc[i][j][4 * g4 + 1], acc[i][j][4 * g4 + 2], acc[i][j][4 * g4 + 3]);
+                    // max(relu(v + b)) = relu(max(v) + b), NaN included: the max keeps it (+inf and -inf may share a window)
+                    out[(size_t)quad * a.Cout + n] = relu_keep_nan(mx + bias);
                 }
             }
         }
@@ -1484,8 +1490,8 @@ __device__ __forceinline__ void conv3x3_img14_body(const Img14Args& a)
                 for (int g4 = 0; g4 < 4; ++g4) {
                     const int n = 32 * j + 8 * g4 + 4 * hh;
                     const float4 bs = *(const float4*)(a.bias + n0 + n);
-                    const float v0 = fmaxf(acc[i][j][4 * g4 + 0] + bs.x, 0.0f), v1 = fmaxf(acc[i][j][4 * g4 + 1] + bs.y, 0.0f);
-                    const float v2 = fmaxf(acc[i][j][4 * g4 + 2] + bs.z, 0.0f), v3 = fmaxf(acc[i][j][4 * g4 + 3] + bs.w, 0.0f);
+                    const float v0 = relu_keep_nan(acc[i][j][4 * g4 + 0] + bs.x), v1 = relu_keep_nan(acc[i][j][4 * g4 + 1] + bs.y);
+                    const float v2 = relu_keep_nan(acc[i][j][4 * g4 + 2] + bs.z), v3 = relu_keep_nan(acc[i][j][4 * g4 + 3] + bs.w);
                     T* const dst = stage + r31 * 64 + (((n / EPC) ^ (r31 & (NCHK - 1))) * EPC) + (n % EPC);
                     if constexpr (F32) {
                         *(float4*)dst = make_float4(v0, v1, v2, v3);
@@ -1731,11 +1737,11 @@ __device__ __forceinline__ void conv3x3_dma_f32_body(const ConvArgs& a)
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     v[j] = acc[mt][nt][4 * g4 + j] + bias;
-                    if (!a.linear) v[j] = fmaxf(v[j], 0.0f);
+                    if (!a.linear) v[j] = relu_keep_nan(v[j]);
                 }
                 if constexpr (POOL) {
                     if (x < W && y < H) {
-                        const float mx = fmaxf(fmaxf(v[0], v[1]), fmaxf(v[2], v[3]));
+                        const float mx = max4_keep_nan(v[0], v[1], v[2], v[3]);
                         a.out[((((size_t)b * (H >> 1)) + (y >> 1)) * (W >> 1) + (x >> 1)) * a.Cout + n] = mx;
                     }
                 } else {
@@ -1870,7 +1876,7 @@ __global__ void k_fc_reduce(const float* __restrict__ slab, const float* __restr
     const int m = idx / N, n = idx - m * N;
     float acc = bias[n];
     for (int s = 0; s < S; ++s) acc += slab[((size_t)s * Mp + m) * Npad + n];
-    out[idx] = relu ? fmaxf(acc, 0.0f) : acc;
+    out[idx] = relu ? relu_keep_nan(acc) : acc;
 }
 
 // Sheet03/spatialModel.py:219-221: mean CE over the batch, first-max argmax, correct count.

@@ -692,7 +692,8 @@ int va_fuse_scores_n(va_ctx* ctx, const void* const* scores, const float* weight
  * layer d is kept and doubled iff video_analytics_amd.synth.hash_uniform(dropout_seed, 100 + d)[i] >= 0.5),
  * mean cross-entropy (nn.CrossEntropyLoss, Sheet03/spatialModel.py:114), backward through the whole network
  * (max-pool gradient to the first maximum of each window, like torch), then torch.optim.SGD's update of every
- * parameter (Sheet03/spatialModel.py:116: buf = momentum*buf + grad; p -= lr*buf; no weight decay).
+ * parameter (Sheet03/spatialModel.py:116: buf = momentum*buf + grad; p -= lr*buf; no weight decay).  Weight decay, another
+ * dropout ratio and frozen layers: va_vgg16_set_solver below; this paragraph describes its defaults.
  *   va_vgg16_train_init   allocates and zeroes the momentum buffers (the only allocation of the training path)
  *   x, labels (i64 [batch]): device; batch <= 64
  *   desc: device f32 [batch][desc_dim] or NULL: the train-mode descriptor tap (after the third Dropout:
@@ -771,6 +772,49 @@ int va_vgg16_train_apply(va_vgg16* model, const void* grad, size_t grad_floats, 
                          void* norm_out, void* workspace, size_t workspace_bytes, void* stream);
 int va_vgg16_unpack_grad(va_vgg16* model, const void* grad, void* const* conv_w, void* const* conv_b, void* const* fc_w,
                          void* const* fc_b, void* stream);
+/*
+ * The solver: L2 weight decay, the ratio of the three Dropout layers and frozen layers, "as [15]" in both
+ * papers (Sheet03/notes.txt:98-111, :196-210, :234-243).  The model carries ONE solver state; va_vgg16_train_step, _consensus,
+ * _multitask, _accumulate and va_vgg16_train_apply read it.  A model whose solver was never set behaves bit for bit as one
+ * with va_solver_default's values: V = mu V + g; W -= lr V, Dropout(0.5), nothing frozen.
+ *
+ * Update of one tensor.  lr_t = lr, wd_t = weight_decay for a weight; lr_t = (float)(lr * bias_lr_mult),
+ * wd_t = (float)(weight_decay * bias_decay_mult) for a bias, both formed once on the host (a multiplier of 1 keeps the bits).
+ * With g the completed gradient element (c g under clipping, as va_vgg16_train_apply forms it):
+ *   wd_t == 0:  V = fmaf(mu, V, g);  W = fmaf(-lr_t, V, W)                       (today's two statements, a path of its own)
+ *   otherwise:  d = fmaf(wd_t, W, g);  V = fmaf(mu, V, d);  W = fmaf(-lr_t, V, W)
+ * torch.optim.SGD's order: clip the raw gradient, add the decay, then the momentum; the clip norm is the raw gradient's and
+ * the decay never enters it.  (Caffe folds lr into the momentum buffer, V = mu V + lr d; W -= V: this library keeps torch's
+ * form, the two differ when lr changes between steps.)  One stored micro-batch plus va_vgg16_train_apply is the fused step
+ * bit for bit under any solver.  The padded input channels of the packed weights are zero and stay zero.
+ *
+ * Dropout with ratio p (float32): element i of layer d is kept iff synth.hash_uniform(dropout_seed, 100 + d)[i] >= p, i.e.
+ * iff (h >> 8) >= T with T = ceil(p * 2^24), and multiplied by s = 1.0f / (1.0f - p); a dropped one by 0.  p = 0.5: T = 2^23,
+ * s = 2, today's bits; p = 0 launches nothing.  The classifier backward multiplies by each layer's own s.
+ *
+ * frozen_layers = n: layers are numbered 0..12 (conv) and 13..16 (fc); the first n keep every bit of weight, bias and both
+ * momentum buffers (no gradient, no decay, no momentum move: requires_grad = False under torch.optim.SGD).  The backward pass
+ * stops above layer n-1 and layer n forms no input gradient; n >= 13 launches no un-pool and no conv backward.  Loss, hits,
+ * descriptors and every other tensor keep the bits of the unfrozen step.  va_vgg16_train_accumulate with first != 0 writes
+ * zeros into the frozen tensors' segments of the gradient buffer and leaves them alone otherwise; va_vgg16_train_apply and
+ * its norm skip them.  n may change between steps.  A VA_OPT_TRAIN_STOP_AT layer that is frozen is never reached.
+ *
+ * va_vgg16_set_solver returns VA_ERR_INVALID, names the field in va_last_error() and
+ * changes nothing for a negative or non-finite weight_decay or multiplier, a dropout ratio outside [0, 1) or NaN,
+ * frozen_layers outside 0..16, or a bf16 model.
+ * va_train_dropout_p: va_train_dropout (testing entry points) with the ratio p of [0, 1).
+ */
+typedef struct va_solver {
+    float weight_decay;     /* L2 coefficient of the weights, torch.optim.SGD's weight_decay; default 0 */
+    float bias_lr_mult;     /* bias lr = lr * this; default 1 (Caffe's VGG and TSN solvers: 2) */
+    float bias_decay_mult;  /* bias decay = weight_decay * this; default 1 (torch); Caffe's: 0 */
+    float dropout[3];       /* ratio of the classifier's three Dropout layers; default 0.5 each */
+    int   frozen_layers;    /* 0..16: the first n of conv 0..12, fc 0..3 take no gradient and no update */
+} va_solver;
+void va_solver_default(va_solver* solver);
+int va_vgg16_set_solver(va_vgg16* model, const va_solver* solver);
+int va_vgg16_get_solver(const va_vgg16* model, va_solver* solver);
+int va_train_dropout_p(va_ctx* ctx, float* x, size_t n, unsigned long long dropout_seed, int layer, float p, void* stream);
 /*
  * Checkpoints (Sheet03/spatialModel.py:234-260, Sheet03/utils.py:29-35): copy the parameters (which = 0) or the
  * momentum buffers (which = 1) out to / in from device tensors in the reference's layouts -- conv OIHW

@@ -39,6 +39,7 @@ EXPORTS = [
     "va_color_jitter_u8",
     "va_frames_prepare_workspace_bytes", "va_frames_prepare",
     "va_flow_quantize_u8", "va_flowq_to_stack_snippets", "va_flowq_to_stack_resize",
+    "va_solver_default", "va_vgg16_set_solver", "va_vgg16_get_solver", "va_train_dropout_p",
 ]
 
 
@@ -72,6 +73,17 @@ def _tuning_property(i):
 
 for _i, _name in enumerate(TUNING_SLOTS):
     setattr(Tvl1Params, _name, _tuning_property(_i))
+
+
+class SolverParams(ctypes.Structure):
+    """Mirror of ``va_solver`` (include/va.h)."""
+    _fields_ = [
+        ("weight_decay", ctypes.c_float),
+        ("bias_lr_mult", ctypes.c_float),
+        ("bias_decay_mult", ctypes.c_float),
+        ("dropout", ctypes.c_float * 3),
+        ("frozen_layers", ctypes.c_int),
+    ]
 
 
 _lib = None
@@ -248,6 +260,14 @@ def lib():
     L.va_train_conv_backward_layer_grad.restype = ci
     L.va_train_fc_backward_layer_grad.argtypes = [vp, ci, ci, ci, vp, vp, vp, ci, vp, vp, vp, vp, cf, ctypes.c_char_p, ci, vp]
     L.va_train_fc_backward_layer_grad.restype = ci
+    L.va_solver_default.argtypes = [ctypes.POINTER(SolverParams)]
+    L.va_solver_default.restype = None
+    L.va_vgg16_set_solver.argtypes = [vp, ctypes.POINTER(SolverParams)]
+    L.va_vgg16_set_solver.restype = ci
+    L.va_vgg16_get_solver.argtypes = [vp, ctypes.POINTER(SolverParams)]
+    L.va_vgg16_get_solver.restype = ci
+    L.va_train_dropout_p.argtypes = [vp, vp, sz, ctypes.c_ulonglong, ci, cf, vp]
+    L.va_train_dropout_p.restype = ci
     _lib = L
     return L
 

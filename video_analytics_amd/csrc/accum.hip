@@ -31,12 +31,16 @@ __global__ void k_scale_dlogits(float* __restrict__ d, int rows, int C, va_heads
     d[i] = d[i] * s;
 }
 
-// The 34 segments by value: one launch walks them all.  tile0[s] = the first tile of segment s, tile0[34] = the number of tiles
+// The 34 segments by value: one launch walks them all.  tile0[s] = the first tile of segment s, tile0[34] = the number of tiles.
+// lr[s], wd[s]: the tensor's lr_t and wd_t under the model's solver.  frozen[s]: the tensor takes no update and
+// does not enter the norm -- such a segment owns NO tiles (tile0[s + 1] == tile0[s]), so no workgroup ever meets it.
 struct SegTable {
     float* w[kSegs];
     float* v[kSegs];
     unsigned long long goff[kSegs], cnt[kSegs];
     unsigned tile0[kSegs + 1];
+    float lr[kSegs], wd[kSegs];
+    unsigned char frozen[kSegs];
 };
 
 struct Seg {
@@ -44,6 +48,7 @@ struct Seg {
     float* v;
     unsigned long long goff, cnt;
     unsigned tile0;
+    float lr, wd;
 };
 
 // The table is the FIRST argument of its kernels and is read where it lies, in the kernel-argument segment (constant address
@@ -51,12 +56,13 @@ struct Seg {
 typedef const SegTable __attribute__((address_space(4))) * SegTablePtr;
 __device__ __forceinline__ SegTablePtr seg_table_arg() { return (SegTablePtr)__builtin_amdgcn_kernarg_segment_ptr(); }
 
-// the segment of a tile: the last one whose first tile is not above it (uniform over the workgroup)
+// the segment of a tile: the last one whose first tile is not above it (uniform over the workgroup); a frozen segment's
+// first tile is its successor's, so the walk passes it
 __device__ __forceinline__ Seg seg_of(SegTablePtr T, unsigned tile)
 {
     int q = 0;
     while (q + 1 < kSegs && tile >= T->tile0[q + 1]) ++q;
-    return Seg{T->w[q], T->v[q], T->goff[q], T->cnt[q], T->tile0[q]};
+    return Seg{T->w[q], T->v[q], T->goff[q], T->cnt[q], T->tile0[q], T->lr[q], T->wd[q]};
 }
 
 // Stage 1 of the norm: part[block] = the float64 sum of squares of the block's tiles (tile = block, block + grid, ...), every
@@ -111,11 +117,24 @@ __global__ void __launch_bounds__(256) k_grad_norm_finish(const double* __restri
     }
 }
 
-// V = fmaf(mu, V, c G); W = fmaf(-lr, V, W) over all segments: the two fused multiply-adds of the fused step's finishing
-// kernels.  CLIP: c = min(1, clip / (norm + 1e-6)) (torch.nn.utils.clip_grad_norm_), read from the device; without CLIP G is
-// used as it is.  A thread loads its four 16-byte pieces of G, V and W (twelve loads in flight), then stores V and W.
+// one element of the update: finish_grad's UPD_SGD statements (train.hip) on g, or on c g under clipping.  wd == 0 is a path
+// of its own (an infinite weight keeps its result); otherwise the decay joins the clipped gradient, then the momentum.
+__device__ __forceinline__ void sgd_element(float g, float v, float w, float lr, float mu, float wd, float& nv, float& nw)
+{
+    if (wd == 0.0f) {
+        nv = fmaf(mu, v, g);
+    } else {
+        nv = fmaf(mu, v, fmaf(wd, w, g));
+    }
+    nw = fmaf(-lr, nv, w);
+}
+
+// V = fmaf(mu, V, c G); W = fmaf(-lr_t, V, W) over all unfrozen segments, with wd_t != 0: V = fmaf(mu, V, fmaf(wd_t, W, c G)):
+// the fused multiply-adds of the fused step's finishing kernels, lr_t and wd_t per segment.  CLIP: c = min(1, clip / (norm +
+// 1e-6)) (torch.nn.utils.clip_grad_norm_), read from the device; without CLIP G is used as it is.  A thread loads its four
+// 16-byte pieces of G, V and W (twelve loads in flight), then stores V and W.
 template <bool CLIP>
-__global__ void __launch_bounds__(256) k_sgd_apply(SegTable T, const float* __restrict__ G, float lr, float mu, double clip,
+__global__ void __launch_bounds__(256) k_sgd_apply(SegTable T, const float* __restrict__ G, float mu, double clip,
                                                    const double* __restrict__ norm)
 {
     float c = 1.0f;
@@ -145,23 +164,26 @@ __global__ void __launch_bounds__(256) k_sgd_apply(SegTable T, const float* __re
                 f32x4 nv, nw;
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
-                    nv[i] = fmaf(mu, qv[j][i], CLIP ? c * qg[j][i] : qg[j][i]);
-                    nw[i] = fmaf(-lr, nv[i], qw[j][i]);
+                    float a, b;
+                    sgd_element(CLIP ? c * qg[j][i] : qg[j][i], qv[j][i], qw[j][i], s.lr, mu, s.wd, a, b);
+                    nv[i] = a;
+                    nw[i] = b;
                 }
                 *reinterpret_cast<f32x4*>(s.v + e) = nv;
                 *reinterpret_cast<f32x4*>(s.w + e) = nw;
             } else {
                 for (unsigned long long i = e; i < s.cnt; ++i) {  // the last one to three elements of a segment
-                    const float nv = fmaf(mu, s.v[i], CLIP ? c * g[i] : g[i]);
+                    float nv, nw;
+                    sgd_element(CLIP ? c * g[i] : g[i], s.v[i], s.w[i], s.lr, mu, s.wd, nv, nw);
                     s.v[i] = nv;
-                    s.w[i] = fmaf(-lr, nv, s.w[i]);
+                    s.w[i] = nw;
                 }
             }
         }
     }
 }
 
-SegTable seg_table(const va_vgg16* m, const va_grad_layout& GL)
+SegTable seg_table(const va_vgg16* m, const va_grad_layout& GL, float lr)
 {
     SegTable T{};
     for (int i = 0; i < 13; ++i) {
@@ -181,7 +203,10 @@ SegTable seg_table(const va_vgg16* m, const va_grad_layout& GL)
         T.goff[s] = GL.off[s];
         T.cnt[s] = GL.cnt[s];
         T.tile0[s] = t;
-        t += (unsigned)((GL.cnt[s] + kTileFloats - 1) / kTileFloats);
+        T.lr[s] = va_solver_lr(m->solver, lr, s & 1);  // odd segments are the biases
+        T.wd[s] = va_solver_wd(m->solver, s & 1);
+        T.frozen[s] = va_solver_frozen(m->solver, s / 2);
+        if (!T.frozen[s]) t += (unsigned)((GL.cnt[s] + kTileFloats - 1) / kTileFloats);
     }
     T.tile0[kSegs] = t;
     return T;
@@ -246,7 +271,7 @@ extern "C" int va_vgg16_train_apply(va_vgg16* m, const void* grad, size_t grad_f
         return VA_ERR_WORKSPACE;
     }
     hipStream_t st = (hipStream_t)stream;
-    const SegTable T = seg_table(m, GL);
+    const SegTable T = seg_table(m, GL, lr);
     const float* G = (const float*)grad;
     double* part = (double*)workspace;
     double* norm = want_norm ? part + kNormBlocks : nullptr;
@@ -255,8 +280,8 @@ extern "C" int va_vgg16_train_apply(va_vgg16* m, const void* grad, size_t grad_f
         k_grad_norm_finish<<<1, 256, 0, st>>>(part, kNormBlocks, norm, (double*)norm_out);
     }
     const unsigned blocks = T.tile0[kSegs] < (unsigned)kApplyBlocks ? T.tile0[kSegs] : (unsigned)kApplyBlocks;
-    if (clip) k_sgd_apply<true><<<blocks, 256, 0, st>>>(T, G, lr, momentum, (double)clip_norm, norm);
-    else k_sgd_apply<false><<<blocks, 256, 0, st>>>(T, G, lr, momentum, 0.0, nullptr);
+    if (clip) k_sgd_apply<true><<<blocks, 256, 0, st>>>(T, G, momentum, (double)clip_norm, norm);
+    else k_sgd_apply<false><<<blocks, 256, 0, st>>>(T, G, momentum, 0.0, nullptr);
     VA_LAUNCH_CHECK();
     return VA_OK;
 }

@@ -2,7 +2,9 @@
 // SpatialNetwork.train() / TemporalNetwork.train() (Sheet03/spatialModel.py:165-182, Sheet03/temporalModel.py:194-211):
 // forward in train mode (Dropout p = 0.5 after the three hidden classifier ReLUs), mean cross-entropy, backward
 // through the whole network, momentum-SGD update (torch.optim.SGD: buf = momentum*buf + grad; w -= lr*buf; no
-// weight decay, no Nesterov -- Sheet03/spatialModel.py:116) of every parameter.  fp32 throughout.
+// weight decay, no Nesterov -- Sheet03/spatialModel.py:116) of every parameter.  fp32 throughout.  The model's solver
+// (va_vgg16_set_solver) adds what both papers train with: L2 weight decay, the ratio of each Dropout layer
+// and frozen layers; its defaults are the step just described, bit for bit.
 //
 // Convolution backward reuses the forward implicit-GEMM kernel for the data gradient (a 3x3 convolution of the
 // output gradient with the flipped, transposed weights) and adds one MFMA kernel for the weight gradient
@@ -85,15 +87,16 @@ __device__ __forceinline__ unsigned mix32(unsigned x)
     return x;
 }
 
-// Dropout(p = 0.5) in place: element i is kept (and doubled) iff the top bit of mix(mix(i ^ key) + key2) is set,
-// i.e. iff synth.hash_uniform(seed, stream)[i] >= 0.5 (the host derives key/key2 from (seed, stream)).  A product with the
-// 0 / 2 mask, as nn.Dropout's: a dropped negative element becomes -0, a dropped NaN stays NaN (the step's inputs are >= 0).
-__global__ void k_dropout(float* __restrict__ x, size_t n, unsigned key, unsigned key2)
+// Dropout(p) in place: element i is kept (and multiplied by s = 1 / (1 - p)) iff the top 24 bits of h = mix(mix(i ^ key) + key2)
+// reach T = ceil(p * 2^24), i.e. iff synth.hash_uniform(seed, stream)[i] = (h >> 8) / 2^24 >= p (the host derives key/key2 from
+// (seed, stream), and T and s from p: dropout_layer).  p = 0.5: T = 2^23, the top bit of h, and s = 2.  A product with the
+// 0 / s mask, as nn.Dropout's: a dropped negative element becomes -0, a dropped NaN stays NaN (the step's inputs are >= 0).
+__global__ void k_dropout(float* __restrict__ x, size_t n, unsigned key, unsigned key2, unsigned T, float s)
 {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const unsigned h = mix32(mix32((unsigned)i ^ key) + key2);
-    x[i] = x[i] * ((h & 0x80000000u) ? 2.0f : 0.0f);
+    x[i] = x[i] * ((h >> 8) >= T ? s : 0.0f);
 }
 
 // logits [B][C], labels i64 -> dlogits = (softmax - onehot) / B; out[0] = mean CE, out[1] = #(argmax == label)
@@ -188,17 +191,28 @@ __global__ void k_ce_consensus_fwd_bwd(const float* __restrict__ logits, const l
 // ---------------------------------------------------------------- the finishing statement -----
 
 // What the four kernels that complete a gradient element g do with it.  UPD_SGD: the fused momentum-SGD
-// update of va_vgg16_train_step, V = mu*V + g; W -= lr*V.  UPD_STORE / UPD_ADD (va_vgg16_train_accumulate): `v` is the
-// element's place in the caller's gradient buffer, G = g or G = G + g (one rounding); `w` is not touched.
+// update of va_vgg16_train_step, V = mu*V + g; W -= lr*V, and with weight decay (wd is the tensor's wd_t,
+// uniform over the launch) V = mu*V + (wd*W + g): torch.optim.SGD's order, one more fused multiply-add on the W that is
+// read anyway.  wd == 0 is a path of its own, not fmaf(0, W, g): an infinite weight keeps its result.  UPD_STORE / UPD_ADD
+// (va_vgg16_train_accumulate): `v` is the element's place in the caller's gradient buffer, G = g or G = G + g (one
+// rounding); `w` is not touched.
 enum { UPD_SGD = 0, UPD_STORE = 1, UPD_ADD = 2 };
 
 template <int MODE>
-__device__ __forceinline__ void finish_grad(float g, size_t idx, float* __restrict__ w, float* __restrict__ v, float lr, float mu)
+__device__ __forceinline__ void finish_grad(float g, size_t idx, float* __restrict__ w, float* __restrict__ v, float lr, float mu,
+                                            float wd)
 {
     if (MODE == UPD_SGD) {
-        const float nv = fmaf(mu, v[idx], g);
-        v[idx] = nv;
-        w[idx] = fmaf(-lr, nv, w[idx]);
+        if (wd == 0.0f) {
+            const float nv = fmaf(mu, v[idx], g);
+            v[idx] = nv;
+            w[idx] = fmaf(-lr, nv, w[idx]);
+        } else {
+            const float wv = w[idx];
+            const float nv = fmaf(mu, v[idx], fmaf(wd, wv, g));
+            v[idx] = nv;
+            w[idx] = fmaf(-lr, nv, wv);
+        }
     } else if (MODE == UPD_STORE) {
         v[idx] = g;
     } else {
@@ -264,7 +278,7 @@ __global__ void __launch_bounds__(256) k_fc_dx(const float* __restrict__ dz, con
 // in registers and walks a slice of the output rows; blockIdx.y selects the slice.  MODE: finish_grad.
 template <int BMAX, int MODE>
 __global__ void __launch_bounds__(256) k_fc_wgrad_sgd(const float* __restrict__ dz, const float* __restrict__ x, float* __restrict__ w,
-                                                      float* __restrict__ v, int B, int O, int I, int orows, float lr, float mu)
+                                                      float* __restrict__ v, int B, int O, int I, int orows, float lr, float mu, float wd)
 {
     extern __shared__ __attribute__((aligned(16))) float sdz[];  // [orows][BMAX]
     const int i = blockIdx.x * 256 + threadIdx.x;
@@ -287,19 +301,20 @@ __global__ void __launch_bounds__(256) k_fc_wgrad_sgd(const float* __restrict__ 
 #pragma unroll
             for (int j = 0; j < 4; ++j) g = fmaf(d[j], xr[4 * b4 + j], g);
         }
-        finish_grad<MODE>(g, (size_t)(o0 + oo) * I + i, w, v, lr, mu);
+        finish_grad<MODE>(g, (size_t)(o0 + oo) * I + i, w, v, lr, mu, wd);
     }
 }
 
 // bias: g[o] = sum_b dZ[b][o]; momentum-SGD (MODE: finish_grad)
 template <int MODE>
-__global__ void k_fc_bgrad_sgd(const float* __restrict__ dz, float* __restrict__ bias, float* __restrict__ vb, int B, int O, float lr, float mu)
+__global__ void k_fc_bgrad_sgd(const float* __restrict__ dz, float* __restrict__ bias, float* __restrict__ vb, int B, int O, float lr, float mu,
+                               float wd)
 {
     const int o = blockIdx.x * blockDim.x + threadIdx.x;
     if (o >= O) return;
     float g = 0.0f;
     for (int b = 0; b < B; ++b) g += dz[(size_t)b * O + o];
-    finish_grad<MODE>(g, (size_t)o, bias, vb, lr, mu);
+    finish_grad<MODE>(g, (size_t)o, bias, vb, lr, mu, wd);
 }
 
 // ---------------------------------------------------------------- convolution backward ---------
@@ -442,7 +457,7 @@ __global__ void __launch_bounds__(WM * WN * 64) k_conv_wgrad(WgradArgs a)
 // for the first layer's 256 slabs, 267 us for conv1_2's.  MODE: finish_grad.
 template <int MODE>
 __global__ void __launch_bounds__(256) k_wgrad_reduce_sgd(const float* __restrict__ slab, float* __restrict__ w, float* __restrict__ v,
-                                                          int M, int N, int Mpad, int Npad, int S, float lr, float mu)
+                                                          int M, int N, int Mpad, int Npad, int S, float lr, float mu, float wd)
 {
     __shared__ float part[8][32];
     const int o = threadIdx.x & 31, grp = threadIdx.x >> 5;
@@ -475,7 +490,7 @@ __global__ void __launch_bounds__(256) k_wgrad_reduce_sgd(const float* __restric
         float g = part[0][o];
 #pragma unroll
         for (int k = 1; k < 8; ++k) g += part[k][o];
-        finish_grad<MODE>(g, idx, w, v, lr, mu);
+        finish_grad<MODE>(g, idx, w, v, lr, mu, wd);
     }
 }
 
@@ -515,7 +530,7 @@ __global__ void __launch_bounds__(256) k_conv_bgrad_partial(const float* __restr
 // pass 2 + momentum SGD (MODE: finish_grad): 64 channels per workgroup, four 64-thread groups each add a quarter of the partials
 template <int MODE>
 __global__ void __launch_bounds__(256) k_conv_bgrad_sgd(const float* __restrict__ part, int nblk, float* __restrict__ bias, float* __restrict__ vb,
-                                                        int Cout, float lr, float mu)
+                                                        int Cout, float lr, float mu, float wd)
 {
     __shared__ float red[3][64];
     const int col = threadIdx.x & 63, grp = threadIdx.x >> 6;
@@ -527,7 +542,7 @@ __global__ void __launch_bounds__(256) k_conv_bgrad_sgd(const float* __restrict_
     __syncthreads();
     if (grp != 0 || c >= Cout) return;
     g = ((g + red[0][col]) + red[1][col]) + red[2][col];
-    finish_grad<MODE>(g, (size_t)c, bias, vb, lr, mu);
+    finish_grad<MODE>(g, (size_t)c, bias, vb, lr, mu, wd);
 }
 
 // ---------------------------------------------------------------- export / import --------------
@@ -689,11 +704,27 @@ void pool_backward(const float* dp, const float* y, const float* p, float* dy, i
     k_unpool<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(dp, y, p, dy, B, hw, C);
 }
 
-void dropout_layer(float* x, size_t n, unsigned long long seed, int layer, hipStream_t st)
+// s = 1 / (1 - p) in float32, the factor of a kept element (p in [0, 1): 1 - p is exact for p >= 0.5 and never 0)
+float dropout_scale(float p) { return 1.0f / (1.0f - p); }
+
+// Dropout with ratio p in [0, 1): T = ceil(p * 2^24) (p * 2^24 is exact in double), kept iff (h >> 8) >= T.  p = 0: no launch.
+void dropout_layer(float* x, size_t n, unsigned long long seed, int layer, float p, hipStream_t st)
 {
+    if (p == 0.0f) return;
     unsigned key, key2;
     keys_for(seed, 100u + (unsigned)layer, key, key2);
-    k_dropout<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(x, n, key, key2);
+    const unsigned T = (unsigned)ceil((double)p * 16777216.0);
+    k_dropout<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(x, n, key, key2, T, dropout_scale(p));
+}
+
+// lr_t and wd_t of a layer's two tensors (include/va.h, "Update of one tensor") and the momentum
+struct Upd {
+    float lr, lr_b, mu, wd, wd_b;
+};
+Upd plain_update(float lr, float mu) { return Upd{lr, lr, mu, 0.0f, 0.0f}; }
+Upd solver_update(const va_solver& s, float lr, float mu)
+{
+    return Upd{va_solver_lr(s, lr, false), va_solver_lr(s, lr, true), mu, va_solver_wd(s, false), va_solver_wd(s, true)};
 }
 
 // The heads of the multi-task form of the loss: tasks i32 [videos] on the device
@@ -713,24 +744,25 @@ int loss_layer(const float* logits, const long long* labels, int B, int segments
     return VA_OK;
 }
 
-// dx (with mask and scale), then the weight and bias updates in place; *inst (may be NULL): the batch instantiation, 32 or 64.
+// dx (with mask and scale; dx == NULL: the layer below is frozen, no input gradient), then the weight and bias updates in
+// place; *inst (may be NULL): the batch instantiation, 32 or 64.
 // mode UPD_STORE / UPD_ADD: vw / vb are the layer's places in the gradient buffer, w is only read (dx), bias not at all.
 int fc_backward_layer(int B, int O, int I, const float* dz, const float* x, float* w, float* bias, float* vw, float* vb, float* dx,
-                      const float* mask, float scale, float lr, float mu, hipStream_t st, int* inst, int mode = UPD_SGD)
+                      const float* mask, float scale, const Upd& u, hipStream_t st, int* inst, int mode = UPD_SGD)
 {
     return update_dispatch(mode, [&](auto MD) {
         constexpr int md = decltype(MD)::value;
         int rc = fc_backward_dispatch(B, [&](auto BM) {
             constexpr int bm = decltype(BM)::value;
             if (inst) *inst = bm;
-            k_fc_dx<bm><<<va_cdiv(I, 64), 256, 0, st>>>(dz, w, dx, B, O, I, mask, scale);
+            if (dx) k_fc_dx<bm><<<va_cdiv(I, 64), 256, 0, st>>>(dz, w, dx, B, O, I, mask, scale);
             const int orows = 16;
             k_fc_wgrad_sgd<bm, md><<<dim3(va_cdiv(I, 256), va_cdiv(O, orows)), 256, (size_t)orows * bm * sizeof(float), st>>>(
-                dz, x, w, vw, B, O, I, orows, lr, mu);
+                dz, x, w, vw, B, O, I, orows, u.lr, u.mu, u.wd);
             return VA_OK;
         });
         if (rc) return rc;
-        k_fc_bgrad_sgd<md><<<va_cdiv(O, 256), 256, 0, st>>>(dz, bias, vb, B, O, lr, mu);
+        k_fc_bgrad_sgd<md><<<va_cdiv(O, 256), 256, 0, st>>>(dz, bias, vb, B, O, u.lr_b, u.mu, u.wd_b);
         return VA_OK;
     });
 }
@@ -745,7 +777,7 @@ int bgrad_blocks(long P) { return (int)((P + bgrad_chunk(P) - 1) / bgrad_chunk(P
 // the layer's places in the gradient buffer, w is only read (dx), bias not at all.
 int conv_backward_layer(int B, int hw, int cin, int cin_pad, int cout, const float* dy, const float* x, float* w, float* bias, float* vw,
                         float* vb, float* dx, const float* mask, const float* zeros, int f32_conv, float* wt, float* slab, float* bpart,
-                        float lr, float mu, hipStream_t st, const char** dgrad_launched = nullptr, int mode = UPD_SGD)
+                        const Upd& u, hipStream_t st, const char** dgrad_launched = nullptr, int mode = UPD_SGD)
 {
     if (dx) {
         const size_t nwt = (size_t)cin * 9 * cout;
@@ -772,9 +804,9 @@ int conv_backward_layer(int B, int hw, int cin, int cin_pad, int cout, const flo
     const int nblk = bgrad_blocks(a.P);
     return update_dispatch(mode, [&](auto MD) {
         constexpr int md = decltype(MD)::value;
-        k_wgrad_reduce_sgd<md><<<(unsigned)((nw + 31) / 32), 256, 0, st>>>(slab, w, vw, cout, a.N, wp.Mpad, wp.Npad, wp.S, lr, mu);
+        k_wgrad_reduce_sgd<md><<<(unsigned)((nw + 31) / 32), 256, 0, st>>>(slab, w, vw, cout, a.N, wp.Mpad, wp.Npad, wp.S, u.lr, u.mu, u.wd);
         k_conv_bgrad_partial<<<nblk, 256, 0, st>>>(dy, bpart, a.P, cout, bgrad_chunk(a.P));
-        k_conv_bgrad_sgd<md><<<va_cdiv(cout, 64), 256, 0, st>>>(bpart, nblk, bias, vb, cout, lr, mu);
+        k_conv_bgrad_sgd<md><<<va_cdiv(cout, 64), 256, 0, st>>>(bpart, nblk, bias, vb, cout, u.lr_b, u.mu, u.wd_b);
         VA_LAUNCH_CHECK();
         return VA_OK;
     });
@@ -845,13 +877,17 @@ static int train_step(const char* who, va_vgg16* m, const void* x, int x_is_u8, 
     hipStream_t st = (hipStream_t)stream;
     const int B = batch;
     const int mode = !acc ? UPD_SGD : acc->first ? UPD_STORE : UPD_ADD;
+    const va_solver& sv = m->solver;
+    const int nf = sv.frozen_layers;  // layers 0 .. nf-1 (conv 0..12, fc 13..16) take no gradient and no update
+    const Upd upd = solver_update(sv, lr, momentum);
     va_grad_layout GL{};
     if (acc) {
         GL = va_grad_layout_of(m);
-        if (acc->first)  // the gaps between the segments hold zeros: a sum across ranks or a norm over the whole buffer sees nothing
-            for (int s = 0; s < 34; ++s) {
-                const size_t end = s < 33 ? GL.off[s + 1] : GL.total, gap = end - (GL.off[s] + GL.cnt[s]);
-                if (gap) VA_HIP(hipMemsetAsync(acc->grad + GL.off[s] + GL.cnt[s], 0, gap * sizeof(float), st));
+        if (acc->first)  // the gaps between the segments hold zeros: a sum across ranks or a norm over the whole buffer sees nothing;
+            for (int s = 0; s < 34; ++s) {  // so do the segments of frozen tensors, which the backward pass never writes
+                const size_t end = s < 33 ? GL.off[s + 1] : GL.total;
+                const size_t from = GL.off[s] + (va_solver_frozen(sv, s / 2) ? 0 : GL.cnt[s]);
+                if (end > from) VA_HIP(hipMemsetAsync(acc->grad + from, 0, (end - from) * sizeof(float), st));
             }
     }
     char* ws = (char*)workspace;
@@ -876,7 +912,7 @@ static int train_step(const char* who, va_vgg16* m, const void* x, int x_is_u8, 
     float* fout[4] = {F(T.a_d[0]), F(T.a_d[1]), F(T.a_d[2]), F(T.logits)};
     for (int l = 0; l < 4; ++l) {
         if (int rc = va_fc_f32(fin[l], m->fcw[l], m->fcb[l], fout[l], slab, B, m->fc_out[l], m->fc_in[l], l < 3, st)) return rc;
-        if (l < 3) dropout_layer(fout[l], (size_t)B * m->fc_out[l], dropout_seed, l, st);
+        if (l < 3) dropout_layer(fout[l], (size_t)B * m->fc_out[l], dropout_seed, l, sv.dropout[l], st);
     }
     if (desc) VA_HIP(hipMemcpyAsync(desc, F(T.a_d[2]), (size_t)B * m->desc_dim * sizeof(float), hipMemcpyDeviceToDevice, st));
     if (int rc = loss_layer(F(T.logits), (const long long*)labels, B, segments, m->n_classes, F(T.dlogits), (float*)loss_out, st, mt)) return rc;
@@ -889,16 +925,19 @@ static int train_step(const char* who, va_vgg16* m, const void* x, int x_is_u8, 
     VA_LAUNCH_CHECK();
 
     // ---------------- classifier backward + update ----------------
-    // dz_l = gradient at FC l's pre-activation; for l < 3 it arrives through Dropout and ReLU: x2 where the
-    // (post-dropout) activation is positive, 0 elsewhere -- applied by the k_fc_dx that produced it.
+    // dz_l = gradient at FC l's pre-activation; for l < 3 it arrives through Dropout and ReLU: times the Dropout layer's own
+    // s = 1 / (1 - p) where the (post-dropout) activation is positive, 0 elsewhere -- applied by the k_fc_dx that produced it.
+    // The loops stop above the last frozen layer, and the first unfrozen one forms no input gradient.
     const float* dz[4] = {F(T.dd[0]), F(T.dd[1]), F(T.dd[2]), F(T.dlogits)};
     float* dxo[4] = {F(T.da0), F(T.dd[0]), F(T.dd[1]), F(T.dd[2])};
-    for (int l = 3; l >= 0; --l) {
+    for (int l = 3; l >= 0 && 13 + l >= nf; --l) {
         const int O = m->fc_out[l], I = m->fc_in[l];
         const float* mask = l > 0 ? fin[l] : nullptr;  // fin[l] = post-dropout activation of layer l-1
+        const float scale = l > 0 ? dropout_scale(sv.dropout[l - 1]) : 1.0f;
         float* vw = acc ? acc->grad + GL.off[26 + 2 * l] : m->fc_mom_w[l];
         float* vb = acc ? acc->grad + GL.off[27 + 2 * l] : m->fc_mom_b[l];
-        if (int rc = fc_backward_layer(B, O, I, dz[l], fin[l], m->fcw[l], m->fcb[l], vw, vb, dxo[l], mask, 2.0f, lr, momentum, st, nullptr, mode))
+        if (int rc = fc_backward_layer(B, O, I, dz[l], fin[l], m->fcw[l], m->fcb[l], vw, vb, 13 + l > nf ? dxo[l] : nullptr, mask, scale, upd, st,
+                                       nullptr, mode))
             return rc;
     }
     VA_LAUNCH_CHECK();
@@ -907,7 +946,7 @@ static int train_step(const char* who, va_vgg16* m, const void* x, int x_is_u8, 
     const int stop_at = m->train_stop_at;  // VA_OPT_TRAIN_STOP_AT (tests): -1 = the whole step
     const float* dout = F(T.da0);  // gradient at layer 12's pooled output
     int cur = -1;                  // which of the two gradient buffers holds `dout` (-1: neither)
-    for (int i = 12; i >= 0; --i) {
+    for (int i = 12; i >= nf; --i) {
         ConvLayer& L = m->conv[i];
         const float* lin = i == 0 ? F(T.x0) : (m->conv[i - 1].pool ? F(T.p[i - 1]) : F(T.y[i - 1]));
         const float* dyr = dout;
@@ -917,16 +956,16 @@ static int train_step(const char* who, va_vgg16* m, const void* x, int x_is_u8, 
             dyr = F(T.g[dst]);
             cur = dst;
         }
-        // data gradient (not for the first layer) into the other gradient buffer, then the weight and bias updates
-        float* g = i > 0 ? F(T.g[1 - cur]) : nullptr;
-        const float* mask = i > 0 && !m->conv[i - 1].pool ? F(T.y[i - 1]) : nullptr;
+        // data gradient (not for the first unfrozen layer) into the other gradient buffer, then the weight and bias updates
+        float* g = i > nf ? F(T.g[1 - cur]) : nullptr;
+        const float* mask = i > nf && !m->conv[i - 1].pool ? F(T.y[i - 1]) : nullptr;
         float* vw = acc ? acc->grad + GL.off[2 * i] : L.mom_w;
         float* vb = acc ? acc->grad + GL.off[2 * i + 1] : L.mom_b;
         if (int rc = conv_backward_layer(B, L.hw, L.cin, L.cin_pad, L.cout, dyr, lin, L.wp, L.bias, vw, vb, g, mask, m->zeros_f32, m->f32_conv,
-                                         F(T.wt), slab, F(T.bpart), lr, momentum, st, nullptr, mode))
+                                         F(T.wt), slab, F(T.bpart), upd, st, nullptr, mode))
             return rc;
-        if (i > 0) dout = g;
-        if (i > 0) cur = 1 - cur;
+        if (g) dout = g;
+        if (g) cur = 1 - cur;
         if (stop_at == i) {  // debugging aid of the tests: leave the gradient buffers as layer i left them; NOT a completed step
             va_set_error("%s: stopped after the backward pass of conv layer %d (VA_OPT_TRAIN_STOP_AT); layers below were not updated", who, i);
             return VA_ERR_STOPPED;
@@ -1161,7 +1200,7 @@ static int conv_backward_entry(const char* who, int mode, va_ctx* ctx, int kerne
     }
     const char* dname = nullptr;
     if (int rc = conv_backward_layer(batch, hw, cin, cin_pad, cout, dy, x, w_packed, bias, mom_w, mom_b, dx, mask, zeros, kernel_opt, wt, slab,
-                                     bpart, lr, momentum, (hipStream_t)stream, &dname, mode))
+                                     bpart, plain_update(lr, momentum), (hipStream_t)stream, &dname, mode))
         return rc;
     if (info && info_len > 0) snprintf(info, (size_t)info_len, "%s dgrad=%s", plan, dname ? dname : "none");
     return VA_OK;
@@ -1199,7 +1238,7 @@ static int fc_backward_entry(const char* who, int mode, va_ctx* ctx, int batch, 
     VA_CHECK_ARG(dz && x && w && bias && mom_w && mom_b && dx, "%s: NULL argument", who);
     VA_CHECK_ARG(VA_ALIGNED16(dz, x, w, bias, mom_w, mom_b, dx, mask), "%s: every pointer must be 16-byte aligned", who);
     int inst = 0;
-    if (int rc = fc_backward_layer(batch, out_f, in_f, dz, x, w, bias, mom_w, mom_b, dx, mask, scale, lr, momentum, (hipStream_t)stream, &inst, mode))
+    if (int rc = fc_backward_layer(batch, out_f, in_f, dz, x, w, bias, mom_w, mom_b, dx, mask, scale, plain_update(lr, momentum), (hipStream_t)stream, &inst, mode))
         return rc;
     VA_LAUNCH_CHECK();
     if (info && info_len > 0) snprintf(info, (size_t)info_len, "k_fc_dx<%d>", inst);
@@ -1276,7 +1315,55 @@ extern "C" int va_train_dropout(va_ctx* ctx, float* x, size_t n, unsigned long l
     VA_USE_DEVICE(ctx);
     VA_CHECK_ARG(x != nullptr && n >= 1 && n <= (size_t)1 << 31, "%s: NULL x or n out of range [1, 2^31]", who);
     VA_CHECK_ARG(layer >= 0 && layer <= 2, "%s: layer %d out of range [0,2]", who, layer);
-    dropout_layer(x, n, dropout_seed, layer, (hipStream_t)stream);
+    dropout_layer(x, n, dropout_seed, layer, 0.5f, (hipStream_t)stream);
     VA_LAUNCH_CHECK();
+    return VA_OK;
+}
+
+extern "C" int va_train_dropout_p(va_ctx* ctx, float* x, size_t n, unsigned long long dropout_seed, int layer, float p, void* stream)
+{
+    const char* who = "va_train_dropout_p";
+    VA_CHECK_ARG(ctx != nullptr, "%s: ctx is NULL", who);
+    VA_USE_DEVICE(ctx);
+    VA_CHECK_ARG(x != nullptr && n >= 1 && n <= (size_t)1 << 31, "%s: NULL x or n out of range [1, 2^31]", who);
+    VA_CHECK_ARG(layer >= 0 && layer <= 2, "%s: layer %d out of range [0,2]", who, layer);
+    VA_CHECK_ARG(p >= 0.0f && p < 1.0f, "%s: p %g outside [0, 1)", who, (double)p);
+    dropout_layer(x, n, dropout_seed, layer, p, (hipStream_t)stream);
+    VA_LAUNCH_CHECK();
+    return VA_OK;
+}
+
+// ---------------------------------------------------------------- the solver ---
+
+extern "C" void va_solver_default(va_solver* s)
+{
+    if (!s) return;
+    s->weight_decay = 0.0f;
+    s->bias_lr_mult = 1.0f;
+    s->bias_decay_mult = 1.0f;
+    for (int i = 0; i < 3; ++i) s->dropout[i] = 0.5f;
+    s->frozen_layers = 0;
+}
+
+extern "C" int va_vgg16_set_solver(va_vgg16* m, const va_solver* s)
+{
+    const char* who = "va_vgg16_set_solver";
+    VA_CHECK_ARG(m != nullptr && s != nullptr, "%s: NULL argument", who);
+    VA_CHECK_ARG(m->dtype == VA_DTYPE_F32, "%s: training is fp32 only (bf16 model)", who);
+    auto ok = [](float v) { return v - v == 0.0f && v >= 0.0f; };  // finite and not negative
+    VA_CHECK_ARG(ok(s->weight_decay), "%s: weight_decay %g must be finite and >= 0", who, (double)s->weight_decay);
+    VA_CHECK_ARG(ok(s->bias_lr_mult), "%s: bias_lr_mult %g must be finite and >= 0", who, (double)s->bias_lr_mult);
+    VA_CHECK_ARG(ok(s->bias_decay_mult), "%s: bias_decay_mult %g must be finite and >= 0", who, (double)s->bias_decay_mult);
+    for (int i = 0; i < 3; ++i)
+        VA_CHECK_ARG(s->dropout[i] >= 0.0f && s->dropout[i] < 1.0f, "%s: dropout[%d] %g outside [0, 1)", who, i, (double)s->dropout[i]);
+    VA_CHECK_ARG(s->frozen_layers >= 0 && s->frozen_layers <= 16, "%s: frozen_layers %d outside 0..16", who, s->frozen_layers);
+    m->solver = *s;
+    return VA_OK;
+}
+
+extern "C" int va_vgg16_get_solver(const va_vgg16* m, va_solver* s)
+{
+    VA_CHECK_ARG(m != nullptr && s != nullptr, "va_vgg16_get_solver: NULL argument");
+    *s = m->solver;
     return VA_OK;
 }

@@ -2355,6 +2355,7 @@ extern "C" int va_vgg16_create(va_ctx* ctx, int c_in, int n_classes, int desc_di
     m->bf16_first = 1;
     m->f32_conv = VA_F32_CONV_DEFAULT;
     m->train_stop_at = -1;
+    va_solver_default(&m->solver);
     if (dtype == VA_DTYPE_BF16) {
         if (hipMalloc(&m->zeros, 256) != hipSuccess || hipMemsetAsync(m->zeros, 0, 256, st) != hipSuccess) {
             va_set_error("va_vgg16_create: hipMalloc failed for the zero line");

@@ -34,7 +34,15 @@ struct va_vgg16 {
     int bf16_variant;   // VA_OPT_BF16_VARIANT: 0 = automatic tile/staging choice, 1 = 64-channel tiles + single buffer, 2 = DMA ring everywhere
     int f32_conv;       // VA_OPT_F32_CONV_KERNEL: 1 = LDS-DMA kernel where Cin % 32 == 0 (default), 0 = register-staged kernel
     int train_stop_at;  // VA_OPT_TRAIN_STOP_AT: -1 = full step; i = va_vgg16_train_step returns VA_ERR_STOPPED after conv layer i's backward
+    va_solver solver;   // va_vgg16_set_solver; va_vgg16_create stores va_solver_default's values
 };
+
+// lr_t and wd_t of a tensor under the model's solver (include/va.h, "Update of one tensor"): formed once on the host, a
+// multiplier of 1 keeps lr's and weight_decay's own bits
+inline float va_solver_lr(const va_solver& s, float lr, bool bias) { return bias ? lr * s.bias_lr_mult : lr; }
+inline float va_solver_wd(const va_solver& s, bool bias) { return bias ? s.weight_decay * s.bias_decay_mult : s.weight_decay; }
+// layer 0..12 = conv, 13..16 = fc
+inline bool va_solver_frozen(const va_solver& s, int layer) { return layer < s.frozen_layers; }
 
 
 // fp32 3x3 convolution (implicit GEMM on MFMA) of an NHWC tensor with explicit packed weights [cout][9*cin_pad]:

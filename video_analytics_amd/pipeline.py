@@ -790,6 +790,19 @@ class TwoStreamPipeline(object):
             augment.check_lighting(lighting, n_snippets, who)
         return jitter
 
+    def _check_solver(self, solver):
+        """``solver=`` of ``train_videos`` -> [(stream, Solver), ...] to set, in the order spatial, temporal, difference."""
+        who = "train_videos"
+        streams = [self.spatial, self.temporal] + ([self.diff] if self.diff is not None else [])
+        if solver is None:
+            return []
+        if isinstance(solver, vgg.Solver):
+            return [(m, solver) for m in streams]
+        if not isinstance(solver, (tuple, list)) or len(solver) != len(streams) or not all(isinstance(s, vgg.Solver) for s in solver):
+            raise ValueError("%s: solver must be None, a vgg.Solver or %d of them (spatial, temporal%s), got %r"
+                             % (who, len(streams), ", difference" if len(streams) == 3 else "", solver))
+        return list(zip(streams, solver))
+
     def _accumulate_step(self, n, k, micro, labels, tasks, lr, momentum, dropout_seed, clip_norm, data_parallel):
         """-> step(model, x) of ``train_videos`` in its accumulate form: the micro-batches of x ``[n*k,C,224,224]`` through
         ``train_accumulate``, the all-reduce of a data-parallel step, ``train_apply`` -> (stats, descriptors); ``step.norms``
@@ -825,7 +838,7 @@ class TwoStreamPipeline(object):
 
     def train_videos(self, videos, labels, k=video.N_SEGMENTS, starts=None, crops=None, lr=1e-3, momentum=0.9, dropout_seed=0,
                      invert_flow_x=False, rng=None, tasks=None, micro_videos=None, clip_norm=None, data_parallel=False,
-                     color_jitter=None, jitter=None, lighting=None, rescale=None, flows=None):
+                     color_jitter=None, jitter=None, lighting=None, rescale=None, flows=None, solver=None):
         """One TSN training step of both streams on whole videos (Sheet03/notes.txt:165-185, 212-223).
         ``videos``: a list of n ``(rgb u8 [T,3,H,W], gray [T,H,W])`` pairs on the device, one frame size, any lengths;
         ``labels``: their n class indices; ``n*k <= 64``.
@@ -891,12 +904,20 @@ class TwoStreamPipeline(object):
         above and the step keeps the bits of the live one (``motion="trajectory"`` included; a bi-directional pipeline raises
         ValueError).  With uint8 the temporal input comes from ``flow.resize_flowq_to_stack``: TSN's order, the 8-bit image is
         resampled; equal to the live step for ``ch = cw = 224`` crops, not for resampling ones; it needs ``motion="stack"`` and
-        ``mean_flow=False``.  The result's ``flow`` holds the planned fields in the stored type."""
+        ``mean_flow=False``.  The result's ``flow`` holds the planned fields in the stored type.
+
+        The solver: ``solver=`` is one ``vgg.Solver`` for every stream, or one per stream in the order
+        spatial, temporal, difference (TSN's dropout ratios differ per stream); each stream keeps it for later steps too
+        (``Vgg16Stream.set_solver``).  None leaves the streams as they are.  Anything else raises ValueError before
+        anything is enqueued."""
         videos = list(videos)
+        solvers = self._check_solver(solver)
         micro = self._check_accumulate(len(videos), int(k), micro_videos, clip_norm, data_parallel)
         videos, labels, plans, crops, tasks, sizes, flows = self._check_train_videos(videos, labels, k, starts, crops, rng, tasks,
                                                                                       micro, rescale, flows)
         jitter = self._check_jitter(len(videos) * int(k), color_jitter, jitter, lighting, rng)
+        for m, sv in solvers:  # host state of each stream: nothing is enqueued
+            m.set_solver(sv)
         if flows is None:
             videos = [v if v[1] is not None else vframes.prepare_frames(v[0], size) for v, size in zip(videos, sizes)]  # S38
         else:  # the gray frames only fed TV-L1: the frames are rescaled (S38) or used as they are

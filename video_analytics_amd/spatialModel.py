@@ -74,11 +74,14 @@ class SpatialNetwork(object):
     C_IN = 3
 
     def __init__(self, nActionClasses, nEpochs, lr, momentumVal, descriptorDim, trainLoader, testLoader, lrMilestones,
-                 ckpLoc, gpu=False, weights=None, seed=1):
+                 ckpLoc, gpu=False, weights=None, seed=1, solver=None):
         """Same positional arguments as the reference.  ``weights``: dict(conv_w, conv_b, fc_w, fc_b) of
         float32 tensors (OIHW / [out,in]); None = deterministic random init of the same architecture
-        (the reference's ImageNet download, ``models.vgg16(pretrained=True)``, is impossible offline)."""
+        (the reference's ImageNet download, ``models.vgg16(pretrained=True)``, is impossible offline).
+        ``solver``: a ``vgg.Solver`` (weight decay, dropout ratios, frozen layers) for every training
+        step of this network, or None: the reference's plain momentum SGD with Dropout(0.5)."""
         super(SpatialNetwork, self).__init__()
+        self.solver = vgg.check_solver(solver, type(self).__name__)
         self.nActionClasses = nActionClasses
         self.nEpochs = nEpochs
         self.lr = lr
@@ -98,6 +101,8 @@ class SpatialNetwork(object):
             weights = synth.synth_vgg16_weights(c_in=self.C_IN, n_classes=nActionClasses, desc_dim=descriptorDim,
                                                 seed=seed, device=self.device)
         self.model = self._build(weights)
+        if self.solver is not None:
+            self.model.set_solver(self.solver)
         self.startEpoch = 0
         self.epoch = 0
         self.highestPrecision = 0.0
@@ -176,13 +181,17 @@ class SpatialNetwork(object):
         print("Epoch %d completed in %f seconds" % (self.epoch, time.time() - startTime))
         self.save()
 
+    def optimizerWeightDecay(self):
+        """``weight_decay`` of the checkpoint's param group: the solver's, or the reference's literal 0 without one."""
+        return 0 if self.solver is None else self.solver.weight_decay
+
     def state(self):
         """What the reference checkpoints (Sheet03/spatialModel.py:256-261): epoch, model.state_dict() (``module.``
         keys), highestPrecision, optimizer.state_dict() (momentum buffers in parameter order + the param group)."""
         params = self.model.export_state()
         names = list(vgg.state_dict_from_weights(params).keys())
         opt = {"state": {}, "param_groups": [{"lr": self.currentLr(), "initial_lr": self.lr, "momentum": self.momentumVal,
-                                              "dampening": 0, "weight_decay": 0, "nesterov": False,
+                                              "dampening": 0, "weight_decay": self.optimizerWeightDecay(), "nesterov": False,
                                               "params": list(range(len(names)))}]}
         if getattr(self.model, "_train_ready", False):
             mom = list(vgg.state_dict_from_weights(self.model.export_state(momentum=True)).values())

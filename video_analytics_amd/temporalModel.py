@@ -101,7 +101,7 @@ class TemporalNetwork(SpatialNetwork):
     """Wrapper of the motion stream (Sheet03/temporalModel.py:96-312)."""
 
     def __init__(self, nActionClasses, flowSampleSize, nEpochs, lr, momentumVal, descriptorDim, trainLoader, testLoader,
-                 lrMilestones, ckpLoc, gpu=False, weights=None, seed=2):
+                 lrMilestones, ckpLoc, gpu=False, weights=None, seed=2, solver=None):
         self.flowSampleSize = flowSampleSize
         self.C_IN = 2 * flowSampleSize
         if weights is None and torch.cuda.is_available():
@@ -110,7 +110,8 @@ class TemporalNetwork(SpatialNetwork):
                                                 seed=seed, device=dev)
             weights["conv_w"][0] = self.__copyFirstLayer__(weights["conv_w"][0].to(dev))
         super(TemporalNetwork, self).__init__(nActionClasses, nEpochs, lr, momentumVal, descriptorDim, trainLoader,
-                                              testLoader, lrMilestones, ckpLoc, gpu=gpu, weights=weights, seed=seed)
+                                              testLoader, lrMilestones, ckpLoc, gpu=gpu, weights=weights, seed=seed,
+                                              solver=solver)
 
     def __copyFirstLayer__(self, w_rgb):
         """Sheet03/temporalModel.py:149-162: RGB-mean kernel replicated over the 2L input channels

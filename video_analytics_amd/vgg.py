@@ -251,6 +251,22 @@ class Vgg16Stream(object):
         _ffi.check(_ffi.lib().va_vgg16_train_init(self._h, _ffi.stream_ptr(self.device)))
         self._train_ready = True
 
+    def set_solver(self, solver):
+        """``va_vgg16_set_solver``: weight decay, bias multipliers, the three dropout ratios and the frozen
+        layers that every form of the step and ``train_apply`` read from now on.  A stream whose solver was never set
+        behaves as with ``Solver()``.  ValueError (nothing changes) for anything but a ``Solver``, and on a bf16 model."""
+        if not isinstance(solver, Solver):
+            raise ValueError("Vgg16Stream.set_solver: need a vgg.Solver, got %r" % (solver,))
+        s = solver.to_struct()
+        _ffi.check(_ffi.lib().va_vgg16_set_solver(self._h, ctypes.byref(s)))
+
+    @property
+    def solver(self):
+        """The stream's solver state (``va_vgg16_get_solver``) as a ``Solver``."""
+        s = _ffi.SolverParams()
+        _ffi.check(_ffi.lib().va_vgg16_get_solver(self._h, ctypes.byref(s)))
+        return Solver.from_struct(s)
+
     def train_step(self, x, labels, lr, momentum, dropout_seed):
         """One iteration of the batch loop of ``train()`` (Sheet03/spatialModel.py:165-182): forward in train
         mode, mean cross-entropy, backward, SGD update.  Returns (stats, descriptors): ``stats`` is a CUDA
@@ -810,10 +826,119 @@ def train_loss_multitask(logits, labels, tasks, heads, dlogits, out, k=0):
                                                   _ffi.stream_ptr(logits.device)))
 
 
-def train_dropout(x, seed, layer):
-    """``va_train_dropout``: the step's Dropout(0.5) of classifier layer ``layer`` (0..2) in place on float32 x."""
+def train_dropout(x, seed, layer, p=0.5):
+    """``va_train_dropout`` / ``va_train_dropout_p``: the step's Dropout(p) of classifier layer ``layer`` (0..2) in place on
+    float32 x.  The default ratio goes through the entry point that has no ratio argument; both give the same bits."""
     _f32_cuda("train_dropout", x, x=x)
-    _ffi.check(_ffi.lib().va_train_dropout(_ffi.ctx(x.device.index), _ffi.ptr(x), x.numel(), int(seed), int(layer), _ffi.stream_ptr(x.device)))
+    if p == 0.5:
+        _ffi.check(_ffi.lib().va_train_dropout(_ffi.ctx(x.device.index), _ffi.ptr(x), x.numel(), int(seed), int(layer), _ffi.stream_ptr(x.device)))
+        return
+    p = _solver_ratio("train_dropout", "p", p)
+    _ffi.check(_ffi.lib().va_train_dropout_p(_ffi.ctx(x.device.index), _ffi.ptr(x), x.numel(), int(seed), int(layer), p,
+                                             _ffi.stream_ptr(x.device)))
+
+
+# ---- the solver, host side (DESIGN.md S42-S44): no device is touched here ----
+
+def _f32(v):
+    """The float32 nearest to v, as a Python float (what crosses the C ABI)."""
+    return ctypes.c_float(v).value
+
+
+def _solver_number(who, name, v):
+    import math
+    import numbers
+    if isinstance(v, bool) or not isinstance(v, numbers.Real):
+        raise ValueError("%s: %s must be a number, got %r" % (who, name, v))
+    f = _f32(float(v)) if math.isfinite(v) else float(v)
+    if not math.isfinite(f) or f < 0.0:
+        raise ValueError("%s: %s must be finite (as a float32) and >= 0, got %r" % (who, name, v))
+    return f
+
+
+def _solver_ratio(who, name, v):
+    import math
+    import numbers
+    if isinstance(v, bool) or not isinstance(v, numbers.Real) or math.isnan(v):
+        raise ValueError("%s: %s must be a number in [0, 1), got %r" % (who, name, v))
+    f = _f32(float(v)) if math.isfinite(v) else float(v)
+    if not 0.0 <= f < 1.0:
+        raise ValueError("%s: %s must lie in [0, 1) as a float32, got %r" % (who, name, v))
+    return f
+
+
+def dropout_threshold(p):
+    """T of Dropout(p): an element is kept iff the top 24 bits of its hash reach ``T = ceil(float32(p) * 2**24)``, that is
+    iff ``synth.hash_uniform(...) >= float32(p)``."""
+    import math
+    return int(math.ceil(_solver_ratio("dropout_threshold", "p", p) * 16777216.0))
+
+
+def dropout_scale(p):
+    """s of Dropout(p): ``float32(1) / (float32(1) - float32(p))``, the factor of a kept element."""
+    p = _solver_ratio("dropout_scale", "p", p)
+    return _f32(1.0 / _f32(1.0 - p))
+
+
+class Solver(object):
+    """The solver state of a ``Vgg16Stream`` (``va_solver``): ``weight_decay`` (torch.optim.SGD's L2
+    coefficient), ``bias_lr_mult`` / ``bias_decay_mult`` (a bias uses ``lr * bias_lr_mult`` and ``weight_decay *
+    bias_decay_mult``; Caffe's VGG and TSN solvers: 2 and 0), ``dropout``: the ratio of the classifier's three Dropout layers,
+    one number or three, each in [0, 1), and ``freeze``: the first n of the 17 layers (conv 0..12, fc 0..3) take no gradient
+    and no update, n in 0..16.  Checked here (ValueError); every number is held as the float32 the library receives."""
+
+    def __init__(self, weight_decay=0.0, bias_lr_mult=1.0, bias_decay_mult=1.0, dropout=0.5, freeze=0):
+        import numbers
+        who = "Solver"
+        self.weight_decay = _solver_number(who, "weight_decay", weight_decay)
+        self.bias_lr_mult = _solver_number(who, "bias_lr_mult", bias_lr_mult)
+        self.bias_decay_mult = _solver_number(who, "bias_decay_mult", bias_decay_mult)
+        if isinstance(dropout, numbers.Real) and not isinstance(dropout, bool):
+            dropout = (dropout,) * 3
+        try:
+            dropout = tuple(dropout)
+        except TypeError:
+            raise ValueError("%s: dropout must be a number or three numbers, got %r" % (who, dropout))
+        if len(dropout) != 3:
+            raise ValueError("%s: dropout must be a number or three numbers, got %r" % (who, dropout))
+        self.dropout = tuple(_solver_ratio(who, "dropout[%d]" % i, v) for i, v in enumerate(dropout))
+        if isinstance(freeze, bool) or not isinstance(freeze, numbers.Integral) or not 0 <= freeze <= 16:
+            raise ValueError("%s: freeze must be an integer in 0..16, got %r" % (who, freeze))
+        self.freeze = int(freeze)
+
+    def _key(self):
+        return (self.weight_decay, self.bias_lr_mult, self.bias_decay_mult, self.dropout, self.freeze)
+
+    def __eq__(self, other):
+        return isinstance(other, Solver) and self._key() == other._key()
+
+    def __ne__(self, other):
+        return not self == other
+
+    def __hash__(self):
+        return hash(self._key())
+
+    def __repr__(self):
+        return "Solver(weight_decay=%r, bias_lr_mult=%r, bias_decay_mult=%r, dropout=%r, freeze=%r)" % self._key()
+
+    def to_struct(self):
+        s = _ffi.SolverParams()
+        s.weight_decay, s.bias_lr_mult, s.bias_decay_mult = self.weight_decay, self.bias_lr_mult, self.bias_decay_mult
+        for i in range(3):
+            s.dropout[i] = self.dropout[i]
+        s.frozen_layers = self.freeze
+        return s
+
+    @classmethod
+    def from_struct(cls, s):
+        return cls(s.weight_decay, s.bias_lr_mult, s.bias_decay_mult, tuple(s.dropout), s.frozen_layers)
+
+
+def check_solver(solver, who):
+    """``solver`` argument of the training surfaces: None or a ``Solver``."""
+    if solver is not None and not isinstance(solver, Solver):
+        raise ValueError("%s: solver must be None or a vgg.Solver, got %r" % (who, solver))
+    return solver
 
 
 def _ffi_conv_cout(i):

@@ -9,6 +9,8 @@ In the reference the first half happens offline
 (precomputed flow JPEGs, Sheet03/temporalModel.py:76-90) and the second half is ``validate()``'s
 forward (Sheet03/spatialModel.py:212-218, Sheet03/temporalModel.py:241-247).
 """
+import types
+
 import torch
 
 from . import flow as vflow
@@ -28,22 +30,42 @@ def build_stream_weights(c_in, seed, device, n_classes=NACTION_CLASSES):
     return w
 
 
-def check_video(rgb, gray, flow_count, motion, n_snippets, views, consensus, fusion_weights, crops=None):
-    """The host-side checks of ``TwoStreamPipeline.submit_video`` (ValueError; nothing touches the device) ->
-    (plan, rgb_views, flow_views, consensus mode, wa, wb)."""
+def _check_rgb(rgb, msg, planes=3):
+    """``rgb`` is a uint8 ``[*,planes,H,W]`` tensor (``planes=None``: any number of them), or ValueError(msg)."""
+    if not isinstance(rgb, torch.Tensor) or rgb.dtype != torch.uint8 or rgb.dim() != 4 or (planes and rgb.shape[1] != planes):
+        raise ValueError(msg)
+
+
+def _check_video_frames(rgb, gray, who):
+    """The frames of one video: rgb uint8 ``[T,3,H,W]`` and gray uint8 or float32 ``[T,H,W]``, one per rgb frame."""
+    _check_rgb(rgb, "%s: rgb must be a uint8 [T,3,H,W] tensor" % who)
+    if not isinstance(gray, torch.Tensor) or gray.dim() != 3 or gray.dtype not in (torch.uint8, torch.float32):
+        raise ValueError("%s: gray must be a uint8 or float32 [T,H,W] tensor" % who)
+    if gray.shape[0] != rgb.shape[0]:
+        raise ValueError("%s: %d rgb frames but %d gray frames" % (who, rgb.shape[0], gray.shape[0]))
+
+
+def _check_view_pair(views, rgb_hw, gray_hw, who):
+    """``views=`` of ``who`` -> (rgb_views, flow_views), each table checked against the size of its frames."""
+    if not isinstance(views, (tuple, list)) or len(views) != 2:
+        raise ValueError("%s: views= must be (rgb_views, flow_views), e.g. two augment.ten_crop_views tables" % who)
+    rgb_views, flow_views = views
+    augment.check_views(rgb_views, rgb_hw[0], rgb_hw[1], augment.CROP_SIZE, "%s(views=)" % who)
+    augment.check_views(flow_views, gray_hw[0], gray_hw[1], augment.CROP_SIZE, "%s(views=)" % who)
+    return rgb_views, flow_views
+
+
+def _check_video_args(rgb, gray, flow_count, motion, n_snippets, views, consensus, fusion_weights, crops, m=2):
+    """``check_video`` for a pipeline that fuses ``m`` streams -> (plan, rgb_views, flow_views, consensus mode, weights)."""
+    who = "submit_video"
     if crops is not None:
         raise ValueError("submit_video: a video takes views=, not crops= (one table for all its snippets)")
     if motion != "stack":
         raise ValueError("submit_video: motion=%r is not offered for whole videos (its chains depend on the window); "
                          "use motion='stack'" % (motion,))
-    if not isinstance(rgb, torch.Tensor) or rgb.dtype != torch.uint8 or rgb.dim() != 4 or rgb.shape[1] != 3:
-        raise ValueError("submit_video: rgb must be a uint8 [T,3,H,W] tensor")
-    if not isinstance(gray, torch.Tensor) or gray.dim() != 3 or gray.dtype not in (torch.uint8, torch.float32):
-        raise ValueError("submit_video: gray must be a uint8 or float32 [T,H,W] tensor")
-    if gray.shape[0] != rgb.shape[0]:
-        raise ValueError("submit_video: %d rgb frames but %d gray frames" % (rgb.shape[0], gray.shape[0]))
-    mode = fusion.check_consensus(consensus, "submit_video")
-    wa, wb = fusion.check_fusion_weights(fusion_weights, "submit_video")
+    _check_video_frames(rgb, gray, who)
+    mode = fusion.check_consensus(consensus, who)
+    ws = fusion.check_fusion_weights(fusion_weights, who) if m == 2 else fusion.check_fusion_weights_n(fusion_weights, m, who)
     try:
         plan = video.snippetPlan(int(gray.shape[0]), flow_count, int(n_snippets))
     except ValueError as e:
@@ -53,14 +75,18 @@ def check_video(rgb, gray, flow_count, motion, n_snippets, views, consensus, fus
             raise ValueError("submit_video: frames of %dx%d need views= (augment.ten_crop_views)" % (rgb.shape[-1], rgb.shape[-2]))
         rgb_views = flow_views = torch.zeros((1, 3), dtype=torch.int32)
     else:
-        if not isinstance(views, (tuple, list)) or len(views) != 2:
-            raise ValueError("submit_video: views= must be (rgb_views, flow_views), e.g. two augment.ten_crop_views tables")
-        rgb_views, flow_views = views
-        augment.check_views(rgb_views, rgb.shape[2], rgb.shape[3], augment.CROP_SIZE, "submit_video(views=)")
-        augment.check_views(flow_views, gray.shape[1], gray.shape[2], augment.CROP_SIZE, "submit_video(views=)")
+        rgb_views, flow_views = _check_view_pair(views, rgb.shape[2:], gray.shape[1:], who)
     for v in (rgb_views, flow_views):
         if v.shape[0] > vgg.Vgg16Stream.VIEW_CHUNK:
             raise ValueError("submit_video: at most %d views, got %d" % (vgg.Vgg16Stream.VIEW_CHUNK, v.shape[0]))
+    return plan, rgb_views, flow_views, mode, ws
+
+
+def check_video(rgb, gray, flow_count, motion, n_snippets, views, consensus, fusion_weights, crops=None):
+    """The host-side checks of ``TwoStreamPipeline.submit_video`` (ValueError; nothing touches the device) ->
+    (plan, rgb_views, flow_views, consensus mode, wa, wb)."""
+    plan, rgb_views, flow_views, mode, (wa, wb) = _check_video_args(rgb, gray, flow_count, motion, n_snippets, views, consensus,
+                                                               fusion_weights, crops)
     return plan, rgb_views, flow_views, mode, wa, wb
 
 
@@ -77,6 +103,8 @@ class TwoStreamPipeline(object):
     beside batch i + 1's TV-L1 instead of holding the TV-L1 streams idle (12 ms of a 140 ms step in round 1).
     ``run_batch()`` = ``submit()`` + ``wait()``: the unpipelined form, same results bit for bit.
     Buffers that cross streams (flow, flow volume) are owned by the pipeline, ``depth`` of each, guarded by events.
+    Every submit path goes through ``_enqueue``, which alone creates, records and waits for those events
+    (``tests/test_pipeline_order_host.py`` pins their order without a GPU).
 
     ``submit_video()`` / ``run_video()`` classify a whole video on the same streams: its snippets share
     one TV-L1 pass over the frame pairs they need, and the scores of snippets and views are averaged and fused on the device.
@@ -207,16 +235,10 @@ class TwoStreamPipeline(object):
         """Host-side checks of ``views=`` before anything is enqueued -> (rgb_views, flow_views)."""
         if flow_stack is not None:
             raise ValueError("submit: views= needs gray frames; flow_stack= is already cropped")
-        if not isinstance(views, (tuple, list)) or len(views) != 2:
-            raise ValueError("submit: views= must be (rgb_views, flow_views), e.g. two augment.ten_crop_views tables")
-        rgb_views, flow_views = views
-        if not isinstance(rgb, torch.Tensor) or rgb.dtype != torch.uint8 or rgb.dim() != 4:
-            raise ValueError("submit: rgb must be a uint8 [B,3,H,W] tensor with views=")
-        augment.check_views(rgb_views, rgb.shape[2], rgb.shape[3], augment.CROP_SIZE, "submit(views=)")
+        _check_rgb(rgb, "submit: rgb must be a uint8 [B,3,H,W] tensor with views=", planes=None)
         if gray is None or gray.dim() != 4:
             raise ValueError("submit: gray must be [B,L+1,H,W] with views=")
-        augment.check_views(flow_views, gray.shape[2], gray.shape[3], augment.CROP_SIZE, "submit(views=)")
-        return rgb_views, flow_views
+        return _check_view_pair(views, rgb.shape[2:], gray.shape[2:], "submit")
 
     def _check_inputs(self, rgb, gray, flow_stack, crops):
         """Host-side checks before anything is enqueued -> (rgb_crops, flow_crops), either None where that input is used as
@@ -227,8 +249,7 @@ class TwoStreamPipeline(object):
                 raise ValueError("submit: crops= must be (rgb_crops, flow_crops) as augment.draw_clip_crops returns")
             rgb_crops, flow_crops = crops
         if rgb_crops is not None:
-            if not isinstance(rgb, torch.Tensor) or rgb.dtype != torch.uint8 or rgb.dim() != 4:
-                raise ValueError("submit: cropped rgb must be a uint8 [B,3,H,W] tensor")
+            _check_rgb(rgb, "submit: cropped rgb must be a uint8 [B,3,H,W] tensor", planes=None)
             augment.check_crops(rgb_crops, rgb.shape[0], rgb.shape[2], rgb.shape[3], augment.CROP_SIZE, "submit(crops=)")
         elif tuple(rgb.shape[-2:]) != (224, 224):
             raise ValueError("submit: rgb frames of %dx%d need crops= (augment.draw_clip_crops)" % (rgb.shape[-1], rgb.shape[-2]))
@@ -277,104 +298,117 @@ class TwoStreamPipeline(object):
         rgb_crops, flow_crops = self._check_inputs(rgb, gray, flow_stack, crops)
         if flow_stack is None and gray.shape[1] != self.L + 1:
             raise ValueError("submit: need %d gray frames per clip, got %d" % (self.L + 1, gray.shape[1]))
-        dev = self.device
-        cur = torch.cuda.current_stream(dev)
-        tv = self._tvl1_frames(gray) if flow_stack is None else None
+        extra = {}
+
+        def spatial(k):
+            rgb.record_stream(self._cnn)
+            return self.spatial.forward(rgb if rgb_crops is None else augment.crop_images(rgb, rgb_crops))[1:]
+
+        def temporal(stack):
+            return self.temporal.forward(stack)[1:]
+
+        def finish(s, t):
+            (desc_s, logits_s), (desc_t, logits_t) = s, t
+            return dict(logits_s=logits_s, logits_t=logits_t, desc_s=desc_s, desc_t=desc_t, **extra)
+
+        if flow_stack is not None:
+            def given_stack(flow, k):
+                flow_stack.record_stream(self._cnn2)
+                return flow_stack
+            return self._enqueue(spatial, given_stack, temporal, finish, beside=True)
+        B, F, H, W = gray.shape
+
+        def to_stack(flow, k):
+            src = self._motion_field(self._camera(flow, extra), k)
+            if flow_crops is None:
+                return vflow.flow_to_stack(src, out=self._buffer(self._stack, k, (B, 2 * self.L, H, W)))
+            # the flow buffer is full-frame, the volume 224x224
+            return vflow.crop_flow_to_stack(src, flow_crops, out=self._buffer(self._stack, k, (B, 2 * self.L, 224, 224)),
+                                            invert_x_on_flip=bool(invert_flow_x))
+        return self._enqueue(spatial, to_stack, temporal, finish, tv=self._tvl1_frames(gray), flow_shape=(B * self.L, 2, H, W))
+
+    def _submit_views(self, rgb, gray, rgb_views, flow_views, invert):
+        """``submit(views=)``: the stream layout of the crops= path, with B*V images per stream and the view means."""
+        B, F, H, W = gray.shape
+        if F != self.L + 1:
+            raise ValueError("submit: need %d gray frames per clip, got %d" % (self.L + 1, F))
+        Vt = flow_views.shape[0]
+        extra = {}
+
+        def spatial(k):
+            rgb.record_stream(self._cnn)
+            return self.spatial.forward_views(augment.crop_image_views(rgb, rgb_views))
+
+        def to_stack(flow, k):
+            src = self._motion_field(self._camera(flow, extra), k)
+            return vflow.crop_flow_to_stack_views(src, flow_views, self.L, invert_x_on_flip=invert,
+                                                  out=self._buffer(self._stack, k, (B, Vt, 2 * self.L, 224, 224)))
+
+        def finish(s, t):
+            (desc_s, logits_s, desc_sv, logits_sv), (desc_t, logits_t, desc_tv, logits_tv) = s, t
+            return dict(logits_s=logits_s, logits_t=logits_t, desc_s=desc_s, desc_t=desc_t, logits_s_views=logits_sv,
+                        logits_t_views=logits_tv, desc_s_views=desc_sv, desc_t_views=desc_tv, **extra)
+        return self._enqueue(spatial, to_stack, self.temporal.forward_views, finish, tv=self._tvl1_frames(gray),
+                             flow_shape=(B * self.L, 2, H, W))
+
+    def _enqueue(self, spatial, to_stack, temporal, finish, tv=None, flow_shape=None, beside=False):
+        """The stream choreography of every submit path (the class docstring); the only place that creates, records or waits
+        for the pipeline's events.  The caller has prepared its inputs on the current stream and supplies what differs:
+
+          * ``tv``, ``flow_shape``: the TV-L1 input and the shape of the slot's flow buffer; None when the flow is given (a
+            stored flow or ``flow_stack=``): no TV-L1 is started and no flow-read event is recorded;
+          * ``spatial(k)``: what runs on the CNN stream before it waits for TV-L1 (the spatial forward, the third stream);
+          * ``to_stack(flow, k)`` -> the temporal input, on the CNN stream behind the TV-L1 events (camera, motion, a gather
+            into slot k's volume);
+          * ``temporal(stack)``: the temporal forward;
+          * ``finish(s, t)``: what follows on the CNN stream (consensus, view means, fusion) -> the result dict, from what
+            ``spatial`` and ``temporal`` returned.
+
+        ``beside``: the ``flow_stack=`` form.  There is no TV-L1 to share the GPU with: the two CNNs (independent models,
+        workspaces of their own) run on two streams, so that the half-empty last round of one layer's workgroups overlaps the
+        other model's layer (measured on the bf16 stack: 2.63 -> 2.53 ms per batch)."""
+        cur = torch.cuda.current_stream(self.device)
         ready = torch.cuda.Event()
         ready.record(cur)  # the inputs are complete here; nothing below makes `cur` wait for anything
         k = self._n % self.depth
         self._n += 1
-        flow = evs = None
-        extra = {}
-        if flow_stack is None:
-            B, F, H, W = gray.shape
-            fbuf = self._buffer(self._flow, k, (B * self.L, 2, H, W))
-            flow, evs = vflow.tvl1_flow_concurrent(tv, self.tvl1_params, self.flow_streams, out=fbuf,
+        flow, evs = None, []
+        if tv is not None:
+            flow, evs = vflow.tvl1_flow_concurrent(tv, self.tvl1_params, self.flow_streams,
+                                                   out=self._buffer(self._flow, k, flow_shape),
                                                    after=[ready, self._flow_read[k]], join=False)
         with torch.cuda.stream(self._cnn):
             self._cnn.wait_event(ready)
-            rgb.record_stream(self._cnn)
-            _, desc_s, logits_s = self.spatial.forward(rgb if rgb_crops is None else augment.crop_images(rgb, rgb_crops))
-            if flow_stack is None:
-                for ev in evs:
-                    self._cnn.wait_event(ev)
-                B, F, H, W = gray.shape
-                src = self._motion_field(self._camera(flow, extra), k)
-                if flow_crops is None:
-                    stack = vflow.flow_to_stack(src, out=self._buffer(self._stack, k, (B, 2 * self.L, H, W)))
-                else:  # the flow buffer is full-frame, the volume 224x224
-                    stack = vflow.crop_flow_to_stack(src, flow_crops,
-                                                     out=self._buffer(self._stack, k, (B, 2 * self.L, 224, 224)),
-                                                     invert_x_on_flip=bool(invert_flow_x))
-                done = torch.cuda.Event()
-                done.record(self._cnn)
-                self._flow_read[k] = done  # after the motion kernel and the gather: both have read the flow
-                if self._t_done is not None:
-                    self._cnn.wait_event(self._t_done)
-                _, desc_t, logits_t = self.temporal.forward(stack)
-                self._t_done = torch.cuda.Event()
-                self._t_done.record(self._cnn)
-            else:
-                # no TV-L1 to share the GPU with: the two CNNs (independent models, workspaces of their own) run on two
-                # streams, so that the half-empty last round of one layer's workgroups overlaps the other model's layer
-                # (measured on the bf16 stack: 2.63 -> 2.53 ms per batch)
+            s = spatial(k)
+            for ev in evs:
+                self._cnn.wait_event(ev)
+            if beside:
                 self._cnn2.wait_event(ready)
-                if self._t_done is not None:
-                    self._cnn2.wait_event(self._t_done)
                 with torch.cuda.stream(self._cnn2):
-                    flow_stack.record_stream(self._cnn2)
-                    _, desc_t, logits_t = self.temporal.forward(flow_stack)
-                    self._t_done = torch.cuda.Event()
-                    self._t_done.record(self._cnn2)
+                    t = self._guarded_temporal(self._cnn2, lambda: temporal(to_stack(flow, k)))
                 self._cnn.wait_stream(self._cnn2)
+            else:
+                stack = to_stack(flow, k)
+                if tv is not None:
+                    self._flow_read[k] = torch.cuda.Event()  # after the motion kernel and the gather: both have read the flow
+                    self._flow_read[k].record(self._cnn)
+                t = self._guarded_temporal(self._cnn, lambda: temporal(stack))
+            out = finish(s, t)
             finished = torch.cuda.Event()
             finished.record(self._cnn)
-        out = dict(logits_s=logits_s, logits_t=logits_t, desc_s=desc_s, desc_t=desc_t, **extra)
-        self._handed_out.extend(out.values())
+        self._handed_out.extend(v for v in out.values() if isinstance(v, torch.Tensor))
         out["done"] = finished  # host-side throttle: out["done"].synchronize() blocks the HOST until this batch is complete
         return out
 
-    def _submit_views(self, rgb, gray, rgb_views, flow_views, invert):
-        """``submit(views=)``: the stream layout of the crops= path, with B*V images per stream and the view means."""
-        dev = self.device
-        B, F, H, W = gray.shape
-        if F != self.L + 1:
-            raise ValueError("submit: need %d gray frames per clip, got %d" % (self.L + 1, F))
-        cur = torch.cuda.current_stream(dev)
-        tv = self._tvl1_frames(gray)
-        ready = torch.cuda.Event()
-        ready.record(cur)
-        k = self._n % self.depth
-        self._n += 1
-        fbuf = self._buffer(self._flow, k, (B * self.L, 2, H, W))
-        flow, evs = vflow.tvl1_flow_concurrent(tv, self.tvl1_params, self.flow_streams, out=fbuf,
-                                               after=[ready, self._flow_read[k]], join=False)
-        with torch.cuda.stream(self._cnn):
-            self._cnn.wait_event(ready)
-            rgb.record_stream(self._cnn)
-            desc_s, logits_s, desc_sv, logits_sv = self.spatial.forward_views(augment.crop_image_views(rgb, rgb_views))
-            for ev in evs:
-                self._cnn.wait_event(ev)
-            Vt = flow_views.shape[0]
-            extra = {}
-            src = self._motion_field(self._camera(flow, extra), k)
-            stack = vflow.crop_flow_to_stack_views(src, flow_views, self.L, invert_x_on_flip=invert,
-                                                   out=self._buffer(self._stack, k, (B, Vt, 2 * self.L, 224, 224)))
-            done = torch.cuda.Event()
-            done.record(self._cnn)
-            self._flow_read[k] = done  # after the motion kernel and the gather
-            if self._t_done is not None:
-                self._cnn.wait_event(self._t_done)
-            desc_t, logits_t, desc_tv, logits_tv = self.temporal.forward_views(stack)
-            self._t_done = torch.cuda.Event()
-            self._t_done.record(self._cnn)
-            finished = torch.cuda.Event()
-            finished.record(self._cnn)
-        out = dict(logits_s=logits_s, logits_t=logits_t, desc_s=desc_s, desc_t=desc_t, logits_s_views=logits_sv,
-                   logits_t_views=logits_tv, desc_s_views=desc_sv, desc_t_views=desc_tv, **extra)
-        self._handed_out.extend(out.values())
-        out["done"] = finished
-        return out
+    def _guarded_temporal(self, stream, forward):
+        """``forward()`` on ``stream`` (the current one), between the wait for the temporal model's previous forward and the
+        record behind this one: the model owns ONE workspace, whichever stream it runs on."""
+        if self._t_done is not None:
+            stream.wait_event(self._t_done)
+        t = forward()
+        self._t_done = torch.cuda.Event()
+        self._t_done.record(stream)
+        return t
 
     def extract_flow(self, frames, rescale=None, dtype=torch.uint8, return_camera=False):
         """The stored flow of one video: TV-L1 once on all ``T - 1`` consecutive frame pairs, kept on the
@@ -412,8 +446,7 @@ class TwoStreamPipeline(object):
                 raise ValueError("%s: gray frames must be uint8 or float32" % who)
         if frames.shape[0] < 2:
             raise ValueError("%s: %d frames hold no frame pair" % (who, frames.shape[0]))
-        if not frames.is_cuda or frames.device != self.device:
-            raise ValueError("%s: frames must be on %s" % (who, self.device))
+        self._check_on_device(who, "frames", frames)
         dev = self.device
         gray = frames.contiguous() if size is None else vframes.prepare_frames(frames, size)[1]
         T, H, W = gray.shape
@@ -469,9 +502,10 @@ class TwoStreamPipeline(object):
         size): one fusion weight per stream, None meaning all ones; ``size`` is None for frames used as they are, else what
         ``frames.prepare_frames`` takes (``gray=None`` / ``rescale=``: the checks then see the prepared shapes).  ``flow``: a
         stored flow, checked against the prepared frames."""
+        who = "submit_video"
         if flow is not None and gray is not None:
             raise ValueError("submit_video: flow= replaces the gray frames and their TV-L1; pass gray=None with it")
-        prep = self._prepared_shapes(rgb, gray, rescale, "submit_video")
+        prep = self._prepared_shapes(rgb, gray, rescale, who)
         decoded = rgb
         if prep is not None:
             _, rgb, gray = prep
@@ -485,27 +519,30 @@ class TwoStreamPipeline(object):
         if given != m:
             raise ValueError("submit_video: this pipeline fuses %d streams (spatial, temporal%s), got %d fusion weights"
                              % (m, ", difference" if m == 3 else "", given))
-        if m == 2:
-            plan, rgb_views, flow_views, mode, wa, wb = check_video(rgb, gray, self.L, self.motion, n_snippets, views, consensus,
-                                                                    fusion_weights, crops)
-            ws = (wa, wb)
-        else:
-            ws = fusion.check_fusion_weights_n(fusion_weights, m, "submit_video")
-            plan, rgb_views, flow_views, mode, _, _ = check_video(rgb, gray, self.L, self.motion, n_snippets, views, consensus,
-                                                                  (1.0, 1.0), crops)
+        plan, rgb_views, flow_views, mode, ws = _check_video_args(rgb, gray, self.L, self.motion, n_snippets, views, consensus,
+                                                             fusion_weights, crops, m)
         if flow is not None:
-            vflow.check_stored_flow(flow, int(gray.shape[0]), int(gray.shape[1]), int(gray.shape[2]), "submit_video")
-            if flow.dtype == torch.uint8 and (self.motion != "stack" or self.mean_flow):
-                raise ValueError("submit_video: motion=%r / mean_flow=%r act on the float field; a uint8 stored flow is already "
-                                 "quantised (store float32 flow for them)" % (self.motion, self.mean_flow))
+            self._check_stored_flow(flow, gray, who, "a uint8 stored flow is")
         if prep is not None:
-            if not decoded.is_cuda or decoded.device != self.device:
-                raise ValueError("submit_video: rgb must be on %s" % (self.device,))
-        elif not rgb.is_cuda or not gray.is_cuda or rgb.device != self.device or gray.device != self.device:
-            raise ValueError("submit_video: rgb and gray must be on %s" % (self.device,))
-        if flow is not None and (not flow.is_cuda or flow.device != self.device):
-            raise ValueError("submit_video: the stored flow must be on %s" % (self.device,))
+            self._check_on_device(who, "rgb", decoded)
+        else:
+            self._check_on_device(who, "rgb and gray", rgb, gray)
+        if flow is not None:
+            self._check_on_device(who, "the stored flow", flow)
         return plan, rgb_views, flow_views, mode, ws, None if prep is None else prep[0]
+
+    def _check_stored_flow(self, flow, gray, who, uint8_flow_is):
+        """The rules of one video's stored flow but the device: its type and its shape against the
+        (prepared) gray frames, and a uint8 store only where nothing acts on the float field."""
+        vflow.check_stored_flow(flow, int(gray.shape[0]), int(gray.shape[1]), int(gray.shape[2]), who)
+        if flow.dtype == torch.uint8 and (self.motion != "stack" or self.mean_flow):
+            raise ValueError("%s: motion=%r / mean_flow=%r act on the float field; %s already quantised (store float32 flow for "
+                             "them)" % (who, self.motion, self.mean_flow, uint8_flow_is))
+
+    def _check_on_device(self, who, what, *tensors):
+        """Every tensor is on the pipeline's device, or ValueError "<who>: <what> must be on <device>"."""
+        if any(not isinstance(t, torch.Tensor) or not t.is_cuda or t.device != self.device for t in tensors):
+            raise ValueError("%s: %s must be on %s" % (who, what, self.device))
 
     def submit_video(self, rgb, gray=None, n_snippets=video.N_SNIPPETS, views=None, invert_flow_x=False, consensus="softmax",
                      fusion_weights=None, crops=None, task=None, rescale=None, flow=None):
@@ -555,89 +592,77 @@ class TwoStreamPipeline(object):
         stored = flow
         plan, rgb_views, flow_views, mode, fw, size = self._check_video(rgb, gray, n_snippets, views, consensus, fusion_weights,
                                                                        crops, rescale, stored)
-        dev = self.device
         n, U = plan.n, len(plan.pairs)
         if stored is not None:  # the gray frames only fed TV-L1: the frames are rescaled (S38) or used as they are
             if size is not None and tuple(size) != tuple(rgb.shape[2:]):
                 rgb, _ = vframes.prepare_frames(rgb, size)
             T, H, W = int(rgb.shape[0]), int(rgb.shape[2]), int(rgb.shape[3])
+            tv = None
         else:
             if gray is None:  # S38: on the current stream, ahead of the gathers and of `ready`
                 rgb, gray = vframes.prepare_frames(rgb, size)
             T, H, W = gray.shape
-        cur = torch.cuda.current_stream(dev)
-        if stored is None:
-            seq = augment.crops_to_device(torch.tensor(plan.sequences, dtype=torch.int64), dev)
-            tv = gray[seq]                                                 # [U,2,H,W]: one two-frame sequence per planned pair
-        frames = rgb[augment.crops_to_device(torch.tensor(plan.starts, dtype=torch.int64), dev)]  # [n,3,H,W]
-        ready = torch.cuda.Event()
-        ready.record(cur)
-        k = self._n % self.depth
-        self._n += 1
-        if stored is None:
-            fbuf = self._buffer(self._flow, k, (U, 2, H, W))
-            flow, evs = vflow.tvl1_flow_concurrent(tv, self.tvl1_params, self.flow_streams, out=fbuf,
-                                                   after=[ready, self._flow_read[k]], join=False)
-        else:  # the store is complete at `ready`; its windows start at the snippets' own pairs
-            flow, evs = stored, []
-        with torch.cuda.stream(self._cnn):
-            self._cnn.wait_event(ready)
+            tv = self._take(gray, plan.sequences)                          # [U,2,H,W]: one two-frame sequence per planned pair
+        frames = self._take(rgb, plan.starts)                              # [n,3,H,W]
+        Vt = flow_views.shape[0]
+        extra = {}
+
+        def spatial(k):
             frames.record_stream(self._cnn)
-            _, _, desc_sv, logits_sv = self.spatial.forward_views(augment.crop_image_views(frames, rgb_views))
-            extra = {}
-            if self.diff is not None:  # S23 / S25: before the wait, so that it fills the time TV-L1 is still running
-                Vs, C = rgb_views.shape[0], 3 * self.D
-                rgb.record_stream(self._cnn)
-                dstack = rgbdiff.rgb_diff_stack(rgb, rgbdiff.view_table(plan.starts, rgb_views), self.D,
-                                                out=self._buffer(self._dstack, k, (n, Vs, C, 224, 224)))
-                _, _, desc_dv, logits_dv = self.diff.forward_views(dstack.view(n, Vs, C, 224, 224))
-            for ev in evs:
-                self._cnn.wait_event(ev)
-            Vt = flow_views.shape[0]
+            s = self.spatial.forward_views(augment.crop_image_views(frames, rgb_views))[2:]
+            if self.diff is None:
+                return s, None
+            # S23 / S25: before the wait for TV-L1, so that it fills the time TV-L1 is still running
+            Vs, C = rgb_views.shape[0], 3 * self.D
+            rgb.record_stream(self._cnn)
+            dstack = rgbdiff.rgb_diff_stack(rgb, rgbdiff.view_table(plan.starts, rgb_views), self.D,
+                                            out=self._buffer(self._dstack, k, (n, Vs, C, 224, 224)))
+            return s, self.diff.forward_views(dstack.view(n, Vs, C, 224, 224))[2:]
+
+        def to_stack(flow, k):
             if stored is None:
                 src = self._camera(flow, extra)  # per planned field, like the means
-            else:
-                flow.record_stream(self._cnn)
-                src = flow
+            else:  # the store is complete at `ready`; its windows start at the snippets' own pairs
+                stored.record_stream(self._cnn)
+                src = stored
             if self.mean_flow:  # S11 / S12 per planned field: no chains, so the clip length does not matter
-                src = vflow.apply_motion(src, 1, "stack", True, out=self._buffer(self._motion, k, tuple(flow.shape)))
+                src = vflow.apply_motion(src, 1, "stack", True, out=self._buffer(self._motion, k, tuple(src.shape)))
             first = plan.index if stored is None else plan.starts
             gather = vflow.flowq_to_stack_snippets if src.dtype == torch.uint8 else vflow.crop_flow_to_stack_snippets
-            stack = gather(src, first, flow_views, self.L, invert_x_on_flip=bool(invert_flow_x),
-                           out=self._buffer(self._stack, k, (n, Vt, 2 * self.L, 224, 224)))
-            if stored is None:
-                done = torch.cuda.Event()
-                done.record(self._cnn)
-                self._flow_read[k] = done
-            if self._t_done is not None:
-                self._cnn.wait_event(self._t_done)
-            _, _, desc_tv, logits_tv = self.temporal.forward_views(stack)
-            self._t_done = torch.cuda.Event()
-            self._t_done.record(self._cnn)
-            own = (lambda t: t) if task is None else (lambda t: vgg.head_logits(t, self.heads, task))  # S26: the video's head
+            return gather(src, first, flow_views, self.L, invert_x_on_flip=bool(invert_flow_x),
+                          out=self._buffer(self._stack, k, (n, Vt, 2 * self.L, 224, 224)))
+
+        def temporal(stack):
+            return self.temporal.forward_views(stack)[2:]
+
+        def finish(s, t):
+            ((desc_sv, logits_sv), d), (desc_tv, logits_tv) = s, t
+            own = (lambda x: x) if task is None else (lambda x: vgg.head_logits(x, self.heads, task))  # S26: the video's head
             scores_s = fusion.score_consensus(own(logits_sv).unsqueeze(0), consensus)
             scores_t = fusion.score_consensus(own(logits_tv).unsqueeze(0), consensus)
             desc_s = vgg.view_mean(desc_sv.view(1, -1, desc_sv.shape[-1]))
             desc_t = vgg.view_mean(desc_tv.view(1, -1, desc_tv.shape[-1]))
-            if self.diff is None:
+            if d is None:
                 scores, pred = fusion.fuse_scores(scores_s, scores_t, fw)
             else:
+                desc_dv, logits_dv = d
                 scores_d = fusion.score_consensus(own(logits_dv).unsqueeze(0), consensus)
                 scores, pred = fusion.fuse_scores_n([scores_s, scores_t, scores_d], fw)
                 desc_d = vgg.view_mean(desc_dv.view(1, -1, desc_dv.shape[-1]))
                 extra.update(scores_d=scores_d[0], desc_d=desc_d[0], logits_d_items=logits_dv)
-            finished = torch.cuda.Event()
-            finished.record(self._cnn)
-        out = dict(scores_s=scores_s[0], scores_t=scores_t[0], scores=scores[0], pred=pred[0], desc_s=desc_s[0], desc_t=desc_t[0],
-                   logits_s_items=logits_sv, logits_t_items=logits_tv, **extra)
-        self._handed_out.extend(out.values())
-        out["starts"] = list(plan.starts)
-        out["plan"] = plan
-        out["frame_size"] = (int(H), int(W))
-        if task is not None:
-            out["task"] = task
-        out["done"] = finished
-        return out
+            out = dict(scores_s=scores_s[0], scores_t=scores_t[0], scores=scores[0], pred=pred[0], desc_s=desc_s[0],
+                       desc_t=desc_t[0], logits_s_items=logits_sv, logits_t_items=logits_tv, **extra)
+            out["starts"] = list(plan.starts)
+            out["plan"] = plan
+            out["frame_size"] = (int(H), int(W))
+            if task is not None:
+                out["task"] = task
+            return out
+        return self._enqueue(spatial, to_stack, temporal, finish, tv=tv, flow_shape=(U, 2, H, W))
+
+    def _take(self, t, idx):
+        """``t[idx]`` for a device tensor and a host list of indices (the index goes to the device on the current stream)."""
+        return t[augment.crops_to_device(torch.tensor(idx, dtype=torch.int64), self.device)]
 
     def run_video(self, rgb, gray=None, n_snippets=video.N_SNIPPETS, views=None, invert_flow_x=False, consensus="softmax",
                   fusion_weights=None, crops=None, task=None, rescale=None, flow=None):
@@ -675,14 +700,14 @@ class TwoStreamPipeline(object):
         return int(micro_videos)
 
     def _check_train_videos(self, videos, labels, k, starts, crops, rng, tasks=None, micro=None, rescale=None, flows=None):
-        """Host-side checks and draws of ``train_videos`` before anything is enqueued -> (videos, labels, plans, crops, tasks,
-        sizes); ``tasks`` is None on a pipeline without heads.  ``micro``: videos per micro-batch (``_check_accumulate``),
+        """Host-side checks and draws of ``train_videos`` before anything is enqueued -> a namespace of ``videos``, ``labels``,
+        ``plans``, ``crops``, ``tasks``, ``sizes`` and ``flows``; ``tasks`` is None on a pipeline without heads.  ``micro``: videos per micro-batch (``_check_accumulate``),
         which lifts the limit on ``n*k``.  ``videos`` comes back as ``(rgb, gray)`` pairs, gray None where it is to be derived;
         ``sizes[i]`` is then what ``frames.prepare_frames`` takes for video i (None for a video used as it is), and every
         shape check has seen the prepared shapes.  ``flows``: None or one stored flow per video (DESIGN.md
         S39-S41), checked against the prepared frames; it comes back as a list."""
         who = "train_videos"
-        heads = getattr(self, "heads", None)
+        heads = getattr(self, "heads", None)  # getattr: the host tests build pipelines attribute by attribute, some without heads
         if heads is None and tasks is not None:
             raise ValueError("%s: tasks= needs a pipeline built with heads=" % who)
         if heads is not None and tasks is None:
@@ -702,16 +727,12 @@ class TwoStreamPipeline(object):
                 raise ValueError("%s: videos must be a list of (rgb u8 [T,3,H,W], gray [T,H,W]) pairs, (rgb, None) or rgb "
                                  "alone" % who)
             rgb, gray = v
-            if not isinstance(rgb, torch.Tensor) or rgb.dtype != torch.uint8 or rgb.dim() != 4 or rgb.shape[1] != 3:
-                raise ValueError("%s: rgb must be a uint8 [T,3,H,W] tensor" % who)
+            _check_rgb(rgb, "%s: rgb must be a uint8 [T,3,H,W] tensor" % who)
             prep = self._prepared_shapes(rgb, gray, rescale, who)
             on_device += [rgb] if prep is not None else [rgb, gray]
             if prep is not None:
                 _, rgb, gray = prep
-            if not isinstance(gray, torch.Tensor) or gray.dim() != 3 or gray.dtype not in (torch.uint8, torch.float32):
-                raise ValueError("%s: gray must be a uint8 or float32 [T,H,W] tensor" % who)
-            if gray.shape[0] != rgb.shape[0]:
-                raise ValueError("%s: %d rgb frames but %d gray frames" % (who, rgb.shape[0], gray.shape[0]))
+            _check_video_frames(rgb, gray, who)
             videos.append((rgb, gray))
             sizes.append(None if prep is None else prep[0])
             if (tuple(rgb.shape[2:]) != tuple(videos[0][0].shape[2:]) or tuple(gray.shape[1:]) != tuple(videos[0][1].shape[1:])
@@ -731,17 +752,12 @@ class TwoStreamPipeline(object):
                 raise ValueError("%s: %d videos but %d stored flows" % (who, n, len(flows)))
             if any(g is not None for _, g in given):
                 raise ValueError("%s: flows= replaces the gray frames and their TV-L1; pass (rgb, None) or rgb alone with it" % who)
-            H, W = (int(d) for d in videos[0][1].shape[1:])
             for f, (_, gray) in zip(flows, videos):
-                vflow.check_stored_flow(f, int(gray.shape[0]), H, W, who)
+                self._check_stored_flow(f, gray, who, "uint8 stored flows are")
             if any(f.dtype != flows[0].dtype for f in flows):
                 raise ValueError("%s: the stored flows of one step must share their type" % who)
-            if flows[0].dtype == torch.uint8 and (self.motion != "stack" or self.mean_flow):
-                raise ValueError("%s: motion=%r / mean_flow=%r act on the float field; uint8 stored flows are already quantised "
-                                 "(store float32 flow for them)" % (who, self.motion, self.mean_flow))
             on_device += flows
-        if any(not isinstance(t, torch.Tensor) or not t.is_cuda or t.device != self.device for t in on_device):
-            raise ValueError("%s: rgb and gray%s must be on %s" % (who, "" if flows is None else " and the stored flows", self.device))
+        self._check_on_device(who, "rgb and gray" + ("" if flows is None else " and the stored flows"), *on_device)
         H, W = (int(d) for d in videos[0][1].shape[1:])
         if not isinstance(labels, torch.Tensor):
             try:
@@ -769,7 +785,8 @@ class TwoStreamPipeline(object):
         if crops is None:
             crops = augment.draw_scale_jitter_crops(n * k, H, W, rng)
         augment.check_jitter_crops(crops, n * k, H, W, who)
-        return [tuple(v) for v in given], labels, plans, crops, tasks, sizes, flows
+        return types.SimpleNamespace(videos=[tuple(v) for v in given], labels=labels, plans=plans, crops=crops, tasks=tasks,
+                                     sizes=sizes, flows=flows)
 
     @staticmethod
     def _check_jitter(n_snippets, color_jitter, jitter, lighting, rng):
@@ -913,85 +930,98 @@ class TwoStreamPipeline(object):
         videos = list(videos)
         solvers = self._check_solver(solver)
         micro = self._check_accumulate(len(videos), int(k), micro_videos, clip_norm, data_parallel)
-        videos, labels, plans, crops, tasks, sizes, flows = self._check_train_videos(videos, labels, k, starts, crops, rng, tasks,
-                                                                                      micro, rescale, flows)
-        jitter = self._check_jitter(len(videos) * int(k), color_jitter, jitter, lighting, rng)
+        c = self._check_train_videos(videos, labels, k, starts, crops, rng, tasks, micro, rescale, flows)
+        n, k = len(c.videos), int(k)
+        jitter = self._check_jitter(n * k, color_jitter, jitter, lighting, rng)
         for m, sv in solvers:  # host state of each stream: nothing is enqueued
             m.set_solver(sv)
-        if flows is None:
-            videos = [v if v[1] is not None else vframes.prepare_frames(v[0], size) for v, size in zip(videos, sizes)]  # S38
+        if c.flows is None:
+            videos = [v if v[1] is not None else vframes.prepare_frames(v[0], size) for v, size in zip(c.videos, c.sizes)]  # S38
         else:  # the gray frames only fed TV-L1: the frames are rescaled (S38) or used as they are
             videos = [(v[0] if tuple(size) == tuple(v[0].shape[2:]) else vframes.prepare_frames(v[0], size)[0], None)
-                      for v, size in zip(videos, sizes)]
+                      for v, size in zip(c.videos, c.sizes)]
+        labels, tasks = c.labels, c.tasks
         if micro is not None:
-            step = self._accumulate_step(len(videos), int(k), micro, labels, tasks, lr, momentum, dropout_seed, clip_norm, data_parallel)
+            step = self._accumulate_step(n, k, micro, labels, tasks, lr, momentum, dropout_seed, clip_norm, data_parallel)
         elif tasks is None:
             step = lambda m, x: m.train_step_consensus(x, labels, k, lr, momentum, dropout_seed)
         else:
             step = lambda m, x: m.train_step_multitask(x, labels, tasks, self.heads, k, lr, momentum, dropout_seed)
-        dev, L, n, k = self.device, self.L, len(videos), int(k)
-        cur = torch.cuda.current_stream(dev)
-        frames = torch.cat([rgb[augment.crops_to_device(torch.tensor(p.starts, dtype=torch.int64), dev)]
-                            for (rgb, _), p in zip(videos, plans)])  # [n*k,3,H,W]
-        if flows is not None:  # the planned fields of every store, in the order TV-L1 would have written them
-            flow = torch.cat([f[augment.crops_to_device(torch.tensor(p.pairs, dtype=torch.int64), dev)] for f, p in zip(flows, plans)])
-            first, base = [], 0
-            for p in plans:
-                first += [base + j for j in p.index]
-                base += len(p.pairs)
-        elif self.motion == "bidirectional":  # S13 per snippet window: its own forward and backward sequences, no sharing
-            win = torch.cat([gray[augment.crops_to_device(torch.tensor([[s + f for f in range(L + 1)] for s in p.starts],
-                                                                        dtype=torch.int64), dev)]
-                             for (_, gray), p in zip(videos, plans)])  # [n*k,L+1,H,W]
-            tv = vflow.bidirectional_sequences(win)
-            first = [i * L for i in range(n * k)]
-        else:
-            tv = torch.cat([gray[augment.crops_to_device(torch.tensor(p.sequences, dtype=torch.int64), dev)]
-                            for (_, gray), p in zip(videos, plans)])  # [U,2,H,W]: one two-frame sequence per planned pair
-            first, base = [], 0
-            for p in plans:
-                first += [base + j for j in p.index]
-                base += len(p.pairs)
+        cur = torch.cuda.current_stream(self.device)
         extra = {}
-        if flows is None:
-            flow = vflow.tvl1_flow_concurrent(tv, self.tvl1_params, self.flow_streams)
-            flow = self._camera(flow, extra)  # per planned field, in place: everything below reads the compensated field
-        if flow.dtype == torch.uint8:  # S41: the stored images themselves
-            src = flow
-        elif self.motion == "trajectory":  # S12 chains follow a window: the windows are laid out one after the other
-            idx = torch.tensor([f + j for f in first for j in range(L)], dtype=torch.int64)
-            src = vflow.apply_motion(flow[augment.crops_to_device(idx, dev)], L, "trajectory", self.mean_flow)
-            first = [i * L for i in range(n * k)]
-        elif self.motion == "bidirectional":
-            src = vflow.apply_motion(flow, L, "bidirectional", self.mean_flow)
-        else:  # S11 / S12 per planned field
-            src = vflow.apply_motion(flow, 1, "stack", self.mean_flow)
-        rgb_table, flow_table = augment.snippet_tables(crops, list(range(n * k)), first, L)
-        xs = augment.resize_images(frames, rgb_table)
-        if jitter is not None or lighting is not None:  # S35: the spatial stream's input alone, in place
-            table = jitter if jitter is not None else torch.tensor([augment.IDENTITY_JITTER_ROW] * (n * k), dtype=torch.float32)
-            xs = augment.color_jitter(xs, table, lighting, out=xs)
-        gather = vflow.resize_flowq_to_stack if src.dtype == torch.uint8 else vflow.resize_flow_to_stack
-        xt = gather(src, flow_table, invert_x_on_flip=bool(invert_flow_x)).view(n * k, 2 * L, 224, 224)
+        xs, xt, flow = self._train_inputs(c, videos, jitter, lighting, bool(invert_flow_x), extra)
         cur.wait_stream(self._cnn)   # forwards submitted earlier read the weights this step updates
         cur.wait_stream(self._cnn2)
         stats_s, desc_s = step(self.spatial, xs)
         stats_t, desc_t = step(self.temporal, xt)
         if micro is not None and clip_norm is not None:
             extra["norm_s"], extra["norm_t"] = step.norms[self.spatial], step.norms[self.temporal]
-        if self.diff is not None:  # S25: the windows' frames one after the other, one S23 call on the snippets' crops
-            D = self.D
-            win = torch.cat([rgb[augment.crops_to_device(torch.tensor([s + f for s in p.starts for f in range(D + 1)],
-                                                                       dtype=torch.int64), dev)]
-                             for (rgb, _), p in zip(videos, plans)])  # [n*k*(D+1),3,H,W]
-            xd = rgbdiff.rgb_diff_stack(win, rgbdiff.window_table([i * (D + 1) for i in range(n * k)], crops), D)
-            extra["stats_d"], extra["desc_d"] = step(self.diff, xd)
+        if self.diff is not None:
+            extra["stats_d"], extra["desc_d"] = step(self.diff, self._train_diff_input(videos, c.plans, c.crops))
             if micro is not None and clip_norm is not None:
                 extra["norm_d"] = step.norms[self.diff]
         self._cnn.wait_stream(cur)
         self._cnn2.wait_stream(cur)
-        return dict(stats_s=stats_s, desc_s=desc_s, stats_t=stats_t, desc_t=desc_t, starts=[list(p.starts) for p in plans],
-                    crops=crops, plans=plans, flow=flow, jitter=jitter, **extra)
+        return dict(stats_s=stats_s, desc_s=desc_s, stats_t=stats_t, desc_t=desc_t, starts=[list(p.starts) for p in c.plans],
+                    crops=c.crops, plans=c.plans, flow=flow, jitter=jitter, **extra)
+
+    @staticmethod
+    def _planned_positions(plans):
+        """-> for every snippet of every plan, video-major, the position of its first field among the planned fields of all
+        plans laid out one plan after the other (the order TV-L1 writes them)."""
+        first, base = [], 0
+        for p in plans:
+            first += [base + j for j in p.index]
+            base += len(p.pairs)
+        return first
+
+    def _train_inputs(self, c, videos, jitter, lighting, invert_flow_x, extra):
+        """The inputs of one ``train_videos`` step from its checked arguments ``c`` (``_check_train_videos``) and the prepared
+        ``videos``, in order on the current stream -> (spatial input u8 ``[n*k,3,224,224]``, temporal input f32
+        ``[n*k,2L,224,224]``, the planned flow fields).  ``extra`` receives the camera step's results."""
+        L, plans, flows = self.L, c.plans, c.flows
+        n_snippets = sum(len(p.starts) for p in plans)
+        windows = [i * L for i in range(n_snippets)]  # the first field of every snippet where each has L fields of its own
+        frames = torch.cat([self._take(rgb, p.starts) for (rgb, _), p in zip(videos, plans)])  # [n*k,3,H,W]
+        if flows is not None:  # the planned fields of every store, in the order TV-L1 would have written them
+            flow = torch.cat([self._take(f, p.pairs) for f, p in zip(flows, plans)])
+            first = self._planned_positions(plans)
+        elif self.motion == "bidirectional":  # S13 per snippet window: its own forward and backward sequences, no sharing
+            win = torch.cat([self._take(gray, [[s + f for f in range(L + 1)] for s in p.starts])
+                             for (_, gray), p in zip(videos, plans)])  # [n*k,L+1,H,W]
+            tv = vflow.bidirectional_sequences(win)
+            first = windows
+        else:
+            tv = torch.cat([self._take(gray, p.sequences) for (_, gray), p in zip(videos, plans)])  # [U,2,H,W]: one two-frame sequence per planned pair
+            first = self._planned_positions(plans)
+        if flows is None:
+            flow = vflow.tvl1_flow_concurrent(tv, self.tvl1_params, self.flow_streams)
+            flow = self._camera(flow, extra)  # per planned field, in place: everything below reads the compensated field
+        if flow.dtype == torch.uint8:  # S41: the stored images themselves
+            src = flow
+        elif self.motion == "trajectory":  # S12 chains follow a window: the windows are laid out one after the other
+            src = vflow.apply_motion(self._take(flow, [f + j for f in first for j in range(L)]), L, "trajectory", self.mean_flow)
+            first = windows
+        elif self.motion == "bidirectional":
+            src = vflow.apply_motion(flow, L, "bidirectional", self.mean_flow)
+        else:  # S11 / S12 per planned field
+            src = vflow.apply_motion(flow, 1, "stack", self.mean_flow)
+        rgb_table, flow_table = augment.snippet_tables(c.crops, list(range(n_snippets)), first, L)
+        xs = augment.resize_images(frames, rgb_table)
+        if jitter is not None or lighting is not None:  # S35: the spatial stream's input alone, in place
+            table = jitter if jitter is not None else torch.tensor([augment.IDENTITY_JITTER_ROW] * n_snippets, dtype=torch.float32)
+            xs = augment.color_jitter(xs, table, lighting, out=xs)
+        gather = vflow.resize_flowq_to_stack if src.dtype == torch.uint8 else vflow.resize_flow_to_stack
+        xt = gather(src, flow_table, invert_x_on_flip=invert_flow_x).view(n_snippets, 2 * L, 224, 224)
+        return xs, xt, flow
+
+    def _train_diff_input(self, videos, plans, crops):
+        """The third stream's input of one ``train_videos`` step (S25): the windows' frames one after the other, one S23 call
+        on the snippets' crops -> f32 ``[n*k,3D,224,224]``."""
+        D = self.D
+        win = torch.cat([self._take(rgb, [s + f for s in p.starts for f in range(D + 1)])
+                         for (rgb, _), p in zip(videos, plans)])  # [n*k*(D+1),3,H,W]
+        return rgbdiff.rgb_diff_stack(win, rgbdiff.window_table([i * (D + 1) for i in range(len(crops))], crops), D)
 
     def wait(self, stream=None):
         """Make ``stream`` (default: the current one) wait for every batch submitted so far."""

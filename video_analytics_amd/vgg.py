@@ -5,6 +5,7 @@ This is the object the reference obtains from ``models.vgg16(pretrained=True)`` 
 Sheet03/spatialModel.py:110-113,136-152; Sheet03/temporalModel.py:122-126,149-181.
 """
 import ctypes
+import types
 
 import torch
 
@@ -272,30 +273,70 @@ class Vgg16Stream(object):
         mode, mean cross-entropy, backward, SGD update.  Returns (stats, descriptors): ``stats`` is a CUDA
         float32 ``[2]`` = (loss, number of arg-max hits) of the forward pass, ``descriptors`` ``[B,D]`` the
         train-mode feature tap; nothing synchronises the host."""
-        if not getattr(self, "_train_ready", False):
+        p = self._train_batch("train_step", x, labels)
+        _ffi.check(_ffi.lib().va_vgg16_train_step(self._h, _ffi.ptr(p.x), p.is_u8, _ffi.ptr(p.labels), p.B, float(lr),
+                                                  float(momentum), int(dropout_seed) & 0xFFFFFFFFFFFFFFFF, _ffi.ptr(p.desc),
+                                                  _ffi.ptr(p.stats), _ffi.ptr(p.ws), p.ws.numel(), _ffi.stream_ptr(self.device)))
+        return p.stats, p.desc
+
+    # what differs between the four wrappers in the checks they share: the letters of x's first dimension, the smallest k (None:
+    # no k, every image is its own video), the two texts about labels (None: check_tasks or the kernel speaks) and the text
+    # for a batch size the library refuses
+    _TRAIN_TEXTS = {
+        "train_step": ("B", None, None, "labels must be [B]", "batch %(B)d unsupported (1..64, fp32 model)"),
+        "train_step_consensus": ("n*k", 1, "labels must be a tensor [n]", "labels must be [%(n)d], one per video",
+                                 "%(n)d videos x %(k)d snippets unsupported (n*k in 1..64, fp32 model)"),
+        "train_step_multitask": ("n*k", 1, None, None, "%(n)d videos x %(k)d snippets unsupported (n*k in 1..64, fp32 model)"),
+        "train_accumulate": ("B", 0, "labels must be a tensor [%(n)d]", "labels must be [%(n)d]",
+                             "%(B)d images unsupported (1..64 per micro-batch, fp32 model)"),
+    }
+
+    def _train_batch(self, name, x, labels, k=None, tasks=None, heads=None, multitask=False, init_first=True):
+        """What every form of the training step does before its ABI call: the lazy ``train_init``, the checks on ``x``, the
+        whole-number-of-videos rule (``k = 0``: images, where ``name`` allows it), labels (``multitask``: and tasks, against
+        ``heads``) checked and moved to the device, the workspace, and the outputs.  -> a namespace: ``x`` (contiguous), ``is_u8``, ``labels``, ``tasks``,
+        ``heads`` (a list, or None), ``B``, ``n``, ``k``, ``ws``, ``stats`` f32 ``[2]`` or ``[2+2H]``, ``desc`` f32 ``[B,D]``.
+        ``init_first=False``: ``train_init`` runs after the checks instead (``train_accumulate`` refuses bad arguments on a
+        model that has never trained without allocating its momentum buffers)."""
+        who = "Vgg16Stream." + name
+        dims, k_min, not_a_tensor, bad_shape, unsupported = self._TRAIN_TEXTS[name]
+        if init_first and not getattr(self, "_train_ready", False):
             self.train_init()
         if not isinstance(x, torch.Tensor) or not x.is_cuda or x.dtype not in (torch.float32, torch.uint8):
-            raise ValueError("Vgg16Stream.train_step: x must be a CUDA float32/uint8 tensor")
+            raise ValueError("%s: x must be a CUDA float32/uint8 tensor" % who)
         if x.dim() != 4 or tuple(x.shape[1:]) != (self.c_in, 224, 224):
-            raise ValueError("Vgg16Stream.train_step: x must be [B,%d,224,224], got %s" % (self.c_in, tuple(x.shape)))
-        self._on_my_device(x, "train_step")
-        B = x.shape[0]
-        _check_labels(labels, self.n_classes, "Vgg16Stream.train_step")
+            raise ValueError("%s: x must be [%s,%d,224,224], got %s" % (who, dims, self.c_in, tuple(x.shape)))
+        self._on_my_device(x, name)
+        if multitask:
+            check_heads(heads, self.n_classes, who)
+            heads = [int(h) for h in heads]
+        B = n = int(x.shape[0])
+        if k_min is not None:
+            k = int(k)
+            if k < k_min or B < 1 or B % max(k, 1):
+                raise ValueError("%s: %d images are not a whole number of videos of k=%d snippets" % (who, B, k))
+            n = B // max(k, 1)
+        sizes = dict(B=B, n=n, k=k)
+        if multitask:
+            labels, tasks = check_tasks(labels, tasks, heads, n, who)
+            tasks = tasks.to(device=x.device, dtype=torch.int32).contiguous()
+        else:
+            _check_labels(labels, self.n_classes, who)
+            if not_a_tensor is not None and not isinstance(labels, torch.Tensor):
+                raise ValueError("%s: %s" % (who, not_a_tensor % sizes))
         labels = labels.to(device=x.device, dtype=torch.int64).contiguous()
-        if labels.dim() != 1 or labels.shape[0] != B:
-            raise ValueError("Vgg16Stream.train_step: labels must be [B]")
-        x = x.contiguous()
-        L = _ffi.lib()
-        nbytes = L.va_vgg16_train_workspace_bytes(self._h, B)
+        if bad_shape is not None and (labels.dim() != 1 or labels.shape[0] != n):
+            raise ValueError("%s: %s" % (who, bad_shape % sizes))
+        if not init_first and not getattr(self, "_train_ready", False):
+            self.train_init()
+        nbytes = _ffi.lib().va_vgg16_train_workspace_bytes(self._h, B)
         if nbytes == 0:
-            raise ValueError("Vgg16Stream.train_step: batch %d unsupported (1..64, fp32 model)" % B)
-        ws = _workspace(nbytes, x.device, ("train", self.ws_slot))
-        stats = torch.empty(2, dtype=torch.float32, device=x.device)
-        desc = torch.empty((B, self.desc_dim), dtype=torch.float32, device=x.device)
-        _ffi.check(L.va_vgg16_train_step(self._h, _ffi.ptr(x), int(x.dtype == torch.uint8), _ffi.ptr(labels), B, float(lr),
-                                         float(momentum), int(dropout_seed) & 0xFFFFFFFFFFFFFFFF, _ffi.ptr(desc), _ffi.ptr(stats),
-                                         _ffi.ptr(ws), ws.numel(), _ffi.stream_ptr(self.device)))
-        return stats, desc
+            raise ValueError("%s: %s" % (who, unsupported % sizes))
+        return types.SimpleNamespace(
+            x=x.contiguous(), is_u8=int(x.dtype == torch.uint8), labels=labels, tasks=tasks, heads=heads, B=B, n=n, k=k,
+            ws=_workspace(nbytes, x.device, ("train", self.ws_slot)),
+            stats=torch.empty(2 + 2 * len(heads) if heads else 2, dtype=torch.float32, device=x.device),
+            desc=torch.empty((B, self.desc_dim), dtype=torch.float32, device=x.device))
 
     def train_step_consensus(self, x, labels, k, lr, momentum, dropout_seed):
         """``train_step`` with the loss on the consensus of each video's ``k`` snippets (TSN's segmental
@@ -303,37 +344,12 @@ class Vgg16Stream(object):
         averaged (in snippet order), the mean cross-entropy of the n averages is the loss, and every snippet receives
         1/k of its video's gradient.  Returns (stats, descriptors): ``stats`` = (loss, arg-max hits of the averaged
         scores), ``descriptors`` ``[n*k,D]``.  ``k = 1`` is ``train_step`` bit for bit."""
-        if not getattr(self, "_train_ready", False):
-            self.train_init()
-        who = "Vgg16Stream.train_step_consensus"
-        if not isinstance(x, torch.Tensor) or not x.is_cuda or x.dtype not in (torch.float32, torch.uint8):
-            raise ValueError("%s: x must be a CUDA float32/uint8 tensor" % who)
-        if x.dim() != 4 or tuple(x.shape[1:]) != (self.c_in, 224, 224):
-            raise ValueError("%s: x must be [n*k,%d,224,224], got %s" % (who, self.c_in, tuple(x.shape)))
-        self._on_my_device(x, "train_step_consensus")
-        B, k = int(x.shape[0]), int(k)
-        if k < 1 or B < 1 or B % k:
-            raise ValueError("%s: %d images are not a whole number of videos of k=%d snippets" % (who, B, k))
-        n = B // k
-        _check_labels(labels, self.n_classes, who)
-        if not isinstance(labels, torch.Tensor):
-            raise ValueError("%s: labels must be a tensor [n]" % who)
-        labels = labels.to(device=x.device, dtype=torch.int64).contiguous()
-        if labels.dim() != 1 or labels.shape[0] != n:
-            raise ValueError("%s: labels must be [%d], one per video" % (who, n))
-        x = x.contiguous()
-        L = _ffi.lib()
-        nbytes = L.va_vgg16_train_workspace_bytes(self._h, B)
-        if nbytes == 0:
-            raise ValueError("%s: %d videos x %d snippets unsupported (n*k in 1..64, fp32 model)" % (who, n, k))
-        ws = _workspace(nbytes, x.device, ("train", self.ws_slot))
-        stats = torch.empty(2, dtype=torch.float32, device=x.device)
-        desc = torch.empty((B, self.desc_dim), dtype=torch.float32, device=x.device)
-        _ffi.check(L.va_vgg16_train_step_consensus(self._h, _ffi.ptr(x), int(x.dtype == torch.uint8), _ffi.ptr(labels), n, k,
-                                                   float(lr), float(momentum), int(dropout_seed) & 0xFFFFFFFFFFFFFFFF,
-                                                   _ffi.ptr(desc), _ffi.ptr(stats), _ffi.ptr(ws), ws.numel(),
-                                                   _ffi.stream_ptr(self.device)))
-        return stats, desc
+        p = self._train_batch("train_step_consensus", x, labels, k)
+        _ffi.check(_ffi.lib().va_vgg16_train_step_consensus(
+            self._h, _ffi.ptr(p.x), p.is_u8, _ffi.ptr(p.labels), p.n, p.k, float(lr), float(momentum),
+            int(dropout_seed) & 0xFFFFFFFFFFFFFFFF, _ffi.ptr(p.desc), _ffi.ptr(p.stats), _ffi.ptr(p.ws), p.ws.numel(),
+            _ffi.stream_ptr(self.device)))
+        return p.stats, p.desc
 
     def train_step_multitask(self, x, labels, tasks, heads, k, lr, momentum, dropout_seed):
         """``train_step_consensus`` with one loss per dataset (multi-task learning, Sheet03/notes.txt:88-96):
@@ -344,36 +360,13 @@ class Vgg16Stream(object):
         descriptors): ``stats`` f32 ``[2+2H]`` = (loss, hits, loss of every head, hits of every head), ``descriptors``
         ``[n*k,D]``.  One head is ``train_step_consensus`` bit for bit.  Labels and tasks still on the host are checked here
         (ValueError); on the device a bad row gives a NaN loss."""
-        if not getattr(self, "_train_ready", False):
-            self.train_init()
-        who = "Vgg16Stream.train_step_multitask"
-        if not isinstance(x, torch.Tensor) or not x.is_cuda or x.dtype not in (torch.float32, torch.uint8):
-            raise ValueError("%s: x must be a CUDA float32/uint8 tensor" % who)
-        if x.dim() != 4 or tuple(x.shape[1:]) != (self.c_in, 224, 224):
-            raise ValueError("%s: x must be [n*k,%d,224,224], got %s" % (who, self.c_in, tuple(x.shape)))
-        self._on_my_device(x, "train_step_multitask")
-        check_heads(heads, self.n_classes, who)
-        heads = [int(h) for h in heads]
-        B, k = int(x.shape[0]), int(k)
-        if k < 1 or B < 1 or B % k:
-            raise ValueError("%s: %d images are not a whole number of videos of k=%d snippets" % (who, B, k))
-        n = B // k
-        labels, tasks = check_tasks(labels, tasks, heads, n, who)
-        labels = labels.to(device=x.device, dtype=torch.int64).contiguous()
-        tasks = tasks.to(device=x.device, dtype=torch.int32).contiguous()
-        x = x.contiguous()
-        L = _ffi.lib()
-        nbytes = L.va_vgg16_train_workspace_bytes(self._h, B)
-        if nbytes == 0:
-            raise ValueError("%s: %d videos x %d snippets unsupported (n*k in 1..64, fp32 model)" % (who, n, k))
-        ws = _workspace(nbytes, x.device, ("train", self.ws_slot))
-        stats = torch.empty(2 + 2 * len(heads), dtype=torch.float32, device=x.device)
-        desc = torch.empty((B, self.desc_dim), dtype=torch.float32, device=x.device)
-        _ffi.check(L.va_vgg16_train_step_multitask(self._h, _ffi.ptr(x), int(x.dtype == torch.uint8), _ffi.ptr(labels), _ffi.ptr(tasks),
-                                                   n, k, len(heads), (ctypes.c_int * len(heads))(*heads), float(lr), float(momentum),
-                                                   int(dropout_seed) & 0xFFFFFFFFFFFFFFFF, _ffi.ptr(desc), _ffi.ptr(stats),
-                                                   _ffi.ptr(ws), ws.numel(), _ffi.stream_ptr(self.device)))
-        return stats, desc
+        p = self._train_batch("train_step_multitask", x, labels, k, tasks, heads, multitask=True)
+        H = len(p.heads)
+        _ffi.check(_ffi.lib().va_vgg16_train_step_multitask(
+            self._h, _ffi.ptr(p.x), p.is_u8, _ffi.ptr(p.labels), _ffi.ptr(p.tasks), p.n, p.k, H, (ctypes.c_int * H)(*p.heads),
+            float(lr), float(momentum), int(dropout_seed) & 0xFFFFFFFFFFFFFFFF, _ffi.ptr(p.desc), _ffi.ptr(p.stats),
+            _ffi.ptr(p.ws), p.ws.numel(), _ffi.stream_ptr(self.device)))
+        return p.stats, p.desc
 
     # ---- the step in two halves: accumulate the gradient, then apply it (DESIGN.md S29, S30) ----
 
@@ -412,45 +405,16 @@ class Vgg16Stream(object):
         n_heads = 0
         if heads is not None:
             check_heads(heads, self.n_classes, who)
-            heads = [int(h) for h in heads]
             n_heads = len(heads)
         scales = check_scales(scales, max(n_heads, 1), who)
-        if not isinstance(x, torch.Tensor) or not x.is_cuda or x.dtype not in (torch.float32, torch.uint8):
-            raise ValueError("%s: x must be a CUDA float32/uint8 tensor" % who)
-        if x.dim() != 4 or tuple(x.shape[1:]) != (self.c_in, 224, 224):
-            raise ValueError("%s: x must be [B,%d,224,224], got %s" % (who, self.c_in, tuple(x.shape)))
-        self._on_my_device(x, "train_accumulate")
-        B = int(x.shape[0])
-        if B < 1 or B % max(k, 1):
-            raise ValueError("%s: %d images are not a whole number of videos of k=%d snippets" % (who, B, k))
-        n = B // max(k, 1)
-        if tasks is not None:
-            labels, tasks = check_tasks(labels, tasks, heads, n, who)
-            tasks = tasks.to(device=x.device, dtype=torch.int32).contiguous()
-        else:
-            _check_labels(labels, self.n_classes, who)
-            if not isinstance(labels, torch.Tensor):
-                raise ValueError("%s: labels must be a tensor [%d]" % (who, n))
-        labels = labels.to(device=x.device, dtype=torch.int64).contiguous()
-        if labels.dim() != 1 or labels.shape[0] != n:
-            raise ValueError("%s: labels must be [%d]" % (who, n))
-        if not getattr(self, "_train_ready", False):
-            self.train_init()
-        x = x.contiguous()
-        L = _ffi.lib()
-        nbytes = L.va_vgg16_train_workspace_bytes(self._h, B)
-        if nbytes == 0:
-            raise ValueError("%s: %d images unsupported (1..64 per micro-batch, fp32 model)" % (who, B))
+        p = self._train_batch("train_accumulate", x, labels, k, tasks, heads, multitask=tasks is not None, init_first=False)
         g = self.grad()
-        ws = _workspace(nbytes, x.device, ("train", self.ws_slot))
-        stats = torch.empty(2 + 2 * n_heads if n_heads else 2, dtype=torch.float32, device=x.device)
-        desc = torch.empty((B, self.desc_dim), dtype=torch.float32, device=x.device)
-        _ffi.check(L.va_vgg16_train_accumulate(
-            self._h, _ffi.ptr(x), int(x.dtype == torch.uint8), _ffi.ptr(labels), _ffi.ptr(tasks), n, k, n_heads,
-            (ctypes.c_int * n_heads)(*heads) if n_heads else None, (ctypes.c_float * len(scales))(*scales), int(bool(first)),
-            int(dropout_seed) & 0xFFFFFFFFFFFFFFFF, _ffi.ptr(desc), _ffi.ptr(stats), _ffi.ptr(g), g.numel(), _ffi.ptr(ws), ws.numel(),
-            _ffi.stream_ptr(self.device)))
-        return stats, desc
+        _ffi.check(_ffi.lib().va_vgg16_train_accumulate(
+            self._h, _ffi.ptr(p.x), p.is_u8, _ffi.ptr(p.labels), _ffi.ptr(p.tasks), p.n, p.k, n_heads,
+            (ctypes.c_int * n_heads)(*p.heads) if n_heads else None, (ctypes.c_float * len(scales))(*scales), int(bool(first)),
+            int(dropout_seed) & 0xFFFFFFFFFFFFFFFF, _ffi.ptr(p.desc), _ffi.ptr(p.stats), _ffi.ptr(g), g.numel(), _ffi.ptr(p.ws),
+            p.ws.numel(), _ffi.stream_ptr(self.device)))
+        return p.stats, p.desc
 
     def train_apply(self, lr, momentum, clip_norm=None):
         """The momentum-SGD update of every parameter from ``grad()`` (``va_vgg16_train_apply``):

@@ -410,6 +410,42 @@ int va_frames_prepare(va_ctx* ctx, const void* src, int n, int w, int h, int src
                       void* gray_out, void* workspace, size_t workspace_bytes, void* stream);
 
 /*
+ * Baseline JPEG decoding: n images of one size, component count and sampling, value for value what
+ * libjpeg's default decompressor gives (Huffman decode, the "islow" integer IDCT, "fancy" chroma upsampling, fixed-point
+ * YCbCr -> RGB).  The host parses the headers (video_analytics_amd/jpeg.py).  ncomp 1 (gray; hs = vs = 1) or 3 (YCbCr; luma
+ * sampling hs x vs of 1x1, 2x1 or 2x2, chroma 1x1); w, h in 3..65535 and the MCU-padded samples of one image, all components
+ * together (64 per 8x8 block), below 2^31 -- 4:2:0 up to about 37800 x 37800; anything else is VA_ERR_INVALID (a workspace of 0 bytes).
+ *   packed: DEVICE, 16-byte aligned, one upload:
+ *     image table    i32 [n][4]            {table set, first segment, segments, 0}
+ *     segment table  i32 [n_segments][8]   {image, byte offset into the data, bytes, first MCU, MCUs, 0, 0, 0}
+ *     table sets     [n_sets][8928 bytes]  quant u16 [3][64] in natural order, one table per component; then the Huffman tables
+ *                                          (DC, AC) of component 0, 1, 2, each 1424 bytes: look u16 [512] (length << 8 | symbol
+ *                                          for codes of up to 9 bits, 0 otherwise), maxcode i32 [18] (per length l the
+ *                                          largest l-bit value that is a code of length l or starts with a shorter code, so it
+ *                                          grows with l; -1 before the first code), valoff i32 [18] (index of a length's first
+ *                                          symbol minus its first code), vals u8 [256]
+ *     data           the segments' entropy-coded bytes, FF 00 un-stuffed, every segment from a multiple of 4
+ *   A segment is a restart interval, or a whole scan: DC prediction starts at 0 in each.
+ *   out: u8 [n][3][h][w] planar RGB, or u8 [n][h][w] for gray files; any alignment.
+ *   status: i32 [n], zeroed by the call; afterwards 0 for an image that decoded, else bits 1 (a code that is in no table), 2 (a
+ *   run past coefficient 63), 4 (the segment's bits ran out), 8 (a bad segment-table row).  A lane never reads outside its
+ *   segment nor writes outside its own blocks, whatever the bytes hold; the pixels of a failed image are unspecified.
+ *   workspace: DEVICE, 16-byte aligned, va_jpeg_decode_workspace_bytes(...) bytes (0: bad shape): the coefficients i16
+ *   [n][blocks][64] and, for colour files, the MCU-padded component planes; too small: VA_ERR_WORKSPACE.
+ * No allocation, no synchronisation; two memsets and three launches (two for gray files) on the caller's stream.
+ *   va_jpeg_idct      (testing entry point) the second launch alone: coef i16 [n][blocks][64], the blocks of an image per component
+ *                     in raster order (Y, Cb, Cr), times quant u16 [ncomp][64] -> dst: the planes u8 [n][blocks * 64] (Y, Cb, Cr, each
+ *                     MCU-padded), or u8 [n][h][w] for ncomp = 1.  32-bit arithmetic that wraps.
+ *   va_jpeg_upsample  (testing entry point) the third launch alone: such planes -> out u8 [n][3][h][w].
+ */
+size_t va_jpeg_decode_workspace_bytes(int n, int w, int h, int ncomp, int hs, int vs);
+int va_jpeg_decode(va_ctx* ctx, const void* packed, size_t packed_bytes, int n, int w, int h, int ncomp, int hs, int vs,
+                   int n_segments, int n_sets, void* out, void* status, void* workspace, size_t workspace_bytes, void* stream);
+int va_jpeg_idct(va_ctx* ctx, const void* coef, const void* quant, int n, int w, int h, int ncomp, int hs, int vs, void* dst,
+                 void* stream);
+int va_jpeg_upsample(va_ctx* ctx, const void* planes, int n, int w, int h, int hs, int vs, void* out, void* stream);
+
+/*
  * Mean flow subtraction, step one: flow f32 [n_pairs][2][h][w] -> means f32 [n_pairs][2], the mean of
  * every displacement field's component over the full frame.  Each value is clamped to [-32768, 32768] (a NaN becomes
  * -32768) and summed as the exact integer rint(a * 65536) in int64, so the result does not depend on the reduction

@@ -40,6 +40,7 @@ EXPORTS = [
     "va_frames_prepare_workspace_bytes", "va_frames_prepare",
     "va_flow_quantize_u8", "va_flowq_to_stack_snippets", "va_flowq_to_stack_resize",
     "va_solver_default", "va_vgg16_set_solver", "va_vgg16_get_solver", "va_train_dropout_p",
+    "va_jpeg_decode_workspace_bytes", "va_jpeg_decode", "va_jpeg_idct", "va_jpeg_upsample",
 ]
 
 
@@ -268,6 +269,14 @@ def lib():
     L.va_vgg16_get_solver.restype = ci
     L.va_train_dropout_p.argtypes = [vp, vp, sz, ctypes.c_ulonglong, ci, cf, vp]
     L.va_train_dropout_p.restype = ci
+    L.va_jpeg_decode_workspace_bytes.argtypes = [ci, ci, ci, ci, ci, ci]
+    L.va_jpeg_decode_workspace_bytes.restype = sz
+    L.va_jpeg_decode.argtypes = [vp, vp, sz, ci, ci, ci, ci, ci, ci, ci, ci, vp, vp, vp, sz, vp]
+    L.va_jpeg_decode.restype = ci
+    L.va_jpeg_idct.argtypes = [vp, vp, vp, ci, ci, ci, ci, ci, ci, vp, vp]
+    L.va_jpeg_idct.restype = ci
+    L.va_jpeg_upsample.argtypes = [vp, vp, ci, ci, ci, ci, ci, vp, vp]
+    L.va_jpeg_upsample.restype = ci
     _lib = L
     return L
 

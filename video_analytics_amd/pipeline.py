@@ -539,6 +539,23 @@ class TwoStreamPipeline(object):
             raise ValueError("%s: motion=%r / mean_flow=%r act on the float field; %s already quantised (store float32 flow for "
                              "them)" % (who, self.motion, self.mean_flow, uint8_flow_is))
 
+    def _decoded(self, video, who):
+        """A path to a Motion-JPEG AVI in the place of a video's rgb frames, alone or as ``(path, None)``
+        -> its frames u8 ``[T,3,H,W]`` in the same form, decoded on the pipeline's device on the current stream; anything else
+        comes back as it is.  This runs ahead of the other checks, which need the frames' shape: the file is parsed (ValueError
+        for a codec or a JPEG the decoder does not take), uploaded and decoded, and the decoder's status is read, one
+        synchronisation.  A path that brings gray frames raises ValueError: they are derived from the decoded frames."""
+        import os
+        pair = isinstance(video, (tuple, list)) and len(video) == 2
+        path = video[0] if pair else video
+        if not isinstance(path, (str, os.PathLike)):
+            return video
+        if pair and video[1] is not None:
+            raise ValueError("%s: a video given as a file's path comes without gray frames (gray=None)" % who)
+        from . import utils
+        frames = utils.loadVideoFrames(path, self.device)
+        return (frames, None) if pair else frames
+
     def _check_on_device(self, who, what, *tensors):
         """Every tensor is on the pipeline's device, or ValueError "<who>: <what> must be on <device>"."""
         if any(not isinstance(t, torch.Tensor) or not t.is_cuda or t.device != self.device for t in tensors):
@@ -587,8 +604,17 @@ class TwoStreamPipeline(object):
         ``mean_flow`` and the float gather and keeps the bits of the live call; a uint8 store goes through
         ``flow.flowq_to_stack_snippets``, needs ``mean_flow=False`` and keeps the bits too.  ``flow=`` with ``gray=``, a store
         of another type, shape, size or device and a uint8 store on a ``mean_flow`` pipeline raise ValueError before
-        anything is enqueued."""
+        anything is enqueued.
+
+        Motion-JPEG files: ``rgb`` may be the path of a Motion-JPEG AVI (with ``gray=None``); its frames
+        are decoded on the device on the current stream (``utils.loadVideoFrames``) and everything above follows.  Any
+        other codec raises ValueError naming it.  The decode comes FIRST, ahead of the checks above, which need the frames'
+        shape: with a path a bad argument is found only after the file was uploaded and decoded, and the call waits once on
+        the host for the decoder's status (a frame that does not decode raises ValueError) before it enqueues the rest --
+        ``evaluateVideos`` therefore runs ahead by less than a video when it is fed paths.  Decode with
+        ``utils.loadVideoFrames`` and pass the tensor where neither is wanted."""
         task = self._check_task(task, "submit_video")
+        rgb, gray = self._decoded((rgb, gray), "submit_video")
         stored = flow
         plan, rgb_views, flow_views, mode, fw, size = self._check_video(rgb, gray, n_snippets, views, consensus, fusion_weights,
                                                                        crops, rescale, stored)
@@ -926,8 +952,13 @@ class TwoStreamPipeline(object):
         The solver: ``solver=`` is one ``vgg.Solver`` for every stream, or one per stream in the order
         spatial, temporal, difference (TSN's dropout ratios differ per stream); each stream keeps it for later steps too
         (``Vgg16Stream.set_solver``).  None leaves the streams as they are.  Anything else raises ValueError before
-        anything is enqueued."""
-        videos = list(videos)
+        anything is enqueued.
+
+        Motion-JPEG files: an entry of ``videos`` may be the path of a Motion-JPEG AVI in the place of
+        ``rgb``, alone or as ``(path, None)``; its frames are decoded on the device first (``utils.loadVideoFrames``): ahead
+        of every check above, with one wait on the host per file for the decoder's status, so with paths a bad argument is
+        found only after the files were decoded."""
+        videos = [self._decoded(v, "train_videos") for v in videos]
         solvers = self._check_solver(solver)
         micro = self._check_accumulate(len(videos), int(k), micro_videos, clip_norm, data_parallel)
         c = self._check_train_videos(videos, labels, k, starts, crops, rng, tasks, micro, rescale, flows)

@@ -7,7 +7,8 @@ stack; they draw from Python's global ``random`` module in the same order as tha
 generation (crop top, crop left, flip, then the colour jitter's numbers: DESIGN.md S32).  Training bookkeeping (``makeCheckpoint``, ``savePerformance``) and
 frame extraction (``extractEveryNthFrame``, ``convertVideosToFrames``) are provided too; the reference decodes
 with ``cv2.VideoCapture``, absent here, so ``iterVideoFrames`` reads RIFF/AVI Motion-JPEG itself and refuses
-other codecs by name.
+other codecs by name; ``loadVideoFrames``, ``loadFrameImages`` and ``loadFlowImages(device=)`` decode
+the same JPEGs on the device.
 """
 from __future__ import division
 
@@ -58,13 +59,10 @@ def multiStepLr(baseLr, milestones, lastEpoch, gamma=0.1):
     return baseLr * gamma ** bisect.bisect_right(sorted(milestones), lastEpoch)
 
 
-def iterVideoFrames(videoLoc):
-    """Decoded frames (PIL RGB images) of a video file, in order.  The reference decodes with ``cv2.VideoCapture``
-    (Sheet03/utils.py:57-68); OpenCV is not in this image, so the container is parsed here: RIFF/AVI with
-    Motion-JPEG streams (``MJPG``: every ``##dc`` / ``##db`` chunk of the ``movi`` list is one JPEG, decoded with
-    PIL).  Any other codec (UCF-101 ships XviD) raises ValueError naming its fourcc: there is no decoder for it
-    here."""
-    import io
+def videoJpegs(videoLoc):
+    """The JPEG byte strings of a video file's frames, in order: RIFF/AVI with Motion-JPEG streams (``MJPG``: every
+    ``##dc`` / ``##db`` chunk of the ``movi`` list is one JPEG).  Any other codec (UCF-101 ships XviD) raises ValueError
+    naming its fourcc: there is no decoder for it here."""
     import struct
     with open(videoLoc, "rb") as f:
         data = f.read()
@@ -85,14 +83,52 @@ def iterVideoFrames(videoLoc):
         raise ValueError("iterVideoFrames: %s has no movi list" % videoLoc)
     end = k - 4 + 8 + struct.unpack("<I", data[k - 4:k])[0]
     k += 4
+    jpegs = []
     while k + 8 <= min(end, len(data)):
         cid, size = data[k:k + 4], struct.unpack("<I", data[k + 4:k + 8])[0]
         if cid == b"LIST":  # 'rec ' groups: descend
             k += 12
             continue
         if cid[2:4] in (b"dc", b"db") and size > 0:
-            yield Image.open(io.BytesIO(data[k + 8:k + 8 + size])).convert("RGB")
+            jpegs.append(data[k + 8:k + 8 + size])
         k += 8 + size + (size & 1)
+    return jpegs
+
+
+def iterVideoFrames(videoLoc):
+    """Decoded frames (PIL RGB images) of a video file, in order.  The reference decodes with ``cv2.VideoCapture``
+    (Sheet03/utils.py:57-68); OpenCV is not in this image, so the container is parsed here (``videoJpegs``: RIFF/AVI with
+    Motion-JPEG streams) and every frame is decoded with PIL.  Any other codec raises ValueError naming its fourcc."""
+    import io
+    for jpg in videoJpegs(videoLoc):
+        yield Image.open(io.BytesIO(jpg)).convert("RGB")
+
+
+def loadVideoFrames(videoLoc, device):
+    """The frames of a Motion-JPEG AVI decoded on the device -> uint8 ``[T,3,H,W]``, the stack of what
+    ``iterVideoFrames`` yields, bit for bit: what ``run_video(rgb, rescale=..., views=...)``, ``extract_flow`` and
+    ``train_videos`` take.  Gray frames come back with three equal channels, as ``convert("RGB")`` gives them.  ValueError as
+    ``videoJpegs``, for a file without frames, and as ``jpeg.decode_jpegs``."""
+    from . import jpeg
+    jpegs = videoJpegs(videoLoc)
+    if not jpegs:
+        raise ValueError("loadVideoFrames: %s holds no frames" % videoLoc)
+    out, _ = jpeg.decode_jpegs(jpegs, device)
+    return out if out.dim() == 4 else out.unsqueeze(1).repeat(1, 3, 1, 1)
+
+
+def loadFrameImages(paths, device):
+    """The numbered frame files ``convertVideosToFrames`` wrote (or any baseline JPEG files of one size) decoded on the
+    device in one call -> uint8 ``[N,3,H,W]``, or ``[N,H,W]`` for gray files, PIL's pixels bit for bit.
+    ValueError for a missing file and as ``jpeg.decode_jpegs``."""
+    from . import jpeg
+    datas = []
+    for p in paths:
+        if not os.path.isfile(p):
+            raise ValueError("loadFrameImages: missing %s" % p)
+        with open(p, "rb") as f:
+            datas.append(f.read())
+    return jpeg.decode_jpegs(datas, device)[0]
 
 
 def extractEveryNthFrame(videoLoc, N):
@@ -198,39 +234,70 @@ def flowToImages(flow, bound=20.0):
     return np.rint(np.clip(t, 0.0, 255.0)).astype(np.uint8)
 
 
-def saveFlowImages(flow, flowDir, bound=20.0, firstIndex=1, quality=95):
+def saveFlowImages(flow, flowDir, bound=20.0, firstIndex=1, quality=95, restartBlocks=None):
     """Write the flow of the N consecutive pairs of one video as the files the reference reads:
     ``flow_x_%04d.jpg`` / ``flow_y_%04d.jpg``, 1-based, single-channel 'L' JPEGs
-    (Sheet03/temporalModel.py:78-81, Sheet03/parameters.py:38-39).  Returns the file count."""
+    (Sheet03/temporalModel.py:78-81, Sheet03/parameters.py:38-39).  Returns the file count.  ``restartBlocks``: PIL's
+    ``restart_marker_blocks``, a restart marker every so many 8x8 blocks, so that the device decoder works on every image
+    with more than one lane; None writes the files without restart markers, byte for byte as before."""
     from PIL import Image
     from .parameters import FRAME_EXTN, X_PREFIX_FLOW, Y_PREFIX_FLOW
     checkAndMakeDirectories(flowDir)
     q = flowToImages(flow, bound)
+    extra = {} if restartBlocks is None else {"restart_marker_blocks": int(restartBlocks)}
     for k in range(q.shape[0]):
         for prefix, plane in ((X_PREFIX_FLOW, 0), (Y_PREFIX_FLOW, 1)):
             Image.fromarray(q[k, plane], mode="L").save(os.path.join(flowDir, flowFileName(prefix, firstIndex + k, FRAME_EXTN)),
-                                                         quality=quality)
+                                                         quality=quality, **extra)
     return 2 * q.shape[0]
 
 
-def loadFlowImages(flowDir, first=1, count=None):
-    """The reader of what ``saveFlowImages`` and the reference's flow directory hold: ``flow_x_%04d.jpg`` /
-    ``flow_y_%04d.jpg`` from index ``first`` (1-based) on -> uint8 numpy ``[N,2,H,W]``, plane 0 x and plane 1 y, a uint8
-    stored flow once on the device (DESIGN.md S39).  ``count``: how many pairs to read; None reads on until an index has
-    neither file.  ValueError for a missing file, images of different sizes and an image that is not single-channel 'L'."""
-    from PIL import Image
+def _flowImagePaths(flowDir, first, count):
+    """Yields the ``[x path, y path]`` pairs ``loadFlowImages`` reads, in order; ValueError for a bad ``count`` and, when its
+    pair is reached, for a missing file."""
     from .parameters import FRAME_EXTN, X_PREFIX_FLOW, Y_PREFIX_FLOW
     first = int(first)
     if count is not None and int(count) < 1:
         raise ValueError("loadFlowImages: count must be >= 1, got %r" % (count,))
-    fields, k = [], first
+    seen, k = False, first
     while count is None or k < first + int(count):
         paths = [os.path.join(flowDir, flowFileName(prefix, k, FRAME_EXTN)) for prefix in (X_PREFIX_FLOW, Y_PREFIX_FLOW)]
         there = [os.path.isfile(p) for p in paths]
-        if count is None and not any(there) and fields:
+        if count is None and not any(there) and seen:
             break
         if not all(there):
             raise ValueError("loadFlowImages: missing %s" % paths[there.index(False)])
+        yield paths
+        seen, k = True, k + 1
+
+
+def loadFlowImages(flowDir, first=1, count=None, device=None):
+    """The reader of what ``saveFlowImages`` and the reference's flow directory hold: ``flow_x_%04d.jpg`` /
+    ``flow_y_%04d.jpg`` from index ``first`` (1-based) on -> uint8 numpy ``[N,2,H,W]``, plane 0 x and plane 1 y, a uint8
+    stored flow once on the device (DESIGN.md S39).  ``count``: how many pairs to read; None reads on until an index has
+    neither file.  ValueError for a missing file, images of different sizes and an image that is not single-channel 'L'.
+
+    ``device``: decode all ``2 N`` images on that device in one call -> a uint8 tensor ``[N,2,H,W]``
+    there, the same bytes and the same ValueErrors; files outside the decoder's subset raise ValueError too."""
+    from PIL import Image
+    if device is not None:
+        from . import jpeg
+        hdrs = []
+        for paths in _flowImagePaths(flowDir, first, count):
+            for p in paths:
+                with open(p, "rb") as f:
+                    hdr = jpeg.parse_jpeg(f.read())
+                if len(hdr["components"]) != 1:
+                    raise ValueError("loadFlowImages: %s has %d components, not the single-channel 'L' of flow images"
+                                     % (p, len(hdr["components"])))
+                if hdrs and (hdr["width"], hdr["height"]) != (hdrs[0]["width"], hdrs[0]["height"]):
+                    raise ValueError("loadFlowImages: %s is %dx%d, not the size of the images before it"
+                                     % (paths[0], hdr["width"], hdr["height"]))
+                hdrs.append(hdr)
+        out, _ = jpeg.decode_jpegs(hdrs, device)
+        return out.view(len(hdrs) // 2, 2, out.shape[1], out.shape[2])
+    fields = []
+    for paths in _flowImagePaths(flowDir, first, count):
         planes = []
         for p in paths:
             with Image.open(p) as img:
@@ -241,7 +308,6 @@ def loadFlowImages(flowDir, first=1, count=None):
             raise ValueError("loadFlowImages: %s is %dx%d, not the size of the images before it"
                              % (paths[0], planes[1].shape[1], planes[1].shape[0]))
         fields.append(np.stack(planes))
-        k += 1
     return np.stack(fields)
 
 

@@ -138,7 +138,10 @@ def evaluateVideos(pipe, videos, labels, flows=None, **kw):
 
     Stored flow: ``flows`` is an iterable parallel to ``videos``, one stored flow per video
     (``TwoStreamPipeline.extract_flow``), handed to ``submit_video(flow=)``: no TV-L1 runs, and the videos come without gray
-    frames.  Fewer or more stored flows than videos raise ValueError."""
+    frames.  Fewer or more stored flows than videos raise ValueError.
+
+    Motion-JPEG files: an entry of ``videos`` may be the path of a Motion-JPEG AVI; ``submit_video``
+    decodes its frames on the device."""
     labels = [int(l) for l in labels]
     stored = iter(flows) if flows is not None else None
     missing = object()

@@ -109,6 +109,11 @@ def test_status_names_the_image_whose_bytes_ran_out():
 
 @pytest.mark.parametrize("w,h,ncomp,hs,vs", [(37, 19, 1, 1, 1), (40, 24, 1, 1, 1), (53, 37, 3, 2, 2), (30, 19, 3, 2, 1), (17, 8, 3, 1, 1)])
 def test_idct_launch_equals_the_host_model(w, h, ncomp, hs, vs):
+    """The out-of-domain test: blocks of +-1023 times the step 255 are coefficients no 8-bit samples give, and
+    the sums wrap at 32 bits.  PIL is deliberately not the judge here: libjpeg's SIMD and C IDCTs give different pixels for
+    such blocks (measured on the host: they differ from each other as much as from this model), so there is no libjpeg
+    value to equal; the kernel is held to the host model's C "islow" arithmetic with 32-bit wrap and a clamp.  Inside the
+    domain PIL judges: tests/test_jpeg_streams_gpu.py, the basis images and the magnitudes."""
     from video_analytics_amd import jpeg
     geo = jpeg.layout(w, h, ncomp, hs, vs)
     rs = np.random.RandomState(w * h)

@@ -3,6 +3,12 @@
 // splits the entropy-coded bytes at the restart markers (video_analytics_amd/jpeg.py); three launches follow: Huffman decode
 // with one lane per segment, dequantisation + the "islow" integer IDCT with one lane per 8x8 block, and for colour files the
 // "fancy" chroma upsampling + the fixed-point YCbCr -> RGB.  Integer work only.
+//
+// The domain of "value for value" (DESIGN.md S47): every block whose dequantised coefficients are the quantised DCT of some
+// 8x8 block of 8-bit samples -- what an encoder writes.  The 64 basis sign images at quality 100, 95 and 50 sit at its edge
+// and are held to PIL (tests/test_jpeg_streams_*.py).  Outside it libjpeg's own builds disagree with each other (its SIMD
+// IDCT against its C one; measured on the host, see S47), so there is nothing to equal: the device follows the C "islow"
+// arithmetic with sums that wrap at 32 bits and a clamp to 0..255, which tests/test_jpeg_gpu.py holds to the host model.
 #include "va_internal.h"
 
 #include <cstdint>

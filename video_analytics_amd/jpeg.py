@@ -7,6 +7,20 @@ lane per segment, dequantisation + the "islow" integer IDCT, "fancy" chroma upsa
 ``decode_jpegs_host`` states the same decoder in numpy and plain Python integers; the tests hold it to PIL and the kernels
 to it.  Baseline files only: one Huffman-coded scan of 8-bit samples, gray or YCbCr 4:4:4 / 4:2:2 / 4:2:0; everything else
 raises ValueError from ``parse_jpeg``, before anything touches the device.
+
+The domain of "value for value" (DESIGN.md S47).  The decoders here equal libjpeg wherever each block's dequantised
+coefficients are the quantised DCT of some 8x8 block of 8-bit samples, which is what an encoder writes; any entropy coding
+of them (tables, restarts, runs, ZRL, symbols libjpeg reads as EOB) is inside.  Outside -- coefficients no pixels give -- the
+builds of libjpeg do not agree with each other, so there is no value to equal; device and host model then follow the C
+"islow" arithmetic with sums that wrap at 32 bits and a clamp to 0..255.  Measured on the host (PIL 12.2.0 with
+libjpeg-turbo, x86-64; nothing of it on a GPU), host model against PIL with its SIMD IDCT / against PIL with the SIMD turned
+off (``JSIMD_FORCENONE=1``, libjpeg-turbo's C IDCT), pixels that differ: 63 AC coefficients of +1023 at step 1, 4 / 9 of 64;
+63 random +-1023 at step 1 in four blocks, 40 / 117 of 256; +-200 at step 8, 78 / 145 of 256; a lone DC of +-2047 at step
+4, 0 / 64 of 64; the two builds differ from each other in 11, 121, 165 and 64 of those pixels.  One coefficient of 1023
+anywhere agrees with both, sixteen of them with the SIMD build only.  The C IDCT limits its range through a table indexed
+by the low 10 bits, which wraps past +-512; the SIMD one is supposed (not verified) to differ through the 16-bit
+intermediates of its first pass and its saturating packs.  Every case of tests/golden/jpeg_streams.npz decodes alike under
+both builds.
 """
 import re
 import struct
@@ -376,7 +390,9 @@ def _idct_pass(a, sh):
 
 def idct_blocks(coef, quant, counters=None):
     """coef int16 [..., 64] (natural order) times quant [64] (or broadcastable) -> uint8 [..., 8, 8]: dequantisation, the
-    column pass with a descale by 11 bits, the row pass with a descale by 18, + 128, clamped."""
+    column pass with a descale by 11 bits, the row pass with a descale by 18, + 128, clamped.  libjpeg's values for the
+    quantised DCT of 8-bit samples; beyond those (the module docstring) the sums wrap at 32 bits and the clamp is a true
+    clamp, which no build of libjpeg promises."""
     c = (np.asarray(coef).astype(np.int32) * np.asarray(quant).astype(np.int32)).reshape(np.shape(coef)[:-1] + (8, 8))
     ws = np.swapaxes(_idct_pass(np.swapaxes(c, -1, -2), 11), -1, -2)  # per column
     out = _idct_pass(ws, 18) + 128                                    # per row
@@ -463,7 +479,8 @@ def _status_error(who, i, status):
 
 def decode_jpegs_host(datas, counters=None):
     """The whole decoder on the host, in numpy and plain Python integers: a list of JPEG files (bytes) of one size and format
-    -> uint8 ``[n,3,h,w]``, or ``[n,h,w]`` for gray files -- what ``decode_jpegs`` gives, and PIL.  ``counters``: a dict that
+    -> uint8 ``[n,3,h,w]``, or ``[n,h,w]`` for gray files -- what ``decode_jpegs`` gives, and PIL wherever the coefficients
+    are ones 8-bit samples give (the module docstring states that domain and what holds outside it).  ``counters``: a dict that
     collects what the decode met (``long_codes``, codes longer than ``LOOK_BITS``; ``zrl``; ``eob``; ``max_dc_category``;
     ``clip_low`` / ``clip_high``, IDCT outputs below 0 / above 255).  ValueError as ``parse_jpeg`` and ``decode_jpegs``."""
     counters = {} if counters is None else counters
@@ -569,7 +586,9 @@ def launch(packed, shape, nseg, nsets, out, status):
 
 def decode_jpegs(datas, device, out=None, check=True):
     """A list of baseline JPEG files (bytes) -> ``(pixels, status)`` on ``device``: pixels uint8 ``[n,3,h,w]`` planar RGB, or
-    ``[n,h,w]`` for gray files, PIL's values bit for bit; status int32 ``[n]``, 0 for every image that
+    ``[n,h,w]`` for gray files, PIL's values bit for bit for every file whose blocks hold the quantised DCT
+    of 8-bit samples -- any file an encoder wrote; for coefficients outside that, where libjpeg's builds differ among
+    themselves, the values of ``decode_jpegs_host`` (the module docstring); status int32 ``[n]``, 0 for every image that
     decoded (the bits: ``STATUS_*``).  All images of one call share the size, the component count and the sampling; their
     tables may differ.  One pinned staging buffer and one upload carry everything; the call is ordered on the current stream.
 

@@ -446,6 +446,42 @@ int va_jpeg_idct(va_ctx* ctx, const void* coef, const void* quant, int n, int w,
 int va_jpeg_upsample(va_ctx* ctx, const void* planes, int n, int w, int h, int hs, int vs, void* out, void* stream);
 
 /*
+ * Baseline JPEG encoding: n images of one size -> the entropy-coded scan of each, byte for byte what libjpeg's
+ * default compressor writes between SOS and EOI (jccolor's fixed-point RGB -> YCbCr, h2v1 / h2v2 downsampling without smoothing,
+ * the "islow" integer forward DCT, quantisation rounding half away from zero, Huffman coding, restart markers).  The host writes
+ * the headers around it (video_analytics_amd/jpeg.py).  Shapes as va_jpeg_decode; restart: the restart interval in MCUs, 0 for
+ * none, at most 65535; the bound below of one image stays below 2^31.  Anything else is VA_ERR_INVALID (a workspace of 0 bytes).
+ *   images: DEVICE, u8 [n][h][w] (ncomp = 1) or planar RGB u8 [n][3][h][w]; any alignment.
+ *   tables: DEVICE, 16-byte aligned, 2560 bytes, one upload: quant u16 [3][64] in natural order, one table per component; then
+ *           the Huffman codes of luma and of chroma, each DC u32 [16] and AC u32 [256] indexed by symbol: length << 16 | code,
+ *           0 for a symbol the table does not hold.
+ *   out: DEVICE, out_bytes bytes: the scans back to back, image i from the sum of lengths[0..i).  One image takes at most
+ *        2 U + 2 (intervals - 1) bytes with U = ceil(blocks * 1658 / 8) + intervals: a block codes to at most 20 bits of DC and
+ *        63 x 26 bits of AC, every interval ends with up to 7 fill bits, stuffing at most doubles it, and an RSTm of two bytes
+ *        stands between intervals.  With n times that nothing is ever cut short; an image that would end behind out_bytes is
+ *        not written at all and gets status bit 2.
+ *   lengths: i32 [n], the bytes of every scan.  status: i32 [n], zeroed by the call; bit 1: a coefficient outside the baseline
+ *        categories (a DC difference above 11 bits, an AC value above 10) or a symbol without a code, which is left out of the
+ *        scan (the image's bytes are then no valid file; its neighbours' are untouched); bit 2: the image did not fit.
+ *   workspace: DEVICE, 16-byte aligned, va_jpeg_encode_workspace_bytes(...) bytes (0: bad shape): the un-stuffed scans and
+ *        the interval marks (U rounded up to 16, each), and the coefficients i16 [n][blocks][64]; too small: VA_ERR_WORKSPACE.
+ * No allocation, no synchronisation; two memsets and four launches on the caller's stream; one workgroup per image in the
+ * entropy stage, none waiting for another, and bytes that depend on no launch shape or timing.
+ *   va_jpeg_fdct            (testing entry point) the first launch alone: images -> coef i16 [n][blocks][64], the decoder's
+ *                           layout (va_jpeg_idct); coef 16-byte aligned.  Only the quant part of tables is read.
+ *   va_jpeg_entropy_encode  (testing entry point) the other three: any coef of that layout -> out, lengths, status; the
+ *                           workspace as above (its front part is used).  Only the Huffman part of tables is read.
+ */
+size_t va_jpeg_encode_workspace_bytes(int n, int w, int h, int ncomp, int hs, int vs, int restart);
+int va_jpeg_encode(va_ctx* ctx, const void* images, int n, int w, int h, int ncomp, int hs, int vs, int restart, const void* tables,
+                   void* out, size_t out_bytes, void* lengths, void* status, void* workspace, size_t workspace_bytes, void* stream);
+int va_jpeg_fdct(va_ctx* ctx, const void* images, const void* tables, int n, int w, int h, int ncomp, int hs, int vs, void* coef,
+                 void* stream);
+int va_jpeg_entropy_encode(va_ctx* ctx, const void* coef, const void* tables, int n, int w, int h, int ncomp, int hs, int vs, int restart,
+                           void* out, size_t out_bytes, void* lengths, void* status, void* workspace, size_t workspace_bytes,
+                           void* stream);
+
+/*
  * Mean flow subtraction, step one: flow f32 [n_pairs][2][h][w] -> means f32 [n_pairs][2], the mean of
  * every displacement field's component over the full frame.  Each value is clamped to [-32768, 32768] (a NaN becomes
  * -32768) and summed as the exact integer rint(a * 65536) in int64, so the result does not depend on the reduction

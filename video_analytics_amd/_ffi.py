@@ -41,6 +41,7 @@ EXPORTS = [
     "va_flow_quantize_u8", "va_flowq_to_stack_snippets", "va_flowq_to_stack_resize",
     "va_solver_default", "va_vgg16_set_solver", "va_vgg16_get_solver", "va_train_dropout_p",
     "va_jpeg_decode_workspace_bytes", "va_jpeg_decode", "va_jpeg_idct", "va_jpeg_upsample",
+    "va_jpeg_encode_workspace_bytes", "va_jpeg_encode", "va_jpeg_fdct", "va_jpeg_entropy_encode",
 ]
 
 
@@ -277,6 +278,14 @@ def lib():
     L.va_jpeg_idct.restype = ci
     L.va_jpeg_upsample.argtypes = [vp, vp, ci, ci, ci, ci, ci, vp, vp]
     L.va_jpeg_upsample.restype = ci
+    L.va_jpeg_encode_workspace_bytes.argtypes = [ci, ci, ci, ci, ci, ci, ci]
+    L.va_jpeg_encode_workspace_bytes.restype = sz
+    L.va_jpeg_encode.argtypes = [vp, vp, ci, ci, ci, ci, ci, ci, ci, vp, vp, sz, vp, vp, vp, sz, vp]
+    L.va_jpeg_encode.restype = ci
+    L.va_jpeg_fdct.argtypes = [vp, vp, vp, ci, ci, ci, ci, ci, ci, vp, vp]
+    L.va_jpeg_fdct.restype = ci
+    L.va_jpeg_entropy_encode.argtypes = [vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, vp, sz, vp, vp, vp, sz, vp]
+    L.va_jpeg_entropy_encode.restype = ci
     _lib = L
     return L
 

@@ -23,7 +23,6 @@ constexpr int kJpegImgInts = 4;           // image table row: {table set, first 
 constexpr int kJpegSegInts = 8;           // segment table row: {image, byte offset, bytes, first MCU, MCUs, 0, 0, 0}
 constexpr int kJpegEntropyThreads = 64;
 constexpr int kJpegThreads = 256;
-constexpr long long kJpegMaxSamples = 0x7fffffffLL;  // MCU-padded samples of one image, all components (jpeg.MAX_SAMPLES)
 
 enum { kJpegBadCode = 1, kJpegBadRun = 2, kJpegOutOfBits = 4, kJpegBadSegment = 8 };
 
@@ -31,42 +30,6 @@ enum { kJpegBadCode = 1, kJpegBadRun = 2, kJpegOutOfBits = 4, kJpegBadSegment = 
 __constant__ unsigned char kJpegZigzag[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
                                               41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
                                               30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
-
-// The block grid of one image.  A gray file is one component of 1x1 blocks per MCU; a colour file has hs x vs luma blocks and
-// one block of each chroma component per MCU.  Blocks are kept per component in raster order: luma first, then Cb, then Cr.
-struct jpeg_geom {
-    int w, h, ncomp, hs, vs;
-    int mw, mh;      // MCUs across and down
-    int bwY, bhY;    // luma blocks across and down (MCU-padded)
-    int bwC, bhC;    // chroma blocks across and down
-    int nbY, nbC;    // blocks per luma / chroma component
-    int blocks;      // blocks per image
-    int plane_bytes; // the MCU-padded component planes of one image: Y, then Cb, then Cr
-};
-
-bool jpeg_shape_ok(int n, int w, int h, int ncomp, int hs, int vs)
-{
-    if (n < 1 || w < 3 || h < 3 || w > 65535 || h > 65535) return false;
-    if (ncomp == 1 ? !(hs == 1 && vs == 1) : !(ncomp == 3 && ((hs == 1 && vs == 1) || (hs == 2 && vs == 1) || (hs == 2 && vs == 2))))
-        return false;
-    // the MCU-padded samples of one image (64 per block, all components) stay below 2^31: every count of jpeg_geom is an int
-    const long long mw = (w + 8 * hs - 1) / (8 * hs), mh = (h + 8 * vs - 1) / (8 * vs);
-    const long long blocks = mw * mh * (hs * vs + (ncomp == 3 ? 2 : 0));
-    return blocks * 64 <= kJpegMaxSamples;
-}
-
-jpeg_geom jpeg_make_geom(int w, int h, int ncomp, int hs, int vs)
-{
-    jpeg_geom g{};
-    g.w = w, g.h = h, g.ncomp = ncomp, g.hs = hs, g.vs = vs;
-    g.mw = va_cdiv(w, 8 * hs), g.mh = va_cdiv(h, 8 * vs);
-    g.bwY = g.mw * hs, g.bhY = g.mh * vs;
-    g.bwC = ncomp == 3 ? g.mw : 0, g.bhC = ncomp == 3 ? g.mh : 0;
-    g.nbY = g.bwY * g.bhY, g.nbC = g.bwC * g.bhC;
-    g.blocks = g.nbY + 2 * g.nbC;
-    g.plane_bytes = g.blocks * 64;
-    return g;
-}
 
 size_t jpeg_coef_bytes(int n, const jpeg_geom& g) { return va_align_up((size_t)n * g.blocks * 128, 256); }
 
@@ -383,13 +346,6 @@ __global__ void __launch_bounds__(kJpegThreads) k_jpeg_color(const unsigned char
                 if (k >= first && k < last) p[k] = (unsigned char)px[c][k];
         }
     }
-}
-
-// workgroups of a launch of `threads` lanes; 0 when one launch cannot hold them
-long long jpeg_grid(long long lanes, int threads)
-{
-    const long long b = (lanes + threads - 1) / threads;
-    return b <= 0x7fffffffLL ? b : 0;
 }
 
 int jpeg_launch_idct(const short* coef, const int* img_table, const unsigned char* sets, int nsets, int n, const jpeg_geom& g,

@@ -81,3 +81,50 @@ enum {
 };
 static inline size_t va_align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 static inline int va_cdiv(int a, int b) { return (a + b - 1) / b; }
+
+// ---- baseline JPEG (jpeg.hip decodes, jpeg_encode.hip encodes): the block grid both speak about
+
+constexpr long long kJpegMaxSamples = 0x7fffffffLL;  // MCU-padded samples of one image, all components (jpeg.MAX_SAMPLES)
+
+// The block grid of one image.  A gray file is one component of 1x1 blocks per MCU; a colour file has hs x vs luma blocks and
+// one block of each chroma component per MCU.  Blocks are kept per component in raster order: luma first, then Cb, then Cr.
+struct jpeg_geom {
+    int w, h, ncomp, hs, vs;
+    int mw, mh;      // MCUs across and down
+    int bwY, bhY;    // luma blocks across and down (MCU-padded)
+    int bwC, bhC;    // chroma blocks across and down
+    int nbY, nbC;    // blocks per luma / chroma component
+    int blocks;      // blocks per image
+    int plane_bytes; // the MCU-padded component planes of one image: Y, then Cb, then Cr
+};
+
+static inline bool jpeg_shape_ok(int n, int w, int h, int ncomp, int hs, int vs)
+{
+    if (n < 1 || w < 3 || h < 3 || w > 65535 || h > 65535) return false;
+    if (ncomp == 1 ? !(hs == 1 && vs == 1) : !(ncomp == 3 && ((hs == 1 && vs == 1) || (hs == 2 && vs == 1) || (hs == 2 && vs == 2))))
+        return false;
+    // the MCU-padded samples of one image (64 per block, all components) stay below 2^31: every count of jpeg_geom is an int
+    const long long mw = (w + 8 * hs - 1) / (8 * hs), mh = (h + 8 * vs - 1) / (8 * vs);
+    const long long blocks = mw * mh * (hs * vs + (ncomp == 3 ? 2 : 0));
+    return blocks * 64 <= kJpegMaxSamples;
+}
+
+static inline jpeg_geom jpeg_make_geom(int w, int h, int ncomp, int hs, int vs)
+{
+    jpeg_geom g{};
+    g.w = w, g.h = h, g.ncomp = ncomp, g.hs = hs, g.vs = vs;
+    g.mw = va_cdiv(w, 8 * hs), g.mh = va_cdiv(h, 8 * vs);
+    g.bwY = g.mw * hs, g.bhY = g.mh * vs;
+    g.bwC = ncomp == 3 ? g.mw : 0, g.bhC = ncomp == 3 ? g.mh : 0;
+    g.nbY = g.bwY * g.bhY, g.nbC = g.bwC * g.bhC;
+    g.blocks = g.nbY + 2 * g.nbC;
+    g.plane_bytes = g.blocks * 64;
+    return g;
+}
+
+// workgroups of a launch of `threads` lanes; 0 when one launch cannot hold them
+static inline long long jpeg_grid(long long lanes, int threads)
+{
+    const long long b = (lanes + threads - 1) / threads;
+    return b <= 0x7fffffffLL ? b : 0;
+}

@@ -21,6 +21,12 @@ anywhere agrees with both, sixteen of them with the SIMD build only.  The C IDCT
 by the low 10 bits, which wraps past +-512; the SIMD one is supposed (not verified) to differ through the 16-bit
 intermediates of its first pass and its saturating packs.  Every case of tests/golden/jpeg_streams.npz decodes alike under
 both builds.
+
+Encoding is the way back: ``encode_jpegs`` runs ``va_jpeg_encode`` -- colour conversion, downsampling,
+the "islow" forward DCT and quantisation with one lane per block, then Huffman coding, byte stuffing and restart markers with
+one workgroup per image -- and writes PIL's headers around the scans; ``encode_jpegs_host`` states the same encoder in numpy
+and plain Python integers.  Both give, byte for byte, the file ``Image.save`` writes: libjpeg's baseline compressor is integer
+arithmetic throughout, so there is one value to equal everywhere.
 """
 import re
 import struct
@@ -652,3 +658,416 @@ def upsample_planes(planes, w, h, hs, vs):
     _ffi.check(_ffi.lib().va_jpeg_upsample(_ffi.ctx(planes.device.index), _ffi.ptr(planes), n, w, h, hs, vs, _ffi.ptr(out),
                                            _ffi.stream_ptr(planes.device)))
     return out
+
+
+# ------------------------------------------------------------------------------------------------ the encoder on the host
+
+# Annex K.1 of the JPEG standard in natural order: the tables libjpeg scales by the quality
+STD_QUANT = (
+    (16, 11, 10, 16, 24, 40, 51, 61, 12, 12, 14, 19, 26, 58, 60, 55, 14, 13, 16, 24, 40, 57, 69, 56, 14, 17, 22, 29, 51, 87, 80, 62,
+     18, 22, 37, 56, 68, 109, 103, 77, 24, 35, 55, 64, 81, 104, 113, 92, 49, 64, 78, 87, 103, 121, 120, 101, 72, 92, 95, 98, 112,
+     100, 103, 99),
+    (17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 24, 26, 56, 99, 99, 99, 99, 99, 47, 66, 99, 99, 99, 99, 99, 99,
+     99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99))
+
+ENC_STATUS_RANGE, ENC_STATUS_FIT = 1, 2  # bits of the encoder's per-image status
+_ENC_STATUS_TEXT = ((ENC_STATUS_RANGE, "a coefficient outside the baseline categories (DC difference above 11 bits, AC above 10)"),
+                    (ENC_STATUS_FIT, "the scan did not fit the output buffer"))
+ENC_TABLE_BYTES = 384 + 2 * (16 + 256) * 4  # quant u16[3][64]; then (DC u32[16], AC u32[256]) of luma and of chroma (include/va.h)
+BLOCK_BITS = 20 + 63 * 26                   # the most one block codes to: a DC code + value, 63 AC codes + values
+_SUBSAMPLING = {0: (1, 1), 1: (2, 1), 2: (2, 2)}  # PIL's keyword -> the luma sampling factors
+
+
+def quant_tables(quality):
+    """libjpeg's ``jpeg_set_quality(quality, force_baseline=TRUE)`` -> ``(luma, chroma)``, uint16 [64] in natural order:
+    Annex K's tables times ``5000 / q`` percent below 50 and ``200 - 2 q`` from there, each entry ``(base * scale + 50) / 100``
+    clamped to 1..255.  ValueError outside 1..100."""
+    if isinstance(quality, bool) or not isinstance(quality, (int, np.integer)) or not 1 <= quality <= 100:
+        raise ValueError("quant_tables: quality must be an integer in 1..100, got %r" % (quality,))
+    q = int(quality)
+    scale = 5000 // q if q < 50 else 200 - 2 * q
+    return tuple(np.clip((np.asarray(t, dtype=np.int64) * scale + 50) // 100, 1, 255).astype(np.uint16) for t in STD_QUANT)
+
+
+def huffman_codes(bits, vals):
+    """(bits [16], values) of one DHT table -> uint32 [256] indexed by symbol: ``length << 16 | code``, 0 for a symbol the
+    table does not hold."""
+    out = np.zeros(256, dtype=np.uint32)
+    code = k = 0
+    for l in range(1, 17):
+        for _ in range(bits[l - 1]):
+            out[vals[k]] = (l << 16) | code
+            code, k = code + 1, k + 1
+        code <<= 1
+    return out
+
+
+def encode_tables(quant, huffman=STD_HUFFMAN):
+    """The encoder's one table block on the device (include/va.h), ``ENC_TABLE_BYTES`` bytes: ``quant`` (luma, chroma) as
+    u16 [3][64] per component, then the codes of the (DC, AC) tables of luma and of chroma, ``huffman_codes``'s form."""
+    q = np.stack([quant[0], quant[1], quant[1]]).astype(np.uint16)
+    parts = [q.tobytes()]
+    for th in (0, 1):
+        parts.append(huffman_codes(*huffman[(0, th)])[:16].tobytes())
+        parts.append(huffman_codes(*huffman[(1, th)]).tobytes())
+    blob = b"".join(parts)
+    assert len(blob) == ENC_TABLE_BYTES
+    return blob
+
+
+def rgb_to_ycc(rgb):
+    """jccolor.c's 16-bit fixed point: uint8 [3, h, w] -> int64 [3, h, w] (Y, Cb, Cr)."""
+    r, g, b = (rgb[c].astype(np.int64) for c in range(3))
+    y = (19595 * r + 38470 * g + 7471 * b + 32768) >> 16
+    cb = (-11059 * r - 21709 * g + 32768 * b + (128 << 16) + 32767) >> 16
+    cr = (32768 * r - 27439 * g - 5329 * b + (128 << 16) + 32767) >> 16
+    return np.stack([y, cb, cr])
+
+
+def _clamp_take(a, rows, cols):
+    """``a`` [h, w] extended to ``rows`` x ``cols`` by repeating its last row and column."""
+    return a[np.minimum(np.arange(rows), a.shape[0] - 1)][:, np.minimum(np.arange(cols), a.shape[1] - 1)]
+
+
+def component_plane(full, hs, vs, chroma):
+    """One component at full resolution int64 [h, w] -> its samples on the grid of its real blocks, [8 hb, 8 wb]: columns
+    repeated at full resolution up to the blocks' width, rows only up to a multiple of ``vs``; then the downsampling
+    (h2v1 with bias 0, 1, ..., h2v2 with 1, 2, ... along every output row); then the last downsampled row repeated."""
+    h, w = full.shape
+    fh, fv = (hs, vs) if chroma else (1, 1)
+    wb, hb = -(-w // (8 * fh)), -(-h // (8 * fv))
+    a = _clamp_take(full, -(-h // fv) * fv, wb * 8 * fh)
+    if fh == 2:
+        x = np.arange(wb * 8)
+        if fv == 2:
+            a = (a[0::2, 0::2] + a[0::2, 1::2] + a[1::2, 0::2] + a[1::2, 1::2] + 1 + (x & 1)) >> 2
+        else:
+            a = (a[:, 0::2] + a[:, 1::2] + (x & 1)) >> 1
+    return _clamp_take(a, hb * 8, a.shape[1])
+
+
+def _fdct_pass(d, first):
+    """One 8-point pass of jfdctint's "islow" forward DCT along the last axis of an int64 array."""
+    t0, t7, t1, t6 = d[..., 0] + d[..., 7], d[..., 0] - d[..., 7], d[..., 1] + d[..., 6], d[..., 1] - d[..., 6]
+    t2, t5, t3, t4 = d[..., 2] + d[..., 5], d[..., 2] - d[..., 5], d[..., 3] + d[..., 4], d[..., 3] - d[..., 4]
+    t10, t13, t11, t12 = t0 + t3, t0 - t3, t1 + t2, t1 - t2
+    sh = 11 if first else 15
+
+    def ds(x, n):
+        return (x + (1 << (n - 1))) >> n
+    o = [None] * 8
+    o[0], o[4] = ((t10 + t11) << 2, (t10 - t11) << 2) if first else (ds(t10 + t11, 2), ds(t10 - t11, 2))
+    z1 = (t12 + t13) * 4433
+    o[2], o[6] = ds(z1 + t13 * 6270, sh), ds(z1 - t12 * 15137, sh)
+    z1, z2, z3, z4 = t4 + t7, t5 + t6, t4 + t6, t5 + t7
+    z5 = (z3 + z4) * 9633
+    t4, t5, t6, t7 = t4 * 2446, t5 * 16819, t6 * 25172, t7 * 12299
+    z1, z2, z3, z4 = z1 * -7373, z2 * -20995, z3 * -16069 + z5, z4 * -3196 + z5
+    o[7], o[5], o[3], o[1] = ds(t4 + z1 + z3, sh), ds(t5 + z2 + z4, sh), ds(t6 + z2 + z3, sh), ds(t7 + z1 + z4, sh)
+    return np.stack(o, axis=-1)
+
+
+def fdct_blocks(px, quant):
+    """Samples [..., 8, 8] -> the quantised coefficients int64 [..., 64] in natural order: ``jfdct_islow`` on samples - 128
+    (rows, then columns; the output is scaled by 8), divided by ``8 q`` rounding half away from zero."""
+    d = _fdct_pass(np.asarray(px).astype(np.int64) - 128, True)
+    d = np.swapaxes(_fdct_pass(np.swapaxes(d, -1, -2), False), -1, -2)
+    c = d.reshape(d.shape[:-2] + (64,))
+    q = np.asarray(quant).astype(np.int64)
+    return np.sign(c) * ((np.abs(c) + 4 * q) // (8 * q))
+
+
+def _scan_order(geo, hs, vs, ncomp, m):
+    """(component, block index within ``layout``'s array) of the blocks of MCU ``m``, in the order they are coded."""
+    my, mx = divmod(m, geo["mcu_w"])
+    if ncomp == 1:
+        return [(0, m)]
+    out = [(0, (my * vs + v) * geo["blocks_w"][0] + mx * hs + u) for v in range(vs) for u in range(hs)]
+    return out + [(c, geo["block_base"][c] + m) for c in (1, 2)]
+
+
+def encode_coefficients(img, quant, hs, vs, counters=None):
+    """One image uint8 [h, w] or [3, h, w] -> int16 [blocks, 64] in ``layout``'s order, the quantised coefficients libjpeg
+    codes: colour conversion, edge padding, downsampling, forward DCT, quantisation; a dummy block (on the MCU-padded grid
+    but outside the component's real blocks) holds zero AC and the DC of the block before it in the MCU's own order."""
+    nc = 1 if img.ndim == 2 else 3
+    h, w = img.shape[-2:]
+    geo = layout(w, h, nc, hs, vs)
+    comps = [img.astype(np.int64)] if nc == 1 else list(rgb_to_ycc(img))
+    coef = np.zeros((geo["blocks"], 64), dtype=np.int64)
+    for c, full in enumerate(comps):
+        p = component_plane(full, hs, vs, c > 0)
+        hb, wb = p.shape[0] // 8, p.shape[1] // 8
+        blk = fdct_blocks(p.reshape(hb, 8, wb, 8).transpose(0, 2, 1, 3), quant[min(c, 1)])
+        grid = coef[geo["block_base"][c]:geo["block_base"][c] + geo["blocks_w"][c] * geo["blocks_h"][c]]
+        grid.reshape(geo["blocks_h"][c], geo["blocks_w"][c], 64)[:hb, :wb] = blk
+        if c == 0 and (wb < geo["blocks_w"][0] or hb < geo["blocks_h"][0]):
+            for m in range(geo["mcu_w"] * geo["mcu_h"]):
+                order = _scan_order(geo, hs, vs, nc, m)[:hs * vs]
+                for k, (_, at) in enumerate(order):
+                    by, bx = divmod(at, geo["blocks_w"][0])
+                    if bx >= wb or by >= hb:
+                        coef[at] = 0
+                        coef[at, 0] = coef[order[k - 1][1], 0]
+                        if counters is not None:
+                            counters["dummy_blocks"] = counters.get("dummy_blocks", 0) + 1
+    return coef.astype(np.int16)
+
+
+def _category(v):
+    return int(abs(int(v))).bit_length()
+
+
+def entropy_encode_host(coef, w, h, ncomp, hs, vs, restart=0, huffman=STD_HUFFMAN, counters=None):
+    """int16 [blocks, 64] (``layout``'s order) -> the scan's bytes: Huffman coding in MCU order with the DC predictors reset at
+    every restart interval, every interval filled up to a whole byte with 1-bits, FF stuffed to FF 00, ``RSTm`` between
+    intervals.  ValueError for a coefficient outside the baseline categories."""
+    counters = {} if counters is None else counters
+    geo = layout(w, h, ncomp, hs, vs)
+    codes = {key: huffman_codes(*spec) for key, spec in huffman.items()}
+    mcus = geo["mcu_w"] * geo["mcu_h"]
+    interval = restart or mcus
+    out = bytearray()
+    for first in range(0, mcus, interval):
+        acc = nbits = 0
+        pred = [0, 0, 0]
+
+        def put(cls, th, sym, value, size):
+            nonlocal acc, nbits
+            e = int(codes[(cls, th)][sym])
+            if e == 0:
+                raise ValueError("encode_jpegs_host: " + _ENC_STATUS_TEXT[0][1])
+            v = value if value >= 0 else value + (1 << size) - 1
+            acc = (((acc << (e >> 16)) | (e & 0xFFFF)) << size) | v
+            nbits += (e >> 16) + size
+        for m in range(first, min(first + interval, mcus)):
+            for c, at in _scan_order(geo, hs, vs, ncomp, m):
+                th = min(c, 1)
+                zz = [int(v) for v in coef[at][ZIGZAG]]
+                diff = zz[0] - pred[c]
+                pred[c] = zz[0]
+                s = _category(diff)
+                if s > 11:
+                    raise ValueError("encode_jpegs_host: " + _ENC_STATUS_TEXT[0][1])
+                counters["max_dc_category"] = max(counters.get("max_dc_category", 0), s)
+                put(0, th, s, diff, s)
+                run = 0
+                for k in range(1, 64):
+                    if zz[k] == 0:
+                        run += 1
+                        continue
+                    while run > 15:
+                        put(1, th, 0xF0, 0, 0)
+                        counters["zrl"] = counters.get("zrl", 0) + 1
+                        run -= 16
+                    s = _category(zz[k])
+                    if s > 10:
+                        raise ValueError("encode_jpegs_host: " + _ENC_STATUS_TEXT[0][1])
+                    counters["max_ac_category"] = max(counters.get("max_ac_category", 0), s)
+                    put(1, th, run << 4 | s, zz[k], s)
+                    run = 0
+                if run:
+                    put(1, th, 0, 0, 0)
+                    counters["eob"] = counters.get("eob", 0) + 1
+                    if run == 63 and diff == 0:
+                        counters["zero_blocks"] = counters.get("zero_blocks", 0) + 1
+                else:
+                    counters["no_eob"] = counters.get("no_eob", 0) + 1
+        pad = -nbits % 8
+        plain = (((acc << pad) | ((1 << pad) - 1)).to_bytes((nbits + pad) // 8, "big"))
+        counters["segments"] = counters.get("segments", 0) + 1
+        counters.setdefault("padding", []).append(pad)
+        counters["stuffed"] = counters.get("stuffed", 0) + plain.count(b"\xff")
+        if first:
+            out += bytes([0xFF, 0xD0 + (first // interval - 1) % 8])
+        out += plain.replace(b"\xff", b"\xff\x00")
+    return bytes(out)
+
+
+def jpeg_header(w, h, ncomp, hs, vs, quant, restart=0, huffman=STD_HUFFMAN):
+    """Everything PIL writes in front of the scan: SOI, APP0 "JFIF" 1.01 (units 0, density 1x1, no thumbnail), one DQT per
+    table, SOF0, one DHT per table in the order DC0, AC0, DC1, AC1, DRI when ``restart`` is not 0, SOS."""
+    def seg(m, payload):
+        return bytes([0xFF, m]) + struct.pack(">H", len(payload) + 2) + payload
+    out = b"\xff\xd8" + seg(0xE0, b"JFIF\x00\x01\x01\x00\x00\x01\x00\x01\x00\x00")
+    for t in range(1 if ncomp == 1 else 2):
+        out += seg(0xDB, bytes([t]) + bytes(int(v) for v in np.asarray(quant[t])[ZIGZAG]))
+    sof = struct.pack(">BHHB", 8, h, w, ncomp)
+    for c in range(ncomp):
+        sof += bytes([c + 1, (hs << 4 | vs) if c == 0 and ncomp == 3 else 0x11, min(c, 1)])
+    out += seg(0xC0, sof)
+    for th in range(1 if ncomp == 1 else 2):
+        for cls in (0, 1):
+            bits, vals = huffman[(cls, th)]
+            out += seg(0xC4, bytes([cls << 4 | th]) + bytes(bits) + bytes(vals))
+    if restart:
+        out += seg(0xDD, struct.pack(">H", restart))
+    sos = bytes([ncomp]) + b"".join(bytes([c + 1, min(c, 1) * 0x11]) for c in range(ncomp)) + b"\x00\x3f\x00"
+    return out + seg(0xDA, sos)
+
+
+def _encode_args(who, shape, quality, subsampling, restart_blocks):
+    """The checks every encoder shares -> ``(n, w, h, ncomp, hs, vs, restart, quant)``; ValueError for a rank other than 3 or
+    4, a size below 3x3 or above 65535, a bad quality or subsampling and a restart interval outside 0..65535."""
+    if len(shape) not in (3, 4) or (len(shape) == 4 and shape[1] != 3) or shape[0] < 1:
+        raise ValueError("%s: images must be [n,h,w] (gray) or [n,3,h,w] (RGB) with n >= 1, got %s" % (who, list(shape)))
+    h, w = int(shape[-2]), int(shape[-1])
+    if not (3 <= w <= 65535 and 3 <= h <= 65535):
+        raise ValueError("%s: %dx%d is outside the sizes 3x3 .. 65535x65535" % (who, w, h))
+    quant = quant_tables(quality)
+    ncomp = 1 if len(shape) == 3 else 3
+    if isinstance(subsampling, bool) or subsampling not in _SUBSAMPLING:
+        raise ValueError("%s: subsampling must be 0 (4:4:4), 1 (4:2:2) or 2 (4:2:0), got %r" % (who, subsampling))
+    hs, vs = _SUBSAMPLING[subsampling] if ncomp == 3 else (1, 1)
+    restart = 0 if restart_blocks is None else restart_blocks
+    if isinstance(restart, bool) or not isinstance(restart, (int, np.integer)) or not 0 <= restart <= 65535:
+        raise ValueError("%s: restart_blocks must be an integer of at most 65535 MCUs per interval, got %r" % (who, restart_blocks))
+    geo = layout(w, h, ncomp, hs, vs)
+    if geo["plane_bytes"] > MAX_SAMPLES:
+        raise ValueError("%s: %dx%d holds %d samples in its MCUs, more than the %d one image may have"
+                         % (who, w, h, geo["plane_bytes"], MAX_SAMPLES))
+    return int(shape[0]), w, h, ncomp, hs, vs, int(restart), quant
+
+
+def encode_jpegs_host(images, quality=95, subsampling=2, restart_blocks=None, counters=None):
+    """The whole encoder on the host, in numpy and plain Python integers: uint8 ``[n,h,w]`` (gray) or ``[n,3,h,w]`` (planar
+    RGB) -> a list of n files (bytes), byte for byte what ``Image.fromarray(...).save(f, "JPEG", quality=, subsampling=,
+    restart_marker_blocks=)`` writes and what ``encode_jpegs`` gives.  ``counters``: a dict that collects what the encode met:
+    ``stuffed`` (FF bytes), ``zrl``, ``eob``, ``no_eob`` (blocks whose coefficient 63 is not zero), ``zero_blocks`` (blocks of
+    a DC difference of 0 and no AC), ``max_dc_category``, ``max_ac_category``, ``segments`` (restart intervals),
+    ``dummy_blocks`` and ``padding``, the fill bits of every interval.  ValueError as ``encode_jpegs``."""
+    images = np.asarray(images)
+    if images.dtype != np.uint8:
+        raise ValueError("encode_jpegs_host: images must be uint8, got %s" % images.dtype)
+    n, w, h, nc, hs, vs, restart, quant = _encode_args("encode_jpegs_host", images.shape, quality, subsampling, restart_blocks)
+    head = jpeg_header(w, h, nc, hs, vs, quant, restart)
+    return [head + entropy_encode_host(encode_coefficients(images[i], quant, hs, vs, counters), w, h, nc, hs, vs, restart,
+                                       counters=counters) + b"\xff\xd9" for i in range(n)]
+
+
+# ------------------------------------------------------------------------------------------------ the encoder on the device
+
+def scan_bound(w, h, ncomp, hs, vs, restart=0):
+    """The most bytes the scan of one image takes (include/va.h): every block at ``BLOCK_BITS``, one byte of fill per
+    interval, all of it stuffed, and two bytes of ``RSTm`` between intervals."""
+    geo = layout(w, h, ncomp, hs, vs)
+    mcus = geo["mcu_w"] * geo["mcu_h"]
+    intervals = -(-mcus // restart) if restart else 1
+    return 2 * (-(-geo["blocks"] * BLOCK_BITS // 8) + intervals) + 2 * (intervals - 1)
+
+
+def _enc_status_error(who, i, status):
+    return ValueError("%s: image %d did not encode: %s" % (who, i, ", ".join(t for bit, t in _ENC_STATUS_TEXT if status & bit)))
+
+
+def _enc_workspace(shape, restart, device):
+    import torch
+    from . import _ffi
+    nbytes = int(_ffi.lib().va_jpeg_encode_workspace_bytes(*shape, restart))
+    if nbytes == 0:
+        raise ValueError("encode_jpegs: %d images of %dx%d are more than one call encodes" % shape[:3])
+    return torch.empty(nbytes, dtype=torch.uint8, device=device), nbytes
+
+
+def _scans(out, lengths, status, who, check):
+    """One synchronisation for the lengths (and the status), one download of the bytes in use -> a list of scans."""
+    ls = lengths.cpu().numpy().astype(np.int64)
+    bad = status.cpu().numpy()
+    if check and bad.any():
+        i = int(np.flatnonzero(bad)[0])
+        raise _enc_status_error(who, i, int(bad[i]))
+    ends = np.cumsum(ls)
+    data = out[:int(ends[-1])].cpu().numpy().tobytes()
+    return [b"" if bad[i] & ENC_STATUS_FIT else data[int(e - l):int(e)] for i, (l, e) in enumerate(zip(ls, ends))]
+
+
+def encode_buffers(shape, restart, device):
+    """What one ``va_jpeg_encode`` call of ``shape = (n, w, h, ncomp, hs, vs)`` fills -> ``(out, lengths, status, work)``:
+    the output sized by ``scan_bound``, so that nothing is ever cut short, and the call's own workspace."""
+    import torch
+    n = shape[0]
+    work, _ = _enc_workspace(shape, restart, device)
+    return (torch.empty(n * scan_bound(*shape[1:], restart), dtype=torch.uint8, device=device),
+            torch.empty(n, dtype=torch.int32, device=device), torch.empty(n, dtype=torch.int32, device=device), work)
+
+
+def encode_launch(images, shape, restart, tables, out, lengths, status, work):
+    """``va_jpeg_encode`` on the current stream: two memsets and four launches, nothing waits."""
+    from . import _ffi
+    device = images.device
+    _ffi.check(_ffi.lib().va_jpeg_encode(_ffi.ctx(device.index), _ffi.ptr(images), *shape, restart, _ffi.ptr(tables), _ffi.ptr(out),
+                                         out.numel(), _ffi.ptr(lengths), _ffi.ptr(status), _ffi.ptr(work), work.numel(),
+                                         _ffi.stream_ptr(device)))
+
+
+def encode_jpegs(images, quality=95, subsampling=2, restart_blocks=None, check=True):
+    """A contiguous CUDA uint8 tensor ``[n,h,w]`` (gray) or ``[n,3,h,w]`` (planar RGB), the shapes ``decode_jpegs`` returns ->
+    a list of n baseline JPEG files (bytes), byte for byte what ``Image.fromarray(...).save(f, "JPEG", quality=,
+    subsampling=, restart_marker_blocks=)`` writes.  ``subsampling``: PIL's 0 / 1 / 2 for 4:4:4, 4:2:2,
+    4:2:0, ignored for gray (a gray file is the one PIL writes without the keyword); ``restart_blocks``: PIL's
+    ``restart_marker_blocks``, the restart interval in MCUs (None or 0: none).  Standard Huffman tables, no ``optimize``, no progressive files, no custom tables, density or comments.
+
+    The tables go up in one block, the kernels run on the current stream into a buffer sized by the bound of the shape (nothing
+    is ever cut short), one synchronisation reads the lengths and one download brings every scan; the host writes the headers
+    around them.  ``check=True`` raises ValueError naming the first image whose status is not 0 (``ENC_STATUS_*``: pixels
+    give no such image); with ``check=False`` such an image comes back as it is.  ValueError before anything touches the
+    device for a tensor that is not a contiguous CUDA uint8 one of those shapes, a size below 3x3 or above 65535, a bad
+    quality or subsampling and more than 65535 MCUs per interval."""
+    import torch
+    if not isinstance(images, torch.Tensor) or images.dtype != torch.uint8:
+        raise ValueError("encode_jpegs: images must be a uint8 tensor, got %s"
+                         % (images.dtype if isinstance(images, torch.Tensor) else type(images).__name__))
+    n, w, h, nc, hs, vs, restart, quant = _encode_args("encode_jpegs", tuple(images.shape), quality, subsampling, restart_blocks)
+    if images.device.type != "cuda" or not images.is_contiguous():
+        raise ValueError("encode_jpegs: images must be contiguous and on a CUDA device, got %s on %s"
+                         % ("a contiguous tensor" if images.is_contiguous() else "a strided view", images.device))
+    device, shape = images.device, (n, w, h, nc, hs, vs)
+    with torch.cuda.device(device):
+        bufs = encode_buffers(shape, restart, device)
+        encode_launch(images, shape, restart, upload(encode_tables(quant), device), *bufs)
+        scans = _scans(*bufs[:3], "encode_jpegs", check)
+    head = jpeg_header(w, h, nc, hs, vs, quant, restart)
+    return [head + s + b"\xff\xd9" for s in scans]
+
+
+def fdct_coefficients(images, quant, hs=1, vs=1):
+    """The first launch alone (``va_jpeg_fdct``, a testing entry point): images as ``encode_jpegs`` takes them and ``quant``
+    (luma, chroma) -> coef int16 ``[n, blocks, 64]`` on the device in ``layout``'s order, dummy blocks included."""
+    import torch
+    from . import _ffi
+    n, w, h, nc, hs, vs, _, _ = _encode_args("fdct_coefficients", tuple(images.shape), 50, {(1, 1): 0, (2, 1): 1, (2, 2): 2}.get((hs, vs)), None)
+    if images.dtype != torch.uint8 or not images.is_contiguous() or images.device.type != "cuda":
+        raise ValueError("fdct_coefficients: images must be a contiguous CUDA uint8 tensor")
+    device = images.device
+    with torch.cuda.device(device):
+        tables = upload(encode_tables(quant), device)
+        coef = torch.empty((n, layout(w, h, nc, hs, vs)["blocks"], 64), dtype=torch.int16, device=device)
+        _ffi.check(_ffi.lib().va_jpeg_fdct(_ffi.ctx(device.index), _ffi.ptr(images), _ffi.ptr(tables), n, w, h, nc, hs, vs,
+                                           _ffi.ptr(coef), _ffi.stream_ptr(device)))
+    return coef
+
+
+def entropy_encode(coef, w, h, ncomp, hs, vs, restart=0, huffman=STD_HUFFMAN, check=True, out_bytes=None):
+    """The entropy stage alone (``va_jpeg_entropy_encode``, a testing entry point): coef int16 ``[n, blocks, 64]`` on the
+    device in ``layout``'s order, whatever it holds -> ``(scans, status)``, the list of n scans (bytes; empty for an image
+    that did not fit) and the status as a numpy array.  ``out_bytes``: the size of the output buffer, by default n times
+    ``scan_bound``."""
+    import torch
+    from . import _ffi
+    geo = layout(w, h, ncomp, hs, vs)
+    n = int(coef.shape[0])
+    if coef.dtype != torch.int16 or tuple(coef.shape) != (n, geo["blocks"], 64) or not coef.is_contiguous() or n < 1:
+        raise ValueError("entropy_encode: coef must be int16 [n,%d,64]" % geo["blocks"])
+    device, shape = coef.device, (n, w, h, ncomp, hs, vs)
+    dummy = (np.ones(64, dtype=np.uint16),) * 2
+    with torch.cuda.device(device):
+        work, nbytes = _enc_workspace(shape, restart, device)
+        tables = upload(encode_tables(dummy, huffman), device)
+        out = torch.empty(n * scan_bound(w, h, ncomp, hs, vs, restart) if out_bytes is None else int(out_bytes), dtype=torch.uint8, device=device)
+        lengths = torch.empty(n, dtype=torch.int32, device=device)
+        status = torch.empty(n, dtype=torch.int32, device=device)
+        _ffi.check(_ffi.lib().va_jpeg_entropy_encode(_ffi.ctx(device.index), _ffi.ptr(coef), _ffi.ptr(tables), *shape, restart,
+                                                     _ffi.ptr(out), out.numel(), _ffi.ptr(lengths), _ffi.ptr(status), _ffi.ptr(work),
+                                                     nbytes, _ffi.stream_ptr(device)))
+        scans = _scans(out, lengths, status, "entropy_encode", check)
+    return scans, status.cpu().numpy()

@@ -143,11 +143,31 @@ def extractEveryNthFrame(videoLoc, N):
     return frameList
 
 
-def convertVideosToFrames(rootDir, saveDir, videoListLoc, sampleRate=VIDEO_FRAME_SAMPLE_RATE, mode="train"):
+def saveFrameImages(frames, frameDir, quality=95, restartBlocks=None):
+    """Write a uint8 ``[T,3,H,W]`` device tensor (what ``loadVideoFrames`` returns) as the numbered frame files
+    ``frameDir/0.jpg, 1.jpg, ...`` that ``SpatialDataset.__getitem__`` opens: one ``jpeg.encode_jpegs`` call on the device
+    (DESIGN.md S49-S52), 4:2:0 like PIL's default, byte for byte the files ``Image.save(..., quality=quality)`` writes.
+    ``restartBlocks``: a restart marker every so many MCUs, which the device decoder reads with one lane per interval.
+    Returns the file count; ValueError as ``jpeg.encode_jpegs`` and for a tensor that is not ``[T,3,H,W]``."""
+    from . import jpeg
+    if not isinstance(frames, torch.Tensor) or frames.dim() != 4 or frames.shape[1] != 3:
+        raise ValueError("saveFrameImages: frames must be a uint8 tensor [T,3,H,W]")
+    files = jpeg.encode_jpegs(frames, quality=quality, subsampling=2, restart_blocks=restartBlocks)
+    checkAndMakeDirectories(frameDir)
+    for i, data in enumerate(files):
+        with open(os.path.join(frameDir, str(i) + FRAME_EXTN), "wb") as f:
+            f.write(data)
+    return len(files)
+
+
+def convertVideosToFrames(rootDir, saveDir, videoListLoc, sampleRate=VIDEO_FRAME_SAMPLE_RATE, mode="train", device=None):
     """Sheet03/utils.py:95-121: every ``sampleRate``-th frame of each listed video goes to
     ``saveDir/<category>/<videoName>/<i>.jpg`` (i = 0, 1, ... counts the SAMPLED frames: the names
     ``SpatialDataset.__getitem__`` opens, Sheet03/spatialModel.py:75-77).  A video whose frame directory already
-    exists is skipped, like in the reference (it takes an existing directory as 'frames written already')."""
+    exists is skipped, like in the reference (it takes an existing directory as 'frames written already').
+
+    ``device``: decode every video there (``loadVideoFrames``) and write its sampled frames with ``saveFrameImages``: the
+    same files byte for byte (the device decodes PIL's pixels and encodes PIL's bytes), and no pixel visits the host."""
     if not rootDir.endswith("/"):
         rootDir = rootDir + "/"
     if not saveDir.endswith("/"):
@@ -158,6 +178,11 @@ def convertVideosToFrames(rootDir, saveDir, videoListLoc, sampleRate=VIDEO_FRAME
             videoLoc = rootDir + videoLoc
             frameDir = saveDir + actionCategory + "/" + videoName
             if all(checkAndMakeDirectories(frameDir)):
+                continue
+            if device is not None:
+                if not (os.path.exists(videoLoc) and os.path.isfile(videoLoc)):
+                    raise ValueError("Video does not exist: %s" % (videoLoc))
+                saveFrameImages(loadVideoFrames(videoLoc, device)[::sampleRate].contiguous(), frameDir, quality=95)
                 continue
             frameList = extractEveryNthFrame(videoLoc, sampleRate)
             for i in range(len(frameList)):
@@ -239,7 +264,8 @@ def saveFlowImages(flow, flowDir, bound=20.0, firstIndex=1, quality=95, restartB
     ``flow_x_%04d.jpg`` / ``flow_y_%04d.jpg``, 1-based, single-channel 'L' JPEGs
     (Sheet03/temporalModel.py:78-81, Sheet03/parameters.py:38-39).  Returns the file count.  ``restartBlocks``: PIL's
     ``restart_marker_blocks``, a restart marker every so many 8x8 blocks, so that the device decoder works on every image
-    with more than one lane; None writes the files without restart markers, byte for byte as before."""
+    with more than one lane; None writes the files without restart markers, byte for byte as before.
+    ``saveFlowImagesDevice`` writes the same files without bringing the flow to the host."""
     from PIL import Image
     from .parameters import FRAME_EXTN, X_PREFIX_FLOW, Y_PREFIX_FLOW
     checkAndMakeDirectories(flowDir)
@@ -250,6 +276,30 @@ def saveFlowImages(flow, flowDir, bound=20.0, firstIndex=1, quality=95, restartB
             Image.fromarray(q[k, plane], mode="L").save(os.path.join(flowDir, flowFileName(prefix, firstIndex + k, FRAME_EXTN)),
                                                          quality=quality, **extra)
     return 2 * q.shape[0]
+
+
+def saveFlowImagesDevice(flow, flowDir, device, bound=20.0, firstIndex=1, quality=95, restartBlocks=None):
+    """``saveFlowImages`` on ``device``, the mirror of ``loadFlowImages(device=)``: a float32 flow
+    ``[N,2,H,W]`` is quantised there (``flow.quantize_flow``), a uint8 one (a stored flow) is taken as it is, all ``2 N``
+    planes are encoded in one ``jpeg.encode_jpegs`` call, and the files ``saveFlowImages`` writes for the same flow,
+    ``quality`` and ``restartBlocks`` come out byte for byte.  (A function of its own: the signature of ``saveFlowImages``
+    is held by the tests as it stands.)  Returns the file count; ValueError for another dtype or shape and as
+    ``jpeg.encode_jpegs``."""
+    from . import flow as vflow
+    from . import jpeg
+    from .parameters import FRAME_EXTN, X_PREFIX_FLOW, Y_PREFIX_FLOW
+    t = flow if isinstance(flow, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(flow))
+    if t.dim() != 4 or t.shape[1] != 2 or t.dtype not in (torch.float32, torch.uint8):
+        raise ValueError("saveFlowImagesDevice: flow must be float32 or uint8 [N,2,H,W], got %s %s" % (t.dtype, list(t.shape)))
+    t = t.to(device).contiguous()
+    q = t if t.dtype == torch.uint8 else vflow.quantize_flow(t, bound)
+    files = jpeg.encode_jpegs(q.view(2 * q.shape[0], q.shape[2], q.shape[3]), quality=quality, restart_blocks=restartBlocks)
+    checkAndMakeDirectories(flowDir)
+    for i, data in enumerate(files):
+        name = flowFileName((X_PREFIX_FLOW, Y_PREFIX_FLOW)[i % 2], firstIndex + i // 2, FRAME_EXTN)
+        with open(os.path.join(flowDir, name), "wb") as f:
+            f.write(data)
+    return len(files)
 
 
 def _flowImagePaths(flowDir, first, count):

@@ -34,6 +34,8 @@
  *                     inputs of the two-stream paper (no reference counterpart).
  *   va_flow_homography, va_flow_compensate   warped optical flow, TSN's camera-compensated temporal input
  *                     (Sheet03/notes.txt:187-194; no reference code): DESIGN.md S21, S22.
+ *   va_frames_warp_pairs   the same in TSN's own two-pass form: the second frame of every pair warped by the fitted
+ *                     homography for a second va_tvl1_flow (no reference code): DESIGN.md S53, S54.
  *   va_flow_quantize_u8, va_flowq_to_stack_snippets, va_flowq_to_stack_resize   stored optical flow: the flow images the
  *                     reference reads are computed once (Sheet03/temporalModel.py:76-81, Sheet03/parameters.py:27), as
  *                     TSN's are (Sheet03/notes.txt:196-199, 245-250); these keep them on the device: DESIGN.md S39-S41.
@@ -522,6 +524,25 @@ int va_flow_homography(va_ctx* ctx, const void* flow, int n_fields, int w, int h
  * bits.  At most 65535 fields per call.
  */
 int va_flow_compensate(va_ctx* ctx, const void* flow, int n_fields, int w, int h, const void* H, void* out, void* stream);
+
+/*
+ * Warped optical flow in TSN's two-pass form, the warp: the frame pairs of TV-L1's input with every
+ * second frame resampled under the pair's homography, so that a second va_tvl1_flow finds the motion that is left when
+ * the camera's is gone.  frames: u8 or f32 [n_seq][frames_per_seq][h][w] (frames_per_seq >= 2), va_tvl1_flow's own input;
+ * H: DEVICE f64 [N][3][3], N = n_seq * (frames_per_seq - 1), H[n] mapping the coordinates of frame k to those of frame
+ * k + 1 for pair n = s * (frames_per_seq - 1) + k (va_tvl1_flow's pair order; what va_flow_homography fits);
+ * pairs: f32 [N][2][h][w], va_tvl1_flow input again: N sequences of two frames.
+ *   pairs[n][0] = (float) frame k.
+ *   pairs[n][1](y, x): (X, Y, D) = H[n] (x, y, 1)^T in float64, left to right, no fused multiply-add; px = X/D, py = Y/D.
+ *   Inside (D > 0 and 0 <= px <= w-1 and 0 <= py <= h-1; a NaN is outside): x0 = floor(px), ax = (float)(px - x0),
+ *   x1 = min(x0 + 1, w-1), rows likewise, and with the four values A B / C D of frame k + 1 as floats, in float32 without
+ *   fused multiply-add: t = A + ax*(B-A), b = C + ax*(D-C), value = t + ay*(b-t).  It is not rounded to 8 bits.
+ *   Outside: frame k's own pixel (no evidence: no residual motion).
+ * H = I gives pairs[n][1] the bits of (float) frame k + 1; a NaN H or D <= 0 everywhere gives the pair (f_k, f_k).
+ * pairs must not overlap frames.  No workspace.  At most 65535 pairs per call.
+ */
+int va_frames_warp_pairs(va_ctx* ctx, const void* frames, int frames_are_u8, int n_seq, int frames_per_seq, int w, int h,
+                         const void* H, void* pairs, void* stream);
 
 /*
  * Self-test of the arithmetic contract: compares the kernel's packed correctly-rounded sqrt and

@@ -29,7 +29,7 @@ EXPORTS = [
     "va_vgg16_export_state", "va_vgg16_import_state", "va_vgg16_train_plan",
     "va_conv3x3_layer", "va_vgg16_first_layer",
     "va_flow_to_stack_resize", "va_resize_images_u8", "va_vgg16_train_step_consensus",
-    "va_flow_homography", "va_flow_compensate",
+    "va_flow_homography", "va_flow_compensate", "va_frames_warp_pairs",
     "va_rgbdiff_to_stack", "va_fuse_scores_n",
     "va_train_conv_backward_layer", "va_train_fc_backward_layer", "va_train_pool_layer", "va_train_loss", "va_train_dropout",
     "va_vgg16_train_step_multitask", "va_train_loss_multitask",
@@ -189,6 +189,8 @@ def lib():
     L.va_flow_homography.restype = ci
     L.va_flow_compensate.argtypes = [vp, vp, ci, ci, ci, vp, vp, vp]
     L.va_flow_compensate.restype = ci
+    L.va_frames_warp_pairs.argtypes = [vp, vp, ci, ci, ci, ci, ci, vp, vp, vp]
+    L.va_frames_warp_pairs.restype = ci
     L.va_selftest_exact_math.argtypes = [vp, cf, cf, vp, vp]
     L.va_selftest_exact_math.restype = ci
     L.va_tvl1_profile_enable.argtypes = [vp, ci]

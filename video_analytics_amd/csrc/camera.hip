@@ -1,7 +1,8 @@
 // Warped optical flow, the camera-compensated temporal input of TSN: a robust homography fit over the
 // dense TV-L1 field of every pair, and the subtraction of the camera's displacement field from that flow.  Both read the
 // TV-L1 buffer [N][2][h][w]; the compensated array has its shape and pair order, so that every S9 - S17 consumer applies to
-// it unchanged.
+// it unchanged.  S53 is the first half of TSN's own two-pass form: every pair's second frame warped by H, for a second
+// TV-L1 pass that finds the residual motion directly.
 #include "va_internal.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -227,6 +228,74 @@ __global__ void __launch_bounds__(kCompThreads) k_flow_compensate(const float* f
     }
 }
 
+// S53: frames [n_seq][fps][h][w] (u8 or f32, TV-L1's input) -> pairs f32 [N][2][h][w], N = n_seq * (fps - 1), TV-L1 input
+// again: plane 0 of pair n = s * (fps - 1) + k is frame k of sequence s as float, plane 1 is frame k + 1 resampled at
+// H[n] (x, y, 1)^T, so that the camera's motion between the two planes is gone.  Block (blockIdx.x, blockIdx.y = pair);
+// each thread owns kWarpPx consecutive pixels.  The position is evaluated as S22 evaluates it (double, left to right, no
+// fused multiply-add), the blend is S17's (float32, no fmaf), and a pixel whose position is not inside the frame (D <= 0
+// and NaN included) keeps frame k's own value: no evidence, no residual motion.  A gather: no atomics, no workspace.
+// vec bit 0: 16-byte aligned pairs and planes of a multiple of 4 pixels (one 16-byte store per plane); bit 1: the same for
+// the frames (one 16-byte load of frame k for f32, one 4-byte load for u8, which needs 4-byte alignment only).
+constexpr int kWarpThreads = 256;
+constexpr int kWarpPx = 4;
+
+template <typename T>
+__global__ void __launch_bounds__(kWarpThreads) k_frames_warp_pairs(const T* __restrict__ frames, const double* __restrict__ Hin,
+                                                                    float* __restrict__ pairs, int w, int h, int fps, int vec)
+{
+    typedef T Tx4 __attribute__((ext_vector_type(4)));
+    const int n = w * h;
+    const int i0 = (blockIdx.x * kWarpThreads + threadIdx.x) * kWarpPx;
+    if (i0 >= n) return;
+    const int pair = blockIdx.y;
+    const int s = pair / (fps - 1), k = pair - s * (fps - 1);
+    const T* __restrict__ fa = frames + ((size_t)s * fps + k) * n;  // frame k
+    const T* __restrict__ fb = fa + n;                              // frame k + 1
+    const double* __restrict__ H = Hin + (size_t)pair * 9;
+    const double h00 = H[0], h01 = H[1], h02 = H[2], h10 = H[3], h11 = H[4], h12 = H[5], h20 = H[6], h21 = H[7], h22 = H[8];
+    float own[kWarpPx];
+    if (vec & 2) {
+        const Tx4 v = *reinterpret_cast<const Tx4*>(fa + i0);
+#pragma unroll
+        for (int j = 0; j < kWarpPx; ++j) own[j] = (float)v[j];
+    } else {
+#pragma unroll
+        for (int j = 0; j < kWarpPx; ++j) own[j] = i0 + j < n ? (float)fa[i0 + j] : 0.0f;
+    }
+    const double xmax = (double)(w - 1), ymax = (double)(h - 1);
+    int y = i0 / w, x = i0 - y * w;
+    float val[kWarpPx];
+#pragma unroll
+    for (int j = 0; j < kWarpPx; ++j) {
+        const double xd = (double)x, yd = (double)y;
+        const double X = h00 * xd + h01 * yd + h02, Y = h10 * xd + h11 * yd + h12, D = h20 * xd + h21 * yd + h22;
+        const double px = X / D, py = Y / D;
+        const bool inside = D > 0.0 && px >= 0.0 && px <= xmax && py >= 0.0 && py <= ymax;  // a NaN fails every comparison
+        const double pxs = inside ? px : 0.0, pys = inside ? py : 0.0;                     // the taps stay in the frame
+        const double fx0 = floor(pxs), fy0 = floor(pys);
+        const float ax = (float)(pxs - fx0), ay = (float)(pys - fy0);
+        const int x0 = (int)fx0, y0 = (int)fy0;
+        const int x1 = min(x0 + 1, w - 1), y1 = min(y0 + 1, h - 1);
+        const T* r0 = fb + (size_t)y0 * w;
+        const T* r1 = fb + (size_t)y1 * w;
+        const float a = (float)r0[x0], b = (float)r0[x1], c = (float)r1[x0], d = (float)r1[x1];
+        const float top = a + ax * (b - a);
+        const float bot = c + ax * (d - c);
+        val[j] = inside ? top + ay * (bot - top) : own[j];
+        if (++x == w) x = 0, ++y;
+    }
+    float* p0 = pairs + (size_t)pair * 2 * n;
+    float* p1 = p0 + n;
+    if (vec & 1) {
+        *reinterpret_cast<f32x4*>(p0 + i0) = f32x4{own[0], own[1], own[2], own[3]};
+        *reinterpret_cast<f32x4*>(p1 + i0) = f32x4{val[0], val[1], val[2], val[3]};
+    } else {
+#pragma unroll
+        for (int j = 0; j < kWarpPx; ++j)
+            if (i0 + j < n) p0[i0 + j] = own[j], p1[i0 + j] = val[j];
+    }
+}
+
 static constexpr int kMaxGridY = 65535;
 static constexpr long long kMaxPlane = 0x7fffffffLL - 3 * kCompThreads * kCompPx;  // w*h and i0 + 3 stay in int
 
@@ -264,6 +333,35 @@ extern "C" int va_flow_compensate(va_ctx* ctx, const void* flow, int n_fields, i
     const int vec4 = (n % 4 == 0 && o0 % 16 == 0 ? 1 : 0) | (n % 4 == 0 && f0 % 16 == 0 ? 2 : 0);
     const dim3 g((unsigned)va_cdiv(n, kCompThreads * kCompPx), (unsigned)n_fields);
     k_flow_compensate<<<g, kCompThreads, 0, (hipStream_t)stream>>>((const float*)flow, (const double*)H, (float*)out, w, h, vec4);
+    VA_LAUNCH_CHECK();
+    return VA_OK;
+}
+
+extern "C" int va_frames_warp_pairs(va_ctx* ctx, const void* frames, int frames_are_u8, int n_seq, int frames_per_seq, int w,
+                                    int h, const void* H, void* pairs, void* stream)
+{
+    VA_CHECK_ARG(ctx != nullptr, "va_frames_warp_pairs: ctx is NULL");
+    VA_USE_DEVICE(ctx);
+    VA_CHECK_ARG(frames != nullptr && H != nullptr && pairs != nullptr, "va_frames_warp_pairs: NULL buffer");
+    VA_CHECK_ARG(frames_are_u8 == 0 || frames_are_u8 == 1, "va_frames_warp_pairs: frames_are_u8 must be 0 or 1");
+    VA_CHECK_ARG(n_seq >= 1 && frames_per_seq >= 2 && w >= 1 && h >= 1,
+                 "va_frames_warp_pairs: bad shape (a sequence holds at least two frames)");
+    const long long n_pairs = (long long)n_seq * (frames_per_seq - 1);
+    VA_CHECK_ARG(n_pairs <= kMaxGridY, "va_frames_warp_pairs: %lld pairs exceed %d per call", n_pairs, kMaxGridY);
+    VA_CHECK_ARG((long long)w * h <= kMaxPlane, "va_frames_warp_pairs: %dx%d planes exceed one launch", w, h);
+    const int n = w * h;
+    const size_t elem = frames_are_u8 ? 1 : sizeof(float);
+    const uintptr_t f0 = reinterpret_cast<uintptr_t>(frames), o0 = reinterpret_cast<uintptr_t>(pairs);
+    const uintptr_t fbytes = (uintptr_t)n_seq * frames_per_seq * n * elem, obytes = (uintptr_t)n_pairs * 2 * n * sizeof(float);
+    VA_CHECK_ARG(f0 + fbytes <= o0 || o0 + obytes <= f0, "va_frames_warp_pairs: pairs must not overlap the frames");
+    const int vec = (n % 4 == 0 && o0 % 16 == 0 ? 1 : 0) | (n % 4 == 0 && f0 % (4 * elem) == 0 ? 2 : 0);
+    const dim3 g((unsigned)va_cdiv(n, kWarpThreads * kWarpPx), (unsigned)n_pairs);
+    if (frames_are_u8)
+        k_frames_warp_pairs<unsigned char><<<g, kWarpThreads, 0, (hipStream_t)stream>>>(
+            (const unsigned char*)frames, (const double*)H, (float*)pairs, w, h, frames_per_seq, vec);
+    else
+        k_frames_warp_pairs<float><<<g, kWarpThreads, 0, (hipStream_t)stream>>>((const float*)frames, (const double*)H,
+                                                                                (float*)pairs, w, h, frames_per_seq, vec);
     VA_LAUNCH_CHECK();
     return VA_OK;
 }

@@ -30,6 +30,11 @@ def release_workspaces():
     _ws_cache.clear()
 
 
+def release_workspace(slot, device):
+    """Drop one TV-L1 workspace slot of ``device`` (its owner has synchronised the stream that used it)."""
+    _ws_cache.pop((device.index, "tvl1", slot), None)
+
+
 def tvl1_flow(frames, params=None, ws_slot=0, out=None, **over):
     """frames: cuda uint8 or float32 tensor ``[S, F, H, W]`` (or ``[F, H, W]``), gray values in [0,255].
 
@@ -385,14 +390,31 @@ MOTIONS = ("stack", "trajectory", "bidirectional")
 
 
 # Camera compensation of the flow: "homography" is TSN's warped optical flow, every field minus the
-# displacement field of the homography fitted to it; it comes before the motion options above, which then see the
-# compensated field in place of the TV-L1 output.
+# displacement field of the homography fitted to it (or, with camera_form="rerun", TV-L1 of the pair warped by it: S53, S54);
+# it comes before the motion options above, which then see the compensated field in place of the TV-L1 output.
 CAMERAS = ("none", "homography")
 
 
 def check_camera(camera, who):
     if not isinstance(camera, str) or camera not in CAMERAS:
         raise ValueError("%s: camera must be one of %s, got %r" % (who, ", ".join(CAMERAS), camera))
+
+
+# The two forms of "homography" (DESIGN.md S22, S54): "subtract" takes the camera's displacement field from the TV-L1 field
+# (S22, one TV-L1 pass, exact where that field is); "rerun" is TSN's own definition: the second frame of every pair is
+# warped by the fitted homography (S53) and TV-L1 runs again on the pair, so that the residual motion is estimated directly.
+CAMERA_FORMS = ("subtract", "rerun")
+RERUN_WS_SLOT = "rerun"  # the second pass's TV-L1 workspace: never slot 0 or one of the flow streams' slots 1..n
+
+
+def check_camera_form(camera_form, who, camera="homography"):
+    """Host-side check (ValueError) of ``camera_form`` (``CAMERA_FORMS``) beside its ``camera``: an unknown form, and
+    ``"rerun"`` without a camera to compensate."""
+    if not isinstance(camera_form, str) or camera_form not in CAMERA_FORMS:
+        raise ValueError("%s: camera_form must be one of %s, got %r" % (who, ", ".join(CAMERA_FORMS), camera_form))
+    if camera_form == "rerun" and camera == "none":
+        raise ValueError("%s: camera_form='rerun' needs camera='homography'; with camera='none' there is nothing to run again"
+                         % who)
 
 
 def check_motion(motion, mean_flow, flow_count, who, camera="none"):
@@ -517,22 +539,80 @@ def compensate_camera(flow, H, out=None):
     return out.view(N, 2, h, w)
 
 
+def _check_frames(frames, who):
+    """TV-L1's input -> ``[S,F,h,w]`` (a ``[F,h,w]`` tensor is one sequence); ValueError for anything else."""
+    if not isinstance(frames, torch.Tensor) or not frames.is_cuda:
+        raise ValueError("%s: frames must be a CUDA tensor" % who)
+    if frames.dim() == 3:
+        frames = frames.unsqueeze(0)
+    if frames.dim() != 4 or frames.dtype not in (torch.uint8, torch.float32):
+        raise ValueError("%s: frames must be uint8 or float32 [S,F,H,W] (or [F,H,W]), TV-L1's input" % who)
+    if frames.shape[0] < 1 or frames.shape[1] < 2 or frames.shape[2] < 1 or frames.shape[3] < 1:
+        raise ValueError("%s: frames %s hold no frame pair" % (who, tuple(frames.shape)))
+    return frames
+
+
+def warp_pairs(frames, H, out=None):
+    """S53: frames ``[S,F,h,w]`` (or ``[F,h,w]``) CUDA uint8 or float32, TV-L1's input, and H CUDA float64 ``[N,3,3]``,
+    ``N = S*(F-1)`` in TV-L1's pair order (``fit_homography`` of their flow) -> float32 ``[N,2,h,w]``, TV-L1 input again:
+    pair n holds frame k as float and frame k+1 resampled at ``H[n] (x, y, 1)``, which takes the camera's motion out of the
+    pair.  Pixels whose position is not inside frame k+1 keep frame k's value.  ``out`` must not overlap ``frames``."""
+    frames = _check_frames(frames, "warp_pairs")
+    S, F, h, w = frames.shape
+    N = S * (F - 1)
+    if (not isinstance(H, torch.Tensor) or H.dtype != torch.float64 or H.device != frames.device
+            or tuple(H.shape) != (N, 3, 3)):
+        raise ValueError("warp_pairs: H must be a float64 [%d,3,3] tensor on the frames' device" % N)
+    frames = frames.contiguous()
+    H = H.contiguous()
+    out = _check_out(out, (N, 2, h, w), frames, "warp_pairs")
+    if _overlaps(out, frames):
+        raise ValueError("warp_pairs: out must not overlap frames")
+    _ffi.check(_ffi.lib().va_frames_warp_pairs(_ffi.ctx(frames.device.index), _ffi.ptr(frames), int(frames.dtype == torch.uint8),
+                                               S, F, w, h, _ffi.ptr(H), _ffi.ptr(out), _ffi.stream_ptr(frames.device)))
+    return out.view(N, 2, h, w)
+
+
+def rerun_camera(frames, flow, params=None, out=None):
+    """S54, TSN's two-pass warped flow -> ``(field, H, share)``: ``fit_homography`` of ``flow`` (the TV-L1 field of
+    ``frames``, S21: ``H`` and ``share`` are the subtract form's), ``warp_pairs`` of the frames under it (S53), and
+    ``tvl1_flow`` of those pairs with the same ``params``: ``field`` is that second pass's flow, written into ``out`` (over
+    the first pass when ``out is flow``).  Everything runs on the current stream; the second pass uses the TV-L1 workspace
+    slot ``RERUN_WS_SLOT``, one of its own.  (``TwoStreamPipeline`` runs the same three steps over its own buffers.)"""
+    _check_flow(flow, "rerun_camera")
+    frames = _check_frames(frames, "rerun_camera")
+    S, F, h, w = frames.shape
+    if frames.device != flow.device or tuple(flow.shape) != (S * (F - 1), 2, h, w):
+        raise ValueError("rerun_camera: flow must be the [%d,2,%d,%d] TV-L1 field of the frames, on their device, got %s"
+                         % (S * (F - 1), h, w, tuple(flow.shape)))
+    H, stats = fit_homography(flow)
+    return tvl1_flow(warp_pairs(frames, H), params, ws_slot=RERUN_WS_SLOT, out=out), H, stats[:, 0]
+
+
 def apply_camera(flow, camera="none", in_place=False):
     """S21 + S22 for ``camera`` (``CAMERAS``) -> ``(field, H, share)``: with ``"none"`` the flow itself and two Nones (no
     kernel, no buffer); with ``"homography"`` the compensated field (written over ``flow`` when ``in_place``), the fitted
-    ``H [N,3,3]`` and the trusted share ``[N]`` of every field."""
+    ``H [N,3,3]`` and the trusted share ``[N]`` of every field.  This is the ``"subtract"`` form; ``rerun_camera`` is the
+    other."""
     if camera == "none":
         return flow, None, None
     H, stats = fit_homography(flow)
     return compensate_camera(flow, H, out=flow if in_place else None), H, stats[:, 0]
 
 
-def apply_motion(flow, flow_count, motion="stack", mean_flow=False, out=None, camera="none"):
+def apply_motion(flow, flow_count, motion="stack", mean_flow=False, out=None, *, camera_form="subtract", frames=None,
+                 tvl1_params=None, camera="none"):
     """The float array S9 / S10 read for the given motion options (checked by ``check_motion``): ``flow`` itself for
     plain or bi-directional stacking without means (no kernel, no buffer), else ``motion_field`` of it (into ``out``).
     ``camera="homography"`` compensates the camera first (S21, S22, into a new array: ``flow`` is left as it is) and the
-    motion options then act on the compensated field."""
-    if camera != "none":
+    motion options then act on the compensated field.  ``camera_form="rerun"`` (``CAMERA_FORMS``) compensates in TSN's
+    two-pass form instead (S53, S54; ``rerun_camera``): it needs ``frames``, the TV-L1 input ``flow`` came from, and runs
+    the second pass with ``tvl1_params``, which must be the first pass's."""
+    if camera != "none" and camera_form == "rerun":
+        if frames is None:
+            raise ValueError("apply_motion: camera_form='rerun' needs frames=, the TV-L1 input of the flow")
+        flow = rerun_camera(frames, flow, tvl1_params)[0]
+    elif camera != "none":
         flow = apply_camera(flow, camera)[0]
     if motion != "trajectory" and not mean_flow:
         return flow

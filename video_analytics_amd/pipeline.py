@@ -9,6 +9,7 @@ In the reference the first half happens offline
 (precomputed flow JPEGs, Sheet03/temporalModel.py:76-90) and the second half is ``validate()``'s
 forward (Sheet03/spatialModel.py:212-218, Sheet03/temporalModel.py:241-247).
 """
+import itertools
 import types
 
 import torch
@@ -90,6 +91,9 @@ def check_video(rgb, gray, flow_count, motion, n_snippets, views, consensus, fus
     return plan, rgb_views, flow_views, mode, wa, wb
 
 
+_rerun_slots = itertools.count()  # one TV-L1 workspace slot per pipeline for the second pass of camera_form="rerun" (S54)
+
+
 class TwoStreamPipeline(object):
     """Batches flow through three sets of HIP streams:
 
@@ -121,6 +125,12 @@ class TwoStreamPipeline(object):
     place in the slot's flow buffer; the motion options and every gather then read the compensated field.  The results
     gain ``homography`` f64 ``[pairs,3,3]`` and ``camera_share`` f64 ``[pairs]``.
 
+    ``camera_form``: ``"rerun"`` takes TSN's own two-pass form of the warped flow instead (``flow.CAMERA_FORMS``; DESIGN.md
+    S53, S54): at the same place on the CNN stream the homography is fitted, the second frame of every pair is warped by it
+    into the slot's pairs buffer, and TV-L1 runs again on those pairs over the slot's flow buffer, with a workspace of this
+    pipeline's own.  ``extract_flow`` then stores that flow and ``train_videos`` trains on it.  It costs a second TV-L1;
+    ``homography`` and ``camera_share`` are the same.  ``"rerun"`` with ``camera="none"`` raises ValueError.
+
     ``rgb_diff``: True adds TSN's RGB-difference stream: ``self.diff``, a third VGG-16 of
     ``3 * rgb_diff_count`` input channels (seed ``diff_seed`` or ``weights[2]``; its first layer is the cross-modality copy of
     an RGB one) that ``submit_video`` / ``run_video`` and ``train_videos`` feed with the differences of each snippet's first
@@ -135,13 +145,15 @@ class TwoStreamPipeline(object):
 
     def __init__(self, device=None, spatial_seed=1, temporal_seed=2, flow_count=VIDEO_INPUT_FLOW_COUNT,
                  tvl1_params=None, weights=None, flow_streams=2, cnn_dtype="f32", depth=2, motion="stack", mean_flow=False,
-                 rgb_diff=False, rgb_diff_count=rgbdiff.RGB_DIFF_COUNT, diff_seed=3, heads=None, camera="none"):
+                 rgb_diff=False, rgb_diff_count=rgbdiff.RGB_DIFF_COUNT, diff_seed=3, heads=None, *, camera_form="subtract",
+                 camera="none"):
         self.heads = None
         if heads is not None:
             vgg.check_heads(heads, None, "TwoStreamPipeline")
             self.heads = tuple(int(h) for h in heads)
         n_classes = NACTION_CLASSES if self.heads is None else sum(self.heads)
         vflow.check_motion(motion, mean_flow, flow_count, "TwoStreamPipeline", camera=camera)
+        vflow.check_camera_form(camera_form, "TwoStreamPipeline", camera)
         self.D = rgbdiff.check_diff_count(rgb_diff_count, flow_count, "TwoStreamPipeline") if rgb_diff else 0
         if weights and len(weights) != (3 if rgb_diff and len(weights) > 2 else 2):
             raise ValueError("TwoStreamPipeline: weights= holds the spatial and temporal weights, and a third entry only with "
@@ -149,7 +161,7 @@ class TwoStreamPipeline(object):
         dev = torch.device("cuda", torch.cuda.current_device() if device is None else device)
         self.device = dev
         self.L = flow_count
-        self.motion, self.mean_flow, self.camera = motion, mean_flow, camera
+        self.motion, self.mean_flow, self.camera, self.camera_form = motion, mean_flow, camera, camera_form
         with torch.cuda.device(dev):
             ws = weights[0] if weights else build_stream_weights(3, spatial_seed, dev, n_classes)
             wt = weights[1] if weights else build_stream_weights(2 * flow_count, temporal_seed, dev, n_classes)
@@ -173,6 +185,8 @@ class TwoStreamPipeline(object):
         self._stack = [None] * self.depth     # per slot: flow volume read by the temporal CNN
         self._motion = [None] * self.depth    # per slot: the motion field S9 / S10 read instead of the flow (S12)
         self._dstack = [None] * self.depth    # per slot: the RGB-difference volume (S23), written and read on the CNN stream
+        self._pairs = [None] * self.depth     # per slot: the warped pairs (S53), written and read on the CNN stream ("rerun" only)
+        self._rerun_slot = (vflow.RERUN_WS_SLOT, next(_rerun_slots))  # the second pass's workspace: this pipeline's CNN stream alone
         self._flow_read = [None] * self.depth  # per slot: event "the flow buffer has been quantised" (it may be overwritten)
         self._handed_out = []                 # output tensors allocated on the CNN stream since the last wait()
         self._retired = []                    # dropped cross-stream buffers + the events after which they may be freed
@@ -188,7 +202,11 @@ class TwoStreamPipeline(object):
             fl = vflow.tvl1_flow_concurrent(tv, self.tvl1_params, self.flow_streams)
         else:
             fl = vflow.tvl1_flow(tv, self.tvl1_params)
-        fl = vflow.apply_motion(fl, self.L, self.motion, self.mean_flow, camera=self.camera)
+        if self._rerun():
+            fl = vflow.apply_motion(fl, self.L, self.motion, self.mean_flow, camera_form="rerun", frames=tv,
+                                    tvl1_params=self.tvl1_params, camera=self.camera)
+        else:
+            fl = vflow.apply_motion(fl, self.L, self.motion, self.mean_flow, camera=self.camera)
         return vflow.flow_to_stack(fl).view(B, 2 * self.L, H, W)
 
     def _tvl1_frames(self, gray):
@@ -196,10 +214,28 @@ class TwoStreamPipeline(object):
         backward sequences ``[2B,L/2+1,H,W]`` (S13), reordered on the current stream."""
         return vflow.bidirectional_sequences(gray) if self.motion == "bidirectional" else gray
 
-    def _camera(self, flow, out):
+    def _rerun(self):
+        """The camera step takes the two-pass form (getattr: the host tests build pipelines attribute by attribute)."""
+        return self.camera != "none" and getattr(self, "camera_form", "subtract") == "rerun"
+
+    def _camera(self, flow, out, tv=None, k=None):
         """On the CNN stream, after the TV-L1 events and before ``_motion_field``: S21 and S22 in place in the flow buffer
-        (no buffer of its own); the fitted homographies and trusted shares go into the result dict ``out``."""
-        if self.camera != "none":
+        (no buffer of its own); the fitted homographies and trusted shares go into the result dict ``out``.
+
+        ``camera_form="rerun"`` (S54): S21, then S53 of ``tv`` -- the TV-L1 input ``flow`` came from -- and TV-L1 again over the
+        flow buffer.  With a slot ``k`` this runs on the CNN stream: the pairs go into slot k's buffer and the second pass
+        has this pipeline's own workspace, which only its CNN stream uses; without one (``train_videos``, ``extract_flow``)
+        everything is in order on the current stream."""
+        if self._rerun():
+            pairs, slot = None, vflow.RERUN_WS_SLOT
+            if k is not None:
+                tv.record_stream(self._cnn)
+                pairs, slot = self._buffer(self._pairs, k, tuple(flow.shape)), self._rerun_slot
+            Hm, stats = vflow.fit_homography(flow)  # flow.rerun_camera's three steps, over the pipeline's own buffers
+            pairs = vflow.warp_pairs(tv, Hm, out=pairs)
+            vflow.tvl1_flow(pairs, self.tvl1_params, ws_slot=slot, out=flow)
+            out["homography"], out["camera_share"] = Hm, stats[:, 0]
+        elif self.camera != "none":
             _, out["homography"], out["camera_share"] = vflow.apply_camera(flow, self.camera, in_place=True)
         return flow
 
@@ -317,15 +353,16 @@ class TwoStreamPipeline(object):
                 return flow_stack
             return self._enqueue(spatial, given_stack, temporal, finish, beside=True)
         B, F, H, W = gray.shape
+        tv = self._tvl1_frames(gray)
 
         def to_stack(flow, k):
-            src = self._motion_field(self._camera(flow, extra), k)
+            src = self._motion_field(self._camera(flow, extra, tv, k), k)
             if flow_crops is None:
                 return vflow.flow_to_stack(src, out=self._buffer(self._stack, k, (B, 2 * self.L, H, W)))
             # the flow buffer is full-frame, the volume 224x224
             return vflow.crop_flow_to_stack(src, flow_crops, out=self._buffer(self._stack, k, (B, 2 * self.L, 224, 224)),
                                             invert_x_on_flip=bool(invert_flow_x))
-        return self._enqueue(spatial, to_stack, temporal, finish, tv=self._tvl1_frames(gray), flow_shape=(B * self.L, 2, H, W))
+        return self._enqueue(spatial, to_stack, temporal, finish, tv=tv, flow_shape=(B * self.L, 2, H, W))
 
     def _submit_views(self, rgb, gray, rgb_views, flow_views, invert):
         """``submit(views=)``: the stream layout of the crops= path, with B*V images per stream and the view means."""
@@ -334,13 +371,14 @@ class TwoStreamPipeline(object):
             raise ValueError("submit: need %d gray frames per clip, got %d" % (self.L + 1, F))
         Vt = flow_views.shape[0]
         extra = {}
+        tv = self._tvl1_frames(gray)
 
         def spatial(k):
             rgb.record_stream(self._cnn)
             return self.spatial.forward_views(augment.crop_image_views(rgb, rgb_views))
 
         def to_stack(flow, k):
-            src = self._motion_field(self._camera(flow, extra), k)
+            src = self._motion_field(self._camera(flow, extra, tv, k), k)
             return vflow.crop_flow_to_stack_views(src, flow_views, self.L, invert_x_on_flip=invert,
                                                   out=self._buffer(self._stack, k, (B, Vt, 2 * self.L, 224, 224)))
 
@@ -348,8 +386,7 @@ class TwoStreamPipeline(object):
             (desc_s, logits_s, desc_sv, logits_sv), (desc_t, logits_t, desc_tv, logits_tv) = s, t
             return dict(logits_s=logits_s, logits_t=logits_t, desc_s=desc_s, desc_t=desc_t, logits_s_views=logits_sv,
                         logits_t_views=logits_tv, desc_s_views=desc_sv, desc_t_views=desc_tv, **extra)
-        return self._enqueue(spatial, to_stack, self.temporal.forward_views, finish, tv=self._tvl1_frames(gray),
-                             flow_shape=(B * self.L, 2, H, W))
+        return self._enqueue(spatial, to_stack, self.temporal.forward_views, finish, tv=tv, flow_shape=(B * self.L, 2, H, W))
 
     def _enqueue(self, spatial, to_stack, temporal, finish, tv=None, flow_shape=None, beside=False):
         """The stream choreography of every submit path (the class docstring); the only place that creates, records or waits
@@ -420,7 +457,8 @@ class TwoStreamPipeline(object):
         (every frame's pyramid is built once per chunk), with the pipeline's ``tvl1_params``; field t is the flow from frame
         t to frame t + 1 and equals ``flow.tvl1_flow`` of those two frames bit for bit.  The pipeline's ``camera`` step (S21,
         S22) is applied to every field before anything is stored, so the store of a ``camera="homography"`` pipeline is TSN's
-        warped flow.  ``dtype``: ``torch.float32`` keeps TV-L1's output, exact; ``torch.uint8`` (the default, a quarter of the
+        warped flow; with ``camera_form="rerun"`` it is TSN's own two-pass warped flow (S53, S54: the second TV-L1 is paid
+        here, once per video).  ``dtype``: ``torch.float32`` keeps TV-L1's output, exact; ``torch.uint8`` (the default, a quarter of the
         size) quantises it last to the 8-bit flow images of S9 (``flow.quantize_flow``).
 
         Returns the store ``[T-1,2,H,W]``, ready on the current stream; with ``return_camera=True``
@@ -468,7 +506,12 @@ class TwoStreamPipeline(object):
                     vflow.tvl1_flow(part.unsqueeze(0), self.tvl1_params, ws_slot=i + 1, out=flow[bounds[i]:bounds[i + 1]])
             for st in streams:
                 cur.wait_stream(st)
-        flow, Hm, share = vflow.apply_camera(flow, self.camera, in_place=True)
+        if self._rerun():  # S54 on the current stream: the warp sees the video as the one sequence it is
+            cam = {}
+            self._camera(flow, cam, gray.unsqueeze(0))
+            Hm, share = cam["homography"], cam["camera_share"]
+        else:
+            flow, Hm, share = vflow.apply_camera(flow, self.camera, in_place=True)
         store = vflow.quantize_flow(flow) if dtype == torch.uint8 else flow
         return (store, Hm, share) if return_camera else store
 
@@ -647,7 +690,7 @@ class TwoStreamPipeline(object):
 
         def to_stack(flow, k):
             if stored is None:
-                src = self._camera(flow, extra)  # per planned field, like the means
+                src = self._camera(flow, extra, tv, k)  # per planned field, like the means
             else:  # the store is complete at `ready`; its windows start at the snippets' own pairs
                 stored.record_stream(self._cnn)
                 src = stored
@@ -1027,7 +1070,7 @@ class TwoStreamPipeline(object):
             first = self._planned_positions(plans)
         if flows is None:
             flow = vflow.tvl1_flow_concurrent(tv, self.tvl1_params, self.flow_streams)
-            flow = self._camera(flow, extra)  # per planned field, in place: everything below reads the compensated field
+            flow = self._camera(flow, extra, tv)  # per planned field, in place: everything below reads the compensated field
         if flow.dtype == torch.uint8:  # S41: the stored images themselves
             src = flow
         elif self.motion == "trajectory":  # S12 chains follow a window: the windows are laid out one after the other
@@ -1072,6 +1115,7 @@ class TwoStreamPipeline(object):
     def close(self):
         self._cnn2.synchronize()
         self._cnn.synchronize()
+        vflow.release_workspace(self._rerun_slot, self.device)  # the second pass's own (S54), if there was one
         self.spatial.close()
         self.temporal.close()
         if self.diff is not None:

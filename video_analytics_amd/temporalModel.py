@@ -63,7 +63,8 @@ class TemporalDataset(Dataset):
 
 
 def flowVolumesFromFrames(gray, flowSampleSize=VIDEO_INPUT_FLOW_COUNT, tvl1_params=None, bound=vflow.FLOW_BOUND, crops=None,
-                          views=None, invert_flow_x=False, motion="stack", mean_flow=False, camera="none"):
+                          views=None, invert_flow_x=False, motion="stack", mean_flow=False, *, camera_form="subtract",
+                          camera="none"):
     """gray CUDA u8/f32 ``[B, L+1, H, W]`` -> flow volumes f32 ``[B, 2L, H, W]`` on the GPU: TV-L1 on the
     L consecutive pairs, 8-bit quantisation, ToTensor+Normalize, x/y interleave -- the tensor
     ``TemporalDataset.__getitem__`` would have assembled from the upstream tool's JPEGs.
@@ -75,20 +76,24 @@ def flowVolumesFromFrames(gray, flowSampleSize=VIDEO_INPUT_FLOW_COUNT, tvl1_para
     ``motion``: ``"stack"`` (optical-flow stacking), ``"trajectory"`` (trajectory stacking) or ``"bidirectional"`` (L/2
     forward and L/2 backward fields around frame L/2; L even); ``mean_flow``: every field minus its mean vector (DESIGN.md
     S11-S13).  ``camera``: ``"homography"`` subtracts from every field the displacement field of the homography fitted to it
-    (TSN's warped optical flow), before the motion options.  All act on the full-frame float flow,
-    before the crops and views."""
+    (TSN's warped optical flow), before the motion options; ``camera_form="rerun"`` takes TSN's own
+    two-pass form instead: every pair's second frame is warped by that homography and TV-L1 runs again on the pair
+    (twice the TV-L1 time).  ``"rerun"`` with ``camera="none"`` raises ValueError.  All act on the
+    full-frame float flow, before the crops and views."""
     if gray.dim() != 4 or gray.shape[1] != flowSampleSize + 1:
         raise ValueError("flowVolumesFromFrames: gray must be [B,%d,H,W]" % (flowSampleSize + 1))
     if crops is not None and views is not None:
         raise ValueError("flowVolumesFromFrames: crops= and views= exclude each other")
     vflow.check_motion(motion, mean_flow, flowSampleSize, "flowVolumesFromFrames", camera=camera)
+    vflow.check_camera_form(camera_form, "flowVolumesFromFrames", camera)
     B, _, H, W = gray.shape
     if views is not None:
         from . import augment
         augment.check_views(views, H, W, 224, "flowVolumesFromFrames")
     if motion == "bidirectional":
         gray = vflow.bidirectional_sequences(gray)
-    fl = vflow.apply_motion(vflow.tvl1_flow(gray, tvl1_params), flowSampleSize, motion, mean_flow, camera=camera)
+    fl = vflow.apply_motion(vflow.tvl1_flow(gray, tvl1_params), flowSampleSize, motion, mean_flow, camera_form=camera_form,
+                            frames=gray, tvl1_params=tvl1_params, camera=camera)
     if views is not None:
         return vflow.crop_flow_to_stack_views(fl, views, flowSampleSize, invert_x_on_flip=invert_flow_x, bound=bound)
     if crops is not None:

@@ -226,6 +226,33 @@ int va_tvl1_flow(va_ctx* ctx, const void* frames, int frames_are_u8, int n_seq, 
                  void* workspace, size_t workspace_bytes, void* stream);
 
 /*
+ * Options carried beside va_tvl1_params (which keeps its size).  DESIGN.md S55: the flow is median filtered between
+ * blocks of inner iterations, as the TV-L1 of OpenCV's CPU class does (median 5, median_every 30 with iters 300 are its
+ * defaults; OpenCV's CUDA class, and this library without the option, do not filter).
+ *   struct_bytes  sizeof(va_tvl1_options) of the caller; a smaller value is refused.
+ *   median        0 (off), 3 or 5: at the head of inner iteration `it` of every warp, for every it with
+ *                 it % median_every == 0, u1 and u2 are each replaced by their median x median median (window centred on
+ *                 the pixel, coordinates clamped to the level's frame, exact selection; the dual variables stay).  With
+ *                 epsilon > 0 a pair that has met the stopping rule in a warp is not filtered again in it.
+ *   median_every  >= 0 inner iterations between two filters; 0 = iters: once per warp.
+ * opt = NULL or median = 0: va_tvl1_flow's result and va_tvl1_workspace_bytes' count, bit for bit.  Values out of range
+ * give VA_ERR_INVALID (a byte count of 0) and a message naming the field before anything is launched.  Results do not
+ * depend on block_iters, tile_mask or tuning with the option either; fast_math is independent of it.
+ */
+typedef struct va_tvl1_options { int struct_bytes; int median; int median_every; } va_tvl1_options;
+size_t va_tvl1_workspace_bytes_opt(int w, int h, int n_seq, int frames_per_seq, const va_tvl1_params* p, const va_tvl1_options* opt);
+int va_tvl1_flow_opt(va_ctx* ctx, const void* frames, int frames_are_u8, int n_seq, int frames_per_seq, int w, int h,
+                     const va_tvl1_params* p, const va_tvl1_options* opt, void* flow, void* workspace, size_t workspace_bytes,
+                     void* stream);
+
+/*
+ * The filter of S55 on stored flow: flow f32 [n_fields][2][h][w] -> out of the same shape, every plane replaced by its
+ * ksize x ksize median (ksize 3 or 5; any w, h >= 1: a plane narrower than the window is legal).  Only finite values
+ * are specified; -0.0 and +0.0 compare equal.  out must not overlap flow (VA_ERR_INVALID).
+ */
+int va_flow_median(va_ctx* ctx, const void* flow, int n_fields, int w, int h, int ksize, void* out, void* stream);
+
+/*
  * flow f32 [n_pairs][2][h][w] -> stack f32 [2*n_pairs][h][w]: channel 2k = x flow of pair k,
  * 2k+1 = y flow (Sheet03/temporalModel.py:83).  Each value is quantised to the 8-bit flow
  * image convention q = rint(clamp(255*(v+bound)/(2*bound), 0, 255)) and then normalised as

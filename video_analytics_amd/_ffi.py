@@ -42,6 +42,7 @@ EXPORTS = [
     "va_solver_default", "va_vgg16_set_solver", "va_vgg16_get_solver", "va_train_dropout_p",
     "va_jpeg_decode_workspace_bytes", "va_jpeg_decode", "va_jpeg_idct", "va_jpeg_upsample",
     "va_jpeg_encode_workspace_bytes", "va_jpeg_encode", "va_jpeg_fdct", "va_jpeg_entropy_encode",
+    "va_tvl1_workspace_bytes_opt", "va_tvl1_flow_opt", "va_flow_median",
 ]
 
 
@@ -52,7 +53,10 @@ TUNING_SLOTS = ("stream_levels", "stream_waves", "stream_chunks", "stream_slots"
 
 
 class Tvl1Params(ctypes.Structure):
-    """Mirror of ``va_tvl1_params`` (include/va.h)."""
+    """Mirror of ``va_tvl1_params`` (include/va.h).  ``median`` and ``median_every`` are plain Python attributes, not C
+    fields: the options of ``va_tvl1_options``, which travel beside the structure (``tvl1_options``)."""
+    median = 0
+    median_every = 0
     _fields_ = [
         ("tau", ctypes.c_float),
         ("lambda_", ctypes.c_float),
@@ -75,6 +79,19 @@ def _tuning_property(i):
 
 for _i, _name in enumerate(TUNING_SLOTS):
     setattr(Tvl1Params, _name, _tuning_property(_i))
+
+
+class Tvl1Options(ctypes.Structure):
+    """Mirror of ``va_tvl1_options`` (include/va.h)."""
+    _fields_ = [("struct_bytes", ctypes.c_int), ("median", ctypes.c_int), ("median_every", ctypes.c_int)]
+
+
+def tvl1_options(params):
+    """The ``va_tvl1_options`` that the Python attributes of ``params`` ask for, or None when they ask for nothing."""
+    median, every = int(getattr(params, "median", 0)), int(getattr(params, "median_every", 0))
+    if median == 0 and every == 0:
+        return None
+    return Tvl1Options(ctypes.sizeof(Tvl1Options), median, every)
 
 
 class SolverParams(ctypes.Structure):
@@ -143,6 +160,12 @@ def lib():
     L.va_tvl1_workspace_bytes.restype = sz
     L.va_tvl1_flow.argtypes = [vp, vp, ci, ci, ci, ci, ci, ctypes.POINTER(Tvl1Params), vp, vp, sz, vp]
     L.va_tvl1_flow.restype = ci
+    L.va_tvl1_workspace_bytes_opt.argtypes = [ci, ci, ci, ci, ctypes.POINTER(Tvl1Params), ctypes.POINTER(Tvl1Options)]
+    L.va_tvl1_workspace_bytes_opt.restype = sz
+    L.va_tvl1_flow_opt.argtypes = [vp, vp, ci, ci, ci, ci, ci, ctypes.POINTER(Tvl1Params), ctypes.POINTER(Tvl1Options), vp, vp, sz, vp]
+    L.va_tvl1_flow_opt.restype = ci
+    L.va_flow_median.argtypes = [vp, vp, ci, ci, ci, ci, vp, vp]
+    L.va_flow_median.restype = ci
     L.va_flow_to_stack.argtypes = [vp, vp, ci, ci, ci, cf, cf, cf, vp, vp]
     L.va_flow_to_stack.restype = ci
     L.va_flow_to_stack_crop.argtypes = [vp, vp, ci, ci, ci, cf, cf, cf, vp, ci, ci, vp, vp]

@@ -1271,6 +1271,131 @@ __global__ void __launch_bounds__(NWV * 64)
     stream_job<PPL, KH, NWV, FAST, NCH>(a, a.pair0 + first + which, ch * a.nsx + sx, a.K, a.sin, a.sout, half);
 }
 
+// ---------------------------------------------------------------- median of the flow (S55) ----
+// u1 and u2 replaced by their KS x KS median (KS = 3, 5): window centred on the pixel, coordinates clamped to the
+// frame, exact selection.  Out of place: k_median writes the filtered planes to scratch, k_median_store copies them
+// back over the state, so that every sample is read from the values before the filter.
+__device__ __forceinline__ void cswap(float& a, float& b)  // a <- min, b <- max
+{
+    const float lo = fminf(a, b), hi = fmaxf(a, b);
+    a = lo;
+    b = hi;
+}
+
+// Forgetful selection.  Of M = live / 2 + 2 values out of `live` (odd) neither the smallest nor the largest can be
+// the median of all: both leave, the median of the rest is the median sought, and one value not yet seen joins the M - 2
+// that stay.  25 values: rounds of 14, 13, ..., 4 and a median of three; 9 values: 6, 5, 4.  A round orders pairs
+// (w[2i] <= w[2i+1]), then carries the minimum of the lower halves to w[0] and the maximum of the upper ones to w[1]:
+// 3M - 4 min/max, 253 for 25 values and 33 for 9.  Every index is a compile-time constant (the recursion is over
+// template arguments): the arrays live in registers.
+template <int M, int NEXT, int N, int M0>
+__device__ __forceinline__ float median_round(float (&w)[M0], const float (&v)[N])
+{
+    if constexpr (M == 3) {
+        static_assert(NEXT == N, "every value has been seen when three are left");
+        return __builtin_amdgcn_fmed3f(w[0], w[1], w[2]);
+    } else {
+#pragma unroll
+        for (int i = 0; i + 1 < M; i += 2) cswap(w[i], w[i + 1]);
+#pragma unroll
+        for (int i = 2; i < M; i += 2) cswap(w[0], w[i]);  // (M odd: the unpaired last value, index M - 1, is among these)
+#pragma unroll
+        for (int i = 3; i < M; i += 2) cswap(w[i], w[1]);
+        if constexpr (M % 2 == 1) cswap(w[M - 1], w[1]);
+        w[0] = v[NEXT];
+        w[1] = w[M - 1];
+        return median_round<M - 1, NEXT + 1, N, M0>(w, v);
+    }
+}
+template <int N>
+__device__ __forceinline__ float median_of(const float (&v)[N])
+{
+    constexpr int M0 = N / 2 + 2;
+    float w[M0];
+#pragma unroll
+    for (int i = 0; i < M0; ++i) w[i] = v[i];
+    return median_round<M0, M0, N, M0>(w, v);
+}
+
+struct MedianArgs {
+    const float* srcA;  // fields to filter, [pair][src_nf][plane]; plane 0 = u1, plane 1 = u2 of a pair
+    const float* srcB;  // the other ping-pong buffer (which of the two: `cur`, in epsilon mode base[pair] ^ (it & 1))
+    float* dstA;        // [pair][dst_nf][plane]
+    float* dstB;
+    const int* base;                // epsilon mode (err != nullptr): as IterArgs
+    const unsigned long long* err;
+    unsigned long long qthr;
+    size_t plane;
+    int src_nf, dst_nf;
+    int cur, it, iters;
+    int w, h, pitch, perm, ntx, pair0;
+};
+
+constexpr int kMedTX = 64, kMedTY = 16, kMedRows = 4;  // tile of a workgroup of 64 x 4 threads; rows per thread
+
+// The buffer of this launch's pair, or -1: the pair has met the stopping rule in this warp (the test of k_iter_tile<EPS>)
+__device__ __forceinline__ int median_buffer(const MedianArgs& a, int pair)
+{
+    if (!a.err) return a.cur;
+    if (a.it > 0 && a.err[(size_t)pair * a.iters + a.it - 1] < a.qthr) return -1;
+    return a.base[pair] ^ (a.it & 1);
+}
+
+template <int KS>
+__global__ void __launch_bounds__(kMedTX * (kMedTY / kMedRows)) k_median(MedianArgs a)
+{
+    constexpr int R = KS / 2, LW = kMedTX + 2 * R, LH = kMedTY + 2 * R, NT = kMedTX * (kMedTY / kMedRows);
+    __shared__ float tile[LH][LW];
+    const int pair = a.pair0 + blockIdx.y, f = blockIdx.z;
+    const int which = median_buffer(a, pair);
+    if (which < 0) return;  // (the same for the whole workgroup)
+    const float* __restrict__ src = (which ? a.srcB : a.srcA) + ((size_t)pair * a.src_nf + f) * a.plane;
+    float* __restrict__ dst = (which ? a.dstB : a.dstA) + ((size_t)pair * a.dst_nf + f) * a.plane;
+    const int w = a.w, h = a.h, pitch = a.pitch, perm = a.perm;
+    const int ox = (int)(blockIdx.x % a.ntx) * kMedTX, oy = (int)(blockIdx.x / a.ntx) * kMedTY;
+    const int tid = threadIdx.y * kMedTX + threadIdx.x;
+    for (int i = tid; i < LW * LH; i += NT) {
+        const int ly = i / LW, lx = i - ly * LW;
+        const int gx = d_min(d_max(ox + lx - R, 0), w - 1), gy = d_min(d_max(oy + ly - R, 0), h - 1);
+        tile[ly][lx] = src[(size_t)gy * pitch + pslot(gx, perm)];
+    }
+    __syncthreads();
+    const int x = ox + threadIdx.x;
+    if (x >= w) return;
+    for (int j = 0; j < kMedRows; ++j) {
+        const int ly = threadIdx.y * kMedRows + j, y = oy + ly;
+        if (y >= h) break;
+        float v[KS * KS];
+#pragma unroll
+        for (int dy = 0; dy < KS; ++dy)
+#pragma unroll
+            for (int dx = 0; dx < KS; ++dx) v[dy * KS + dx] = tile[ly + dy][threadIdx.x + dx];
+        dst[(size_t)y * pitch + pslot(x, perm)] = median_of<KS * KS>(v);
+    }
+}
+
+// scratch [pair][2][plane] -> u1, u2 of the state (columns x < w: the pitch padding of the state stays zero)
+__global__ void k_median_store(MedianArgs a)
+{
+    const int pair = a.pair0 + blockIdx.y, f = blockIdx.z;
+    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= a.w * a.h) return;
+    const int which = median_buffer(a, pair);
+    if (which < 0) return;
+    const float* __restrict__ src = (which ? a.srcB : a.srcA) + ((size_t)pair * a.src_nf + f) * a.plane;
+    float* __restrict__ dst = (which ? a.dstB : a.dstA) + ((size_t)pair * a.dst_nf + f) * a.plane;
+    const int y = idx / a.w, x = idx - y * a.w;
+    const size_t o = (size_t)y * a.pitch + pslot(x, a.perm);
+    dst[o] = src[o];
+}
+
+void launch_median(int ksize, const MedianArgs& a, int npairs, hipStream_t st)
+{
+    const dim3 grid(a.ntx * va_cdiv(a.h, kMedTY), npairs, 2), block(kMedTX, kMedTY / kMedRows);
+    if (ksize == 3) k_median<3><<<grid, block, 0, st>>>(a);
+    else k_median<5><<<grid, block, 0, st>>>(a);
+}
+
 // ---------------------------------------------------------------- host side -------------------
 
 struct TileCfg {
@@ -1577,6 +1702,21 @@ int check_params(const va_tvl1_params* p, int w, int h, int n_seq, int fps)
     return VA_OK;
 }
 
+// va_tvl1_options (NULL: every option off).  On success *median is 0, 3 or 5 and *every the iterations between two filters.
+int check_options(const va_tvl1_options* o, const va_tvl1_params* p, int* median, int* every)
+{
+    *median = 0;
+    *every = p->iters;
+    if (!o) return VA_OK;
+    VA_CHECK_ARG(o->struct_bytes >= (int)sizeof(va_tvl1_options), "va_tvl1: options.struct_bytes is %d, need at least %d", o->struct_bytes,
+                 (int)sizeof(va_tvl1_options));
+    VA_CHECK_ARG(o->median == 0 || o->median == 3 || o->median == 5, "va_tvl1: options.median must be 0, 3 or 5 (got %d)", o->median);
+    VA_CHECK_ARG(o->median_every >= 0, "va_tvl1: options.median_every must be >= 0 (got %d)", o->median_every);
+    *median = o->median;
+    if (o->median_every > 0 && o->median_every < p->iters) *every = o->median_every;
+    return VA_OK;
+}
+
 int pyramid_sizes(int w, int h, const va_tvl1_params* p, int* ws, int* hs)
 {
     int n = 1;
@@ -1707,7 +1847,16 @@ extern "C" int va_tvl1_tile_plan(int w, int h, const va_tvl1_params* p, int* out
 
 extern "C" size_t va_tvl1_workspace_bytes(int w, int h, int n_seq, int frames_per_seq, const va_tvl1_params* p)
 {
+    return va_tvl1_workspace_bytes_opt(w, h, n_seq, frames_per_seq, p, nullptr);
+}
+
+// (the median goes through the pyramid's scratch planes, which are free once the pyramid stands: no option changes the size)
+extern "C" size_t va_tvl1_workspace_bytes_opt(int w, int h, int n_seq, int frames_per_seq, const va_tvl1_params* p,
+                                              const va_tvl1_options* opt)
+{
     if (check_params(p, w, h, n_seq, frames_per_seq) != VA_OK) return 0;
+    int median, every;
+    if (check_options(opt, p, &median, &every) != VA_OK) return 0;
     Plan P;
     make_plan(P, w, h, n_seq, frames_per_seq, p);
     return P.total;
@@ -1717,10 +1866,19 @@ extern "C" int va_tvl1_flow(va_ctx* ctx, const void* frames, int frames_are_u8, 
                             int h, const va_tvl1_params* p, void* flow, void* workspace, size_t workspace_bytes,
                             void* stream)
 {
+    return va_tvl1_flow_opt(ctx, frames, frames_are_u8, n_seq, frames_per_seq, w, h, p, nullptr, flow, workspace, workspace_bytes, stream);
+}
+
+extern "C" int va_tvl1_flow_opt(va_ctx* ctx, const void* frames, int frames_are_u8, int n_seq, int frames_per_seq, int w,
+                                int h, const va_tvl1_params* p, const va_tvl1_options* opt, void* flow, void* workspace,
+                                size_t workspace_bytes, void* stream)
+{
     VA_CHECK_ARG(ctx != nullptr, "va_tvl1_flow: ctx is NULL");
     VA_USE_DEVICE(ctx);
     VA_CHECK_ARG(frames != nullptr && flow != nullptr && workspace != nullptr, "va_tvl1_flow: NULL buffer");
     if (int rc = check_params(p, w, h, n_seq, frames_per_seq)) return rc;
+    int median, median_every;  // S55: median = 0 runs one segment of p->iters iterations, the launch sequence without the option
+    if (int rc = check_options(opt, p, &median, &median_every)) return rc;
     VA_CHECK_ARG(((uintptr_t)workspace & 255) == 0, "va_tvl1_flow: workspace must be 256-byte aligned");
     Plan P;
     make_plan(P, w, h, n_seq, frames_per_seq, p);
@@ -1780,7 +1938,8 @@ extern "C" int va_tvl1_flow(va_ctx* ctx, const void* frames, int frames_are_u8, 
         const int lw = P.ws[s], lh = P.hs[s], lp = P.pitch[s];
         const size_t plane = P.plane[s];
         const unsigned tmask = (unsigned)p->tile_mask & (unsigned)(kStreamBit - 1);
-        const TilePick tp = K0 > 0 ? pick_tiles(lw, lh, K0, tmask) : pick_tiles_auto(lw, lh, p->iters, tmask);
+        // (S55: the block depth is chosen for the run of iterations between two filters)
+        const TilePick tp = K0 > 0 ? pick_tiles(lw, lh, K0, tmask) : pick_tiles_auto(lw, lh, median ? median_every : p->iters, tmask);
         const bool strm = P.lk[s] == LK_STREAM;
         const int perm = strm ? 0 : 1;
         if (lp != lw) {
@@ -1829,6 +1988,8 @@ extern "C" int va_tvl1_flow(va_ctx* ctx, const void* frames, int frames_are_u8, 
             a.theta = p->theta;
             a.pair0 = c0;
             int launches = 0;
+            // iterations it0 .. it0 + n - 1 of this warp, from state[cur]: the whole warp, or (S55) the segment between two filters
+            auto run_iters = [&](const int it0, const int n) -> int {
             if (strm) {
                 const StreamPick sp = pick_stream(p, lw, lh, nc);
                 StreamArgs sa{};
@@ -1855,9 +2016,9 @@ extern "C" int va_tvl1_flow(va_ctx* ctx, const void* frames, int frames_are_u8, 
                 int mw_n = 0, mw_base = 0, mw_extra = 0;
                 if (sp.nwv) {
                     const int kmax = sp.nwv * sp.kh, kmin = (sp.nwv - 1) * sp.kh + 1;
-                    mw_n = va_cdiv(p->iters, kmax);
-                    mw_base = p->iters / mw_n;
-                    mw_extra = p->iters % mw_n;
+                    mw_n = va_cdiv(n, kmax);
+                    mw_base = n / mw_n;
+                    mw_extra = n % mw_n;
                     if (mw_base < kmin) mw_n = 0;
                 }
                 for (int i = 0; i < mw_n; ++i) {
@@ -1871,8 +2032,8 @@ extern "C" int va_tvl1_flow(va_ctx* ctx, const void* frames, int frames_are_u8, 
                     cur ^= 1;
                     ++launches;
                 }
-                for (int it = mw_n ? p->iters : 0; it < p->iters;) {
-                    const int rem = p->iters - it;
+                for (int it = mw_n ? n : 0; it < n;) {
+                    const int rem = n - it;
                     // the two-wave kernel needs its last level in the second wave: a shorter remainder runs in one wave
                     const bool fb = rem > (sp.fb_nwv - 1) * sp.fb_kh;
                     const int nwv = fb ? sp.fb_nwv : 1, kh = fb ? sp.fb_kh : kStreamK1;
@@ -1886,16 +2047,16 @@ extern "C" int va_tvl1_flow(va_ctx* ctx, const void* frames, int frames_are_u8, 
                     ++launches;
                 }
             }
-            for (int it = strm ? p->iters : 0; it < p->iters;) {
+            for (int it = strm ? n : 0; it < n;) {
                 // the tile grid depends on the halo depth: a shorter last launch gets its own grid
-                const int k = (p->iters - it) < tp.K ? (p->iters - it) : tp.K;
+                const int k = (n - it) < tp.K ? (n - it) : tp.K;
                 const TilePick tk = (k == tp.K) ? tp : pick_tiles(lw, lh, k, tmask);
                 a.ntx = tk.ntx;
                 a.nty = tk.nty;
                 a.HX = tk.HX;
                 a.cur = cur;
                 a.K = tk.K;
-                a.it = it;
+                a.it = it0 + it;
                 a.rev = launches & 1;
                 if (eps) {
                     if (p->fast_math) launch_iter<true, true>(tk, a, nc, st);
@@ -1907,6 +2068,44 @@ extern "C" int va_tvl1_flow(va_ctx* ctx, const void* frames, int frames_are_u8, 
                 cur ^= 1;
                 it += tk.K;
                 ++launches;
+            }
+            return VA_OK;
+            };
+            if (!median) {
+                if (int rc = run_iters(0, p->iters)) return rc;
+            } else {
+                // S55: u1, u2 of every pair still iterating <- their median, at the head of iteration it0; through the
+                // pyramid's scratch planes ([pair][2][plane]: NP x 2 planes fit the NF x 2 of tmp1, tmp2)
+                MedianArgs m{};
+                m.base = base;
+                m.err = eps ? err : nullptr;
+                m.qthr = a.qthr;
+                m.plane = plane;
+                m.iters = p->iters;
+                m.w = lw;
+                m.h = lh;
+                m.pitch = lp;
+                m.perm = perm;
+                m.ntx = va_cdiv(lw, kMedTX);
+                m.pair0 = c0;
+                for (int it0 = 0; it0 < p->iters; it0 += median_every) {
+                    m.cur = cur;
+                    m.it = it0;
+                    m.srcA = state[0];
+                    m.srcB = state[1];
+                    m.src_nf = kNF_STATE;
+                    m.dstA = m.dstB = tmp1;
+                    m.dst_nf = 2;
+                    launch_median(median, m, nc, st);
+                    m.srcA = m.srcB = tmp1;
+                    m.src_nf = 2;
+                    m.dstA = state[0];
+                    m.dstB = state[1];
+                    m.dst_nf = kNF_STATE;
+                    k_median_store<<<dim3(va_cdiv(lw * lh, TPB), nc, 2), TPB, 0, st>>>(m);
+                    const int n = p->iters - it0 < median_every ? p->iters - it0 : median_every;
+                    if (int rc = run_iters(it0, n)) return rc;
+                }
             }
             VA_LAUNCH_CHECK();
             if (ctx->prof_on) {
@@ -1954,6 +2153,33 @@ extern "C" int va_flow_to_stack(va_ctx* ctx, const void* flow, int n_pairs, int 
     VA_CHECK_ARG(bound > 0.0f && stdv > 0.0f, "va_flow_to_stack: bound and std must be > 0");
     const size_t n = (size_t)n_pairs * 2 * w * h;
     k_flow_to_stack<<<(unsigned)((n + 255) / 256), 256, 0, (hipStream_t)stream>>>((const float*)flow, (float*)stack, n, bound, mean, stdv);
+    VA_LAUNCH_CHECK();
+    return VA_OK;
+}
+
+// S55 on stored flow: every plane of flow [n_fields][2][h][w] -> its ksize x ksize median (k_median on dense planes)
+extern "C" int va_flow_median(va_ctx* ctx, const void* flow, int n_fields, int w, int h, int ksize, void* out, void* stream)
+{
+    VA_CHECK_ARG(ctx != nullptr, "va_flow_median: ctx is NULL");
+    VA_USE_DEVICE(ctx);
+    VA_CHECK_ARG(flow != nullptr && out != nullptr, "va_flow_median: NULL buffer");
+    VA_CHECK_ARG(n_fields >= 1 && w >= 1 && h >= 1 && w <= 16384 && h <= 16384, "va_flow_median: bad shape (%d fields of %dx%d)", n_fields, w, h);
+    VA_CHECK_ARG(ksize == 3 || ksize == 5, "va_flow_median: ksize must be 3 or 5 (got %d)", ksize);
+    const size_t bytes = (size_t)n_fields * 2 * w * h * sizeof(float);
+    const uintptr_t f0 = (uintptr_t)flow, o0 = (uintptr_t)out;
+    VA_CHECK_ARG(f0 + bytes <= o0 || o0 + bytes <= f0, "va_flow_median: out must not overlap flow");
+    MedianArgs m{};
+    m.plane = (size_t)w * h;
+    m.src_nf = m.dst_nf = 2;
+    m.w = w;
+    m.h = h;
+    m.pitch = w;
+    m.ntx = va_cdiv(w, kMedTX);
+    for (int f = 0; f < n_fields; f += 32768) {  // (the grid's y extent)
+        m.srcA = m.srcB = (const float*)flow + (size_t)f * 2 * m.plane;
+        m.dstA = m.dstB = (float*)out + (size_t)f * 2 * m.plane;
+        launch_median(ksize, m, n_fields - f < 32768 ? n_fields - f : 32768, (hipStream_t)stream);
+    }
     VA_LAUNCH_CHECK();
     return VA_OK;
 }

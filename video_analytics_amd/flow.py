@@ -57,7 +57,11 @@ def tvl1_flow(frames, params=None, ws_slot=0, out=None, **over):
     p = params if params is not None else _ffi.default_tvl1_params(**over)
     L = _ffi.lib()
     c = _ffi.ctx(frames.device.index)
-    nbytes = L.va_tvl1_workspace_bytes(W, H, S, F, ctypes.byref(p))
+    opt = _ffi.tvl1_options(p)  # (S55: the median of the flow between blocks of inner iterations)
+    if opt is None:
+        nbytes = L.va_tvl1_workspace_bytes(W, H, S, F, ctypes.byref(p))
+    else:
+        nbytes = L.va_tvl1_workspace_bytes_opt(W, H, S, F, ctypes.byref(p), ctypes.byref(opt))
     if nbytes == 0:
         raise ValueError(L.va_last_error().decode())
     ws = _workspace(nbytes, frames.device, ws_slot)
@@ -68,9 +72,26 @@ def tvl1_flow(frames, params=None, ws_slot=0, out=None, **over):
         if (tuple(flow.shape) != (S * (F - 1), 2, H, W) or flow.dtype != torch.float32 or flow.device != frames.device
                 or not flow.is_contiguous()):
             raise ValueError("tvl1_flow: out must be a contiguous float32 [%d,2,%d,%d] tensor on the frames' device" % (S * (F - 1), H, W))
-    _ffi.check(L.va_tvl1_flow(c, _ffi.ptr(frames), int(frames.dtype == torch.uint8), S, F, W, H, ctypes.byref(p),
-                              _ffi.ptr(flow), _ffi.ptr(ws), ws.numel(), _ffi.stream_ptr(frames.device)))
+    if opt is None:
+        _ffi.check(L.va_tvl1_flow(c, _ffi.ptr(frames), int(frames.dtype == torch.uint8), S, F, W, H, ctypes.byref(p),
+                                  _ffi.ptr(flow), _ffi.ptr(ws), ws.numel(), _ffi.stream_ptr(frames.device)))
+    else:
+        _ffi.check(L.va_tvl1_flow_opt(c, _ffi.ptr(frames), int(frames.dtype == torch.uint8), S, F, W, H, ctypes.byref(p),
+                                      ctypes.byref(opt), _ffi.ptr(flow), _ffi.ptr(ws), ws.numel(), _ffi.stream_ptr(frames.device)))
     return flow
+
+
+def median_filter(flow, ksize=5, out=None):
+    """The filter of DESIGN.md S55 on stored flow (``va_flow_median``): flow ``[N,2,H,W]`` CUDA float32 -> the same shape,
+    every plane replaced by its ``ksize`` x ``ksize`` median (3 or 5; window clamped to the plane, exact selection).
+    ``out`` must not overlap ``flow``."""
+    _check_flow(flow, "median_filter")
+    flow = flow.contiguous()
+    N, _, H, W = flow.shape
+    out = _check_out(out, (N, 2, H, W), flow, "median_filter")
+    _ffi.check(_ffi.lib().va_flow_median(_ffi.ctx(flow.device.index), _ffi.ptr(flow), N, W, H, int(ksize), _ffi.ptr(out),
+                                         _ffi.stream_ptr(flow.device)))
+    return out
 
 
 _streams = {}

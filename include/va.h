@@ -252,6 +252,52 @@ int va_tvl1_flow_opt(va_ctx* ctx, const void* frames, int frames_are_u8, int n_s
  */
 int va_flow_median(va_ctx* ctx, const void* flow, int n_fields, int w, int h, int ksize, void* out, void* stream);
 
+/* ------------------------------------------------------------------ Brox flow -------- */
+
+/*
+ * The flow method of the two-stream paper (Sheet03/notes.txt:11-16): Brox, Bruhn, Papenberg, Weickert, "High accuracy
+ * optical flow estimation based on a theory for warping", ECCV 2004, in the form of IPOL's "Robust Optical Flow
+ * Estimation" (Sanchez, Monzon, Salgado 2013).  DESIGN.md S57-S62 are the specification: constancy of the intensity and
+ * of its gradient, a robust smoothness term, lagged nonlinearities, red-black SOR.  Values out of range (alpha <= 0,
+ * gamma < 0, scale_step outside (0,1), omega outside (0,2), epsilon <= 0, a count < 1, a tuning value with no kernel
+ * shape) give VA_ERR_INVALID, or a byte count of 0, and a message naming the field before anything is launched.
+ */
+typedef struct va_brox_params {
+    int struct_bytes;  /* sizeof(va_brox_params) of the caller; a smaller value is refused */
+    float alpha;       /* 0.197; weight of the smoothness term (frames are scaled to [0,1]) */
+    float gamma;       /* 50; weight of the gradient-constancy term; 0 turns it off */
+    float scale_step;  /* 0.8; in (0,1): the pyramid of S1 */
+    float omega;       /* 1.9; SOR relaxation, in (0,2) */
+    float epsilon;     /* 1e-3; the regulariser under every square root, > 0 */
+    int nscales;       /* 16: as deep as S1 allows (levels stop before min(w,h) < 16; a larger value is read as 16) */
+    int warps;         /* 1; warps (outer iterations) per level */
+    int inner_iters;   /* 10; lagged-nonlinearity steps per warp */
+    int solver_iters;  /* 10; red-black SOR sweeps per step */
+    int tuning[8];     /* shapes of the inner-step kernel (csrc/va_internal.h, VA_BROX_TUNE_*); va_brox_default_params fills
+                          in (-1, 0, 0, 0, 0, 0, 0, 0).  Results do not depend on any of them. */
+} va_brox_params;
+
+void va_brox_default_params(va_brox_params* p);
+
+/* Needs no device.  0 and a va_last_error text on bad parameters or sizes (w, h in [16,16384]). */
+size_t va_brox_workspace_bytes(int w, int h, int n_seq, int frames_per_seq, const va_brox_params* p);
+
+/* va_tvl1_flow's arguments and output layout: frames u8 or f32 in [0,255] [n_seq][frames_per_seq][h][w] gray ->
+ * flow f32 [n_seq*(frames_per_seq-1)][2][h][w]. */
+int va_brox_flow(va_ctx* ctx, const void* frames, int frames_are_u8, int n_seq, int frames_per_seq, int w, int h,
+                 const va_brox_params* p, void* flow, void* workspace, size_t workspace_bytes, void* stream);
+
+/*
+ * Test entry: exactly one inner step of S60-S61 (the coefficients from du, dv as they come in, then solver_iters red-black
+ * SOR sweeps) on n fields of w x h dense f32 device arrays [n][h][w], in place on du, dv.  The step reads I1wx .. I1wyy,
+ * Iz, Ixz, Iyz, u, v; I0x, I0y and I1w enter only through the differences and are not read.  scratch: 256-byte aligned,
+ * >= 4*n*w*h floats (the ping-pong fields of the tiled launches).  w, h in [16,16384].
+ */
+int va_brox_inner_step(va_ctx* ctx, const void* I0x, const void* I0y, const void* I1w, const void* I1wx, const void* I1wy,
+                       const void* I1wxx, const void* I1wxy, const void* I1wyy, const void* Iz, const void* Ixz,
+                       const void* Iyz, const void* u, const void* v, void* du, void* dv, int n, int w, int h,
+                       const va_brox_params* p, void* scratch, size_t scratch_bytes, void* stream);
+
 /*
  * flow f32 [n_pairs][2][h][w] -> stack f32 [2*n_pairs][h][w]: channel 2k = x flow of pair k,
  * 2k+1 = y flow (Sheet03/temporalModel.py:83).  Each value is quantised to the 8-bit flow

@@ -43,6 +43,7 @@ EXPORTS = [
     "va_jpeg_decode_workspace_bytes", "va_jpeg_decode", "va_jpeg_idct", "va_jpeg_upsample",
     "va_jpeg_encode_workspace_bytes", "va_jpeg_encode", "va_jpeg_fdct", "va_jpeg_entropy_encode",
     "va_tvl1_workspace_bytes_opt", "va_tvl1_flow_opt", "va_flow_median",
+    "va_brox_default_params", "va_brox_workspace_bytes", "va_brox_flow", "va_brox_inner_step",
 ]
 
 
@@ -92,6 +93,31 @@ def tvl1_options(params):
     if median == 0 and every == 0:
         return None
     return Tvl1Options(ctypes.sizeof(Tvl1Options), median, every)
+
+
+# names of the slots of va_brox_params.tuning (csrc/va_internal.h, VA_BROX_TUNE_*)
+BROX_TUNING_SLOTS = ("whole_field", "tile_w", "tile_h", "sweeps_per_launch")
+
+
+class BroxParams(ctypes.Structure):
+    """Mirror of ``va_brox_params`` (include/va.h)."""
+    _fields_ = [
+        ("struct_bytes", ctypes.c_int),
+        ("alpha", ctypes.c_float),
+        ("gamma", ctypes.c_float),
+        ("scale_step", ctypes.c_float),
+        ("omega", ctypes.c_float),
+        ("epsilon", ctypes.c_float),
+        ("nscales", ctypes.c_int),
+        ("warps", ctypes.c_int),
+        ("inner_iters", ctypes.c_int),
+        ("solver_iters", ctypes.c_int),
+        ("tuning", ctypes.c_int * 8),
+    ]
+
+
+for _i, _name in enumerate(BROX_TUNING_SLOTS):
+    setattr(BroxParams, _name, _tuning_property(_i))
 
 
 class SolverParams(ctypes.Structure):
@@ -166,6 +192,14 @@ def lib():
     L.va_tvl1_flow_opt.restype = ci
     L.va_flow_median.argtypes = [vp, vp, ci, ci, ci, ci, vp, vp]
     L.va_flow_median.restype = ci
+    L.va_brox_default_params.argtypes = [ctypes.POINTER(BroxParams)]
+    L.va_brox_default_params.restype = None
+    L.va_brox_workspace_bytes.argtypes = [ci, ci, ci, ci, ctypes.POINTER(BroxParams)]
+    L.va_brox_workspace_bytes.restype = sz
+    L.va_brox_flow.argtypes = [vp, vp, ci, ci, ci, ci, ci, ctypes.POINTER(BroxParams), vp, vp, sz, vp]
+    L.va_brox_flow.restype = ci
+    L.va_brox_inner_step.argtypes = [vp] + [vp] * 15 + [ci, ci, ci, ctypes.POINTER(BroxParams), vp, sz, vp]
+    L.va_brox_inner_step.restype = ci
     L.va_flow_to_stack.argtypes = [vp, vp, ci, ci, ci, cf, cf, cf, vp, vp]
     L.va_flow_to_stack.restype = ci
     L.va_flow_to_stack_crop.argtypes = [vp, vp, ci, ci, ci, cf, cf, cf, vp, ci, ci, vp, vp]
@@ -334,6 +368,18 @@ def default_tvl1_params(**over):
             k = "lambda_"
         if not hasattr(p, k):
             raise ValueError("unknown TV-L1 parameter %r" % k)
+        setattr(p, k, v)
+    return p
+
+
+def default_brox_params(**over):
+    """``va_brox_default_params`` with keyword overrides: alpha, gamma, scale_step, omega, epsilon, nscales, warps,
+    inner_iters, solver_iters and the tuning slots ``BROX_TUNING_SLOTS``.  An unknown name raises ValueError."""
+    p = BroxParams()
+    lib().va_brox_default_params(ctypes.byref(p))
+    for k, v in over.items():
+        if k == "struct_bytes" or not hasattr(p, k):
+            raise ValueError("unknown Brox parameter %r" % k)
         setattr(p, k, v)
     return p
 

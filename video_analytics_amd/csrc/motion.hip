@@ -57,21 +57,10 @@ __global__ void __launch_bounds__(kMeansThreads) k_flow_field_means(const float*
     }
 }
 
-// S12's bilinear sample of plane f at (px, py): the position is clamped into the frame (a NaN lands on 0), the taps are
-// the four neighbours (the last row / column repeats), and the interpolation is plain float32 (no fused multiply-add: the
-// library builds with -ffp-contract=off).
+// S12's bilinear sample of plane f at (px, py): va_bilinear_plain (va_internal.h) on dense rows
 __device__ __forceinline__ float bilinear(const float* __restrict__ f, int w, int h, float px, float py)
 {
-    const float xc = fminf(fmaxf(px, 0.0f), (float)(w - 1)), yc = fminf(fmaxf(py, 0.0f), (float)(h - 1));
-    const int x0 = (int)floorf(xc), y0 = (int)floorf(yc);
-    const int x1 = min(x0 + 1, w - 1), y1 = min(y0 + 1, h - 1);
-    const float ax = xc - (float)x0, ay = yc - (float)y0;
-    const float* r0 = f + (size_t)y0 * w;
-    const float* r1 = f + (size_t)y1 * w;
-    const float a = r0[x0], b = r0[x1], c = r1[x0], d = r1[x1];
-    const float top = a + ax * (b - a);
-    const float bot = c + ax * (d - c);
-    return top + ay * (bot - top);
+    return va_bilinear_plain(f, w, h, w, px, py);
 }
 
 // S12: flow f32 [n_chains*chain_len][2][h][w] -> out of the same shape.  Block (blockIdx.x, blockIdx.y = chain b): the

@@ -2269,3 +2269,61 @@ extern "C" int va_tvl1_profile_levels(va_ctx* ctx, double* out, int n, int reset
         for (int s = 0; s < kVaProfLevels; ++s) ctx->prof_level_ms[s] = ctx->prof_level_pxiters[s] = ctx->prof_level_launches[s] = 0.0;
     return VA_OK;
 }
+
+// ---- S1, S2, S8 for the other flow method of the library (brox.hip): the kernels above, launched as
+// va_tvl1_flow launches them, on the caller's buffers in TV-L1's layout (frames [frame][3][plane], state [pair][6][plane]
+// in plain row order).  Nothing here is on va_tvl1_flow's own path.
+
+void va_stage_layout(int w, int h, int* pitch, size_t* plane)
+{
+    *pitch = level_pitch(w);
+    *plane = va_align_up((size_t)*pitch * h, 64);
+}
+
+// S1: levels 1 .. ns-1 of every frame from level 0 (plane 0 of pyr[0]); tmp1, tmp2: [NF][tmp_stride] scratch
+int va_stage_pyramid(float* const* pyr, const int* ws, const int* hs, const int* pitch, const size_t* plane, int ns, int NF,
+                     float* tmp1, float* tmp2, size_t tmp_stride, float step, hipStream_t st)
+{
+    const int TPB = 256;
+    Taps taps;
+    zoom_taps(step, &taps);
+    for (int s = 1; s < ns; ++s) {
+        const int pw = ws[s - 1], ph = hs[s - 1], pp = pitch[s - 1];
+        const dim3 g(va_cdiv(pw * ph, TPB), NF);
+        k_gauss<false><<<g, TPB, 0, st>>>(pyr[s - 1], 3 * plane[s - 1], tmp1, tmp_stride, pw, ph, pp, taps);
+        k_gauss<true><<<g, TPB, 0, st>>>(tmp1, tmp_stride, tmp2, tmp_stride, pw, ph, pp, taps);
+        const dim3 g2(va_cdiv(ws[s] * hs[s], TPB), NF);
+        k_resample<<<g2, TPB, 0, st>>>(tmp2, tmp_stride, pw, ph, pp, pyr[s], 3 * plane[s], ws[s], hs[s], pitch[s]);
+        VA_LAUNCH_CHECK();
+    }
+    return VA_OK;
+}
+
+// S2: planes 1, 2 of every frame's [3][plane] block <- the centred gradient of its plane 0
+int va_stage_gradient(float* pyr, int w, int h, int pitch, size_t plane, int NF, hipStream_t st)
+{
+    k_grad<<<dim3(va_cdiv(w * h, 256), NF), 256, 0, st>>>(pyr, w, h, pitch, plane);
+    VA_LAUNCH_CHECK();
+    return VA_OK;
+}
+
+// S8: planes 0, 1 of the coarse state -> planes 0, 1 of the fine state (through tmp [pair][2][fplane]); the fine state's
+// planes 2..5 and its pitch padding become 0 (k_level_init).  The coarse and the fine state may be the same buffer.
+int va_stage_upsample(const float* cstate, int cw, int ch, int cpitch, size_t cplane, float* tmp, float* fstate, int fw, int fh,
+                      int fpitch, size_t fplane, float inv_step, int NP, hipStream_t st)
+{
+    const int TPB = 256;
+    k_upsample<<<dim3(va_cdiv(fw * fh, TPB), NP), TPB, 0, st>>>(cstate, cstate, nullptr, 0, cw, ch, cpitch, cplane, tmp, fw, fh, fpitch,
+                                                                 fplane, inv_step, 0);
+    k_level_init<<<dim3(va_cdiv(fpitch * fh, TPB), NP), TPB, 0, st>>>(tmp, fstate, fw, fh, fpitch, fplane, 0);
+    VA_LAUNCH_CHECK();
+    return VA_OK;
+}
+
+// planes 0, 1 of the state -> flow [pair][2][h][w]
+int va_stage_flow_out(const float* state, int w, int h, int pitch, size_t plane, float* flow, int NP, hipStream_t st)
+{
+    k_flow_out<<<dim3(va_cdiv(w * h, 256), NP), 256, 0, st>>>(state, state, nullptr, 0, w, h, pitch, plane, flow, 0);
+    VA_LAUNCH_CHECK();
+    return VA_OK;
+}

@@ -79,6 +79,40 @@ enum {
     VA_TUNE_STREAM_QUEUE = 6,   // reserved: 0 (2 is accepted: a launch per pass, which is what runs)
     VA_TUNE_ROWS_CFG = 7,       // reserved: 0
 };
+// va_brox_params.tuning[]: shapes of the inner-step kernel (brox.hip).  No value changes a result.
+enum {
+    VA_BROX_TUNE_WHOLE = 0,   // -1: a level whose field fits one workgroup runs there whole; 0: every level is tiled
+    VA_BROX_TUNE_TILE_W = 1,  // 0: the largest tile the sweep depth allows; else the tile's width in pixels
+    VA_BROX_TUNE_TILE_H = 2,  // likewise its height
+    VA_BROX_TUNE_K = 3,       // 0: default; else the SOR sweeps of one tiled launch (halo 2K + 2), at most solver_iters
+};                            // (slots 4..7: reserved, 0)
+
+// S12's bilinear sample of plane f (rows `pitch` floats apart) at (px, py): the position is clamped into the frame (a NaN
+// lands on 0), the taps are the four neighbours (the last row / column repeats), and the interpolation is plain float32 (no
+// fused multiply-add: the library builds with -ffp-contract=off).  S58 samples the second frame's derivatives with it.
+__device__ __forceinline__ float va_bilinear_plain(const float* __restrict__ f, int w, int h, int pitch, float px, float py)
+{
+    const float xc = fminf(fmaxf(px, 0.0f), (float)(w - 1)), yc = fminf(fmaxf(py, 0.0f), (float)(h - 1));
+    const int x0 = (int)floorf(xc), y0 = (int)floorf(yc);
+    const int x1 = min(x0 + 1, w - 1), y1 = min(y0 + 1, h - 1);
+    const float ax = xc - (float)x0, ay = yc - (float)y0;
+    const float* r0 = f + (size_t)y0 * pitch;
+    const float* r1 = f + (size_t)y1 * pitch;
+    const float a = r0[x0], b = r0[x1], c = r1[x0], d = r1[x1];
+    const float top = a + ax * (b - a);
+    const float bot = c + ax * (d - c);
+    return top + ay * (bot - top);
+}
+
+// TV-L1's stages S1, S2, S8 as brox.hip launches them (defined in tvl1.hip beside their kernels)
+void va_stage_layout(int w, int h, int* pitch, size_t* plane);
+int va_stage_pyramid(float* const* pyr, const int* ws, const int* hs, const int* pitch, const size_t* plane, int ns, int NF,
+                     float* tmp1, float* tmp2, size_t tmp_stride, float step, hipStream_t st);
+int va_stage_gradient(float* pyr, int w, int h, int pitch, size_t plane, int NF, hipStream_t st);
+int va_stage_upsample(const float* cstate, int cw, int ch, int cpitch, size_t cplane, float* tmp, float* fstate, int fw, int fh,
+                      int fpitch, size_t fplane, float inv_step, int NP, hipStream_t st);
+int va_stage_flow_out(const float* state, int w, int h, int pitch, size_t plane, float* flow, int NP, hipStream_t st);
+
 static inline size_t va_align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 static inline int va_cdiv(int a, int b) { return (a + b - 1) / b; }
 

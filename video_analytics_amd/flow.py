@@ -43,7 +43,13 @@ def tvl1_flow(frames, params=None, ws_slot=0, out=None, **over):
     warps, epsilon, iters, scale_step, block_iters).  ``lambda`` is a Python keyword: pass it as ``lambda_=0.1`` (or as
     ``**{"lambda": 0.1}``, which is taken as the same field).  Parameters out of range (``va_tvl1_params`` in include/va.h)
     raise ValueError.
+
+    ``params`` may also be an ``_ffi.BroxParams``: the call is then ``brox_flow``'s, so that everything
+    built on this function -- ``tvl1_flow_concurrent``, ``rerun_camera``'s second pass, ``flowVolumesFromFrames`` and
+    ``TwoStreamPipeline`` with their ``tvl1_params`` -- computes Brox flow when it is handed one.
     """
+    if isinstance(params, _ffi.BroxParams):
+        return brox_flow(frames, params, ws_slot=ws_slot, out=out, **over)
     if not isinstance(frames, torch.Tensor) or not frames.is_cuda:
         raise ValueError("tvl1_flow: frames must be a CUDA tensor")
     if frames.dim() == 3:
@@ -81,6 +87,54 @@ def tvl1_flow(frames, params=None, ws_slot=0, out=None, **over):
     return flow
 
 
+def brox_flow(frames, params=None, ws_slot=0, out=None, **over):
+    """Brox optical flow (``va_brox_flow``), the two-stream paper's own method: frames, result, ``out``
+    and ``ws_slot`` as ``tvl1_flow`` has them (the two methods share the workspace slots).  ``params``: ``_ffi.BroxParams`` or
+    keyword overrides (alpha, gamma, scale_step, omega, epsilon, nscales, warps, inner_iters, solver_iters).  Parameters out
+    of range (``va_brox_params`` in include/va.h) raise ValueError; so does the median option of TV-L1 (S55), which this
+    method does not have."""
+    if not isinstance(frames, torch.Tensor) or not frames.is_cuda:
+        raise ValueError("brox_flow: frames must be a CUDA tensor")
+    if frames.dim() == 3:
+        frames = frames.unsqueeze(0)
+    if frames.dim() != 4:
+        raise ValueError("brox_flow: frames must be [S,F,H,W] or [F,H,W]")
+    if frames.dtype not in (torch.uint8, torch.float32):
+        raise ValueError("brox_flow: frames must be uint8 or float32")
+    _refuse_brox_median(params, over, "brox_flow")
+    frames = frames.contiguous()
+    S, F, H, W = frames.shape
+    p = params if params is not None else _ffi.default_brox_params(**over)
+    if not isinstance(p, _ffi.BroxParams):
+        raise ValueError("brox_flow: params must be an _ffi.BroxParams")
+    L = _ffi.lib()
+    c = _ffi.ctx(frames.device.index)
+    nbytes = L.va_brox_workspace_bytes(W, H, S, F, ctypes.byref(p))
+    if nbytes == 0:
+        raise ValueError(L.va_last_error().decode())
+    ws = _workspace(nbytes, frames.device, ws_slot)
+    if out is None:
+        flow = torch.empty((S * (F - 1), 2, H, W), dtype=torch.float32, device=frames.device)
+    else:
+        flow = out
+        if (tuple(flow.shape) != (S * (F - 1), 2, H, W) or flow.dtype != torch.float32 or flow.device != frames.device
+                or not flow.is_contiguous()):
+            raise ValueError("brox_flow: out must be a contiguous float32 [%d,2,%d,%d] tensor on the frames' device" % (S * (F - 1), H, W))
+    _ffi.check(L.va_brox_flow(c, _ffi.ptr(frames), int(frames.dtype == torch.uint8), S, F, W, H, ctypes.byref(p),
+                              _ffi.ptr(flow), _ffi.ptr(ws), ws.numel(), _ffi.stream_ptr(frames.device)))
+    return flow
+
+
+def _refuse_brox_median(params, over, who):
+    if "median" in over or "median_every" in over or getattr(params, "median", 0) or getattr(params, "median_every", 0):
+        raise ValueError("%s: median and median_every are options of TV-L1 (S55); Brox flow has no median filter" % who)
+
+
+def _refuse_brox(params, who):
+    if isinstance(params, _ffi.BroxParams):
+        raise ValueError("%s: describes TV-L1's kernels and takes an _ffi.Tvl1Params, not a BroxParams" % who)
+
+
 def median_filter(flow, ksize=5, out=None):
     """The filter of DESIGN.md S55 on stored flow (``va_flow_median``): flow ``[N,2,H,W]`` CUDA float32 -> the same shape,
     every plane replaced by its ``ksize`` x ``ksize`` median (3 or 5; window clamped to the plane, exact selection).
@@ -107,7 +161,7 @@ def flow_streams(device, n):
 
 
 def tvl1_flow_concurrent(frames, params=None, n_streams=2, out=None, after=None, join=True):
-    """Same result as ``tvl1_flow`` for ``[S,F,H,W]`` frames, with the sequences split into ``n_streams``
+    """Same result as ``tvl1_flow`` for ``[S,F,H,W]`` frames (``params``: a ``Tvl1Params`` or a ``BroxParams``), with the sequences split into ``n_streams``
     groups that run on separate HIP streams (each with its own workspace).  Kernels of the groups
     then overlap on the GPU: the un-overlapped HBM round trips and partial last rounds of one
     group's tile launches are filled by the other's (measured +10 % at 320 pairs).
@@ -598,7 +652,7 @@ def rerun_camera(frames, flow, params=None, out=None):
     """S54, TSN's two-pass warped flow -> ``(field, H, share)``: ``fit_homography`` of ``flow`` (the TV-L1 field of
     ``frames``, S21: ``H`` and ``share`` are the subtract form's), ``warp_pairs`` of the frames under it (S53), and
     ``tvl1_flow`` of those pairs with the same ``params``: ``field`` is that second pass's flow, written into ``out`` (over
-    the first pass when ``out is flow``).  Everything runs on the current stream; the second pass uses the TV-L1 workspace
+    the first pass when ``out is flow``; with a ``BroxParams`` the second pass is ``brox_flow``).  Everything runs on the current stream; the second pass uses the TV-L1 workspace
     slot ``RERUN_WS_SLOT``, one of its own.  (``TwoStreamPipeline`` runs the same three steps over its own buffers.)"""
     _check_flow(flow, "rerun_camera")
     frames = _check_frames(frames, "rerun_camera")
@@ -640,7 +694,12 @@ def apply_motion(flow, flow_count, motion="stack", mean_flow=False, out=None, *,
     means = flow_field_means(flow) if mean_flow else None
     return motion_field(flow, flow_count, trajectory=motion == "trajectory", means=means, out=out)
 
+
 def pyramid_sizes(w, h, params=None):
+    """The level sizes of S1 for ``params``: an ``_ffi.Tvl1Params`` or an ``_ffi.BroxParams`` (its ``scale_step`` and
+    ``nscales``; the two methods share the pyramid)."""
+    if isinstance(params, _ffi.BroxParams):
+        params = _ffi.default_tvl1_params(scale_step=params.scale_step, nscales=params.nscales)
     p = params if params is not None else _ffi.default_tvl1_params()
     ws = (ctypes.c_int * 16)()
     hs = (ctypes.c_int * 16)()
@@ -650,7 +709,8 @@ def pyramid_sizes(w, h, params=None):
 
 def tile_plan(w, h, params=None):
     """The register tiling ``tvl1_flow`` will use per pyramid level (host logic, no GPU needed):
-    list of dict(tile_w, tile_h, waves, block_iters, tiles_x, tiles_y)."""
+    list of dict(tile_w, tile_h, waves, block_iters, tiles_x, tiles_y).  A ``BroxParams`` raises ValueError."""
+    _refuse_brox(params, "tile_plan")
     p = params if params is not None else _ffi.default_tvl1_params()
     out = (ctypes.c_int * 96)()
     n = _ffi.lib().va_tvl1_tile_plan(w, h, ctypes.byref(p), out)
@@ -659,12 +719,15 @@ def tile_plan(w, h, params=None):
 
 
 def profile_enable(on=True, device=None):
+    _refuse_brox(on, "profile_enable")
+    _refuse_brox(device, "profile_enable")
     _ffi.check(_ffi.lib().va_tvl1_profile_enable(_ffi.ctx(device), int(bool(on))))
 
 
 def profile_levels(n_levels, reset=True, device=None):
     """Per pyramid level since the last reset: list of dict(ms, px_iters, launches) (call ``profile_read(reset=False)``
-    first: it synchronises the recorded events)."""
+    first: it synchronises the recorded events).  TV-L1's inner iterations only: a ``BroxParams`` raises ValueError."""
+    _refuse_brox(n_levels, "profile_levels")
     out = (ctypes.c_double * (3 * n_levels))()
     _ffi.check(_ffi.lib().va_tvl1_profile_levels(_ffi.ctx(device), out, n_levels, int(bool(reset))))
     return [dict(ms=out[3 * s], px_iters=out[3 * s + 1], launches=out[3 * s + 2]) for s in range(n_levels)]
@@ -673,7 +736,8 @@ def profile_levels(n_levels, reset=True, device=None):
 def profile_read(reset=True, device=None):
     """-> dict(ms, launches, px_iters, px_warps, union_ms) for the inner-iteration kernel since the last
     reset (``ms``: summed per-call kernel time; ``union_ms``: wall time with at least one call's
-    inner-iteration launches in flight -- they differ when several streams overlap)."""
+    inner-iteration launches in flight -- they differ when several streams overlap).  A ``BroxParams`` raises ValueError."""
+    _refuse_brox(reset, "profile_read")
     out = (ctypes.c_double * 5)()
     _ffi.check(_ffi.lib().va_tvl1_profile_read(_ffi.ctx(device), out, int(bool(reset))))
     return dict(ms=out[0], launches=out[1], px_iters=out[2], px_warps=out[3], union_ms=out[4])

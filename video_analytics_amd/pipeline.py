@@ -131,6 +131,10 @@ class TwoStreamPipeline(object):
     pipeline's own.  ``extract_flow`` then stores that flow and ``train_videos`` trains on it.  It costs a second TV-L1;
     ``homography`` and ``camera_share`` are the same.  ``"rerun"`` with ``camera="none"`` raises ValueError.
 
+    ``tvl1_params``: an ``_ffi.Tvl1Params`` (None: TV-L1's defaults) or an ``_ffi.BroxParams``.  With the latter every flow of
+    the pipeline -- ``run_batch``, ``run_video``, ``train_videos``, the second pass of ``camera_form="rerun"`` and what
+    ``extract_flow`` stores -- is Brox flow, the two-stream paper's own method (``flow.brox_flow``).
+
     ``rgb_diff``: True adds TSN's RGB-difference stream: ``self.diff``, a third VGG-16 of
     ``3 * rgb_diff_count`` input channels (seed ``diff_seed`` or ``weights[2]``; its first layer is the cross-modality copy of
     an RGB one) that ``submit_video`` / ``run_video`` and ``train_videos`` feed with the differences of each snippet's first
@@ -454,7 +458,7 @@ class TwoStreamPipeline(object):
         device; for RGB the gray frames and ``rescale=`` go through ``frames.prepare_frames`` as in ``submit_video``.
 
         The pairs are split into ``flow_streams`` contiguous chunks, each one TV-L1 sequence that includes its boundary frame
-        (every frame's pyramid is built once per chunk), with the pipeline's ``tvl1_params``; field t is the flow from frame
+        (every frame's pyramid is built once per chunk), with the pipeline's ``tvl1_params`` (a ``BroxParams`` there stores Brox flow, ``flow.brox_flow``); field t is the flow from frame
         t to frame t + 1 and equals ``flow.tvl1_flow`` of those two frames bit for bit.  The pipeline's ``camera`` step (S21,
         S22) is applied to every field before anything is stored, so the store of a ``camera="homography"`` pipeline is TSN's
         warped flow; with ``camera_form="rerun"`` it is TSN's own two-pass warped flow (S53, S54: the second TV-L1 is paid

@@ -298,6 +298,52 @@ int va_brox_inner_step(va_ctx* ctx, const void* I0x, const void* I0y, const void
                        const void* Iyz, const void* u, const void* v, void* du, void* dv, int n, int w, int h,
                        const va_brox_params* p, void* scratch, size_t scratch_bytes, void* stream);
 
+/* ------------------------------------------------------------------ Farneback flow --- */
+
+/*
+ * The third dense flow method: G. Farneback, "Two-frame motion estimation based on polynomial expansion", SCIA 2003, in
+ * the structure of OpenCV's calcOpticalFlowFarneback (the one flow method the modelled project calls by name:
+ * Sheet01.py:79, Sheet02.py:191; the defaults below are that call's arguments).  DESIGN.md S63-S67 are the specification:
+ * S1's pyramid, a quadratic fitted around every pixel, `iterations` passes per level of matrix update, window sum and 2x2
+ * solve.  It is the build's own specification, not OpenCV's arithmetic: no bit parity with OpenCV is claimed.  Values out of
+ * range (pyr_scale outside (0,1), winsize even or < 3 or > 63, poly_n not 5 or 7, poly_sigma <= 0, gaussian not 0 or 1, a
+ * count < 1, a tuning value with no kernel shape) give VA_ERR_INVALID, or a byte count of 0, and a message naming the field
+ * before anything is launched.
+ */
+typedef struct va_farneback_params {
+    int struct_bytes;  /* sizeof(va_farneback_params) of the caller; a smaller value is refused */
+    float pyr_scale;   /* 0.5; in (0,1): S1's scale_step */
+    float poly_sigma;  /* 1.2; standard deviation of the Gaussian applicability of the polynomial expansion, > 0 */
+    int levels;        /* 3; S1's nscales: levels stop before min(w,h) < 16, a larger value is read as the deepest S1 allows */
+    int winsize;       /* 15; side of the averaging window, odd, in [3,63] */
+    int iterations;    /* 3; passes per level */
+    int poly_n;        /* 5; radius of the applicability: 5 or 7 */
+    int gaussian;      /* 0: box window; 1: Gaussian window of the same support (OPTFLOW_FARNEBACK_GAUSSIAN) */
+    int tuning[8];     /* tile shapes of the two kernels (csrc/va_internal.h, VA_FARNEBACK_TUNE_*); 0 = the library's choice.
+                          Results do not depend on any of them. */
+} va_farneback_params;
+
+void va_farneback_default_params(va_farneback_params* p);
+
+/* Needs no device.  0 and a va_last_error text on bad parameters or sizes (w, h in [16,16384]). */
+size_t va_farneback_workspace_bytes(int w, int h, int n_seq, int frames_per_seq, const va_farneback_params* p);
+
+/* va_tvl1_flow's arguments and output layout: frames u8 or f32 in [0,255] [n_seq][frames_per_seq][h][w] gray ->
+ * flow f32 [n_seq*(frames_per_seq-1)][2][h][w]. */
+int va_farneback_flow(va_ctx* ctx, const void* frames, int frames_are_u8, int n_seq, int frames_per_seq, int w, int h,
+                      const va_farneback_params* p, void* flow, void* workspace, size_t workspace_bytes, void* stream);
+
+/* Test entry: S64 alone.  fields f32 [n][h][w] -> coef f32 [n][5][h][w]: (b_x, b_y, a_xx, a_yy, a_xy).  w, h in [16,16384]. */
+int va_farneback_polyexp(va_ctx* ctx, const void* fields, int n, int w, int h, const va_farneback_params* p, void* coef,
+                         void* stream);
+
+/*
+ * Test entry: exactly one pass of S65-S67 on n pairs.  coef0, coef1 f32 [n][5][h][w] (the first and the second frame's
+ * coefficients), flow_in f32 [n][2][h][w] -> flow_out of the same shape, which must not be flow_in.  w, h in [16,16384].
+ */
+int va_farneback_pass(va_ctx* ctx, const void* coef0, const void* coef1, const void* flow_in, void* flow_out, int n, int w,
+                      int h, const va_farneback_params* p, void* stream);
+
 /*
  * flow f32 [n_pairs][2][h][w] -> stack f32 [2*n_pairs][h][w]: channel 2k = x flow of pair k,
  * 2k+1 = y flow (Sheet03/temporalModel.py:83).  Each value is quantised to the 8-bit flow

@@ -44,6 +44,7 @@ EXPORTS = [
     "va_jpeg_encode_workspace_bytes", "va_jpeg_encode", "va_jpeg_fdct", "va_jpeg_entropy_encode",
     "va_tvl1_workspace_bytes_opt", "va_tvl1_flow_opt", "va_flow_median",
     "va_brox_default_params", "va_brox_workspace_bytes", "va_brox_flow", "va_brox_inner_step",
+    "va_farneback_default_params", "va_farneback_workspace_bytes", "va_farneback_flow", "va_farneback_polyexp", "va_farneback_pass",
 ]
 
 
@@ -118,6 +119,29 @@ class BroxParams(ctypes.Structure):
 
 for _i, _name in enumerate(BROX_TUNING_SLOTS):
     setattr(BroxParams, _name, _tuning_property(_i))
+
+
+# names of the slots of va_farneback_params.tuning (csrc/va_internal.h, VA_FARNEBACK_TUNE_*)
+FARNEBACK_TUNING_SLOTS = ("poly_tile_w", "poly_tile_h", "pass_tile_w", "pass_tile_h")
+
+
+class FarnebackParams(ctypes.Structure):
+    """Mirror of ``va_farneback_params`` (include/va.h)."""
+    _fields_ = [
+        ("struct_bytes", ctypes.c_int),
+        ("pyr_scale", ctypes.c_float),
+        ("poly_sigma", ctypes.c_float),
+        ("levels", ctypes.c_int),
+        ("winsize", ctypes.c_int),
+        ("iterations", ctypes.c_int),
+        ("poly_n", ctypes.c_int),
+        ("gaussian", ctypes.c_int),
+        ("tuning", ctypes.c_int * 8),
+    ]
+
+
+for _i, _name in enumerate(FARNEBACK_TUNING_SLOTS):
+    setattr(FarnebackParams, _name, _tuning_property(_i))
 
 
 class SolverParams(ctypes.Structure):
@@ -200,6 +224,16 @@ def lib():
     L.va_brox_flow.restype = ci
     L.va_brox_inner_step.argtypes = [vp] + [vp] * 15 + [ci, ci, ci, ctypes.POINTER(BroxParams), vp, sz, vp]
     L.va_brox_inner_step.restype = ci
+    L.va_farneback_default_params.argtypes = [ctypes.POINTER(FarnebackParams)]
+    L.va_farneback_default_params.restype = None
+    L.va_farneback_workspace_bytes.argtypes = [ci, ci, ci, ci, ctypes.POINTER(FarnebackParams)]
+    L.va_farneback_workspace_bytes.restype = sz
+    L.va_farneback_flow.argtypes = [vp, vp, ci, ci, ci, ci, ci, ctypes.POINTER(FarnebackParams), vp, vp, sz, vp]
+    L.va_farneback_flow.restype = ci
+    L.va_farneback_polyexp.argtypes = [vp, vp, ci, ci, ci, ctypes.POINTER(FarnebackParams), vp, vp]
+    L.va_farneback_polyexp.restype = ci
+    L.va_farneback_pass.argtypes = [vp, vp, vp, vp, vp, ci, ci, ci, ctypes.POINTER(FarnebackParams), vp]
+    L.va_farneback_pass.restype = ci
     L.va_flow_to_stack.argtypes = [vp, vp, ci, ci, ci, cf, cf, cf, vp, vp]
     L.va_flow_to_stack.restype = ci
     L.va_flow_to_stack_crop.argtypes = [vp, vp, ci, ci, ci, cf, cf, cf, vp, ci, ci, vp, vp]
@@ -381,6 +415,22 @@ def default_brox_params(**over):
         if k == "struct_bytes" or not hasattr(p, k):
             raise ValueError("unknown Brox parameter %r" % k)
         setattr(p, k, v)
+    return p
+
+
+def default_farneback_params(**over):
+    """``va_farneback_default_params`` with keyword overrides: pyr_scale, poly_sigma, levels, winsize, iterations, poly_n,
+    gaussian and the tuning slots ``FARNEBACK_TUNING_SLOTS``.  An unknown name raises ValueError, and so does a value out of
+    range (the text is ``va_farneback_workspace_bytes``', which names the field)."""
+    p = FarnebackParams()
+    L = lib()
+    L.va_farneback_default_params(ctypes.byref(p))
+    for k, v in over.items():
+        if k == "struct_bytes" or not hasattr(p, k):
+            raise ValueError("unknown Farneback parameter %r" % k)
+        setattr(p, k, v)
+    if L.va_farneback_workspace_bytes(64, 64, 1, 2, ctypes.byref(p)) == 0:
+        raise ValueError(L.va_last_error().decode())
     return p
 
 

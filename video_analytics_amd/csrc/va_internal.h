@@ -86,6 +86,13 @@ enum {
     VA_BROX_TUNE_TILE_H = 2,  // likewise its height
     VA_BROX_TUNE_K = 3,       // 0: default; else the SOR sweeps of one tiled launch (halo 2K + 2), at most solver_iters
 };                            // (slots 4..7: reserved, 0)
+// va_farneback_params.tuning[]: tile shapes of the two kernels (farneback.hip).  No value changes a result.
+enum {
+    VA_FARNEBACK_TUNE_POLY_TILE_W = 0,  // 0: the library's tile; else the tile width of k_farneback_polyexp in pixels
+    VA_FARNEBACK_TUNE_POLY_TILE_H = 1,  // likewise its height
+    VA_FARNEBACK_TUNE_PASS_TILE_W = 2,  // 0: the library's tile; else the tile width of k_farneback_pass
+    VA_FARNEBACK_TUNE_PASS_TILE_H = 3,  // likewise its height
+};                                      // (slots 4..7: reserved, 0)
 
 // S12's bilinear sample of plane f (rows `pitch` floats apart) at (px, py): the position is clamped into the frame (a NaN
 // lands on 0), the taps are the four neighbours (the last row / column repeats), and the interpolation is plain float32 (no

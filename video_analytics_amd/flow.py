@@ -46,10 +46,13 @@ def tvl1_flow(frames, params=None, ws_slot=0, out=None, **over):
 
     ``params`` may also be an ``_ffi.BroxParams``: the call is then ``brox_flow``'s, so that everything
     built on this function -- ``tvl1_flow_concurrent``, ``rerun_camera``'s second pass, ``flowVolumesFromFrames`` and
-    ``TwoStreamPipeline`` with their ``tvl1_params`` -- computes Brox flow when it is handed one.
+    ``TwoStreamPipeline`` with their ``tvl1_params`` -- computes Brox flow when it is handed one.  An
+    ``_ffi.FarnebackParams`` does the same for ``farneback_flow``.
     """
     if isinstance(params, _ffi.BroxParams):
         return brox_flow(frames, params, ws_slot=ws_slot, out=out, **over)
+    if isinstance(params, _ffi.FarnebackParams):
+        return farneback_flow(frames, params, ws_slot=ws_slot, out=out, **over)
     if not isinstance(frames, torch.Tensor) or not frames.is_cuda:
         raise ValueError("tvl1_flow: frames must be a CUDA tensor")
     if frames.dim() == 3:
@@ -133,6 +136,49 @@ def _refuse_brox_median(params, over, who):
 def _refuse_brox(params, who):
     if isinstance(params, _ffi.BroxParams):
         raise ValueError("%s: describes TV-L1's kernels and takes an _ffi.Tvl1Params, not a BroxParams" % who)
+    if isinstance(params, _ffi.FarnebackParams):
+        raise ValueError("%s: describes TV-L1's kernels and takes an _ffi.Tvl1Params, not a FarnebackParams" % who)
+
+
+def farneback_flow(frames, params=None, ws_slot=0, out=None, **over):
+    """Farneback optical flow (``va_farneback_flow``), the direct method of the three: frames, result,
+    ``out`` and ``ws_slot`` as ``tvl1_flow`` has them (the three methods share the workspace slots).  ``params``:
+    ``_ffi.FarnebackParams`` or keyword overrides (pyr_scale, poly_sigma, levels, winsize, iterations, poly_n, gaussian).
+    Parameters out of range (``va_farneback_params`` in include/va.h) raise ValueError; so does the median option of TV-L1
+    (S55), which this method does not have."""
+    if not isinstance(frames, torch.Tensor) or not frames.is_cuda:
+        raise ValueError("farneback_flow: frames must be a CUDA tensor")
+    if frames.dim() == 3:
+        frames = frames.unsqueeze(0)
+    if frames.dim() != 4:
+        raise ValueError("farneback_flow: frames must be [S,F,H,W] or [F,H,W]")
+    if frames.dtype not in (torch.uint8, torch.float32):
+        raise ValueError("farneback_flow: frames must be uint8 or float32")
+    if "median" in over or "median_every" in over or getattr(params, "median", 0) or getattr(params, "median_every", 0):
+        raise ValueError("farneback_flow: median and median_every are options of TV-L1 (S55); Farneback flow has no median filter")
+    frames = frames.contiguous()
+    S, F, H, W = frames.shape
+    p = params if params is not None else _ffi.default_farneback_params(**over)
+    if not isinstance(p, _ffi.FarnebackParams):
+        raise ValueError("farneback_flow: params must be an _ffi.FarnebackParams")
+    if params is not None and over:
+        raise ValueError("farneback_flow: pass a FarnebackParams or keyword overrides, not both")
+    L = _ffi.lib()
+    c = _ffi.ctx(frames.device.index)
+    nbytes = L.va_farneback_workspace_bytes(W, H, S, F, ctypes.byref(p))
+    if nbytes == 0:
+        raise ValueError(L.va_last_error().decode())
+    ws = _workspace(nbytes, frames.device, ws_slot)
+    if out is None:
+        flow = torch.empty((S * (F - 1), 2, H, W), dtype=torch.float32, device=frames.device)
+    else:
+        flow = out
+        if (tuple(flow.shape) != (S * (F - 1), 2, H, W) or flow.dtype != torch.float32 or flow.device != frames.device
+                or not flow.is_contiguous()):
+            raise ValueError("farneback_flow: out must be a contiguous float32 [%d,2,%d,%d] tensor on the frames' device" % (S * (F - 1), H, W))
+    _ffi.check(L.va_farneback_flow(c, _ffi.ptr(frames), int(frames.dtype == torch.uint8), S, F, W, H, ctypes.byref(p),
+                                   _ffi.ptr(flow), _ffi.ptr(ws), ws.numel(), _ffi.stream_ptr(frames.device)))
+    return flow
 
 
 def median_filter(flow, ksize=5, out=None):
@@ -696,10 +742,12 @@ def apply_motion(flow, flow_count, motion="stack", mean_flow=False, out=None, *,
 
 
 def pyramid_sizes(w, h, params=None):
-    """The level sizes of S1 for ``params``: an ``_ffi.Tvl1Params`` or an ``_ffi.BroxParams`` (its ``scale_step`` and
-    ``nscales``; the two methods share the pyramid)."""
+    """The level sizes of S1 for ``params``: an ``_ffi.Tvl1Params``, an ``_ffi.BroxParams`` (its ``scale_step`` and
+    ``nscales``) or an ``_ffi.FarnebackParams`` (its ``pyr_scale`` and ``levels``); the three methods share the pyramid."""
     if isinstance(params, _ffi.BroxParams):
         params = _ffi.default_tvl1_params(scale_step=params.scale_step, nscales=params.nscales)
+    if isinstance(params, _ffi.FarnebackParams):  # (its ``pyr_scale`` and ``levels``)
+        params = _ffi.default_tvl1_params(scale_step=params.pyr_scale, nscales=params.levels)
     p = params if params is not None else _ffi.default_tvl1_params()
     ws = (ctypes.c_int * 16)()
     hs = (ctypes.c_int * 16)()

@@ -133,7 +133,8 @@ class TwoStreamPipeline(object):
 
     ``tvl1_params``: an ``_ffi.Tvl1Params`` (None: TV-L1's defaults) or an ``_ffi.BroxParams``.  With the latter every flow of
     the pipeline -- ``run_batch``, ``run_video``, ``train_videos``, the second pass of ``camera_form="rerun"`` and what
-    ``extract_flow`` stores -- is Brox flow, the two-stream paper's own method (``flow.brox_flow``).
+    ``extract_flow`` stores -- is Brox flow, the two-stream paper's own method (``flow.brox_flow``).  An
+    ``_ffi.FarnebackParams`` does the same for Farneback flow, the direct method (``flow.farneback_flow``).
 
     ``rgb_diff``: True adds TSN's RGB-difference stream: ``self.diff``, a third VGG-16 of
     ``3 * rgb_diff_count`` input channels (seed ``diff_seed`` or ``weights[2]``; its first layer is the cross-modality copy of

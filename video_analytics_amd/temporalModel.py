@@ -69,6 +69,7 @@ def flowVolumesFromFrames(gray, flowSampleSize=VIDEO_INPUT_FLOW_COUNT, tvl1_para
     L consecutive pairs, 8-bit quantisation, ToTensor+Normalize, x/y interleave -- the tensor
     ``TemporalDataset.__getitem__`` would have assembled from the upstream tool's JPEGs.  ``tvl1_params`` takes an
     ``_ffi.Tvl1Params`` or an ``_ffi.BroxParams``; with the latter the flow is Brox flow (``flow.brox_flow``).
+    An ``_ffi.FarnebackParams`` gives Farneback flow (``flow.farneback_flow``).
 
     ``crops``: CPU int32 ``[B*2L,3]`` (``augment.draw_flow_crops``): frames of any size >= 224 then give
     ``[B, 2L, 224, 224]``, each flow image cropped and flipped by its own row (Sheet03/temporalModel.py:86).

@@ -246,6 +246,43 @@ int va_tvl1_flow_opt(va_ctx* ctx, const void* frames, int frames_are_u8, int n_s
                      void* stream);
 
 /*
+ * The launches va_tvl1_flow_opt makes for a call of this shape, from the code that makes them (the level, chunk, warp and
+ * iteration loop runs dry: nothing is launched and no device is needed).  One record per inner-iteration launch and per
+ * median launch, in launch order:
+ *   level, warp     pyramid level (0 = the frame) and warp of the level
+ *   pair0, npairs   the chunk of pairs the launch covers (a register-tile level whose pairs exceed the cache runs them
+ *                   chunk by chunk: all warps of chunk 0, then chunk 1, ...)
+ *   w, h, pitch     the level's size and its row pitch in floats
+ *   family          VA_TVL1_LAUNCH_TILE (k_iter_tile), _STREAM (k_iter_stream) or _MEDIAN (k_median)
+ *   cfg             tile: the candidate (bit of tile_mask) 0..7; otherwise -1
+ *   waves, levels   tile: waves per workgroup, 0; stream: waves x levels per wave of the pipeline; median: 0, 0
+ *   eps, fast       the EPS and FAST template arguments (median: eps = the stopping rule is on, fast = 0)
+ *   median          median: the window (3 or 5); otherwise 0
+ *   K, it0          iterations the launch runs and the first of them within the warp (median: 0 and the iteration at whose
+ *                   head it filters)
+ *   grid_x, grid_y  the launch grid
+ *   strips, row_chunks, rows_per_chunk, halo_x
+ *                   stream: strips in x, chunks of rows, rows per chunk, x halo; tile: tiles in x, tiles in y, tile height,
+ *                   x halo; median: tiles in x, tiles in y, tile height, window radius
+ *   narrow, rev     stream: the last strips of two pairs share a wave; the workgroup order is reversed (tile and stream)
+ * records: HOST array of `capacity` records (NULL with capacity 0 to count).  Returns the number of launches of the call
+ * (only the first `capacity` are written), or -1 on bad arguments (va_last_error names the parameter).
+ */
+enum { VA_TVL1_LAUNCH_TILE = 0, VA_TVL1_LAUNCH_STREAM = 1, VA_TVL1_LAUNCH_MEDIAN = 2 };
+typedef struct va_tvl1_launch {
+    int level, warp, pair0, npairs;
+    int w, h, pitch;
+    int family, cfg, waves, levels;
+    int eps, fast, median;
+    int K, it0;
+    int grid_x, grid_y;
+    int strips, row_chunks, rows_per_chunk, halo_x;
+    int narrow, rev;
+} va_tvl1_launch;
+int va_tvl1_launch_plan(int w, int h, int n_seq, int frames_per_seq, const va_tvl1_params* p, const va_tvl1_options* opt,
+                        va_tvl1_launch* records, int capacity);
+
+/*
  * The filter of S55 on stored flow: flow f32 [n_fields][2][h][w] -> out of the same shape, every plane replaced by its
  * ksize x ksize median (ksize 3 or 5; any w, h >= 1: a plane narrower than the window is legal).  Only finite values
  * are specified; -0.0 and +0.0 compare equal.  out must not overlap flow (VA_ERR_INVALID).

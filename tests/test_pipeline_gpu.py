@@ -122,6 +122,9 @@ def test_full_batch_properties():
     assert float(fa[50:60].abs().max()) == 0.0
     alone = vflow.tvl1_flow(gray_d[7:8], epsilon=0.0)
     assert torch.equal(alone, fa[70:80])
+    # the 320 pairs go through the coarsest level in two chunks of 160 (tests/test_tvl1_launches_gpu.py): clip 21 lies in the second
+    alone = vflow.tvl1_flow(gray_d[21:22], epsilon=0.0)
+    assert torch.equal(alone, fa[210:220])
     # the flow tracks the synthetic motion field away from the borders
     c = slice(32, -32)
     err = (fa[0:10, :, c, c].cpu() - true_flow[0][:, c, c]).abs().mean()

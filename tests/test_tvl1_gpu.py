@@ -69,7 +69,15 @@ def test_block_depth_and_remainders_bit_exact(oracle_tvl1, block_iters, iters):
 def test_every_register_tile_candidate_bit_exact(oracle_tvl1, bit):
     # tile_mask forces one candidate of the inner-iteration kernel (8-wave 256x32 .. 64x128 and 4-wave
     # 256x16 .. 64x64): 300x150 needs several tiles with halos in x and in y for each of them; the
-    # epsilon run exercises the same instantiations with the stopping rule
+    # epsilon run exercises the same instantiations with the stopping rule.  That candidate `bit` alone runs, with several
+    # tiles and halos in x and y (pick_tiles allows every candidate when the forced one cannot fit its halo), is asserted from
+    # the launch report: the cases of tests/test_tvl1_launches_gpu.py with this frame and these parameters
+    from test_tvl1_launches_gpu import CAND, CAND_EPS, CASES, assert_claims
+    for cid, kw in (("cand%d_300x150" % bit, CAND), ("cand%d_300x150_eps" % bit, CAND_EPS)):
+        assert (CASES[cid]["W"], CASES[cid]["H"], CASES[cid]["S"], CASES[cid]["F"]) == (300, 150, 1, 3)
+        assert CASES[cid]["kw"] == dict(kw, tile_mask=1 << bit) and "only_c%d" % bit in CASES[cid]["must"]
+        assert_claims(cid)
+    assert CAND == dict(epsilon=0.0, iters=17, warps=2, nscales=2, block_iters=5) and CAND_EPS == dict(epsilon=0.02, iters=40, warps=1, nscales=2)
     gray = _frames(1, 3, 150, 300, seed=21 + bit)
     ref, out = _run_both(oracle_tvl1, gray, epsilon=0.0, iters=17, warps=2, nscales=2, block_iters=5, tile_mask=1 << bit)
     assert np.array_equal(out, ref), "max abs diff %g" % np.abs(out - ref).max()

@@ -42,7 +42,7 @@ EXPORTS = [
     "va_solver_default", "va_vgg16_set_solver", "va_vgg16_get_solver", "va_train_dropout_p",
     "va_jpeg_decode_workspace_bytes", "va_jpeg_decode", "va_jpeg_idct", "va_jpeg_upsample",
     "va_jpeg_encode_workspace_bytes", "va_jpeg_encode", "va_jpeg_fdct", "va_jpeg_entropy_encode",
-    "va_tvl1_workspace_bytes_opt", "va_tvl1_flow_opt", "va_flow_median",
+    "va_tvl1_workspace_bytes_opt", "va_tvl1_flow_opt", "va_flow_median", "va_tvl1_launch_plan",
     "va_brox_default_params", "va_brox_workspace_bytes", "va_brox_flow", "va_brox_inner_step",
     "va_farneback_default_params", "va_farneback_workspace_bytes", "va_farneback_flow", "va_farneback_polyexp", "va_farneback_pass",
 ]
@@ -86,6 +86,17 @@ for _i, _name in enumerate(TUNING_SLOTS):
 class Tvl1Options(ctypes.Structure):
     """Mirror of ``va_tvl1_options`` (include/va.h)."""
     _fields_ = [("struct_bytes", ctypes.c_int), ("median", ctypes.c_int), ("median_every", ctypes.c_int)]
+
+
+# va_tvl1_launch.family (include/va.h)
+TVL1_LAUNCH_FAMILIES = ("tile", "stream", "median")
+
+
+class Tvl1Launch(ctypes.Structure):
+    """Mirror of ``va_tvl1_launch`` (include/va.h): one launch of ``va_tvl1_launch_plan``'s report."""
+    _fields_ = [(name, ctypes.c_int) for name in (
+        "level", "warp", "pair0", "npairs", "w", "h", "pitch", "family", "cfg", "waves", "levels", "eps", "fast", "median",
+        "K", "it0", "grid_x", "grid_y", "strips", "row_chunks", "rows_per_chunk", "halo_x", "narrow", "rev")]
 
 
 def tvl1_options(params):
@@ -214,6 +225,9 @@ def lib():
     L.va_tvl1_workspace_bytes_opt.restype = sz
     L.va_tvl1_flow_opt.argtypes = [vp, vp, ci, ci, ci, ci, ci, ctypes.POINTER(Tvl1Params), ctypes.POINTER(Tvl1Options), vp, vp, sz, vp]
     L.va_tvl1_flow_opt.restype = ci
+    L.va_tvl1_launch_plan.argtypes = [ci, ci, ci, ci, ctypes.POINTER(Tvl1Params), ctypes.POINTER(Tvl1Options),
+                                      ctypes.POINTER(Tvl1Launch), ci]
+    L.va_tvl1_launch_plan.restype = ci
     L.va_flow_median.argtypes = [vp, vp, ci, ci, ci, ci, vp, vp]
     L.va_flow_median.restype = ci
     L.va_brox_default_params.argtypes = [ctypes.POINTER(BroxParams)]

@@ -1389,9 +1389,10 @@ __global__ void k_median_store(MedianArgs a)
     dst[o] = src[o];
 }
 
+dim3 median_grid(const MedianArgs& a, int npairs) { return dim3(a.ntx * va_cdiv(a.h, kMedTY), npairs, 2); }
 void launch_median(int ksize, const MedianArgs& a, int npairs, hipStream_t st)
 {
-    const dim3 grid(a.ntx * va_cdiv(a.h, kMedTY), npairs, 2), block(kMedTX, kMedTY / kMedRows);
+    const dim3 grid = median_grid(a, npairs), block(kMedTX, kMedTY / kMedRows);
     if (ksize == 3) k_median<3><<<grid, block, 0, st>>>(a);
     else k_median<5><<<grid, block, 0, st>>>(a);
 }
@@ -1490,10 +1491,11 @@ TilePick pick_tiles_auto(int w, int h, int iters, unsigned mask)
     return best;
 }
 
+dim3 iter_grid(const TilePick& tp, int npairs) { return dim3(tp.ntx * tp.nty, npairs); }
 template <bool EPS, bool FAST>
 void launch_iter(const TilePick& tp, const IterArgs& a, int npairs, hipStream_t st)
 {
-    const dim3 grid(tp.ntx * tp.nty, npairs);
+    const dim3 grid = iter_grid(tp, npairs);
     switch (tp.cfg) {
         case 0: k_iter_tile<2, 4, 8, 64, EPS, FAST><<<grid, 512, 0, st>>>(a); break;  // 256 x 32 tile
         case 1: k_iter_tile<2, 4, 8, 32, EPS, FAST><<<grid, 512, 0, st>>>(a); break;  // 128 x 64 (2 row groups per wave)
@@ -1692,7 +1694,7 @@ int check_params(const va_tvl1_params* p, int w, int h, int n_seq, int fps)
                      !(p->tile_mask & kRetiredRowsBit),
                  "va_tvl1: this tuning value selected a retired VA_EXPERIMENTS kernel family (k_iter_rows, k_iter_stream_q, k_iter_stream4, one "
                  "deep wave, two chains per wave, 3 x 5 / 3 x 6 / 4 x 6 waves x levels, 3 pixels per lane): measured slower and removed, see "
-                 "DESIGN.md section 7; commit eebd154 is the last one that contains them");
+                 "DESIGN.md section 7; commit eebd154 is the last one that contains them.  Valid stream_waves: 0, 1, 2, 7, 8, 9");
     VA_CHECK_ARG(p->tuning[VA_TUNE_STREAM_PPL] == 0 || p->tuning[VA_TUNE_STREAM_PPL] == 2, "va_tvl1: stream_ppl must be 0 (default) or 2");
     VA_CHECK_ARG(p->tuning[VA_TUNE_STREAM_QUEUE] == 0 || p->tuning[VA_TUNE_STREAM_QUEUE] == 2, "va_tvl1: stream_queue must be 0 (default) or 2 (a launch per pass)");
     VA_CHECK_ARG(p->tuning[VA_TUNE_STREAM_LEVELS] >= -1 && p->tuning[VA_TUNE_STREAM_LEVELS] < (1 << kMaxScales) && (sw >= 0 && sw < kMwFirst + kNumMwShapes) &&
@@ -1780,6 +1782,323 @@ va_prof_span prof_get(va_ctx* ctx)
     return s;
 }
 
+// The buffers of a call inside its workspace (make_plan's offsets)
+struct LevelBufs {
+    float* pyr[kMaxScales];
+    float *tmp1, *state[2], *ro;
+    unsigned long long* err;
+    int *sel, *base;
+};
+
+// va_tvl1_launch_plan's records: run_levels writes one next to every inner-iteration and median launch
+struct LaunchLog {
+    va_tvl1_launch* out;
+    int cap, n;
+    void add(const va_tvl1_launch& r)
+    {
+        if (n < cap) out[n] = r;
+        ++n;
+    }
+};
+
+// S5-S8 over the pyramid: the level, chunk, warp and iteration loop of va_tvl1_flow_opt, from the coarsest level's zero
+// state to level 0's result in state[*cur_out].  live: every kernel, memset and event goes to `st`.  Not live
+// (va_tvl1_launch_plan): the same decisions are taken and nothing touches a device -- ctx is NULL and B holds null pointers.
+// log (NULL: none) receives a record per inner-iteration and per median launch, live or not.
+int run_levels(va_ctx* ctx, const bool live, const Plan& P, const va_tvl1_params* p, const int median, const int median_every,
+               const LevelBufs& B, hipStream_t st, LaunchLog* log, int* cur_out)
+{
+    float* const* pyr = B.pyr;
+    float* const tmp1 = B.tmp1;
+    float* const state[2] = {B.state[0], B.state[1]};
+    float* const ro = B.ro;
+    unsigned long long* const err = B.err;
+    int* const sel = B.sel;
+    int* const base = B.base;
+    const bool eps = p->epsilon > 0.0f;
+    const bool prof = live && ctx->prof_on;
+    const int TPB = 256;
+    const int sc = P.ns - 1;
+    int cur = 0;
+    int K0 = p->block_iters;  // 0 = per-level automatic choice (12 on every level of the 224x224 pyramid's top three)
+    if (eps) K0 = 1;
+
+    for (int s = sc; s >= 0; --s) {
+        const int lw = P.ws[s], lh = P.hs[s], lp = P.pitch[s];
+        const size_t plane = P.plane[s];
+        const unsigned tmask = (unsigned)p->tile_mask & (unsigned)(kStreamBit - 1);
+        // (S55: the block depth is chosen for the run of iterations between two filters)
+        const TilePick tp = K0 > 0 ? pick_tiles(lw, lh, K0, tmask) : pick_tiles_auto(lw, lh, median ? median_every : p->iters, tmask);
+        const bool strm = P.lk[s] == LK_STREAM;
+        const int perm = strm ? 0 : 1;
+        if (live && lp != lw) {
+            k_zero_pad<<<dim3(va_cdiv((lp - lw) * lh * kNF_RO, TPB), P.NP), TPB, 0, st>>>(ro, kNF_RO, lw, lh, lp, plane, perm);
+            VA_LAUNCH_CHECK();
+        }
+        // the pairs of a level go through its warps x iterations in chunks (cache residency: chunk_pairs); every chunk
+        // starts from the level's entry buffer index and ends on the same one
+        const int cp = (eps || strm) ? P.NP : chunk_pairs(lw, lh, tp, P.NP);
+        const int cur_in = cur;
+        for (int c0 = 0; c0 < P.NP; c0 += cp) {
+            const int nc = P.NP - c0 < cp ? P.NP - c0 : cp;
+            const dim3 gpc(va_cdiv(lw * lh, TPB), nc);
+            cur = cur_in;
+            for (int wp = 0; wp < p->warps; ++wp) {
+                if (live) {
+                    k_warp<<<gpc, TPB, 0, st>>>(pyr[s], plane, lw, lh, lp, P.F, state[0], state[1], eps ? sel : nullptr, cur,
+                                                 eps ? base : nullptr, ro, c0, perm);
+                    VA_LAUNCH_CHECK();
+                    if (eps) VA_HIP(hipMemsetAsync(err, 0, (size_t)P.NP * p->iters * sizeof(unsigned long long), st));
+                }
+                va_prof_span span{};
+                if (prof) {
+                    span = prof_get(ctx);
+                    span.level = s;
+                    VA_HIP(hipEventRecord(span.beg, st));
+                }
+                IterArgs a{};
+                a.ro = ro;
+                a.stA = state[0];
+                a.stB = state[1];
+                a.outA = state[0];
+                a.outB = state[1];
+                a.base = base;
+                a.sel = sel;
+                a.err = err;
+                a.qthr = eps ? (unsigned long long)((double)p->epsilon * (double)p->epsilon * (double)lw * (double)lh * 4294967296.0) : 0ull;
+                a.plane = plane;
+                a.w = lw;
+                a.h = lh;
+                a.pitch = lp;
+                a.ntx = tp.ntx;
+                a.nty = tp.nty;
+                a.HX = tp.HX;
+                a.iters = p->iters;
+                a.l_t = p->lambda * p->theta;
+                a.taut = p->tau / p->theta;
+                a.theta = p->theta;
+                a.pair0 = c0;
+                int launches = 0;
+                // what every record of this warp and chunk shares
+                va_tvl1_launch rec{};
+                rec.level = s;
+                rec.warp = wp;
+                rec.pair0 = c0;
+                rec.npairs = nc;
+                rec.w = lw;
+                rec.h = lh;
+                rec.pitch = lp;
+                rec.cfg = -1;
+                rec.fast = p->fast_math != 0;
+                // one pass of the row pipeline in the shape nwv x kh over `grid`
+                auto stream_pass = [&](const StreamPick& sp, StreamArgs& sa, int nwv, int kh, const dim3& grid, int it) -> int {
+                    sa.sin = state[cur];
+                    sa.sout = state[cur ^ 1];
+                    sa.rev = launches & 1;
+                    if (log) {
+                        va_tvl1_launch r = rec;
+                        r.family = VA_TVL1_LAUNCH_STREAM;
+                        r.waves = nwv;
+                        r.levels = kh;
+                        r.K = sa.K;
+                        r.it0 = it;
+                        r.grid_x = (int)grid.x;
+                        r.grid_y = (int)grid.y;
+                        r.strips = sp.nsx;
+                        r.row_chunks = sp.nch;
+                        r.rows_per_chunk = sp.R;
+                        r.halo_x = sp.HX;
+                        r.narrow = sa.narrow;
+                        r.rev = sa.rev;
+                        log->add(r);
+                    }
+                    if (live)
+                        if (int rc = launch_stream(nwv, kh, p->fast_math != 0, grid, st, sa)) return rc;
+                    cur ^= 1;
+                    ++launches;
+                    return VA_OK;
+                };
+                // iterations it0 .. it0 + n - 1 of this warp, from state[cur]: the whole warp, or (S55) the segment between two filters
+                auto run_iters = [&](const int it0, const int n) -> int {
+                    if (strm) {
+                        const StreamPick sp = pick_stream(p, lw, lh, nc);
+                        StreamArgs sa{};
+                        sa.ro = ro;
+                        sa.plane = plane;
+                        sa.w = lw;
+                        sa.h = lh;
+                        sa.pitch = lp;
+                        sa.nsx = sp.nsx;
+                        sa.nch = sp.nch;
+                        sa.R = sp.R;
+                        sa.HX = sp.HX;
+                        sa.pair0 = c0;
+                        sa.l_t = a.l_t;
+                        sa.taut = a.taut;
+                        sa.theta = a.theta;
+                        const dim3 grid(sp.nsx * sp.nch, nc);
+                        // the four-wave passes of a level whose last strip fits 32 lanes: one wave for the last strips of two pairs
+                        const bool narrow = sp.narrow != 0;
+                        const dim3 grid_mw = narrow ? dim3((2 * sp.nsx - 1) * sp.nch, va_cdiv(nc, 2)) : grid;
+                        sa.npairs = nc;
+                        // pipelines of four waves: the passes share the iterations as evenly as possible, so that every pass
+                        // is deep enough to end in the last wave (K > (waves - 1) x levels per wave); otherwise the forms below run
+                        int mw_n = 0, mw_base = 0, mw_extra = 0;
+                        if (sp.nwv) {
+                            const int kmax = sp.nwv * sp.kh, kmin = (sp.nwv - 1) * sp.kh + 1;
+                            mw_n = va_cdiv(n, kmax);
+                            mw_base = n / mw_n;
+                            mw_extra = n % mw_n;
+                            if (mw_base < kmin) mw_n = 0;
+                        }
+                        int it = 0;
+                        for (int i = 0; i < mw_n; ++i) {
+                            sa.K = mw_base + (i < mw_extra ? 1 : 0);
+                            sa.narrow = narrow ? 1 : 0;
+                            if (int rc = stream_pass(sp, sa, sp.nwv, sp.kh, grid_mw, it0 + it)) return rc;
+                            sa.narrow = 0;
+                            it += sa.K;
+                        }
+                        for (it = mw_n ? n : 0; it < n;) {
+                            const int rem = n - it;
+                            // the two-wave kernel needs its last level in the second wave: a shorter remainder runs in one wave
+                            const bool fb = rem > (sp.fb_nwv - 1) * sp.fb_kh;
+                            const int nwv = fb ? sp.fb_nwv : 1, kh = fb ? sp.fb_kh : kStreamK1;
+                            sa.K = rem < nwv * kh ? rem : nwv * kh;
+                            if (int rc = stream_pass(sp, sa, nwv, kh, grid, it0 + it)) return rc;
+                            it += sa.K;
+                        }
+                    }
+                    for (int it = strm ? n : 0; it < n;) {
+                        // the tile grid depends on the halo depth: a shorter last launch gets its own grid
+                        const int k = (n - it) < tp.K ? (n - it) : tp.K;
+                        const TilePick tk = (k == tp.K) ? tp : pick_tiles(lw, lh, k, tmask);
+                        a.ntx = tk.ntx;
+                        a.nty = tk.nty;
+                        a.HX = tk.HX;
+                        a.cur = cur;
+                        a.K = tk.K;
+                        a.it = it0 + it;
+                        a.rev = launches & 1;
+                        if (log) {
+                            const TileCfg& c = kCfgs[tk.cfg];
+                            const dim3 grid = iter_grid(tk, nc);
+                            va_tvl1_launch r = rec;
+                            r.family = VA_TVL1_LAUNCH_TILE;
+                            r.cfg = tk.cfg;
+                            r.waves = c.NW;
+                            r.eps = eps;
+                            r.K = a.K;
+                            r.it0 = a.it;
+                            r.grid_x = (int)grid.x;
+                            r.grid_y = (int)grid.y;
+                            r.strips = tk.ntx;
+                            r.row_chunks = tk.nty;
+                            r.rows_per_chunk = c.NW * (64 / c.LX) * c.C;
+                            r.halo_x = tk.HX;
+                            r.rev = a.rev;
+                            log->add(r);
+                        }
+                        if (live) {
+                            if (eps) {
+                                if (p->fast_math) launch_iter<true, true>(tk, a, nc, st);
+                                else launch_iter<true, false>(tk, a, nc, st);
+                            } else {
+                                if (p->fast_math) launch_iter<false, true>(tk, a, nc, st);
+                                else launch_iter<false, false>(tk, a, nc, st);
+                            }
+                        }
+                        cur ^= 1;
+                        it += tk.K;
+                        ++launches;
+                    }
+                    return VA_OK;
+                };
+                if (!median) {
+                    if (int rc = run_iters(0, p->iters)) return rc;
+                } else {
+                    // S55: u1, u2 of every pair still iterating <- their median, at the head of iteration it0; through the
+                    // pyramid's scratch planes ([pair][2][plane]: NP x 2 planes fit the NF x 2 of tmp1, tmp2)
+                    MedianArgs m{};
+                    m.base = base;
+                    m.err = eps ? err : nullptr;
+                    m.qthr = a.qthr;
+                    m.plane = plane;
+                    m.iters = p->iters;
+                    m.w = lw;
+                    m.h = lh;
+                    m.pitch = lp;
+                    m.perm = perm;
+                    m.ntx = va_cdiv(lw, kMedTX);
+                    m.pair0 = c0;
+                    for (int it0 = 0; it0 < p->iters; it0 += median_every) {
+                        m.cur = cur;
+                        m.it = it0;
+                        m.srcA = state[0];
+                        m.srcB = state[1];
+                        m.src_nf = kNF_STATE;
+                        m.dstA = m.dstB = tmp1;
+                        m.dst_nf = 2;
+                        if (log) {
+                            const dim3 grid = median_grid(m, nc);
+                            va_tvl1_launch r = rec;
+                            r.family = VA_TVL1_LAUNCH_MEDIAN;
+                            r.fast = 0;
+                            r.eps = eps;
+                            r.median = median;
+                            r.it0 = it0;
+                            r.grid_x = (int)grid.x;
+                            r.grid_y = (int)grid.y;
+                            r.strips = m.ntx;
+                            r.row_chunks = va_cdiv(lh, kMedTY);
+                            r.rows_per_chunk = kMedTY;
+                            r.halo_x = median / 2;
+                            log->add(r);
+                        }
+                        if (live) launch_median(median, m, nc, st);
+                        m.srcA = m.srcB = tmp1;
+                        m.src_nf = 2;
+                        m.dstA = state[0];
+                        m.dstB = state[1];
+                        m.dst_nf = kNF_STATE;
+                        if (live) k_median_store<<<dim3(va_cdiv(lw * lh, TPB), nc, 2), TPB, 0, st>>>(m);
+                        const int n = p->iters - it0 < median_every ? p->iters - it0 : median_every;
+                        if (int rc = run_iters(it0, n)) return rc;
+                    }
+                }
+                if (live) VA_LAUNCH_CHECK();
+                if (prof) {
+                    VA_HIP(hipEventRecord(span.end, st));
+                    ctx->prof_spans.push_back(span);
+                    ctx->prof_launches += launches;
+                    ctx->prof_pxiters += (double)nc * lw * lh * p->iters;
+                    ctx->prof_pxwarps += (double)nc * lw * lh;
+                    if (s < kVaProfLevels) {
+                        ctx->prof_level_pxiters[s] += (double)nc * lw * lh * p->iters;
+                        ctx->prof_level_launches[s] += launches;
+                    }
+                }
+            }
+        }
+        if (s > 0) {
+            if (live) {
+                // ro is free between levels: use it as the upsampling target (2 of its 4 planes per pair)
+                const dim3 g(va_cdiv(P.ws[s - 1] * P.hs[s - 1], TPB), P.NP);
+                k_upsample<<<g, TPB, 0, st>>>(state[0], state[1], eps ? sel : nullptr, cur, lw, lh, lp, plane, ro, P.ws[s - 1],
+                                               P.hs[s - 1], P.pitch[s - 1], P.plane[s - 1], 1.0f / p->scale_step, perm);
+                const int fperm = P.lk[s - 1] != LK_TILE ? 0 : 1;
+                const dim3 gi(va_cdiv(P.pitch[s - 1] * P.hs[s - 1], TPB), P.NP);
+                k_level_init<<<gi, TPB, 0, st>>>(ro, state[0], P.ws[s - 1], P.hs[s - 1], P.pitch[s - 1], P.plane[s - 1], fperm);
+                VA_LAUNCH_CHECK();
+            }
+            cur = 0;
+            if (live && eps) VA_HIP(hipMemsetAsync(sel, 0, (size_t)P.NP * sizeof(int), st));
+        }
+    }
+    *cur_out = cur;
+    return VA_OK;
+}
+
 }  // namespace
 
 extern "C" void va_tvl1_default_params(va_tvl1_params* p)
@@ -1862,6 +2181,26 @@ extern "C" size_t va_tvl1_workspace_bytes_opt(int w, int h, int n_seq, int frame
     return P.total;
 }
 
+// The launches of a call, from run_levels itself running dry (host only, no device: include/va.h)
+extern "C" int va_tvl1_launch_plan(int w, int h, int n_seq, int frames_per_seq, const va_tvl1_params* p, const va_tvl1_options* opt,
+                                   va_tvl1_launch* records, int capacity)
+{
+    if (check_params(p, w, h, n_seq, frames_per_seq) != VA_OK) return -1;
+    int median, median_every;
+    if (check_options(opt, p, &median, &median_every) != VA_OK) return -1;
+    if (capacity < 0 || (capacity > 0 && !records)) {
+        va_set_error("va_tvl1_launch_plan: records is NULL or capacity negative");
+        return -1;
+    }
+    Plan P;
+    make_plan(P, w, h, n_seq, frames_per_seq, p);
+    const LevelBufs B{};
+    LaunchLog log{records, capacity, 0};
+    int cur = 0;
+    if (run_levels(nullptr, false, P, p, median, median_every, B, nullptr, &log, &cur) != VA_OK) return -1;
+    return log.n;
+}
+
 extern "C" int va_tvl1_flow(va_ctx* ctx, const void* frames, int frames_are_u8, int n_seq, int frames_per_seq, int w,
                             int h, const va_tvl1_params* p, void* flow, void* workspace, size_t workspace_bytes,
                             void* stream)
@@ -1931,209 +2270,16 @@ extern "C" int va_tvl1_flow_opt(va_ctx* ctx, const void* frames, int frames_are_
     VA_HIP(hipMemsetAsync(state[0], 0, (size_t)P.NP * kNF_STATE * P.plane[sc] * sizeof(float), st));
     VA_HIP(hipMemsetAsync(sel, 0, (size_t)P.NP * 2 * sizeof(int), st));
     int cur = 0;
-    int K0 = p->block_iters;  // 0 = per-level automatic choice (12 on every level of the 224x224 pyramid's top three)
-    if (eps) K0 = 1;
-
-    for (int s = sc; s >= 0; --s) {
-        const int lw = P.ws[s], lh = P.hs[s], lp = P.pitch[s];
-        const size_t plane = P.plane[s];
-        const unsigned tmask = (unsigned)p->tile_mask & (unsigned)(kStreamBit - 1);
-        // (S55: the block depth is chosen for the run of iterations between two filters)
-        const TilePick tp = K0 > 0 ? pick_tiles(lw, lh, K0, tmask) : pick_tiles_auto(lw, lh, median ? median_every : p->iters, tmask);
-        const bool strm = P.lk[s] == LK_STREAM;
-        const int perm = strm ? 0 : 1;
-        if (lp != lw) {
-            k_zero_pad<<<dim3(va_cdiv((lp - lw) * lh * kNF_RO, TPB), P.NP), TPB, 0, st>>>(ro, kNF_RO, lw, lh, lp, plane, perm);
-            VA_LAUNCH_CHECK();
-        }
-        // the pairs of a level go through its warps x iterations in chunks (cache residency: chunk_pairs); every chunk
-        // starts from the level's entry buffer index and ends on the same one
-        const int cp = (eps || strm) ? P.NP : chunk_pairs(lw, lh, tp, P.NP);
-        const int cur_in = cur;
-        for (int c0 = 0; c0 < P.NP; c0 += cp) {
-        const int nc = P.NP - c0 < cp ? P.NP - c0 : cp;
-        const dim3 gpc(va_cdiv(lw * lh, TPB), nc);
-        cur = cur_in;
-        for (int wp = 0; wp < p->warps; ++wp) {
-            k_warp<<<gpc, TPB, 0, st>>>(pyr[s], plane, lw, lh, lp, P.F, state[0], state[1], eps ? sel : nullptr, cur,
-                                         eps ? base : nullptr, ro, c0, perm);
-            VA_LAUNCH_CHECK();
-            if (eps) VA_HIP(hipMemsetAsync(err, 0, (size_t)P.NP * p->iters * sizeof(unsigned long long), st));
-            va_prof_span span{};
-            if (ctx->prof_on) {
-                span = prof_get(ctx);
-                span.level = s;
-                VA_HIP(hipEventRecord(span.beg, st));
-            }
-            IterArgs a{};
-            a.ro = ro;
-            a.stA = state[0];
-            a.stB = state[1];
-            a.outA = state[0];
-            a.outB = state[1];
-            a.base = base;
-            a.sel = sel;
-            a.err = err;
-            a.qthr = eps ? (unsigned long long)((double)p->epsilon * (double)p->epsilon * (double)lw * (double)lh * 4294967296.0) : 0ull;
-            a.plane = plane;
-            a.w = lw;
-            a.h = lh;
-            a.pitch = lp;
-            a.ntx = tp.ntx;
-            a.nty = tp.nty;
-            a.HX = tp.HX;
-            a.iters = p->iters;
-            a.l_t = p->lambda * p->theta;
-            a.taut = p->tau / p->theta;
-            a.theta = p->theta;
-            a.pair0 = c0;
-            int launches = 0;
-            // iterations it0 .. it0 + n - 1 of this warp, from state[cur]: the whole warp, or (S55) the segment between two filters
-            auto run_iters = [&](const int it0, const int n) -> int {
-            if (strm) {
-                const StreamPick sp = pick_stream(p, lw, lh, nc);
-                StreamArgs sa{};
-                sa.ro = ro;
-                sa.plane = plane;
-                sa.w = lw;
-                sa.h = lh;
-                sa.pitch = lp;
-                sa.nsx = sp.nsx;
-                sa.nch = sp.nch;
-                sa.R = sp.R;
-                sa.HX = sp.HX;
-                sa.pair0 = c0;
-                sa.l_t = a.l_t;
-                sa.taut = a.taut;
-                sa.theta = a.theta;
-                const dim3 grid(sp.nsx * sp.nch, nc);
-                // the four-wave passes of a level whose last strip fits 32 lanes: one wave for the last strips of two pairs
-                const bool narrow = sp.narrow != 0;
-                const dim3 grid_mw = narrow ? dim3((2 * sp.nsx - 1) * sp.nch, va_cdiv(nc, 2)) : grid;
-                sa.npairs = nc;
-                // pipelines of four waves: the passes share the iterations as evenly as possible, so that every pass
-                // is deep enough to end in the last wave (K > (waves - 1) x levels per wave); otherwise the forms below run
-                int mw_n = 0, mw_base = 0, mw_extra = 0;
-                if (sp.nwv) {
-                    const int kmax = sp.nwv * sp.kh, kmin = (sp.nwv - 1) * sp.kh + 1;
-                    mw_n = va_cdiv(n, kmax);
-                    mw_base = n / mw_n;
-                    mw_extra = n % mw_n;
-                    if (mw_base < kmin) mw_n = 0;
-                }
-                for (int i = 0; i < mw_n; ++i) {
-                    sa.K = mw_base + (i < mw_extra ? 1 : 0);
-                    sa.sin = state[cur];
-                    sa.sout = state[cur ^ 1];
-                    sa.rev = launches & 1;
-                    sa.narrow = narrow ? 1 : 0;
-                    if (int rc = launch_stream(sp.nwv, sp.kh, p->fast_math != 0, grid_mw, st, sa)) return rc;
-                    sa.narrow = 0;
-                    cur ^= 1;
-                    ++launches;
-                }
-                for (int it = mw_n ? n : 0; it < n;) {
-                    const int rem = n - it;
-                    // the two-wave kernel needs its last level in the second wave: a shorter remainder runs in one wave
-                    const bool fb = rem > (sp.fb_nwv - 1) * sp.fb_kh;
-                    const int nwv = fb ? sp.fb_nwv : 1, kh = fb ? sp.fb_kh : kStreamK1;
-                    sa.K = rem < nwv * kh ? rem : nwv * kh;
-                    sa.sin = state[cur];
-                    sa.sout = state[cur ^ 1];
-                    sa.rev = launches & 1;
-                    if (int rc = launch_stream(nwv, kh, p->fast_math != 0, grid, st, sa)) return rc;
-                    cur ^= 1;
-                    it += sa.K;
-                    ++launches;
-                }
-            }
-            for (int it = strm ? n : 0; it < n;) {
-                // the tile grid depends on the halo depth: a shorter last launch gets its own grid
-                const int k = (n - it) < tp.K ? (n - it) : tp.K;
-                const TilePick tk = (k == tp.K) ? tp : pick_tiles(lw, lh, k, tmask);
-                a.ntx = tk.ntx;
-                a.nty = tk.nty;
-                a.HX = tk.HX;
-                a.cur = cur;
-                a.K = tk.K;
-                a.it = it0 + it;
-                a.rev = launches & 1;
-                if (eps) {
-                    if (p->fast_math) launch_iter<true, true>(tk, a, nc, st);
-                    else launch_iter<true, false>(tk, a, nc, st);
-                } else {
-                    if (p->fast_math) launch_iter<false, true>(tk, a, nc, st);
-                    else launch_iter<false, false>(tk, a, nc, st);
-                }
-                cur ^= 1;
-                it += tk.K;
-                ++launches;
-            }
-            return VA_OK;
-            };
-            if (!median) {
-                if (int rc = run_iters(0, p->iters)) return rc;
-            } else {
-                // S55: u1, u2 of every pair still iterating <- their median, at the head of iteration it0; through the
-                // pyramid's scratch planes ([pair][2][plane]: NP x 2 planes fit the NF x 2 of tmp1, tmp2)
-                MedianArgs m{};
-                m.base = base;
-                m.err = eps ? err : nullptr;
-                m.qthr = a.qthr;
-                m.plane = plane;
-                m.iters = p->iters;
-                m.w = lw;
-                m.h = lh;
-                m.pitch = lp;
-                m.perm = perm;
-                m.ntx = va_cdiv(lw, kMedTX);
-                m.pair0 = c0;
-                for (int it0 = 0; it0 < p->iters; it0 += median_every) {
-                    m.cur = cur;
-                    m.it = it0;
-                    m.srcA = state[0];
-                    m.srcB = state[1];
-                    m.src_nf = kNF_STATE;
-                    m.dstA = m.dstB = tmp1;
-                    m.dst_nf = 2;
-                    launch_median(median, m, nc, st);
-                    m.srcA = m.srcB = tmp1;
-                    m.src_nf = 2;
-                    m.dstA = state[0];
-                    m.dstB = state[1];
-                    m.dst_nf = kNF_STATE;
-                    k_median_store<<<dim3(va_cdiv(lw * lh, TPB), nc, 2), TPB, 0, st>>>(m);
-                    const int n = p->iters - it0 < median_every ? p->iters - it0 : median_every;
-                    if (int rc = run_iters(it0, n)) return rc;
-                }
-            }
-            VA_LAUNCH_CHECK();
-            if (ctx->prof_on) {
-                VA_HIP(hipEventRecord(span.end, st));
-                ctx->prof_spans.push_back(span);
-                ctx->prof_launches += launches;
-                ctx->prof_pxiters += (double)nc * lw * lh * p->iters;
-                ctx->prof_pxwarps += (double)nc * lw * lh;
-                if (s < kVaProfLevels) {
-                    ctx->prof_level_pxiters[s] += (double)nc * lw * lh * p->iters;
-                    ctx->prof_level_launches[s] += launches;
-                }
-            }
-        }
-        }
-        if (s > 0) {
-            // ro is free between levels: use it as the upsampling target (2 of its 4 planes per pair)
-            const dim3 g(va_cdiv(P.ws[s - 1] * P.hs[s - 1], TPB), P.NP);
-            k_upsample<<<g, TPB, 0, st>>>(state[0], state[1], eps ? sel : nullptr, cur, lw, lh, lp, plane, ro, P.ws[s - 1],
-                                           P.hs[s - 1], P.pitch[s - 1], P.plane[s - 1], 1.0f / p->scale_step, perm);
-            const int fperm = P.lk[s - 1] != LK_TILE ? 0 : 1;
-            const dim3 gi(va_cdiv(P.pitch[s - 1] * P.hs[s - 1], TPB), P.NP);
-            k_level_init<<<gi, TPB, 0, st>>>(ro, state[0], P.ws[s - 1], P.hs[s - 1], P.pitch[s - 1], P.plane[s - 1], fperm);
-            VA_LAUNCH_CHECK();
-            cur = 0;
-            if (eps) VA_HIP(hipMemsetAsync(sel, 0, (size_t)P.NP * sizeof(int), st));
-        }
-    }
+    LevelBufs B{};
+    for (int s = 0; s < P.ns; ++s) B.pyr[s] = pyr[s];
+    B.tmp1 = tmp1;
+    B.state[0] = state[0];
+    B.state[1] = state[1];
+    B.ro = ro;
+    B.err = err;
+    B.sel = sel;
+    B.base = base;
+    if (int rc = run_levels(ctx, true, P, p, median, median_every, B, st, nullptr, &cur)) return rc;
     {
         const dim3 g(va_cdiv(w * h, TPB), P.NP);
         k_flow_out<<<g, TPB, 0, st>>>(state[0], state[1], eps ? sel : nullptr, cur, w, h, P.pitch[0], P.plane[0], (float*)flow,

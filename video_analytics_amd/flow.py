@@ -766,6 +766,32 @@ def tile_plan(w, h, params=None):
     return [dict(zip(keys, [out[6 * s + k] for k in range(6)])) for s in range(n)]
 
 
+def launch_plan(w, h, n_seq, frames_per_seq, params=None, **over):
+    """The inner-iteration and median launches ``tvl1_flow`` makes for ``n_seq`` sequences of ``frames_per_seq`` frames of
+    ``w`` x ``h``, in launch order, reported by the loop that makes them running dry (``va_tvl1_launch_plan``; host logic,
+    no GPU needed): a list of dicts with the fields of ``va_tvl1_launch`` (include/va.h), ``family`` as one of
+    ``_ffi.TVL1_LAUNCH_FAMILIES``.  ``params`` / keyword overrides as ``tvl1_flow`` takes them (``median``, ``median_every``
+    included); parameters out of range raise ValueError.  A ``BroxParams`` raises ValueError."""
+    _refuse_brox(params, "launch_plan")
+    p = params if params is not None else _ffi.default_tvl1_params(**over)
+    opt = _ffi.tvl1_options(p)
+    ref = ctypes.byref(opt) if opt is not None else None
+    L = _ffi.lib()
+    n = L.va_tvl1_launch_plan(w, h, n_seq, frames_per_seq, ctypes.byref(p), ref, None, 0)
+    if n < 0:
+        raise ValueError(L.va_last_error().decode())
+    recs = (_ffi.Tvl1Launch * max(n, 1))()
+    if L.va_tvl1_launch_plan(w, h, n_seq, frames_per_seq, ctypes.byref(p), ref, recs, n) != n:
+        raise RuntimeError("va_tvl1_launch_plan: two runs of one plan differ")
+    names = [f[0] for f in _ffi.Tvl1Launch._fields_]
+    out = []
+    for r in recs[:n]:
+        d = {k: getattr(r, k) for k in names}
+        d["family"] = _ffi.TVL1_LAUNCH_FAMILIES[d["family"]]
+        out.append(d)
+    return out
+
+
 def profile_enable(on=True, device=None):
     _refuse_brox(on, "profile_enable")
     _refuse_brox(device, "profile_enable")

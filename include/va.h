@@ -568,7 +568,7 @@ int va_frames_prepare(va_ctx* ctx, const void* src, int n, int w, int h, int src
                       void* gray_out, void* workspace, size_t workspace_bytes, void* stream);
 
 /*
- * Baseline JPEG decoding (DESIGN.md S45-S48): n images of one size, component count and sampling, value for value what
+ * Baseline JPEG decoding (DESIGN.md S28a-S48): n images of one size, component count and sampling, value for value what
  * libjpeg's default decompressor gives (Huffman decode, the "islow" integer IDCT, "fancy" chroma upsampling, fixed-point
  * YCbCr -> RGB).  The host parses the headers (video_analytics_amd/jpeg.py).  ncomp 1 (gray; hs = vs = 1) or 3 (YCbCr; luma
  * sampling hs x vs of 1x1, 2x1 or 2x2, chroma 1x1); w, h in 3..65535 and the MCU-padded samples of one image, all components
@@ -825,6 +825,42 @@ int va_train_loss_multitask(va_ctx* ctx, const float* logits, const void* labels
 /* Dropout(p = 0.5) of the step's classifier layer `layer` (0..2) in place on x f32 [n] (k_dropout, keys from
  * (dropout_seed, layer) as va_vgg16_train_step derives them). */
 int va_train_dropout(va_ctx* ctx, float* x, size_t n, unsigned long long dropout_seed, int layer, void* stream);
+
+/*
+ * The stages of va_linear_svm_fit (below) one at a time, for stage-by-stage tests: the fit's own
+ * loop is written over the same helpers, so a phase enqueues exactly the launches the fit enqueues for it.
+ *
+ * va_linear_svm_fit_layout (host only): offsets: HOST size_t[VA_SVM_FIT_FIELDS], the byte offsets into the workspace of
+ *   W G S R P HP          f64 [rows][dim + 1]   iterate, gradient, Newton direction, CG residual, CG direction, H P
+ *   M U Q                 f64 [n][rows]         margins Xh W, the active part of the last product's input, Xh S
+ *   part                  f64 [ceil(n / 256)][rows][dim + 1]   Xh^T U per 256-row chunk
+ *   losspart              f64 [ceil(n / 64)][rows]             squared hinge per 64-row block
+ *   f gn g0 steps rr cgtol cgs   f64 [rows]     objective, |G|, |G(0)|, Newton steps, the CG's |R|^2 and stop threshold, CG steps
+ *   live notdone          i32 [rows]            the row's CG is running; the row has not met the stop rule
+ * in this order, each on a 256-byte boundary.  Returns the total, equal to va_linear_svm_fit_workspace_bytes; sizes out of
+ * range, offsets == NULL or count != VA_SVM_FIT_FIELDS answer 0 and set va_last_error.
+ *
+ * va_linear_svm_fit_phase: x, y, n, dim, n_classes, C, intercept_scaling, tol, workspace, workspace_bytes, stream and their
+ * checks as va_linear_svm_fit's.  It reads and writes the solver state in the workspace and nothing else:
+ *   VA_SVM_PHASE_INIT         k_svm_init: the six vectors and seven scalars 0, live 0, notdone 1
+ *   VA_SVM_PHASE_EVAL_FIRST   k_svm_fwd<EVAL>, k_svm_xtu, k_svm_cls_grad(first = 1): M, U, f, G, the stop rule with g0 = gn,
+ *                             and the start of the CG (S = 0, R = P = -G, rr, cgtol, live)
+ *   VA_SVM_PHASE_EVAL         the same with first = 0: g0 is kept
+ *   VA_SVM_PHASE_CG           `count` (1 .. 100) rounds of k_svm_fwd<CG>, k_svm_xtu, k_svm_cls_cg
+ *   VA_SVM_PHASE_LINE_SEARCH  k_svm_fwd<LS>, k_svm_cls_ls
+ * `count` is read by the CG phase only.  An unknown phase or a CG count outside 1 .. 100: VA_ERR_INVALID before any launch.
+ * One Newton step of the fit is CG with count 100, LINE_SEARCH, EVAL; restart = 1 is INIT, EVAL_FIRST.
+ */
+#define VA_SVM_FIT_FIELDS 20
+#define VA_SVM_PHASE_INIT 0
+#define VA_SVM_PHASE_EVAL_FIRST 1
+#define VA_SVM_PHASE_EVAL 2
+#define VA_SVM_PHASE_CG 3
+#define VA_SVM_PHASE_LINE_SEARCH 4
+size_t va_linear_svm_fit_layout(int n, int dim, int n_class_rows, size_t* offsets, int count);
+int va_linear_svm_fit_phase(va_ctx* ctx, const void* x, const void* y, int n, int dim, int n_classes, double C,
+                            double intercept_scaling, double tol, int phase, int count, void* workspace,
+                            size_t workspace_bytes, void* stream);
 
 /*
  * Measurement hooks (bench.py): when enabled, va_tvl1_flow brackets every run of

@@ -34,6 +34,7 @@ EXPORTS = [
     "va_train_conv_backward_layer", "va_train_fc_backward_layer", "va_train_pool_layer", "va_train_loss", "va_train_dropout",
     "va_vgg16_train_step_multitask", "va_train_loss_multitask",
     "va_linear_svm_fit_workspace_bytes", "va_linear_svm_fit", "va_linear_svm_fit_cg_steps",
+    "va_linear_svm_fit_layout", "va_linear_svm_fit_phase",
     "va_vgg16_train_grad_floats", "va_vgg16_train_grad_layout", "va_vgg16_train_accumulate", "va_vgg16_train_apply_workspace_bytes",
     "va_vgg16_train_apply", "va_vgg16_unpack_grad", "va_train_conv_backward_layer_grad", "va_train_fc_backward_layer_grad",
     "va_color_jitter_u8",
@@ -352,6 +353,10 @@ def lib():
     L.va_linear_svm_fit_cg_steps.argtypes = [vp, ci, ci, ci, vp, sz, vp, vp]
     L.va_linear_svm_fit_cg_steps.restype = ci
     psz = ctypes.POINTER(sz)
+    L.va_linear_svm_fit_layout.argtypes = [ci, ci, ci, psz, ci]
+    L.va_linear_svm_fit_layout.restype = sz
+    L.va_linear_svm_fit_phase.argtypes = [vp, vp, vp, ci, ci, ci, cd, cd, cd, ci, ci, vp, sz, vp]
+    L.va_linear_svm_fit_phase.restype = ci
     L.va_vgg16_train_grad_floats.argtypes = [vp]
     L.va_vgg16_train_grad_floats.restype = sz
     L.va_vgg16_train_grad_layout.argtypes = [vp, psz, psz]

@@ -347,6 +347,7 @@ __global__ void k_svm_cg_steps(SvmState s, int c, double* __restrict__ out)
 }
 
 constexpr int kSvmMaxDim = 8192, kSvmMaxClasses = 4096;
+constexpr int kSvmFields = VA_SVM_FIT_FIELDS;  // the fields of SvmState, in svm_layout's order
 
 // The workspace, in order: six [c][D] vectors, three [n][c] matrices, the partial sums of both reductions, seven [c] scalars,
 // two [c] flags; every part starts on a 256-byte boundary.
@@ -395,13 +396,46 @@ extern "C" size_t va_linear_svm_fit_workspace_bytes(int n, int dim, int n_class_
     return svm_layout(n, dim, n_class_rows, nullptr, nullptr);
 }
 
-extern "C" int va_linear_svm_fit(va_ctx* ctx, const void* x, const void* y, int n, int dim, int n_classes, double C, double intercept_scaling,
-                                 double tol, int newton_iters, int restart, void* coef, void* intercept, void* stats, void* workspace,
-                                 size_t workspace_bytes, void* stream)
+namespace {
+
+// One problem's launch geometry and state: what every phase of the fit's loop needs.  The launches exist in this one copy;
+// va_linear_svm_fit and va_linear_svm_fit_phase both enqueue them through it.
+struct SvmRun {
+    const double* X;
+    const int* lab;
+    int n, dim, c, pos_off, D, chunks, row_blocks;
+    double C, sc, tol;
+    SvmState s;
+    hipStream_t st;
+    dim3 gfwd, gxtu;
+
+    void init() const { k_svm_init<<<(unsigned)(((size_t)c * D + 255) / 256), 256, 0, st>>>(s, c, D); }
+    // margins, loss and gradient at W, the stop rule, and the start of the next CG
+    void eval(int first) const
+    {
+        k_svm_fwd<SVM_EVAL><<<gfwd, 256, 0, st>>>(X, lab, n, dim, sc, c, pos_off, s.W, s.notdone, s.M, s.U, s.Q, s.losspart);
+        k_svm_xtu<<<gxtu, 256, 0, st>>>(X, n, dim, sc, c, s.U, s.notdone, s.part);
+        k_svm_cls_grad<<<c, 256, 0, st>>>(s, c, D, chunks, row_blocks, C, tol, first);
+    }
+    void cg(int rounds) const
+    {
+        for (int cg = 0; cg < rounds; ++cg) {
+            k_svm_fwd<SVM_CG><<<gfwd, 256, 0, st>>>(X, lab, n, dim, sc, c, pos_off, s.P, s.live, s.M, s.U, s.Q, s.losspart);
+            k_svm_xtu<<<gxtu, 256, 0, st>>>(X, n, dim, sc, c, s.U, s.live, s.part);
+            k_svm_cls_cg<<<c, 256, 0, st>>>(s, c, D, chunks, C);
+        }
+    }
+    void line_search() const
+    {
+        k_svm_fwd<SVM_LS><<<gfwd, 256, 0, st>>>(X, lab, n, dim, sc, c, pos_off, s.S, s.notdone, s.M, s.U, s.Q, s.losspart);
+        k_svm_cls_ls<<<c, 256, 0, st>>>(s, lab, n, c, D, pos_off, C);
+    }
+};
+
+// The argument checks va_linear_svm_fit and va_linear_svm_fit_phase share; fills `run` when they pass.
+int svm_prepare(const void* x, const void* y, int n, int dim, int n_classes, double C, double intercept_scaling, double tol,
+                void* workspace, size_t workspace_bytes, void* stream, SvmRun* run)
 {
-    VA_CHECK_ARG(ctx != nullptr, "va_linear_svm_fit: ctx is NULL");
-    VA_USE_DEVICE(ctx);
-    VA_CHECK_ARG(x && y && coef && intercept && stats && workspace, "va_linear_svm_fit: NULL pointer");
     VA_CHECK_ARG(n_classes >= 2 && n_classes <= kSvmMaxClasses, "va_linear_svm_fit: need 2 <= n_classes <= %d (got %d)", kSvmMaxClasses,
                  n_classes);
     const int c = n_classes == 2 ? 1 : n_classes, pos_off = n_classes == 2 ? 1 : 0;
@@ -410,45 +444,91 @@ extern "C" int va_linear_svm_fit(va_ctx* ctx, const void* x, const void* y, int 
     VA_CHECK_ARG(svm_finite(tol) && tol > 0.0, "va_linear_svm_fit: tol must be finite and > 0 (got %g)", tol);
     VA_CHECK_ARG(svm_finite(intercept_scaling) && intercept_scaling >= 0.0,
                  "va_linear_svm_fit: intercept_scaling must be finite and >= 0 (got %g)", intercept_scaling);
-    VA_CHECK_ARG(newton_iters >= 0 && newton_iters <= 1000, "va_linear_svm_fit: need 0 <= newton_iters <= 1000 (got %d)", newton_iters);
-    VA_CHECK_ARG(restart == 0 || restart == 1, "va_linear_svm_fit: restart must be 0 or 1 (got %d)", restart);
-    SvmState s;
-    const size_t need = svm_layout(n, dim, c, (char*)workspace, &s);
+    SvmRun r;
+    r.X = (const double*)x;
+    r.lab = (const int*)y;
+    r.n = n, r.dim = dim, r.c = c, r.pos_off = pos_off;
+    r.D = dim + 1, r.chunks = va_cdiv(n, kSvmChunkRows), r.row_blocks = va_cdiv(n, 64);
+    r.C = C, r.sc = intercept_scaling, r.tol = tol;
+    r.st = (hipStream_t)stream;
+    r.gfwd = dim3(r.row_blocks, va_cdiv(c, 64));
+    r.gxtu = dim3(r.chunks, va_cdiv(c, 64), va_cdiv(r.D, 64));
+    const size_t need = svm_layout(n, dim, c, (char*)workspace, &r.s);
     if (workspace_bytes < need) {
         va_set_error("va_linear_svm_fit: workspace of %zu bytes, %zu needed", workspace_bytes, need);
         return VA_ERR_WORKSPACE;
     }
     VA_CHECK_ARG(((size_t)workspace & 7) == 0, "va_linear_svm_fit: workspace must be 8-byte aligned");
+    *run = r;
+    return VA_OK;
+}
 
-    hipStream_t st = (hipStream_t)stream;
-    const int D = dim + 1, chunks = va_cdiv(n, kSvmChunkRows), row_blocks = va_cdiv(n, 64);
-    const double* X = (const double*)x;
-    const int* lab = (const int*)y;
-    const double sc = intercept_scaling;
-    const dim3 gfwd(row_blocks, va_cdiv(c, 64)), gxtu(chunks, va_cdiv(c, 64), va_cdiv(D, 64));
-    // margins, loss and gradient at W, the stop rule, and the start of the next CG
-    auto eval = [&](int first) {
-        k_svm_fwd<SVM_EVAL><<<gfwd, 256, 0, st>>>(X, lab, n, dim, sc, c, pos_off, s.W, s.notdone, s.M, s.U, s.Q, s.losspart);
-        k_svm_xtu<<<gxtu, 256, 0, st>>>(X, n, dim, sc, c, s.U, s.notdone, s.part);
-        k_svm_cls_grad<<<c, 256, 0, st>>>(s, c, D, chunks, row_blocks, C, tol, first);
-    };
+}  // namespace
+
+extern "C" int va_linear_svm_fit(va_ctx* ctx, const void* x, const void* y, int n, int dim, int n_classes, double C, double intercept_scaling,
+                                 double tol, int newton_iters, int restart, void* coef, void* intercept, void* stats, void* workspace,
+                                 size_t workspace_bytes, void* stream)
+{
+    VA_CHECK_ARG(ctx != nullptr, "va_linear_svm_fit: ctx is NULL");
+    VA_USE_DEVICE(ctx);
+    VA_CHECK_ARG(x && y && coef && intercept && stats && workspace, "va_linear_svm_fit: NULL pointer");
+    VA_CHECK_ARG(newton_iters >= 0 && newton_iters <= 1000, "va_linear_svm_fit: need 0 <= newton_iters <= 1000 (got %d)", newton_iters);
+    VA_CHECK_ARG(restart == 0 || restart == 1, "va_linear_svm_fit: restart must be 0 or 1 (got %d)", restart);
+    SvmRun run;
+    const int rc = svm_prepare(x, y, n, dim, n_classes, C, intercept_scaling, tol, workspace, workspace_bytes, stream, &run);
+    if (rc != VA_OK) return rc;
     if (restart) {
-        k_svm_init<<<(unsigned)(((size_t)c * D + 255) / 256), 256, 0, st>>>(s, c, D);
-        eval(1);
+        run.init();
+        run.eval(1);
         VA_LAUNCH_CHECK();
     }
     for (int it = 0; it < newton_iters; ++it) {
-        for (int cg = 0; cg < kSvmCgSteps; ++cg) {
-            k_svm_fwd<SVM_CG><<<gfwd, 256, 0, st>>>(X, lab, n, dim, sc, c, pos_off, s.P, s.live, s.M, s.U, s.Q, s.losspart);
-            k_svm_xtu<<<gxtu, 256, 0, st>>>(X, n, dim, sc, c, s.U, s.live, s.part);
-            k_svm_cls_cg<<<c, 256, 0, st>>>(s, c, D, chunks, C);
-        }
-        k_svm_fwd<SVM_LS><<<gfwd, 256, 0, st>>>(X, lab, n, dim, sc, c, pos_off, s.S, s.notdone, s.M, s.U, s.Q, s.losspart);
-        k_svm_cls_ls<<<c, 256, 0, st>>>(s, lab, n, c, D, pos_off, C);
-        eval(0);
+        run.cg(kSvmCgSteps);
+        run.line_search();
+        run.eval(0);
         VA_LAUNCH_CHECK();
     }
-    k_svm_export<<<c, 256, 0, st>>>(s, dim, sc, (double*)coef, (double*)intercept, (double*)stats);
+    k_svm_export<<<run.c, 256, 0, run.st>>>(run.s, dim, run.sc, (double*)coef, (double*)intercept, (double*)stats);
+    VA_LAUNCH_CHECK();
+    return VA_OK;
+}
+
+extern "C" size_t va_linear_svm_fit_layout(int n, int dim, int n_class_rows, size_t* offsets, int count)
+{
+    if (!svm_sizes_ok(n, dim, n_class_rows)) return 0;
+    if (offsets == nullptr || count != kSvmFields) {
+        va_set_error("va_linear_svm_fit_layout: offsets must hold exactly %d fields (got %s, count %d)", kSvmFields,
+                     offsets ? "a pointer" : "NULL", count);
+        return 0;
+    }
+    SvmState s;
+    const size_t total = svm_layout(n, dim, n_class_rows, nullptr, &s);
+    const void* field[kSvmFields] = {s.W, s.G, s.S, s.R, s.P, s.HP, s.M, s.U, s.Q, s.part, s.losspart, s.f, s.gn, s.g0,
+                                     s.steps, s.rr, s.cgtol, s.cgs, s.live, s.notdone};
+    for (int i = 0; i < kSvmFields; ++i) offsets[i] = (size_t)(uintptr_t)field[i];
+    return total;
+}
+
+extern "C" int va_linear_svm_fit_phase(va_ctx* ctx, const void* x, const void* y, int n, int dim, int n_classes, double C,
+                                       double intercept_scaling, double tol, int phase, int count, void* workspace, size_t workspace_bytes,
+                                       void* stream)
+{
+    VA_CHECK_ARG(ctx != nullptr, "va_linear_svm_fit_phase: ctx is NULL");
+    VA_USE_DEVICE(ctx);
+    VA_CHECK_ARG(x && y && workspace, "va_linear_svm_fit_phase: NULL pointer");
+    VA_CHECK_ARG(phase >= VA_SVM_PHASE_INIT && phase <= VA_SVM_PHASE_LINE_SEARCH, "va_linear_svm_fit_phase: unknown phase %d", phase);
+    VA_CHECK_ARG(phase != VA_SVM_PHASE_CG || (count >= 1 && count <= kSvmCgSteps),
+                 "va_linear_svm_fit_phase: the CG phase needs 1 <= count <= %d (got %d)", kSvmCgSteps, count);
+    SvmRun run;
+    const int rc = svm_prepare(x, y, n, dim, n_classes, C, intercept_scaling, tol, workspace, workspace_bytes, stream, &run);
+    if (rc != VA_OK) return rc;
+    switch (phase) {
+    case VA_SVM_PHASE_INIT: run.init(); break;
+    case VA_SVM_PHASE_EVAL_FIRST: run.eval(1); break;
+    case VA_SVM_PHASE_EVAL: run.eval(0); break;
+    case VA_SVM_PHASE_CG: run.cg(count); break;
+    default: run.line_search(); break;
+    }
     VA_LAUNCH_CHECK();
     return VA_OK;
 }

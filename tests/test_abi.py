@@ -174,6 +174,29 @@ def test_tvl1_plans_equal_the_recorded_ones(lib):
     assert int(got["levels"].min()) >= 1 and int(got["workspace"].min()) > 0  # every case of the grid is an accepted one
 
 
+def test_flow_plans_equal_the_recorded_ones(lib):
+    """va_brox_workspace_bytes, va_farneback_workspace_bytes and flow.pyramid_sizes through a BroxParams and a FarnebackParams,
+    over a grid of frame sizes, sequence and frame counts, scale steps, level counts and kernel shapes, reproduce
+    tests/golden/flow_plans.npz exactly: the file was recorded from the library before the three methods' front end became
+    one (tests/golden/make_flow_plan_golden.py)."""
+    import importlib.util
+    import numpy as np
+    path = os.path.join(ROOT, "tests", "golden", "make_flow_plan_golden.py")
+    spec = importlib.util.spec_from_file_location("make_flow_plan_golden", path)
+    gen = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(gen)
+    assert os.path.getsize(gen.OUT) < 100 * 1024
+    want, got = np.load(gen.OUT), gen.compute()
+    assert sorted(want.files) == sorted(got)
+    for name in want.files:
+        assert want[name].dtype == got[name].dtype and want[name].shape == got[name].shape, name
+        bad = np.argwhere(want[name] != got[name])
+        assert len(bad) == 0, "%s differs at %d places, first at index %s" % (name, len(bad), bad[0])
+    for method in ("brox", "farneback"):  # every case of the grid is an accepted one, in the recording too
+        for g in (want, got):
+            assert int(g[method + "_levels"].min()) >= 1 and int(g[method + "_workspace"].min()) > 0, method
+
+
 def test_public_header_is_plain_c(tmp_path):
     """include/va.h is a C ABI: it must compile as C99 (no C++ or torch types) with the system compiler."""
     import shutil

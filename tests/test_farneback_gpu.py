@@ -118,8 +118,10 @@ def _frames(kind):
     if kind == "80x64":  # [2,3,64,80] uint8: three levels
         _, gray, _ = synth.synth_clips(2, seed=3, H=64, W=80, n_gray=3)
         return gray
-    _, gray, _ = synth.synth_clips(2, seed=4, H=67, W=83, n_gray=3)  # [2,3,67,83] float32, not whole numbers
-    return gray.float() * 0.97 + 1.25
+    _, gray, _ = synth.synth_clips(2, seed=4, H=67, W=83, n_gray=3)  # [2,3,67,83]: rows of 83 in a pitch of 84
+    if kind == "83x67u8":
+        return gray
+    return gray.float() * 0.97 + 1.25  # float32, not whole numbers
 
 
 _flow_ref = {}
@@ -132,7 +134,7 @@ def _flow_reference(kind):
     return _flow_ref[kind]
 
 
-@pytest.mark.parametrize("kind", ["80x64", "83x67"])
+@pytest.mark.parametrize("kind", ["80x64", "83x67", "83x67u8"])
 def test_farneback_flow_is_the_oracle_through_every_entry(kind):
     """2 sequences of 3 frames, iterations 2: ``farneback_flow``, its keyword form, ``tvl1_flow`` and ``tvl1_flow_concurrent``
     handed the FarnebackParams, ``out=``, a workspace slot that a TV-L1 call and a Brox call left dirty, and a second tile

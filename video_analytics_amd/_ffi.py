@@ -413,43 +413,36 @@ def check(rc):
     raise RuntimeError(msg)
 
 
-def default_tvl1_params(**over):
-    p = Tvl1Params()
-    lib().va_tvl1_default_params(ctypes.byref(p))
+def _default_params(cls, fill, label, over, alias=None):
+    """``cls()`` filled by the library's ``fill``, then the keyword overrides; an unknown name raises ValueError."""
+    p = cls()
+    getattr(lib(), fill)(ctypes.byref(p))
     for k, v in over.items():
-        if k == "lambda":
-            k = "lambda_"
-        if not hasattr(p, k):
-            raise ValueError("unknown TV-L1 parameter %r" % k)
+        if k == alias:
+            k += "_"
+        if k == "struct_bytes" or not hasattr(p, k):
+            raise ValueError("unknown %s parameter %r" % (label, k))
         setattr(p, k, v)
     return p
+
+
+def default_tvl1_params(**over):
+    return _default_params(Tvl1Params, "va_tvl1_default_params", "TV-L1", over, alias="lambda")
 
 
 def default_brox_params(**over):
     """``va_brox_default_params`` with keyword overrides: alpha, gamma, scale_step, omega, epsilon, nscales, warps,
     inner_iters, solver_iters and the tuning slots ``BROX_TUNING_SLOTS``.  An unknown name raises ValueError."""
-    p = BroxParams()
-    lib().va_brox_default_params(ctypes.byref(p))
-    for k, v in over.items():
-        if k == "struct_bytes" or not hasattr(p, k):
-            raise ValueError("unknown Brox parameter %r" % k)
-        setattr(p, k, v)
-    return p
+    return _default_params(BroxParams, "va_brox_default_params", "Brox", over)
 
 
 def default_farneback_params(**over):
     """``va_farneback_default_params`` with keyword overrides: pyr_scale, poly_sigma, levels, winsize, iterations, poly_n,
     gaussian and the tuning slots ``FARNEBACK_TUNING_SLOTS``.  An unknown name raises ValueError, and so does a value out of
     range (the text is ``va_farneback_workspace_bytes``', which names the field)."""
-    p = FarnebackParams()
-    L = lib()
-    L.va_farneback_default_params(ctypes.byref(p))
-    for k, v in over.items():
-        if k == "struct_bytes" or not hasattr(p, k):
-            raise ValueError("unknown Farneback parameter %r" % k)
-        setattr(p, k, v)
-    if L.va_farneback_workspace_bytes(64, 64, 1, 2, ctypes.byref(p)) == 0:
-        raise ValueError(L.va_last_error().decode())
+    p = _default_params(FarnebackParams, "va_farneback_default_params", "Farneback", over)
+    if lib().va_farneback_workspace_bytes(64, 64, 1, 2, ctypes.byref(p)) == 0:
+        raise ValueError(lib().va_last_error().decode())
     return p
 
 

@@ -5,8 +5,9 @@
 // file must be compiled with -ffp-contract=off and writes no fmaf in any stage of its own, so that results are independent
 // of the tiling and comparable bit for bit with an independent float32 implementation.
 //
-// Pyramid (S1), derivatives (S2), upsampling (S8) and the output copy are TV-L1's kernels (va_stage_*, tvl1.hip), in
-// TV-L1's layout: rows `pitch` = width rounded up to 4 floats, planes rounded up to 64 floats.
+// Frames (S0), pyramid (S1) and derivatives (S2) are the flow methods' shared front end (va_stage_*, flow_common.hip);
+// upsampling (S8) and the output copy are TV-L1's kernels (va_stage_*, tvl1.hip).  The layout is the shared one: rows
+// `pitch` = width rounded up to 4 floats, planes rounded up to 64 floats.
 //   pyramid  3 x [level][frame][3][plane]: (I, Ix, Iy), (Ix, Ixx, -) and (Iy, Ixy, Iyy): S2 applied to I, Ix and Iy
 //   state    [pair][6][plane]: u, v and two of the three (du, dv) buffers; the third is [pair][2][plane]
 //   ro       [pair][8][plane]: I1wx, I1wy, I1wxx, I1wxy, I1wyy, Iz, Ixz, Iyz of the current warp
@@ -24,7 +25,6 @@
 
 namespace {
 
-constexpr int kMaxScales = 16;
 constexpr int kRoPlanes = 8;
 constexpr int kMaxPairs = 3072;  // pixel pairs of the largest region: 1024 lanes x 3 pairs (a fourth pair spills: 128 registers)
 constexpr int kMaxK = 17;  // halo 36: a tile of 6 x 6 is left
@@ -44,9 +44,6 @@ struct InnerArgs {
     int TW, TH, ntx, H, K;
     float alpha, gamma, eps2, omega, om1;
 };
-
-__device__ __forceinline__ int d_min(int a, int b) { return a < b ? a : b; }
-__device__ __forceinline__ int d_max(int a, int b) { return a > b ? a : b; }
 
 // value -> cell i of a framed LDS array, and into the frame where the cell lies on the region's edge (a field border
 // then reads its own pixel: the clamped index of S60; an inner region edge reads something finite that never reaches the core)
@@ -196,17 +193,6 @@ __global__ void __launch_bounds__(NT) k_brox_inner(InnerArgs a)
 #undef BROX_PIXEL
 }
 
-// S0 for this method: gray values divided by 255 into plane 0 of every frame's level-0 block
-template <typename T>
-__global__ void k_brox_frames(const T* __restrict__ frames, float* __restrict__ pyr0, int w, int h, int pitch, size_t plane)
-{
-    const int f = blockIdx.y;
-    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= w * h) return;
-    const int y = idx / w, x = idx - y * w;
-    pyr0[(size_t)f * 3 * plane + (size_t)y * pitch + x] = (float)frames[(size_t)f * w * h + idx] / 255.0f;
-}
-
 // S58, S59: the second frame's derivatives at (x + u, y + v), the three differences, and du = dv = 0 (pitch padding included).
 // One lane per run of four pixels of a row: 16-byte loads of u, v and the first frame, 16-byte stores of the ten outputs.
 __global__ void __launch_bounds__(256) k_brox_warp(const float* __restrict__ pa, const float* __restrict__ pb, const float* __restrict__ pc,
@@ -315,8 +301,7 @@ int pick_shape(const va_brox_params* p, int w, int h, Shape* s)
 template <int NT, int PPT>
 int launch_inner_as(const InnerArgs& a, dim3 grid, size_t lds, hipStream_t st)
 {
-    if (lds > 64 * 1024)  // (more than 64 KB of dynamic LDS has to be asked for)
-        VA_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_brox_inner<NT, PPT>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    if (int rc = va_allow_lds(&k_brox_inner<NT, PPT>, lds)) return rc;
     k_brox_inner<NT, PPT><<<grid, NT, lds, st>>>(a);
     VA_LAUNCH_CHECK();
     return VA_OK;
@@ -390,32 +375,19 @@ int check_params(const va_brox_params* p)
     return VA_OK;
 }
 
-struct Plan {
-    int ns, ws[kMaxScales], hs[kMaxScales], pitch[kMaxScales];
-    size_t plane[kMaxScales], plane_max;
-    Shape shape[kMaxScales];
-    int NF, NP, F;
-    size_t off_pyr[3][kMaxScales], off_tmp, off_state, off_extra, off_ro, total;
+struct Plan : va_flow_levels {
+    Shape shape[kVaMaxScales];
+    size_t off_pyr[3][kVaMaxScales], off_tmp, off_state, off_extra, off_ro, total;
 };
 
 int make_plan(Plan& P, int w, int h, int n_seq, int fps, const va_brox_params* p)
 {
     if (int rc = check_params(p)) return rc;
-    VA_CHECK_ARG(w >= 16 && h >= 16 && w <= 16384 && h <= 16384, "va_brox: frame size %dx%d out of range [16,16384]", w, h);
-    VA_CHECK_ARG(n_seq >= 1 && fps >= 2, "va_brox: need n_seq >= 1 and frames_per_seq >= 2 (got %d, %d)", n_seq, fps);
-    VA_CHECK_ARG((long)n_seq * (fps - 1) <= 65535 && (long)n_seq * fps <= 65535, "va_brox: more than 65535 frames in one call");
-    va_tvl1_params tp;  // S1's sizes are TV-L1's
-    va_tvl1_default_params(&tp);
-    tp.scale_step = p->scale_step;
-    tp.nscales = p->nscales;
-    P.ns = va_tvl1_pyramid_sizes(w, h, &tp, P.ws, P.hs);
-    P.F = fps, P.NF = n_seq * fps, P.NP = n_seq * (fps - 1);
+    if (int rc = va_flow_check_shape("va_brox", w, h, n_seq, fps, true)) return rc;
+    va_flow_levels_fill(&P, w, h, n_seq, fps, p->scale_step, p->nscales);
     size_t off = 0;
-    P.plane_max = 0;
     for (int s = 0; s < P.ns; ++s) {
-        va_stage_layout(P.ws[s], P.hs[s], &P.pitch[s], &P.plane[s]);
         if (int rc = pick_shape(p, P.ws[s], P.hs[s], &P.shape[s])) return rc;
-        if (P.plane[s] > P.plane_max) P.plane_max = P.plane[s];
         for (int k = 0; k < 3; ++k) {
             P.off_pyr[k][s] = off;
             off += va_align_up((size_t)P.NF * 3 * P.plane[s] * sizeof(float), 256);
@@ -473,17 +445,13 @@ extern "C" int va_brox_flow(va_ctx* ctx, const void* frames, int frames_are_u8, 
 {
     VA_CHECK_ARG(ctx != nullptr, "va_brox_flow: ctx is NULL");
     VA_USE_DEVICE(ctx);
-    VA_CHECK_ARG(frames != nullptr && flow != nullptr && workspace != nullptr, "va_brox_flow: NULL buffer");
+    if (int rc = va_flow_check_buffers("va_brox_flow", frames, flow, workspace, 0, 0)) return rc;
     Plan P;
     if (int rc = make_plan(P, w, h, n_seq, frames_per_seq, p)) return rc;
-    VA_CHECK_ARG(((uintptr_t)workspace & 255) == 0, "va_brox_flow: workspace must be 256-byte aligned");
-    if (workspace_bytes < P.total) {
-        va_set_error("va_brox_flow: workspace too small (%zu < %zu bytes)", workspace_bytes, P.total);
-        return VA_ERR_WORKSPACE;
-    }
+    if (int rc = va_flow_check_buffers("va_brox_flow", frames, flow, workspace, workspace_bytes, P.total)) return rc;
     hipStream_t st = (hipStream_t)stream;
     char* ws = (char*)workspace;
-    float* pyr[3][kMaxScales];
+    float* pyr[3][kVaMaxScales];
     for (int k = 0; k < 3; ++k)
         for (int s = 0; s < P.ns; ++s) pyr[k][s] = (float*)(ws + P.off_pyr[k][s]);
     float* tmp1 = (float*)(ws + P.off_tmp);
@@ -494,14 +462,7 @@ extern "C" int va_brox_flow(va_ctx* ctx, const void* frames, int frames_are_u8, 
     const int TPB = 256;
 
     // S57: frames / 255, S1's pyramid, S2 applied to I, then to Ix and to Iy
-    {
-        const dim3 g(va_cdiv(w * h, TPB), P.NF);
-        if (frames_are_u8)
-            k_brox_frames<unsigned char><<<g, TPB, 0, st>>>((const unsigned char*)frames, pyr[0][0], w, h, P.pitch[0], P.plane[0]);
-        else
-            k_brox_frames<float><<<g, TPB, 0, st>>>((const float*)frames, pyr[0][0], w, h, P.pitch[0], P.plane[0]);
-        VA_LAUNCH_CHECK();
-    }
+    if (int rc = va_stage_frames(frames, frames_are_u8, true, pyr[0][0], w, h, P.pitch[0], P.plane[0], P.NF, st)) return rc;
     if (int rc = va_stage_pyramid(pyr[0], P.ws, P.hs, P.pitch, P.plane, P.ns, P.NF, tmp1, tmp2, P.plane_max, p->scale_step, st)) return rc;
     for (int s = 0; s < P.ns; ++s) {
         const size_t pl = P.plane[s], row = 3 * pl * sizeof(float);
@@ -554,7 +515,7 @@ extern "C" int va_brox_inner_step(va_ctx* ctx, const void* I0x, const void* I0y,
     (void)I0x, (void)I0y, (void)I1w;
     VA_CHECK_ARG(I1wx && I1wy && I1wxx && I1wxy && I1wyy && Iz && Ixz && Iyz && u && v && du && dv, "va_brox_inner_step: NULL field");
     if (int rc = check_params(p)) return rc;
-    VA_CHECK_ARG(n >= 1 && n <= 65535 && w >= 16 && h >= 16 && w <= 16384 && h <= 16384, "va_brox_inner_step: bad shape (n %d, %d x %d)", n, w, h);
+    if (int rc = va_flow_check_fields("va_brox_inner_step", n, w, h)) return rc;
     Shape s;
     if (int rc = pick_shape(p, w, h, &s)) return rc;
     const size_t fl = (size_t)w * h;

@@ -5,8 +5,9 @@
 // -ffp-contract=off and writes no fmaf of its own, so that results are independent of the tiling and comparable bit for bit
 // with an independent float32 implementation.
 //
-// Pyramid (S1), upsampling (S8) and the output copy are TV-L1's kernels (va_stage_*, tvl1.hip), in TV-L1's layout: rows
-// `pitch` = width rounded up to 4 floats, planes rounded up to 64 floats.
+// Frames (S0) and pyramid (S1) are the flow methods' shared front end (va_stage_*, flow_common.hip); upsampling (S8) and the
+// output copy are TV-L1's kernels (va_stage_*, tvl1.hip).  The layout is the shared one: rows `pitch` = width rounded up to
+// 4 floats, planes rounded up to 64 floats.
 //   pyramid  [level][frame][3][plane]: plane 0 is the frame (gray values in [0,255]); planes 1, 2 are not used
 //   coef     [frame][5][plane]: (b_x, b_y, a_xx, a_yy, a_xy) of the current level (S64)
 //   state    [pair][6][plane]: the flow ping-pongs between planes (0, 1) and planes (2, 3)
@@ -21,15 +22,11 @@
 
 namespace {
 
-constexpr int kMaxScales = 16;
 constexpr int kNT = 256;
 constexpr int kMaxRadius = 31;       // winsize <= 63
-constexpr int kMaxLds = 160 * 1024;  // what one workgroup of gfx950 can hold
 constexpr int kDefTileW = 32, kDefTileH = 16;
 constexpr float kDetReg = 1e-3f;     // S67
 
-__device__ __forceinline__ int d_min(int a, int b) { return a < b ? a : b; }
-__device__ __forceinline__ int d_max(int a, int b) { return a > b ? a : b; }
 __device__ __forceinline__ int d_clamp(int v, int hi) { return d_min(d_max(v, 0), hi); }
 
 struct PolyArgs {
@@ -229,17 +226,6 @@ __global__ void __launch_bounds__(kNT) k_farneback_pass(PassArgs a)
     }
 }
 
-// S0 for this method: gray values as they are into plane 0 of every frame's level-0 block
-template <typename T>
-__global__ void k_farneback_frames(const T* __restrict__ frames, float* __restrict__ pyr0, int w, int h, int pitch, size_t plane)
-{
-    const int f = blockIdx.y;
-    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= w * h) return;
-    const int y = idx / w, x = idx - y * w;
-    pyr0[(size_t)f * 3 * plane + (size_t)y * pitch + x] = (float)frames[(size_t)f * w * h + idx];
-}
-
 // ---------------------------------------------------------------- host side ------------------
 
 struct Tile {
@@ -275,9 +261,9 @@ int poly_tile(const va_farneback_params* p, Tile* t)
     t->TH = p->tuning[VA_FARNEBACK_TUNE_POLY_TILE_H] ? p->tuning[VA_FARNEBACK_TUNE_POLY_TILE_H] : kDefTileH;
     const size_t rw = t->TW + 2 * n, rh = t->TH + 2 * n;
     t->lds = (rw * rh + 3 * rw * t->TH) * sizeof(float);
-    VA_CHECK_ARG(t->lds <= (size_t)kMaxLds,
+    VA_CHECK_ARG(t->lds <= (size_t)kVaMaxLds,
                  "va_farneback: tuning: a %d x %d tile of the polynomial expansion with poly_n %d needs %zu bytes of LDS, more than one "
-                 "workgroup holds (%d)", t->TW, t->TH, n, t->lds, kMaxLds);
+                 "workgroup holds (%d)", t->TW, t->TH, n, t->lds, kVaMaxLds);
     return VA_OK;
 }
 
@@ -290,11 +276,11 @@ int pass_tile(const va_farneback_params* p, Tile* t)
     for (;;) {
         const size_t rw = t->TW + 2 * m, rh = t->TH + 2 * m;
         t->lds = 5 * (rw * rh + rw * t->TH) * sizeof(float);
-        if (t->lds <= (size_t)kMaxLds) return VA_OK;
+        if (t->lds <= (size_t)kVaMaxLds) return VA_OK;
         // (the library's own tile halves until the window fits beside it: 16 x 16 holds the largest window; a caller's is refused)
         VA_CHECK_ARG(!own && t->TW * t->TH > 64,
                      "va_farneback: tuning: a %d x %d tile of the pass with winsize %d needs %zu bytes of LDS, more than one workgroup "
-                     "holds (%d)", t->TW, t->TH, p->winsize, t->lds, kMaxLds);
+                     "holds (%d)", t->TW, t->TH, p->winsize, t->lds, kVaMaxLds);
         if (t->TW > t->TH) t->TW /= 2; else t->TH /= 2;
     }
 }
@@ -348,12 +334,10 @@ int launch_poly(PolyArgs a, const Tile& t, int poly_n, int nframes, hipStream_t 
     a.TW = t.TW, a.TH = t.TH, a.ntx = va_cdiv(a.w, t.TW);
     const dim3 grid(a.ntx * va_cdiv(a.h, t.TH), nframes);
     if (poly_n == 5) {
-        if (t.lds > 64 * 1024)  // (more than 64 KB of dynamic LDS has to be asked for)
-            VA_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_farneback_polyexp<5>), hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLds));
+        if (int rc = va_allow_lds(&k_farneback_polyexp<5>, t.lds)) return rc;
         k_farneback_polyexp<5><<<grid, kNT, t.lds, st>>>(a);
     } else {
-        if (t.lds > 64 * 1024)
-            VA_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_farneback_polyexp<7>), hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLds));
+        if (int rc = va_allow_lds(&k_farneback_polyexp<7>, t.lds)) return rc;
         k_farneback_polyexp<7><<<grid, kNT, t.lds, st>>>(a);
     }
     VA_LAUNCH_CHECK();
@@ -364,19 +348,15 @@ int launch_pass(PassArgs a, const Tile& t, int npairs, hipStream_t st)
 {
     a.TW = t.TW, a.TH = t.TH, a.ntx = va_cdiv(a.w, t.TW);
     const dim3 grid(a.ntx * va_cdiv(a.h, t.TH), npairs);
-    if (t.lds > 64 * 1024)
-        VA_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_farneback_pass), hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLds));
+    if (int rc = va_allow_lds(&k_farneback_pass, t.lds)) return rc;
     k_farneback_pass<<<grid, kNT, t.lds, st>>>(a);
     VA_LAUNCH_CHECK();
     return VA_OK;
 }
 
-struct Plan {
-    int ns, ws[kMaxScales], hs[kMaxScales], pitch[kMaxScales];
-    size_t plane[kMaxScales], plane_max;
+struct Plan : va_flow_levels {
     Tile poly, pass;
-    int NF, NP, F;
-    size_t off_pyr[kMaxScales], off_tmp, off_coef, off_state, off_up, total;
+    size_t off_pyr[kVaMaxScales], off_tmp, off_coef, off_state, off_up, total;
 };
 
 int make_plan(Plan& P, int w, int h, int n_seq, int fps, const va_farneback_params* p)
@@ -384,20 +364,10 @@ int make_plan(Plan& P, int w, int h, int n_seq, int fps, const va_farneback_para
     if (int rc = check_params(p)) return rc;
     if (int rc = poly_tile(p, &P.poly)) return rc;
     if (int rc = pass_tile(p, &P.pass)) return rc;
-    VA_CHECK_ARG(w >= 16 && h >= 16 && w <= 16384 && h <= 16384, "va_farneback: frame size %dx%d out of range [16,16384]", w, h);
-    VA_CHECK_ARG(n_seq >= 1 && fps >= 2, "va_farneback: need n_seq >= 1 and frames_per_seq >= 2 (got %d, %d)", n_seq, fps);
-    VA_CHECK_ARG((long)n_seq * (fps - 1) <= 65535 && (long)n_seq * fps <= 65535, "va_farneback: more than 65535 frames in one call");
-    va_tvl1_params tp;  // S1's sizes are TV-L1's
-    va_tvl1_default_params(&tp);
-    tp.scale_step = p->pyr_scale;
-    tp.nscales = p->levels;
-    P.ns = va_tvl1_pyramid_sizes(w, h, &tp, P.ws, P.hs);
-    P.F = fps, P.NF = n_seq * fps, P.NP = n_seq * (fps - 1);
+    if (int rc = va_flow_check_shape("va_farneback", w, h, n_seq, fps, true)) return rc;
+    va_flow_levels_fill(&P, w, h, n_seq, fps, p->pyr_scale, p->levels);
     size_t off = 0;
-    P.plane_max = 0;
     for (int s = 0; s < P.ns; ++s) {
-        va_stage_layout(P.ws[s], P.hs[s], &P.pitch[s], &P.plane[s]);
-        if (P.plane[s] > P.plane_max) P.plane_max = P.plane[s];
         P.off_pyr[s] = off;
         off += va_align_up((size_t)P.NF * 3 * P.plane[s] * sizeof(float), 256);
     }
@@ -441,34 +411,22 @@ extern "C" int va_farneback_flow(va_ctx* ctx, const void* frames, int frames_are
 {
     VA_CHECK_ARG(ctx != nullptr, "va_farneback_flow: ctx is NULL");
     VA_USE_DEVICE(ctx);
-    VA_CHECK_ARG(frames != nullptr && flow != nullptr && workspace != nullptr, "va_farneback_flow: NULL buffer");
+    if (int rc = va_flow_check_buffers("va_farneback_flow", frames, flow, workspace, 0, 0)) return rc;
     Plan P;
     if (int rc = make_plan(P, w, h, n_seq, frames_per_seq, p)) return rc;
-    VA_CHECK_ARG(((uintptr_t)workspace & 255) == 0, "va_farneback_flow: workspace must be 256-byte aligned");
-    if (workspace_bytes < P.total) {
-        va_set_error("va_farneback_flow: workspace too small (%zu < %zu bytes)", workspace_bytes, P.total);
-        return VA_ERR_WORKSPACE;
-    }
+    if (int rc = va_flow_check_buffers("va_farneback_flow", frames, flow, workspace, workspace_bytes, P.total)) return rc;
     hipStream_t st = (hipStream_t)stream;
     char* ws = (char*)workspace;
-    float* pyr[kMaxScales];
+    float* pyr[kVaMaxScales];
     for (int s = 0; s < P.ns; ++s) pyr[s] = (float*)(ws + P.off_pyr[s]);
     float* tmp1 = (float*)(ws + P.off_tmp);
     float* tmp2 = tmp1 + (size_t)P.NF * P.plane_max;
     float* coef = (float*)(ws + P.off_coef);
     float* state = (float*)(ws + P.off_state);
     float* up = (float*)(ws + P.off_up);
-    const int TPB = 256;
 
     // S63: the frames as they are, S1's pyramid
-    {
-        const dim3 g(va_cdiv(w * h, TPB), P.NF);
-        if (frames_are_u8)
-            k_farneback_frames<unsigned char><<<g, TPB, 0, st>>>((const unsigned char*)frames, pyr[0], w, h, P.pitch[0], P.plane[0]);
-        else
-            k_farneback_frames<float><<<g, TPB, 0, st>>>((const float*)frames, pyr[0], w, h, P.pitch[0], P.plane[0]);
-        VA_LAUNCH_CHECK();
-    }
+    if (int rc = va_stage_frames(frames, frames_are_u8, false, pyr[0], w, h, P.pitch[0], P.plane[0], P.NF, st)) return rc;
     if (int rc = va_stage_pyramid(pyr, P.ws, P.hs, P.pitch, P.plane, P.ns, P.NF, tmp1, tmp2, P.plane_max, p->pyr_scale, st)) return rc;
 
     PolyArgs pa{};
@@ -514,7 +472,7 @@ extern "C" int va_farneback_polyexp(va_ctx* ctx, const void* fields, int n, int 
     VA_USE_DEVICE(ctx);
     VA_CHECK_ARG(fields != nullptr && coef != nullptr, "va_farneback_polyexp: NULL buffer");
     if (int rc = check_params(p)) return rc;
-    VA_CHECK_ARG(n >= 1 && n <= 65535 && w >= 16 && h >= 16 && w <= 16384 && h <= 16384, "va_farneback_polyexp: bad shape (n %d, %d x %d)", n, w, h);
+    if (int rc = va_flow_check_fields("va_farneback_polyexp", n, w, h)) return rc;
     Tile t;
     if (int rc = poly_tile(p, &t)) return rc;
     const size_t fl = (size_t)w * h;
@@ -534,7 +492,7 @@ extern "C" int va_farneback_pass(va_ctx* ctx, const void* coef0, const void* coe
     VA_CHECK_ARG(coef0 != nullptr && coef1 != nullptr && flow_in != nullptr && flow_out != nullptr, "va_farneback_pass: NULL buffer");
     VA_CHECK_ARG(flow_in != flow_out, "va_farneback_pass: flow_out must not be flow_in (a pass reads its neighbours' flow)");
     if (int rc = check_params(p)) return rc;
-    VA_CHECK_ARG(n >= 1 && n <= 65535 && w >= 16 && h >= 16 && w <= 16384 && h <= 16384, "va_farneback_pass: bad shape (n %d, %d x %d)", n, w, h);
+    if (int rc = va_flow_check_fields("va_farneback_pass", n, w, h)) return rc;
     Tile t;
     if (int rc = pass_tile(p, &t)) return rc;
     const size_t fl = (size_t)w * h;

@@ -8,6 +8,8 @@
 // operation order with explicit fmaf only, so that results are independent of the tiling and of
 // block_iters, and comparable bit for bit with an independent implementation.
 //
+// S0-S2 (frames, pyramid, gradient) and the level geometry are the front end the three flow methods share: flow_common.hip.
+//
 // Data layout in HBM (all fp32, row pitch = width rounded up to 4 floats so that a lane's
 // 4-pixel run is one aligned 16-byte access):
 //   pyramid  [level][frame][3 = I, Ix, Iy][h][pitch]      built once per FRAME, shared by the
@@ -39,101 +41,8 @@
 
 namespace {
 
-constexpr int kMaxScales = 16;
-constexpr int kMaxRadius = 8;
 constexpr int kNF_STATE = 6;
 constexpr int kNF_RO = 4;
-
-struct Taps {
-    float g[2 * kMaxRadius + 1];
-    int R;
-};
-
-__device__ __forceinline__ int d_min(int a, int b) { return a < b ? a : b; }
-__device__ __forceinline__ int d_max(int a, int b) { return a > b ? a : b; }
-
-// State / per-warp-constant planes store every aligned run of four pixels as [x0, x0+2, x0+1, x0+3]: a thread of
-// k_iter_tile then gets its four pixels as the register pairs E = (x0, x0+2), O = (x0+1, x0+3) straight from one
-// 16-byte load, and two of its four x differences per row are a single packed subtract (O - E).
-// (`perm` = 0: plain row order, the layout of the levels that k_iter_stream iterates.)
-__device__ __forceinline__ int pslot(int x, int perm) { return perm ? ((x & ~3) | ((x & 1) << 1) | ((x >> 1) & 1)) : x; }
-
-// S3 (perm: the image uses the interleaved state layout above)
-__device__ __forceinline__ float bilinear(const float* __restrict__ img, int w, int h, int pitch, float x, float y, int perm = 0)
-{
-    x = fminf(fmaxf(x, 0.0f), (float)(w - 1));
-    y = fminf(fmaxf(y, 0.0f), (float)(h - 1));
-    const int x0 = (int)x, y0 = (int)y;
-    const int x1 = d_min(x0 + 1, w - 1), y1 = d_min(y0 + 1, h - 1);
-    const float ax = x - (float)x0, ay = y - (float)y0;
-    const int s0 = pslot(x0, perm), s1 = pslot(x1, perm);
-    const float a = img[y0 * pitch + s0], b = img[y0 * pitch + s1];
-    const float c = img[y1 * pitch + s0], d = img[y1 * pitch + s1];
-    const float top = fmaf(ax, b - a, a);
-    const float bot = fmaf(ax, d - c, c);
-    return fmaf(ay, bot - top, top);
-}
-
-// ---------------------------------------------------------------- pyramid kernels ------------
-
-template <typename T>
-__global__ void k_frames_to_level0(const T* __restrict__ frames, float* __restrict__ pyr0, int w, int h, int pitch,
-                                   size_t plane)
-{
-    const int f = blockIdx.y;
-    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= w * h) return;
-    const int y = idx / w, x = idx - y * w;
-    pyr0[(size_t)f * 3 * plane + (size_t)y * pitch + x] = (float)frames[(size_t)f * w * h + idx];
-}
-
-// S1: horizontal / vertical Gaussian; src and dst are [frame][stride_f floats] images of pitch `pitch`.
-template <bool VERT>
-__global__ void k_gauss(const float* __restrict__ src, size_t src_fstride, float* __restrict__ dst, size_t dst_fstride,
-                        int w, int h, int pitch, Taps t)
-{
-    const int f = blockIdx.y;
-    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= w * h) return;
-    const int y = idx / w, x = idx - y * w;
-    const float* s = src + (size_t)f * src_fstride;
-    const int R = t.R;
-    float acc;
-    if (VERT) {
-        acc = t.g[0] * s[d_max(y - R, 0) * pitch + x];
-        for (int k = -R + 1; k <= R; ++k) acc = fmaf(t.g[k + R], s[d_min(d_max(y + k, 0), h - 1) * pitch + x], acc);
-    } else {
-        acc = t.g[0] * s[y * pitch + d_max(x - R, 0)];
-        for (int k = -R + 1; k <= R; ++k) acc = fmaf(t.g[k + R], s[y * pitch + d_min(d_max(x + k, 0), w - 1)], acc);
-    }
-    dst[(size_t)f * dst_fstride + (size_t)y * pitch + x] = acc;
-}
-
-// S1: bilinear resample of the smoothed level s-1 into level s.
-__global__ void k_resample(const float* __restrict__ src, size_t src_fstride, int w, int h, int pitch,
-                           float* __restrict__ dst, size_t dst_fstride, int ow, int oh, int opitch)
-{
-    const int f = blockIdx.y;
-    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= ow * oh) return;
-    const int y = idx / ow, x = idx - y * ow;
-    const float fx = (float)w / (float)ow, fy = (float)h / (float)oh;
-    dst[(size_t)f * dst_fstride + (size_t)y * opitch + x] =
-        bilinear(src + (size_t)f * src_fstride, w, h, pitch, (float)x * fx, (float)y * fy);
-}
-
-// S2: centred gradient of every frame's level (planes 1,2 of the frame's [3][plane] block).
-__global__ void k_grad(float* __restrict__ pyr, int w, int h, int pitch, size_t plane)
-{
-    const int f = blockIdx.y;
-    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= w * h) return;
-    const int y = idx / w, x = idx - y * w;
-    float* base = pyr + (size_t)f * 3 * plane;
-    const float* I = base;
-    base[plane + (size_t)y * pitch + x] = 0.5f * (I[y * pitch + d_min(x + 1, w - 1)] - I[y * pitch + d_max(x - 1, 0)]);
-    base[2 * plane + (size_t)y * pitch + x] = 0.5f * (I[d_min(y + 1, h - 1) * pitch + x] - I[d_max(y - 1, 0) * pitch + x]);
-}
 
 // ---------------------------------------------------------------- per-warp kernel ------------
 
@@ -1643,45 +1552,21 @@ int chunk_pairs(int lw, int lh, const TilePick& tp, int NP)
 }
 
 enum { LK_TILE = 0, LK_STREAM = 1 };
-// Row pitch in floats: the width rounded up to 4 (rows start 16-byte aligned: k_iter_tile's 4-pixel runs)
-int level_pitch(int w) { return (w + 3) / 4 * 4; }
-// kernel and layout of level s.  Explicit choices first (tests), then the measured default: level_streams.
-int plan_level(const va_tvl1_params* p, int s, int w, int h, int* pitch, size_t* plane)
+// kernel of level s.  Explicit choices first (tests), then the measured default: level_streams.
+int level_kind(const va_tvl1_params* p, int s, int w, int h, size_t plane)
 {
-    *pitch = level_pitch(w);
-    *plane = va_align_up((size_t)*pitch * h, 64);
-    return level_streams(p, p->epsilon > 0.0f, s, w, h, *plane) ? LK_STREAM : LK_TILE;
+    return level_streams(p, p->epsilon > 0.0f, s, w, h, plane) ? LK_STREAM : LK_TILE;
 }
 
-struct Plan {
-    int ns, ws[kMaxScales], hs[kMaxScales], pitch[kMaxScales];
-    int lk[kMaxScales];        // LK_TILE / LK_STREAM per level
-    size_t plane[kMaxScales], plane_max;
-    int NF, NP, F;
-    size_t off_pyr[kMaxScales], off_tmp, off_state[2], off_ro, off_err, off_sel, total;
+struct Plan : va_flow_levels {
+    int lk[kVaMaxScales];        // LK_TILE / LK_STREAM per level
+    size_t off_pyr[kVaMaxScales], off_tmp, off_state[2], off_ro, off_err, off_sel, total;
 };
-
-int zoom_taps(float step, Taps* t)
-{
-    const float sigma = 0.6f * sqrtf(1.0f / (step * step) - 1.0f);
-    int R = (int)(3.0f * sigma) + 1;
-    if (R > kMaxRadius) R = kMaxRadius;
-    double g[2 * kMaxRadius + 1], sum = 0.0;
-    for (int k = -R; k <= R; ++k) {
-        g[k + R] = std::exp(-(double)(k * k) / (2.0 * (double)sigma * (double)sigma));
-        sum += g[k + R];
-    }
-    for (int k = 0; k <= 2 * R; ++k) t->g[k] = (float)(g[k] / sum);
-    t->R = R;
-    return R;
-}
 
 int check_params(const va_tvl1_params* p, int w, int h, int n_seq, int fps)
 {
     VA_CHECK_ARG(p != nullptr, "va_tvl1: params is NULL");
-    VA_CHECK_ARG(w >= 16 && h >= 16 && w <= 16384 && h <= 16384, "va_tvl1: frame size %dx%d out of range [16,16384]", w, h);
-    VA_CHECK_ARG(n_seq >= 1 && fps >= 2, "va_tvl1: need n_seq >= 1 and frames_per_seq >= 2 (got %d, %d)", n_seq, fps);
-    VA_CHECK_ARG((long)n_seq * (fps - 1) <= 65535, "va_tvl1: more than 65535 pairs in one call");
+    if (int rc = va_flow_check_shape("va_tvl1", w, h, n_seq, fps, false)) return rc;
     VA_CHECK_ARG(p->nscales >= 1 && p->warps >= 1 && p->iters >= 1, "va_tvl1: nscales, warps, iters must be >= 1");
     VA_CHECK_ARG(p->scale_step > 0.0f && p->scale_step < 1.0f, "va_tvl1: scale_step must be in (0,1)");
     VA_CHECK_ARG(p->tau > 0.0f && p->lambda > 0.0f && p->theta > 0.0f, "va_tvl1: tau, lambda, theta must be > 0");
@@ -1697,7 +1582,7 @@ int check_params(const va_tvl1_params* p, int w, int h, int n_seq, int fps)
                  "DESIGN.md section 7; commit eebd154 is the last one that contains them.  Valid stream_waves: 0, 1, 2, 7, 8, 9");
     VA_CHECK_ARG(p->tuning[VA_TUNE_STREAM_PPL] == 0 || p->tuning[VA_TUNE_STREAM_PPL] == 2, "va_tvl1: stream_ppl must be 0 (default) or 2");
     VA_CHECK_ARG(p->tuning[VA_TUNE_STREAM_QUEUE] == 0 || p->tuning[VA_TUNE_STREAM_QUEUE] == 2, "va_tvl1: stream_queue must be 0 (default) or 2 (a launch per pass)");
-    VA_CHECK_ARG(p->tuning[VA_TUNE_STREAM_LEVELS] >= -1 && p->tuning[VA_TUNE_STREAM_LEVELS] < (1 << kMaxScales) && (sw >= 0 && sw < kMwFirst + kNumMwShapes) &&
+    VA_CHECK_ARG(p->tuning[VA_TUNE_STREAM_LEVELS] >= -1 && p->tuning[VA_TUNE_STREAM_LEVELS] < (1 << kVaMaxScales) && (sw >= 0 && sw < kMwFirst + kNumMwShapes) &&
                      p->tuning[VA_TUNE_STREAM_CHUNKS] >= 0 && p->tuning[VA_TUNE_STREAM_SLOTS] >= 0,
                  "va_tvl1: stream_levels must be -1 or a level bit set, stream_waves in [0, 9], stream_chunks and stream_slots >= 0");
     VA_CHECK_ARG(p->tau / p->theta <= 1000.0f && p->lambda * p->theta <= 1000.0f, "va_tvl1: tau/theta and lambda*theta must be <= 1000");
@@ -1719,39 +1604,16 @@ int check_options(const va_tvl1_options* o, const va_tvl1_params* p, int* median
     return VA_OK;
 }
 
-int pyramid_sizes(int w, int h, const va_tvl1_params* p, int* ws, int* hs)
-{
-    int n = 1;
-    ws[0] = w;
-    hs[0] = h;
-    const int want = p->nscales > kMaxScales ? kMaxScales : p->nscales;
-    while (n < want) {
-        const int nw = (int)((float)ws[n - 1] * p->scale_step + 0.5f);
-        const int nh = (int)((float)hs[n - 1] * p->scale_step + 0.5f);
-        if ((nw < nh ? nw : nh) < 16) break;
-        ws[n] = nw;
-        hs[n] = nh;
-        ++n;
-    }
-    return n;
-}
-
 void make_plan(Plan& P, int w, int h, int n_seq, int fps, const va_tvl1_params* p)
 {
-    P.ns = pyramid_sizes(w, h, p, P.ws, P.hs);
-    P.F = fps;
-    P.NF = n_seq * fps;
-    P.NP = n_seq * (fps - 1);
+    va_flow_levels_fill(&P, w, h, n_seq, fps, p->scale_step, p->nscales);
     size_t off = 0;
     for (int s = 0; s < P.ns; ++s) {
-        P.lk[s] = plan_level(p, s, P.ws[s], P.hs[s], &P.pitch[s], &P.plane[s]);
+        P.lk[s] = level_kind(p, s, P.ws[s], P.hs[s], P.plane[s]);
         P.off_pyr[s] = off;
         off += va_align_up((size_t)P.NF * 3 * P.plane[s] * sizeof(float), 256);
     }
-    // the buffers every level shares are sized for the LARGEST plane of the pyramid
-    P.plane_max = 0;
-    for (int s = 0; s < P.ns; ++s) P.plane_max = P.plane[s] > P.plane_max ? P.plane[s] : P.plane_max;
-    P.off_tmp = off;
+    P.off_tmp = off;  // (the buffers every level shares are sized for the largest plane of the pyramid)
     off += va_align_up((size_t)P.NF * 2 * P.plane_max * sizeof(float), 256);
     for (int b = 0; b < 2; ++b) {
         P.off_state[b] = off;
@@ -1784,7 +1646,7 @@ va_prof_span prof_get(va_ctx* ctx)
 
 // The buffers of a call inside its workspace (make_plan's offsets)
 struct LevelBufs {
-    float* pyr[kMaxScales];
+    float* pyr[kVaMaxScales];
     float *tmp1, *state[2], *ro;
     unsigned long long* err;
     int *sel, *base;
@@ -2128,7 +1990,7 @@ extern "C" void va_tvl1_default_params(va_tvl1_params* p)
 extern "C" int va_tvl1_pyramid_sizes(int w, int h, const va_tvl1_params* p, int* ws, int* hs)
 {
     if (!p || !ws || !hs || w < 1 || h < 1 || !(p->scale_step > 0.0f && p->scale_step < 1.0f)) return 0;
-    return pyramid_sizes(w, h, p, ws, hs);
+    return va_flow_pyramid_sizes(w, h, p->scale_step, p->nscales, ws, hs);
 }
 
 // The register tiling va_tvl1_flow will use (host logic only; no device needed): for every pyramid level s,
@@ -2136,8 +1998,8 @@ extern "C" int va_tvl1_pyramid_sizes(int w, int h, const va_tvl1_params* p, int*
 extern "C" int va_tvl1_tile_plan(int w, int h, const va_tvl1_params* p, int* out)
 {
     if (!p || !out || w < 16 || h < 16 || !(p->scale_step > 0.0f && p->scale_step < 1.0f) || p->iters < 1) return 0;
-    int ws[kMaxScales], hs[kMaxScales];
-    const int ns = pyramid_sizes(w, h, p, ws, hs);
+    int ws[kVaMaxScales], hs[kVaMaxScales];
+    const int ns = va_flow_pyramid_sizes(w, h, p->scale_step, p->nscales, ws, hs);
     int K0 = p->block_iters;
     if (p->epsilon > 0.0f) K0 = 1;
     for (int s = 0; s < ns; ++s) {
@@ -2146,7 +2008,8 @@ extern "C" int va_tvl1_tile_plan(int w, int h, const va_tvl1_params* p, int* out
         const TileCfg& c = kCfgs[tp.cfg];
         int lp;
         size_t lplane;
-        if (plan_level(p, s, ws[s], hs[s], &lp, &lplane) == LK_STREAM) {
+        va_stage_layout(ws[s], hs[s], &lp, &lplane);
+        if (level_kind(p, s, ws[s], hs[s], lplane) == LK_STREAM) {
             StreamPick sp{};
             stream_strips(p, ws[s], sp);
             const int nwv = sp.nwv ? sp.nwv : sp.fb_nwv, kh = sp.nwv ? sp.kh : sp.fb_kh;
@@ -2214,20 +2077,16 @@ extern "C" int va_tvl1_flow_opt(va_ctx* ctx, const void* frames, int frames_are_
 {
     VA_CHECK_ARG(ctx != nullptr, "va_tvl1_flow: ctx is NULL");
     VA_USE_DEVICE(ctx);
-    VA_CHECK_ARG(frames != nullptr && flow != nullptr && workspace != nullptr, "va_tvl1_flow: NULL buffer");
+    if (int rc = va_flow_check_buffers("va_tvl1_flow", frames, flow, workspace, 0, 0)) return rc;
     if (int rc = check_params(p, w, h, n_seq, frames_per_seq)) return rc;
     int median, median_every;  // S55: median = 0 runs one segment of p->iters iterations, the launch sequence without the option
     if (int rc = check_options(opt, p, &median, &median_every)) return rc;
-    VA_CHECK_ARG(((uintptr_t)workspace & 255) == 0, "va_tvl1_flow: workspace must be 256-byte aligned");
     Plan P;
     make_plan(P, w, h, n_seq, frames_per_seq, p);
-    if (workspace_bytes < P.total) {
-        va_set_error("va_tvl1_flow: workspace too small (%zu < %zu bytes)", workspace_bytes, P.total);
-        return VA_ERR_WORKSPACE;
-    }
+    if (int rc = va_flow_check_buffers("va_tvl1_flow", frames, flow, workspace, workspace_bytes, P.total)) return rc;
     hipStream_t st = (hipStream_t)stream;
     char* ws = (char*)workspace;
-    float* pyr[kMaxScales];
+    float* pyr[kVaMaxScales];
     for (int s = 0; s < P.ns; ++s) pyr[s] = (float*)(ws + P.off_pyr[s]);
     float* tmp1 = (float*)(ws + P.off_tmp);
     float* tmp2 = tmp1 + (size_t)P.NF * P.plane_max;
@@ -2239,31 +2098,11 @@ extern "C" int va_tvl1_flow_opt(va_ctx* ctx, const void* frames, int frames_are_
     const bool eps = p->epsilon > 0.0f;
     const int TPB = 256;
 
-    // S0/S1: level 0, then the pyramid of every FRAME (shared by both pairs it belongs to).
-    {
-        const dim3 g(va_cdiv(w * h, TPB), P.NF);
-        if (frames_are_u8)
-            k_frames_to_level0<unsigned char><<<g, TPB, 0, st>>>((const unsigned char*)frames, pyr[0], w, h, P.pitch[0], P.plane[0]);
-        else
-            k_frames_to_level0<float><<<g, TPB, 0, st>>>((const float*)frames, pyr[0], w, h, P.pitch[0], P.plane[0]);
-        VA_LAUNCH_CHECK();
-    }
-    Taps taps;
-    zoom_taps(p->scale_step, &taps);
-    for (int s = 1; s < P.ns; ++s) {
-        const int pw = P.ws[s - 1], ph = P.hs[s - 1], pp = P.pitch[s - 1];
-        const dim3 g(va_cdiv(pw * ph, TPB), P.NF);
-        k_gauss<false><<<g, TPB, 0, st>>>(pyr[s - 1], 3 * P.plane[s - 1], tmp1, P.plane_max, pw, ph, pp, taps);
-        k_gauss<true><<<g, TPB, 0, st>>>(tmp1, P.plane_max, tmp2, P.plane_max, pw, ph, pp, taps);
-        const dim3 g2(va_cdiv(P.ws[s] * P.hs[s], TPB), P.NF);
-        k_resample<<<g2, TPB, 0, st>>>(tmp2, P.plane_max, pw, ph, pp, pyr[s], 3 * P.plane[s], P.ws[s], P.hs[s], P.pitch[s]);
-        VA_LAUNCH_CHECK();
-    }
-    for (int s = 0; s < P.ns; ++s) {
-        const dim3 g(va_cdiv(P.ws[s] * P.hs[s], TPB), P.NF);
-        k_grad<<<g, TPB, 0, st>>>(pyr[s], P.ws[s], P.hs[s], P.pitch[s], P.plane[s]);
-        VA_LAUNCH_CHECK();
-    }
+    // S0-S2: level 0, then the pyramid of every FRAME (shared by both pairs it belongs to) and its gradient.
+    if (int rc = va_stage_frames(frames, frames_are_u8, false, pyr[0], w, h, P.pitch[0], P.plane[0], P.NF, st)) return rc;
+    if (int rc = va_stage_pyramid(pyr, P.ws, P.hs, P.pitch, P.plane, P.ns, P.NF, tmp1, tmp2, P.plane_max, p->scale_step, st)) return rc;
+    for (int s = 0; s < P.ns; ++s)
+        if (int rc = va_stage_gradient(pyr[s], P.ws[s], P.hs[s], P.pitch[s], P.plane[s], P.NF, st)) return rc;
 
     // S4: u = 0, p = 0 at the coarsest level.
     const int sc = P.ns - 1;
@@ -2416,42 +2255,8 @@ extern "C" int va_tvl1_profile_levels(va_ctx* ctx, double* out, int n, int reset
     return VA_OK;
 }
 
-// ---- S1, S2, S8 for the other flow method of the library (brox.hip): the kernels above, launched as
-// va_tvl1_flow launches them, on the caller's buffers in TV-L1's layout (frames [frame][3][plane], state [pair][6][plane]
-// in plain row order).  Nothing here is on va_tvl1_flow's own path.
-
-void va_stage_layout(int w, int h, int* pitch, size_t* plane)
-{
-    *pitch = level_pitch(w);
-    *plane = va_align_up((size_t)*pitch * h, 64);
-}
-
-// S1: levels 1 .. ns-1 of every frame from level 0 (plane 0 of pyr[0]); tmp1, tmp2: [NF][tmp_stride] scratch
-int va_stage_pyramid(float* const* pyr, const int* ws, const int* hs, const int* pitch, const size_t* plane, int ns, int NF,
-                     float* tmp1, float* tmp2, size_t tmp_stride, float step, hipStream_t st)
-{
-    const int TPB = 256;
-    Taps taps;
-    zoom_taps(step, &taps);
-    for (int s = 1; s < ns; ++s) {
-        const int pw = ws[s - 1], ph = hs[s - 1], pp = pitch[s - 1];
-        const dim3 g(va_cdiv(pw * ph, TPB), NF);
-        k_gauss<false><<<g, TPB, 0, st>>>(pyr[s - 1], 3 * plane[s - 1], tmp1, tmp_stride, pw, ph, pp, taps);
-        k_gauss<true><<<g, TPB, 0, st>>>(tmp1, tmp_stride, tmp2, tmp_stride, pw, ph, pp, taps);
-        const dim3 g2(va_cdiv(ws[s] * hs[s], TPB), NF);
-        k_resample<<<g2, TPB, 0, st>>>(tmp2, tmp_stride, pw, ph, pp, pyr[s], 3 * plane[s], ws[s], hs[s], pitch[s]);
-        VA_LAUNCH_CHECK();
-    }
-    return VA_OK;
-}
-
-// S2: planes 1, 2 of every frame's [3][plane] block <- the centred gradient of its plane 0
-int va_stage_gradient(float* pyr, int w, int h, int pitch, size_t plane, int NF, hipStream_t st)
-{
-    k_grad<<<dim3(va_cdiv(w * h, 256), NF), 256, 0, st>>>(pyr, w, h, pitch, plane);
-    VA_LAUNCH_CHECK();
-    return VA_OK;
-}
+// ---- S8 and the output copy for the methods whose state is TV-L1's [pair][6][plane] in plain row order (brox.hip,
+// farneback.hip): k_upsample, k_level_init and k_flow_out as va_tvl1_flow launches them, without the per-pair buffer select.
 
 // S8: planes 0, 1 of the coarse state -> planes 0, 1 of the fine state (through tmp [pair][2][fplane]); the fine state's
 // planes 2..5 and its pitch padding become 0 (k_level_init).  The coarse and the fine state may be the same buffer.

@@ -111,17 +111,75 @@ __device__ __forceinline__ float va_bilinear_plain(const float* __restrict__ f, 
     return top + ay * (bot - top);
 }
 
-// TV-L1's stages S1, S2, S8 as brox.hip launches them (defined in tvl1.hip beside their kernels)
+static inline size_t va_align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+static inline int va_cdiv(int a, int b) { return (a + b - 1) / b; }
+
+// ---- flow methods (tvl1.hip, brox.hip, farneback.hip): the front end they share, S0-S2 and the geometry (flow_common.hip)
+
+constexpr int kVaMaxScales = 16;
+constexpr int kVaMaxLds = 160 * 1024;  // what one workgroup of gfx950 can hold
+
+__device__ __forceinline__ int d_min(int a, int b) { return a < b ? a : b; }
+__device__ __forceinline__ int d_max(int a, int b) { return a > b ? a : b; }
+
+// State / per-warp-constant planes store every aligned run of four pixels as [x0, x0+2, x0+1, x0+3]: a thread of
+// k_iter_tile then gets its four pixels as the register pairs E = (x0, x0+2), O = (x0+1, x0+3) straight from one
+// 16-byte load, and two of its four x differences per row are a single packed subtract (O - E).
+// (`perm` = 0: plain row order, the layout of the levels that k_iter_stream iterates.)
+__device__ __forceinline__ int pslot(int x, int perm) { return perm ? ((x & ~3) | ((x & 1) << 1) | ((x >> 1) & 1)) : x; }
+
+// S3 (perm: the image uses the interleaved state layout above)
+__device__ __forceinline__ float bilinear(const float* __restrict__ img, int w, int h, int pitch, float x, float y, int perm = 0)
+{
+    x = fminf(fmaxf(x, 0.0f), (float)(w - 1));
+    y = fminf(fmaxf(y, 0.0f), (float)(h - 1));
+    const int x0 = (int)x, y0 = (int)y;
+    const int x1 = d_min(x0 + 1, w - 1), y1 = d_min(y0 + 1, h - 1);
+    const float ax = x - (float)x0, ay = y - (float)y0;
+    const int s0 = pslot(x0, perm), s1 = pslot(x1, perm);
+    const float a = img[y0 * pitch + s0], b = img[y0 * pitch + s1];
+    const float c = img[y1 * pitch + s0], d = img[y1 * pitch + s1];
+    const float top = fmaf(ax, b - a, a);
+    const float bot = fmaf(ax, d - c, c);
+    return fmaf(ay, bot - top, top);
+}
+
+// A kernel launched with more than 64 KB of dynamic LDS has to ask for it first
+template <typename K>
+int va_allow_lds(K* kernel, size_t lds)
+{
+    if (lds > 64 * 1024) VA_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, kVaMaxLds));
+    return VA_OK;
+}
+
+// The levels of a call's pyramid (S1's sizes; rows `pitch` = width rounded up to 4 floats, planes rounded up to 64 floats)
+// and its counts: F frames per sequence, NF frames, NP pairs.  Every method's plan starts with it.
+struct va_flow_levels {
+    int ns, ws[kVaMaxScales], hs[kVaMaxScales], pitch[kVaMaxScales];
+    size_t plane[kVaMaxScales], plane_max;
+    int F, NF, NP;
+};
+int va_flow_pyramid_sizes(int w, int h, float scale_step, int nscales, int* ws, int* hs);
+void va_flow_levels_fill(va_flow_levels* L, int w, int h, int n_seq, int fps, float scale_step, int nscales);
+
+// The shapes a call accepts (frames: the 65535 bound a grid's y extent sets holds the frames, not only the pairs), those of a
+// stage's entry point (n fields of w x h), and the buffers of a call: none NULL and, once the plan is known (need > 0), the
+// workspace 256-byte aligned and at least `need` bytes (VA_ERR_WORKSPACE otherwise).  `who` heads the message.
+int va_flow_check_shape(const char* who, int w, int h, int n_seq, int fps, bool frames);
+int va_flow_check_fields(const char* who, int n, int w, int h);
+int va_flow_check_buffers(const char* who, const void* frames, const void* flow, const void* workspace, size_t have, size_t need);
+
+// S0 (unit_range: gray values divided by 255), S1, S2 on the caller's buffers, frames [frame][3][plane]
 void va_stage_layout(int w, int h, int* pitch, size_t* plane);
+int va_stage_frames(const void* frames, int frames_are_u8, bool unit_range, float* pyr0, int w, int h, int pitch, size_t plane, int NF,
+                    hipStream_t st);
 int va_stage_pyramid(float* const* pyr, const int* ws, const int* hs, const int* pitch, const size_t* plane, int ns, int NF,
                      float* tmp1, float* tmp2, size_t tmp_stride, float step, hipStream_t st);
 int va_stage_gradient(float* pyr, int w, int h, int pitch, size_t plane, int NF, hipStream_t st);
+// S8 and the output copy for a state [pair][6][plane] in plain row order (tvl1.hip, beside the kernels of TV-L1's state layout)
 int va_stage_upsample(const float* cstate, int cw, int ch, int cpitch, size_t cplane, float* tmp, float* fstate, int fw, int fh,
                       int fpitch, size_t fplane, float inv_step, int NP, hipStream_t st);
 int va_stage_flow_out(const float* state, int w, int h, int pitch, size_t plane, float* flow, int NP, hipStream_t st);
-
-static inline size_t va_align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-static inline int va_cdiv(int a, int b) { return (a + b - 1) / b; }
 
 // ---- baseline JPEG (jpeg.hip decodes, jpeg_encode.hip encodes): the block grid both speak about
 

@@ -1,10 +1,12 @@
-"""Dense TV-L1 optical flow on MI355X: host wrappers over ``va_tvl1_flow`` / ``va_flow_to_stack``.
+"""Dense optical flow on MI355X by three methods (TV-L1, Brox, Farneback): host wrappers over ``va_tvl1_flow_opt``,
+``va_brox_flow`` and ``va_farneback_flow``, and over what consumes their result (``va_flow_to_stack`` and its kin).
 
 The reference never computes flow; it reads the ``flow_x_%04d.jpg`` / ``flow_y_%04d.jpg`` images of
 an upstream TV-L1 tool (Sheet03/temporalModel.py:76-81, Sheet03/parameters.py:27,38-39).  These
 functions are that tool, re-built for gfx950, producing directly the ``[2L,H,W]`` flow volume that
 ``TemporalDataset.__getitem__`` assembles (Sheet03/temporalModel.py:83-90).
 """
+import collections
 import ctypes
 
 import torch
@@ -35,6 +37,64 @@ def release_workspace(slot, device):
     _ws_cache.pop((device.index, "tvl1", slot), None)
 
 
+# One row per flow method, all that _flow and pyramid_sizes know of it: the public function's name (it heads every message),
+# the parameter class and its defaults, the two C entry points, whether the method has TV-L1's options (S55: they travel
+# beside the parameters, and ``lambda`` is taken as ``lambda_``), whether ``params`` together with keyword overrides is
+# refused (else the overrides are ignored), and the names of the fields that shape the pyramid.
+_Method = collections.namedtuple("_Method", "who params defaults workspace_bytes flow tvl1_options refuses_both step levels")
+_METHODS = (
+    _Method("tvl1_flow", _ffi.Tvl1Params, _ffi.default_tvl1_params, "va_tvl1_workspace_bytes_opt", "va_tvl1_flow_opt",
+            True, False, "scale_step", "nscales"),
+    _Method("brox_flow", _ffi.BroxParams, _ffi.default_brox_params, "va_brox_workspace_bytes", "va_brox_flow",
+            False, False, "scale_step", "nscales"),
+    _Method("farneback_flow", _ffi.FarnebackParams, _ffi.default_farneback_params, "va_farneback_workspace_bytes", "va_farneback_flow",
+            False, True, "pyr_scale", "levels"),
+)
+_TVL1, _BROX, _FARNEBACK = _METHODS
+
+
+def _flow(m, frames, params, ws_slot, out, over):
+    """The call the three public functions share: frames, parameters, workspace, ``out``, the library."""
+    who = m.who
+    if not isinstance(frames, torch.Tensor) or not frames.is_cuda:
+        raise ValueError("%s: frames must be a CUDA tensor" % who)
+    if frames.dim() == 3:
+        frames = frames.unsqueeze(0)
+    if frames.dim() != 4:
+        raise ValueError("%s: frames must be [S,F,H,W] or [F,H,W]" % who)
+    if frames.dtype not in (torch.uint8, torch.float32):
+        raise ValueError("%s: frames must be uint8 or float32" % who)
+    if not m.tvl1_options:
+        _refuse_median(params, over, who)
+    frames = frames.contiguous()
+    S, F, H, W = frames.shape
+    p = params if params is not None else m.defaults(**over)
+    if not m.tvl1_options and not isinstance(p, m.params):
+        raise ValueError("%s: params must be an _ffi.%s" % (who, m.params.__name__))
+    if m.refuses_both and params is not None and over:
+        raise ValueError("%s: pass a %s or keyword overrides, not both" % (who, m.params.__name__))
+    L = _ffi.lib()
+    c = _ffi.ctx(frames.device.index)
+    args = (ctypes.byref(p),)
+    if m.tvl1_options:  # (S55: the median of the flow between blocks of inner iterations; NULL when no option is set)
+        opt = _ffi.tvl1_options(p)
+        args += (ctypes.byref(opt) if opt is not None else None,)
+    nbytes = getattr(L, m.workspace_bytes)(W, H, S, F, *args)
+    if nbytes == 0:
+        raise ValueError(L.va_last_error().decode())
+    ws = _workspace(nbytes, frames.device, ws_slot)
+    if out is None:
+        flow = torch.empty((S * (F - 1), 2, H, W), dtype=torch.float32, device=frames.device)
+    else:
+        flow = out
+        if (tuple(flow.shape) != (S * (F - 1), 2, H, W) or flow.dtype != torch.float32 or flow.device != frames.device
+                or not flow.is_contiguous()):
+            raise ValueError("%s: out must be a contiguous float32 [%d,2,%d,%d] tensor on the frames' device" % (who, S * (F - 1), H, W))
+    _ffi.check(getattr(L, m.flow)(c, _ffi.ptr(frames), int(frames.dtype == torch.uint8), S, F, W, H, *args,
+                                  _ffi.ptr(flow), _ffi.ptr(ws), ws.numel(), _ffi.stream_ptr(frames.device)))
+    return flow
+
+
 def tvl1_flow(frames, params=None, ws_slot=0, out=None, **over):
     """frames: cuda uint8 or float32 tensor ``[S, F, H, W]`` (or ``[F, H, W]``), gray values in [0,255].
 
@@ -49,45 +109,10 @@ def tvl1_flow(frames, params=None, ws_slot=0, out=None, **over):
     ``TwoStreamPipeline`` with their ``tvl1_params`` -- computes Brox flow when it is handed one.  An
     ``_ffi.FarnebackParams`` does the same for ``farneback_flow``.
     """
-    if isinstance(params, _ffi.BroxParams):
-        return brox_flow(frames, params, ws_slot=ws_slot, out=out, **over)
-    if isinstance(params, _ffi.FarnebackParams):
-        return farneback_flow(frames, params, ws_slot=ws_slot, out=out, **over)
-    if not isinstance(frames, torch.Tensor) or not frames.is_cuda:
-        raise ValueError("tvl1_flow: frames must be a CUDA tensor")
-    if frames.dim() == 3:
-        frames = frames.unsqueeze(0)
-    if frames.dim() != 4:
-        raise ValueError("tvl1_flow: frames must be [S,F,H,W] or [F,H,W]")
-    if frames.dtype not in (torch.uint8, torch.float32):
-        raise ValueError("tvl1_flow: frames must be uint8 or float32")
-    frames = frames.contiguous()
-    S, F, H, W = frames.shape
-    p = params if params is not None else _ffi.default_tvl1_params(**over)
-    L = _ffi.lib()
-    c = _ffi.ctx(frames.device.index)
-    opt = _ffi.tvl1_options(p)  # (S55: the median of the flow between blocks of inner iterations)
-    if opt is None:
-        nbytes = L.va_tvl1_workspace_bytes(W, H, S, F, ctypes.byref(p))
-    else:
-        nbytes = L.va_tvl1_workspace_bytes_opt(W, H, S, F, ctypes.byref(p), ctypes.byref(opt))
-    if nbytes == 0:
-        raise ValueError(L.va_last_error().decode())
-    ws = _workspace(nbytes, frames.device, ws_slot)
-    if out is None:
-        flow = torch.empty((S * (F - 1), 2, H, W), dtype=torch.float32, device=frames.device)
-    else:
-        flow = out
-        if (tuple(flow.shape) != (S * (F - 1), 2, H, W) or flow.dtype != torch.float32 or flow.device != frames.device
-                or not flow.is_contiguous()):
-            raise ValueError("tvl1_flow: out must be a contiguous float32 [%d,2,%d,%d] tensor on the frames' device" % (S * (F - 1), H, W))
-    if opt is None:
-        _ffi.check(L.va_tvl1_flow(c, _ffi.ptr(frames), int(frames.dtype == torch.uint8), S, F, W, H, ctypes.byref(p),
-                                  _ffi.ptr(flow), _ffi.ptr(ws), ws.numel(), _ffi.stream_ptr(frames.device)))
-    else:
-        _ffi.check(L.va_tvl1_flow_opt(c, _ffi.ptr(frames), int(frames.dtype == torch.uint8), S, F, W, H, ctypes.byref(p),
-                                      ctypes.byref(opt), _ffi.ptr(flow), _ffi.ptr(ws), ws.numel(), _ffi.stream_ptr(frames.device)))
-    return flow
+    for m in (_BROX, _FARNEBACK):
+        if isinstance(params, m.params):
+            return _flow(m, frames, params, ws_slot, out, over)
+    return _flow(_TVL1, frames, params, ws_slot, out, over)
 
 
 def brox_flow(frames, params=None, ws_slot=0, out=None, **over):
@@ -96,48 +121,7 @@ def brox_flow(frames, params=None, ws_slot=0, out=None, **over):
     keyword overrides (alpha, gamma, scale_step, omega, epsilon, nscales, warps, inner_iters, solver_iters).  Parameters out
     of range (``va_brox_params`` in include/va.h) raise ValueError; so does the median option of TV-L1 (S55), which this
     method does not have."""
-    if not isinstance(frames, torch.Tensor) or not frames.is_cuda:
-        raise ValueError("brox_flow: frames must be a CUDA tensor")
-    if frames.dim() == 3:
-        frames = frames.unsqueeze(0)
-    if frames.dim() != 4:
-        raise ValueError("brox_flow: frames must be [S,F,H,W] or [F,H,W]")
-    if frames.dtype not in (torch.uint8, torch.float32):
-        raise ValueError("brox_flow: frames must be uint8 or float32")
-    _refuse_brox_median(params, over, "brox_flow")
-    frames = frames.contiguous()
-    S, F, H, W = frames.shape
-    p = params if params is not None else _ffi.default_brox_params(**over)
-    if not isinstance(p, _ffi.BroxParams):
-        raise ValueError("brox_flow: params must be an _ffi.BroxParams")
-    L = _ffi.lib()
-    c = _ffi.ctx(frames.device.index)
-    nbytes = L.va_brox_workspace_bytes(W, H, S, F, ctypes.byref(p))
-    if nbytes == 0:
-        raise ValueError(L.va_last_error().decode())
-    ws = _workspace(nbytes, frames.device, ws_slot)
-    if out is None:
-        flow = torch.empty((S * (F - 1), 2, H, W), dtype=torch.float32, device=frames.device)
-    else:
-        flow = out
-        if (tuple(flow.shape) != (S * (F - 1), 2, H, W) or flow.dtype != torch.float32 or flow.device != frames.device
-                or not flow.is_contiguous()):
-            raise ValueError("brox_flow: out must be a contiguous float32 [%d,2,%d,%d] tensor on the frames' device" % (S * (F - 1), H, W))
-    _ffi.check(L.va_brox_flow(c, _ffi.ptr(frames), int(frames.dtype == torch.uint8), S, F, W, H, ctypes.byref(p),
-                              _ffi.ptr(flow), _ffi.ptr(ws), ws.numel(), _ffi.stream_ptr(frames.device)))
-    return flow
-
-
-def _refuse_brox_median(params, over, who):
-    if "median" in over or "median_every" in over or getattr(params, "median", 0) or getattr(params, "median_every", 0):
-        raise ValueError("%s: median and median_every are options of TV-L1 (S55); Brox flow has no median filter" % who)
-
-
-def _refuse_brox(params, who):
-    if isinstance(params, _ffi.BroxParams):
-        raise ValueError("%s: describes TV-L1's kernels and takes an _ffi.Tvl1Params, not a BroxParams" % who)
-    if isinstance(params, _ffi.FarnebackParams):
-        raise ValueError("%s: describes TV-L1's kernels and takes an _ffi.Tvl1Params, not a FarnebackParams" % who)
+    return _flow(_BROX, frames, params, ws_slot, out, over)
 
 
 def farneback_flow(frames, params=None, ws_slot=0, out=None, **over):
@@ -146,39 +130,19 @@ def farneback_flow(frames, params=None, ws_slot=0, out=None, **over):
     ``_ffi.FarnebackParams`` or keyword overrides (pyr_scale, poly_sigma, levels, winsize, iterations, poly_n, gaussian).
     Parameters out of range (``va_farneback_params`` in include/va.h) raise ValueError; so does the median option of TV-L1
     (S55), which this method does not have."""
-    if not isinstance(frames, torch.Tensor) or not frames.is_cuda:
-        raise ValueError("farneback_flow: frames must be a CUDA tensor")
-    if frames.dim() == 3:
-        frames = frames.unsqueeze(0)
-    if frames.dim() != 4:
-        raise ValueError("farneback_flow: frames must be [S,F,H,W] or [F,H,W]")
-    if frames.dtype not in (torch.uint8, torch.float32):
-        raise ValueError("farneback_flow: frames must be uint8 or float32")
+    return _flow(_FARNEBACK, frames, params, ws_slot, out, over)
+
+
+def _refuse_median(params, over, who):
     if "median" in over or "median_every" in over or getattr(params, "median", 0) or getattr(params, "median_every", 0):
-        raise ValueError("farneback_flow: median and median_every are options of TV-L1 (S55); Farneback flow has no median filter")
-    frames = frames.contiguous()
-    S, F, H, W = frames.shape
-    p = params if params is not None else _ffi.default_farneback_params(**over)
-    if not isinstance(p, _ffi.FarnebackParams):
-        raise ValueError("farneback_flow: params must be an _ffi.FarnebackParams")
-    if params is not None and over:
-        raise ValueError("farneback_flow: pass a FarnebackParams or keyword overrides, not both")
-    L = _ffi.lib()
-    c = _ffi.ctx(frames.device.index)
-    nbytes = L.va_farneback_workspace_bytes(W, H, S, F, ctypes.byref(p))
-    if nbytes == 0:
-        raise ValueError(L.va_last_error().decode())
-    ws = _workspace(nbytes, frames.device, ws_slot)
-    if out is None:
-        flow = torch.empty((S * (F - 1), 2, H, W), dtype=torch.float32, device=frames.device)
-    else:
-        flow = out
-        if (tuple(flow.shape) != (S * (F - 1), 2, H, W) or flow.dtype != torch.float32 or flow.device != frames.device
-                or not flow.is_contiguous()):
-            raise ValueError("farneback_flow: out must be a contiguous float32 [%d,2,%d,%d] tensor on the frames' device" % (S * (F - 1), H, W))
-    _ffi.check(L.va_farneback_flow(c, _ffi.ptr(frames), int(frames.dtype == torch.uint8), S, F, W, H, ctypes.byref(p),
-                                   _ffi.ptr(flow), _ffi.ptr(ws), ws.numel(), _ffi.stream_ptr(frames.device)))
-    return flow
+        raise ValueError("%s: median and median_every are options of TV-L1 (S55); %s flow has no median filter"
+                         % (who, who.split("_")[0].capitalize()))
+
+
+def _tvl1_only(params, who):
+    for m in (_BROX, _FARNEBACK):
+        if isinstance(params, m.params):
+            raise ValueError("%s: describes TV-L1's kernels and takes an _ffi.Tvl1Params, not a %s" % (who, m.params.__name__))
 
 
 def median_filter(flow, ksize=5, out=None):
@@ -744,11 +708,10 @@ def apply_motion(flow, flow_count, motion="stack", mean_flow=False, out=None, *,
 def pyramid_sizes(w, h, params=None):
     """The level sizes of S1 for ``params``: an ``_ffi.Tvl1Params``, an ``_ffi.BroxParams`` (its ``scale_step`` and
     ``nscales``) or an ``_ffi.FarnebackParams`` (its ``pyr_scale`` and ``levels``); the three methods share the pyramid."""
-    if isinstance(params, _ffi.BroxParams):
-        params = _ffi.default_tvl1_params(scale_step=params.scale_step, nscales=params.nscales)
-    if isinstance(params, _ffi.FarnebackParams):  # (its ``pyr_scale`` and ``levels``)
-        params = _ffi.default_tvl1_params(scale_step=params.pyr_scale, nscales=params.levels)
     p = params if params is not None else _ffi.default_tvl1_params()
+    for m in (_BROX, _FARNEBACK):  # (va_tvl1_pyramid_sizes reads two fields: the method's names for them)
+        if isinstance(p, m.params):
+            p = _ffi.default_tvl1_params(scale_step=getattr(p, m.step), nscales=getattr(p, m.levels))
     ws = (ctypes.c_int * 16)()
     hs = (ctypes.c_int * 16)()
     n = _ffi.lib().va_tvl1_pyramid_sizes(w, h, ctypes.byref(p), ws, hs)
@@ -758,7 +721,7 @@ def pyramid_sizes(w, h, params=None):
 def tile_plan(w, h, params=None):
     """The register tiling ``tvl1_flow`` will use per pyramid level (host logic, no GPU needed):
     list of dict(tile_w, tile_h, waves, block_iters, tiles_x, tiles_y).  A ``BroxParams`` raises ValueError."""
-    _refuse_brox(params, "tile_plan")
+    _tvl1_only(params, "tile_plan")
     p = params if params is not None else _ffi.default_tvl1_params()
     out = (ctypes.c_int * 96)()
     n = _ffi.lib().va_tvl1_tile_plan(w, h, ctypes.byref(p), out)
@@ -772,7 +735,7 @@ def launch_plan(w, h, n_seq, frames_per_seq, params=None, **over):
     no GPU needed): a list of dicts with the fields of ``va_tvl1_launch`` (include/va.h), ``family`` as one of
     ``_ffi.TVL1_LAUNCH_FAMILIES``.  ``params`` / keyword overrides as ``tvl1_flow`` takes them (``median``, ``median_every``
     included); parameters out of range raise ValueError.  A ``BroxParams`` raises ValueError."""
-    _refuse_brox(params, "launch_plan")
+    _tvl1_only(params, "launch_plan")
     p = params if params is not None else _ffi.default_tvl1_params(**over)
     opt = _ffi.tvl1_options(p)
     ref = ctypes.byref(opt) if opt is not None else None
@@ -793,15 +756,15 @@ def launch_plan(w, h, n_seq, frames_per_seq, params=None, **over):
 
 
 def profile_enable(on=True, device=None):
-    _refuse_brox(on, "profile_enable")
-    _refuse_brox(device, "profile_enable")
+    _tvl1_only(on, "profile_enable")
+    _tvl1_only(device, "profile_enable")
     _ffi.check(_ffi.lib().va_tvl1_profile_enable(_ffi.ctx(device), int(bool(on))))
 
 
 def profile_levels(n_levels, reset=True, device=None):
     """Per pyramid level since the last reset: list of dict(ms, px_iters, launches) (call ``profile_read(reset=False)``
     first: it synchronises the recorded events).  TV-L1's inner iterations only: a ``BroxParams`` raises ValueError."""
-    _refuse_brox(n_levels, "profile_levels")
+    _tvl1_only(n_levels, "profile_levels")
     out = (ctypes.c_double * (3 * n_levels))()
     _ffi.check(_ffi.lib().va_tvl1_profile_levels(_ffi.ctx(device), out, n_levels, int(bool(reset))))
     return [dict(ms=out[3 * s], px_iters=out[3 * s + 1], launches=out[3 * s + 2]) for s in range(n_levels)]
@@ -811,7 +774,7 @@ def profile_read(reset=True, device=None):
     """-> dict(ms, launches, px_iters, px_warps, union_ms) for the inner-iteration kernel since the last
     reset (``ms``: summed per-call kernel time; ``union_ms``: wall time with at least one call's
     inner-iteration launches in flight -- they differ when several streams overlap).  A ``BroxParams`` raises ValueError."""
-    _refuse_brox(reset, "profile_read")
+    _tvl1_only(reset, "profile_read")
     out = (ctypes.c_double * 5)()
     _ffi.check(_ffi.lib().va_tvl1_profile_read(_ffi.ctx(device), out, int(bool(reset))))
     return dict(ms=out[0], launches=out[1], px_iters=out[2], px_warps=out[3], union_ms=out[4])

@@ -381,6 +381,96 @@ int va_farneback_polyexp(va_ctx* ctx, const void* fields, int n, int w, int h, c
 int va_farneback_pass(va_ctx* ctx, const void* coef0, const void* coef1, const void* flow_in, void* flow_out, int n, int w,
                       int h, const va_farneback_params* p, void* stream);
 
+/* ------------------------------------------------------------------ Dense trajectories */
+
+/*
+ * Dense trajectories (Wang, Klaeser, Schmid, Liu, CVPR 2011) with the constants of the modelled project's Sheet02.py:26-38:
+ * points sampled on a grid where the gray frame has structure, followed through the 3x3-median-filtered flow for `length`
+ * frames, and HOG / HOF / MBHx / MBHy histograms collected in a patch x patch x length tube of nxy x nxy x nt cells around
+ * each track.  DESIGN.md S69-S76 are the specification; it is the build's own (no parity with OpenCV or with Sheet02's
+ * arithmetic is claimed).  Orientation votes are quantised to fixed point, every later sum is an integer sum: no result
+ * depends on a reduction order or on a tuning value.  Values out of range (length not a multiple of nt, patch not a multiple
+ * of nxy, patch / nxy > 64, step < 2, quality outside (0,1), a threshold <= 0, a tuning value with no kernel shape) give
+ * VA_ERR_INVALID, or a byte count of 0, and a message naming the field before anything is launched.
+ */
+typedef struct va_dtraj_params {
+    int struct_bytes;     /* sizeof(va_dtraj_params) of the caller; a smaller value is refused */
+    int step;             /* 5; side of a sampling grid cell in pixels, >= 2 */
+    int length;           /* 15; steps of a trajectory (it has length + 1 points), a multiple of nt */
+    int patch;            /* 32; side of the tube in pixels, a multiple of nxy, patch / nxy <= 64 */
+    int nxy;              /* 2; cells across and down the tube */
+    int nt;               /* 3; cells along the tube */
+    float quality;        /* 0.001; a point starts where the corner response exceeds quality * the frame's maximum */
+    float min_flow;       /* 0.4; HOF: a flow vector no longer than this votes into the ninth bin */
+    float min_std;        /* 1.7320508; standard deviation (pixels) of x and of y below which a trajectory is static */
+    float max_std;        /* 30; standard deviation of x or of y above which it is erratic */
+    float max_dis;        /* 20; longest step in pixels above which it is a jump */
+    float max_dis_share;  /* 0.7; share of the whole length one step may have */
+    int tuning[8];        /* chunk length and tile shape (csrc/va_internal.h, VA_DTRAJ_TUNE_*); 0 = the library's choice.
+                             Results do not depend on any of them. */
+} va_dtraj_params;
+
+void va_dtraj_default_params(va_dtraj_params* p);
+
+/* Needs no device.  0 and a va_last_error text on bad parameters or sizes (w, h in [16,16384], n_frames in [2,65536],
+ * capacity >= 1).  The bytes hold the track table of (w/step)(h/step) * length slots and one chunk of frames: 33 planes of
+ * votes and 33 integral planes each. */
+size_t va_dtraj_workspace_bytes(int w, int h, int n_frames, int capacity, const va_dtraj_params* p);
+
+/*
+ * gray u8 or f32 in [0,255] [n_frames][h][w]; flow f32 [n_frames-1][2][h][w] and flow_median, the same flow after
+ * va_flow_median with ksize 3 -> desc f32 [capacity][2*length + 33*nt*nxy*nxy] (shape | HOG | HOF | MBHx | MBHy; 426 values
+ * at the defaults), points f32 [capacity][length+1][2] (x, y), starts i32 [capacity] (first frame), in order of the last
+ * frame, then of the track.  *count (host) is the number of trajectories FOUND: when it exceeds capacity only the first
+ * `capacity` were written and the caller must say so.  rejected (host, 5 ints): left the frame, static, erratic, jump,
+ * still unfinished behind the last frame.  The call synchronises the stream once, at its end, to read these counts.
+ * workspace: 256-byte aligned, >= va_dtraj_workspace_bytes (VA_ERR_WORKSPACE otherwise).
+ */
+int va_dtraj_extract(va_ctx* ctx, const void* gray, int gray_is_u8, const void* flow, const void* flow_median, int n_frames,
+                     int w, int h, const va_dtraj_params* p, void* desc, void* points, void* starts, int capacity, int* count,
+                     int* rejected, void* workspace, size_t workspace_bytes, void* stream);
+
+/*
+ * Test entries, one per stage.  The track table is one device buffer, `state`, of va_dtraj_state_layout bytes (needs no
+ * device; 0 on bad values); offsets receives up to 8 byte offsets of its regions:
+ *   0 counts  i32 [16]: live tracks, current list (0 or 1), trajectories found, found before the last finish, rejected
+ *             [4..7] (left, static, erratic, jump)
+ *   1 lists   i32 [2][slots]: the slots of the live tracks in track order; slots = (w/step)(h/step) * length
+ *   2 status  i32 [slots] by list position, left by a step: 0 alive, 1 left the frame, 2 has `length` steps
+ *   3 start   i32 [slots]: first frame of the slot's track; a track that starts at frame t in grid cell c owns slot
+ *             (t mod length) * cells + c
+ *   4 points  f32 [slots][length+1][2]
+ *   5 sums    u64 [slots][nt][nxy*nxy][33]
+ *   6 occupancy i32 [cells], all 0 between calls        7 i32 [slots]: the slots the last finish wrote out
+ */
+size_t va_dtraj_state_layout(int w, int h, const va_dtraj_params* p, size_t* offsets, int capacity);
+
+/* S69-S71: gray [n][h][w], unfiltered flow f32 [n][2][h][w] -> votes u32 [n][33][h][w]
+ * (planes: HOG 0-7, HOF 8-16, MBHx 17-24, MBHy 25-32). */
+int va_dtraj_votes(va_ctx* ctx, const void* gray, int gray_is_u8, const void* flow, int n, int w, int h,
+                   const va_dtraj_params* p, void* votes, void* stream);
+
+/* S72: u32 [planes][h][w] -> u32 [planes][h+1][w+1], sums mod 2^32; w, h in [1,16384]. */
+int va_dtraj_integral(va_ctx* ctx, const void* votes, int planes, int w, int h, void* integral, void* stream);
+
+/* S73: gray [n][h][w] -> response f32 [n][h][w] and max_bits u32 [n], the bit pattern of each frame's largest response. */
+int va_dtraj_corner(va_ctx* ctx, const void* gray, int gray_is_u8, int n, int w, int h, void* response, void* max_bits,
+                    void* stream);
+
+/* S74: one frame's response [h][w] and max_bits [1]; appends the tracks that start at `frame` to the state. */
+int va_dtraj_sample(va_ctx* ctx, const void* response, const void* max_bits, int w, int h, int frame,
+                    const va_dtraj_params* p, void* state, void* stream);
+
+/* S75: one frame's integral planes u32 [33][h+1][w+1] and median-filtered flow f32 [2][h][w]; every live track adds its
+ * slice, moves, and gets its status. */
+int va_dtraj_step(va_ctx* ctx, const void* integral, const void* flow_median, int w, int h, int frame,
+                  const va_dtraj_params* p, void* state, void* stream);
+
+/* S76: the tracks with `length` steps are tested and written out (as va_dtraj_extract writes them, from index counts[2]
+ * on), the alive ones go to the other list, the counts are updated. */
+int va_dtraj_finish(va_ctx* ctx, int w, int h, const va_dtraj_params* p, void* state, void* desc, void* points, void* starts,
+                    int capacity, void* stream);
+
 /*
  * flow f32 [n_pairs][2][h][w] -> stack f32 [2*n_pairs][h][w]: channel 2k = x flow of pair k,
  * 2k+1 = y flow (Sheet03/temporalModel.py:83).  Each value is quantised to the 8-bit flow

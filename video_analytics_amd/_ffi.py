@@ -46,6 +46,8 @@ EXPORTS = [
     "va_tvl1_workspace_bytes_opt", "va_tvl1_flow_opt", "va_flow_median", "va_tvl1_launch_plan",
     "va_brox_default_params", "va_brox_workspace_bytes", "va_brox_flow", "va_brox_inner_step",
     "va_farneback_default_params", "va_farneback_workspace_bytes", "va_farneback_flow", "va_farneback_polyexp", "va_farneback_pass",
+    "va_dtraj_default_params", "va_dtraj_workspace_bytes", "va_dtraj_extract", "va_dtraj_state_layout",
+    "va_dtraj_votes", "va_dtraj_integral", "va_dtraj_corner", "va_dtraj_sample", "va_dtraj_step", "va_dtraj_finish",
 ]
 
 
@@ -156,6 +158,35 @@ for _i, _name in enumerate(FARNEBACK_TUNING_SLOTS):
     setattr(FarnebackParams, _name, _tuning_property(_i))
 
 
+# names of the slots of va_dtraj_params.tuning (csrc/va_internal.h, VA_DTRAJ_TUNE_*)
+DTRAJ_TUNING_SLOTS = ("chunk_frames", "votes_tile_w", "votes_tile_h")
+# the regions of the track table, in the order of va_dtraj_state_layout's offsets (include/va.h)
+DTRAJ_STATE_REGIONS = ("counts", "lists", "status", "start", "points", "sums", "occupancy", "pending")
+
+
+class DenseTrajParams(ctypes.Structure):
+    """Mirror of ``va_dtraj_params`` (include/va.h)."""
+    _fields_ = [
+        ("struct_bytes", ctypes.c_int),
+        ("step", ctypes.c_int),
+        ("length", ctypes.c_int),
+        ("patch", ctypes.c_int),
+        ("nxy", ctypes.c_int),
+        ("nt", ctypes.c_int),
+        ("quality", ctypes.c_float),
+        ("min_flow", ctypes.c_float),
+        ("min_std", ctypes.c_float),
+        ("max_std", ctypes.c_float),
+        ("max_dis", ctypes.c_float),
+        ("max_dis_share", ctypes.c_float),
+        ("tuning", ctypes.c_int * 8),
+    ]
+
+
+for _i, _name in enumerate(DTRAJ_TUNING_SLOTS):
+    setattr(DenseTrajParams, _name, _tuning_property(_i))
+
+
 class SolverParams(ctypes.Structure):
     """Mirror of ``va_solver`` (include/va.h)."""
     _fields_ = [
@@ -249,6 +280,27 @@ def lib():
     L.va_farneback_polyexp.restype = ci
     L.va_farneback_pass.argtypes = [vp, vp, vp, vp, vp, ci, ci, ci, ctypes.POINTER(FarnebackParams), vp]
     L.va_farneback_pass.restype = ci
+    pdt = ctypes.POINTER(DenseTrajParams)
+    L.va_dtraj_default_params.argtypes = [pdt]
+    L.va_dtraj_default_params.restype = None
+    L.va_dtraj_workspace_bytes.argtypes = [ci, ci, ci, ci, pdt]
+    L.va_dtraj_workspace_bytes.restype = sz
+    L.va_dtraj_state_layout.argtypes = [ci, ci, pdt, ctypes.POINTER(sz), ci]
+    L.va_dtraj_state_layout.restype = sz
+    L.va_dtraj_extract.argtypes = [vp, vp, ci, vp, vp, ci, ci, ci, pdt, vp, vp, vp, ci, ctypes.POINTER(ci), ctypes.POINTER(ci), vp, sz, vp]
+    L.va_dtraj_extract.restype = ci
+    L.va_dtraj_votes.argtypes = [vp, vp, ci, vp, ci, ci, ci, pdt, vp, vp]
+    L.va_dtraj_votes.restype = ci
+    L.va_dtraj_integral.argtypes = [vp, vp, ci, ci, ci, vp, vp]
+    L.va_dtraj_integral.restype = ci
+    L.va_dtraj_corner.argtypes = [vp, vp, ci, ci, ci, ci, vp, vp, vp]
+    L.va_dtraj_corner.restype = ci
+    L.va_dtraj_sample.argtypes = [vp, vp, vp, ci, ci, ci, pdt, vp, vp]
+    L.va_dtraj_sample.restype = ci
+    L.va_dtraj_step.argtypes = [vp, vp, vp, ci, ci, ci, pdt, vp, vp]
+    L.va_dtraj_step.restype = ci
+    L.va_dtraj_finish.argtypes = [vp, ci, ci, pdt, vp, vp, vp, vp, ci, vp]
+    L.va_dtraj_finish.restype = ci
     L.va_flow_to_stack.argtypes = [vp, vp, ci, ci, ci, cf, cf, cf, vp, vp]
     L.va_flow_to_stack.restype = ci
     L.va_flow_to_stack_crop.argtypes = [vp, vp, ci, ci, ci, cf, cf, cf, vp, ci, ci, vp, vp]
@@ -444,6 +496,25 @@ def default_farneback_params(**over):
     if lib().va_farneback_workspace_bytes(64, 64, 1, 2, ctypes.byref(p)) == 0:
         raise ValueError(lib().va_last_error().decode())
     return p
+
+
+def default_dense_traj_params(**over):
+    """``va_dtraj_default_params`` with keyword overrides: step, length, patch, nxy, nt, quality, min_flow, min_std, max_std,
+    max_dis, max_dis_share and the tuning slots ``DTRAJ_TUNING_SLOTS``.  An unknown name raises ValueError, and so does a value
+    out of range (the text is ``va_dtraj_workspace_bytes``', which names the field)."""
+    p = _default_params(DenseTrajParams, "va_dtraj_default_params", "dense-trajectory", over)
+    if lib().va_dtraj_state_layout(64, 64, ctypes.byref(p), None, 0) == 0:
+        raise ValueError(lib().va_last_error().decode())
+    return p
+
+
+def dtraj_state_layout(w, h, params):
+    """``va_dtraj_state_layout``: (bytes of the track table, {region name: byte offset}) -- see include/va.h."""
+    off = (ctypes.c_size_t * len(DTRAJ_STATE_REGIONS))()
+    n = lib().va_dtraj_state_layout(int(w), int(h), ctypes.byref(params), off, len(DTRAJ_STATE_REGIONS))
+    if n == 0:
+        raise ValueError(lib().va_last_error().decode())
+    return n, dict(zip(DTRAJ_STATE_REGIONS, (int(o) for o in off)))
 
 
 _ctx = {}

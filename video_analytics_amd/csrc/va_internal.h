@@ -93,6 +93,12 @@ enum {
     VA_FARNEBACK_TUNE_PASS_TILE_W = 2,  // 0: the library's tile; else the tile width of k_farneback_pass
     VA_FARNEBACK_TUNE_PASS_TILE_H = 3,  // likewise its height
 };                                      // (slots 4..7: reserved, 0)
+// va_dtraj_params.tuning[]: chunk length and tile shape (dtraj.hip).  No value changes a result.
+enum {
+    VA_DTRAJ_TUNE_CHUNK = 0,   // 0: the library's chunk; else the frames whose votes and integral planes are held at once
+    VA_DTRAJ_TUNE_TILE_W = 1,  // 0: the library's tile; else the tile width of k_dtraj_votes in pixels
+    VA_DTRAJ_TUNE_TILE_H = 2,  // likewise its height
+};                             // (slots 3..7: reserved, 0)
 
 // S12's bilinear sample of plane f (rows `pitch` floats apart) at (px, py): the position is clamped into the frame (a NaN
 // lands on 0), the taps are the four neighbours (the last row / column repeats), and the interpolation is plain float32 (no

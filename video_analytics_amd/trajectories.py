@@ -1,0 +1,102 @@
+"""Dense trajectories on MI355X (``va_dtraj_extract``): the extraction stage of the modelled project's
+Sheet02 -- sampling points, following them through the median-filtered flow, HOG / HOF / MBHx / MBHy histograms and the
+trajectory shape in a tube around each track -- ending at the per-trajectory descriptors ``[n, 426]``.
+
+The flow comes from this library (Farneback with Sheet02's arguments by default, Sheet02.py:191) or from the caller; the 3x3
+median Sheet02 applies before tracking (Sheet02.py:293-299) is ``flow.median_filter``.  PCA, the GMM and the Fisher vector
+(Sheet02.py:568-617) are not part of this module.
+"""
+import ctypes
+
+import torch
+
+from . import _ffi
+from . import flow as vflow
+
+REJECTED = ("left_frame", "static", "erratic", "jump", "unfinished")
+# what the outputs sized for the proven bound cells * (T - length) may take when max_trajectories is None
+MEMORY_BUDGET_BYTES = 8 << 30
+
+
+def descriptor_length(params):
+    """2 * length values of shape, then 8 + 9 + 8 + 8 bins in each of the nt * nxy * nxy cells: 426 at the defaults"""
+    return 2 * params.length + 33 * params.nt * params.nxy * params.nxy
+
+
+def trajectory_bound(w, h, n_frames, params):
+    """No video yields more: every grid cell can start one track at every frame t <= T - 1 - length (S74)."""
+    return (w // params.step) * (h // params.step) * max(n_frames - params.length, 0)
+
+
+def dense_trajectories(gray, flow=None, params=None, flow_params=None, max_trajectories=None, **over):
+    """gray: CUDA uint8 or float32 ``[T,H,W]`` in [0,255], T >= 2, H and W in [16,16384].
+
+    ``flow``: None computes ``farneback_flow(gray, flow_params)`` (an ``_ffi.Tvl1Params`` or ``_ffi.BroxParams`` in
+    ``flow_params`` selects those methods, as ``flow.tvl1_flow`` does everywhere); a CUDA float32 ``[T-1,2,H,W]`` tensor is
+    used as it is (a stored flow of ``extract_flow`` in float32 is one).  ``params``: an ``_ffi.DenseTrajParams`` or keyword
+    overrides (step, length, patch, nxy, nt, quality, min_flow, min_std, max_std, max_dis, max_dis_share), not both.
+
+    Returns a dict: ``desc`` float32 ``[n, 426]`` (shape 30 | HOG 96 | HOF 108 | MBHx 96 | MBHy 96 at the defaults),
+    ``points`` float32 ``[n, length+1, 2]`` (x, y), ``start`` int32 ``[n]`` (first frame), all CUDA and in order of the last
+    frame, then of the track; ``rejected``: a dict of the five counts ``REJECTED``; ``count``: n.  More than
+    ``max_trajectories`` raises ValueError stating the count found; nothing is cut short.  With ``max_trajectories=None``
+    the outputs are sized for ``trajectory_bound`` and the call raises ValueError when that does not fit
+    ``MEMORY_BUDGET_BYTES``.  The inputs are left untouched.
+    """
+    who = "dense_trajectories"
+    if not isinstance(gray, torch.Tensor) or not gray.is_cuda:
+        raise ValueError("%s: gray must be a CUDA tensor" % who)
+    if gray.dim() != 3 or gray.dtype not in (torch.uint8, torch.float32):
+        raise ValueError("%s: gray must be uint8 or float32 [T,H,W]" % who)
+    if gray.shape[0] < 2:
+        raise ValueError("%s: gray must hold at least 2 frames, got %d" % (who, gray.shape[0]))
+    if params is not None and over:
+        raise ValueError("%s: pass an _ffi.DenseTrajParams or keyword overrides, not both" % who)
+    p = params if params is not None else _ffi.default_dense_traj_params(**over)
+    if not isinstance(p, _ffi.DenseTrajParams):
+        raise ValueError("%s: params must be an _ffi.DenseTrajParams" % who)
+    gray = gray.contiguous()
+    T, H, W = gray.shape
+    if flow is None:
+        if flow_params is None:
+            flow = vflow.farneback_flow(gray)
+        else:
+            flow = vflow.tvl1_flow(gray, flow_params)
+    else:
+        if flow_params is not None:
+            raise ValueError("%s: flow_params describes the flow this call computes; with a given flow it must be None" % who)
+        if (not isinstance(flow, torch.Tensor) or flow.device != gray.device or flow.dtype != torch.float32
+                or tuple(flow.shape) != (T - 1, 2, H, W)):
+            raise ValueError("%s: flow must be a float32 [%d,2,%d,%d] tensor on gray's device" % (who, T - 1, H, W))
+        flow = flow.contiguous()
+    L = _ffi.lib()
+    dim, npts = descriptor_length(p), p.length + 1
+    if max_trajectories is None:
+        cap = max(trajectory_bound(W, H, T, p), 1)
+        need = cap * (dim + 2 * npts + 1) * 4
+        if need > MEMORY_BUDGET_BYTES:
+            raise ValueError("%s: the bound of %d trajectories needs %d bytes of output, more than MEMORY_BUDGET_BYTES (%d): pass "
+                             "max_trajectories" % (who, cap, need, MEMORY_BUDGET_BYTES))
+    else:
+        cap = int(max_trajectories)
+        if cap < 1:
+            raise ValueError("%s: max_trajectories must be >= 1, got %d" % (who, cap))
+    nbytes = L.va_dtraj_workspace_bytes(W, H, T, cap, ctypes.byref(p))
+    if nbytes == 0:
+        raise ValueError(L.va_last_error().decode())
+    dev = gray.device
+    median = vflow.median_filter(flow, 3)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    desc = torch.empty((cap, dim), dtype=torch.float32, device=dev)
+    points = torch.empty((cap, npts, 2), dtype=torch.float32, device=dev)
+    start = torch.empty((cap,), dtype=torch.int32, device=dev)
+    count = ctypes.c_int(0)
+    rejected = (ctypes.c_int * 5)()
+    _ffi.check(L.va_dtraj_extract(_ffi.ctx(dev.index), _ffi.ptr(gray), int(gray.dtype == torch.uint8), _ffi.ptr(flow), _ffi.ptr(median),
+                                  T, W, H, ctypes.byref(p), _ffi.ptr(desc), _ffi.ptr(points), _ffi.ptr(start), cap, ctypes.byref(count),
+                                  rejected, _ffi.ptr(ws), ws.numel(), _ffi.stream_ptr(dev)))
+    n = int(count.value)
+    if n > cap:
+        raise ValueError("%s: found %d trajectories, more than max_trajectories = %d" % (who, n, cap))
+    return {"desc": desc[:n], "points": points[:n], "start": start[:n], "rejected": dict(zip(REJECTED, (int(r) for r in rejected))),
+            "count": n}

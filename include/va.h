@@ -46,6 +46,8 @@
  *   va_linear_svm_predict   LinearSVC.predict on the joined descriptors:
  *                     Sheet03/combinedModel.py:38.
  *   va_linear_svm_fit*      LinearSVC().fit on the same descriptors: Sheet03/combinedModel.py:34-35.
+ *   va_pca_*, va_gmm_*, va_fisher_encode   PCA, the diagonal Gaussian mixture and the Fisher vector on the trajectory
+ *                     descriptors: Sheet02/Sheet02.py:568-617.
  *   va_vgg16_train_*  the batch-loop body of train(): Sheet03/spatialModel.py:165-182;
  *   va_vgg16_export/import_state   checkpoint contents: Sheet03/spatialModel.py:234-260.
  *
@@ -1206,6 +1208,78 @@ int va_vgg16_export_state(va_vgg16* model, int which, void* const* conv_w, void*
                           void* const* fc_w, void* const* fc_b, void* stream);
 int va_vgg16_import_state(va_vgg16* model, int which, const void* const* conv_w, const void* const* conv_b,
                           const void* const* fc_w, const void* const* fc_b, void* stream);
+
+/*
+ * Fisher vectors (csrc/fisher.hip): the part of the modelled project's Sheet02 between the trajectory
+ * descriptors and the linear SVM (Sheet02.py:568-617) -- PCA to 64 dimensions (Sheet02.py:40), a 256-component
+ * diagonal-covariance Gaussian mixture (Sheet02.py:41), one Fisher vector of length k + 2 k d per video.  All arithmetic is
+ * float64 (the descriptors are float32 and widened exactly); every sum has a fixed order that depends on the inputs and the
+ * parameters alone; there are no floating-point atomics.  The dense products run on v_mfma_f64_16x16x4_f64.
+ *
+ * va_pca_moments: x DEVICE float32 [n][d], 1 <= n, 1 <= d <= 2048.  sums: DEVICE float64 [1 + d + d*d]: the row count, the
+ * column sums, and X^T X as [d][d] of which the upper triangle (column >= row) is filled and the rest is 0.  first = 1
+ * stores, first = 0 adds to what sums holds: one call per video accumulates a training set that never sits in one tensor.
+ * Rows are summed in chunks of va_pca_chunk_rows(n, d) rows, then the chunks in ascending order.  workspace:
+ * va_pca_workspace_bytes(n, d) bytes (0 and va_last_error() for sizes out of range; never above 1 GiB), 8-byte aligned.
+ */
+size_t va_pca_workspace_bytes(int n, int d);
+int va_pca_chunk_rows(int n, int d);
+int va_pca_moments(va_ctx* ctx, const void* x, int n, int d, int first, void* sums, void* workspace, size_t workspace_bytes,
+                   void* stream);
+/* out float32 [n][m] = (x - mean) components^T: x float32 [n][d], mean float64 [d], components float64 [m][d],
+ * 1 <= m <= d <= 2048; accumulated in float64 over the columns in ascending groups of four, stored as float32.  No
+ * whitening (sklearn's PCA default, Sheet02.py:574). */
+int va_pca_transform(va_ctx* ctx, const void* x, int n, int d, const void* mean, const void* components, int m, void* out,
+                     void* stream);
+
+/*
+ * The statistics of a diagonal-covariance Gaussian mixture, the one hot path of fitting it and of encoding with it.
+ * For every row x of x float32 [n][d]:
+ *   log p_j = log w_j - 1/2 sum_c (x_c - mu_jc)^2 / var_jc - 1/2 sum_c log var_jc - d/2 log 2 pi   (evaluated expanded,
+ *             [x^2, x] against [-1/(2 var), mu / var], plus a constant per component: DESIGN.md S78)
+ *   gamma_j = exp(log p_j - logsumexp_j log p)              mode VA_GMM_SOFT
+ *           = 1 for the lowest j that attains max_j log p_j, else 0   mode VA_GMM_HARD
+ * and for every segment s (rows segments[s] .. segments[s+1]-1; segments: DEVICE int64 [n_segments + 1], ascending, from 0
+ * to n; empty segments allowed):
+ *   stats[s][j] = [ S0 = sum gamma_j | S1[d] = sum gamma_j x | S2[d] = sum gamma_j x^2 ]   float64 [n_segments][k][1 + 2d]
+ *   loglik[s]   = sum logsumexp_j log p                                                    float64 [n_segments] (both modes)
+ * weights [k], means [k][d], variances [k][d]: DEVICE float64.
+ * Limits, checked by va_gmm_workspace_bytes (0 and the field's name in va_last_error()): 1 <= n, 1 <= d <= 512,
+ * 1 <= k <= 256, 1 <= n_segments <= 65536, 16 <= chunk_rows <= 65536, chunk_rows <= batch_rows <= 65536.
+ * Order of the sums: rows are cut into chunks at every multiple of chunk_rows and at every segment boundary; within a
+ * chunk rows are added four at a time in ascending order, then the chunks of a segment in ascending order.  The
+ * responsibilities exist only for one batch of batch_rows rows (rounded down to a multiple of chunk_rows) at a time, so the
+ * workspace does not grow with n: gamma of one batch, the chunk sums of one batch, the expanded parameters.
+ */
+#define VA_GMM_SOFT 0
+#define VA_GMM_HARD 1
+typedef struct va_gmm_params {
+    int struct_bytes; /* sizeof(va_gmm_params) of the caller; a smaller value is refused */
+    int chunk_rows;   /* rows whose statistics are accumulated serially before the chunks are summed; default 1024 */
+    int batch_rows;   /* rows whose responsibilities exist at once; default 65536 */
+    int reserved[5];
+} va_gmm_params;
+void va_gmm_default_params(va_gmm_params* p);
+size_t va_gmm_workspace_bytes(int n, int d, int k, int n_segments, const va_gmm_params* p);
+int va_gmm_stats(va_ctx* ctx, const void* x, int n, int d, const void* segments, int n_segments, const void* weights,
+                 const void* means, const void* variances, int k, int mode, const va_gmm_params* p, void* stats, void* loglik,
+                 void* workspace, size_t workspace_bytes, void* stream);
+/* The responsibilities themselves, for tests and small inputs: gamma float64 [n][k], lse float64 [n] (the row's
+ * logsumexp), n <= 65536; the same kernel as va_gmm_stats'.  workspace: va_gmm_workspace_bytes(n, d, k, 1, NULL). */
+int va_gmm_posteriors(va_ctx* ctx, const void* x, int n, int d, const void* weights, const void* means, const void* variances,
+                      int k, int mode, void* gamma, void* lse, void* workspace, size_t workspace_bytes, void* stream);
+/* sklearn's diagonal M-step from the ascending sum of stats over its n_segments segments: nk = S0 + 10 DBL_EPSILON,
+ * mu = S1 / nk, var = S2 / nk - 2 (mu S1) / nk + mu^2 + reg_covar, w = nk / sum_j nk (j ascending).  One small kernel. */
+int va_gmm_mstep(va_ctx* ctx, const void* stats, int n_segments, int k, int d, double reg_covar, void* weights, void* means,
+                 void* variances, void* stream);
+/* out float32 [n_segments][k + 2 k d] = [ G_alpha [k] | G_mu [k][d] | G_sigma [k][d] ] (Sheet02.py:611-615), with T =
+ * counts[s] (DEVICE int64 [n_segments], the segment's rows) and sigma = sqrt(var):
+ *   G_alpha = (S0 - T w) / sqrt(w),  G_mu = (S1 - mu S0) / (sigma sqrt(w)),
+ *   G_sigma = ((S2 - 2 mu S1 + mu^2 S0) / var - S0) / sqrt(2 w),
+ * all divided by T; power > 0: sign(v) |v|^power (0: none, Sheet02's; 0.5: the improved Fisher vector); then divided by the
+ * L2 norm unless that is below 1e-6 (Sheet02.py:39, 112-115).  T = 0 gives zeros.  0 <= power <= 1. */
+int va_fisher_encode(va_ctx* ctx, const void* stats, const void* counts, int n_segments, int k, int d, const void* weights,
+                     const void* means, const void* variances, double power, void* out, void* stream);
 
 #ifdef __cplusplus
 }

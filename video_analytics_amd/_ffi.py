@@ -48,6 +48,8 @@ EXPORTS = [
     "va_farneback_default_params", "va_farneback_workspace_bytes", "va_farneback_flow", "va_farneback_polyexp", "va_farneback_pass",
     "va_dtraj_default_params", "va_dtraj_workspace_bytes", "va_dtraj_extract", "va_dtraj_state_layout",
     "va_dtraj_votes", "va_dtraj_integral", "va_dtraj_corner", "va_dtraj_sample", "va_dtraj_step", "va_dtraj_finish",
+    "va_pca_workspace_bytes", "va_pca_chunk_rows", "va_pca_moments", "va_pca_transform",
+    "va_gmm_default_params", "va_gmm_workspace_bytes", "va_gmm_stats", "va_gmm_posteriors", "va_gmm_mstep", "va_fisher_encode",
 ]
 
 
@@ -187,6 +189,19 @@ for _i, _name in enumerate(DTRAJ_TUNING_SLOTS):
     setattr(DenseTrajParams, _name, _tuning_property(_i))
 
 
+VA_GMM_SOFT, VA_GMM_HARD = 0, 1  # include/va.h: va_gmm_stats' mode
+
+
+class GmmParams(ctypes.Structure):
+    """Mirror of ``va_gmm_params`` (include/va.h)."""
+    _fields_ = [
+        ("struct_bytes", ctypes.c_int),
+        ("chunk_rows", ctypes.c_int),
+        ("batch_rows", ctypes.c_int),
+        ("reserved", ctypes.c_int * 5),
+    ]
+
+
 class SolverParams(ctypes.Structure):
     """Mirror of ``va_solver`` (include/va.h)."""
     _fields_ = [
@@ -301,6 +316,27 @@ def lib():
     L.va_dtraj_step.restype = ci
     L.va_dtraj_finish.argtypes = [vp, ci, ci, pdt, vp, vp, vp, vp, ci, vp]
     L.va_dtraj_finish.restype = ci
+    pgp, cdb = ctypes.POINTER(GmmParams), ctypes.c_double
+    L.va_pca_workspace_bytes.argtypes = [ci, ci]
+    L.va_pca_workspace_bytes.restype = sz
+    L.va_pca_chunk_rows.argtypes = [ci, ci]
+    L.va_pca_chunk_rows.restype = ci
+    L.va_pca_moments.argtypes = [vp, vp, ci, ci, ci, vp, vp, sz, vp]
+    L.va_pca_moments.restype = ci
+    L.va_pca_transform.argtypes = [vp, vp, ci, ci, vp, vp, ci, vp, vp]
+    L.va_pca_transform.restype = ci
+    L.va_gmm_default_params.argtypes = [pgp]
+    L.va_gmm_default_params.restype = None
+    L.va_gmm_workspace_bytes.argtypes = [ci, ci, ci, ci, pgp]
+    L.va_gmm_workspace_bytes.restype = sz
+    L.va_gmm_stats.argtypes = [vp, vp, ci, ci, vp, ci, vp, vp, vp, ci, ci, pgp, vp, vp, vp, sz, vp]
+    L.va_gmm_stats.restype = ci
+    L.va_gmm_posteriors.argtypes = [vp, vp, ci, ci, vp, vp, vp, ci, ci, vp, vp, vp, sz, vp]
+    L.va_gmm_posteriors.restype = ci
+    L.va_gmm_mstep.argtypes = [vp, vp, ci, ci, ci, cdb, vp, vp, vp, vp]
+    L.va_gmm_mstep.restype = ci
+    L.va_fisher_encode.argtypes = [vp, vp, vp, ci, ci, ci, vp, vp, vp, cdb, vp, vp]
+    L.va_fisher_encode.restype = ci
     L.va_flow_to_stack.argtypes = [vp, vp, ci, ci, ci, cf, cf, cf, vp, vp]
     L.va_flow_to_stack.restype = ci
     L.va_flow_to_stack_crop.argtypes = [vp, vp, ci, ci, ci, cf, cf, cf, vp, ci, ci, vp, vp]
@@ -504,6 +540,17 @@ def default_dense_traj_params(**over):
     out of range (the text is ``va_dtraj_workspace_bytes``', which names the field)."""
     p = _default_params(DenseTrajParams, "va_dtraj_default_params", "dense-trajectory", over)
     if lib().va_dtraj_state_layout(64, 64, ctypes.byref(p), None, 0) == 0:
+        raise ValueError(lib().va_last_error().decode())
+    return p
+
+
+def default_gmm_params(**over):
+    """``va_gmm_default_params`` with keyword overrides: chunk_rows (rows summed serially before the chunks are added, 16 ..
+    65536, default 1024) and batch_rows (rows whose responsibilities exist at once, chunk_rows .. 65536, default 65536).  An
+    unknown name raises ValueError, and so does a value out of range (the text is ``va_gmm_workspace_bytes``', which names the
+    field)."""
+    p = _default_params(GmmParams, "va_gmm_default_params", "GMM", over)
+    if lib().va_gmm_workspace_bytes(1, 1, 1, 1, ctypes.byref(p)) == 0:
         raise ValueError(lib().va_last_error().decode())
     return p
 

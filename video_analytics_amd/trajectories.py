@@ -3,15 +3,20 @@ Sheet02 -- sampling points, following them through the median-filtered flow, HOG
 trajectory shape in a tube around each track -- ending at the per-trajectory descriptors ``[n, 426]``.
 
 The flow comes from this library (Farneback with Sheet02's arguments by default, Sheet02.py:191) or from the caller; the 3x3
-median Sheet02 applies before tracking (Sheet02.py:293-299) is ``flow.median_filter``.  PCA, the GMM and the Fisher vector
-(Sheet02.py:568-617) are not part of this module.
+median Sheet02 applies before tracking (Sheet02.py:293-299) is ``flow.median_filter``.
+
+``TrajectoryClassifier`` is the rest of Sheet02's ``main()`` (Sheet02.py:568-617, 710-763) on top of ``desc``: PCA, the
+diagonal Gaussian mixture and the Fisher vectors of ``fisher``, then ``fusion.linear_svm_fit``.
 """
 import ctypes
 
+import numpy as np
 import torch
 
 from . import _ffi
+from . import fisher
 from . import flow as vflow
+from . import fusion
 
 REJECTED = ("left_frame", "static", "erratic", "jump", "unfinished")
 # what the outputs sized for the proven bound cells * (T - length) may take when max_trajectories is None
@@ -100,3 +105,88 @@ def dense_trajectories(gray, flow=None, params=None, flow_params=None, max_traje
         raise ValueError("%s: found %d trajectories, more than max_trajectories = %d" % (who, n, cap))
     return {"desc": desc[:n], "points": points[:n], "start": start[:n], "rejected": dict(zip(REJECTED, (int(r) for r in rejected))),
             "count": n}
+
+
+class TrajectoryClassifier(object):
+    """Sheet02's ``main()`` after the extraction (Sheet02.py:710-763): PCA of all training descriptors, a diagonal Gaussian
+    mixture fitted to the reduced rows, one Fisher vector per video, a linear SVM on those.
+
+    ``descs_per_video``: a list of CUDA float32 ``[n_i, d]`` tensors, one per video (``dense_trajectories(...)["desc"]``); a
+    video with no trajectories (``n_i = 0``) is legal and gets a zero vector.  The Fisher vector's length
+    ``n_gmm (1 + 2 n_components)`` must not exceed 8192, the widest problem ``fusion.linear_svm_fit`` takes; ``encode`` has no
+    such limit (Sheet02's 64 x 256 gives 33,024)."""
+
+    SVM_MAX_DIM = 8192
+
+    def __init__(self):
+        self.pca = self.gmm = self.coef = self.intercept = self.classes = None
+        self.power = 0.0
+
+    @staticmethod
+    def _videos(descs_per_video, who):
+        if isinstance(descs_per_video, torch.Tensor) or not isinstance(descs_per_video, (list, tuple)) or len(descs_per_video) == 0:
+            raise ValueError("%s: descs_per_video must be a non-empty list of CUDA float32 [n_i, d] tensors" % who)
+        for v in descs_per_video:
+            if not isinstance(v, torch.Tensor) or not v.is_cuda or v.dtype != torch.float32 or v.dim() != 2:
+                raise ValueError("%s: descs_per_video must be a non-empty list of CUDA float32 [n_i, d] tensors" % who)
+        if len(set(int(v.shape[1]) for v in descs_per_video)) != 1:
+            raise ValueError("%s: descs_per_video must share one descriptor length" % who)
+        segments = np.concatenate([[0], np.cumsum([int(v.shape[0]) for v in descs_per_video])]).astype(np.int64)
+        return list(descs_per_video), segments
+
+    def fit(self, descs_per_video, labels, n_components=64, n_gmm=256, power=0.0, **gmm_kw):
+        """PCA to ``n_components`` (Sheet02.py:40), ``gmm_fit`` with ``n_gmm`` components (Sheet02.py:41) and ``gmm_kw``,
+        Fisher vectors with ``power``, ``fusion.linear_svm_fit``.  -> self."""
+        who = "TrajectoryClassifier.fit"
+        videos, segments = self._videos(descs_per_video, who)
+        if len(labels) != len(videos):
+            raise ValueError("%s: %d videos but %d labels" % (who, len(videos), len(labels)))
+        if isinstance(n_gmm, bool) or not isinstance(n_gmm, (int, np.integer)) or n_gmm < 1:
+            raise ValueError("%s: n_gmm must be an integer >= 1, got %r" % (who, n_gmm))
+        if isinstance(n_components, (int, np.integer)) and n_gmm * (1 + 2 * n_components) > self.SVM_MAX_DIM:
+            raise ValueError("%s: the Fisher vector's length n_gmm (1 + 2 n_components) = %d exceeds the %d columns linear_svm_fit takes"
+                             % (who, n_gmm * (1 + 2 * n_components), self.SVM_MAX_DIM))
+        self.pca = fisher.pca_fit(videos, n_components)
+        reduced = self.pca.transform(torch.cat(videos, 0))
+        self.gmm = fisher.gmm_fit(reduced, n_gmm, **gmm_kw)
+        self.power = float(power)
+        fv = fisher.fisher_vectors(reduced, segments, self.gmm, self.power)
+        self.coef, self.intercept, self.classes = fusion.linear_svm_fit(fv, labels)
+        return self
+
+    def encode(self, descs_per_video):
+        """The Fisher vectors CUDA float32 ``[n_videos, K + 2KD]`` of the fitted PCA and mixture, for callers who fuse them
+        elsewhere."""
+        who = "TrajectoryClassifier.encode"
+        if self.pca is None or self.gmm is None:
+            raise ValueError("%s: the model is not fitted" % who)
+        videos, segments = self._videos(descs_per_video, who)
+        return fisher.fisher_vectors(self.pca.transform(torch.cat(videos, 0)), segments, self.gmm, self.power)
+
+    def predict(self, descs_per_video):
+        """-> the predicted labels, one per video (``fusion.linear_svm_predict`` on the Fisher vectors)."""
+        if self.coef is None:
+            raise ValueError("TrajectoryClassifier.predict: the model is not fitted")
+        fv = self.encode(descs_per_video)
+        return fusion.linear_svm_predict(fv.double().cpu().numpy(), self.coef, self.intercept, self.classes, device=fv.device.index)
+
+    def save(self, path):
+        if self.coef is None:
+            raise ValueError("TrajectoryClassifier.save: the model is not fitted")
+        with open(path, "wb") as f:
+            np.savez(f, pca_mean=self.pca.mean, pca_components=self.pca.components, pca_explained_variance=self.pca.explained_variance,
+                     pca_n_samples=np.int64(self.pca.n_samples), gmm_weights=self.gmm.weights, gmm_means=self.gmm.means,
+                     gmm_variances=self.gmm.variances, gmm_converged=np.bool_(self.gmm.converged), gmm_n_iter=np.int64(self.gmm.n_iter),
+                     gmm_lower_bound=np.float64(self.gmm.lower_bound), gmm_history=np.asarray(self.gmm.history, dtype=np.float64),
+                     power=np.float64(self.power), coef=self.coef, intercept=self.intercept, classes=self.classes)
+
+    @classmethod
+    def load(cls, path):
+        m = cls()
+        with np.load(path) as z:
+            m.pca = fisher.PCAModel(z["pca_mean"], z["pca_components"], z["pca_explained_variance"], int(z["pca_n_samples"]))
+            m.gmm = fisher.GMMModel(z["gmm_weights"], z["gmm_means"], z["gmm_variances"], bool(z["gmm_converged"]), int(z["gmm_n_iter"]),
+                                    float(z["gmm_lower_bound"]), z["gmm_history"].tolist())
+            m.power = float(z["power"])
+            m.coef, m.intercept, m.classes = z["coef"], z["intercept"], z["classes"]
+        return m

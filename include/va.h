@@ -48,6 +48,7 @@
  *   va_linear_svm_fit*      LinearSVC().fit on the same descriptors: Sheet03/combinedModel.py:34-35.
  *   va_pca_*, va_gmm_*, va_fisher_encode   PCA, the diagonal Gaussian mixture and the Fisher vector on the trajectory
  *                     descriptors: Sheet02/Sheet02.py:568-617.
+ *   va_stip_*         the space-time interest points and HOG / HOF cuboids of findSTIPs(): Sheet01/Sheet01.py:129-256.
  *   va_vgg16_train_*  the batch-loop body of train(): Sheet03/spatialModel.py:165-182;
  *   va_vgg16_export/import_state   checkpoint contents: Sheet03/spatialModel.py:234-260.
  *
@@ -472,6 +473,92 @@ int va_dtraj_step(va_ctx* ctx, const void* integral, const void* flow_median, in
  * on), the alive ones go to the other list, the counts are updated. */
 int va_dtraj_finish(va_ctx* ctx, int w, int h, const va_dtraj_params* p, void* state, void* desc, void* points, void* starts,
                     int capacity, void* stream);
+
+/* ------------------------------------------------------------------ Space-time interest points */
+
+/*
+ * Space-time interest points (Laptev, "On space-time interest points", IJCV 2005) with HOG / HOF cuboid descriptors, with
+ * the constants of the modelled project's Sheet01.py:13-23.  DESIGN.md S83-S90 are the specification; it is the build's own
+ * (no parity with Sheet01's arithmetic is claimed; S90 lists what Sheet01 does by accident and this library does not).  The
+ * volume is [T][h][w].  Per scale pair (sigma, tau): L = g(sigma, sigma, tau) * f, np.gradient's derivatives, the six
+ * products smoothed with (s sigma, s sigma, s tau), H = det - k trace^3, strict local maxima above min_response, and around
+ * each a cuboid of nx x ny x nt cells of `bins` orientation bins of (Lx, Ly) and of the flow.  Smoothing is float32 in one
+ * written order (the same bits under every tile shape); votes are fixed point and every later sum an integer sum.
+ * Values out of range give VA_ERR_INVALID, or a byte count of 0, and a message naming the field before anything is launched.
+ */
+#define VA_STIP_MAX_SIGMAS 8
+#define VA_STIP_MAX_TAUS 4
+#define VA_STIP_MAX_RADIUS 512
+typedef struct va_stip_params {
+    int struct_bytes;      /* sizeof(va_stip_params) of the caller; a smaller value is refused */
+    int n_sigmas;          /* 6; spatial scales in use, 1..8 */
+    int n_taus;            /* 2; temporal scales in use, 1..4 */
+    float sigmas[VA_STIP_MAX_SIGMAS]; /* 2^((1+i)/2), i = 1..6; each > 0 with int(4 s sigma + 0.5) <= 512 */
+    float taus[VA_STIP_MAX_TAUS];     /* 2^(j/2), j = 1, 2; likewise */
+    float integration;     /* 2.0; s: the products are smoothed with (s sigma, s sigma, s tau) */
+    float k;               /* 0.005; H = det - k trace^3 */
+    float min_response;    /* 0; a point has H > min_response (finite) */
+    float cuboid;          /* 9; the cuboid's sides are 2 cuboid sigma (x, y) and 2 cuboid tau (t) */
+    int neighbours;        /* 6 (the axes, Sheet01's rule) or 26 (Laptev's full neighbourhood) */
+    int nx, ny, nt;        /* 3, 3, 2; cells of a cuboid, each 1..8 */
+    int bins;              /* 4; orientation bins of 360 / bins degrees, 2..16; 2 nx ny nt bins <= 512 */
+    int tuning[8];         /* tile shapes of the smoothing passes (csrc/va_internal.h, VA_STIP_TUNE_*); 0 = the library's
+                              choice.  Results do not depend on any of them. */
+} va_stip_params;
+
+void va_stip_default_params(va_stip_params* p);
+
+/* Needs no device.  0 and a va_last_error text on bad parameters or sizes (w, h in [1,16384], n_frames in [2,65535],
+ * w h n_frames < 2^31, capacity >= 1).  The bytes hold ten float volumes (L, six products, two pass buffers, H), one volume
+ * of `bins` vote planes and two of integral planes, the row counts and the taps: one scale pair's worth, reused by all. */
+size_t va_stip_workspace_bytes(int w, int h, int n_frames, int capacity, const va_stip_params* p);
+
+/*
+ * gray u8 or f32 in [0,255] [n_frames][h][w]; flow f32 [n_frames-1][2][h][w] (the field of the last pair stands in for the
+ * last frame) -> points i32 [capacity][5] (x, y, t, sigma index, tau index), response f32 [capacity] (H there), desc f32
+ * [capacity][2 nx ny nt bins] (HOG | HOF, cells in (t, y, x) order, divided by the L2 norm of the whole; a zero norm gives
+ * zeros), in the order scale pair (sigma outer, tau inner), t, y, x.  *count (host) is the number of points FOUND: when it
+ * exceeds capacity only the first `capacity` were written and the caller must say so.  The call synchronises the stream
+ * twice: after the taps are uploaded, and at its end to read the count.
+ * workspace: 256-byte aligned, >= va_stip_workspace_bytes (VA_ERR_WORKSPACE otherwise).
+ */
+int va_stip_extract(va_ctx* ctx, const void* gray, int gray_is_u8, const void* flow, int n_frames, int w, int h,
+                    const va_stip_params* p, void* points, void* response, void* desc, int capacity, int* count,
+                    void* workspace, size_t workspace_bytes, void* stream);
+
+/* Test entries, one per stage. */
+
+/* S83: the taps g[0..r] of sigma as the device uses them; returns r = int(4 sigma + 0.5), or -1 (sigma <= 0, r > 512 or
+ * capacity < r + 1).  Needs no device. */
+int va_stip_taps(double sigma, float* taps, int capacity);
+
+/* S84: src u8 or f32 [n_frames][h][w] -> dst f32, smoothed with sigma along x and y and tau along t (reflected borders).
+ * tmp: device scratch of tmp_floats >= 2 n_frames h w + 2048 floats, 256-byte aligned.  p supplies the tuning only.
+ * n_frames, w, h >= 1 here.  dst may not alias src or tmp. */
+int va_stip_smooth(va_ctx* ctx, const void* src, int src_is_u8, int n_frames, int w, int h, double sigma, double tau,
+                   const va_stip_params* p, void* dst, void* tmp, size_t tmp_floats, void* stream);
+
+/* S85: L f32 [n_frames][h][w] -> products f32 [6][n_frames][h][w]: LxLx, LyLy, LtLt, LxLy, LxLt, LyLt. */
+int va_stip_gradient_products(va_ctx* ctx, const void* L, int n_frames, int w, int h, void* products, void* stream);
+
+/* S86: the six smoothed products -> H f32 [n_frames][h][w]. */
+int va_stip_response(va_ctx* ctx, const void* products, int n_frames, int w, int h, float k, void* H, void* stream);
+
+/* S87: H -> the maxima appended to points / response from index counts[0] on (never past capacity), tagged with the two
+ * scale indices.  counts: device i32 [16]; [0] points found so far (in and out), [1] its value before this call.
+ * scratch: device i32 [2 n_frames h + 256]. */
+int va_stip_maxima(va_ctx* ctx, const void* H, int n_frames, int w, int h, float min_response, int neighbours, int sigma_index,
+                   int tau_index, void* points, void* response, int capacity, void* counts, void* scratch, void* stream);
+
+/* S88: L f32 [n_frames][h][w] and flow f32 [n_frames-1][2][h][w] -> hog, hof u32 [n_frames][bins][h][w]; either output
+ * (with its input) may be NULL.  n_frames >= 2. */
+int va_stip_votes(va_ctx* ctx, const void* L, const void* flow, int n_frames, int w, int h, const va_stip_params* p, void* hog,
+                  void* hof, void* stream);
+
+/* S89: points i32 [n][5] and the integral planes u32 [n_frames][bins][h+1][w+1] of both groups (va_dtraj_integral of the
+ * votes) -> desc f32 [n][2 nx ny nt bins]. */
+int va_stip_describe(va_ctx* ctx, const void* points, int n, const void* hog_integral, const void* hof_integral, int n_frames,
+                     int w, int h, const va_stip_params* p, void* desc, void* stream);
 
 /*
  * flow f32 [n_pairs][2][h][w] -> stack f32 [2*n_pairs][h][w]: channel 2k = x flow of pair k,

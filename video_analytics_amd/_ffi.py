@@ -50,6 +50,8 @@ EXPORTS = [
     "va_dtraj_votes", "va_dtraj_integral", "va_dtraj_corner", "va_dtraj_sample", "va_dtraj_step", "va_dtraj_finish",
     "va_pca_workspace_bytes", "va_pca_chunk_rows", "va_pca_moments", "va_pca_transform",
     "va_gmm_default_params", "va_gmm_workspace_bytes", "va_gmm_stats", "va_gmm_posteriors", "va_gmm_mstep", "va_fisher_encode",
+    "va_stip_default_params", "va_stip_workspace_bytes", "va_stip_extract", "va_stip_taps", "va_stip_smooth",
+    "va_stip_gradient_products", "va_stip_response", "va_stip_maxima", "va_stip_votes", "va_stip_describe",
 ]
 
 
@@ -189,6 +191,53 @@ for _i, _name in enumerate(DTRAJ_TUNING_SLOTS):
     setattr(DenseTrajParams, _name, _tuning_property(_i))
 
 
+# names of the slots of va_stip_params.tuning (csrc/va_internal.h, VA_STIP_TUNE_*)
+STIP_TUNING_SLOTS = ("row_tile_w", "col_tile_w", "col_tile_n")
+STIP_MAX_SIGMAS, STIP_MAX_TAUS, STIP_MAX_RADIUS = 8, 4, 512
+
+
+class StipParams(ctypes.Structure):
+    """Mirror of ``va_stip_params`` (include/va.h).  ``sigma_list`` and ``tau_list`` read and write the
+    scales in use together with their counts."""
+    _fields_ = [
+        ("struct_bytes", ctypes.c_int),
+        ("n_sigmas", ctypes.c_int),
+        ("n_taus", ctypes.c_int),
+        ("sigmas", ctypes.c_float * STIP_MAX_SIGMAS),
+        ("taus", ctypes.c_float * STIP_MAX_TAUS),
+        ("integration", ctypes.c_float),
+        ("k", ctypes.c_float),
+        ("min_response", ctypes.c_float),
+        ("cuboid", ctypes.c_float),
+        ("neighbours", ctypes.c_int),
+        ("nx", ctypes.c_int),
+        ("ny", ctypes.c_int),
+        ("nt", ctypes.c_int),
+        ("bins", ctypes.c_int),
+        ("tuning", ctypes.c_int * 8),
+    ]
+
+
+def _scale_list(field, count, limit):
+    def get(self):
+        return [float(v) for v in getattr(self, field)[:getattr(self, count)]]
+
+    def put(self, values):
+        values = [float(v) for v in values]
+        if not 1 <= len(values) <= limit:
+            raise ValueError("%s must hold 1 to %d scales, got %d" % (field, limit, len(values)))
+        for i in range(limit):
+            getattr(self, field)[i] = values[i] if i < len(values) else 0.0
+        setattr(self, count, len(values))
+    return property(get, put)
+
+
+StipParams.sigma_list = _scale_list("sigmas", "n_sigmas", STIP_MAX_SIGMAS)
+StipParams.tau_list = _scale_list("taus", "n_taus", STIP_MAX_TAUS)
+for _i, _name in enumerate(STIP_TUNING_SLOTS):
+    setattr(StipParams, _name, _tuning_property(_i))
+
+
 VA_GMM_SOFT, VA_GMM_HARD = 0, 1  # include/va.h: va_gmm_stats' mode
 
 
@@ -317,6 +366,27 @@ def lib():
     L.va_dtraj_finish.argtypes = [vp, ci, ci, pdt, vp, vp, vp, vp, ci, vp]
     L.va_dtraj_finish.restype = ci
     pgp, cdb = ctypes.POINTER(GmmParams), ctypes.c_double
+    psp = ctypes.POINTER(StipParams)
+    L.va_stip_default_params.argtypes = [psp]
+    L.va_stip_default_params.restype = None
+    L.va_stip_workspace_bytes.argtypes = [ci, ci, ci, ci, psp]
+    L.va_stip_workspace_bytes.restype = sz
+    L.va_stip_extract.argtypes = [vp, vp, ci, vp, ci, ci, ci, psp, vp, vp, vp, ci, ctypes.POINTER(ci), vp, sz, vp]
+    L.va_stip_extract.restype = ci
+    L.va_stip_taps.argtypes = [cdb, ctypes.POINTER(cf), ci]
+    L.va_stip_taps.restype = ci
+    L.va_stip_smooth.argtypes = [vp, vp, ci, ci, ci, ci, cdb, cdb, psp, vp, vp, sz, vp]
+    L.va_stip_smooth.restype = ci
+    L.va_stip_gradient_products.argtypes = [vp, vp, ci, ci, ci, vp, vp]
+    L.va_stip_gradient_products.restype = ci
+    L.va_stip_response.argtypes = [vp, vp, ci, ci, ci, cf, vp, vp]
+    L.va_stip_response.restype = ci
+    L.va_stip_maxima.argtypes = [vp, vp, ci, ci, ci, cf, ci, ci, ci, vp, vp, ci, vp, vp, vp]
+    L.va_stip_maxima.restype = ci
+    L.va_stip_votes.argtypes = [vp, vp, vp, ci, ci, ci, psp, vp, vp, vp]
+    L.va_stip_votes.restype = ci
+    L.va_stip_describe.argtypes = [vp, vp, ci, vp, vp, ci, ci, ci, psp, vp, vp]
+    L.va_stip_describe.restype = ci
     L.va_pca_workspace_bytes.argtypes = [ci, ci]
     L.va_pca_workspace_bytes.restype = sz
     L.va_pca_chunk_rows.argtypes = [ci, ci]
@@ -542,6 +612,32 @@ def default_dense_traj_params(**over):
     if lib().va_dtraj_state_layout(64, 64, ctypes.byref(p), None, 0) == 0:
         raise ValueError(lib().va_last_error().decode())
     return p
+
+
+def default_stip_params(**over):
+    """``va_stip_default_params`` with keyword overrides: sigmas and taus (lists of 1..8 and 1..4 scales), integration, k,
+    min_response, cuboid, neighbours, nx, ny, nt, bins and the tuning slots ``STIP_TUNING_SLOTS``.  An unknown name raises
+    ValueError, and so does a value out of range (the text is ``va_stip_workspace_bytes``', which names the field)."""
+    over = dict(over)
+    lists = {k: over.pop(k) for k in ("sigmas", "taus") if k in over}
+    p = _default_params(StipParams, "va_stip_default_params", "space-time interest point", over)
+    if "sigmas" in lists:
+        p.sigma_list = lists["sigmas"]
+    if "taus" in lists:
+        p.tau_list = lists["taus"]
+    if lib().va_stip_workspace_bytes(64, 64, 8, 1, ctypes.byref(p)) == 0:
+        raise ValueError(lib().va_last_error().decode())
+    return p
+
+
+def stip_taps(sigma):
+    """``va_stip_taps``: the float32 taps g[0..r] of ``sigma`` as the device uses them (numpy array of r + 1 values)."""
+    import numpy as np
+    buf = (ctypes.c_float * (STIP_MAX_RADIUS + 1))()
+    r = lib().va_stip_taps(float(sigma), buf, STIP_MAX_RADIUS + 1)
+    if r < 0:
+        raise ValueError("stip_taps: sigma must be > 0 with a radius int(4 sigma + 0.5) <= %d, got %r" % (STIP_MAX_RADIUS, sigma))
+    return np.frombuffer(buf, dtype=np.float32, count=r + 1).copy()
 
 
 def default_gmm_params(**over):

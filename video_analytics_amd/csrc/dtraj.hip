@@ -31,10 +31,6 @@ constexpr float kHogVmax = 2048.0f, kHogScale = 256.0f;      // S = 8
 constexpr float kFlowVmax = 32.0f, kFlowScale = 16384.0f;    // S = 14
 constexpr double kHogUnit = 1.0 / 256.0, kFlowUnit = 1.0 / 16384.0;
 
-// S70: p(s) ~ atan(s) 4 / pi on [0,1], odd, Horner in s^2
-constexpr float kAtanC0 = 1.2732345f, kAtanC1 = -0.4242086f, kAtanC2 = 0.25219768f, kAtanC3 = -0.16850284f, kAtanC4 = 0.10143076f,
-                kAtanC5 = -0.042850755f, kAtanC6 = 0.0086996285f;
-
 // state counts (int32 each)
 enum { C_LIVE = 0, C_CUR = 1, C_OUT = 2, C_OUT0 = 3, C_REJ = 4, C_WORDS = 16 };
 // what a step leaves for a track
@@ -76,39 +72,10 @@ __device__ __forceinline__ void sobel(const float* t, int RW, float& gx, float& 
     gy = ((bl - tl) + 2.0f * (bc - tc)) + (br - tr);
 }
 
-// S70: magnitude and bin coordinate in [0,8] of the vector (x, y)
-__device__ __forceinline__ void orient(float x, float y, float& m, float& a)
-{
-    m = sqrtf(x * x + y * y);
-    const float ax = fabsf(x), ay = fabsf(y);
-    const float lo = fminf(ax, ay), hi = fmaxf(ax, ay);
-    const float s = lo / (hi > 0.0f ? hi : 1.0f);
-    const float s2 = s * s;
-    float p = kAtanC6;
-    p = p * s2 + kAtanC5;
-    p = p * s2 + kAtanC4;
-    p = p * s2 + kAtanC3;
-    p = p * s2 + kAtanC2;
-    p = p * s2 + kAtanC1;
-    p = p * s2 + kAtanC0;
-    p = p * s;
-    if (ay > ax) p = 2.0f - p;
-    if (x < 0.0f) p = 4.0f - p;
-    if (y < 0.0f) p = 8.0f - p;
-    a = p;
-}
-
-// S70-S71: the two quantised votes of one group; a magnitude that is not finite votes nothing
+// S70-S71 with this file's 8 bins (va_internal.h holds the functions: stip.hip votes with them too)
 __device__ __forceinline__ void votes_of(float x, float y, float vmax, float scale, int& b0, unsigned& q0, unsigned& q1, float& m)
 {
-    float a;
-    orient(x, y, m, a);
-    b0 = 0, q0 = 0u, q1 = 0u;
-    if (!(fabsf(m) <= 3.4028234663852886e38f)) return;
-    const float fl = floorf(a), f = a - fl;
-    b0 = (int)fl & 7;
-    q0 = (unsigned)rintf(fminf(m * (1.0f - f), vmax) * scale);
-    q1 = (unsigned)rintf(fminf(m * f, vmax) * scale);
+    va_votes_of(x, y, vmax, scale, 8, b0, q0, q1, m);
 }
 
 struct VoteArgs {

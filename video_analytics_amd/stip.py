@@ -1,0 +1,99 @@
+"""Space-time interest points on MI355X (``va_stip_extract``): the detector and descriptors of the
+modelled project's Sheet01 -- Laptev's Harris3D response at every pair of a spatial and a temporal scale, its strict local
+maxima, and around each a cuboid of HOG / HOF histograms -- ending at the per-point descriptors ``[n, 144]``.
+
+The flow comes from this library (Farneback with Sheet01's arguments by default, Sheet01.py:79) or from the caller.  It is
+computed once on the input frames and shared by all scales.  The k-means codebook and the bag-of-words histograms
+(Sheet01.py:259-277) are not part of this module.
+"""
+import ctypes
+
+import torch
+
+from . import _ffi
+from . import flow as vflow
+
+# what the outputs sized for the proven bound may take when max_points is None
+MEMORY_BUDGET_BYTES = 8 << 30
+
+
+def descriptor_length(params):
+    """HOG then HOF, ``bins`` values in each of the nx * ny * nt cells: 144 at the defaults"""
+    return 2 * params.nx * params.ny * params.nt * params.bins
+
+
+def point_bound(w, h, n_frames, params):
+    """No video yields more: strict maxima along x cannot be adjacent and the faces never qualify, so a row holds at most
+    ceil((w - 2) / 2) of them, and only the (h - 2)(T - 2) inner rows hold any, at each scale pair (S87)."""
+    per_row = max((w - 2 + 1) // 2, 0)
+    return per_row * max(h - 2, 0) * max(n_frames - 2, 0) * params.n_sigmas * params.n_taus
+
+
+def space_time_interest_points(gray, flow=None, params=None, flow_params=None, max_points=None, **over):
+    """gray: CUDA uint8 or float32 ``[T,H,W]`` in [0,255], T >= 2, H and W in [1,16384].
+
+    ``flow``: None computes ``farneback_flow(gray, flow_params)`` (an ``_ffi.Tvl1Params`` or ``_ffi.BroxParams`` in
+    ``flow_params`` selects those methods, as ``flow.tvl1_flow`` does everywhere); a CUDA float32 ``[T-1,2,H,W]`` tensor is
+    used as it is.  ``params``: an ``_ffi.StipParams`` or keyword overrides (sigmas, taus, integration, k, min_response,
+    cuboid, neighbours, nx, ny, nt, bins), not both.
+
+    Returns a dict: ``desc`` float32 ``[n, 144]`` (HOG 72 | HOF 72 at the defaults), ``points`` int32 ``[n, 5]`` (x, y, t,
+    sigma index, tau index), ``response`` float32 ``[n]``, all CUDA and in the order scale pair (sigma outer, tau inner), t,
+    y, x; ``count``: n.  More than ``max_points`` raises ValueError stating the count found; nothing is cut short.  With
+    ``max_points=None`` the outputs are sized for ``point_bound`` and the call raises ValueError when that does not fit
+    ``MEMORY_BUDGET_BYTES``.  The inputs are left untouched.
+    """
+    who = "space_time_interest_points"
+    if not isinstance(gray, torch.Tensor) or not gray.is_cuda:
+        raise ValueError("%s: gray must be a CUDA tensor" % who)
+    if gray.dim() != 3 or gray.dtype not in (torch.uint8, torch.float32):
+        raise ValueError("%s: gray must be uint8 or float32 [T,H,W]" % who)
+    if gray.shape[0] < 2:
+        raise ValueError("%s: gray must hold at least 2 frames, got %d" % (who, gray.shape[0]))
+    if params is not None and over:
+        raise ValueError("%s: pass an _ffi.StipParams or keyword overrides, not both" % who)
+    p = params if params is not None else _ffi.default_stip_params(**over)
+    if not isinstance(p, _ffi.StipParams):
+        raise ValueError("%s: params must be an _ffi.StipParams" % who)
+    gray = gray.contiguous()
+    T, H, W = gray.shape
+    if flow is None:
+        if flow_params is None:
+            flow = vflow.farneback_flow(gray)
+        else:
+            flow = vflow.tvl1_flow(gray, flow_params)
+    else:
+        if flow_params is not None:
+            raise ValueError("%s: flow_params describes the flow this call computes; with a given flow it must be None" % who)
+        if (not isinstance(flow, torch.Tensor) or flow.device != gray.device or flow.dtype != torch.float32
+                or tuple(flow.shape) != (T - 1, 2, H, W)):
+            raise ValueError("%s: flow must be a float32 [%d,2,%d,%d] tensor on gray's device" % (who, T - 1, H, W))
+        flow = flow.contiguous()
+    L = _ffi.lib()
+    dim = descriptor_length(p)
+    if max_points is None:
+        cap = max(point_bound(W, H, T, p), 1)
+        need = cap * (dim + 5 + 1) * 4
+        if need > MEMORY_BUDGET_BYTES:
+            raise ValueError("%s: the bound of %d points needs %d bytes of output, more than MEMORY_BUDGET_BYTES (%d): pass max_points"
+                             % (who, cap, need, MEMORY_BUDGET_BYTES))
+    else:
+        cap = int(max_points)
+        if cap < 1:
+            raise ValueError("%s: max_points must be >= 1, got %d" % (who, cap))
+    nbytes = L.va_stip_workspace_bytes(W, H, T, cap, ctypes.byref(p))
+    if nbytes == 0:
+        raise ValueError(L.va_last_error().decode())
+    dev = gray.device
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    desc = torch.empty((cap, dim), dtype=torch.float32, device=dev)
+    points = torch.empty((cap, 5), dtype=torch.int32, device=dev)
+    response = torch.empty((cap,), dtype=torch.float32, device=dev)
+    count = ctypes.c_int(0)
+    _ffi.check(L.va_stip_extract(_ffi.ctx(dev.index), _ffi.ptr(gray), int(gray.dtype == torch.uint8), _ffi.ptr(flow), T, W, H,
+                                 ctypes.byref(p), _ffi.ptr(points), _ffi.ptr(response), _ffi.ptr(desc), cap, ctypes.byref(count),
+                                 _ffi.ptr(ws), ws.numel(), _ffi.stream_ptr(dev)))
+    n = int(count.value)
+    if n > cap:
+        raise ValueError("%s: found %d points, more than max_points = %d" % (who, n, cap))
+    return {"desc": desc[:n], "points": points[:n], "response": response[:n], "count": n}

@@ -49,6 +49,7 @@
  *   va_pca_*, va_gmm_*, va_fisher_encode   PCA, the diagonal Gaussian mixture and the Fisher vector on the trajectory
  *                     descriptors: Sheet02/Sheet02.py:568-617.
  *   va_stip_*         the space-time interest points and HOG / HOF cuboids of findSTIPs(): Sheet01/Sheet01.py:129-256.
+ *   va_kmeans_*, va_bow_*   makeCodebook() and makeVideoHistogram(): Sheet01/Sheet01.py:259-277.
  *   va_vgg16_train_*  the batch-loop body of train(): Sheet03/spatialModel.py:165-182;
  *   va_vgg16_export/import_state   checkpoint contents: Sheet03/spatialModel.py:234-260.
  *
@@ -1367,6 +1368,57 @@ int va_gmm_mstep(va_ctx* ctx, const void* stats, int n_segments, int k, int d, d
  * L2 norm unless that is below 1e-6 (Sheet02.py:39, 112-115).  T = 0 gives zeros.  0 <= power <= 1. */
 int va_fisher_encode(va_ctx* ctx, const void* stats, const void* counts, int n_segments, int k, int d, const void* weights,
                      const void* means, const void* variances, double power, void* out, void* stream);
+
+/*
+ * Bag of words (csrc/codebook.hip): the k-means codebook and the per-video histograms of the modelled
+ * project's Sheet01 (Sheet01.py:259-277).  x: DEVICE float32 [n][d], widened exactly; centres: DEVICE float64 [k][d]; all
+ * arithmetic is float64 in a fixed order, there are no floating-point atomics, and nothing of size n * k exists.
+ * Limits, checked by va_kmeans_workspace_bytes (0 and the field's name in va_last_error()): 1 <= n <= 2^31 - 1,
+ * 1 <= d <= 512, 1 <= k <= 4096, 1 <= n_segments <= 65536, 64 <= chunk_rows <= 2^20.  One workspace size serves every entry
+ * point below (256-byte aligned): O(n) integers (labels and a permutation), n / 256 doubles and n k / chunk_rows integers.
+ * chunk_rows is the chunk of the counting sort in va_kmeans_update; the sort is stable, so no result depends on it (it is
+ * raised internally so that there are never more than 65536 chunks).
+ */
+#define VA_BOW_NONE 0
+#define VA_BOW_L1 1
+#define VA_BOW_L2 2
+typedef struct va_kmeans_params {
+    int struct_bytes; /* sizeof(va_kmeans_params) of the caller; a smaller value is refused */
+    int chunk_rows;   /* rows per chunk of the counting sort; default 8192 */
+    int reserved[6];
+} va_kmeans_params;
+void va_kmeans_default_params(va_kmeans_params* p);
+size_t va_kmeans_workspace_bytes(int n, int d, int k, int n_segments, const va_kmeans_params* p);
+/* The centres of one LDS tile of va_kmeans_assign (64): the sizes at which its tests walk one tile more. */
+int va_kmeans_tile_centres(void);
+/* labels int32 [n]: the lowest j that attains min_j s_ij, s_ij = 1/2 |c_j|^2 - x_i . c_j (|c_j|^2 summed over the columns in
+ * ascending order, the products on the float64 MFMA, centres walked in LDS tiles with a running (min, index) per row; ties
+ * go to the lower index).  d2 float64 [n] or NULL: sum_c (x_ic - c_{label,c})^2, columns ascending, computed directly after
+ * the arg-min.  inertia float64 [1]: the sum of d2 (blocks of 256 rows by a fixed tree, then the blocks).  changed
+ * uint64 [1]: the rows whose label differs from prev_labels (int32 [n], or NULL: every row). */
+int va_kmeans_assign(va_ctx* ctx, const void* x, int n, int d, const void* centres, int k, const void* prev_labels, void* labels,
+                     void* d2, void* inertia, void* changed, void* workspace, size_t workspace_bytes, void* stream);
+/* counts int64 [k]; new_centres float64 [k][d]: the mean of the cluster's rows, added in the tree of DESIGN.md S92 over the
+ * rows in ascending order; an empty cluster keeps its centre.  shift2 float64 [1] = sum_j |new_j - old_j|^2, j ascending.
+ * Labels outside 0 .. k-1 are counted nowhere. */
+int va_kmeans_update(va_ctx* ctx, const void* x, int n, int d, const void* labels, const void* centres, int k,
+                     const va_kmeans_params* p, void* counts, void* new_centres, void* shift2, void* workspace,
+                     size_t workspace_bytes, void* stream);
+/* k-means++ (Arthur and Vassilvitskii; one trial per centre) from u float64 [k] in [0, 1): centre 0 is row floor(u_0 n);
+ * for j >= 1, m_i = min(m_i, |x_i - c_{j-1}|^2) and the chosen row is the lowest i whose running sum of m
+ * exceeds u_j total, the last row with m_i > 0 if there is none, floor(u_j n) when total = 0.  No host synchronisation.
+ * centres float64 [k][d], rows int32 [k], m float64 [n] (as after the last step; +inf when k = 1). */
+int va_kmeans_seed(va_ctx* ctx, const void* x, int n, int d, const void* u, int k, void* centres, void* rows, void* m,
+                   void* workspace, size_t workspace_bytes, void* stream);
+/* out float32 [n_segments][k]: the counts of the labels (int32 [n]) of the rows segments[s] .. segments[s+1]-1 (DEVICE
+ * int64 [n_segments + 1], as va_gmm_stats'), counted in integers, then divided once by their L2 norm (VA_BOW_L2, Sheet01's
+ * normalize), their sum (VA_BOW_L1) or nothing (VA_BOW_NONE); the norm is float64 over the words in ascending order.  An
+ * empty segment gives zeros. */
+int va_bow_histograms(va_ctx* ctx, const void* labels, int n, const void* segments, int n_segments, int k, int norm, void* out,
+                      void* stream);
+/* va_kmeans_assign's labels (kept in the workspace; no d2) followed by va_bow_histograms, in one call. */
+int va_bow_encode(va_ctx* ctx, const void* x, int n, int d, const void* centres, int k, const void* segments, int n_segments,
+                  int norm, void* out, void* workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

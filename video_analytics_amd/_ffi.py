@@ -52,6 +52,8 @@ EXPORTS = [
     "va_gmm_default_params", "va_gmm_workspace_bytes", "va_gmm_stats", "va_gmm_posteriors", "va_gmm_mstep", "va_fisher_encode",
     "va_stip_default_params", "va_stip_workspace_bytes", "va_stip_extract", "va_stip_taps", "va_stip_smooth",
     "va_stip_gradient_products", "va_stip_response", "va_stip_maxima", "va_stip_votes", "va_stip_describe",
+    "va_kmeans_default_params", "va_kmeans_workspace_bytes", "va_kmeans_tile_centres", "va_kmeans_assign", "va_kmeans_update",
+    "va_kmeans_seed", "va_bow_histograms", "va_bow_encode",
 ]
 
 
@@ -251,6 +253,18 @@ class GmmParams(ctypes.Structure):
     ]
 
 
+VA_BOW_NONE, VA_BOW_L1, VA_BOW_L2 = 0, 1, 2  # include/va.h: va_bow_histograms' norm
+
+
+class KmeansParams(ctypes.Structure):
+    """Mirror of ``va_kmeans_params`` (include/va.h)."""
+    _fields_ = [
+        ("struct_bytes", ctypes.c_int),
+        ("chunk_rows", ctypes.c_int),
+        ("reserved", ctypes.c_int * 6),
+    ]
+
+
 class SolverParams(ctypes.Structure):
     """Mirror of ``va_solver`` (include/va.h)."""
     _fields_ = [
@@ -407,6 +421,23 @@ def lib():
     L.va_gmm_mstep.restype = ci
     L.va_fisher_encode.argtypes = [vp, vp, vp, ci, ci, ci, vp, vp, vp, cdb, vp, vp]
     L.va_fisher_encode.restype = ci
+    pkp = ctypes.POINTER(KmeansParams)
+    L.va_kmeans_default_params.argtypes = [pkp]
+    L.va_kmeans_default_params.restype = None
+    L.va_kmeans_workspace_bytes.argtypes = [ci, ci, ci, ci, pkp]
+    L.va_kmeans_workspace_bytes.restype = sz
+    L.va_kmeans_tile_centres.argtypes = []
+    L.va_kmeans_tile_centres.restype = ci
+    L.va_kmeans_assign.argtypes = [vp, vp, ci, ci, vp, ci, vp, vp, vp, vp, vp, vp, sz, vp]
+    L.va_kmeans_assign.restype = ci
+    L.va_kmeans_update.argtypes = [vp, vp, ci, ci, vp, vp, ci, pkp, vp, vp, vp, vp, sz, vp]
+    L.va_kmeans_update.restype = ci
+    L.va_kmeans_seed.argtypes = [vp, vp, ci, ci, vp, ci, vp, vp, vp, vp, sz, vp]
+    L.va_kmeans_seed.restype = ci
+    L.va_bow_histograms.argtypes = [vp, vp, ci, vp, ci, ci, ci, vp, vp]
+    L.va_bow_histograms.restype = ci
+    L.va_bow_encode.argtypes = [vp, vp, ci, ci, vp, ci, vp, ci, ci, vp, vp, sz, vp]
+    L.va_bow_encode.restype = ci
     L.va_flow_to_stack.argtypes = [vp, vp, ci, ci, ci, cf, cf, cf, vp, vp]
     L.va_flow_to_stack.restype = ci
     L.va_flow_to_stack_crop.argtypes = [vp, vp, ci, ci, ci, cf, cf, cf, vp, ci, ci, vp, vp]
@@ -647,6 +678,16 @@ def default_gmm_params(**over):
     field)."""
     p = _default_params(GmmParams, "va_gmm_default_params", "GMM", over)
     if lib().va_gmm_workspace_bytes(1, 1, 1, 1, ctypes.byref(p)) == 0:
+        raise ValueError(lib().va_last_error().decode())
+    return p
+
+
+def default_kmeans_params(**over):
+    """``va_kmeans_default_params`` with keyword overrides: chunk_rows (rows per chunk of the update's counting sort, 64 ..
+    2^20, default 8192; no result depends on it).  An unknown name raises ValueError, and so does a value out of range (the
+    text is ``va_kmeans_workspace_bytes``', which names the field)."""
+    p = _default_params(KmeansParams, "va_kmeans_default_params", "k-means", over)
+    if lib().va_kmeans_workspace_bytes(1, 1, 1, 1, ctypes.byref(p)) == 0:
         raise ValueError(lib().va_last_error().decode())
     return p
 

@@ -3,15 +3,18 @@ modelled project's Sheet01 -- Laptev's Harris3D response at every pair of a spat
 maxima, and around each a cuboid of HOG / HOF histograms -- ending at the per-point descriptors ``[n, 144]``.
 
 The flow comes from this library (Farneback with Sheet01's arguments by default, Sheet01.py:79) or from the caller.  It is
-computed once on the input frames and shared by all scales.  The k-means codebook and the bag-of-words histograms
-(Sheet01.py:259-277) are not part of this module.
+computed once on the input frames and shared by all scales.  ``StipClassifier`` carries the descriptors on to a class label:
+the k-means codebook and the bag-of-words histograms of ``codebook`` (Sheet01.py:259-277) and a linear SVM (Sheet01.py:379-390).
 """
 import ctypes
 
+import numpy as np
 import torch
 
 from . import _ffi
+from . import codebook as vcodebook
 from . import flow as vflow
+from . import fusion
 
 # what the outputs sized for the proven bound may take when max_points is None
 MEMORY_BUDGET_BYTES = 8 << 30
@@ -97,3 +100,74 @@ def space_time_interest_points(gray, flow=None, params=None, flow_params=None, m
     if n > cap:
         raise ValueError("%s: found %d points, more than max_points = %d" % (who, n, cap))
     return {"desc": desc[:n], "points": points[:n], "response": response[:n], "count": n}
+
+
+class StipClassifier(object):
+    """Sheet01's ``main()`` after the extraction (Sheet01.py:259-277, 379-390): a k-means codebook of all training
+    descriptors, one histogram of words per video, a linear SVM on those.
+
+    ``descs_per_video``: a list of CUDA float32 ``[n_i, d]`` tensors, one per video
+    (``space_time_interest_points(...)["desc"]``); a video without points (``n_i = 0``) is legal and gets a zero histogram."""
+
+    def __init__(self):
+        self.codebook = self.coef = self.intercept = self.classes = None
+        self.norm = "l2"
+
+    @staticmethod
+    def _videos(descs_per_video, who):
+        if isinstance(descs_per_video, torch.Tensor) or not isinstance(descs_per_video, (list, tuple)) or len(descs_per_video) == 0:
+            raise ValueError("%s: descs_per_video must be a non-empty list of CUDA float32 [n_i, d] tensors" % who)
+        for v in descs_per_video:
+            if not isinstance(v, torch.Tensor) or not v.is_cuda or v.dtype != torch.float32 or v.dim() != 2:
+                raise ValueError("%s: descs_per_video must be a non-empty list of CUDA float32 [n_i, d] tensors" % who)
+        if len(set(int(v.shape[1]) for v in descs_per_video)) != 1:
+            raise ValueError("%s: descs_per_video must share one descriptor length" % who)
+        segments = np.concatenate([[0], np.cumsum([int(v.shape[0]) for v in descs_per_video])]).astype(np.int64)
+        return list(descs_per_video), segments
+
+    def fit(self, descs_per_video, labels, n_words=256, norm="l2", **kmeans_kw):
+        """``codebook.kmeans_fit`` with ``n_words`` clusters (Sheet01.py:262) and ``kmeans_kw``, histograms with ``norm``
+        (``"l2"``: Sheet01's ``normalize``), ``fusion.linear_svm_fit``.  -> self."""
+        who = "StipClassifier.fit"
+        videos, segments = self._videos(descs_per_video, who)
+        if len(labels) != len(videos):
+            raise ValueError("%s: %d videos but %d labels" % (who, len(videos), len(labels)))
+        if norm not in vcodebook.NORMS:
+            raise ValueError("%s: norm must be 'l2', 'l1' or 'none', got %r" % (who, norm))
+        rows = torch.cat(videos, 0)
+        self.codebook = vcodebook.kmeans_fit(rows, n_words, **kmeans_kw)
+        self.norm = norm
+        self.coef, self.intercept, self.classes = fusion.linear_svm_fit(self.codebook.histograms(rows, segments, norm), labels)
+        return self
+
+    def encode(self, descs_per_video):
+        """The histograms CUDA float32 ``[n_videos, n_words]`` of the fitted codebook, for callers who fuse them elsewhere."""
+        who = "StipClassifier.encode"
+        if self.codebook is None:
+            raise ValueError("%s: the model is not fitted" % who)
+        videos, segments = self._videos(descs_per_video, who)
+        return self.codebook.histograms(torch.cat(videos, 0), segments, self.norm)
+
+    def predict(self, descs_per_video):
+        """-> the predicted labels, one per video (``fusion.linear_svm_predict`` on the histograms)."""
+        if self.coef is None:
+            raise ValueError("StipClassifier.predict: the model is not fitted")
+        h = self.encode(descs_per_video)
+        return fusion.linear_svm_predict(h.double().cpu().numpy(), self.coef, self.intercept, self.classes, device=h.device.index)
+
+    def save(self, path):
+        if self.coef is None:
+            raise ValueError("StipClassifier.save: the model is not fitted")
+        cb = self.codebook
+        with open(path, "wb") as f:
+            np.savez(f, centres=cb.centres, inertia=np.float64(cb.inertia), n_iter=np.int64(cb.n_iter), converged=np.bool_(cb.converged),
+                     counts=cb.counts, norm=np.str_(self.norm), coef=self.coef, intercept=self.intercept, classes=self.classes)
+
+    @classmethod
+    def load(cls, path):
+        m = cls()
+        with np.load(path) as z:
+            m.codebook = vcodebook.Codebook(z["centres"], float(z["inertia"]), int(z["n_iter"]), bool(z["converged"]), z["counts"])
+            m.norm = str(z["norm"])
+            m.coef, m.intercept, m.classes = z["coef"], z["intercept"], z["classes"]
+        return m

@@ -227,6 +227,21 @@ def test_maxima_count_zero_and_count_above_the_capacity():
     assert _maxima(H, 1.0, 6)[2] == 0  # min_response is strict
 
 
+@pytest.mark.parametrize("shape", [(5, 204, 9), (4, 256, 9), (5, 205, 9), (8, 205, 9)], ids=str)
+def test_maxima_across_the_rounds_of_the_row_scan(shape):
+    """k_stip_scan scans the T h row counts 1024 at a time: 1020 rows (short of one round), 1024 (one full round), 1025 (one
+    row into a second round, a face row) and 1640, where points lie in rows of the second round and their offsets carry the
+    first round's total"""
+    T, h, w = shape
+    H = _volume(T, h, w, seed=11)
+    ref = so.maxima(H, 0.0, 6)
+    assert 100 < len(ref) < 4096
+    assert ((ref[:, 2] * h + ref[:, 1] >= 1024).sum() > 100) == (T * h > 1025)
+    pts, resp, n = _maxima(H, 0.0, 6, before=5)
+    assert n == len(ref) and np.array_equal(pts[:, :3], ref)
+    assert _same(resp, H[ref[:, 2], ref[:, 1], ref[:, 0]])
+
+
 # ---------------------------------------------------------------- votes and cuboids (S88-S89)
 
 def _votes(L, flow, p):

@@ -18,28 +18,22 @@ import torch
 
 from . import _ffi
 from . import fisher
+from ._features import check_rows, check_segments, dev64, workspace
 
 MAX_DIM, MAX_CLUSTERS, MAX_SEGMENTS = 512, 4096, 65536
 NORMS = {"none": _ffi.VA_BOW_NONE, "l1": _ffi.VA_BOW_L1, "l2": _ffi.VA_BOW_L2}
 
 
-def _check_rows(x, who, name="x"):
-    return fisher._check_rows(x, who, name, MAX_DIM)
-
-
 def _centres(centres, d, dev, who):
-    c = centres.to(device=dev, dtype=torch.float64).contiguous() if isinstance(centres, torch.Tensor) else fisher._dev64(centres, dev)
+    c = centres.to(device=dev, dtype=torch.float64).contiguous() if isinstance(centres, torch.Tensor) else dev64(centres, dev)
     if c.dim() != 2 or c.shape[1] != d or not 1 <= c.shape[0] <= MAX_CLUSTERS:
         raise ValueError("%s: centres must be [K, %d] with 1 <= K <= %d, got %s" % (who, d, MAX_CLUSTERS, tuple(c.shape)))
     return c
 
 
 def _workspace(n, d, k, n_segments, dev, params=None):
-    L = _ffi.lib()
-    need = L.va_kmeans_workspace_bytes(n, d, k, n_segments, None if params is None else ctypes.byref(params))
-    if need == 0:
-        raise ValueError(L.va_last_error().decode())
-    return torch.empty((need,), dtype=torch.uint8, device=dev), need
+    ws = workspace(_ffi.lib().va_kmeans_workspace_bytes(n, d, k, n_segments, None if params is None else ctypes.byref(params)), dev)
+    return ws, ws.numel()
 
 
 def _norm(norm, who):
@@ -54,7 +48,7 @@ def assign(x, centres, prev_labels=None, want_d2=True):
     centre of each row, its squared distance, their sum, and the rows whose label differs from ``prev_labels`` (all rows when
     that is None)."""
     who = "assign"
-    x = _check_rows(x, who)
+    x = check_rows(x, who, MAX_DIM)
     n, d, dev = int(x.shape[0]), int(x.shape[1]), x.device
     if n < 1:
         raise ValueError("%s: x holds no rows" % who)
@@ -80,7 +74,7 @@ def update(x, labels, centres, chunk_rows=None):
     centre is the mean of its rows, added in a fixed tree over the rows in ascending order; an empty cluster keeps its centre;
     ``shift2 = sum_j |new_j - old_j|^2``.  ``chunk_rows`` sizes the counting sort's chunks and reaches no result."""
     who = "update"
-    x = _check_rows(x, who)
+    x = check_rows(x, who, MAX_DIM)
     n, d, dev = int(x.shape[0]), int(x.shape[1]), x.device
     if n < 1:
         raise ValueError("%s: x holds no rows" % who)
@@ -105,7 +99,7 @@ def seed(x, n_clusters, u):
     m float64 [n])``, all CUDA: the chosen rows widened, their indices and each row's squared distance to the nearest of the
     centres chosen before the last."""
     who = "seed"
-    x = _check_rows(x, who)
+    x = check_rows(x, who, MAX_DIM)
     n, d, dev, k = int(x.shape[0]), int(x.shape[1]), x.device, int(n_clusters)
     if n < 1:
         raise ValueError("%s: x holds no rows" % who)
@@ -130,7 +124,7 @@ def bow_histograms(labels, segments, n_words, norm="l2"):
     if not isinstance(labels, torch.Tensor) or not labels.is_cuda or labels.dtype != torch.int32 or labels.dim() != 1:
         raise ValueError("%s: labels must be a CUDA int32 [n] tensor" % who)
     mode, n, dev, k = _norm(norm, who), int(labels.shape[0]), labels.device, int(n_words)
-    seg = fisher._check_segments(segments, n, who)
+    seg = check_segments(segments, n, who)
     ns = len(seg) - 1
     if not 1 <= k <= MAX_CLUSTERS or ns > MAX_SEGMENTS:
         raise ValueError("%s: need 1 <= n_words <= %d and at most %d segments, got %d and %d" % (who, MAX_CLUSTERS, MAX_SEGMENTS, k, ns))
@@ -147,11 +141,11 @@ def bow_histograms(labels, segments, n_words, norm="l2"):
 def bow_encode(x, segments, centres, norm="l2"):
     """``va_bow_encode``: assignment and histograms in one call; the labels live in the workspace and no ``d2`` exists."""
     who = "bow_encode"
-    x = _check_rows(x, who)
+    x = check_rows(x, who, MAX_DIM)
     mode, n, d, dev = _norm(norm, who), int(x.shape[0]), int(x.shape[1]), x.device
     c = _centres(centres, d, dev, who)
     k = int(c.shape[0])
-    seg = fisher._check_segments(segments, n, who)
+    seg = check_segments(segments, n, who)
     ns = len(seg) - 1
     if ns > MAX_SEGMENTS:
         raise ValueError("%s: at most %d segments, got %d" % (who, MAX_SEGMENTS, ns))
@@ -187,7 +181,7 @@ class Codebook(object):
 
     def assign(self, x):
         """-> the int32 CUDA labels of a CUDA float32 ``[n,d]`` tensor (an empty tensor gives an empty one)."""
-        x = _check_rows(x, "Codebook.assign")
+        x = check_rows(x, "Codebook.assign", MAX_DIM)
         if x.shape[1] != self.centres.shape[1]:
             raise ValueError("Codebook.assign: x has %d columns, the codebook %d" % (x.shape[1], self.centres.shape[1]))
         if x.shape[0] == 0:
@@ -198,7 +192,7 @@ class Codebook(object):
         """One histogram of words per segment (video): x CUDA float32 ``[n,d]``, ``segments [S + 1]`` ascending row offsets
         from 0 to n.  -> CUDA float32 ``[S, K]``: the counts divided by their L2 norm (``"l2"``, Sheet01's ``normalize``), their
         sum (``"l1"``) or nothing (``"none"``).  An empty segment gives zeros (Sheet01 would give NaN there)."""
-        x = _check_rows(x, "Codebook.histograms")
+        x = check_rows(x, "Codebook.histograms", MAX_DIM)
         if x.shape[1] != self.centres.shape[1]:
             raise ValueError("Codebook.histograms: x has %d columns, the codebook %d" % (x.shape[1], self.centres.shape[1]))
         return bow_encode(x, segments, self.centres, norm)
@@ -277,7 +271,7 @@ def _one_fit(x, k, init, max_iter, tol_scaled, seed_value):
         rows = np.random.RandomState(seed_value).permutation(n)[:k]
         centres = x[torch.as_tensor(rows, device=dev)].to(torch.float64)
     else:
-        centres = fisher._dev64(init.cpu().numpy() if isinstance(init, torch.Tensor) else init, dev)
+        centres = dev64(init.cpu().numpy() if isinstance(init, torch.Tensor) else init, dev)
     prev, n_iter, converged = None, 0, False
     for it in range(1, max_iter + 1):
         labels, _d2, _inertia, changed = assign(x, centres, prev, want_d2=False)
@@ -312,14 +306,14 @@ def kmeans_fit(x, n_clusters=256, *, init="k-means++", n_init=1, max_iter=300, t
     empties to the caller."""
     who = "kmeans_fit"
     if isinstance(x, (list, tuple)):
-        parts = [_check_rows(p, who) for p in x]
+        parts = [check_rows(p, who, MAX_DIM) for p in x]
         parts = [p for p in parts if p.shape[0] > 0]
         if not parts:
             raise ValueError("%s: x holds no rows" % who)
         if len(set((int(p.shape[1]), p.device) for p in parts)) != 1:
             raise ValueError("%s: x must share one width and one device" % who)
         x = torch.cat(parts, 0) if len(parts) > 1 else parts[0]
-    x = _check_rows(x, who)
+    x = check_rows(x, who, MAX_DIM)
     n, d = int(x.shape[0]), int(x.shape[1])
     check_kmeans_fit_args(n, d, n_clusters, init, n_init, max_iter, tol, seed)
     tol_scaled = tolerance(*fisher.pca_moments(x), tol=tol)

@@ -3,18 +3,15 @@
 // descriptors and the linear SVM.
 //
 // Everything is float64 (float32 inputs are widened exactly).  The products of the assignment run on v_mfma_f64_16x16x4_f64
-// with the operand layout of fisher.hip (one f64 of A and of B per lane: A[row lane&15][k lane>>4], B[k lane>>4][col lane&15];
-// four results per lane: col lane&15, row (lane>>4) + 4 reg).  Nothing of size n x K exists.  Every floating-point sum has a
-// fixed order that depends on the inputs and the parameters alone; the only atomics are integer ones (counts, the lowest and
-// the highest row index), whose results do not depend on their order: two calls give the same bits.
-#include "va_internal.h"
+// (operand layout: v4d in va_feature_device.h).  Nothing of size n x K exists.  Every floating-point sum has a fixed order that
+// depends on the inputs and the parameters alone; the only atomics are integer ones (counts, the lowest and the highest row
+// index), whose results do not depend on their order: two calls give the same bits.
+#include "va_feature_device.h"
 
 #include <climits>
 #include <cmath>
 
 namespace {
-
-typedef double v4d __attribute__((ext_vector_type(4)));
 
 constexpr int kKmMaxDim = 512, kKmMaxK = 4096, kKmMaxSegments = 65536;
 constexpr int kKmMinChunk = 64, kKmMaxChunk = 1 << 20, kKmMaxChunks = 65536;
@@ -24,18 +21,6 @@ constexpr int kTileLd = kTileD + 1;    // row stride in doubles: 130 dwords = 2 
 constexpr int kRowBlocks = 2;          // 16-row blocks per wave
 constexpr int kWgRows = 4 * 16 * kRowBlocks;
 constexpr int kSumBlock = 256;         // rows per block sum (inertia, seeding)
-
-// The sum of v over the 256 threads of a workgroup, the same bits in every thread: an xor butterfly over the lanes of each
-// wave (offsets 32, 16, ..., 1), then ((w0 + w1) + w2) + w3.
-__device__ __forceinline__ double wg_sum(double v, double* red)
-{
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v = v + __shfl_xor(v, off, 64);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return ((red[0] + red[1]) + red[2]) + red[3];
-}
 
 // sum_c (x[i][c] - ctr[c])^2 for the 256 rows of a workgroup, row r0 + thread: columns ascending, one rounding per operation.
 // The rows' floats pass through LDS 32 columns at a time (loaded along the rows, read down the thread's own row; the stride
@@ -182,7 +167,7 @@ __global__ void __launch_bounds__(256, 2) k_km_assign(const float* __restrict__ 
 }
 
 // d2[i] = sum_c (x[i][c] - centres[label_i][c])^2 (stored when d2 is given), the number of rows whose label differs from
-// prev's (every row when prev is NULL), and part[block] = the block's sum of d2 (wg_sum) for the inertia.
+// prev's (every row when prev is NULL), and part[block] = the block's sum of d2 (va_wg_sum256) for the inertia.
 __global__ void __launch_bounds__(256) k_km_d2(const float* __restrict__ x, int n, int d, const double* __restrict__ centres, int K,
                                                const int* __restrict__ labels, const int* __restrict__ prev, double* __restrict__ d2,
                                                double* __restrict__ part, unsigned long long* __restrict__ changed)
@@ -202,17 +187,17 @@ __global__ void __launch_bounds__(256) k_km_d2(const float* __restrict__ x, int 
     }
     const unsigned long long mv = __ballot(moved);
     if ((threadIdx.x & 63) == 0 && mv) atomicAdd(changed, (unsigned long long)__popcll(mv));
-    const double s = wg_sum(v, red);
+    const double s = va_wg_sum256(v, red);
     if (threadIdx.x == 0) part[blockIdx.x] = s;
 }
 
-// out[0] = the sum of part[0 .. count): thread t adds t, t + 256, ... in ascending order, then wg_sum
+// out[0] = the sum of part[0 .. count): thread t adds t, t + 256, ... in ascending order, then va_wg_sum256
 __global__ void __launch_bounds__(256) k_km_sum_parts(const double* __restrict__ part, long long count, double* __restrict__ out)
 {
     __shared__ double red[4];
     double v = 0.0;
     for (long long b = threadIdx.x; b < count; b += 256) v = v + part[b];
-    const double s = wg_sum(v, red);
+    const double s = va_wg_sum256(v, red);
     if (threadIdx.x == 0) out[0] = s;
 }
 
@@ -375,7 +360,7 @@ __global__ void __launch_bounds__(256) k_seed_init(int n, int K, double* __restr
     if (i < K) cand[i] = INT_MAX, last[i] = -1;
 }
 
-// m[i] = min(m[i], sum_c (x[i][c] - x[rows[j-1]][c])^2) and bs[block] = the block's sum of m (wg_sum; rows past n add 0)
+// m[i] = min(m[i], sum_c (x[i][c] - x[rows[j-1]][c])^2) and bs[block] = the block's sum of m (va_wg_sum256; rows past n add 0)
 __global__ void __launch_bounds__(256) k_seed_dist(const float* __restrict__ x, int n, int d, const int* __restrict__ rows, int j,
                                                    double* __restrict__ m, double* __restrict__ bs)
 {
@@ -389,7 +374,7 @@ __global__ void __launch_bounds__(256) k_seed_dist(const float* __restrict__ x, 
         v = acc < mo ? acc : mo;
         m[i] = v;
     }
-    const double s = wg_sum(v, red);
+    const double s = va_wg_sum256(v, red);
     if (threadIdx.x == 0) bs[blockIdx.x] = s;
 }
 
@@ -509,35 +494,21 @@ struct KmPlan {
     size_t bytes;
 };
 
-bool km_plan(const char* who, long long n, int d, int k, int n_segments, const va_kmeans_params* p, char* base, KmPlan* out)
+// The argument checks every entry point shares, and the workspace cut from `base` (NULL: the size alone)
+int km_plan(const char* who, long long n, int d, int k, int n_segments, const va_kmeans_params* p, void* base, KmPlan* out)
 {
     va_kmeans_params def;
     va_kmeans_default_params(&def);
     if (p == nullptr) p = &def;
-    if (p->struct_bytes < (int)sizeof(va_kmeans_params)) {
-        va_set_error("%s: struct_bytes %d is smaller than sizeof(va_kmeans_params) = %d", who, p->struct_bytes, (int)sizeof(va_kmeans_params));
-        return false;
-    }
-    if (n < 1 || n > INT_MAX) {
-        va_set_error("%s: n out of range: need 1 <= n <= %d (got %lld)", who, INT_MAX, n);
-        return false;
-    }
-    if (d < 1 || d > kKmMaxDim) {
-        va_set_error("%s: d out of range: need 1 <= d <= %d (got %d)", who, kKmMaxDim, d);
-        return false;
-    }
-    if (k < 1 || k > kKmMaxK) {
-        va_set_error("%s: k out of range: need 1 <= k <= %d (got %d)", who, kKmMaxK, k);
-        return false;
-    }
-    if (n_segments < 1 || n_segments > kKmMaxSegments) {
-        va_set_error("%s: n_segments out of range: need 1 <= n_segments <= %d (got %d)", who, kKmMaxSegments, n_segments);
-        return false;
-    }
-    if (p->chunk_rows < kKmMinChunk || p->chunk_rows > kKmMaxChunk) {
-        va_set_error("%s: chunk_rows out of range: need %d <= chunk_rows <= %d (got %d)", who, kKmMinChunk, kKmMaxChunk, p->chunk_rows);
-        return false;
-    }
+    VA_CHECK_ARG(p->struct_bytes >= (int)sizeof(va_kmeans_params), "%s: struct_bytes %d is smaller than sizeof(va_kmeans_params) = %d", who,
+                 p->struct_bytes, (int)sizeof(va_kmeans_params));
+    VA_CHECK_ARG(n >= 1 && n <= INT_MAX, "%s: n out of range: need 1 <= n <= %d (got %lld)", who, INT_MAX, n);
+    VA_CHECK_ARG(d >= 1 && d <= kKmMaxDim, "%s: d out of range: need 1 <= d <= %d (got %d)", who, kKmMaxDim, d);
+    VA_CHECK_ARG(k >= 1 && k <= kKmMaxK, "%s: k out of range: need 1 <= k <= %d (got %d)", who, kKmMaxK, k);
+    VA_CHECK_ARG(n_segments >= 1 && n_segments <= kKmMaxSegments, "%s: n_segments out of range: need 1 <= n_segments <= %d (got %d)", who,
+                 kKmMaxSegments, n_segments);
+    VA_CHECK_ARG(p->chunk_rows >= kKmMinChunk && p->chunk_rows <= kKmMaxChunk,
+                 "%s: chunk_rows out of range: need %d <= chunk_rows <= %d (got %d)", who, kKmMinChunk, kKmMaxChunk, p->chunk_rows);
     KmPlan g;
     long long cr = p->chunk_rows;
     const long long least = (n + kKmMaxChunks - 1) / kKmMaxChunks;  // never more than 65536 chunks: the sort is stable, so the
@@ -545,36 +516,29 @@ bool km_plan(const char* who, long long n, int d, int k, int n_segments, const v
     g.chunk_rows = (int)cr;
     g.chunks = (int)((n + cr - 1) / cr);
     g.blocks = (n + kSumBlock - 1) / kSumBlock;
-    size_t off = 0;
-    auto take = [&](size_t count, size_t elem) {
-        const uintptr_t at = (uintptr_t)base + off;
-        off += va_align_up(count * elem, 256);
-        return (void*)at;
-    };
-    g.hn = (double*)take((size_t)k, sizeof(double));
-    g.sq = (double*)take((size_t)k, sizeof(double));
-    g.part = (double*)take((size_t)g.blocks, sizeof(double));
-    g.pre = (double*)take((size_t)g.blocks, sizeof(double));
-    g.tt = (double*)take(2, sizeof(double));
-    g.labels = (int*)take((size_t)n, sizeof(int));
-    g.perm = (int*)take((size_t)n, sizeof(int));
-    g.hist = (int*)take((size_t)g.chunks * k, sizeof(int));
-    g.start = (int*)take((size_t)k + 1, sizeof(int));
-    g.cand = (int*)take((size_t)k, sizeof(int));
-    g.last = (int*)take((size_t)k, sizeof(int));
-    g.bytes = off;
+    va_carver ws{base};
+    g.hn = ws.take<double>((size_t)k);
+    g.sq = ws.take<double>((size_t)k);
+    g.part = ws.take<double>((size_t)g.blocks);
+    g.pre = ws.take<double>((size_t)g.blocks);
+    g.tt = ws.take<double>(2);
+    g.labels = ws.take<int>((size_t)n);
+    g.perm = ws.take<int>((size_t)n);
+    g.hist = ws.take<int>((size_t)g.chunks * k);
+    g.start = ws.take<int>((size_t)k + 1);
+    g.cand = ws.take<int>((size_t)k);
+    g.last = ws.take<int>((size_t)k);
+    g.bytes = ws.off;
     if (out) *out = g;
-    return true;
+    return VA_OK;
 }
 
+// the workspace's pointer, the plan and the workspace's size, in that order
 int km_ready(const char* who, int n, int d, int k, int n_segments, const va_kmeans_params* p, void* workspace, size_t workspace_bytes,
              KmPlan* g)
 {
-    if (workspace == nullptr || ((size_t)workspace & 255) != 0) {
-        va_set_error("%s: workspace must be a 256-byte aligned DEVICE pointer", who);
-        return VA_ERR_INVALID;
-    }
-    if (!km_plan(who, n, d, k, n_segments, p, (char*)workspace, g)) return VA_ERR_INVALID;
+    VA_CHECK_ARG(workspace != nullptr && ((size_t)workspace & 255) == 0, "%s: workspace must be a 256-byte aligned DEVICE pointer", who);
+    if (int rc = km_plan(who, n, d, k, n_segments, p, workspace, g)) return rc;
     if (workspace_bytes < g->bytes) {
         va_set_error("%s: workspace of %zu bytes, %zu needed", who, workspace_bytes, g->bytes);
         return VA_ERR_WORKSPACE;
@@ -605,7 +569,7 @@ extern "C" int va_kmeans_tile_centres(void) { return kTileK; }
 extern "C" size_t va_kmeans_workspace_bytes(int n, int d, int k, int n_segments, const va_kmeans_params* p)
 {
     KmPlan g;
-    if (!km_plan("va_kmeans_workspace_bytes", n, d, k, n_segments, p, nullptr, &g)) return 0;
+    if (km_plan("va_kmeans_workspace_bytes", n, d, k, n_segments, p, nullptr, &g) != VA_OK) return 0;
     return g.bytes;
 }
 
@@ -685,7 +649,7 @@ extern "C" int va_bow_histograms(va_ctx* ctx, const void* labels, int n, const v
     VA_USE_DEVICE(ctx);
     VA_CHECK_ARG(labels && segments && out, "va_bow_histograms: NULL pointer");
     VA_CHECK_ARG(bow_norm_ok(norm), "va_bow_histograms: norm must be VA_BOW_NONE, VA_BOW_L1 or VA_BOW_L2 (got %d)", norm);
-    if (!km_plan("va_bow_histograms", n, 1, k, n_segments, nullptr, nullptr, nullptr)) return VA_ERR_INVALID;
+    if (int rc = km_plan("va_bow_histograms", n, 1, k, n_segments, nullptr, nullptr, nullptr)) return rc;
     k_bow_hist<<<n_segments, 256, 0, (hipStream_t)stream>>>((const int*)labels, n, (const long long*)segments, k, norm, (float*)out);
     VA_LAUNCH_CHECK();
     return VA_OK;

@@ -13,7 +13,7 @@
 //             cells + c for its `length` steps: no allocation, and the table of cells * length slots cannot overflow (S76).
 //
 // Per frame the host makes the same launches whatever the counts are; kernels read the live count from the state.
-#include "va_internal.h"
+#include "va_feature_device.h"
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -72,12 +72,6 @@ __device__ __forceinline__ void sobel(const float* t, int RW, float& gx, float& 
     gy = ((bl - tl) + 2.0f * (bc - tc)) + (br - tr);
 }
 
-// S70-S71 with this file's 8 bins (va_internal.h holds the functions: stip.hip votes with them too)
-__device__ __forceinline__ void votes_of(float x, float y, float vmax, float scale, int& b0, unsigned& q0, unsigned& q1, float& m)
-{
-    va_votes_of(x, y, vmax, scale, 8, b0, q0, q1, m);
-}
-
 struct VoteArgs {
     const void* gray;   // frame f: [h][w] at gray + f * h * w elements
     const float* flow;  // [frame][2][h][w], unfiltered
@@ -86,15 +80,8 @@ struct VoteArgs {
     float min_flow;
 };
 
-__device__ __forceinline__ void store_bins(unsigned* o, size_t fl, int b0, unsigned q0, unsigned q1)
-{
-    const int b1 = (b0 + 1) & 7;
-#pragma unroll
-    for (int b = 0; b < 8; ++b) o[b * fl] = b == b0 ? q0 : (b == b1 ? q1 : 0u);
-}
-
-// S69-S71.  grid (tiles, frames); dynamic LDS: 3 (TW + 2)(TH + 2) floats.  Lanes run along x: every plane's stores of a wave
-// are one contiguous run.
+// S69-S71 with 8 bins in every group (va_votes_of, va_store_bins).  grid (tiles, frames); dynamic LDS: 3 (TW + 2)(TH + 2) floats.
+// Lanes run along x: every plane's stores of a wave are one contiguous run.
 __global__ void __launch_bounds__(kNT) k_dtraj_votes(VoteArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -128,19 +115,19 @@ __global__ void __launch_bounds__(kNT) k_dtraj_votes(VoteArgs a)
         int b0;
         unsigned q0, q1;
         sobel(G + c, RW, dx, dy);  // HOG
-        votes_of(dx, dy, kHogVmax, kHogScale, b0, q0, q1, m);
-        store_bins(o, fl, b0, q0, q1);
-        votes_of(U[c], V[c], kFlowVmax, kFlowScale, b0, q0, q1, m);  // HOF: the flow itself, and the bin of the still pixels
+        va_votes_of(dx, dy, kHogVmax, kHogScale, 8, b0, q0, q1, m);
+        va_store_bins(o, fl, 8, b0, q0, q1);
+        va_votes_of(U[c], V[c], kFlowVmax, kFlowScale, 8, b0, q0, q1, m);  // HOF: the flow itself, and the bin of the still pixels
         const bool still = m <= a.min_flow;
         if (still) q0 = 0u, q1 = 0u;
-        store_bins(o + 8 * fl, fl, b0, q0, q1);
+        va_store_bins(o + 8 * fl, fl, 8, b0, q0, q1);
         o[16 * fl] = still ? (unsigned)kFlowScale : 0u;
         sobel(U + c, RW, dx, dy);  // MBHx
-        votes_of(dx, dy, kFlowVmax, kFlowScale, b0, q0, q1, m);
-        store_bins(o + 17 * fl, fl, b0, q0, q1);
+        va_votes_of(dx, dy, kFlowVmax, kFlowScale, 8, b0, q0, q1, m);
+        va_store_bins(o + 17 * fl, fl, 8, b0, q0, q1);
         sobel(V + c, RW, dx, dy);  // MBHy
-        votes_of(dx, dy, kFlowVmax, kFlowScale, b0, q0, q1, m);
-        store_bins(o + 25 * fl, fl, b0, q0, q1);
+        va_votes_of(dx, dy, kFlowVmax, kFlowScale, 8, b0, q0, q1, m);
+        va_store_bins(o + 25 * fl, fl, 8, b0, q0, q1);
     }
 }
 
@@ -160,13 +147,7 @@ __global__ void __launch_bounds__(kNT) k_dtraj_scan_rows(const unsigned* __restr
     unsigned carry = 0u;
     for (int x0 = 0; x0 < w; x0 += 64) {
         const int x = x0 + lane;
-        unsigned v = x < w ? src[x] : 0u;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const unsigned t = __shfl_up(v, d);
-            if (lane >= d) v += t;
-        }
-        v += carry;
+        const unsigned v = va_wave_scan_incl(x < w ? src[x] : 0u, lane) + carry;
         if (x < w) dst[x + 1] = v;
         carry = __shfl(v, 63);
     }
@@ -246,34 +227,6 @@ __global__ void __launch_bounds__(kNT) k_dtraj_corner(const void* gray, int gray
     if (threadIdx.x == 0 && wgmax != 0u) atomicMax(maxbits + f, wgmax);
 }
 
-// exclusive scan of one int per thread over a workgroup of kScanNT; sh: kScanNT / 64 + 1 ints
-__device__ __forceinline__ int block_scan(int v, int* total, int* sh)
-{
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    int x = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int t = __shfl_up(x, d);
-        if (lane >= d) x += t;
-    }
-    if (lane == 63) sh[wv] = x;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int run = 0;
-        for (int i = 0; i < kScanNT / 64; ++i) {
-            const int t = sh[i];
-            sh[i] = run;
-            run += t;
-        }
-        sh[kScanNT / 64] = run;
-    }
-    __syncthreads();
-    const int r = sh[wv] + x - v;
-    *total = sh[kScanNT / 64];
-    __syncthreads();
-    return r;
-}
-
 // S74: nearest pixel of a position, inside the frame
 __device__ __forceinline__ int nearest(float p, int n) { return d_clampi((int)floorf(p + 0.5f), 0, n - 1); }
 
@@ -313,7 +266,7 @@ __global__ void __launch_bounds__(kScanNT) k_dtraj_sample(State s, Geo g, const 
             s.occ[c] = 0;
         }
         int total;
-        const int idx = n0 + run + block_scan(flag, &total, sh);
+        const int idx = n0 + run + va_wg_scan_excl<kScanNT>(flag, total, sh);
         if (flag && idx < g.slots) {  // (idx < slots always holds for a table this library built: S76)
             const int slot = base + c;
             live[idx] = slot;
@@ -428,8 +381,8 @@ __global__ void __launch_bounds__(kScanNT) k_dtraj_finish(State s, Geo g)
             }
         }
         int ta, to;
-        const int pa = block_scan(alive, &ta, sh);
-        const int po = block_scan(valid, &to, sh);
+        const int pa = va_wg_scan_excl<kScanNT>(alive, ta, sh);
+        const int po = va_wg_scan_excl<kScanNT>(valid, to, sh);
         if (alive) next[run_a + pa] = slot;
         if (valid) s.pend[run_o + po] = slot;
         run_a += ta, run_o += to;
@@ -562,12 +515,9 @@ int make_geo(Plan& P, const char* who, int w, int h, const va_dtraj_params* p)
     const size_t bytes[R_N] = {C_WORDS * sizeof(int), 2 * slots * sizeof(int), slots * sizeof(int), slots * sizeof(int),
                                slots * (g.L + 1) * 2 * sizeof(float), slots * g.accn * sizeof(unsigned long long),
                                (size_t)g.cells * sizeof(int), slots * sizeof(int)};
-    size_t off = 0;
-    for (int r = 0; r < R_N; ++r) {
-        P.off[r] = off;
-        off += va_align_up(bytes[r], 256);
-    }
-    P.state_bytes = off;
+    va_carver st{nullptr};
+    for (int r = 0; r < R_N; ++r) P.off[r] = (size_t)st.take<char>(bytes[r]);
+    P.state_bytes = st.off;
     return VA_OK;
 }
 
@@ -579,16 +529,12 @@ int make_plan(Plan& P, const char* who, int w, int h, int n_frames, int capacity
     VA_CHECK_ARG((long long)capacity * P.g.dim <= (1LL << 40), "%s: capacity %d is too large", who, capacity);
     P.chunk = P.chunk < n_frames - 1 ? P.chunk : n_frames - 1;
     const size_t fl = (size_t)w * h, il = (size_t)(w + 1) * (h + 1);
-    size_t off = P.state_bytes;
-    P.off_votes = off;
-    off += va_align_up((size_t)P.chunk * kPlanes * fl * sizeof(unsigned), 256);
-    P.off_integral = off;
-    off += va_align_up((size_t)P.chunk * kPlanes * il * sizeof(unsigned), 256);
-    P.off_resp = off;
-    off += va_align_up((size_t)P.chunk * fl * sizeof(float), 256);
-    P.off_max = off;
-    off += va_align_up((size_t)P.chunk * sizeof(unsigned), 256);
-    P.total = off;
+    va_carver ws{nullptr, P.state_bytes};  // the state first, then the chunk's buffers
+    P.off_votes = (size_t)ws.take<unsigned>((size_t)P.chunk * kPlanes * fl);
+    P.off_integral = (size_t)ws.take<unsigned>((size_t)P.chunk * kPlanes * il);
+    P.off_resp = (size_t)ws.take<float>((size_t)P.chunk * fl);
+    P.off_max = (size_t)ws.take<unsigned>((size_t)P.chunk);
+    P.total = ws.off;
     return VA_OK;
 }
 
@@ -621,7 +567,10 @@ int launch_votes(const Plan& P, const void* gray, int gray_u8, const float* flow
     return VA_OK;
 }
 
-int launch_integral(const unsigned* votes, unsigned* out, long long planes, int w, int h, hipStream_t st)
+}  // namespace
+
+// S72, both passes (va_internal.h: va_stip_extract sums its votes with it too)
+int va_integral_planes(const unsigned* votes, unsigned* out, long long planes, int w, int h, hipStream_t st)
 {
     const long long rows = planes * h, cols = planes * (w + 1);
     const long long gr = (rows + kNT / 64 - 1) / (kNT / 64), gc = (cols + kNT - 1) / kNT;
@@ -632,6 +581,8 @@ int launch_integral(const unsigned* votes, unsigned* out, long long planes, int 
     VA_LAUNCH_CHECK();
     return VA_OK;
 }
+
+namespace {
 
 int launch_corner(const void* gray, int gray_u8, float* resp, unsigned* maxbits, int n, int w, int h, hipStream_t st)
 {
@@ -743,7 +694,7 @@ extern "C" int va_dtraj_extract(va_ctx* ctx, const void* gray, int gray_is_u8, c
         const int nc = std::min(P.chunk, n_frames - 1 - t0);
         const char* gr = (const char*)gray + (size_t)t0 * fl * gbytes;
         if (int rc = launch_votes(P, gr, gray_is_u8, (const float*)flow + (size_t)t0 * 2 * fl, votes, nc, st)) return rc;
-        if (int rc = launch_integral(votes, integral, (long long)nc * kPlanes, w, h, st)) return rc;
+        if (int rc = va_integral_planes(votes, integral, (long long)nc * kPlanes, w, h, st)) return rc;
         const int ns = std::min(nc, last_start - t0 + 1);
         if (ns > 0)
             if (int rc = launch_corner(gr, gray_is_u8, resp, maxbits, ns, w, h, st)) return rc;
@@ -781,7 +732,7 @@ extern "C" int va_dtraj_integral(va_ctx* ctx, const void* votes, int planes, int
     VA_USE_DEVICE(ctx);
     VA_CHECK_ARG(planes >= 1 && w >= 1 && h >= 1 && w <= 16384 && h <= 16384, "va_dtraj_integral: planes >= 1 and w, h in [1,16384], got %d, %d x %d",
                  planes, w, h);
-    return launch_integral((const unsigned*)votes, (unsigned*)integral, planes, w, h, (hipStream_t)stream);
+    return va_integral_planes((const unsigned*)votes, (unsigned*)integral, planes, w, h, (hipStream_t)stream);
 }
 
 extern "C" int va_dtraj_corner(va_ctx* ctx, const void* gray, int gray_is_u8, int n, int w, int h, void* response, void* max_bits,

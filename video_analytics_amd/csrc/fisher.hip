@@ -2,34 +2,20 @@
 // Gaussian mixture (the E-step of fitting it and the first half of encoding with it), its M-step and the Fisher vector
 // epilogue -- the modelled project's Sheet02.py:568-617 between the trajectory descriptors and the linear SVM.
 //
-// Everything is float64 (float32 inputs are widened exactly).  The dense products run on v_mfma_f64_16x16x4_f64 with the
-// operand layout of svm.hip (one f64 of A and of B per lane: A[row lane&15][k lane>>4], B[k lane>>4][col lane&15]; four results
-// per lane: col lane&15, row (lane>>4) + 4 reg).  Every sum has a fixed order that depends on the inputs and the parameters
-// alone, and there are no atomics: two calls give the same bits.
-#include "va_internal.h"
+// Everything is float64 (float32 inputs are widened exactly).  The dense products run on v_mfma_f64_16x16x4_f64 (operand
+// layout: v4d in va_feature_device.h).  Every sum has a fixed order that depends on the inputs and the parameters alone, and
+// there are no atomics: two calls give the same bits.
+#include "va_feature_device.h"
 
 #include <cfloat>
 #include <cmath>
 
 namespace {
 
-typedef double v4d __attribute__((ext_vector_type(4)));
-
 constexpr int kPcaMaxDim = 2048, kPcaMinChunkRows = 256;
 constexpr int kGmmMaxDim = 512, kGmmMaxComp = 256, kGmmMaxSegments = 65536;
 constexpr int kGmmMinChunk = 16, kGmmMaxChunk = 65536, kGmmMaxBatch = 65536;
 constexpr double kFisherEpsilon = 1e-6;  // Sheet02.py:39
-
-// The sum of v over the 256 threads of a workgroup, the same bits in every thread (svm.hip's block_sum).
-__device__ __forceinline__ double wg_sum(double v, double* red)
-{
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v = v + __shfl_xor(v, off, 64);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return ((red[0] + red[1]) + red[2]) + red[3];
-}
 
 // ---- S77 PCA ----------------------------------------------------------------------------------------------------------
 
@@ -452,40 +438,24 @@ struct GmmPlan {
     size_t bytes;
 };
 
-bool gmm_plan(const char* who, int n, int d, int k, int n_segments, const va_gmm_params* p, char* base, GmmPlan* out)
+// The argument checks every mixture entry point shares, and the workspace cut from `base` (NULL: the size alone)
+int gmm_plan(const char* who, int n, int d, int k, int n_segments, const va_gmm_params* p, void* base, GmmPlan* out)
 {
     va_gmm_params def;
     va_gmm_default_params(&def);
     if (p == nullptr) p = &def;
-    if (p->struct_bytes < (int)sizeof(va_gmm_params)) {
-        va_set_error("%s: struct_bytes %d is smaller than sizeof(va_gmm_params) = %d", who, p->struct_bytes, (int)sizeof(va_gmm_params));
-        return false;
-    }
-    if (n < 1) {
-        va_set_error("%s: n out of range: need n >= 1 (got %d)", who, n);
-        return false;
-    }
-    if (d < 1 || d > kGmmMaxDim) {
-        va_set_error("%s: d out of range: need 1 <= d <= %d (got %d)", who, kGmmMaxDim, d);
-        return false;
-    }
-    if (k < 1 || k > kGmmMaxComp) {
-        va_set_error("%s: k out of range: need 1 <= k <= %d (got %d)", who, kGmmMaxComp, k);
-        return false;
-    }
-    if (n_segments < 1 || n_segments > kGmmMaxSegments) {
-        va_set_error("%s: n_segments out of range: need 1 <= n_segments <= %d (got %d)", who, kGmmMaxSegments, n_segments);
-        return false;
-    }
-    if (p->chunk_rows < kGmmMinChunk || p->chunk_rows > kGmmMaxChunk) {
-        va_set_error("%s: chunk_rows out of range: need %d <= chunk_rows <= %d (got %d)", who, kGmmMinChunk, kGmmMaxChunk, p->chunk_rows);
-        return false;
-    }
-    if (p->batch_rows < p->chunk_rows || p->batch_rows > kGmmMaxBatch) {
-        va_set_error("%s: batch_rows out of range: need chunk_rows <= batch_rows <= %d (got %d, chunk_rows %d)", who, kGmmMaxBatch,
-                     p->batch_rows, p->chunk_rows);
-        return false;
-    }
+    VA_CHECK_ARG(p->struct_bytes >= (int)sizeof(va_gmm_params), "%s: struct_bytes %d is smaller than sizeof(va_gmm_params) = %d", who,
+                 p->struct_bytes, (int)sizeof(va_gmm_params));
+    VA_CHECK_ARG(n >= 1, "%s: n out of range: need n >= 1 (got %d)", who, n);
+    VA_CHECK_ARG(d >= 1 && d <= kGmmMaxDim, "%s: d out of range: need 1 <= d <= %d (got %d)", who, kGmmMaxDim, d);
+    VA_CHECK_ARG(k >= 1 && k <= kGmmMaxComp, "%s: k out of range: need 1 <= k <= %d (got %d)", who, kGmmMaxComp, k);
+    VA_CHECK_ARG(n_segments >= 1 && n_segments <= kGmmMaxSegments, "%s: n_segments out of range: need 1 <= n_segments <= %d (got %d)", who,
+                 kGmmMaxSegments, n_segments);
+    VA_CHECK_ARG(p->chunk_rows >= kGmmMinChunk && p->chunk_rows <= kGmmMaxChunk,
+                 "%s: chunk_rows out of range: need %d <= chunk_rows <= %d (got %d)", who, kGmmMinChunk, kGmmMaxChunk, p->chunk_rows);
+    VA_CHECK_ARG(p->batch_rows >= p->chunk_rows && p->batch_rows <= kGmmMaxBatch,
+                 "%s: batch_rows out of range: need chunk_rows <= batch_rows <= %d (got %d, chunk_rows %d)", who, kGmmMaxBatch, p->batch_rows,
+                 p->chunk_rows);
     GmmPlan g;
     g.d = d, g.k = k, g.n_segments = n_segments;
     g.nt = k <= 16 ? 1 : (k <= 64 ? 4 : 16);
@@ -496,22 +466,30 @@ bool gmm_plan(const char* who, int n, int d, int k, int n_segments, const va_gmm
     g.chunks_per_batch = p->batch_rows / p->chunk_rows;
     g.batch_rows = g.chunks_per_batch * g.chunk_rows;
     g.slots = g.chunks_per_batch + n_segments;
-    size_t off = 0;
-    auto take = [&](size_t count, size_t elem) {
-        const uintptr_t at = (uintptr_t)base + off;
-        off += va_align_up(count * elem, 256);
-        return (void*)at;
-    };
-    g.Bm = (double*)take((size_t)g.kpad * g.DD, sizeof(double));
-    g.ck = (double*)take((size_t)g.kpad, sizeof(double));
-    g.G = (double*)take((size_t)g.batch_rows * g.kpad, sizeof(double));
-    g.rowlse = (double*)take((size_t)g.batch_rows, sizeof(double));
-    g.part = (double*)take((size_t)g.slots * k * g.C, sizeof(double));
-    g.pll = (double*)take((size_t)g.slots, sizeof(double));
-    g.pseg = (int*)take((size_t)g.slots, sizeof(int));
-    g.bytes = off;
-    if (out) *out = g;
-    return true;
+    va_carver ws{base};
+    g.Bm = ws.take<double>((size_t)g.kpad * g.DD);
+    g.ck = ws.take<double>((size_t)g.kpad);
+    g.G = ws.take<double>((size_t)g.batch_rows * g.kpad);
+    g.rowlse = ws.take<double>((size_t)g.batch_rows);
+    g.part = ws.take<double>((size_t)g.slots * k * g.C);
+    g.pll = ws.take<double>((size_t)g.slots);
+    g.pseg = ws.take<int>((size_t)g.slots);
+    g.bytes = ws.off;
+    *out = g;
+    return VA_OK;
+}
+
+// the workspace's alignment, the plan and the workspace's size, in that order
+int gmm_ready(const char* who, int n, int d, int k, int n_segments, const va_gmm_params* p, void* workspace, size_t workspace_bytes,
+              GmmPlan* g)
+{
+    VA_CHECK_ARG(((size_t)workspace & 255) == 0, "%s: workspace must be 256-byte aligned", who);
+    if (int rc = gmm_plan(who, n, d, k, n_segments, p, workspace, g)) return rc;
+    if (workspace_bytes < g->bytes) {
+        va_set_error("%s: workspace of %zu bytes, %zu needed", who, workspace_bytes, g->bytes);
+        return VA_ERR_WORKSPACE;
+    }
+    return VA_OK;
 }
 
 void gmm_launch_resp(const GmmPlan& g, const float* x, long long r0, int rows, int hard, double* G, int ldg, int ncols, double* rowlse,
@@ -537,7 +515,7 @@ extern "C" void va_gmm_default_params(va_gmm_params* p)
 extern "C" size_t va_gmm_workspace_bytes(int n, int d, int k, int n_segments, const va_gmm_params* p)
 {
     GmmPlan g;
-    if (!gmm_plan("va_gmm_workspace_bytes", n, d, k, n_segments, p, nullptr, &g)) return 0;
+    if (gmm_plan("va_gmm_workspace_bytes", n, d, k, n_segments, p, nullptr, &g) != VA_OK) return 0;
     return g.bytes;
 }
 
@@ -549,13 +527,8 @@ extern "C" int va_gmm_stats(va_ctx* ctx, const void* x, int n, int d, const void
     VA_USE_DEVICE(ctx);
     VA_CHECK_ARG(x && segments && weights && means && variances && stats && loglik && workspace, "va_gmm_stats: NULL pointer");
     VA_CHECK_ARG(mode == VA_GMM_SOFT || mode == VA_GMM_HARD, "va_gmm_stats: mode must be VA_GMM_SOFT or VA_GMM_HARD (got %d)", mode);
-    VA_CHECK_ARG(((size_t)workspace & 255) == 0, "va_gmm_stats: workspace must be 256-byte aligned");
     GmmPlan g;
-    if (!gmm_plan("va_gmm_stats", n, d, k, n_segments, p, (char*)workspace, &g)) return VA_ERR_INVALID;
-    if (workspace_bytes < g.bytes) {
-        va_set_error("va_gmm_stats: workspace of %zu bytes, %zu needed", workspace_bytes, g.bytes);
-        return VA_ERR_WORKSPACE;
-    }
+    if (int rc = gmm_ready("va_gmm_stats", n, d, k, n_segments, p, workspace, workspace_bytes, &g)) return rc;
     hipStream_t st = (hipStream_t)stream;
     const int kc = k * g.C;
     VA_HIP(hipMemsetAsync(stats, 0, (size_t)n_segments * kc * sizeof(double), st));
@@ -588,13 +561,8 @@ extern "C" int va_gmm_posteriors(va_ctx* ctx, const void* x, int n, int d, const
     VA_CHECK_ARG(x && weights && means && variances && gamma && lse && workspace, "va_gmm_posteriors: NULL pointer");
     VA_CHECK_ARG(mode == VA_GMM_SOFT || mode == VA_GMM_HARD, "va_gmm_posteriors: mode must be VA_GMM_SOFT or VA_GMM_HARD (got %d)", mode);
     VA_CHECK_ARG(n <= kGmmMaxBatch, "va_gmm_posteriors: n out of range: need n <= %d (got %d)", kGmmMaxBatch, n);
-    VA_CHECK_ARG(((size_t)workspace & 255) == 0, "va_gmm_posteriors: workspace must be 256-byte aligned");
     GmmPlan g;
-    if (!gmm_plan("va_gmm_posteriors", n, d, k, 1, nullptr, (char*)workspace, &g)) return VA_ERR_INVALID;
-    if (workspace_bytes < g.bytes) {
-        va_set_error("va_gmm_posteriors: workspace of %zu bytes, %zu needed", workspace_bytes, g.bytes);
-        return VA_ERR_WORKSPACE;
-    }
+    if (int rc = gmm_ready("va_gmm_posteriors", n, d, k, 1, nullptr, workspace, workspace_bytes, &g)) return rc;
     hipStream_t st = (hipStream_t)stream;
     k_gmm_prep<<<g.kpad, 256, 0, st>>>((const double*)weights, (const double*)means, (const double*)variances, k, d, g.DD, g.Bm, g.ck);
     gmm_launch_resp(g, (const float*)x, 0, n, mode == VA_GMM_HARD, (double*)gamma, k, k, (double*)lse, st);
@@ -606,13 +574,6 @@ extern "C" int va_gmm_posteriors(va_ctx* ctx, const void* x, int n, int d, const
 
 namespace {
 
-__device__ __forceinline__ double seg_sum(const double* __restrict__ stats, int n_segments, size_t stride, size_t at)
-{
-    double acc = stats[at];
-    for (int s = 1; s < n_segments; ++s) acc = acc + stats[(size_t)s * stride + at];
-    return acc;
-}
-
 __global__ void __launch_bounds__(256) k_gmm_mstep(const double* __restrict__ stats, int n_segments, int k, int d, double reg,
                                                    double* __restrict__ w, double* __restrict__ mu, double* __restrict__ var)
 {
@@ -620,7 +581,7 @@ __global__ void __launch_bounds__(256) k_gmm_mstep(const double* __restrict__ st
     __shared__ double total;
     const int C = 1 + 2 * d;
     const size_t stride = (size_t)k * C;
-    for (int j = threadIdx.x; j < k; j += 256) nk[j] = seg_sum(stats, n_segments, stride, (size_t)j * C) + 10.0 * DBL_EPSILON;
+    for (int j = threadIdx.x; j < k; j += 256) nk[j] = va_strided_sum(stats, n_segments, stride, (size_t)j * C) + 10.0 * DBL_EPSILON;
     __syncthreads();
     if (threadIdx.x == 0) {
         double t = 0.0;
@@ -631,8 +592,8 @@ __global__ void __launch_bounds__(256) k_gmm_mstep(const double* __restrict__ st
     for (int j = threadIdx.x; j < k; j += 256) w[j] = nk[j] / total;
     for (int e = threadIdx.x; e < k * d; e += 256) {
         const int j = e / d, c = e % d;
-        const double s1 = seg_sum(stats, n_segments, stride, (size_t)j * C + 1 + c);
-        const double s2 = seg_sum(stats, n_segments, stride, (size_t)j * C + 1 + d + c);
+        const double s1 = va_strided_sum(stats, n_segments, stride, (size_t)j * C + 1 + c);
+        const double s2 = va_strided_sum(stats, n_segments, stride, (size_t)j * C + 1 + d + c);
         const double m = s1 / nk[j];
         mu[e] = m;
         var[e] = ((s2 / nk[j] - 2.0 * (m * s1 / nk[j])) + m * m) + reg;
@@ -677,7 +638,7 @@ __global__ void __launch_bounds__(256) k_fisher_encode(const double* __restrict_
         const double v = fisher_value(st, e, k, d, (double)T, w, mu, var, power);
         ss = ss + v * v;
     }
-    const double norm = sqrt(wg_sum(ss, red));
+    const double norm = sqrt(va_wg_sum256(ss, red));
     for (int e = threadIdx.x; e < L; e += 256) {
         const double v = fisher_value(st, e, k, d, (double)T, w, mu, var, power);
         o[e] = (float)(norm < kFisherEpsilon ? v : v / norm);

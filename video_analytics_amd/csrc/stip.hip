@@ -3,15 +3,15 @@
 // I. Laptev, "On space-time interest points" (IJCV 2005), with the constants of the modelled project's Sheet01 and HOG / HOF
 // cuboid descriptors.  DESIGN.md S83-S90 fix every expression and its operation order.  The smoothing passes are float32 in
 // one written order per output (centre first, then the tap pairs outwards), so a result never depends on a tile shape; the
-// orientation votes are S70's polynomial quantised once to fixed point (S71's functions, va_internal.h), and every sum
+// orientation votes are S70's polynomial quantised once to fixed point (S71's functions, va_feature_device.h), and every sum
 // behind them is an integer sum.  This file is compiled with -ffp-contract=off and writes no fmaf of its own.
 //
 //   volumes   f32 [T][h][w]: L, the six products (smoothed in place), two pass buffers, H
-//   votes     u32 [T][bins][h][w], integral planes u32 [T][bins][h+1][w+1] (va_dtraj_integral: S72)
+//   votes     u32 [T][bins][h][w], integral planes u32 [T][bins][h+1][w+1] (va_integral_planes: S72)
 //   counts    i32 [16]: [0] points found so far, [1] the count before the current scale pair
 //
 // The host makes the same launches whatever the counts are; kernels read the counts from the device.
-#include "va_internal.h"
+#include "va_feature_device.h"
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -191,34 +191,15 @@ __global__ void __launch_bounds__(kNT) k_stip_count(MaxArgs a, int* __restrict__
 __global__ void __launch_bounds__(kScanNT) k_stip_scan(const int* __restrict__ rowcnt, int* __restrict__ rowoff, long long rows, int* counts)
 {
     __shared__ int sh[kScanNT / 64 + 1];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int base = counts[C_FOUND];
     int run = 0;
     __syncthreads();
     for (long long r0 = 0; r0 < rows; r0 += kScanNT) {
         const long long r = r0 + threadIdx.x;
-        const int v = r < rows ? rowcnt[r] : 0;
-        int x = v;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const int t = __shfl_up(x, d);
-            if (lane >= d) x += t;
-        }
-        if (lane == 63) sh[wv] = x;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            int s = 0;
-            for (int i = 0; i < kScanNT / 64; ++i) {
-                const int t = sh[i];
-                sh[i] = s;
-                s += t;
-            }
-            sh[kScanNT / 64] = s;
-        }
-        __syncthreads();
-        if (r < rows) rowoff[r] = base + run + sh[wv] + x - v;
-        run += sh[kScanNT / 64];
-        __syncthreads();
+        int total;
+        const int before = va_wg_scan_excl<kScanNT>(r < rows ? rowcnt[r] : 0, total, sh);
+        if (r < rows) rowoff[r] = base + run + before;
+        run += total;
     }
     if (threadIdx.x == 0) {
         counts[C_BEGIN] = base;
@@ -249,12 +230,6 @@ __global__ void __launch_bounds__(kNT) k_stip_write(MaxArgs a, const int* __rest
     }
 }
 
-__device__ __forceinline__ void store_bins(unsigned* o, size_t fl, int bins, int b0, unsigned q0, unsigned q1)
-{
-    const int b1 = b0 + 1 == bins ? 0 : b0 + 1;
-    for (int b = 0; b < bins; ++b) o[b * fl] = b == b0 ? q0 : (b == b1 ? q1 : 0u);
-}
-
 // S88: the votes of (Lx, Ly) of this scale's L -> u32 [T][bins][h][w]
 __global__ void __launch_bounds__(kNT) k_stip_votes_hog(const float* __restrict__ L, unsigned* __restrict__ out, int T, int h, int w, int bins, size_t vox)
 {
@@ -269,7 +244,7 @@ __global__ void __launch_bounds__(kNT) k_stip_votes_hog(const float* __restrict_
     unsigned q0, q1;
     float m;
     va_votes_of(lx, ly, kHogVmax, kHogScale, bins, b0, q0, q1, m);
-    store_bins(out + (size_t)t * bins * fl + rem, fl, bins, b0, q0, q1);
+    va_store_bins(out + (size_t)t * bins * fl + rem, fl, bins, b0, q0, q1);
 }
 
 // S88: the votes of the flow; frame t reads the field of pair min(t, T - 2)
@@ -286,7 +261,7 @@ __global__ void __launch_bounds__(kNT) k_stip_votes_hof(const float* __restrict_
     unsigned q0, q1;
     float m;
     va_votes_of(u[0], u[fl], kFlowVmax, kFlowScale, bins, b0, q0, q1, m);
-    store_bins(out + (size_t)t * bins * fl + rem, fl, bins, b0, q0, q1);
+    va_store_bins(out + (size_t)t * bins * fl + rem, fl, bins, b0, q0, q1);
 }
 
 struct DescArgs {
@@ -564,11 +539,14 @@ int launch_describe(const va_stip_params* p, const int* points, const int* count
 
 struct Plan {
     Tune tu;
-    size_t vox, votes_bytes, integral_bytes;
-    size_t off_taps, off_counts, off_rows, off_L, off_P, off_A, off_B, off_H, off_votes, off_hogI, off_hofI, total;
+    size_t vox, total;
+    float *taps, *L, *Pr, *A, *B, *H;
+    int *counts, *rows;
+    unsigned *votes, *hogI, *hofI;
 };
 
-int make_plan(Plan& P, const char* who, int w, int h, int T, int capacity, const va_stip_params* p)
+// the argument checks, and the workspace cut from `base` (NULL: the size alone)
+int make_plan(Plan& P, const char* who, int w, int h, int T, int capacity, const va_stip_params* p, void* base)
 {
     if (int rc = check_params(who, p, &P.tu)) return rc;
     if (int rc = check_volume(who, T, w, h, 2)) return rc;
@@ -577,23 +555,21 @@ int make_plan(Plan& P, const char* who, int w, int h, int T, int capacity, const
     VA_CHECK_ARG(bound <= 0x7fffffffLL, "%s: %d scale pairs of a %d x %d x %d volume could yield 2^31 points or more", who, p->n_sigmas * p->n_taus, T,
                  h, w);
     P.vox = (size_t)T * h * w;
-    P.votes_bytes = P.vox * p->bins * sizeof(unsigned);
-    P.integral_bytes = (size_t)T * p->bins * (h + 1) * (w + 1) * sizeof(unsigned);
     VA_CHECK_ARG((long long)T * p->bins <= 0x7fffffffLL / 4, "%s: too many vote planes", who);
-    const size_t vb = va_align_up(P.vox * sizeof(float), 256);
-    size_t off = 0;
-    P.off_taps = off, off += va_align_up((size_t)(VA_STIP_MAX_SIGMAS + VA_STIP_MAX_TAUS) * 2 * kTapStride * sizeof(float), 256);
-    P.off_counts = off, off += va_align_up(C_WORDS * sizeof(int), 256);
-    P.off_rows = off, off += va_align_up((2 * va_align_up((size_t)T * h, 64)) * sizeof(int), 256);
-    P.off_L = off, off += vb;
-    P.off_P = off, off += va_align_up(6 * P.vox * sizeof(float), 256);
-    P.off_A = off, off += vb;
-    P.off_B = off, off += vb;
-    P.off_H = off, off += vb;
-    P.off_votes = off, off += va_align_up(P.votes_bytes, 256);
-    P.off_hogI = off, off += va_align_up(P.integral_bytes, 256);
-    P.off_hofI = off, off += va_align_up(P.integral_bytes, 256);
-    P.total = off;
+    const size_t integral = (size_t)T * p->bins * (h + 1) * (w + 1);
+    va_carver ws{base};
+    P.taps = ws.take<float>((size_t)(VA_STIP_MAX_SIGMAS + VA_STIP_MAX_TAUS) * 2 * kTapStride);
+    P.counts = ws.take<int>(C_WORDS);
+    P.rows = ws.take<int>(2 * va_align_up((size_t)T * h, 64));
+    P.L = ws.take<float>(P.vox);
+    P.Pr = ws.take<float>(6 * P.vox);
+    P.A = ws.take<float>(P.vox);
+    P.B = ws.take<float>(P.vox);
+    P.H = ws.take<float>(P.vox);
+    P.votes = ws.take<unsigned>(P.vox * p->bins);
+    P.hogI = ws.take<unsigned>(integral);
+    P.hofI = ws.take<unsigned>(integral);
+    P.total = ws.off;
     return VA_OK;
 }
 
@@ -620,7 +596,7 @@ extern "C" void va_stip_default_params(va_stip_params* p)
 extern "C" size_t va_stip_workspace_bytes(int w, int h, int n_frames, int capacity, const va_stip_params* p)
 {
     Plan P;
-    if (make_plan(P, "va_stip_workspace_bytes", w, h, n_frames, capacity, p) != VA_OK) return 0;
+    if (make_plan(P, "va_stip_workspace_bytes", w, h, n_frames, capacity, p, nullptr) != VA_OK) return 0;
     return P.total;
 }
 
@@ -644,25 +620,13 @@ extern "C" int va_stip_extract(va_ctx* ctx, const void* gray, int gray_is_u8, co
                  "%s: NULL buffer", who);
     VA_USE_DEVICE(ctx);
     Plan P;
-    if (int rc = make_plan(P, who, w, h, n_frames, capacity, p)) return rc;
+    if (int rc = make_plan(P, who, w, h, n_frames, capacity, p, workspace)) return rc;
     VA_CHECK_ARG(((size_t)workspace & 255) == 0, "%s: workspace must be 256-byte aligned", who);
     if (workspace_bytes < P.total) {
         va_set_error("%s: workspace of %zu bytes, need %zu", who, workspace_bytes, P.total);
         return VA_ERR_WORKSPACE;
     }
     hipStream_t st = (hipStream_t)stream;
-    char* ws = (char*)workspace;
-    float* taps = (float*)(ws + P.off_taps);
-    int* counts = (int*)(ws + P.off_counts);
-    int* rows = (int*)(ws + P.off_rows);
-    float* L = (float*)(ws + P.off_L);
-    float* Pr = (float*)(ws + P.off_P);
-    float* A = (float*)(ws + P.off_A);
-    float* B = (float*)(ws + P.off_B);
-    float* H = (float*)(ws + P.off_H);
-    unsigned* votes = (unsigned*)(ws + P.off_votes);
-    unsigned* hogI = (unsigned*)(ws + P.off_hogI);
-    unsigned* hofI = (unsigned*)(ws + P.off_hofI);
     const int T = n_frames;
     // tap sets: sigma i at slot 2i, its integration scale at 2i + 1; the taus behind them likewise
     const int nsets = 2 * (VA_STIP_MAX_SIGMAS + VA_STIP_MAX_TAUS);
@@ -677,32 +641,33 @@ extern "C" int va_stip_extract(va_ctx* ctx, const void* gray, int gray_is_u8, co
         make_taps((double)p->taus[j], &radius[s], &host[(size_t)s * kTapStride]);
         make_taps((double)p->integration * (double)p->taus[j], &radius[s + 1], &host[(size_t)(s + 1) * kTapStride]);
     }
-    VA_HIP(hipMemcpyAsync(taps, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice, st));
+    VA_HIP(hipMemcpyAsync(P.taps, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice, st));
     VA_HIP(hipStreamSynchronize(st));  // `host` may go once the copy has read it
-    VA_HIP(hipMemsetAsync(counts, 0, C_WORDS * sizeof(int), st));
+    VA_HIP(hipMemsetAsync(P.counts, 0, C_WORDS * sizeof(int), st));
     // S88: the flow's votes and their integral planes, once for all scales
-    if (int rc = launch_votes(nullptr, (const float*)flow, T, h, w, p->bins, nullptr, votes, st)) return rc;
-    if (int rc = va_dtraj_integral(ctx, votes, T * p->bins, w, h, hofI, stream)) return rc;
+    const long long planes = (long long)T * p->bins;
+    if (int rc = launch_votes(nullptr, (const float*)flow, T, h, w, p->bins, nullptr, P.votes, st)) return rc;
+    if (int rc = va_integral_planes(P.votes, P.hofI, planes, w, h, st)) return rc;
     for (int si = 0; si < p->n_sigmas; ++si)
         for (int ti = 0; ti < p->n_taus; ++ti) {
             const int ss = 2 * si, ts = 2 * (VA_STIP_MAX_SIGMAS + ti);
-            const float* gs = taps + (size_t)ss * kTapStride;
-            const float* gt = taps + (size_t)ts * kTapStride;
-            if (int rc = smooth3(gray, gray_is_u8, L, A, B, gs, radius[ss], gt, radius[ts], T, h, w, P.tu, st)) return rc;
-            if (int rc = launch_products(L, Pr, T, h, w, st)) return rc;
+            const float* gs = P.taps + (size_t)ss * kTapStride;
+            const float* gt = P.taps + (size_t)ts * kTapStride;
+            if (int rc = smooth3(gray, gray_is_u8, P.L, P.A, P.B, gs, radius[ss], gt, radius[ts], T, h, w, P.tu, st)) return rc;
+            if (int rc = launch_products(P.L, P.Pr, T, h, w, st)) return rc;
             for (int c = 0; c < 6; ++c) {
-                float* Pc = Pr + (size_t)c * P.vox;
-                if (int rc = smooth3(Pc, 0, Pc, A, B, gs + kTapStride, radius[ss + 1], gt + kTapStride, radius[ts + 1], T, h, w, P.tu, st)) return rc;
+                float* Pc = P.Pr + (size_t)c * P.vox;
+                if (int rc = smooth3(Pc, 0, Pc, P.A, P.B, gs + kTapStride, radius[ss + 1], gt + kTapStride, radius[ts + 1], T, h, w, P.tu, st)) return rc;
             }
-            if (int rc = launch_response(Pr, H, p->k, P.vox, st)) return rc;
-            if (int rc = launch_maxima(H, T, h, w, p->min_response, p->neighbours, si, ti, (int*)points, (float*)response, capacity, counts, rows, st))
+            if (int rc = launch_response(P.Pr, P.H, p->k, P.vox, st)) return rc;
+            if (int rc = launch_maxima(P.H, T, h, w, p->min_response, p->neighbours, si, ti, (int*)points, (float*)response, capacity, P.counts, P.rows, st))
                 return rc;
-            if (int rc = launch_votes(L, nullptr, T, h, w, p->bins, votes, nullptr, st)) return rc;
-            if (int rc = va_dtraj_integral(ctx, votes, T * p->bins, w, h, hogI, stream)) return rc;
-            if (int rc = launch_describe(p, (const int*)points, counts, 0, capacity, hogI, hofI, T, h, w, (float*)desc, st)) return rc;
+            if (int rc = launch_votes(P.L, nullptr, T, h, w, p->bins, P.votes, nullptr, st)) return rc;
+            if (int rc = va_integral_planes(P.votes, P.hogI, planes, w, h, st)) return rc;
+            if (int rc = launch_describe(p, (const int*)points, P.counts, 0, capacity, P.hogI, P.hofI, T, h, w, (float*)desc, st)) return rc;
         }
     int found = 0;
-    VA_HIP(hipMemcpyAsync(&found, counts + C_FOUND, sizeof(int), hipMemcpyDeviceToHost, st));
+    VA_HIP(hipMemcpyAsync(&found, P.counts + C_FOUND, sizeof(int), hipMemcpyDeviceToHost, st));
     VA_HIP(hipStreamSynchronize(st));
     *count = found;
     return VA_OK;

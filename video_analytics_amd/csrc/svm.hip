@@ -7,14 +7,11 @@
 // class-major, [rows][D] with D = dim + 1: row r is [coef_r, intercept_r / s].  The homogeneous column s is supplied by the
 // product kernels; X is never copied.  With s = 0 the last coordinate has gradient W[D-1] = 0 and stays 0.
 //
-// Both products run on v_mfma_f64_16x16x4_f64 (one f64 of A and of B per lane: A[row lane&15][k lane>>4],
-// B[k lane>>4][col lane&15]; four results per lane: col lane&15, row (lane>>4) + 4 reg).  Every sum has a fixed order, there
+// Both products run on v_mfma_f64_16x16x4_f64 (operand layout: v4d in va_feature_device.h).  Every sum has a fixed order, there
 // are no atomics: the result is a function of the inputs alone.
-#include "va_internal.h"
+#include "va_feature_device.h"
 
 namespace {
-
-typedef double v4d __attribute__((ext_vector_type(4)));
 
 constexpr int kSvmCgSteps = 100;    // CG steps enqueued per Newton step (a class whose CG has converged skips the rest)
 constexpr int kSvmChunkRows = 256;  // rows of X per partial sum of the transposed product
@@ -162,18 +159,6 @@ __global__ void __launch_bounds__(256) k_svm_xtu(const double* __restrict__ X, i
         }
 }
 
-// The sum of v over the 256 threads of a workgroup, the same bits in every thread: an xor butterfly in each wave, then
-// the four waves in order.
-__device__ __forceinline__ double block_sum(double v, double* red)
-{
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v = v + __shfl_xor(v, off, 64);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return ((red[0] + red[1]) + red[2]) + red[3];
-}
-
 struct SvmState {
     double *W, *G, *S, *R, *P, *HP;        // [c][D]
     double *M, *U, *Q;                     // [n][c]
@@ -182,13 +167,6 @@ struct SvmState {
     double *f, *gn, *g0, *steps, *rr, *cgtol, *cgs;  // [c]
     int *live, *notdone;                   // [c]
 };
-
-__device__ __forceinline__ double part_sum(const double* __restrict__ part, int chunks, size_t stride, size_t at)
-{
-    double acc = part[at];
-    for (int ch = 1; ch < chunks; ++ch) acc = acc + part[(size_t)ch * stride + at];
-    return acc;
-}
 
 __global__ void __launch_bounds__(256) k_svm_init(SvmState s, int c, int D)
 {
@@ -213,7 +191,7 @@ __global__ void __launch_bounds__(256) k_svm_cls_grad(SvmState s, int c, int D, 
     double ww = 0.0, gg = 0.0, ls = 0.0;
     for (int k = threadIdx.x; k < D; k += 256) {
         const double w = s.W[base + k];
-        const double g = w + 2.0 * C * part_sum(s.part, chunks, (size_t)c * D, base + k);
+        const double g = w + 2.0 * C * va_strided_sum(s.part, chunks, (size_t)c * D, base + k);
         s.G[base + k] = g;
         s.S[base + k] = 0.0;
         s.R[base + k] = -g;
@@ -222,9 +200,9 @@ __global__ void __launch_bounds__(256) k_svm_cls_grad(SvmState s, int c, int D, 
         gg = gg + g * g;
     }
     for (int b = threadIdx.x; b < row_blocks; b += 256) ls = ls + s.losspart[(size_t)b * c + r];
-    ww = block_sum(ww, red);
-    gg = block_sum(gg, red);
-    ls = block_sum(ls, red);
+    ww = va_wg_sum256(ww, red);
+    gg = va_wg_sum256(gg, red);
+    ls = va_wg_sum256(ls, red);
     if (threadIdx.x == 0) {
         const double gn = sqrt(gg);
         const double g0 = first ? gn : s.g0[r];
@@ -251,11 +229,11 @@ __global__ void __launch_bounds__(256) k_svm_cls_cg(SvmState s, int c, int D, in
     double php = 0.0;
     for (int k = threadIdx.x; k < D; k += 256) {
         const double p = s.P[base + k];
-        const double hp = p + 2.0 * C * part_sum(s.part, chunks, (size_t)c * D, base + k);
+        const double hp = p + 2.0 * C * va_strided_sum(s.part, chunks, (size_t)c * D, base + k);
         s.HP[base + k] = hp;
         php = php + p * hp;
     }
-    php = block_sum(php, red);
+    php = va_wg_sum256(php, red);
     if (!(php > 0.0)) {  // P = 0 or not finite: the direction found so far is the step
         if (threadIdx.x == 0) s.live[r] = 0;
         return;
@@ -268,7 +246,7 @@ __global__ void __launch_bounds__(256) k_svm_cls_cg(SvmState s, int c, int D, in
         s.R[base + k] = res;
         rn = rn + res * res;
     }
-    rn = block_sum(rn, red);
+    rn = va_wg_sum256(rn, red);
     if (threadIdx.x == 0) s.cgs[r] = s.cgs[r] + 1.0;
     if (sqrt(rn) <= cgtol) {
         if (threadIdx.x == 0) s.live[r] = 0;
@@ -296,9 +274,9 @@ __global__ void __launch_bounds__(256) k_svm_cls_ls(SvmState s, const int* __res
         ss = ss + sv * sv;
         gs = gs + s.G[base + k] * sv;
     }
-    ws = block_sum(ws, red);
-    ss = block_sum(ss, red);
-    gs = block_sum(gs, red);
+    ws = va_wg_sum256(ws, red);
+    ss = va_wg_sum256(ss, red);
+    gs = va_wg_sum256(gs, red);
     double t = 1.0;
     bool found = false;
     if (gs < 0.0) {
@@ -311,7 +289,7 @@ __global__ void __launch_bounds__(256) k_svm_cls_ls(SvmState s, const int* __res
                 const double ht = fmax(0.0, 1.0 - y * (m + t * s.Q[(size_t)i * c + r]));
                 acc = acc + (ht - h0) * (ht + h0);
             }
-            acc = block_sum(acc, red);
+            acc = va_wg_sum256(acc, red);
             const double delta = t * ws + 0.5 * t * t * ss + C * acc;
             if (delta <= kSvmArmijo * t * gs) {
                 found = true;
@@ -355,25 +333,20 @@ size_t svm_layout(int n, int dim, int c, char* base, SvmState* st)
 {
     const size_t D = (size_t)dim + 1;
     const size_t chunks = (size_t)va_cdiv(n, kSvmChunkRows), row_blocks = (size_t)va_cdiv(n, 64);
-    size_t off = 0;
-    auto take = [&](size_t count, size_t elem) {
-        const uintptr_t p = (uintptr_t)base + off;
-        off += va_align_up(count * elem, 256);
-        return (void*)p;
-    };
+    va_carver ws{base};
     SvmState s;
     double** vec[6] = {&s.W, &s.G, &s.S, &s.R, &s.P, &s.HP};
-    for (double** v : vec) *v = (double*)take((size_t)c * D, sizeof(double));
+    for (double** v : vec) *v = ws.take<double>((size_t)c * D);
     double** mat[3] = {&s.M, &s.U, &s.Q};
-    for (double** m : mat) *m = (double*)take((size_t)n * c, sizeof(double));
-    s.part = (double*)take(chunks * c * D, sizeof(double));
-    s.losspart = (double*)take(row_blocks * c, sizeof(double));
+    for (double** m : mat) *m = ws.take<double>((size_t)n * c);
+    s.part = ws.take<double>(chunks * c * D);
+    s.losspart = ws.take<double>(row_blocks * c);
     double** sca[7] = {&s.f, &s.gn, &s.g0, &s.steps, &s.rr, &s.cgtol, &s.cgs};
-    for (double** v : sca) *v = (double*)take((size_t)c, sizeof(double));
-    s.live = (int*)take((size_t)c, sizeof(int));
-    s.notdone = (int*)take((size_t)c, sizeof(int));
+    for (double** v : sca) *v = ws.take<double>((size_t)c);
+    s.live = ws.take<int>((size_t)c);
+    s.notdone = ws.take<int>((size_t)c);
     if (st) *st = s;
-    return off;
+    return ws.off;
 }
 
 bool svm_sizes_ok(int n, int dim, int rows)

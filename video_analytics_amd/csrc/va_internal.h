@@ -126,6 +126,23 @@ __device__ __forceinline__ float va_bilinear_plain(const float* __restrict__ f, 
 static inline size_t va_align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 static inline int va_cdiv(int a, int b) { return (a + b - 1) / b; }
 
+// A workspace cut into parts that each start on a 256-byte boundary.  `base` may be NULL: the pointers are then the parts'
+// offsets and `off` is the size the workspace needs.
+struct va_carver {
+    void* base;
+    size_t off = 0;
+    template <class T>
+    T* take(size_t count)
+    {
+        T* p = (T*)((uintptr_t)base + off);
+        off += va_align_up(count * sizeof(T), 256);
+        return p;
+    }
+};
+
+// S72: the integral planes [planes][h+1][w+1] of u32 [planes][h][w], sums mod 2^32 (dtraj.hip; stip.hip sums its votes with it)
+int va_integral_planes(const unsigned* votes, unsigned* out, long long planes, int w, int h, hipStream_t st);
+
 // ---- flow methods (tvl1.hip, brox.hip, farneback.hip): the front end they share, S0-S2 and the geometry (flow_common.hip)
 
 constexpr int kVaMaxScales = 16;
@@ -133,49 +150,6 @@ constexpr int kVaMaxLds = 160 * 1024;  // what one workgroup of gfx950 can hold
 
 __device__ __forceinline__ int d_min(int a, int b) { return a < b ? a : b; }
 __device__ __forceinline__ int d_max(int a, int b) { return a > b ? a : b; }
-
-// ---- orientation votes (dtraj.hip with 8 bins, stip.hip with va_stip_params.bins): DESIGN.md S70-S71
-// S70: p(s) ~ atan(s) 4 / pi on [0,1], odd, Horner in s^2
-constexpr float kAtanC0 = 1.2732345f, kAtanC1 = -0.4242086f, kAtanC2 = 0.25219768f, kAtanC3 = -0.16850284f, kAtanC4 = 0.10143076f,
-                kAtanC5 = -0.042850755f, kAtanC6 = 0.0086996285f;
-
-// S70: magnitude and bin coordinate in [0,8] of the vector (x, y)
-__device__ __forceinline__ void va_orient(float x, float y, float& m, float& a)
-{
-    m = sqrtf(x * x + y * y);
-    const float ax = fabsf(x), ay = fabsf(y);
-    const float lo = fminf(ax, ay), hi = fmaxf(ax, ay);
-    const float s = lo / (hi > 0.0f ? hi : 1.0f);
-    const float s2 = s * s;
-    float p = kAtanC6;
-    p = p * s2 + kAtanC5;
-    p = p * s2 + kAtanC4;
-    p = p * s2 + kAtanC3;
-    p = p * s2 + kAtanC2;
-    p = p * s2 + kAtanC1;
-    p = p * s2 + kAtanC0;
-    p = p * s;
-    if (ay > ax) p = 2.0f - p;
-    if (x < 0.0f) p = 4.0f - p;
-    if (y < 0.0f) p = 8.0f - p;
-    a = p;
-}
-
-// S70-S71: the two quantised votes of one group of `bins` circular bins (S70's coordinate times bins / 8, which is exact for
-// the powers of two and changes nothing at 8); a magnitude that is not finite votes nothing
-__device__ __forceinline__ void va_votes_of(float x, float y, float vmax, float scale, int bins, int& b0, unsigned& q0, unsigned& q1,
-                                            float& m)
-{
-    float a;
-    va_orient(x, y, m, a);
-    b0 = 0, q0 = 0u, q1 = 0u;
-    if (!(fabsf(m) <= 3.4028234663852886e38f)) return;
-    if (bins != 8) a = a * ((float)bins * 0.125f);
-    const float fl = floorf(a), f = a - fl;
-    b0 = (int)fl % bins;
-    q0 = (unsigned)rintf(fminf(m * (1.0f - f), vmax) * scale);
-    q1 = (unsigned)rintf(fminf(m * f, vmax) * scale);
-}
 
 // State / per-warp-constant planes store every aligned run of four pixels as [x0, x0+2, x0+1, x0+3]: a thread of
 // k_iter_tile then gets its four pixels as the register pairs E = (x0, x0+2), O = (x0+1, x0+3) straight from one

@@ -17,23 +17,10 @@ import numpy as np
 import torch
 
 from . import _ffi
+from ._features import check_rows, check_segments, dev64, workspace
 
 EPSILON = 1e-6  # Sheet02.py:39: a Fisher vector whose norm is below it is stored as it is
 MAX_PCA_DIM, MAX_GMM_DIM, MAX_GMM_COMPONENTS, MAX_POSTERIOR_ROWS = 2048, 512, 256, 65536
-
-
-def _check_rows(x, who, name="x", max_dim=MAX_GMM_DIM):
-    if not isinstance(x, torch.Tensor) or not x.is_cuda:
-        raise ValueError("%s: %s must be a CUDA tensor" % (who, name))
-    if x.dim() != 2 or x.dtype != torch.float32:
-        raise ValueError("%s: %s must be float32 [n, d], got %s %s" % (who, name, x.dtype, tuple(x.shape)))
-    if x.shape[1] < 1 or x.shape[1] > max_dim:
-        raise ValueError("%s: %s must have 1 .. %d columns, got %d" % (who, name, max_dim, x.shape[1]))
-    return x.contiguous()
-
-
-def _dev64(a, dev):
-    return torch.as_tensor(np.ascontiguousarray(np.asarray(a, dtype=np.float64))).to(dev)
 
 
 # ---- PCA -----------------------------------------------------------------------------------------------------------------
@@ -43,7 +30,7 @@ def pca_moments(descs):
     stores, the others add.  -> ``(count, column sums [d], upper triangle of X^T X [d,d])`` as float64 numpy."""
     who = "pca_moments"
     parts = [descs] if isinstance(descs, torch.Tensor) else list(descs)
-    parts = [_check_rows(p, who, "descs", MAX_PCA_DIM) for p in parts]
+    parts = [check_rows(p, who, MAX_PCA_DIM, "descs") for p in parts]
     parts = [p for p in parts if p.shape[0] > 0]
     if not parts:
         raise ValueError("%s: descs holds no rows" % who)
@@ -56,11 +43,8 @@ def pca_moments(descs):
     with torch.cuda.device(dev):
         for i, p in enumerate(parts):
             n = int(p.shape[0])
-            need = L.va_pca_workspace_bytes(n, d)
-            if need == 0:
-                raise ValueError(L.va_last_error().decode())
-            ws = torch.empty((need // 8,), dtype=torch.float64, device=dev)
-            _ffi.check(L.va_pca_moments(_ffi.ctx(dev.index), _ffi.ptr(p), n, d, int(i == 0), _ffi.ptr(sums), _ffi.ptr(ws), need,
+            ws = workspace(L.va_pca_workspace_bytes(n, d), dev)
+            _ffi.check(L.va_pca_moments(_ffi.ctx(dev.index), _ffi.ptr(p), n, d, int(i == 0), _ffi.ptr(sums), _ffi.ptr(ws), ws.numel(),
                                         _ffi.stream_ptr(dev)))
         s = sums.cpu().numpy()
     return float(s[0]), s[1:1 + d].copy(), s[1 + d:].reshape(d, d).copy()
@@ -79,7 +63,7 @@ class PCAModel(object):
     def transform(self, x):
         """``(x - mean) components^T`` for a CUDA float32 ``[n,d]`` tensor -> CUDA float32 ``[n,m]`` (``va_pca_transform``:
         float64 accumulation, no whitening)."""
-        x = _check_rows(x, "PCAModel.transform", "x", MAX_PCA_DIM)
+        x = check_rows(x, "PCAModel.transform", MAX_PCA_DIM)
         m, d = self.components.shape
         if x.shape[1] != d:
             raise ValueError("PCAModel.transform: x has %d columns, the model %d" % (x.shape[1], d))
@@ -87,7 +71,7 @@ class PCAModel(object):
         out = torch.empty((n, m), dtype=torch.float32, device=dev)
         if n == 0:
             return out
-        mean, comp = _dev64(self.mean, dev), _dev64(self.components, dev)
+        mean, comp = dev64(self.mean, dev), dev64(self.components, dev)
         with torch.cuda.device(dev):
             _ffi.check(_ffi.lib().va_pca_transform(_ffi.ctx(dev.index), _ffi.ptr(x), n, d, _ffi.ptr(mean), _ffi.ptr(comp), m, _ffi.ptr(out),
                                                    _ffi.stream_ptr(dev)))
@@ -143,47 +127,34 @@ def _gmm_params(chunk_rows, batch_rows):
     return _ffi.default_gmm_params(**over)
 
 
-def _check_segments(segments, n, who):
-    seg = np.asarray(segments.cpu() if isinstance(segments, torch.Tensor) else segments)
-    if seg.ndim != 1 or len(seg) < 2 or seg.dtype.kind not in "iu":
-        raise ValueError("%s: segments must be integers [n_segments + 1]" % who)
-    seg = seg.astype(np.int64)
-    if seg[0] != 0 or seg[-1] != n or (np.diff(seg) < 0).any():
-        raise ValueError("%s: segments must ascend from 0 to the number of rows (%d)" % (who, n))
-    return seg
-
-
 def gmm_stats(x, segments, weights, means, variances, mode="soft", chunk_rows=None, batch_rows=None):
     """``va_gmm_stats``: x CUDA float32 ``[n,d]`` (n >= 1, d <= 512), segments ``[n_segments + 1]`` ascending from 0 to n,
     the parameters float64 ``[k]``, ``[k,d]``, ``[k,d]`` (k <= 256) as arrays or tensors on x's device.  ``mode``: "soft"
     (posteriors) or "hard" (one-hot of the arg-max, lowest component on ties).  -> ``(stats, loglik)``: CUDA float64
     ``[n_segments, k, 1 + 2d]`` = ``[S0 | S1 | S2]`` and ``[n_segments]``."""
     who = "gmm_stats"
-    x = _check_rows(x, who)
+    x = check_rows(x, who, MAX_GMM_DIM)
     if mode not in ("soft", "hard"):
         raise ValueError("%s: mode must be 'soft' or 'hard', got %r" % (who, mode))
     n, d, dev = int(x.shape[0]), int(x.shape[1]), x.device
     if n < 1:
         raise ValueError("%s: x holds no rows" % who)
-    seg = _check_segments(segments, n, who)
-    w, mu, var = (t.to(device=dev, dtype=torch.float64).contiguous() if isinstance(t, torch.Tensor) else _dev64(t, dev)
+    seg = check_segments(segments, n, who)
+    w, mu, var = (t.to(device=dev, dtype=torch.float64).contiguous() if isinstance(t, torch.Tensor) else dev64(t, dev)
                   for t in (weights, means, variances))
     k = int(w.shape[0])
     if w.dim() != 1 or tuple(mu.shape) != (k, d) or tuple(var.shape) != (k, d):
         raise ValueError("%s: weights [k], means [k,%d], variances [k,%d] expected, got %s %s %s"
                          % (who, d, d, tuple(w.shape), tuple(mu.shape), tuple(var.shape)))
     L, p, ns = _ffi.lib(), _gmm_params(chunk_rows, batch_rows), len(seg) - 1
-    need = L.va_gmm_workspace_bytes(n, d, k, ns, ctypes.byref(p))
-    if need == 0:
-        raise ValueError(L.va_last_error().decode())
+    ws = workspace(L.va_gmm_workspace_bytes(n, d, k, ns, ctypes.byref(p)), dev)
     segd = torch.as_tensor(seg).to(dev)
-    ws = torch.empty((need,), dtype=torch.uint8, device=dev)
     stats = torch.empty((ns, k, 1 + 2 * d), dtype=torch.float64, device=dev)
     loglik = torch.empty((ns,), dtype=torch.float64, device=dev)
     with torch.cuda.device(dev):
         _ffi.check(L.va_gmm_stats(_ffi.ctx(dev.index), _ffi.ptr(x), n, d, _ffi.ptr(segd), ns, _ffi.ptr(w), _ffi.ptr(mu), _ffi.ptr(var), k,
                                   _ffi.VA_GMM_HARD if mode == "hard" else _ffi.VA_GMM_SOFT, ctypes.byref(p), _ffi.ptr(stats),
-                                  _ffi.ptr(loglik), _ffi.ptr(ws), need, _ffi.stream_ptr(dev)))
+                                  _ffi.ptr(loglik), _ffi.ptr(ws), ws.numel(), _ffi.stream_ptr(dev)))
     return stats, loglik
 
 
@@ -226,7 +197,7 @@ class GMMModel(object):
         """The responsibilities ``[n,K]`` float64 (numpy) of a CUDA float32 ``[n,D]`` tensor: for tests and small inputs
         only, at most 65536 rows -- the library itself never holds them for more than one batch of rows."""
         who = "GMMModel.posteriors"
-        x = _check_rows(x, who)
+        x = check_rows(x, who, MAX_GMM_DIM)
         n, d, dev, k = int(x.shape[0]), int(x.shape[1]), x.device, len(self.weights)
         if d != self.means.shape[1]:
             raise ValueError("%s: x has %d columns, the model %d" % (who, d, self.means.shape[1]))
@@ -235,17 +206,14 @@ class GMMModel(object):
         if mode not in ("soft", "hard"):
             raise ValueError("%s: mode must be 'soft' or 'hard', got %r" % (who, mode))
         L = _ffi.lib()
-        need = L.va_gmm_workspace_bytes(n, d, k, 1, None)
-        if need == 0:
-            raise ValueError(L.va_last_error().decode())
-        w, mu, var = _dev64(self.weights, dev), _dev64(self.means, dev), _dev64(self.variances, dev)
-        ws = torch.empty((need,), dtype=torch.uint8, device=dev)
+        ws = workspace(L.va_gmm_workspace_bytes(n, d, k, 1, None), dev)
+        w, mu, var = dev64(self.weights, dev), dev64(self.means, dev), dev64(self.variances, dev)
         g = torch.empty((n, k), dtype=torch.float64, device=dev)
         lse = torch.empty((n,), dtype=torch.float64, device=dev)
         with torch.cuda.device(dev):
             _ffi.check(L.va_gmm_posteriors(_ffi.ctx(dev.index), _ffi.ptr(x), n, d, _ffi.ptr(w), _ffi.ptr(mu), _ffi.ptr(var), k,
                                            _ffi.VA_GMM_HARD if mode == "hard" else _ffi.VA_GMM_SOFT, _ffi.ptr(g), _ffi.ptr(lse),
-                                           _ffi.ptr(ws), need, _ffi.stream_ptr(dev)))
+                                           _ffi.ptr(ws), ws.numel(), _ffi.stream_ptr(dev)))
         return g.cpu().numpy()
 
     def save(self, path):
@@ -286,7 +254,7 @@ def gmm_fit(x, n_components=256, *, tol=1e-3, max_iter=100, reg_covar=1e-6, seed
     less than ``tol`` (sklearn's rule) or after ``max_iter`` iterations; the host reads one float64 per iteration.  A
     non-finite log-likelihood raises RuntimeError naming the iteration.  -> ``GMMModel``."""
     who = "gmm_fit"
-    x = _check_rows(x, who)
+    x = check_rows(x, who, MAX_GMM_DIM)
     check_gmm_fit_args(n_components, tol, max_iter, reg_covar, seed, kmeans_iters)
     n, d, dev, k = int(x.shape[0]), int(x.shape[1]), x.device, int(n_components)
     if n < k:
@@ -296,7 +264,7 @@ def gmm_fit(x, n_components=256, *, tol=1e-3, max_iter=100, reg_covar=1e-6, seed
     if init is not None:
         if not isinstance(init, (tuple, list)) or len(init) != 3:
             raise ValueError("%s: init must be (weights, means, variances)" % who)
-        w, mu, var = (_dev64(a, dev) for a in init)
+        w, mu, var = (dev64(a, dev) for a in init)
         if tuple(w.shape) != (k,) or tuple(mu.shape) != (k, d) or tuple(var.shape) != (k, d):
             raise ValueError("%s: init must hold weights [%d], means [%d,%d], variances [%d,%d]" % (who, k, k, d, k, d))
     else:
@@ -340,7 +308,7 @@ def fisher_encode(stats, counts, weights, means, variances, power=0.0):
     cnt = np.asarray(counts.cpu() if isinstance(counts, torch.Tensor) else counts).astype(np.int64)
     if cnt.shape != (ns,) or (cnt < 0).any():
         raise ValueError("%s: counts must be %d non-negative integers" % (who, ns))
-    w, mu, var = (t.to(device=dev, dtype=torch.float64).contiguous() if isinstance(t, torch.Tensor) else _dev64(t, dev)
+    w, mu, var = (t.to(device=dev, dtype=torch.float64).contiguous() if isinstance(t, torch.Tensor) else dev64(t, dev)
                   for t in (weights, means, variances))
     if tuple(w.shape) != (k,) or tuple(mu.shape) != (k, d) or tuple(var.shape) != (k, d):
         raise ValueError("%s: weights [%d], means [%d,%d], variances [%d,%d] expected" % (who, k, k, d, k, d))
@@ -360,7 +328,7 @@ def fisher_vectors(x, segments, gmm, power=0.0, chunk_rows=None, batch_rows=None
     its L2 norm unless that is below ``EPSILON``.  One ``va_gmm_stats`` call and one ``va_fisher_encode`` call cover all
     segments."""
     who = "fisher_vectors"
-    x = _check_rows(x, who)
+    x = check_rows(x, who, MAX_GMM_DIM)
     if not isinstance(gmm, GMMModel):
         raise ValueError("%s: gmm must be a GMMModel" % who)
     if isinstance(power, bool) or not isinstance(power, (int, float, np.integer, np.floating)) or not 0.0 <= power <= 1.0:
@@ -368,7 +336,7 @@ def fisher_vectors(x, segments, gmm, power=0.0, chunk_rows=None, batch_rows=None
     n, d, k = int(x.shape[0]), int(x.shape[1]), len(gmm.weights)
     if d != gmm.means.shape[1]:
         raise ValueError("%s: x has %d columns, the mixture %d" % (who, d, gmm.means.shape[1]))
-    seg = _check_segments(segments, n, who)
+    seg = check_segments(segments, n, who)
     if n == 0:
         return torch.zeros((len(seg) - 1, k + 2 * k * d), dtype=torch.float32, device=x.device)
     stats, _ll = gmm_stats(x, seg, gmm.weights, gmm.means, gmm.variances, "soft", chunk_rows, batch_rows)

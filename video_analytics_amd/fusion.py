@@ -15,6 +15,7 @@ import warnings
 import numpy as np
 import torch
 
+from . import _features
 from . import _ffi
 
 
@@ -308,11 +309,9 @@ def linear_svm_fit(descriptors, labels, C=1.0, tol=1e-8, max_iter=100, fit_inter
     rows = 1 if len(classes) == 2 else len(classes)
     scale = float(intercept_scaling) if fit_intercept else 0.0
     L = _ffi.lib()
-    need = L.va_linear_svm_fit_workspace_bytes(n, d, rows)
-    if need == 0:
-        raise ValueError(L.va_last_error().decode("utf-8", "replace"))
+    work = _features.workspace(L.va_linear_svm_fit_workspace_bytes(n, d, rows), dev)
+    need = work.numel()
     yd = torch.as_tensor(y).to(dev)
-    work = torch.empty((need // 8,), dtype=torch.float64, device=dev)
     coef = torch.empty((rows, d), dtype=torch.float64, device=dev)
     intercept = torch.empty((rows,), dtype=torch.float64, device=dev)
     stats = torch.empty((rows, 4), dtype=torch.float64, device=dev)

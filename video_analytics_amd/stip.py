@@ -11,9 +11,9 @@ import ctypes
 import numpy as np
 import torch
 
+from . import _features
 from . import _ffi
 from . import codebook as vcodebook
-from . import flow as vflow
 from . import fusion
 
 # what the outputs sized for the proven bound may take when max_points is None
@@ -47,48 +47,14 @@ def space_time_interest_points(gray, flow=None, params=None, flow_params=None, m
     ``MEMORY_BUDGET_BYTES``.  The inputs are left untouched.
     """
     who = "space_time_interest_points"
-    if not isinstance(gray, torch.Tensor) or not gray.is_cuda:
-        raise ValueError("%s: gray must be a CUDA tensor" % who)
-    if gray.dim() != 3 or gray.dtype not in (torch.uint8, torch.float32):
-        raise ValueError("%s: gray must be uint8 or float32 [T,H,W]" % who)
-    if gray.shape[0] < 2:
-        raise ValueError("%s: gray must hold at least 2 frames, got %d" % (who, gray.shape[0]))
-    if params is not None and over:
-        raise ValueError("%s: pass an _ffi.StipParams or keyword overrides, not both" % who)
-    p = params if params is not None else _ffi.default_stip_params(**over)
-    if not isinstance(p, _ffi.StipParams):
-        raise ValueError("%s: params must be an _ffi.StipParams" % who)
-    gray = gray.contiguous()
+    gray, flow, p = _features.extraction_inputs(who, gray, flow, flow_params, params, over, _ffi.StipParams, _ffi.default_stip_params)
     T, H, W = gray.shape
-    if flow is None:
-        if flow_params is None:
-            flow = vflow.farneback_flow(gray)
-        else:
-            flow = vflow.tvl1_flow(gray, flow_params)
-    else:
-        if flow_params is not None:
-            raise ValueError("%s: flow_params describes the flow this call computes; with a given flow it must be None" % who)
-        if (not isinstance(flow, torch.Tensor) or flow.device != gray.device or flow.dtype != torch.float32
-                or tuple(flow.shape) != (T - 1, 2, H, W)):
-            raise ValueError("%s: flow must be a float32 [%d,2,%d,%d] tensor on gray's device" % (who, T - 1, H, W))
-        flow = flow.contiguous()
     L = _ffi.lib()
     dim = descriptor_length(p)
-    if max_points is None:
-        cap = max(point_bound(W, H, T, p), 1)
-        need = cap * (dim + 5 + 1) * 4
-        if need > MEMORY_BUDGET_BYTES:
-            raise ValueError("%s: the bound of %d points needs %d bytes of output, more than MEMORY_BUDGET_BYTES (%d): pass max_points"
-                             % (who, cap, need, MEMORY_BUDGET_BYTES))
-    else:
-        cap = int(max_points)
-        if cap < 1:
-            raise ValueError("%s: max_points must be >= 1, got %d" % (who, cap))
-    nbytes = L.va_stip_workspace_bytes(W, H, T, cap, ctypes.byref(p))
-    if nbytes == 0:
-        raise ValueError(L.va_last_error().decode())
+    cap = _features.extraction_capacity(who, lambda: point_bound(W, H, T, p), (dim + 5 + 1) * 4, max_points, MEMORY_BUDGET_BYTES,
+                                        "points", "max_points")
     dev = gray.device
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    ws = _features.workspace(L.va_stip_workspace_bytes(W, H, T, cap, ctypes.byref(p)), dev)
     desc = torch.empty((cap, dim), dtype=torch.float32, device=dev)
     points = torch.empty((cap, 5), dtype=torch.int32, device=dev)
     response = torch.empty((cap,), dtype=torch.float32, device=dev)
@@ -113,23 +79,11 @@ class StipClassifier(object):
         self.codebook = self.coef = self.intercept = self.classes = None
         self.norm = "l2"
 
-    @staticmethod
-    def _videos(descs_per_video, who):
-        if isinstance(descs_per_video, torch.Tensor) or not isinstance(descs_per_video, (list, tuple)) or len(descs_per_video) == 0:
-            raise ValueError("%s: descs_per_video must be a non-empty list of CUDA float32 [n_i, d] tensors" % who)
-        for v in descs_per_video:
-            if not isinstance(v, torch.Tensor) or not v.is_cuda or v.dtype != torch.float32 or v.dim() != 2:
-                raise ValueError("%s: descs_per_video must be a non-empty list of CUDA float32 [n_i, d] tensors" % who)
-        if len(set(int(v.shape[1]) for v in descs_per_video)) != 1:
-            raise ValueError("%s: descs_per_video must share one descriptor length" % who)
-        segments = np.concatenate([[0], np.cumsum([int(v.shape[0]) for v in descs_per_video])]).astype(np.int64)
-        return list(descs_per_video), segments
-
     def fit(self, descs_per_video, labels, n_words=256, norm="l2", **kmeans_kw):
         """``codebook.kmeans_fit`` with ``n_words`` clusters (Sheet01.py:262) and ``kmeans_kw``, histograms with ``norm``
         (``"l2"``: Sheet01's ``normalize``), ``fusion.linear_svm_fit``.  -> self."""
         who = "StipClassifier.fit"
-        videos, segments = self._videos(descs_per_video, who)
+        videos, segments = _features.check_videos(descs_per_video, who)
         if len(labels) != len(videos):
             raise ValueError("%s: %d videos but %d labels" % (who, len(videos), len(labels)))
         if norm not in vcodebook.NORMS:
@@ -145,7 +99,7 @@ class StipClassifier(object):
         who = "StipClassifier.encode"
         if self.codebook is None:
             raise ValueError("%s: the model is not fitted" % who)
-        videos, segments = self._videos(descs_per_video, who)
+        videos, segments = _features.check_videos(descs_per_video, who)
         return self.codebook.histograms(torch.cat(videos, 0), segments, self.norm)
 
     def predict(self, descs_per_video):

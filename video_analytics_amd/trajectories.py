@@ -13,6 +13,7 @@ import ctypes
 import numpy as np
 import torch
 
+from . import _features
 from . import _ffi
 from . import fisher
 from . import flow as vflow
@@ -49,49 +50,16 @@ def dense_trajectories(gray, flow=None, params=None, flow_params=None, max_traje
     ``MEMORY_BUDGET_BYTES``.  The inputs are left untouched.
     """
     who = "dense_trajectories"
-    if not isinstance(gray, torch.Tensor) or not gray.is_cuda:
-        raise ValueError("%s: gray must be a CUDA tensor" % who)
-    if gray.dim() != 3 or gray.dtype not in (torch.uint8, torch.float32):
-        raise ValueError("%s: gray must be uint8 or float32 [T,H,W]" % who)
-    if gray.shape[0] < 2:
-        raise ValueError("%s: gray must hold at least 2 frames, got %d" % (who, gray.shape[0]))
-    if params is not None and over:
-        raise ValueError("%s: pass an _ffi.DenseTrajParams or keyword overrides, not both" % who)
-    p = params if params is not None else _ffi.default_dense_traj_params(**over)
-    if not isinstance(p, _ffi.DenseTrajParams):
-        raise ValueError("%s: params must be an _ffi.DenseTrajParams" % who)
-    gray = gray.contiguous()
+    gray, flow, p = _features.extraction_inputs(who, gray, flow, flow_params, params, over, _ffi.DenseTrajParams,
+                                                _ffi.default_dense_traj_params)
     T, H, W = gray.shape
-    if flow is None:
-        if flow_params is None:
-            flow = vflow.farneback_flow(gray)
-        else:
-            flow = vflow.tvl1_flow(gray, flow_params)
-    else:
-        if flow_params is not None:
-            raise ValueError("%s: flow_params describes the flow this call computes; with a given flow it must be None" % who)
-        if (not isinstance(flow, torch.Tensor) or flow.device != gray.device or flow.dtype != torch.float32
-                or tuple(flow.shape) != (T - 1, 2, H, W)):
-            raise ValueError("%s: flow must be a float32 [%d,2,%d,%d] tensor on gray's device" % (who, T - 1, H, W))
-        flow = flow.contiguous()
     L = _ffi.lib()
     dim, npts = descriptor_length(p), p.length + 1
-    if max_trajectories is None:
-        cap = max(trajectory_bound(W, H, T, p), 1)
-        need = cap * (dim + 2 * npts + 1) * 4
-        if need > MEMORY_BUDGET_BYTES:
-            raise ValueError("%s: the bound of %d trajectories needs %d bytes of output, more than MEMORY_BUDGET_BYTES (%d): pass "
-                             "max_trajectories" % (who, cap, need, MEMORY_BUDGET_BYTES))
-    else:
-        cap = int(max_trajectories)
-        if cap < 1:
-            raise ValueError("%s: max_trajectories must be >= 1, got %d" % (who, cap))
-    nbytes = L.va_dtraj_workspace_bytes(W, H, T, cap, ctypes.byref(p))
-    if nbytes == 0:
-        raise ValueError(L.va_last_error().decode())
+    cap = _features.extraction_capacity(who, lambda: trajectory_bound(W, H, T, p), (dim + 2 * npts + 1) * 4, max_trajectories,
+                                        MEMORY_BUDGET_BYTES, "trajectories", "max_trajectories")
     dev = gray.device
+    ws = _features.workspace(L.va_dtraj_workspace_bytes(W, H, T, cap, ctypes.byref(p)), dev)
     median = vflow.median_filter(flow, 3)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
     desc = torch.empty((cap, dim), dtype=torch.float32, device=dev)
     points = torch.empty((cap, npts, 2), dtype=torch.float32, device=dev)
     start = torch.empty((cap,), dtype=torch.int32, device=dev)
@@ -122,23 +90,11 @@ class TrajectoryClassifier(object):
         self.pca = self.gmm = self.coef = self.intercept = self.classes = None
         self.power = 0.0
 
-    @staticmethod
-    def _videos(descs_per_video, who):
-        if isinstance(descs_per_video, torch.Tensor) or not isinstance(descs_per_video, (list, tuple)) or len(descs_per_video) == 0:
-            raise ValueError("%s: descs_per_video must be a non-empty list of CUDA float32 [n_i, d] tensors" % who)
-        for v in descs_per_video:
-            if not isinstance(v, torch.Tensor) or not v.is_cuda or v.dtype != torch.float32 or v.dim() != 2:
-                raise ValueError("%s: descs_per_video must be a non-empty list of CUDA float32 [n_i, d] tensors" % who)
-        if len(set(int(v.shape[1]) for v in descs_per_video)) != 1:
-            raise ValueError("%s: descs_per_video must share one descriptor length" % who)
-        segments = np.concatenate([[0], np.cumsum([int(v.shape[0]) for v in descs_per_video])]).astype(np.int64)
-        return list(descs_per_video), segments
-
     def fit(self, descs_per_video, labels, n_components=64, n_gmm=256, power=0.0, **gmm_kw):
         """PCA to ``n_components`` (Sheet02.py:40), ``gmm_fit`` with ``n_gmm`` components (Sheet02.py:41) and ``gmm_kw``,
         Fisher vectors with ``power``, ``fusion.linear_svm_fit``.  -> self."""
         who = "TrajectoryClassifier.fit"
-        videos, segments = self._videos(descs_per_video, who)
+        videos, segments = _features.check_videos(descs_per_video, who)
         if len(labels) != len(videos):
             raise ValueError("%s: %d videos but %d labels" % (who, len(videos), len(labels)))
         if isinstance(n_gmm, bool) or not isinstance(n_gmm, (int, np.integer)) or n_gmm < 1:
@@ -160,7 +116,7 @@ class TrajectoryClassifier(object):
         who = "TrajectoryClassifier.encode"
         if self.pca is None or self.gmm is None:
             raise ValueError("%s: the model is not fitted" % who)
-        videos, segments = self._videos(descs_per_video, who)
+        videos, segments = _features.check_videos(descs_per_video, who)
         return fisher.fisher_vectors(self.pca.transform(torch.cat(videos, 0)), segments, self.gmm, self.power)
 
     def predict(self, descs_per_video):

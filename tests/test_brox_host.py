@@ -68,6 +68,37 @@ def test_the_oracle_agrees_with_the_float64_witness(synth_pair):
     assert d.max() <= 4 * 4.15e-5 and np.median(d) <= 4 * 6.97e-7
 
 
+# The oracle against the witness away from PAPER, one parameter at a time, on the 48 x 40 pair with two levels: (overrides,
+# largest difference in px, median difference in px), measured when the tests were written and printed by the test below.
+# None is derivable (see test_the_oracle_agrees_with_the_float64_witness).  gamma 0 and alpha 5 move the flow slowly: with
+# inner_iters 2, solver_iters 5 it stays below 0.05 px, so these two run four warps of 4 x 25 sweeps (flow of 2.1 and 2.6 px).
+AWAY = [
+    (dict(gamma=0.0, warps=4, inner_iters=4, solver_iters=25), 2.315e-6, 4.924e-7),
+    (dict(alpha=5.0, warps=4, inner_iters=4, solver_iters=25), 2.747e-6, 3.732e-7),
+    (dict(omega=0.5, inner_iters=2, solver_iters=5), 1.823e-6, 3.816e-8),
+    (dict(scale_step=0.5, inner_iters=2, solver_iters=5), 3.604e-5, 8.218e-7),
+]
+
+
+@pytest.mark.parametrize("over,dmax,dmed", AWAY, ids=[",".join("%s=%g" % kv for kv in o.items()) for o, _, _ in AWAY])
+def test_the_oracle_agrees_with_the_float64_witness_away_from_the_defaults(synth_pair, over, dmax, dmed):
+    """Gradient constancy off, under-relaxation (1 - omega > 0), a smoothness weight 25 times the paper's and a scale step
+    whose inverse is 2: the settings tests/test_brox_params_gpu.py holds the kernels to the oracle at.  Measured when the
+    test was written (maximum / median difference, the witness's largest flow):
+        gamma 0          2.315e-6 / 4.924e-7 px, flow up to 2.13 px
+        alpha 5          2.747e-6 / 3.732e-7 px, flow up to 2.56 px
+        omega 0.5        1.823e-6 / 3.816e-8 px, flow up to 1.36 px
+        scale_step 0.5   3.604e-5 / 8.218e-7 px, flow up to 4.76 px
+    asserted: four times the measured figures, a finite oracle flow, and a flow above 1 px."""
+    p = bo.params(**dict(dict(PAPER, nscales=2), **over))
+    assert len(bo.pyramid(synth_pair[0], p)) == 2
+    fo, fw = bo.flow_pair(synth_pair[0], synth_pair[1], p), bw.flow_pair(synth_pair[0], synth_pair[1], p)
+    d = np.abs(fo.astype(np.float64) - fw)
+    print("max %.3e median %.3e (flow up to %.2f px)" % (d.max(), np.median(d), np.abs(fw).max()))
+    assert np.isfinite(fo).all() and np.abs(fw).max() > 1.0  # the pair moves
+    assert d.max() <= 4 * dmax and np.median(d) <= 4 * dmed
+
+
 def test_sor_never_raises_the_quadratic_energy(synth_pair):
     """A frozen inner step's system is symmetric positive definite and 0 < omega < 2: every SOR sweep lowers (or keeps)
     1/2 x'Ax - b'x.  A theorem, asserted strictly, sweep by sweep, in the witness."""
@@ -142,3 +173,60 @@ def test_brox_parameter_object():
         assert flow.pyramid_sizes(w, h, _ffi.default_brox_params(**dict(PAPER, nscales=3))) == tvl1_oracle.pyramid_sizes(w, h, 3, 0.8)
     with pytest.raises(ValueError, match="tile_plan"):
         flow.tile_plan(224, 224, p)
+
+
+def _accepts(w, h, **kw):
+    from video_analytics_amd import _ffi
+    return _ffi.lib().va_brox_workspace_bytes(w, h, 1, 2, ctypes.byref(_ffi.default_brox_params(**dict(PAPER, nscales=1, **kw)))) > 0
+
+
+@pytest.mark.parametrize("K,th,last", [(1, 70, 70), (3, 62, 62), (5, 54, 54), (17, 6, 6)])
+def test_the_shape_helper_refuses_the_tiles_the_library_refuses(K, th, last):
+    """tests/flow_shapes.py against ``pick_shape`` where its decision shows on the host: on 224 x 224, every tile width
+    from 2 to 120 beside a height that makes the region 78 rows.  The two agree on every width; the largest accepted tile
+    has a region of 78 x 78 (3042 pixel pairs of the 3072) and the next width is refused (79 x 78: 3120).
+
+    This is also the one place where the halo H = 2K + 2 itself shows.  The coefficients are wrong up to one pixel from an
+    inner region edge and K red-black sweeps carry that to 2K pixels at the most, so a halo of 2K + 1 would give the same
+    flow bit for bit: no comparison of results can tell the two apart, the accepted tile widths do."""
+    import flow_shapes as fs
+    got = [tw for tw in range(2, 121) if _accepts(224, 224, solver_iters=K, whole_field=0, tile_w=tw, tile_h=th, sweeps_per_launch=K)]
+    want = [tw for tw in range(2, 121) if fs.brox_shape(224, 224, K, whole_field=0, tile_w=tw, tile_h=th, sweeps_per_launch=K)]
+    assert got == want == list(range(2, last + 1))
+    s = fs.brox_shape(224, 224, K, whole_field=0, tile_w=last, tile_h=th, sweeps_per_launch=K)
+    assert (s["rw"], s["rh"], s["pairs"], s["form"]) == (78, 78, 3042, (1024, 3)) and s["lds"] == 80 * 80 * 12
+    # a region of exactly 3072 pairs (96 x 64, as wide as the frame) is the last one accepted
+    assert _accepts(96, 224, solver_iters=3, whole_field=0, tile_w=96, tile_h=48, sweeps_per_launch=3)
+    assert fs.brox_shape(96, 224, 3, whole_field=0, tile_w=96, tile_h=48, sweeps_per_launch=3)["pairs"] == 3072
+    assert not _accepts(97, 224, solver_iters=3, whole_field=0, tile_w=97, tile_h=48, sweeps_per_launch=3)
+    assert fs.brox_shape(97, 224, 3, whole_field=0, tile_w=97, tile_h=48, sweeps_per_launch=3) is None
+
+
+def test_every_brox_limit_case_is_legal_and_reaches_the_form_it_is_named_for():
+    """the cases of tests/test_brox_params_gpu.py, before a GPU sees them: the library accepts each, and the helper gives the
+    pixel pairs, the instantiation, the sweep split and an LDS size below the limit"""
+    import flow_shapes as fs
+    for w, h, it, pairs, form in fs.BROX_WHOLE_CASES:
+        s = fs.brox_shape(w, h, it)
+        assert _accepts(w, h, solver_iters=it) and s["whole"] and (s["pairs"], s["form"]) == (pairs, form) and s["lds"] <= fs.MAX_LDS
+    # both sides of each number launch_inner compares with, and of the whole-field limit
+    assert [fs.brox_form(n) for n in (256, 257, 1024, 1025, 2048, 2049, 3072)] == [(256, 1), (256, 4), (256, 4), (1024, 2), (1024, 2),
+                                                                                   (1024, 3), (1024, 3)]
+    for c in fs.BROX_TILED_CASES:
+        s = fs.brox_shape(c["w"], c["h"], c["solver_iters"], **c["tuning"])
+        assert _accepts(c["w"], c["h"], solver_iters=c["solver_iters"], **c["tuning"]) and not s["whole"]
+        assert all(s[k] == c[k] for k in ("K", "H", "TW", "TH", "rw", "rh", "pairs", "form")), s
+        assert max(fs._pairs(*r) for r in fs.brox_regions(s, c["w"], c["h"])) == c["runs"]
+    for w, h in fs.BROX_SPLIT_FIELDS:
+        for it, spl, K, launches in fs.BROX_SPLIT_CASES:
+            s = fs.brox_shape(w, h, it, whole_field=0, sweeps_per_launch=spl)
+            assert _accepts(w, h, solver_iters=it, whole_field=0, sweeps_per_launch=spl), (w, h, it, spl)
+            assert (s["K"], s["launches"]) == (K, launches) and s["pairs"] <= fs.BROX_MAX_PAIRS and s["lds"] <= fs.MAX_LDS
+    s = fs.brox_shape(150, 131, 17, whole_field=0, sweeps_per_launch=17)
+    assert (s["TW"], s["TH"], s["H"], s["rw"], s["rh"], s["pairs"]) == (6, 6, 36, 78, 78, 3042)
+    # the rotation of the three (du, dv) buffers: three launches and two launches per step end in each buffer in turn
+    for spl, ends in ((1, [1, 2, 0, 1]), (2, [2, 1, 0, 2]), (3, [1, 2, 0, 1])):
+        assert fs.brox_rotation(fs.brox_shape(67, 45, 3, whole_field=0, tile_w=32, tile_h=24, sweeps_per_launch=spl), 4) == ends
+    assert fs.brox_rotation(fs.brox_shape(67, 45, 3), 4) == [0, 0, 0, 0]
+    assert not _accepts(64, 48, solver_iters=20, whole_field=0, sweeps_per_launch=18)  # kMaxK is the last K
+    assert _accepts(64, 48, solver_iters=20, whole_field=0, sweeps_per_launch=fs.BROX_MAX_K)

@@ -162,3 +162,92 @@ def test_farneback_parameter_object():
                       ("profile_levels", lambda: flow.profile_levels(p)), ("profile_read", lambda: flow.profile_read(p))):
         with pytest.raises(ValueError, match=who):
             call()
+
+
+# The oracle against the witness away from SHEET, one setting at a time, on the 80 x 64 pair with three levels and three
+# iterations (the odd count: SHEET's own, repeated here beside the others): (overrides, largest difference in px), measured
+# when the tests were written and printed by the test below.  None is derivable (see FLOW_DIFF).
+AWAY = [
+    (dict(winsize=3), 4.382e-5),      # an ill-conditioned 3 x 3 window: the flow reaches 15 px
+    (dict(winsize=63), 3.462e-6),
+    (dict(winsize=63, gaussian=1), 1.425e-6),
+    (dict(gaussian=1), 3.362e-6),
+    (dict(pyr_scale=0.8), 1.694e-6),
+    (dict(iterations=3), 1.523e-6),
+    (dict(poly_n=7, poly_sigma=1.5), 1.780e-6),
+]
+
+
+@pytest.mark.parametrize("over,dmax", AWAY, ids=[",".join("%s=%g" % kv for kv in o.items()) for o, _ in AWAY])
+def test_the_oracle_flow_agrees_with_the_float64_witness_away_from_the_defaults(planted, over, dmax):
+    """The settings tests/test_farneback_params_gpu.py holds the kernels to the oracle at.  Measured when the test was
+    written (maximum difference, the witness's largest flow):
+        winsize 3               4.382e-5 px, flow up to 15.47 px
+        winsize 63              3.462e-6 px, flow up to 1.51 px
+        winsize 63, gaussian 1  1.425e-6 px, flow up to 1.53 px
+        gaussian 1              3.362e-6 px, flow up to 3.48 px
+        pyr_scale 0.8           1.694e-6 px, flow up to 1.65 px
+        iterations 3            1.523e-6 px, flow up to 1.65 px
+        poly_n 7, sigma 1.5     1.780e-6 px, flow up to 1.70 px
+    asserted: four times the measured figure, a finite oracle flow, and a flow above 1 px."""
+    p = fo.params(**dict(SHEET, **over))
+    a, b = fo.flow_pair(planted[0], planted[1], p), fw.flow_pair(planted[0], planted[1], p)
+    d = np.abs(a.astype(np.float64) - b)
+    print("max difference %.3e median %.3e (flow up to %.2f px)" % (d.max(), np.median(d), np.abs(b).max()))
+    assert np.isfinite(a).all() and np.abs(b).max() > 1.0  # the pair moves
+    assert d.max() <= 4 * dmax
+
+
+def _accepts(**over):
+    return _ffi_lib().va_farneback_workspace_bytes(64, 48, 1, 2, ctypes.byref(_raw(**over))) > 0
+
+
+def _ffi_lib():
+    from video_analytics_amd import _ffi
+    return _ffi.lib()
+
+
+@pytest.mark.parametrize("winsize,th,last", [(63, 16, 25), (59, 16, 33), (31, 16, 102), (63, 1, 66), (15, 0, 164)])
+def test_the_shape_helper_refuses_the_pass_tiles_the_library_refuses(winsize, th, last):
+    """tests/flow_shapes.py against ``pass_tile`` where its decision shows on the host: every caller's tile width from 1 to
+    256 beside one height (0: the library's 16).  The two agree on every width, and the last accepted one is named."""
+    import flow_shapes as fs
+    got = [tw for tw in range(1, 257) if _accepts(winsize=winsize, pass_tile_w=tw, pass_tile_h=th)]
+    want = [tw for tw in range(1, 257) if fs.pass_tile(winsize, tw, th)]
+    assert got == want == list(range(1, last + 1))
+    assert fs.pass_lds(winsize, last, th or 16) <= fs.MAX_LDS and (last == 256 or fs.pass_lds(winsize, last + 1, th or 16) > fs.MAX_LDS)
+
+
+@pytest.mark.parametrize("poly_n,th,last", [(5, 64, 143), (7, 64, 137), (5, 256, 29), (7, 8, 256)])
+def test_the_shape_helper_refuses_the_polyexp_tiles_the_library_refuses(poly_n, th, last):
+    """the same for ``poly_tile``"""
+    import flow_shapes as fs
+    got = [tw for tw in range(1, 257) if _accepts(poly_n=poly_n, poly_tile_w=tw, poly_tile_h=th)]
+    want = [tw for tw in range(1, 257) if fs.poly_tile(poly_n, tw, th)]
+    assert got == want == list(range(1, last + 1))
+    assert fs.poly_lds(poly_n, last, th) <= fs.MAX_LDS and (last == 256 or fs.poly_lds(poly_n, last + 1, th) > fs.MAX_LDS)
+
+
+def test_every_farneback_limit_case_is_legal_and_runs_the_tile_it_is_named_for():
+    """the cases of tests/test_farneback_params_gpu.py, before a GPU sees them, and the figures the tiles are known by"""
+    import flow_shapes as fs
+    # the window of 63: a caller's 16 x 16 is accepted with 146,640 B, 32 x 16 refused with 176,720 B of the 163,840
+    assert _accepts(winsize=63, pass_tile_w=16, pass_tile_h=16) and fs.pass_tile(63, 16, 16) == (16, 16, 146640)
+    assert not _accepts(winsize=63, pass_tile_w=32, pass_tile_h=16) and fs.pass_tile(63, 32, 16) is None and fs.pass_lds(63, 32, 16) == 176720
+    assert b"tuning" in _ffi_lib().va_last_error()
+    # the library's own tile: 32 x 16 up to a window of 59 (162,000 B), halved once for 61 and 63
+    assert [fs.pass_tile(ws)[:2] for ws in (3, 5, 15, 31, 57, 59, 61, 63)] == [(32, 16)] * 6 + [(16, 16)] * 2
+    assert fs.pass_tile(59)[2] == 162000 and fs.pass_lds(61, 32, 16) > fs.MAX_LDS == 163840
+    # poly_n 7: 128 x 64 is accepted with 153,360 B, 256 x 64 refused
+    assert _accepts(poly_n=7, poly_tile_w=128, poly_tile_h=64) and fs.poly_tile(7, 128, 64) == (128, 64, 153360)
+    assert not _accepts(poly_n=7, poly_tile_w=256, poly_tile_h=64) and fs.poly_tile(7, 256, 64) is None
+    for winsize, tile, run, lds, fields in fs.FB_PASS_CASES:
+        assert fs.pass_tile(winsize, *tile) == run + (lds,) and lds <= fs.MAX_LDS
+        for w, h in fields:
+            p = _raw(winsize=winsize, levels=1, pass_tile_w=tile[0], pass_tile_h=tile[1])
+            assert _ffi_lib().va_farneback_workspace_bytes(w, h, 1, 2, ctypes.byref(p)) > 0, (winsize, tile, w, h)
+    for poly_n, sigma, tile, lds, (w, h) in fs.FB_POLY_CASES:
+        assert fs.poly_tile(poly_n, *tile)[2] == lds <= fs.MAX_LDS
+        p = _raw(poly_n=poly_n, poly_sigma=sigma, levels=1, poly_tile_w=tile[0], poly_tile_h=tile[1])
+        assert _ffi_lib().va_farneback_workspace_bytes(w, h, 1, 2, ctypes.byref(p)) > 0, (poly_n, tile, w, h)
+    assert sorted(lds > 64 * 1024 for _, _, _, lds, _ in fs.FB_POLY_CASES) == [False] * 7 + [True] * 2

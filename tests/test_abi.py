@@ -1,5 +1,6 @@
 """The C-ABI shared library loads on a CPU-only box and exports every symbol include/va.h declares
-(no compute calls: there is no GPU here and no CPU fallback in the library)."""
+(no compute calls: there is no GPU here and no CPU fallback in the library); the binding's signature table, struct mirrors
+and restated constants are held to the header's text."""
 import ctypes
 import os
 import re
@@ -27,6 +28,161 @@ def test_every_declared_symbol_is_exported(lib):
     for name in declared:
         assert hasattr(lib, name), name
     assert lib.va_version() >= 1
+
+
+def _header():
+    """include/va.h without its comments."""
+    text = open(os.path.join(ROOT, "include", "va.h")).read()
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    assert "//" not in text  # the header is C89-commented throughout; a // comment would hide text from the parsers below
+    return text
+
+
+def _mirrors():
+    """The header's struct names and the ctypes mirrors of video_analytics_amd._ffi."""
+    from video_analytics_amd import _ffi
+    return {"va_tvl1_params": _ffi.Tvl1Params, "va_tvl1_options": _ffi.Tvl1Options, "va_tvl1_launch": _ffi.Tvl1Launch,
+            "va_brox_params": _ffi.BroxParams, "va_farneback_params": _ffi.FarnebackParams, "va_dtraj_params": _ffi.DenseTrajParams,
+            "va_stip_params": _ffi.StipParams, "va_gmm_params": _ffi.GmmParams, "va_kmeans_params": _ffi.KmeansParams,
+            "va_solver": _ffi.SolverParams}
+
+
+_SCALARS = {"int": ctypes.c_int, "float": ctypes.c_float, "double": ctypes.c_double, "size_t": ctypes.c_size_t,
+            "unsigned long long": ctypes.c_ulonglong}
+_RETURNS = {"int": ctypes.c_int, "size_t": ctypes.c_size_t, "void": None, "const char*": ctypes.c_char_p}
+_HANDLES = ("void", "va_ctx", "va_vgg16")
+
+
+def _prototypes(hdr):
+    """[(name, return type, [argument, ...])] of every function the header declares, in its order.  What is left of the header
+    once the preprocessor lines, the extern "C" braces, the struct and enum definitions are taken out is cut at every ';',
+    and each piece must be a prototype: one that does not parse fails here."""
+    text = re.sub(r"^[ \t]*#.*$", "", hdr, flags=re.M)
+    text = re.sub(r'extern\s+"C"\s*\{', "", text)
+    text = re.sub(r"typedef\s+struct\s+\w+\s*\{[^{}]*\}\s*\w+\s*;", "", text)
+    text = re.sub(r"typedef\s+struct\s+\w+\s+\w+\s*;", "", text)
+    text = re.sub(r"enum\s*\{[^{}]*\}\s*;", "", text)
+    out = []
+    for stmt in text.split(";"):
+        stmt = " ".join(stmt.split())
+        if stmt in ("", "}"):  # "}" closes extern "C"
+            continue
+        m = re.fullmatch(r"([a-z_ ]+\*?) ?\b(va_[a-z0-9_]+) ?\(([^()]+)\)", stmt)
+        assert m, "not a prototype: %r" % stmt
+        args = m.group(3).strip()
+        out.append((m.group(2), m.group(1).strip(), [] if args == "void" else [a.strip() for a in args.split(",")]))
+    return out
+
+
+def _allowed(arg, mirrors):
+    """The ctypes types an argument declared as ``arg`` may be bound as."""
+    stars = arg.count("*")
+    words = re.sub(r"\bconst\b|\*", " ", arg).split()
+    assert len(words) >= 2 and re.fullmatch(r"[A-Za-z_]\w*", words[-1]), "unnamed or unparsed argument %r" % arg
+    base = " ".join(words[:-1])
+    assert base in _SCALARS or base in _HANDLES or base in mirrors or base == "char", "unknown type in %r" % arg
+    if stars >= 2:
+        return (ctypes.POINTER(ctypes.c_void_p),)
+    if stars == 0:
+        return (_SCALARS[base],)  # a struct, void or char by value is a KeyError: the ABI has none
+    if base == "char":
+        return (ctypes.c_char_p,)
+    if base in _HANDLES:
+        return (ctypes.c_void_p,)
+    if base in mirrors:
+        return (ctypes.POINTER(mirrors[base]),)
+    return (ctypes.c_void_p, ctypes.POINTER(_SCALARS[base]))  # a device buffer, or a host array of exactly that scalar
+
+
+def test_signature_table_equals_the_header():
+    """Every row of _ffi.SIGNATURES against the prototype include/va.h declares: the same functions in the same order, the
+    return type, the argument count and every argument's type.  A device buffer may be bound as c_void_p whatever scalar
+    the header points it at; everything else has one legal ctypes type.  Needs no library."""
+    from video_analytics_amd import _ffi
+    hdr = _header()
+    protos = _prototypes(hdr)
+    names = [p[0] for p in protos]
+    scanned = re.findall(r"\b(va_[a-z0-9_]+)\s*\(", hdr)  # test_every_declared_symbol_is_exported's scan
+    assert names == scanned and len(set(names)) == len(names)  # no prototype is left out, none twice
+    assert list(_ffi.SIGNATURES) == names, [(a, b) for a, b in zip(_ffi.SIGNATURES, names) if a != b][:3] or (
+        set(names) ^ set(_ffi.SIGNATURES))
+    assert _ffi.EXPORTS == names
+    mirrors = _mirrors()
+    assert set(mirrors) == set(re.findall(r"typedef\s+struct\s+(\w+)\s*\{", hdr))  # every struct of the header has a mirror
+    bad = []
+    for name, ret, args in protos:
+        restype, argtypes = _ffi.SIGNATURES[name]
+        if restype is not _RETURNS[ret]:
+            bad.append("%s returns %s, bound as %s" % (name, ret, restype))
+        if len(argtypes) != len(args):
+            bad.append("%s takes %d arguments, bound with %d" % (name, len(args), len(argtypes)))
+            continue
+        for i, (arg, bound) in enumerate(zip(args, argtypes)):
+            if not any(bound is t for t in _allowed(arg, mirrors)):
+                bad.append("%s argument %d, %r, bound as %s" % (name, i, arg, bound.__name__))
+    assert not bad, "\n".join(bad)
+
+
+def _c_name(field):
+    return "lambda" if field == "lambda_" else field  # the one rename: lambda is a Python keyword
+
+
+def test_struct_mirrors_have_the_header_layout(tmp_path):
+    """sizeof, and offsetof and size of every field, of the ten structs as the C compiler lays include/va.h out, against
+    the ctypes mirrors.  A field the header lacks does not compile; a field the mirror lacks changes sizeof.  The program
+    calls no library function and links against nothing."""
+    import shutil
+    import subprocess
+    cc = shutil.which("gcc") or shutil.which("cc")
+    if cc is None:
+        pytest.skip("no C compiler")
+    mirrors = _mirrors()
+    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "va.h"', 'int main(void) {']
+    want = []
+    for cname, cls in mirrors.items():
+        lines.append('    printf("%s %%lu\\n", (unsigned long)sizeof(%s));' % (cname, cname))
+        want.append("%s %d" % (cname, ctypes.sizeof(cls)))
+        for field, _ in cls._fields_:
+            c = _c_name(field)
+            lines.append('    printf("%s.%s %%lu %%lu\\n", (unsigned long)offsetof(%s, %s), (unsigned long)sizeof(((%s*)0)->%s));'
+                         % (cname, c, cname, c, cname, c))
+            want.append("%s.%s %d %d" % (cname, c, getattr(cls, field).offset, getattr(cls, field).size))
+    lines += ['    return 0;', '}', '']
+    src, exe = tmp_path / "layout.c", tmp_path / "layout"
+    src.write_text("\n".join(lines))
+    r = subprocess.run([cc, "-std=c99", "-Wall", "-Wextra", "-pedantic", "-Werror", "-I", os.path.join(ROOT, "include"), str(src),
+                        "-o", str(exe)], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    r = subprocess.run([str(exe)], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    got = r.stdout.split("\n")[:-1]
+    assert len(got) == len(want) == sum(1 + len(cls._fields_) for cls in mirrors.values())
+    bad = ["header: %s   mirror: %s" % (g, w) for g, w in zip(got, want) if g != w]
+    assert not bad, "(name, [offset,] size)\n" + "\n".join(bad)
+
+
+def test_restated_constants_equal_the_header():
+    """Every #define and enum constant of include/va.h that _ffi restates has the header's value."""
+    from video_analytics_amd import _ffi
+    hdr = _header()
+    value = {k: int(v, 0) for k, v in re.findall(r"^[ \t]*#define[ \t]+(VA_\w+)[ \t]+(-?\w+)[ \t]*$", hdr, flags=re.M)}
+    for body in re.findall(r"enum\s*\{([^{}]*)\}", hdr):
+        for item in body.split(","):
+            k, v = item.split("=")  # every enumerator of the header states its value
+            assert k.strip() not in value
+            value[k.strip()] = int(v, 0)
+    same = ["VA_OK", "VA_ERR_INVALID", "VA_ERR_HIP", "VA_ERR_WORKSPACE", "VA_ERR_STOPPED", "VA_COLOR_JITTER_PARTIALS",
+            "VA_GMM_SOFT", "VA_GMM_HARD", "VA_BOW_NONE", "VA_BOW_L1", "VA_BOW_L2"]
+    same += [k for k in value if k.startswith("VA_OPT_")]
+    assert sorted(k for k in value if k.startswith("VA_ERR_")) == sorted(same[1:5])
+    got = {k: getattr(_ffi, k) for k in same}
+    got.update({"VA_STIP_MAX_" + k: getattr(_ffi, "STIP_MAX_" + k) for k in ("SIGMAS", "TAUS", "RADIUS")})
+    got.update({"VA_TVL1_LAUNCH_" + k.upper(): i for i, k in enumerate(_ffi.TVL1_LAUNCH_FAMILIES)})
+    assert sorted(k for k in value if k.startswith("VA_TVL1_LAUNCH_")) == sorted(k for k in got if k.startswith("VA_TVL1_LAUNCH_"))
+    bad = ["%s is %d in va.h, %r in _ffi" % (k, value[k], v) for k, v in got.items() if value[k] != v or type(v) is not int]
+    assert not bad, "\n".join(bad)
+    # every name of the module that looks like a header constant is one of the checked ones
+    assert {k for k in vars(_ffi) if k.startswith("VA_")} == set(same)
 
 
 def test_host_only_entry_points(lib):

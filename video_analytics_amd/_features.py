@@ -49,7 +49,7 @@ def workspace(nbytes, dev):
     """The uint8 workspace of ``nbytes``, what a ``va_*_workspace_bytes`` call returned: 0 means that call refused its
     arguments, and ``va_last_error`` says why."""
     if nbytes == 0:
-        raise ValueError(_ffi.lib().va_last_error().decode("utf-8", "replace"))
+        raise ValueError(_ffi.last_error())
     return torch.empty((nbytes,), dtype=torch.uint8, device=dev)
 
 

@@ -81,7 +81,7 @@ def _flow(m, frames, params, ws_slot, out, over):
         args += (ctypes.byref(opt) if opt is not None else None,)
     nbytes = getattr(L, m.workspace_bytes)(W, H, S, F, *args)
     if nbytes == 0:
-        raise ValueError(L.va_last_error().decode())
+        raise ValueError(_ffi.last_error())
     ws = _workspace(nbytes, frames.device, ws_slot)
     if out is None:
         flow = torch.empty((S * (F - 1), 2, H, W), dtype=torch.float32, device=frames.device)
@@ -742,7 +742,7 @@ def launch_plan(w, h, n_seq, frames_per_seq, params=None, **over):
     L = _ffi.lib()
     n = L.va_tvl1_launch_plan(w, h, n_seq, frames_per_seq, ctypes.byref(p), ref, None, 0)
     if n < 0:
-        raise ValueError(L.va_last_error().decode())
+        raise ValueError(_ffi.last_error())
     recs = (_ffi.Tvl1Launch * max(n, 1))()
     if L.va_tvl1_launch_plan(w, h, n_seq, frames_per_seq, ctypes.byref(p), ref, recs, n) != n:
         raise RuntimeError("va_tvl1_launch_plan: two runs of one plan differ")

@@ -1420,6 +1420,83 @@ int va_bow_histograms(va_ctx* ctx, const void* labels, int n, const void* segmen
 int va_bow_encode(va_ctx* ctx, const void* x, int n, int d, const void* centres, int k, const void* segments, int n_segments,
                   int norm, void* out, void* workspace, size_t workspace_bytes, void* stream);
 
+/*
+ * HMM action segmentation (csrc/hmm.hip): the Gaussian emission table, batched Viterbi decoding and the
+ * Baum-Welch statistics of the modelled project's Sheet04 (Kuehne, Arslan and Serre, CVPR 2014; Sheet04.py:242-252, :300-420
+ * and :520-560).  All arithmetic is
+ * float64 and there are no atomics.
+ *
+ * A model is flat, in CSR form by predecessor: emit int32 [N] (the state's Gaussian), pred_ptr int32 [N + 1], pred_idx
+ * int32 [E] (ascending within a state), pred_logp float64 [E], log_pi and log_final float64 [N]; -inf is legal everywhere,
+ * NaN nowhere.  1 <= N <= 1024, any in-degree.  The models of a call are concatenated: state_ptr int32 [n_models + 1] cuts
+ * emit, log_pi and log_final, edge_ptr int32 [n_models + 1] cuts pred_idx and pred_logp, and the pred_ptr rows (N + 1 each,
+ * counting from 0 within the model) follow one another, so model m's starts at state_ptr[m] + m.  The sequences are the
+ * rows seq_ptr[s] .. seq_ptr[s + 1] - 1 of logb (seq_ptr: int32 [n_seqs + 1]).  Every array is a DEVICE array.
+ *
+ * va_hmm_wave_states, va_hmm_wave_edges: a model of at most that many states (64) and edges (512) runs in the single-wave
+ * form of the kernel, every other one in the workgroup form.  va_hmm_backtrack_block: the frames of backpointers (16) that
+ * pass through LDS per step of the backtrack.  The results do not depend on any of the three.
+ */
+int va_hmm_wave_states(void);
+int va_hmm_wave_edges(void);
+int va_hmm_backtrack_block(void);
+/* logb float64 [t_total][g] = consts[g] - 0.5 q, q = the sum over the columns in ascending order of
+ * ((x - mean) (x - mean)) inv_var, one rounding per operation.  x: float32 (x_is_f64 = 0, widened exactly) or float64
+ * [t_total][d], 1 <= d <= 512; means, inv_var float64 [g][d]; consts float64 [g] (the host's
+ * -0.5 (d log 2 pi + sum log var)). */
+int va_hmm_emissions(va_ctx* ctx, const void* x, int x_is_f64, int t_total, int d, const void* means, const void* inv_var,
+                     const void* consts, int g, void* logb, void* stream);
+/* jobs int32 [n_jobs][3]: (sequence, model, want_path).  delta_0[j] = log_pi[j] + logb[0][emit j]; delta_t[j] = max_i
+ * (delta_{t-1}[i] + pred_logp[i -> j]) + logb[t][emit j], a predecessor winning only by > over the running best in ascending
+ * pred_idx; score float64 [n_jobs] = max_j (delta_{T-1}[j] + log_final[j]), the lowest j on ties.  status int32 [n_jobs]:
+ * 0 ok; 1 no path of finite score (score -inf, path -1); 2 a NaN reached the recursion (score NaN, path -1); 3 the job's
+ * indices leave the arrays of the call (score NaN, nothing else written).  A job with want_path = 1 writes its states to
+ * path[path_off[job] ..] (int32, T entries; path_off, bp_off: int64 [n_jobs], read only for such jobs) and keeps its
+ * backpointers, uint16 [T][N], at element bp_off[job] of the workspace; path_elems and bp_elems are the sizes the offsets
+ * address, and a workspace below 2 bp_elems bytes is VA_ERR_WORKSPACE with nothing written.  A job with want_path = 0
+ * needs no workspace. */
+int va_hmm_viterbi(va_ctx* ctx, const void* logb, int t_total, int g, const void* seq_ptr, int n_seqs, const void* state_ptr,
+                   const void* edge_ptr, int n_models, int n_states_total, int n_edges_total, const void* emit,
+                   const void* pred_ptr, const void* pred_idx, const void* pred_logp, const void* log_pi, const void* log_final,
+                   const void* jobs, int n_jobs, const void* path_off, const void* bp_off, void* score, void* status, void* path,
+                   size_t path_elems, size_t bp_elems, void* workspace, size_t workspace_bytes, void* stream);
+/*
+ * The scaled forward-backward pass of the same jobs (the jobs' third column is not read).  With
+ * b_t[j] = exp(logb[t][emit j] - m_t), m_t the maximum over the model's states, and a, pi, f the exponentials of pred_logp,
+ * log_pi and log_final:
+ *   alpha_0[j] = pi[j] b_0[j] / c_0,  alpha_t[j] = b_t[j] (sum_i alpha_{t-1}[i] a[i -> j]) / c_t   (predecessors ascending;
+ *   c_t: the frame's sum of the numerators), c_T = sum_j alpha_{T-1}[j] f[j], beta_{T-1}[j] = f[j] / c_T,
+ *   beta_t[i] = sum_j a[i -> j] ((b_{t+1}[j] beta_{t+1}[j]) / c_{t+1})   (successors ascending),
+ *   gamma_t = alpha_t beta_t,  xi[e] = sum_t (alpha_t[i] a[e]) ((b_{t+1}[j] beta_{t+1}[j]) / c_{t+1})  (t descending),
+ *   loglik = sum_t (log c_t + m_t) + log c_T   (t ascending).
+ * A frame's sum runs over each wave's lanes as an xor butterfly (offsets 32 .. 1) and then over the waves in ascending
+ * order.  succ_ptr (rows laid out like pred_ptr's), succ_idx and succ_edge int32 [E] list every state's successors in
+ * ascending order and each edge's place in the model's pred_idx.  Job k writes gamma float64 [T][N] at gamma_off[k], xi
+ * float64 [E] at xi_off[k] and uses 2 T doubles of the workspace at mc_off[k] (all int64 [n_jobs], in elements; gamma_elems,
+ * xi_elems and mc_elems are the sizes they address).  status: 0 ok; 1 the likelihood is zero -- a frame whose states all
+ * have logb -inf, or a c_t that is 0 -- with gamma and xi zeros and loglik -inf; 2 a NaN or +inf in the job's logb, or a
+ * c_t that is not finite, with gamma and xi zeros and loglik NaN; 3 as va_hmm_viterbi's.  workspace:
+ * va_hmm_fb_workspace_bytes (0 and va_last_error() for sizes out of range), 256-byte aligned; too small a one is
+ * VA_ERR_WORKSPACE with nothing written.
+ */
+size_t va_hmm_fb_workspace_bytes(int n_states_total, int n_edges_total, size_t mc_elems);
+int va_hmm_forward_backward(va_ctx* ctx, const void* logb, int t_total, int g, const void* seq_ptr, int n_seqs,
+                            const void* state_ptr, const void* edge_ptr, int n_models, int n_states_total, int n_edges_total,
+                            const void* emit, const void* pred_ptr, const void* pred_idx, const void* pred_logp, const void* log_pi,
+                            const void* log_final, const void* succ_ptr, const void* succ_idx, const void* succ_edge,
+                            const void* jobs, int n_jobs, const void* gamma_off, const void* xi_off, const void* mc_off, void* gamma,
+                            size_t gamma_elems, void* xi, size_t xi_elems, size_t mc_elems, void* loglik, void* status,
+                            void* workspace, size_t workspace_bytes, void* stream);
+/* stats float64 [g][1 + 2 d] = [ sum w | sum w x | sum w (x x) ] per Gaussian, x as va_hmm_emissions'.  mode 0: w is gamma;
+ * Gaussian k takes the contributions contrib_ptr[k] .. contrib_ptr[k + 1] - 1 (int32 [g + 1]), each a row (first frame,
+ * frames T, states N, state j) of contrib int32 [n_contrib][4] whose weights are gamma[contrib_off[c] + t N + j] (int64
+ * [n_contrib]).  mode 1: w = 1 on the frames t with align[t] = k (int32 [t_total]; -1 for none).  One wave of four adds the
+ * frames t = v, v + 4, ... of each contribution in ascending order, the contributions in ascending order; the result is
+ * ((p0 + p1) + p2) + p3.  A contribution that leaves the arrays turns its Gaussian's sum w into NaN. */
+int va_hmm_gauss_stats(va_ctx* ctx, const void* x, int x_is_f64, int t_total, int d, int g, int mode, const void* gamma,
+                       size_t gamma_elems, const void* contrib_ptr, const void* contrib, const void* contrib_off, int n_contrib,
+                       const void* align, void* stats, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

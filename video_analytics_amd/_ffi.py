@@ -210,6 +210,7 @@ class GmmParams(ctypes.Structure):
 
 
 VA_BOW_NONE, VA_BOW_L1, VA_BOW_L2 = 0, 1, 2  # include/va.h: va_bow_histograms' norm
+HMM_MAX_STATES, HMM_MAX_DIM = 1024, 512  # include/va.h: the limits of va_hmm_viterbi's models and va_hmm_emissions' columns
 
 
 class KmeansParams(ctypes.Structure):
@@ -383,6 +384,15 @@ SIGNATURES = {
     "va_kmeans_seed": (ci, [vp, vp, ci, ci, vp, ci, vp, vp, vp, vp, sz, vp]),
     "va_bow_histograms": (ci, [vp, vp, ci, vp, ci, ci, ci, vp, vp]),
     "va_bow_encode": (ci, [vp, vp, ci, ci, vp, ci, vp, ci, ci, vp, vp, sz, vp]),
+    "va_hmm_wave_states": (ci, []),
+    "va_hmm_wave_edges": (ci, []),
+    "va_hmm_backtrack_block": (ci, []),
+    "va_hmm_emissions": (ci, [vp, vp, ci, ci, ci, vp, vp, vp, ci, vp, vp]),
+    "va_hmm_viterbi": (ci, [vp, vp, ci, ci, vp, ci, vp, vp, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, ci, vp, vp, vp, vp, vp, sz, sz, vp, sz, vp]),
+    "va_hmm_fb_workspace_bytes": (sz, [ci, ci, sz]),
+    "va_hmm_forward_backward": (ci, [vp, vp, ci, ci, vp, ci, vp, vp, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, vp, vp, vp, vp, sz, vp,
+                                     sz, sz, vp, vp, vp, sz, vp]),
+    "va_hmm_gauss_stats": (ci, [vp, vp, ci, ci, ci, ci, ci, vp, sz, vp, vp, vp, ci, vp, vp, vp]),
 }
 
 # every symbol include/va.h declares (tests check that the library exports exactly these)

@@ -1082,7 +1082,9 @@ int va_meter_average(va_ctx* ctx, const void* sums, const void* counts, int n_sl
  * intercept f64 [n_class_rows] (sklearn's coef_ / intercept_; n_class_rows == 1 for a binary problem)
  * -> scores f64 [n][n_class_rows] = x coef^T + intercept (sum over dim in ascending order, double
  * multiply then add), pred i32 [n] = index into classes_: arg-max (first maximum), or score > 0 for
- * the binary case.  The model is a fitted LinearSVC's or va_linear_svm_fit's.
+ * the binary case.  The model is a fitted LinearSVC's or va_linear_svm_fit's; with x the test rows of a Gram matrix and coef
+ * va_kernel_svm_fit's dual_coef it is the kernel SVM's prediction.  1 <= dim <= 65536 (up to 8192 the row of x is staged in
+ * LDS, above that it is read in place: the same operations in the same order).
  */
 int va_linear_svm_predict(va_ctx* ctx, const void* x, int n, int dim, const void* coef,
                           const void* intercept, int n_class_rows, void* scores, void* pred,
@@ -1496,6 +1498,93 @@ int va_hmm_forward_backward(va_ctx* ctx, const void* logb, int t_total, int g, c
 int va_hmm_gauss_stats(va_ctx* ctx, const void* x, int x_is_f64, int t_total, int d, int g, int mode, const void* gamma,
                        size_t gamma_elems, const void* contrib_ptr, const void* contrib, const void* contrib_off, int n_contrib,
                        const void* align, void* stats, void* stream);
+
+/* --------------------------------------------------------------- kernel SVMs --- */
+
+/*
+ * Gram matrices for the kernel SVM.  x [m][d] and y [n][d] are DEVICE float32 (x_is_f64 = 0) or float64 (1) rows, widened as
+ * they are read; out is float64 [m][n].  y == NULL is the symmetric form: n is ignored, out is [m][m], only the 64 x 64 tiles
+ * on and above the diagonal are computed and every result is also written to its mirror place, so that out is bitwise
+ * symmetric and equal to the call on (x, x).  1 <= m, n <= 2^20, 1 <= d <= 65536, else VA_ERR_INVALID before any launch.
+ *
+ * va_chi2_distance: out[i][j] = sum_k (x[i][k] - y[j][k])^2 / (x[i][k] + y[j][k]) over the columns c0 <= k < c1 in ascending
+ * order (0 <= c0 < c1 <= d), one float64 accumulator per result, every operation IEEE (no contraction); a term whose
+ * denominator is 0 counts 0 (sklearn's chi2_kernel convention, no factor 1/2).  The diagonal of the symmetric form is exactly
+ * 0.  chunk: the columns staged in LDS at a time, 1 .. 32, 0 for the library's 16; no value changes a result.
+ *
+ * va_linear_gram: out[i][j] = sum_k x[i][k] y[j][k] on v_mfma_f64_16x16x4_f64, k in a fixed order.
+ */
+#define VA_CHI2_MAX_CHANNELS 16
+int va_chi2_distance(va_ctx* ctx, const void* x, const void* y, int m, int n, int d, int c0, int c1, int x_is_f64, int chunk,
+                     void* out, void* stream);
+int va_linear_gram(va_ctx* ctx, const void* x, const void* y, int m, int n, int d, int x_is_f64, void* out, void* stream);
+/* mean float64 [1] = the mean of the strict upper triangle of dist float64 [n][n], 2 <= n <= 2^20 (Laptev's and Wang's
+ * normaliser A of a chi-square channel): rowsum float64 [n] (scratch) takes each row's sum over j > i, lane l of 256 adding
+ * j = i + 1 + l, i + 1 + l + 256, ... in ascending order, then an xor butterfly; the rows are added the same way.  No atomics. */
+int va_upper_mean(va_ctx* ctx, const void* dist, int n, void* rowsum, void* mean, void* stream);
+/* out float64 [count] = exp(-(weights[0] dist[0] + weights[1] dist[1] + ...)), elementwise over n_channels (1 ..
+ * VA_CHI2_MAX_CHANNELS) DEVICE float64 arrays of `count` elements, the products added in channel order; dist and weights are
+ * HOST arrays, the weights finite and >= 0, 1 <= count <= 2^38.  Distances that are exactly 0 (a symmetric diagonal) give
+ * exactly 1. */
+int va_chi2_combine(va_ctx* ctx, const void* const* dist, const double* weights, int n_channels, size_t count, void* out,
+                    void* stream);
+
+/*
+ * The one-vs-rest kernel SVM fit over a Gram matrix: va_linear_svm_fit's model, L2-regularised squared
+ * hinge with the regularised bias s = intercept_scaling, posed in the dual.  With Kt = k + s^2 and H = Kt + I / (2C), class row
+ * r (y_i = +1 where y[i] is the row's class, -1 elsewhere) solves
+ *     min over alpha >= 0 of  1/2 alpha^T ((y y^T) o H) alpha - e^T alpha,
+ * dual_coef[r][i] = y_i alpha_i, intercept[r] = s^2 sum_i dual_coef[r][i]; the score of a row x is sum_i dual_coef[r][i]
+ * k(x_i, x) + intercept[r], which is va_linear_svm_predict on the test rows of the Gram matrix.  With k = X X^T the model
+ * dual_coef [X, s] is va_linear_svm_fit's.  rows = n_classes == 2 ? 1 : n_classes, as there.
+ *
+ * k float64 [n][n] symmetric positive semi-definite (the caller's promise; only the finite, symmetric part is checked by the
+ * Python layer), y i32 [n] with values in [0, n_classes).  The solver is a Newton-CG on the primal written in beta (S107):
+ * every outer step judges the feasible candidate by the dual's projected gradient pg and a row stops, and is frozen, when
+ * |pg|_2 <= tol sqrt(n).  The call enqueues outer_iters outer steps on the caller's stream and then writes dual_coef f64
+ * [rows][n] (alpha >= 0 exactly, zeros exact), intercept f64 [rows] and stats f64 [rows][5] = the dual objective, |pg|, the
+ * support vectors, the outer steps taken, the CG steps taken; it allocates nothing and does not synchronise.  restart as
+ * va_linear_svm_fit's.  Every product H V serves all rows at once on the float64 MFMA; no atomics: two fits agree bit for bit.
+ * workspace: va_kernel_svm_fit_workspace_bytes(n, rows) bytes, 8-byte aligned (too small: VA_ERR_WORKSPACE).  2 <= n <=
+ * 16384, 2 <= n_classes <= 1024, C > 0, tol > 0, intercept_scaling >= 0, all finite, 0 <= outer_iters <= 1000, else
+ * VA_ERR_INVALID before anything is launched.  The size query answers 0 and sets va_last_error for sizes out of range
+ * (n_class_rows is 1 or 3 .. 1024).
+ */
+size_t va_kernel_svm_fit_workspace_bytes(int n, int n_class_rows);
+int va_kernel_svm_fit(va_ctx* ctx, const void* k, const void* y, int n, int n_classes, double C, double intercept_scaling,
+                      double tol, int outer_iters, int restart, void* dual_coef, void* intercept, void* stats,
+                      void* workspace, size_t workspace_bytes, void* stream);
+/*
+ * The stages of va_kernel_svm_fit one at a time, for stage-by-stage tests; the fit's own loop is written over the same helpers.
+ *
+ * va_kernel_svm_fit_layout (host only): offsets: HOST size_t[VA_KSVM_FIT_FIELDS], the byte offsets into the workspace of
+ *   B HB BC Z X R P HP Q   f64 [rows][n]   iterate beta, H B, the feasible candidate, H BC, the CG's solution (then the step
+ *                                          S = X - B), CG residual, CG direction, H P on the face, H S
+ *   free                   i32 [rows][n]   the row's face: 1 where 1 - y f > 0
+ *   q pgn nsv steps rr cgtol cgs ref   f64 [rows]   dual objective, |pg|, support vectors, outer steps, the CG's |R|^2 and
+ *                                          stop threshold, CG steps, the size of the Newton system's right-hand side
+ *   live notdone tight     i32 [rows]      the row's CG is running; the row has not met the stop rule; its last step was refused
+ * in this order, each on a 256-byte boundary.  Returns the total, equal to va_kernel_svm_fit_workspace_bytes; sizes out of
+ * range, offsets == NULL or count != VA_KSVM_FIT_FIELDS answer 0 and set va_last_error.
+ *
+ * va_kernel_svm_fit_phase: the arguments and checks of va_kernel_svm_fit.  It reads and writes the state in the workspace:
+ *   VA_KSVM_PHASE_INIT         k_ksvm_init: every vector and scalar 0, notdone 1
+ *   VA_KSVM_PHASE_EVAL         k_ksvm_prod (HB = H B), k_ksvm_face, k_ksvm_prod (Z = H BC), k_ksvm_grad: the face, the
+ *                              candidate, pg, the stop rule, and the start of the CG (X = BC, R = P = y - Z on the face)
+ *   VA_KSVM_PHASE_CG           `count` (1 .. 100) rounds of k_ksvm_prod<masked> (HP = H P on the face) and k_ksvm_cg
+ *   VA_KSVM_PHASE_LINE_SEARCH  k_ksvm_dir (S = X - B), k_ksvm_prod (Q = H S), k_ksvm_ls
+ * `count` is read by the CG phase only.  One outer step of the fit is CG with count 100, LINE_SEARCH, EVAL; restart = 1 is
+ * INIT, EVAL.
+ */
+#define VA_KSVM_FIT_FIELDS 21
+#define VA_KSVM_PHASE_INIT 0
+#define VA_KSVM_PHASE_EVAL 1
+#define VA_KSVM_PHASE_CG 2
+#define VA_KSVM_PHASE_LINE_SEARCH 3
+size_t va_kernel_svm_fit_layout(int n, int n_class_rows, size_t* offsets, int count);
+int va_kernel_svm_fit_phase(va_ctx* ctx, const void* k, const void* y, int n, int n_classes, double C,
+                            double intercept_scaling, double tol, int phase, int count, void* workspace,
+                            size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -213,6 +213,14 @@ VA_BOW_NONE, VA_BOW_L1, VA_BOW_L2 = 0, 1, 2  # include/va.h: va_bow_histograms' 
 HMM_MAX_STATES, HMM_MAX_DIM = 1024, 512  # include/va.h: the limits of va_hmm_viterbi's models and va_hmm_emissions' columns
 
 
+# include/va.h: the channels of va_chi2_combine, the fields of va_kernel_svm_fit_layout in its order, the phases of
+# va_kernel_svm_fit_phase
+CHI2_MAX_CHANNELS = 16
+KSVM_FIT_FIELDS = ("B", "HB", "BC", "Z", "X", "R", "P", "HP", "Q", "free", "q", "pgn", "nsv", "steps", "rr", "cgtol", "cgs", "ref",
+                   "live", "notdone", "tight")
+KSVM_PHASES = ("init", "eval", "cg", "line_search")
+
+
 class KmeansParams(ctypes.Structure):
     """Mirror of ``va_kmeans_params`` (include/va.h)."""
     _fields_ = [
@@ -393,6 +401,14 @@ SIGNATURES = {
     "va_hmm_forward_backward": (ci, [vp, vp, ci, ci, vp, ci, vp, vp, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, vp, vp, vp, vp, sz, vp,
                                      sz, sz, vp, vp, vp, sz, vp]),
     "va_hmm_gauss_stats": (ci, [vp, vp, ci, ci, ci, ci, ci, vp, sz, vp, vp, vp, ci, vp, vp, vp]),
+    "va_chi2_distance": (ci, [vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, vp, vp]),
+    "va_linear_gram": (ci, [vp, vp, vp, ci, ci, ci, ci, vp, vp]),
+    "va_upper_mean": (ci, [vp, vp, ci, vp, vp, vp]),
+    "va_chi2_combine": (ci, [vp, pp, pd, ci, sz, vp, vp]),
+    "va_kernel_svm_fit_workspace_bytes": (sz, [ci, ci]),
+    "va_kernel_svm_fit": (ci, [vp, vp, vp, ci, ci, cd, cd, cd, ci, ci, vp, vp, vp, vp, sz, vp]),
+    "va_kernel_svm_fit_layout": (sz, [ci, ci, psz, ci]),
+    "va_kernel_svm_fit_phase": (ci, [vp, vp, vp, ci, ci, cd, cd, cd, ci, ci, vp, sz, vp]),
 }
 
 # every symbol include/va.h declares (tests check that the library exports exactly these)

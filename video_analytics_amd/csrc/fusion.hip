@@ -35,17 +35,21 @@ __global__ void k_meter_average(const float* __restrict__ sums, const int* __res
 
 // scores[n][c] = sum_k x[n][k] * coef[c][k] (k ascending, IEEE double multiply then add: -ffp-contract=off)
 // + intercept[c].  One workgroup per row n: the row is staged in LDS, thread c walks coef row c.
+template <bool STAGED>
 __global__ void k_svm_scores(const double* __restrict__ x, int dim, const double* __restrict__ coef, const double* __restrict__ intercept,
                              int C, double* __restrict__ scores)
 {
     extern __shared__ double sx[];
     const int n = blockIdx.x;
-    for (int k = threadIdx.x; k < dim; k += blockDim.x) sx[k] = x[(size_t)n * dim + k];
-    __syncthreads();
+    const double* __restrict__ xr = x + (size_t)n * dim;  // !STAGED (dim > 8192 doubles of LDS): the row is read in place
+    if (STAGED) {
+        for (int k = threadIdx.x; k < dim; k += blockDim.x) sx[k] = xr[k];
+        __syncthreads();
+    }
     for (int c = threadIdx.x; c < C; c += blockDim.x) {
         const double* w = coef + (size_t)c * dim;
         double acc = 0.0;
-        for (int k = 0; k < dim; ++k) acc = acc + sx[k] * w[k];
+        for (int k = 0; k < dim; ++k) acc = acc + (STAGED ? sx[k] : xr[k]) * w[k];
         scores[(size_t)n * C + c] = acc + intercept[c];
     }
 }
@@ -283,10 +287,14 @@ extern "C" int va_linear_svm_predict(va_ctx* ctx, const void* x, int n, int dim,
     VA_CHECK_ARG(ctx != nullptr, "va_linear_svm_predict: ctx is NULL");
     VA_USE_DEVICE(ctx);
     VA_CHECK_ARG(x && coef && intercept && scores && pred, "va_linear_svm_predict: NULL pointer");
-    VA_CHECK_ARG(n >= 1 && dim >= 1 && dim <= 8192 && n_class_rows >= 1,
-                 "va_linear_svm_predict: need n >= 1, 1 <= dim <= 8192, n_class_rows >= 1 (got %d, %d, %d)", n, dim, n_class_rows);
-    k_svm_scores<<<n, 128, (size_t)dim * sizeof(double), (hipStream_t)stream>>>((const double*)x, dim, (const double*)coef, (const double*)intercept,
-                                                                               n_class_rows, (double*)scores);
+    VA_CHECK_ARG(n >= 1 && dim >= 1 && dim <= 65536 && n_class_rows >= 1,
+                 "va_linear_svm_predict: need n >= 1, 1 <= dim <= 65536, n_class_rows >= 1 (got %d, %d, %d)", n, dim, n_class_rows);
+    if (dim <= 8192)  // 64 KB of LDS hold 8192 doubles
+        k_svm_scores<true><<<n, 128, (size_t)dim * sizeof(double), (hipStream_t)stream>>>((const double*)x, dim, (const double*)coef,
+                                                                                         (const double*)intercept, n_class_rows, (double*)scores);
+    else
+        k_svm_scores<false><<<n, 128, 0, (hipStream_t)stream>>>((const double*)x, dim, (const double*)coef, (const double*)intercept,
+                                                                n_class_rows, (double*)scores);
     VA_LAUNCH_CHECK();
     k_svm_argmax<<<va_cdiv(n, 256), 256, 0, (hipStream_t)stream>>>((const double*)scores, n, n_class_rows, (int*)pred);
     VA_LAUNCH_CHECK();

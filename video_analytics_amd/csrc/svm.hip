@@ -20,13 +20,6 @@ constexpr double kSvmArmijo = 1e-4;
 
 enum { SVM_EVAL = 0, SVM_CG = 1, SVM_LS = 2 };
 
-// True when any of the (at most 64) class rows j0 .. j0+63 has its flag set; the same answer in every lane and wave.
-__device__ __forceinline__ bool tile_is_live(const int* __restrict__ flags, int j0, int c, int lane)
-{
-    const int j = j0 + lane;
-    return __any(j < c ? flags[j] : 0) != 0;
-}
-
 // out[i][j] = sum_k Xh[i][k] P[j][k], Xh = [X, s]: a workgroup computes 64 rows x 64 class rows, wave w rows 16w .. 16w+15.
 // k is walked 16 at a time; lane (q = lane>>4) reads the four consecutive values k0 + 4q .. k0 + 4q + 3 of its row of X and
 // of P and feeds value s to MFMA number s of the group (both operands agree on the assignment, so the products are those of
@@ -44,7 +37,7 @@ __global__ void __launch_bounds__(256) k_svm_fwd(const double* __restrict__ X, c
     __shared__ double red[4][64];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, q = lane >> 4, r16 = lane & 15;
     const int c0 = blockIdx.y * 64;
-    if (!tile_is_live(flags, c0, c, lane)) return;
+    if (!va_tile_is_live(flags, c0, c, lane)) return;
     const int D = d + 1;
     const int rowbase = blockIdx.x * 64 + wave * 16;
     const double* __restrict__ xr = X + (size_t)min(rowbase + r16, n - 1) * d;
@@ -131,7 +124,7 @@ __global__ void __launch_bounds__(256) k_svm_xtu(const double* __restrict__ X, i
     const int D = d + 1;
     const int kbase = blockIdx.z * 64 + wave * 16;
     if (kbase >= D) return;
-    if (!tile_is_live(flags, j0, c, lane)) return;
+    if (!va_tile_is_live(flags, j0, c, lane)) return;
     const int k = kbase + r16;
     const int i_beg = blockIdx.x * kSvmChunkRows, i_end = min(i_beg + kSvmChunkRows, n);
     int jl[4];

@@ -1,4 +1,4 @@
-// Device helpers the classical feature chains share (svm.hip, fisher.hip, codebook.hip, dtraj.hip, stip.hip): one copy of every
+// Device helpers the classical feature chains share (svm.hip, ksvm.hip, fisher.hip, codebook.hip, dtraj.hip, stip.hip): one copy of every
 // sum whose written order reaches a result, of the scans, and of the orientation votes.
 #pragma once
 #include "va_internal.h"
@@ -27,6 +27,14 @@ __device__ __forceinline__ double va_strided_sum(const double* __restrict__ p, i
     double acc = p[at];
     for (int i = 1; i < n; ++i) acc = acc + p[(size_t)i * stride + at];
     return acc;
+}
+
+// True when any of the (at most 64) class rows j0 .. j0+63 has its flag set; the same answer in every lane and wave (svm.hip
+// and ksvm.hip skip the tiles of finished rows with it).
+__device__ __forceinline__ bool va_tile_is_live(const int* __restrict__ flags, int j0, int c, int lane)
+{
+    const int j = j0 + lane;
+    return __any(j < c ? flags[j] : 0) != 0;
 }
 
 // ---- integer scans (sums mod 2^32: the order is free)

@@ -15,6 +15,7 @@ from . import _features
 from . import _ffi
 from . import codebook as vcodebook
 from . import fusion
+from . import ksvm
 
 # what the outputs sized for the proven bound may take when max_points is None
 MEMORY_BUDGET_BYTES = 8 << 30
@@ -70,19 +71,25 @@ def space_time_interest_points(gray, flow=None, params=None, flow_params=None, m
 
 class StipClassifier(object):
     """Sheet01's ``main()`` after the extraction (Sheet01.py:259-277, 379-390): a k-means codebook of all training
-    descriptors, one histogram of words per video, a linear SVM on those.
+    descriptors, one histogram of words per video, a linear SVM on those -- or, with ``svm="chi2"``, the chi-square kernel SVM
+    that Laptev's interest points are evaluated with (``ksvm``; ``norm="l1"`` is its usual companion).
 
     ``descs_per_video``: a list of CUDA float32 ``[n_i, d]`` tensors, one per video
     (``space_time_interest_points(...)["desc"]``); a video without points (``n_i = 0``) is legal and gets a zero histogram."""
 
     def __init__(self):
-        self.codebook = self.coef = self.intercept = self.classes = None
+        self.codebook = self.coef = self.intercept = self.classes = self.kernel_svm = None
         self.norm = "l2"
 
-    def fit(self, descs_per_video, labels, n_words=256, norm="l2", **kmeans_kw):
+    def fit(self, descs_per_video, labels, n_words=256, norm="l2", svm="linear", C=1.0, **kmeans_kw):
         """``codebook.kmeans_fit`` with ``n_words`` clusters (Sheet01.py:262) and ``kmeans_kw``, histograms with ``norm``
-        (``"l2"``: Sheet01's ``normalize``), ``fusion.linear_svm_fit``.  -> self."""
+        (``"l2"``: Sheet01's ``normalize``), then ``svm="linear"``: ``fusion.linear_svm_fit`` (Sheet01's classifier), or
+        ``svm="chi2"``: ``ksvm.KernelSvm("chi2", C)`` on the histograms as one channel normalised by its mean distance, which
+        keeps the training histograms, the scale and ``dual_coef`` (``C`` is read by this route only; ``norm="l1"`` is the
+        usual companion of the chi-square kernel).  -> self."""
         who = "StipClassifier.fit"
+        if svm not in ("linear", "chi2"):
+            raise ValueError("%s: svm must be 'linear' or 'chi2', got %r" % (who, svm))
         videos, segments = _features.check_videos(descs_per_video, who)
         if len(labels) != len(videos):
             raise ValueError("%s: %d videos but %d labels" % (who, len(videos), len(labels)))
@@ -91,7 +98,13 @@ class StipClassifier(object):
         rows = torch.cat(videos, 0)
         self.codebook = vcodebook.kmeans_fit(rows, n_words, **kmeans_kw)
         self.norm = norm
-        self.coef, self.intercept, self.classes = fusion.linear_svm_fit(self.codebook.histograms(rows, segments, norm), labels)
+        hist = self.codebook.histograms(rows, segments, norm)
+        if svm == "linear":
+            self.kernel_svm = None
+            self.coef, self.intercept, self.classes = fusion.linear_svm_fit(hist, labels)
+        else:
+            self.kernel_svm = ksvm.KernelSvm("chi2", C).fit(hist, labels)
+            self.coef, self.intercept, self.classes = None, self.kernel_svm.intercept, self.kernel_svm.classes
         return self
 
     def encode(self, descs_per_video):
@@ -103,19 +116,27 @@ class StipClassifier(object):
         return self.codebook.histograms(torch.cat(videos, 0), segments, self.norm)
 
     def predict(self, descs_per_video):
-        """-> the predicted labels, one per video (``fusion.linear_svm_predict`` on the histograms)."""
-        if self.coef is None:
+        """-> the predicted labels, one per video (``fusion.linear_svm_predict`` on the histograms, or on their chi-square
+        kernel against the training histograms)."""
+        if self.classes is None:
             raise ValueError("StipClassifier.predict: the model is not fitted")
         h = self.encode(descs_per_video)
+        if self.kernel_svm is not None:
+            return self.kernel_svm.predict(h)
         return fusion.linear_svm_predict(h.double().cpu().numpy(), self.coef, self.intercept, self.classes, device=h.device.index)
 
     def save(self, path):
-        if self.coef is None:
+        if self.classes is None:
             raise ValueError("StipClassifier.save: the model is not fitted")
         cb = self.codebook
+        if self.kernel_svm is None:
+            model = dict(coef=self.coef, intercept=self.intercept, classes=self.classes)
+        else:  # the kernel model's arrays under a ksvm_ prefix, beside the keys every file has
+            model = dict(intercept=self.intercept, classes=self.classes)
+            model.update(("ksvm_" + k, v) for k, v in self.kernel_svm.state().items())
         with open(path, "wb") as f:
             np.savez(f, centres=cb.centres, inertia=np.float64(cb.inertia), n_iter=np.int64(cb.n_iter), converged=np.bool_(cb.converged),
-                     counts=cb.counts, norm=np.str_(self.norm), coef=self.coef, intercept=self.intercept, classes=self.classes)
+                     counts=cb.counts, norm=np.str_(self.norm), **model)
 
     @classmethod
     def load(cls, path):
@@ -123,5 +144,9 @@ class StipClassifier(object):
         with np.load(path) as z:
             m.codebook = vcodebook.Codebook(z["centres"], float(z["inertia"]), int(z["n_iter"]), bool(z["converged"]), z["counts"])
             m.norm = str(z["norm"])
-            m.coef, m.intercept, m.classes = z["coef"], z["intercept"], z["classes"]
+            m.intercept, m.classes = z["intercept"], z["classes"]
+            if "ksvm_kernel" in z.files:
+                m.kernel_svm = ksvm.KernelSvm.from_state(z, prefix="ksvm_")
+            else:
+                m.coef = z["coef"]
         return m

@@ -18,6 +18,7 @@ from . import _ffi
 from . import fisher
 from . import flow as vflow
 from . import fusion
+from . import ksvm
 
 REJECTED = ("left_frame", "static", "erratic", "jump", "unfinished")
 # what the outputs sized for the proven bound cells * (T - length) may take when max_trajectories is None
@@ -80,9 +81,10 @@ class TrajectoryClassifier(object):
     mixture fitted to the reduced rows, one Fisher vector per video, a linear SVM on those.
 
     ``descs_per_video``: a list of CUDA float32 ``[n_i, d]`` tensors, one per video (``dense_trajectories(...)["desc"]``); a
-    video with no trajectories (``n_i = 0``) is legal and gets a zero vector.  The Fisher vector's length
-    ``n_gmm (1 + 2 n_components)`` must not exceed 8192, the widest problem ``fusion.linear_svm_fit`` takes; ``encode`` has no
-    such limit (Sheet02's 64 x 256 gives 33,024)."""
+    video with no trajectories (``n_i = 0``) is legal and gets a zero vector.  With the default ``svm="primal"`` the Fisher
+    vector's length ``n_gmm (1 + 2 n_components)`` must not exceed 8192, the widest problem ``fusion.linear_svm_fit`` takes;
+    ``svm="dual"`` fits the same model over the videos' linear Gram matrix (``ksvm``) and has no such limit, and neither has
+    ``encode`` (Sheet02's 64 x 256 gives 33,024)."""
 
     SVM_MAX_DIM = 8192
 
@@ -90,16 +92,20 @@ class TrajectoryClassifier(object):
         self.pca = self.gmm = self.coef = self.intercept = self.classes = None
         self.power = 0.0
 
-    def fit(self, descs_per_video, labels, n_components=64, n_gmm=256, power=0.0, **gmm_kw):
+    def fit(self, descs_per_video, labels, n_components=64, n_gmm=256, power=0.0, svm="primal", **gmm_kw):
         """PCA to ``n_components`` (Sheet02.py:40), ``gmm_fit`` with ``n_gmm`` components (Sheet02.py:41) and ``gmm_kw``,
-        Fisher vectors with ``power``, ``fusion.linear_svm_fit``.  -> self."""
+        Fisher vectors with ``power``, then the linear SVM: ``svm="primal"`` is ``fusion.linear_svm_fit`` (at most 8192
+        columns), ``svm="dual"`` is ``ksvm.kernel_svm_fit`` on ``ksvm.linear_gram`` of the Fisher vectors (2 .. 16384 videos,
+        any length), collapsed to the same ``coef`` and ``intercept``.  -> self."""
         who = "TrajectoryClassifier.fit"
+        if svm not in ("primal", "dual"):
+            raise ValueError("%s: svm must be 'primal' or 'dual', got %r" % (who, svm))
         videos, segments = _features.check_videos(descs_per_video, who)
         if len(labels) != len(videos):
             raise ValueError("%s: %d videos but %d labels" % (who, len(videos), len(labels)))
         if isinstance(n_gmm, bool) or not isinstance(n_gmm, (int, np.integer)) or n_gmm < 1:
             raise ValueError("%s: n_gmm must be an integer >= 1, got %r" % (who, n_gmm))
-        if isinstance(n_components, (int, np.integer)) and n_gmm * (1 + 2 * n_components) > self.SVM_MAX_DIM:
+        if svm == "primal" and isinstance(n_components, (int, np.integer)) and n_gmm * (1 + 2 * n_components) > self.SVM_MAX_DIM:
             raise ValueError("%s: the Fisher vector's length n_gmm (1 + 2 n_components) = %d exceeds the %d columns linear_svm_fit takes"
                              % (who, n_gmm * (1 + 2 * n_components), self.SVM_MAX_DIM))
         self.pca = fisher.pca_fit(videos, n_components)
@@ -107,7 +113,11 @@ class TrajectoryClassifier(object):
         self.gmm = fisher.gmm_fit(reduced, n_gmm, **gmm_kw)
         self.power = float(power)
         fv = fisher.fisher_vectors(reduced, segments, self.gmm, self.power)
-        self.coef, self.intercept, self.classes = fusion.linear_svm_fit(fv, labels)
+        if svm == "primal":
+            self.coef, self.intercept, self.classes = fusion.linear_svm_fit(fv, labels)
+        else:
+            dual_coef, self.intercept, self.classes = ksvm.kernel_svm_fit(ksvm.linear_gram(fv), labels)
+            self.coef = (dual_coef @ fv.to(torch.float64)).cpu().numpy()
         return self
 
     def encode(self, descs_per_video):
